@@ -12,10 +12,16 @@ ibh_weighted_apply_many_device (ONE launch serves up to 32 independent 64-field 
 figure of the same run).  Every step still reads its own 39 MB of X from HBM and writes its own
 Y; the CSR is counted ONCE per launch in the roofline bytes.
 
-Statistics: after W warm-up steps the K-step timed region (barrier + synchronize on both sides, max
-over ranks) is repeated --repeats R (default 21) times; `value` / `ms_per_step` are the MEDIAN region,
-`roofline.kernel_us` the median over all R x launches kernel durations (HIP events attached to each
-SpMM dispatch), with min / max beside them.
+Statistics: after W warm-up steps exactly K (--steps) steps are timed, as up to --repeats R (default 21)
+consecutive regions of whole launches, each at least MIN_REGION_LAUNCHES launches long -- so fewer than
+2 x MIN_REGION_LAUNCHES launches are ONE region, a single sample (barrier + synchronize on both sides of a
+region, max over ranks); `value` / `ms_per_step` come from the MEDIAN
+region's time per step, `roofline.kernel_us` from the median over all launches' kernel durations (HIP
+events attached to each SpMM dispatch), with min / max beside them.
+
+--dump-outputs DIR: right after the timed steps, the result of the last timed step -- the [fields, nrow]
+float64 array the caller of the apply receives (rank 0: the gathered one) -- is written as DIR/y.npy;
+beyond DUMP_MAX_BYTES a fixed, seeded sample of its rows.  The inputs depend on the arguments only.
 
 N GPUs: `python bench.py --gpus N` starts its own `python -m torch.distributed.run` (one rank per GPU)
 as a child process when it was not launched by one; two modes:
@@ -45,6 +51,10 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0       # MI355X HBM3E spec peak (MI355X_MICROARCH.md); ~6300 GB/s is the measured copy rate
+# a timed region spans at least this many launches, so that the synchronisation around it stays small beside it
+MIN_REGION_LAUNCHES = 64
+DUMP_MAX_BYTES = 60 << 20   # what --dump-outputs writes at most (below 64 MB with the .npy header)
+DUMP_SEED = 20240501
 
 
 def spmm_bytes(nnz, nrow, ncol, nf):
@@ -60,9 +70,10 @@ def asm_bytes(nX, nI, nnz, nrow, ncol):
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=1920)
+    # default: 21 regions of MIN_REGION_LAUNCHES launches of 32 steps (about the 40 320 steps the 21 x 1920 repetitions timed before)
+    ap.add_argument("--steps", type=int, default=21 * 64 * 32, help="timed steps, in total")
     ap.add_argument("--warmup", type=int, default=160)
-    ap.add_argument("--repeats", type=int, default=21, help="repetitions of the K-step timed region (median reported)")
+    ap.add_argument("--repeats", type=int, default=21, help="the timed steps run as up to this many timed regions (median reported)")
     ap.add_argument("--config", default="g5", help="synthetic grid config (icebin_amd/synthetic.py)")
     ap.add_argument("--matrix", default="AvI")
     ap.add_argument("--fields", type=int, default=64, help="fields per GPU (weak scaling)")
@@ -76,7 +87,37 @@ def parse_args(argv=None):
     ap.add_argument("--tune", action="append", default=[], metavar="KEY=INT", help="ibh_set_tuning override (experiments)")
     ap.add_argument("--no-kernel-events", action="store_true", help="do not attach HIP events to the SpMM dispatches (plain launches: what a rocprofv3 kernel trace of a product call sees; roofline figures then come from the region events)")
     ap.add_argument("--dry-run", action="store_true", help="rehearse launcher + rendezvous + sharding + gather check on CPU (gloo, scipy apply); NOT a measurement")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the result of the last timed step as DIR/y.npy (float64)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+def region_sizes(steps, repeats, depth):
+    """Steps per timed region, `steps` in all: up to `repeats` regions of whole launches of `depth` steps, each at least
+    MIN_REGION_LAUNCHES launches long; the steps of a partial launch go to the last region."""
+    full = steps // depth
+    n = max(1, min(repeats, full // MIN_REGION_LAUNCHES))
+    sizes = [(full // n + (1 if j < full % n else 0)) * depth for j in range(n)]
+    sizes[-1] += steps - full * depth
+    return sizes
+
+
+def dump_outputs(out_dir, y):
+    """y: the [fields, rows] result of the last timed step (a torch tensor) -> out_dir/y.npy in float64.  Beyond
+    DUMP_MAX_BYTES whole rows are sampled: the same sorted rows for the same shape on every run.  Returns what was written."""
+    import torch
+    nf, nrow = y.shape
+    keep = max(1, min(nrow, DUMP_MAX_BYTES // (8 * max(nf, 1))))
+    info = {"file": "y.npy", "shape": [nf, nrow], "rows": "all"}
+    if keep < nrow:
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(nrow, keep, replace=False))
+        y = y.index_select(1, torch.from_numpy(rows).to(y.device))
+        info["rows"] = "%d of %d: np.sort(np.random.default_rng(%d).choice(%d, %d, replace=False))" % (keep, nrow, DUMP_SEED, nrow, keep)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "y.npy"), np.ascontiguousarray(y.detach().cpu().numpy(), dtype=np.float64))
+    return info
 
 
 def free_port():
@@ -307,6 +348,8 @@ def main():
             L.ibh_event_destroy(a); L.ibh_event_destroy(b)
         return out
 
+    last_gathered = [None]          # (group, slot) of the last gathered apply: where its result is read
+
     def run(launches, gather=True, kev=None):
         """kev: one (start, stop) HIP event pair per launch, attached to the SpMM kernel's own dispatch
         (ibh_set_launch_events): the kernel's duration without submission gaps."""
@@ -317,11 +360,12 @@ def main():
                 L.ibh_set_launch_events(pair[0], pair[1])
             if use_dist and gather:       # field-sharded SpMM + grouped all-gather, icebin_amd/distributed.py
                 if m <= sharded.G:
-                    sharded.apply_many_ptr(xs, ncol)
+                    g_, s_ = sharded.apply_many_ptr(xs, ncol)
                     sharded.flush()           # one all-gather per launch (a short last launch too)
+                    last_gathered[0] = (g_, s_ + m - 1)
                 else:
                     for xptr in xs:
-                        sharded.apply_ptr(xptr, ncol)
+                        last_gathered[0] = sharded.apply_ptr(xptr, ncol)
                 continue
             if m == 1:
                 rc = fn(W._h, xa[0], nf, ncol, ya[0], ldy, nan, 0, cs)
@@ -355,27 +399,36 @@ def main():
         return dt, e0.elapsed_time(e1)
 
     R = max(1, args.repeats)
-    warm_plan, timed_plan = plan(0, args.warmup), plan(args.warmup, args.steps)
+    warm_plan, region_plans, i0 = plan(0, args.warmup), [], args.warmup
+    for n in region_sizes(args.steps, R, depth):         # the K timed steps, numbered on from the warm-up's
+        region_plans.append((n, plan(i0, n)))
+        i0 += n
+    timed_plan = [launch for _, p in region_plans for launch in p]
     nlaunch = len(timed_plan)
     B = spmm_bytes(nnz, nrow, ncol, nf)
     csr_bytes = 12 * nnz + 4 * (nrow + 1)
     single_call_launches = (not use_dist or all(m <= gsteps for (m, _, _, _) in timed_plan)) and not args.no_kernel_events
-    regions = []            # (wall s, region events ms, [kernel ms per launch]) per repetition
+    regions = []            # (wall s, region events ms, [kernel ms per launch], steps) per timed region
     spmm_only = None
     extras = {}
+    dumped = None
     with torch.cuda.stream(compute):
         run(warm_plan)
         sync_all()
         if use_dist:        # the same K steps without the collectives (diagnostic; not the reported value)
-            so = []
-            for _ in range(min(R, 5)):
-                dt_s, _ = timed(timed_plan, gather=False)
-                so.append(dt_s / max(args.steps, 1) * 1e3)
-            spmm_only = median(so)
-        for rep in range(R):
-            kev = new_pairs(timed_plan) if single_call_launches else None
-            dt, region_ms = timed(timed_plan, True, kev)
-            regions.append((dt, region_ms, read_pairs(kev) if kev else []))
+            spmm_only = median([timed(p, gather=False)[0] / n * 1e3 for n, p in region_plans])
+        for n, p in region_plans:
+            kev = new_pairs(p) if single_call_launches else None
+            dt, region_ms = timed(p, True, kev)
+            regions.append((dt, region_ms, read_pairs(kev) if kev else [], n))
+        if args.dump_outputs and rank == 0:      # before anything else is computed into the same buffers
+            if use_dist:
+                y_last = sharded.result(*last_gathered[0])
+            else:
+                m, _, _, ya = timed_plan[-1]
+                y_last = {y.data_ptr(): y for y in Y}[ya[m - 1]][:, :nrow]
+            dumped = dump_outputs(args.dump_outputs, y_last)
+            del y_last
         if not args.no_extras and not use_dist and args.steps > 0:
             # one apply() per launch -- the reference's own call shape (merge_topo.cpp:65, icebin22m.cpp:153)
             p1 = plan(0, min(args.steps, 16), depth_=1)
@@ -444,14 +497,16 @@ def main():
 
     result = None
     if rank == 0:
-        walls = [r[0] for r in regions]
-        dt = median(walls)
-        region_ms = median([r[1] for r in regions])
-        # per-launch kernel durations of all repetitions; full-size launches carry the roofline figure
+        step_ms = [r[0] / r[3] * 1e3 for r in regions]            # wall time per step of each timed region
+        regions_said = ("%d timed regions" % len(regions) if len(regions) > 1 else
+                        "ONE timed region (a single sample: min = median = max, no spread)")
+        ms_step = median(step_ms)
+        region_us_per_step = median([r[1] * 1e3 / r[3] for r in regions])
+        # per-launch kernel durations of all regions; full-size launches carry the roofline figure
         per = timed_plan[0][0] if timed_plan else 0
-        all_ms = [ms for r in regions for ms in r[2]]
-        full_ms = [ms for r in regions for ms, (m, _, _, _) in zip(r[2], timed_plan) if m == per]
-        per_apply_us = [ms * 1e3 / m for r in regions for ms, (m, _, _, _) in zip(r[2], timed_plan)]
+        launched_ms = [(ms, m) for r, (_, p) in zip(regions, region_plans) for ms, (m, _, _, _) in zip(r[2], p)]
+        full_ms = [ms for ms, m in launched_ms if m == per]
+        per_apply_us = [ms * 1e3 / m for ms, m in launched_ms]
         have_k = len(full_ms) > 0
         B_launch = per * (B - csr_bytes) + csr_bytes              # CSR once per LAUNCH
         if have_k:
@@ -459,10 +514,9 @@ def main():
             kernel_us = launch_us / per
             achieved = B_launch / (launch_us * 1e-6) / 1e9
         else:                                                     # no kernel-attached events (sharded per-apply path): region events
-            launch_us = region_ms * 1e3 / max(nlaunch, 1)
-            kernel_us = region_ms * 1e3 / max(args.steps, 1)
-            achieved = (args.steps * (B - csr_bytes) + nlaunch * csr_bytes) / (region_ms * 1e-3) / 1e9
-        cells = n_in_cells * nf_total * args.steps
+            launch_us = median([r[1] * 1e3 / len(p) for r, (_, p) in zip(regions, region_plans)])
+            kernel_us = region_us_per_step
+            achieved = (args.steps * (B - csr_bytes) + nlaunch * csr_bytes) / (sum(r[1] for r in regions) * 1e-3) / 1e9
         par = "1 GPU"
         if use_dist:
             par = ("field-shard x%d (%s: %d fields/rank) + all-gather every %d steps" %
@@ -472,11 +526,11 @@ def main():
                 "launched": W.last_launch(),
                 "kernel_us": kernel_us, "algorithmic_bytes": B,
                 "launches": nlaunch, "steps_per_launch": per, "launch_us": launch_us,
-                "statistic": "median over %d launches (%d repetitions of the timed region x %d launches)" % (len(full_ms), R, nlaunch) if have_k
-                             else "median over %d repetitions of the timed region" % R,
-                "repeats": R,
+                "statistic": "median over %d launches (%d launches in %s)" % (len(full_ms), nlaunch, regions_said) if have_k
+                             else "median over %s" % regions_said,
+                "repeats": len(regions),
                 "timing": "HIP events attached to each SpMM dispatch of the timed regions (kernel start -> end)" if have_k else "HIP events around the timed region on the launch stream",
-                "region_us_per_step": region_ms * 1e3 / max(args.steps, 1),
+                "region_us_per_step": region_us_per_step,
                 "algorithmic_bytes_per_launch": B_launch,
                 "traffic_source": "profiles/*_pmc_traffic.json: separate rocprofv3 --pmc passes of this command, per launch; not measured in this run; null when that profile was taken on another kernel instantiation than `launched`"}
         if have_k:
@@ -503,11 +557,11 @@ def main():
                                   "what": "the headline launch shape (%d applies per launch) over 1 (Infinity-Cache-resident) / 7 / 14 / 28 rotating field batches" % depth}
         result = {
             "metric": "regridded cells/sec (%s, %s, %d fields%s)" % (args.matrix, args.config, nf_total if strong else nf, "" if strong else "/GPU"),
-            "value": cells / dt, "unit": "cells/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "strong" if strong else "weak",
+            "value": n_in_cells * nf_total / (ms_step * 1e-3), "unit": "cells/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": ms_step, "higher_is_better": True, "scaling": "strong" if strong else "weak",
             "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "repeats": {"R": R, "statistic": "median", "ms_per_step_min": min(walls) / args.steps * 1e3,
-                        "ms_per_step_max": max(walls) / args.steps * 1e3, "ms_per_step_first": walls[0] / args.steps * 1e3},
+            "repeats": {"R": len(regions), "statistic": "median over %s" % regions_said, "steps_per_region": [r[3] for r in regions],
+                        "ms_per_step_min": min(step_ms), "ms_per_step_max": max(step_ms), "ms_per_step_first": step_ms[0]},
             "config": {"workload": "searise 5 km Greenland -> ModelE 2x2.5 %s, %d fields" % (args.matrix, nf)
                        if args.config == "g5" else "%s %s %d fields" % (args.config, args.matrix, nf),
                        "nI": grids["nI"], "nX": int(len(grids["ex_area"])), "unmasked_cells": n_unmasked,
@@ -525,7 +579,7 @@ def main():
             result["assembly"]["sharded"] = asm_sharded
         if use_dist:
             result["spmm_only_ms"] = spmm_only
-            result["spmm_plus_gather_ms"] = dt / args.steps * 1e3
+            result["spmm_plus_gather_ms"] = ms_step
             result["gather_bytes_per_rank_per_step"] = 8 * nf * ((nrow + 63) // 64 * 64)
             result["gather_via"] = sharded_via
             if sharded_fallback:
@@ -543,6 +597,8 @@ def main():
         else:
             y = torch.stack(Y[:min(2 * depth, args.steps, 4)])[:, :, :nrow].cpu().numpy() if args.steps > 0 else None
         result["finite_output"] = bool(y is not None and np.isfinite(y).all())
+        if dumped is not None:
+            result["dump_outputs"] = dumped
         print(json.dumps(result), flush=True)
     failed = bool(gather_check is not None and not gather_check["pass"])
     if use_dist:
@@ -591,30 +647,39 @@ def dry_run(args):
     sh = FieldShardedApply(Mat(), nf_total, None, ops=HostOps(), steps_per_gather=depth, local_apply=local_apply,
                            local_apply_many=None, nrow=nrow, ncol=ncol)
     x = torch.from_numpy(fields_of(rank))
+
+    def steps(i0, n):               # step i applies its own fields, x + 1e-3 * i (the real run rotates batches too)
+        last = None
+        for i in range(i0, i0 + n):
+            last = sh.apply(x + 1e-3 * i)
+        sh.flush(); sh.wait()
+        dist.barrier()
+        return last
+    steps(0, args.warmup)
     t0 = time.perf_counter()
-    last = None
-    for i in range(args.warmup + args.steps):
-        last = sh.apply(x)
-    sh.flush(); sh.wait()
-    dist.barrier()
+    last = steps(args.warmup, args.steps)
     dt = time.perf_counter() - t0
-    # the cross-rank check of the real run: every rank recomputes its own and its right neighbour's shard
+    # the cross-rank check of the real run: every rank recomputes its own and its right neighbour's shard of the last step
+    i_last = args.warmup + args.steps - 1
     g_, slot_ = last
     res = sh.result(g_, slot_).numpy()
     ok = True
     for r in sorted({rank, (rank + 1) % world}):
         r0, r1 = field_shard(nf_total, world, r)
-        ok = ok and np.array_equal(res[r0:r1], (M @ fields_of(r).T).T)
+        ok = ok and np.array_equal(res[r0:r1], (M @ (fields_of(r) + 1e-3 * i_last).T).T)
     t = torch.tensor([1 if ok else 0], dtype=torch.int32)
     dist.all_reduce(t, op=dist.ReduceOp.MIN)
     seen = [None] * world
     dist.all_gather_object(seen, {"rank": rank, "device": None, "host": socket.gethostname()})
     if rank == 0:
-        print(json.dumps({"metric": "DRY RUN of bench.py's N>1 path on CPU (gloo, scipy apply) -- not a measurement", "dry_run": True,
-                          "value": None, "unit": "cells/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-                          "ms_per_step": dt / max(args.steps + args.warmup, 1) * 1e3, "scaling": "strong" if strong else "weak",
-                          "fields_per_rank": nf, "fields_total": nf_total,
-                          "gather_check": {"pass": bool(t.item() == 1), "ranks": world}, "ranks_seen": seen}), flush=True)
+        out = {"metric": "DRY RUN of bench.py's N>1 path on CPU (gloo, scipy apply) -- not a measurement", "dry_run": True,
+               "value": None, "unit": "cells/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+               "ms_per_step": dt / args.steps * 1e3, "scaling": "strong" if strong else "weak",
+               "fields_per_rank": nf, "fields_total": nf_total,
+               "gather_check": {"pass": bool(t.item() == 1), "ranks": world}, "ranks_seen": seen}
+        if args.dump_outputs:
+            out["dump_outputs"] = dump_outputs(args.dump_outputs, sh.result(g_, slot_))
+        print(json.dumps(out), flush=True)
     dist.barrier()
     dist.destroy_process_group()
     return 0 if t.item() == 1 else 3

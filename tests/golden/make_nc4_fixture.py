@@ -1,8 +1,7 @@
 """Writes tests/golden/nc4_example1.json: what icebin_amd.hdf5 reads out of the reference's own NetCDF-4 example files
-(/root/reference/examples/example1/*.nc -- ModelE diagnostics on the 2 x 2.5 degree grid with 40 elevation classes, the
-inputs of examples/example1/runme.py).  Runs only where /root/reference exists (the build container); the files themselves
-are not copied -- the fixture holds dimensions, variables, shapes, attributes and a SHA-256 / min / max / float64 sum per
-variable, so the test can tell a reader regression from a changed file.
+(examples/example1/*.nc, stored beside this script -- ModelE diagnostics on the 2 x 2.5 degree grid with 40 elevation
+classes, the inputs of examples/example1/runme.py).  The fixture holds dimensions, variables, shapes, attributes and a
+SHA-256 / min / max / float64 sum per variable, so the test can tell a reader regression from a changed file.
 
 usage: python tests/golden/make_nc4_fixture.py
 """
@@ -18,7 +17,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
 from icebin_amd import hdf5  # noqa: E402
 
-SRC = "/root/reference/examples/example1"
+SRC = HERE
 
 
 def describe(path):

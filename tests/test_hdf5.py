@@ -3,7 +3,7 @@
 No HDF5 / NetCDF library exists in the image, so the reader is pinned by
   * the published known answers of its checksum (Bob Jenkins' lookup3 self-test values) -- every version-2 metadata
     block of a file read is verified with it, which is independent evidence that blocks are parsed where the writer put them;
-  * the reference's own NetCDF-4 example files (examples/example1/*.nc, present in the build container only) against the
+  * the reference's own NetCDF-4 example files (examples/example1/*.nc, stored under tests/golden/) against the
     committed fixture tests/golden/nc4_example1.json, plus physical sanity of what comes out (the grid-cell areas of the
     2 x 2.5 degree grid add up to the area of the Earth);
   * an HDF5 file of a different vintage that ships with scipy (MATLAB 7.3: superblock 0 behind a 512-byte user block,
@@ -19,8 +19,7 @@ import pytest
 from icebin_amd import hdf5, ncio
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-REF = "/root/reference/examples/example1"
-needs_reference = pytest.mark.skipif(not os.path.isdir(REF), reason="the reference's example files exist in the build container only")
+REF = os.path.join(HERE, "golden")        # the reference's examples/example1/*.nc
 
 
 def test_lookup3_known_answers():
@@ -67,7 +66,6 @@ def test_fletcher32_is_the_librarys_loop():
         assert hdf5.fletcher32(b) == _fletcher32_loop(b)
 
 
-@needs_reference
 def test_reference_example_files_against_the_committed_fixture():
     golden = json.load(open(os.path.join(HERE, "golden", "nc4_example1.json")))
     assert len(golden) == 2
@@ -90,7 +88,6 @@ def test_reference_example_files_against_the_committed_fixture():
             assert (got if isinstance(got, (str, list)) else np.asarray(got).tolist()) == x
 
 
-@needs_reference
 def test_reference_example_files_make_physical_sense():
     # what no parser bug would produce by accident: the ModelE 2 x 2.5 degree grid, whose cell areas add up to the sphere
     ds = ncio.Dataset.read(os.path.join(REF, "130516-Regrid_examples_e4f40-hc40-g5_JUL1956.ijhce4f40-hc40.nc"))     # (dispatch on the signature)
@@ -108,7 +105,6 @@ def test_reference_example_files_make_physical_sense():
     assert not {"CLASS", "NAME", "DIMENSION_LIST", "REFERENCE_LIST", "_Netcdf4Dimid"} & set(ds.variables["lon"].attrs)
 
 
-@needs_reference
 def test_a_flipped_metadata_byte_is_caught_by_the_checksum():
     path = os.path.join(REF, "130516-Regrid_examples_e4f40-hc40-g5_JUL1956.aije4f40-hc40-prec.nc")
     raw = bytearray(open(path, "rb").read())
@@ -134,7 +130,6 @@ def test_matlab73_file_of_scipy_old_style_structures():
     assert bytes(np.asarray(o.attrs["MATLAB_class"]).reshape(-1)[0]) == b"double"
 
 
-@needs_reference
 def test_truncated_and_damaged_files_raise_h5error():
     path = os.path.join(REF, "130516-Regrid_examples_e4f40-hc40-g5_JUL1956.aije4f40-hc40-prec.nc")
     raw = open(path, "rb").read()

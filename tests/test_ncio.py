@@ -195,24 +195,23 @@ def test_cpp_hdf5_reader_agrees_with_the_python_reader(tmp_path):
         assert r.returncode == 0 and r.stdout == _dump_dataset(hdf5.read_netcdf4(p2)[0])
         assert "var testdouble (phony_dim_0_9,phony_dim_1_1) type6[9]" in r.stdout
     # (3) the reference's own NetCDF-4 files: superblock 2, version-2 headers, chunked + deflate + shuffle, dimension scales
-    ref = "/root/reference/examples/example1"
-    if os.path.isdir(ref):
-        for fn in sorted(os.listdir(ref)):
-            if not fn.endswith(".nc"):
-                continue
-            path = os.path.join(ref, fn)
-            r = _cpp_dump(path)
-            assert r.returncode == 0, r.stdout
-            assert r.stdout == _dump_dataset(hdf5.read_netcdf4(path)[0]), fn
-            raw = open(path, "rb").read()
-            # damage: a flipped metadata byte is caught by the checksum; truncation and a broken deflate stream fail loudly
-            bad = bytearray(raw)
-            bad[raw.index(b"OHDR") + 9] ^= 0x40
-            cases = {"flip": bytes(bad), "half": raw[:len(raw) // 2], "tail": raw[:len(raw) - 1000], "head": raw[:200]}
-            for key, img in cases.items():
-                q = tmp_path / (key + ".nc")
-                q.write_bytes(img)
-                r = _cpp_dump(q)
-                assert r.returncode == 1 and r.stdout.startswith("ERROR ncio:") and "hdf5:" in r.stdout, (fn, key, r.stdout)
-                if key == "flip":
-                    assert "checksum" in r.stdout
+    ref = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")       # examples/example1/*.nc
+    ncs = sorted(fn for fn in os.listdir(ref) if fn.endswith(".nc"))
+    assert len(ncs) == 2, ncs
+    for fn in ncs:
+        path = os.path.join(ref, fn)
+        r = _cpp_dump(path)
+        assert r.returncode == 0, r.stdout
+        assert r.stdout == _dump_dataset(hdf5.read_netcdf4(path)[0]), fn
+        raw = open(path, "rb").read()
+        # damage: a flipped metadata byte is caught by the checksum; truncation and a broken deflate stream fail loudly
+        bad = bytearray(raw)
+        bad[raw.index(b"OHDR") + 9] ^= 0x40
+        cases = {"flip": bytes(bad), "half": raw[:len(raw) // 2], "tail": raw[:len(raw) - 1000], "head": raw[:200]}
+        for key, img in cases.items():
+            q = tmp_path / (key + ".nc")
+            q.write_bytes(img)
+            r = _cpp_dump(q)
+            assert r.returncode == 1 and r.stdout.startswith("ERROR ncio:") and "hdf5:" in r.stdout, (fn, key, r.stdout)
+            if key == "flip":
+                assert "checksum" in r.stdout
