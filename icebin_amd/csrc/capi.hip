@@ -656,22 +656,22 @@ int ibh_weighted_device_view_get(const ibh_weighted *w, ibh_weighted_device_view
     });
 }
 
+// ApplyKernel -> name.  rowdual, colsweep and rowgroup fall back to rowblock when the matrix has no bands / column-sweep
+// structure / row groups.
+static const char *const kernel_names[] = {"auto", "rowblock", "shortrow", "rowdual", "colsweep", "rowgroup"};
+static_assert(sizeof(kernel_names) / sizeof(kernel_names[0]) == KERNEL_ROWGROUP + 1, "one name per ApplyKernel");
 int ibh_weighted_set_kernel(ibh_weighted *w, const char *name) {
     return guarded([&] {
         IBH_CHECK(w && name, "null argument");
-        if (!strcmp(name, "auto")) w->kernel_override = 0;
-        else if (!strcmp(name, "rowblock")) w->kernel_override = 1;
-        else if (!strcmp(name, "shortrow")) w->kernel_override = 2;
-        else if (!strcmp(name, "colsweep")) w->kernel_override = 4;       // falls back to rowblock when the matrix has no column-sweep structure
-        else if (!strcmp(name, "rowdual")) w->kernel_override = 3;        // falls back to rowblock when the matrix has no bands
-        else if (!strcmp(name, "rowgroup")) w->kernel_override = 5;       // falls back to rowblock when the matrix has no row groups
-        else fail(IBH_EINVAL, "unknown kernel '%s'", name);
+        for (int k = KERNEL_AUTO; k <= KERNEL_ROWGROUP; ++k)
+            if (!strcmp(name, kernel_names[k])) { w->kernel_override = static_cast<ApplyKernel>(k); return; }
+        fail(IBH_EINVAL, "unknown kernel '%s'", name);
     });
 }
 int ibh_weighted_last_kernel(const ibh_weighted *w, char *buf, int buflen) {
     return guarded([&] {
         IBH_CHECK(w && buf && buflen > 0, "bad argument");
-        snprintf(buf, (size_t)buflen, "%s", w->last_kernel == 1 ? "rowblock" : w->last_kernel == 2 ? "shortrow" : w->last_kernel == 3 ? "rowdual" : w->last_kernel == 4 ? "colsweep" : w->last_kernel == 5 ? "rowgroup" : "none");
+        snprintf(buf, (size_t)buflen, "%s", w->last_kernel == KERNEL_AUTO ? "none" : kernel_names[w->last_kernel]);
     });
 }
 int ibh_weighted_last_launch(const ibh_weighted *w, char *buf, int buflen) {

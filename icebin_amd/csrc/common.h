@@ -230,6 +230,8 @@ inline uint64_t next_weighted_uid() {
     static std::atomic<uint64_t> n{0};
     return ++n;
 }
+// the apply kernel families (spmm.hip), as ibh_weighted_set_kernel / ibh_weighted_last_kernel name them (capi.hip)
+enum ApplyKernel { KERNEL_AUTO = 0, KERNEL_ROWBLOCK = 1, KERNEL_SHORTROW, KERNEL_ROWDUAL, KERNEL_COLSWEEP, KERNEL_ROWGROUP };
 }  // namespace ibh
 struct ibh_weighted {
     const uint64_t uid = ibh::next_weighted_uid();     // never reused: a pairing names its second matrix by (address, uid)
@@ -243,12 +245,12 @@ struct ibh_weighted {
     int conservative = 1, scaled = 1;
     int built_fast = 0;                 // assembled by the plan-based fast path (fastasm.inl); introspection only
     // SpMM dispatch
-    int kernel_override = 0;            // 0 auto, 1 rowblock, 2 shortrow, 3 rowdual
+    ibh::ApplyKernel kernel_override = ibh::KERNEL_AUTO;
     mutable char last_sig[64] = {0};    // the kernel instantiation the last apply launched, as rocprofv3 names it (rowblock / rowone; else the kernel family)
     // per-handle launch options (ibh_weighted_set_option): looked up before the process-wide ibh_set_tuning map by every apply of
     // THIS matrix, so two host threads tuning different handles do not interfere
     mutable std::unordered_map<std::string, int> opts;
-    mutable int last_kernel = 0;
+    mutable ibh::ApplyKernel last_kernel = ibh::KERNEL_AUTO;     // KERNEL_AUTO: no apply yet
     // apply_transformed: scratch fields + small transform, and M*1 (row sums) for the offset term
     mutable ibh::DevBuf<double> scratch, tbuf, rowsum1;
     mutable ibh::DevBuf<double> consv;  // force_conservation: the two dot products per variable [2*nvar] + chunk sums
@@ -289,7 +291,6 @@ struct ibh_weighted {
     mutable ibh::DevBuf<double> pair_w;
     mutable ibh::DevBuf<uint32_t> pair_mask;
     mutable ibh::DevBuf<int32_t> pair_row;
-    mutable ibh::DevBuf<uint32_t> chain_cnt;             // chain (ibh_weighted_apply_chain_device): {workgroups of the pair kernel done, of the last kernel through}
     mutable int32_t grp_n = 0, grp_nslot = 0, grp_nitems = 0;          // groups (0: not built), most rows in a group, items
     mutable ibh::DevBuf<int32_t> grp_ptr, grp_ns, grp_slotrow, grp_col; // [grp_n+1] items of a group; [grp_n] rows of a group; [grp_n*IBH_GSLOTS]; [nitems]
     mutable ibh::DevBuf<uint32_t> grp_meta;
@@ -331,7 +332,7 @@ void weighted_reserve(const ibh_weighted *w, int nvar);
 void weighted_prepare(const ibh_weighted *w, int nvar, int nbatch);
 void weighted_pair_prepare(const ibh_weighted *first, const ibh_weighted *second, int nvar);
 void spmm_launch_pair(const ibh_weighted *first, const ibh_weighted *second, const double *dA, int nvar, int64_t lda, double *dB1,
-                      int64_t ldb1, double *dB2, int64_t ldb2, double fill, hipStream_t stream, unsigned *done = nullptr);
+                      int64_t ldb1, double *dB2, int64_t ldb2, double fill, hipStream_t stream);
 void spmm_launch_chain(const ibh_weighted *first, const ibh_weighted *second, const ibh_weighted *third, const double *dA, int nvar, int64_t lda,
                        double *dB1, int64_t ldb1, double *dB2, int64_t ldb2, double *dB3, int64_t ldb3, double fill, hipStream_t stream);
 // assemble.hip: the band structure of an E-row matrix from its CSR (same result as building it with the matrix)

@@ -72,9 +72,6 @@ void set_tuning(const char *key, int value) {
 // next rowblock launch of this thread attaches them to its own dispatch (hipExtLaunchKernel: start =
 // kernel begins, stop = kernel ends -- the interval rocprofv3's kernel trace reports).  One-shot.
 static thread_local hipEvent_t g_ev_start = nullptr, g_ev_stop = nullptr;
-// chain (ibh_weighted_apply_chain_device): the next I-row launch of this thread waits on a device counter instead of the queue
-static thread_local unsigned *g_chain_cnt = nullptr;
-static thread_local unsigned g_chain_n = 0;
 void set_launch_events(hipEvent_t start, hipEvent_t stop) { g_ev_start = start; g_ev_stop = stop; }
 
 // ---- helpers -------------------------------------------------------------------------------
@@ -148,10 +145,7 @@ typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 // buffer_load + one FMA instead of a 64-bit address computation per load; at the 40 MB headline
 // size the kernel is as much instruction-issue- as bandwidth-limited.
 __device__ __forceinline__ double xload(__amdgpu_buffer_rsrc_t rs, int byte_off) {
-#ifndef IBH_X_AUX
-#define IBH_X_AUX 0
-#endif
-    return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rs, byte_off, 0, IBH_X_AUX));
+    return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rs, byte_off, 0, 0));
 }
 
 // Field batches of one launch (ibh_weighted_apply_many_device): batch q reads x[q] and writes y[q],
@@ -496,48 +490,7 @@ struct PairView {
     const double *wM2;
     double *Y2;
     long ldy2;
-    unsigned *done;     // chain (ibh_weighted_apply_chain_device): every workgroup counts itself here when its results are visible
 };
-// a workgroup of the first kernel of a chain is finished: its stores are released to the device, then it counts itself
-// Chain counters {c, flag}: every workgroup of the first kernel clears `flag` when it starts (the kernel before it in the queue --
-// the previous chain's last kernel -- has completed: a barrier packet) and counts itself at `c` when its results are out; the
-// one that counts last re-arms c and raises the flag.  The last kernel's workgroups only READ the flag: same-address
-// read-modify-writes go through one L2 channel one after the other (1 200 waiting workgroups counting themselves cost 20 us).
-// (the results the next kernel reads were stored with chain_store -- written through to the device-coherent level -- so no
-// release fence is needed, which at agent scope writes back the whole L2 of the XCD: every wave waits for its own stores, the
-// barrier collects the waves)
-__device__ __forceinline__ void chain_begin(unsigned *cnt) {
-    if (threadIdx.x == 0) __hip_atomic_store(cnt + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void chain_signal(unsigned *cnt) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const unsigned total = gridDim.x * gridDim.y * gridDim.z;
-        if (__hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == total - 1) {
-            __hip_atomic_store(cnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(cnt + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
-}
-__device__ __forceinline__ void chain_store(double *p, double v) {
-    __hip_atomic_store(reinterpret_cast<unsigned long long *>(p), __builtin_bit_cast(unsigned long long, v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// a value the kernel before this one wrote (and released at agent scope): a load that is coherent across the XCDs' L2s
-__device__ __forceinline__ double chain_load(const double *p) {
-    return __builtin_bit_cast(double, __hip_atomic_load(reinterpret_cast<const unsigned long long *>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-}
-#ifndef CHAIN_SLEEP
-#define CHAIN_SLEEP 32
-#endif
-// the first thing a workgroup of the chain's last kernel does: wait until the kernel before it has raised the flag (that kernel
-// was dispatched first, so its workgroups are placed first and always finish)
-__device__ __forceinline__ void chain_wait(unsigned *cnt, unsigned) {
-    if (threadIdx.x == 0) {
-        while (__hip_atomic_load(cnt + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u) __builtin_amdgcn_s_sleep(CHAIN_SLEEP);
-    }
-    __syncthreads();
-}
 template <int NW, int U, int TW, bool PAIR = false>
 __global__ __launch_bounds__(NW * 64) void spmm_rowgroup_kernel(const GroupView gv, const BatchPtrs bp, long ldx, int ncol, long ldy, int nf,
                                                                int nfc, int xcd_mode, const double *__restrict__ wM, double fill,
@@ -551,11 +504,7 @@ __global__ __launch_bounds__(NW * 64) void spmm_rowgroup_kernel(const GroupView 
     unsigned *s_meta = reinterpret_cast<unsigned *>(s_col + SEG);
     double *s_tab = rg_lds + 3 * SEG;                       // [NW][nslot][64]
     int g, fc;
-    if (PAIR && pv.done) chain_begin(pv.done);
-    if (!block_to_task(blockIdx.x, gv.ngrp, nfc, xcd_mode, g, fc)) {
-        if (PAIR && pv.done) chain_signal(pv.done);
-        return;
-    }
+    if (!block_to_task(blockIdx.x, gv.ngrp, nfc, xcd_mode, g, fc)) return;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int fw = fc * NW + wave;
@@ -671,12 +620,8 @@ __global__ __launch_bounds__(NW * 64) void spmm_rowgroup_kernel(const GroupView 
             double v = 0.0;
             if (half == 0 && sl < ns && ((pv.mask[g] >> sl) & 1u)) v = pv.w[g * IBH_GSLOTS + sl] * y1;
             const double s2 = wave_sum(v);
-            if (lane == 0 && fw < nf) {
-                const double o2 = pv.wM2[a2] == 0.0 ? fill : s2;
-                if (pv.done) chain_store(&pv.Y2[(long)fw * pv.ldy2 + a2], o2); else pv.Y2[(long)fw * pv.ldy2 + a2] = o2;
-            }
+            if (lane == 0 && fw < nf) pv.Y2[(long)fw * pv.ldy2 + a2] = pv.wM2[a2] == 0.0 ? fill : s2;
         }
-        if (pv.done) chain_signal(pv.done);
     }
 }
 
@@ -705,7 +650,7 @@ __global__ __launch_bounds__(NW * 64) void spmm_rowgroup_kernel(const GroupView 
 //      conflict-free ds_read_b64) and does one FMA into a REGISTER: the slot of a quad is wave-uniform.  ~20 B through LDS per
 //      entry and field, no atomics, no read-modify-write, no predicate.
 // Which wave sums what is static, so the sums stay in registers across tiles: every slot's list of a tile is cut into SP parts
-// (SP = the largest power of two with SP * ns <= 32, by the group's number of rows ns -- a GCM cell of two classes keeps all
+// (SP = the largest power of two with SP * ns <= 16, by the group's number of rows ns -- a GCM cell of two classes keeps all
 // waves busy as one of sixteen does); the units u = s * SP + part, in this order, are dealt to the waves in contiguous, balanced
 // ranges -- consecutive units are consecutive quads of the tile's list, so a wave walks ONE run of quads per tile and only
 // switches its accumulator on the way.
@@ -727,15 +672,7 @@ struct TileView {
 #define GT_STAMP(i) do {} while (0)
 #define GT_STAMP_W(i) do {} while (0)
 #endif
-#ifndef GT_WPS
-#define GT_WPS 4
-#endif
-#ifndef GT_ULIMIT
-#define GT_ULIMIT 16
-#endif
-#ifndef GT_BATCH
-#define GT_BATCH 4
-#endif
+constexpr int GT_UNITS = 16;         // the SP bound above: a group's units (slot, part) number max(16, ns)
 constexpr int GT_TABP = 65;          // row stride of the epilogue's table of partial sums [unit][lane]
 template <int F, int SEG>
 constexpr size_t grouptile_lds() { return (size_t)F * (SEG + 2) * 8 + ibh_gt_ecap(SEG) * 10 + 256; }     // (+ slack: a batch reads a few steps past its run)
@@ -751,7 +688,7 @@ __device__ __forceinline__ void wave_half_sums(double v, double &lo, double &hi)
     hi = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), 63), __builtin_amdgcn_readlane(__double2loint(v), 63));
 }
 template <int F, int NS, int SEG, int NW, bool PAIR = false>
-__global__ __launch_bounds__(NW * 64, GT_WPS) void spmm_grouptile_kernel(const TileView tv, const BatchPtrs bp, long ldx, int ncol, long ldy, int nf,
+__global__ __launch_bounds__(NW * 64, 4) void spmm_grouptile_kernel(const TileView tv, const BatchPtrs bp, long ldx, int ncol, long ldy, int nf,
                                                                             int nfc, int xcd_mode, const double *__restrict__ wM, double fill,
                                                                             const PairView pv = PairView{})
 {
@@ -759,7 +696,7 @@ __global__ __launch_bounds__(NW * 64, GT_WPS) void spmm_grouptile_kernel(const T
     constexpr int FW = F / (NW / NB);                   // fields a wave gathers for its 64 items
     constexpr int EPT = (ECAP + T - 1) / T;      // entries staged per thread
     constexpr int J = 64 / F, R = 4 / J;                // sublanes; entries of a quad per sublane = partial sums per lane and unit
-    constexpr int OS = ((NS > GT_ULIMIT ? NS : GT_ULIMIT) + NW - 1) / NW;     // most units (slot, part) of a wave: groups of <= NS rows
+    constexpr int OS = ((NS > GT_UNITS ? NS : GT_UNITS) + NW - 1) / NW;     // most units (slot, part) of a wave: groups of <= NS rows
     static_assert(F == 16 || F == 32, "fields per workgroup");
     static_assert(NW % NB == 0 && F % (NW / NB) == 0, "shape");
     extern __shared__ double gt_lds[];
@@ -768,11 +705,7 @@ __global__ __launch_bounds__(NW * 64, GT_WPS) void spmm_grouptile_kernel(const T
     unsigned short *s_ek = reinterpret_cast<unsigned short *>(s_ev + ECAP);      // [ECAP]
     double *s_tab = gt_lds;                                              // epilogue: [R][32 units][GT_TABP], over s_x
     int g, fc;
-    if (PAIR && pv.done) chain_begin(pv.done);
-    if (!block_to_task(blockIdx.x, tv.ngrp, nfc, xcd_mode, g, fc)) {
-        if (PAIR && pv.done) chain_signal(pv.done);
-        return;
-    }
+    if (!block_to_task(blockIdx.x, tv.ngrp, nfc, xcd_mode, g, fc)) return;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     GT_STAMP(0);
@@ -783,9 +716,8 @@ __global__ __launch_bounds__(NW * 64, GT_WPS) void spmm_grouptile_kernel(const T
     GT_STAMP(1 + 0 * (t0 + t1 + ns + nitems));
     const int ib = wave % NB, fg = wave / NB;           // this wave gathers items [64 ib, 64 ib + 64) for fields [FW fg, FW fg + FW)
     const int j = lane / F, f = lane % F;
-    // parts per slot: the largest power of two with sp * ns <= 32; this wave's units [ub, ue)
-    constexpr int UL = GT_ULIMIT;                       // most units of a group
-    static_assert(UL == 32 || UL == 16, "units");
+    // parts per slot: the largest power of two with sp * ns <= GT_UNITS; this wave's units [ub, ue)
+    constexpr int UL = GT_UNITS;
     const int lsp = ns * 16 <= UL ? 4 : ns * 8 <= UL ? 3 : ns * 4 <= UL ? 2 : ns * 2 <= UL ? 1 : 0;
     const int nunit = ns << lsp;
     const int ub = (wave * nunit) / NW, ue = ((wave + 1) * nunit) / NW;
@@ -868,9 +800,9 @@ __global__ __launch_bounds__(NW * 64, GT_WPS) void spmm_grouptile_kernel(const T
         __builtin_amdgcn_sched_barrier(0);              // (the loads above fly while the tile is summed: nothing of them sinks below)
         if (t == t0) GT_STAMP(13);
         // Unit o of this wave = steps [B[o], B[o + 1]) of the tile's list (a step = J entries x F fields), walked in batches of
-        // 8 steps: lane 16 r + i fetches the item index 8 k of the entry that step i of the batch hands to sublane r / (F / 16) --
+        // 4 steps: lane 16 r + i fetches the item index 8 k of the entry that step i of the batch hands to sublane r / (F / 16) --
         // one LDS read per lane and batch; a DPP row broadcast folded into the address add then gives every step its X
-        // address, the weights come as broadcast reads at fixed offsets, and the 16 reads of a batch are in flight together.
+        // address, the weights come as broadcast reads at fixed offsets, and the 8 reads of a batch are in flight together.
         int B[OS + 1];
 #pragma unroll
         for (int o = 0; o <= OS; ++o) {
@@ -883,23 +815,17 @@ __global__ __launch_bounds__(NW * 64, GT_WPS) void spmm_grouptile_kernel(const T
         if (t == t0) { GT_STAMP(14); if (tv.dbg && threadIdx.x == 0 && blockIdx.y == 0) tv.dbg[(long)blockIdx.x * 16 + 15] = ((long long)(B[OS] - B[0]) << 32) | (unsigned)(B[1] - B[0]); }
 #pragma unroll
         for (int o = 0; o < OS; ++o) {
-            for (int p0 = B[o]; p0 < B[o + 1]; p0 += GT_BATCH) {
+            for (int p0 = B[o]; p0 < B[o + 1]; p0 += 4) {
                 const int nb = B[o + 1] - p0;
                 const int mk = *reinterpret_cast<const unsigned short *>(a_ek + p0 * J * 2);
                 const char *pv = a_ev + p0 * J * 8;
-                double xx[GT_BATCH], vv[GT_BATCH];
+                double xx[4], vv[4];
 #define GT_XR(S)                                                                                                                          \
                 xx[S] = *reinterpret_cast<const double *>(a_x + __builtin_amdgcn_update_dpp(0, mk, 0x150 + (S), 0xf, 0xf, false));        \
                 vv[S] = *reinterpret_cast<const double *>(pv + (S) * J * 8)
 #define GT_FM(S) if ((S) < nb) acc[o][(S) % R] = fma(vv[S], xx[S], acc[o][(S) % R])
                 GT_XR(0); GT_XR(1); GT_XR(2); GT_XR(3);
-#if GT_BATCH == 8
-                if (nb > 4) { GT_XR(4); GT_XR(5); GT_XR(6); GT_XR(7); }
-#endif
                 GT_FM(0); GT_FM(1); GT_FM(2); GT_FM(3);
-#if GT_BATCH == 8
-                if (nb > 4) { GT_FM(4); GT_FM(5); GT_FM(6); GT_FM(7); }
-#endif
 #undef GT_XR
 #undef GT_FM
             }
@@ -943,15 +869,11 @@ __global__ __launch_bounds__(NW * 64, GT_WPS) void spmm_grouptile_kernel(const T
                 double s_lo, s_hi;
                 wave_half_sums(v2, s_lo, s_hi);
                 const double s2 = half ? s_hi : s_lo;
-                if (sl == 0 && fw < nf) {
-                    const double o2 = pv.wM2[a2] == 0.0 ? fill : s2;
-                    if (pv.done) chain_store(&pv.Y2[(long)fw * pv.ldy2 + a2], o2); else pv.Y2[(long)fw * pv.ldy2 + a2] = o2;
-                }
+                if (sl == 0 && fw < nf) pv.Y2[(long)fw * pv.ldy2 + a2] = pv.wM2[a2] == 0.0 ? fill : s2;
             }
         }
     }
     GT_STAMP(12);
-    if (PAIR && pv.done) chain_signal(pv.done);
 }
 
 constexpr int SR_THREADS = 256;
@@ -996,10 +918,9 @@ template <bool NT, int G, bool REALIGN, bool XT>
 __global__ __launch_bounds__(SR_THREADS) void spmm_shortrow_kernel(
     const int *__restrict__ rowptr, const int *__restrict__ colind, const double *__restrict__ vals,
     const BatchPtrs bp, const double *__restrict__ XT0, long xt_stride, long ldx, long ldy, int nrow, int nf, int fper,
-    const double *__restrict__ wM, double fill, unsigned *chain_cnt = nullptr, unsigned chain_n = 0, int chain_ncol = 0)
+    const double *__restrict__ wM, double fill)
 {
     __shared__ double s_y[REALIGN ? G : 1][SR_THREADS];
-    extern __shared__ double sr_chain[];                 // chain: this workgroup's fields of X, [fper][chain_ncol]
     // blockIdx.y = field batch of a batched launch (ibh_weighted_apply_many_device): the workgroups of batch q+1 start while
     // those of batch q still store, so launch ramp and drain are paid once per launch
     const double *__restrict__ X = XT ? XT0 + (long)blockIdx.y * xt_stride : bp.x[blockIdx.y];
@@ -1015,18 +936,6 @@ __global__ __launch_bounds__(SR_THREADS) void spmm_shortrow_kernel(
     const bool live = r < nrow;
     const int fbeg = fy * fper;
     const int fend = min(nf, fbeg + fper);
-    if (chain_cnt) {
-        // last kernel of a chain: dispatched without a barrier behind the kernel that makes X.  Wait for that kernel's workgroups,
-        // then take this workgroup's fields of the (small: an A-space result) X into LDS through device-coherent loads -- once
-        // per workgroup; the gathers below read LDS (plain loads could hit stale lines, coherent ones bypass the L1 they live on)
-        chain_wait(chain_cnt, chain_n);
-        const int nel = (fend - fbeg) * chain_ncol;
-        for (int k = threadIdx.x; k < nel; k += SR_THREADS) {
-            const int ff = k / chain_ncol, c = k - ff * chain_ncol;
-            sr_chain[k] = chain_load(X + (long)(fbeg + ff) * ldx + c);
-        }
-        __syncthreads();
-    }
     if (!REALIGN && !live) return;
     int beg = 0, end = 0;
     bool dead = false;
@@ -1145,20 +1054,11 @@ __global__ __launch_bounds__(SR_THREADS) void spmm_shortrow_kernel(
             const double *xf = X + (long)f * ldx;
             // predicated, never multiplied by a padded zero: 0*NaN must not leak into a row
             double a = 0.0;
-            if (chain_cnt) {                            // (X comes from the kernel this one was dispatched behind without a barrier: staged)
-                const double *xs = sr_chain + (f - fbeg) * chain_ncol;
-                if (n > 0) a = v0 * xs[c0];
-                if (n > 1) a = fma(v1, xs[c1], a);
-                if (n > 2) a = fma(v2, xs[c2], a);
-                if (n > 3) a = fma(v3, xs[c3], a);
-                for (int k = beg + 4; k < end; ++k) a = fma(vals[k], xs[colind[k]], a);
-            } else {
-                if (n > 0) a = v0 * xf[c0];
-                if (n > 1) a = fma(v1, xf[c1], a);
-                if (n > 2) a = fma(v2, xf[c2], a);
-                if (n > 3) a = fma(v3, xf[c3], a);
-                for (int k = beg + 4; k < end; ++k) a = fma(vals[k], xf[colind[k]], a);
-            }
+            if (n > 0) a = v0 * xf[c0];
+            if (n > 1) a = fma(v1, xf[c1], a);
+            if (n > 2) a = fma(v2, xf[c2], a);
+            if (n > 3) a = fma(v3, xf[c3], a);
+            for (int k = beg + 4; k < end; ++k) a = fma(vals[k], xf[colind[k]], a);
             acc[g] = dead ? fill : a;
         }
         }
@@ -1361,8 +1261,10 @@ static void launch_rowblock(const ibh_weighted *w, const BatchPtrs &bp, int nbat
     else if (unroll == 2) IBH_RB(2);
     else if (unroll == 8) IBH_RB(8);
     else if (unroll > 8 && FPW == 1 && WK == 1) {      // one batch covers a whole row of <= 768 / 896 / 1024 entries
-        constexpr bool one = FPW == 1 && WK == 1;
-        if (unroll <= 12) IBH_RB((one ? 12 : 8)); else if (unroll <= 14) IBH_RB((one ? 14 : 8)); else IBH_RB((one ? 16 : 8));
+        // (4 waves: a lane stages twice the entries of a segment, and 12..16 gathers no longer fit 64 registers: they spill; 8)
+        if constexpr (FPW == 1 && WK == 1 && NW == 8) {
+            if (unroll <= 12) IBH_RB(12); else if (unroll <= 14) IBH_RB(14); else IBH_RB(16);
+        } else IBH_RB(8);
     }
     else IBH_RB(4);
 #undef IBH_RB
@@ -1606,23 +1508,23 @@ static void launch_sweep(const ibh_weighted *w, const BatchPtrs &bp, int nbatch,
     IBH_HIP(hipGetLastError());
 }
 
-// which kernel serves (w, nvar): 1 rowblock, 2 shortrow, 3 rowdual, 4 colsweep, 5 rowgroup
-static int pick_kernel(const ibh_weighted *w, int nvar, int nbatch = 1) {
-    int kernel = w->kernel_override;
-    if (kernel == 4 && w->sweep_ntask == 0) kernel = 0;       // no column-sweep structure: the automatic choice
-    if (kernel == 0) {
+// which kernel serves (w, nvar)
+static ApplyKernel pick_kernel(const ibh_weighted *w, int nvar, int nbatch = 1) {
+    ApplyKernel kernel = w->kernel_override;
+    if (kernel == KERNEL_COLSWEEP && w->sweep_ntask == 0) kernel = KERNEL_AUTO;       // no column-sweep structure: the automatic choice
+    if (kernel == KERNEL_AUTO) {
         // rowblock = one workgroup per (row, field chunk): for FEW LONG rows.  Many rows of 6..63 entries (a smoothed IvE:
         // 76 k rows of ~16) are thread-per-row work (measured, 5 km smoothed IvE, 16 fields: 220 us as rowblock)
         const double mean = w->nrow ? (double)w->nnz / (double)w->nrow : 0.0;
         const bool few_rows = w->nrow <= get_tuning("rowblock_max_short_rows", 16384);
-        kernel = (mean >= 64.0 || (few_rows && mean >= (double)get_tuning("rowblock_min_mean_nnz", 6))) ? 1 : 2;
+        kernel = (mean >= 64.0 || (few_rows && mean >= (double)get_tuning("rowblock_min_mean_nnz", 6))) ? KERNEL_ROWBLOCK : KERNEL_SHORTROW;
     }
     // E-row matrices (EvI, EvX), once the structure exists: the row groups (every X element gathered once per GCM cell; measured
     // against the sweep at 1 km, 64 fields: 221 against 247 us one launch per apply, 199 against 203-223 batched) -- except
     // batched launches of FEWER than 32 fields, where the batches share the lanes of the column sweep (1 km, 16 fields, 16 per
     // launch: 51 against 63 us per apply).  The other long-row matrices (AvI, AvX) take the sweep in batched launches only
     // (1 km, 64 fields: 167 against 173 us per apply 32 deep, but 193 against 183 us one launch per apply).
-    if (kernel == 1 && w->kernel_override == 0) {
+    if (kernel == KERNEL_ROWBLOCK && w->kernel_override == KERNEL_AUTO) {
         // (round 4, the Antarctic sheet -- 17.6 / 35.2 M entries -- one apply per launch: AvI, 128 fields, sweep 3 131 against 3 654 us;
         // EvI, 16 fields, row groups 641 against 812 (bands) / 747 (rows) / 1 994 us (sweep): scratch/kernel_choice.py)
         const bool huge = w->nnz >= (1l << 24);
@@ -1632,12 +1534,13 @@ static int pick_kernel(const ibh_weighted *w, int nvar, int nbatch = 1) {
         // (round 5: on matrices of 2^24 entries and more the tiled row groups beat the sweep in batched launches of few fields too --
         // the Antarctic EvI, 16 fields, batches of 4: bench.py 0.487 of peak through the sweep, measured again below)
         const bool tiles_win = w->gt_ntile > 0 && w->nnz >= (1l << 24) && get_tuning("rowgroup_form", -1) != 0;
-        if (grp_ok && (nvar >= 32 || !sweep_ok || tiles_win)) kernel = 5;
-        else if (sweep_ok) kernel = 4;
+        if (grp_ok && (nvar >= 32 || !sweep_ok || tiles_win)) kernel = KERNEL_ROWGROUP;
+        else if (sweep_ok) kernel = KERNEL_COLSWEEP;
     }
-    if (kernel == 5 && w->grp_n == 0) kernel = 1;             // no row groups were built for this matrix
-    if (kernel == 1 && w->kernel_override == 0 && w->band_n > 0 && nvar >= 4 && get_tuning("rowdual_auto", 1)) kernel = 3;
-    if (kernel == 3 && w->band_n == 0) kernel = 1;            // no bands were built for this matrix
+    if (kernel == KERNEL_ROWGROUP && w->grp_n == 0) kernel = KERNEL_ROWBLOCK;             // no row groups were built for this matrix
+    if (kernel == KERNEL_ROWBLOCK && w->kernel_override == KERNEL_AUTO && w->band_n > 0 && nvar >= 4 && get_tuning("rowdual_auto", 1))
+        kernel = KERNEL_ROWDUAL;
+    if (kernel == KERNEL_ROWDUAL && w->band_n == 0) kernel = KERNEL_ROWBLOCK;            // no bands were built for this matrix
     return kernel;
 }
 struct ShortrowPlan { int fper, g, use_xt, ldt; bool one_entry, big; };
@@ -1682,16 +1585,16 @@ static ShortrowPlan shortrow_plan(const ibh_weighted *w, int nvar, int nbatch = 
 // must not pay for a structure it never reuses; ibh_weighted_prepare builds at once).
 static bool wants_sweep(const ibh_weighted *w, int nvar, int nbatch, bool seen) {
     if (w->sweep_tried || w->sweep_ntask > 0) return false;
-    if (w->kernel_override == 4) return true;
+    if (w->kernel_override == KERNEL_COLSWEEP) return true;
     const bool long_rows = w->nrow > 0 && (double)w->nnz / (double)w->nrow >= 64.0 && w->nnz <= 2 * (int64_t)w->ncol;      // AvI, AvX
     const bool e_rows = w->band_eligible && (nvar < 32 || (w->grp_tried && w->grp_n == 0) || !get_tuning("rowgroup_auto", 1));
     const bool huge_wide = w->nnz >= (1l << 24) && nvar >= 128;      // (one launch of >= 128 fields on the Antarctic AvI: see launch_kernel_for)
-    return (e_rows || (long_rows && (nbatch >= get_tuning("sweep_min_batch", 4) || huge_wide))) && w->kernel_override == 0 && seen &&
+    return (e_rows || (long_rows && (nbatch >= get_tuning("sweep_min_batch", 4) || huge_wide))) && w->kernel_override == KERNEL_AUTO && seen &&
            sweep_lanes(nvar, nbatch) >= get_tuning("sweep_min_nvar", 32) && get_tuning("sweep_auto", 1) &&
            (double)w->nnz * sweep_lanes(nvar, nbatch) >= (double)get_tuning("sweep_min_work", 64 << 20);
 }
 static bool wants_bands(const ibh_weighted *w, int nvar, bool seen) {
-    return w->band_eligible && !w->band_tried && w->band_n == 0 && w->sweep_ntask == 0 && seen && w->kernel_override == 0 && nvar >= 4 &&
+    return w->band_eligible && !w->band_tried && w->band_n == 0 && w->sweep_ntask == 0 && seen && w->kernel_override == KERNEL_AUTO && nvar >= 4 &&
            (double)w->nnz * nvar >= (double)get_tuning("rowdual_min_work", 128 << 20) && get_tuning("rowdual_auto", 1);
 }
 // Row groups (rowgroup kernel) of an E-row matrix: bandwidth-sized matrices applied to >= 32 fields get them like the sweep
@@ -1705,8 +1608,8 @@ static bool sweep_sized(const ibh_weighted *w, int nvar, int nbatch) {
 }
 static bool wants_groups(const ibh_weighted *w, int nvar, int nbatch, long seen) {
     if (!w->band_eligible || w->grp_tried || w->grp_n > 0) return false;
-    if (w->kernel_override == 5) return true;
-    if (w->kernel_override != 0 || nvar < 4 || !get_tuning("rowgroup_auto", 1)) return false;
+    if (w->kernel_override == KERNEL_ROWGROUP) return true;
+    if (w->kernel_override != KERNEL_AUTO || nvar < 4 || !get_tuning("rowgroup_auto", 1)) return false;
     // (bandwidth-sized matrices: from 32 fields -- fewer fields per launch share the lanes of the column sweep when launches are
     // batched; a single launch of a 2^24-entry matrix takes the groups from 4 fields on)
     if (sweep_sized(w, nvar, nbatch)) return (nvar >= 32 || (nbatch < 4 && w->nnz >= (1l << 24))) && seen >= 1;
@@ -1759,11 +1662,11 @@ static void build_structures(const ibh_weighted *w, int nvar, int nbatch, bool s
 static void size_scratch(const ibh_weighted *w, int nvar, int nbatch) {
     if (w->band_n > 0) grow_scratch(w->band_part, band_part_count(w, nvar, nbatch), nullptr, "band");
     if (w->sweep_ntask > 0) grow_scratch(w->sweep_part, sweep_part_count(w, nvar, nbatch), nullptr, "column-sweep");
-    if (pick_kernel(w, nvar, nbatch) == 2 || pick_kernel(w, nvar, 1) == 2 || w->kernel_override == 0) {
+    if (pick_kernel(w, nvar, nbatch) == KERNEL_SHORTROW || pick_kernel(w, nvar, 1) == KERNEL_SHORTROW || w->kernel_override == KERNEL_AUTO) {
         for (int nb : {1, nbatch}) {
             const ShortrowPlan p = shortrow_plan(w, nvar, nb);
             const int qmax = std::max(1, get_tuning("shortrow_many", w->nrow >= (1 << 19) ? 1 : IBH_MAX_BATCH));
-            if (p.use_xt && (pick_kernel(w, nvar, nb) == 2 || w->kernel_override == 2))
+            if (p.use_xt && (pick_kernel(w, nvar, nb) == KERNEL_SHORTROW || w->kernel_override == KERNEL_SHORTROW))
                 grow_scratch(w->xt, (size_t)w->ncol * (size_t)p.ldt * (size_t)std::min(qmax, nb), nullptr, "transposed-input");
         }
     }
@@ -1802,8 +1705,8 @@ void weighted_pair_prepare(const ibh_weighted *first, const ibh_weighted *second
     IBH_CHECK(second->nnz <= (1 << 22), "pair: the second matrix is too large (%ld entries) to be paired on the host", (long)second->nnz);
     first->pair_second = nullptr;
     if (first->grp_n == 0) {                                  // row groups first (small matrices get them from an explicit request only)
-        const int keep = first->kernel_override;
-        const_cast<ibh_weighted *>(first)->kernel_override = 5;
+        const ApplyKernel keep = first->kernel_override;
+        const_cast<ibh_weighted *>(first)->kernel_override = KERNEL_ROWGROUP;
         try { weighted_prepare(first, nvar > 0 ? nvar : 16, 1); } catch (...) { const_cast<ibh_weighted *>(first)->kernel_override = keep; throw; }
         const_cast<ibh_weighted *>(first)->kernel_override = keep;
     }
@@ -1867,9 +1770,8 @@ void weighted_pair_prepare(const ibh_weighted *first, const ibh_weighted *second
     first->pair_uid = second->uid;
 }
 
-static unsigned pair_grid_blocks(const ibh_weighted *first, int nvar);
 void spmm_launch_pair(const ibh_weighted *first, const ibh_weighted *second, const double *dA, int nvar, int64_t lda, double *dB1,
-                      int64_t ldb1, double *dB2, int64_t ldb2, double fill, hipStream_t stream, unsigned *done)
+                      int64_t ldb1, double *dB2, int64_t ldb2, double fill, hipStream_t stream)
 {
     HandleScope hs_(first);
     IBH_CHECK(first->pair_second == second && first->pair_uid == second->uid && first->grp_n > 0,
@@ -1880,7 +1782,7 @@ void spmm_launch_pair(const ibh_weighted *first, const ibh_weighted *second, con
     IBH_CHECK(first->conservative && second->conservative, "pair apply: smoothed (non-conservative) matrices take separate applies");
     BatchPtrs bp{};
     bp.x[0] = dA; bp.y[0] = dB1;
-    const PairView pv{first->pair_w.p, first->pair_mask.p, first->pair_row.p, second->wM.p, dB2, (long)ldb2, done};
+    const PairView pv{first->pair_w.p, first->pair_mask.p, first->pair_row.p, second->wM.p, dB2, (long)ldb2};
     const int nw = get_tuning("rowgroup_waves", nvar >= 32 ? 8 : 4), tw = get_tuning("rowgroup_tw", first->nnz < (1 << 20) ? 32 : 64);
 #define IBH_RGP(N, TT) launch_rowgroup<N, 8, TT>(first, bp, 1, nvar, (long)lda, (long)ldb1, fill, stream, &pv)
     if (use_grouptile(first, nvar)) {
@@ -1888,61 +1790,29 @@ void spmm_launch_pair(const ibh_weighted *first, const ibh_weighted *second, con
     } else if (nw == 8) { if (tw == 32) IBH_RGP(8, 32); else IBH_RGP(8, 64); }
     else { if (tw == 32) IBH_RGP(4, 32); else IBH_RGP(4, 64); }
 #undef IBH_RGP
-    first->last_kernel = 5;
-    second->last_kernel = 5;
+    first->last_kernel = KERNEL_ROWGROUP;
+    second->last_kernel = KERNEL_ROWGROUP;
     ++first->napply; ++second->napply;
-}
-// workgroups of the pair launch of (first, nvar): what the chain's last kernel waits for
-static unsigned pair_grid_blocks(const ibh_weighted *first, int nvar) {
-    int xcd_mode;
-    if (use_grouptile(first, nvar)) return (unsigned)rowblock_grid(first->grp_n, ceil_div(nvar, 16), xcd_mode);
-    const int nw = get_tuning("rowgroup_waves", nvar >= 32 ? 8 : 4);
-    return (unsigned)rowblock_grid(first->grp_n, ceil_div(nvar, nw == 8 ? 8 : 4), xcd_mode);
 }
 // B1 = first * A, B2 = second * B1 (the fused pair), B3 = third * B2: the chain ice -> elevation classes -> atmosphere -> ice of
 // BASELINE config 3 (EvI, AvE, IvA): the pair launch and the third matrix's apply, stream-ordered.
-// ibh_set_tuning("chain_overlap", 1): the second launch is dispatched WITHOUT a barrier behind the first (hipExtAnyOrderLaunch) --
-// its launch latency runs while the first kernel computes -- and its workgroups wait on a device flag the first kernel's last
-// workgroup raises once all results are out (chain_begin / chain_signal / chain_wait; the first kernel's packet precedes it in
-// the queue, so its workgroups are placed first: the waiting ones cannot starve them).  Bitwise the ordered launches, and MEASURED
-// SLOWER on MI355X / ROCm 7.2 (5 km, 16 fields, back-to-back chains: 33 us per chain against 15.9 ordered; 68 us with agent-scope
-// acquire fences in the waiting workgroups -- every one of them invalidates its XCD's L2 --, 43 with device-coherent loads of X,
-// 33 with X staged in LDS and the flag only read; the length of the sleep in the wait loop changes nothing; under rocprofv3 the
-// pair kernel lasts 28 us instead of 9 with the waiting kernel resident): off by default, kept for a runtime where an unordered
-// dispatch is cheap.
 void spmm_launch_chain(const ibh_weighted *first, const ibh_weighted *second, const ibh_weighted *third, const double *dA, int nvar, int64_t lda,
                        double *dB1, int64_t ldb1, double *dB2, int64_t ldb2, double *dB3, int64_t ldb3, double fill, hipStream_t stream)
 {
     IBH_CHECK(third->ncol == second->nrow, "chain: the third matrix reads %d columns, the second makes %d rows", third->ncol, second->nrow);
     if (nvar <= 0 || first->nrow == 0) return;
-    bool overlap = get_tuning("chain_overlap", 0) != 0 && third->conservative && third->nrow > 0;
-    if (overlap) {
-        HandleScope hs_(third);
-        const ShortrowPlan sp = shortrow_plan(third, nvar, 1);
-        overlap = pick_kernel(third, nvar, 1) == 2 && !sp.use_xt && (size_t)sp.fper * (size_t)third->ncol * sizeof(double) <= 32 * 1024;
-    }
-    if (!overlap) {
-        spmm_launch_pair(first, second, dA, nvar, lda, dB1, ldb1, dB2, ldb2, fill, stream, nullptr);
-        spmm_launch(third, dB2, nvar, ldb2, dB3, ldb3, fill, 0, stream);
-        return;
-    }
-    if (!first->chain_cnt.p) { first->chain_cnt.alloc(2); first->chain_cnt.zero(stream); }
-    unsigned nblk;
-    { HandleScope hs_(first); nblk = pair_grid_blocks(first, nvar); }
-    spmm_launch_pair(first, second, dA, nvar, lda, dB1, ldb1, dB2, ldb2, fill, stream, first->chain_cnt.p);
-    g_chain_cnt = first->chain_cnt.p; g_chain_n = nblk;
+    spmm_launch_pair(first, second, dA, nvar, lda, dB1, ldb1, dB2, ldb2, fill, stream);
     spmm_launch(third, dB2, nvar, ldb2, dB3, ldb3, fill, 0, stream);
-    IBH_CHECK(g_chain_cnt == nullptr, "internal: the chain's last apply did not take the counter");
 }
 
-static void launch_one_impl(const ibh_weighted *w, int kernel, const BatchPtrs &bp, int nbatch, int nvar, int64_t lda,
+static void launch_one_impl(const ibh_weighted *w, ApplyKernel kernel, const BatchPtrs &bp, int nbatch, int nvar, int64_t lda,
                             int64_t ldb, double fill, hipStream_t stream);
-static void launch_one(const ibh_weighted *w, int kernel, const BatchPtrs &bp, int nbatch, int nvar, int64_t lda,
+static void launch_one(const ibh_weighted *w, ApplyKernel kernel, const BatchPtrs &bp, int nbatch, int nvar, int64_t lda,
                        int64_t ldb, double fill, hipStream_t stream)
 {
     // launch timing (ibh_set_launch_events): the single-kernel paths attach the events to their dispatch, the I-row path
     // to its first and last one (transposed input + row kernel); bands + combine records them around the sequence
-    if (kernel == 3 && g_ev_start && g_ev_stop) {
+    if (kernel == KERNEL_ROWDUAL && g_ev_start && g_ev_stop) {
         hipEvent_t ev0 = g_ev_start, ev1 = g_ev_stop;
         g_ev_start = g_ev_stop = nullptr;
         IBH_HIP(hipEventRecord(ev0, stream));
@@ -1952,10 +1822,10 @@ static void launch_one(const ibh_weighted *w, int kernel, const BatchPtrs &bp, i
     }
     launch_one_impl(w, kernel, bp, nbatch, nvar, lda, ldb, fill, stream);
 }
-static void launch_one_impl(const ibh_weighted *w, int kernel, const BatchPtrs &bp, int nbatch, int nvar, int64_t lda,
+static void launch_one_impl(const ibh_weighted *w, ApplyKernel kernel, const BatchPtrs &bp, int nbatch, int nvar, int64_t lda,
                             int64_t ldb, double fill, hipStream_t stream)
 {
-    if (kernel == 5) {
+    if (kernel == KERNEL_ROWGROUP) {
         // 8 waves (fields) share a staged segment from 32 fields (5 km, 64 fields: 17.1 against 19.3 us with 4)
         const int u = get_tuning("rowgroup_unroll", 8), nw = get_tuning("rowgroup_waves", nvar >= 32 ? 8 : 4);
         // class tables of half width (two lanes per entry) for the small matrices: all workgroups of a 5 km launch fit the LDS at
@@ -1969,15 +1839,15 @@ static void launch_one_impl(const ibh_weighted *w, int kernel, const BatchPtrs &
         else if (nw == 8) { if (u <= 8) IBH_RG(8, 8, 64); else IBH_RG(8, 16, 64); }
         else { if (u <= 4) IBH_RG(4, 4, 64); else if (u <= 8) IBH_RG(4, 8, 64); else IBH_RG(4, 16, 64); }
 #undef IBH_RG
-    } else if (kernel == 4) {
+    } else if (kernel == KERNEL_COLSWEEP) {
         launch_sweep(w, bp, nbatch, nvar, (long)lda, (long)ldb, fill, stream);
-    } else if (kernel == 3) {
+    } else if (kernel == KERNEL_ROWDUAL) {
         const long pairs = (long)w->nrow * nvar;
         const int fpw = get_tuning("rowdual_fpw", pairs >= 4 * 8192 ? 4 : pairs >= 2 * 8192 ? 2 : 1);
         if (fpw >= 4) launch_rowdual<4>(w, bp, nbatch, nvar, (long)lda, (long)ldb, fill, stream);
         else if (fpw == 2) launch_rowdual<2>(w, bp, nbatch, nvar, (long)lda, (long)ldb, fill, stream);
         else launch_rowdual<1>(w, bp, nbatch, nvar, (long)lda, (long)ldb, fill, stream);
-    } else if (kernel == 1) {
+    } else if (kernel == KERNEL_ROWBLOCK) {
         int fpw = get_tuning(nbatch > 1 ? "rowblock_many_fpw" : "rowblock_fpw", 0), wk = get_tuning("rowblock_wk", 0);
         if (fpw == 0 || wk == 0) {
             // enough workgroups to give every CU ~8: small problems are latency-bound and want many
@@ -1999,7 +1869,8 @@ static void launch_one_impl(const ibh_weighted *w, int kernel, const BatchPtrs &
             const double *X1 = bp.x[0];
             double *Y1 = bp.y[0];
 #define IBH_R1(N, UU) launch_rowone<N, UU>(w, X1, Y1, nvar, (long)lda, (long)ldb, fill, stream)
-            if (nw == 4) { if (u <= 8) IBH_R1(4, 8); else if (u <= 12) IBH_R1(4, 12); else if (u <= 14) IBH_R1(4, 14); else IBH_R1(4, 16); }
+            // (4 waves: a lane stages twice the entries, and 16 gathers no longer fit 64 registers: they spill; 14)
+            if (nw == 4) { if (u <= 8) IBH_R1(4, 8); else if (u <= 12) IBH_R1(4, 12); else IBH_R1(4, 14); }
             else { if (u <= 8) IBH_R1(8, 8); else if (u <= 12) IBH_R1(8, 12); else if (u <= 14) IBH_R1(8, 14); else IBH_R1(8, 16); }
 #undef IBH_R1
             return;
@@ -2019,7 +1890,7 @@ static void launch_one_impl(const ibh_weighted *w, int kernel, const BatchPtrs &
         else if (fpw == 4 && wk == 4) IBH_L(4, 4, 4);
         else IBH_L(1, 4, 4);
 #undef IBH_L
-    } else {
+    } else {                                                    // KERNEL_SHORTROW
         const ShortrowPlan p = shortrow_plan(w, nvar, nbatch);
         const int fper = p.fper, g = p.g;
         const long xt_stride = (long)w->ncol * p.ldt;
@@ -2058,16 +1929,10 @@ static void launch_one_impl(const ibh_weighted *w, int kernel, const BatchPtrs &
                 e_first = nullptr;
                 xld = p.ldt;
             }
-            unsigned *ccnt = g_chain_cnt;
-            const unsigned cn = g_chain_n;
-            g_chain_cnt = nullptr; g_chain_n = 0;
-            IBH_CHECK(!ccnt || (!p.use_xt && nbatch == 1), "internal: a chain's last apply must read its input in place");
-            const size_t clds = ccnt ? (size_t)fper * (size_t)w->ncol * sizeof(double) : 0;
-#define IBH_SR4(NT, GG, RA, XTT)                                                                                \
-    hipExtLaunchKernelGGL((spmm_shortrow_kernel<NT, GG, RA, XTT>), grid, dim3(SR_THREADS), clds, stream, e_first, e_last,   \
-                          ccnt ? hipExtAnyOrderLaunch : 0,                                                                  \
+#define IBH_SR4(NT, GG, RA, XTT)                                                                                        \
+    hipExtLaunchKernelGGL((spmm_shortrow_kernel<NT, GG, RA, XTT>), grid, dim3(SR_THREADS), 0, stream, e_first, e_last, 0,  \
                           w->rowptr.p, w->colind.p, w->val.p, bq, (const double *)w->xt.p, xt_stride, xld, (long)ldb,       \
-                          w->nrow, nvar, fper, w->wM.p, fill, ccnt, cn, w->ncol)
+                          w->nrow, nvar, fper, w->wM.p, fill)
 #define IBH_SR(NT, GG)                                                                                          \
     do {                                                                                                        \
         if (realign) { if (p.use_xt) IBH_SR4(NT, GG, true, true); else IBH_SR4(NT, GG, true, false); }          \
@@ -2100,9 +1965,10 @@ void spmm_launch_many(const ibh_weighted *w, int nbatch, const double *const *dA
     // ibh_set_tuning("lazy_structures", 0) switches it off.
     if (get_tuning("lazy_structures", 1)) build_structures(w, nvar, std::min(nbatch, IBH_MAX_BATCH), w->napply >= 1, stream, (long)w->napply);
     ++w->napply;
-    int kernel = pick_kernel(w, nvar, nbatch);
+    ApplyKernel kernel = pick_kernel(w, nvar, nbatch);
     // the column sweep addresses a wave's 16 field planes through one buffer descriptor (32-bit offsets)
-    if (kernel == 4 && ((uint64_t)16 * (uint64_t)lda * 8 + (uint64_t)w->ncol * 8 >= (1ull << 32))) kernel = w->band_n > 0 ? 3 : 1;
+    if (kernel == KERNEL_COLSWEEP && ((uint64_t)16 * (uint64_t)lda * 8 + (uint64_t)w->ncol * 8 >= (1ull << 32)))
+        kernel = w->band_n > 0 ? KERNEL_ROWDUAL : KERNEL_ROWBLOCK;
     w->last_kernel = kernel;
     w->last_sig[0] = 0;
     const bool correct = !w->conservative && force_conservation;

@@ -299,9 +299,8 @@ class linear_Weighted:
         return out1, out2
 
     def apply_chain_device(self, second, third, dA, out1=None, out2=None, out3=None, fill=float("nan"), stream=None):
-        """B1 = self * A, B2 = second * B1 (the fused pair: pair_prepare(second) first), B3 = third * B2 with the third product's
-        launch overlapped with the pair kernel (ibh_weighted_apply_chain_device); returns (B1, B2, B3), bitwise the pair apply
-        followed by third.apply_device."""
+        """B1 = self * A, B2 = second * B1 (the fused pair: pair_prepare(second) first), B3 = third * B2, as two stream-ordered
+        launches (ibh_weighted_apply_chain_device); returns (B1, B2, B3), bitwise the pair apply followed by third.apply_device."""
         import torch
         assert dA.is_cuda and dA.dtype == torch.float64 and dA.dim() == 2 and dA.stride(1) == 1 and dA.shape[1] == self.ncol_d
         nvar = dA.shape[0]

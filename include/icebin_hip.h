@@ -268,9 +268,7 @@ int ibh_weighted_apply_pair_device(const ibh_weighted *first, const ibh_weighted
 /* The chain of BASELINE config 3, ice -> elevation classes -> atmosphere -> ice, in one call: B1 = first * A and B2 = second * B1
  * as the fused pair above (ibh_weighted_pair_prepare(first, second) first), B3 = third * B2 (IvA; the reference: three
  * Weighted_Eigen::apply calls, IceCoupler.cpp:203-252 builds its inputs the same way).  Two stream-ordered launches; B1, B2, B3 are
- * bitwise what the pair apply followed by ibh_weighted_apply_device(third) writes; a pure enqueue (graph-capturable).
- * ibh_set_tuning("chain_overlap", 1) dispatches the second launch without a queue barrier behind the pair kernel and lets its
- * workgroups wait on a device flag instead (same bits; measured slower on MI355X / ROCm 7.2: DESIGN.md K1f). */
+ * bitwise what the pair apply followed by ibh_weighted_apply_device(third) writes; a pure enqueue (graph-capturable). */
 int ibh_weighted_apply_chain_device(const ibh_weighted *first, const ibh_weighted *second, const ibh_weighted *third, const double *dA_b,
                                     int32_t nvar, int64_t lda, double *dB1_b, int64_t ldb1, double *dB2_b, int64_t ldb2, double *dB3_b,
                                     int64_t ldb3, double fill, void *stream);

@@ -109,3 +109,21 @@ def test_missing_rccl_is_enotimpl_not_a_crash(lib):
     assert r.returncode == 0, r.stderr
     rc, msg = r.stdout.strip().split(" ", 1)
     assert int(rc) == _capi.IBH_ENOTIMPL and "needs RCCL" in msg and "/nonexistent/librccl.so" in msg, r.stdout
+
+
+def test_no_apply_kernel_uses_scratch_memory(lib, tmp_path):
+    # a kernel that spills registers to scratch is slow whether or not the dispatch picks it: no instantiation in spmm.hip may.
+    # The code object's metadata lists every kernel with its private segment (scratch) size per lane.
+    import subprocess
+    llvm = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin")
+    obj = os.path.join(ROOT, "icebin_amd", "lib", "spmm.o")
+    fatbin, dev = str(tmp_path / "spmm.hip_fatbin"), str(tmp_path / "spmm_gfx950.o")
+    subprocess.run([os.path.join(llvm, "llvm-objcopy"), "--dump-section=.hip_fatbin=" + fatbin, obj, str(tmp_path / "host.o")], check=True)
+    subprocess.run([os.path.join(llvm, "clang-offload-bundler"), "--unbundle", "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950",
+                    "--input=" + fatbin, "--output=" + dev], check=True)
+    notes = subprocess.run([os.path.join(llvm, "llvm-readelf"), "--notes", dev], check=True, capture_output=True, text=True).stdout
+    names = re.findall(r"^    \.name:\s+(\S+)", notes, re.M)
+    sizes = [int(s) for s in re.findall(r"^    \.private_segment_fixed_size:\s+(\d+)", notes, re.M)]
+    assert len(names) == len(sizes) and len(names) > 100, (len(names), len(sizes))
+    spilling = [(n, s) for n, s in zip(names, sizes) if s != 0]
+    assert not spilling, spilling
