@@ -246,7 +246,7 @@ struct ibh_weighted {
     int built_fast = 0;                 // assembled by the plan-based fast path (fastasm.inl); introspection only
     // SpMM dispatch
     ibh::ApplyKernel kernel_override = ibh::KERNEL_AUTO;
-    mutable char last_sig[64] = {0};    // the kernel instantiation the last apply launched, as rocprofv3 names it (rowblock / rowone; else the kernel family)
+    mutable char last_sig[64] = {0};    // the kernel instantiation the last apply launched, as rocprofv3 names it (every apply kernel family records it)
     // per-handle launch options (ibh_weighted_set_option): looked up before the process-wide ibh_set_tuning map by every apply of
     // THIS matrix, so two host threads tuning different handles do not interfere
     mutable std::unordered_map<std::string, int> opts;

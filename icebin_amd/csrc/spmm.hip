@@ -1404,16 +1404,20 @@ static void launch_rowdual(const ibh_weighted *w, const BatchPtrs &bp, int nbatc
     const long pstride = (long)nvar * ldp;                       // one batch's lower (or upper) partial sums
     grow_scratch(w->band_part, band_part_count(w, nvar, nbatch), stream, "band");
     double *P0 = w->band_part.p, *P1 = P0 + (size_t)nbatch * (size_t)pstride;
-    const double mean = w->nrow ? (double)w->band_n / (double)w->nrow / 64.0 : 1.0;
-    const int unroll = mean > 4.0 ? 8 : mean > 2.0 ? 4 : mean > 1.0 ? 2 : 1;
+    int unroll = get_tuning("rowdual_unroll", 0);
+    if (unroll <= 0) {
+        const double mean = w->nrow ? (double)w->band_n / (double)w->nrow / 64.0 : 1.0;
+        unroll = mean > 4.0 ? 8 : mean > 2.0 ? 4 : mean > 1.0 ? 2 : 1;
+    }
     BatchPtrs bq{};
     for (int q = 0; q < nbatch; ++q) { bq.x[q] = bp.x[q]; bq.y[q] = P0 + (size_t)q * (size_t)pstride; }
     const dim3 grid((unsigned)nb, (unsigned)nbatch);
 #define IBH_RD(U)                                                                                                  \
+    snprintf(w->last_sig, sizeof(w->last_sig), "spmm_rowblock_kernel<%d, 1, %d, %d, true>", FPW, (int)(U), NW);     \
     hipLaunchKernelGGL((spmm_rowblock_kernel<FPW, 1, U, NW, true>), grid, dim3(NW * 64), 0, stream,                 \
                        w->band_ptr.p, w->band_col.p, w->band_v0.p, bq, nbatch, 1, lda, w->ncol, ldp, w->nrow, nvar, nfc, xcd_mode, \
                        w->wM.p, fill, w->band_v1.p, P1, (const int *)nullptr, pstride)
-    if (unroll == 1) IBH_RD(1); else if (unroll == 2) IBH_RD(2); else if (unroll == 8) IBH_RD(8); else IBH_RD(4);
+    if (unroll == 1) { IBH_RD(1); } else if (unroll == 2) { IBH_RD(2); } else if (unroll == 8) { IBH_RD(8); } else { IBH_RD(4); }
 #undef IBH_RD
     hipLaunchKernelGGL(dual_combine_kernel, dim3((unsigned)ceil_div(w->nrow, 256), (unsigned)nvar, (unsigned)nbatch), dim3(256), 0, stream,
                        P0, P1, ldp, pstride, w->band_rb1.p, w->wM.p, fill, bp, ldb, w->nrow, nvar);
@@ -1498,9 +1502,10 @@ static void launch_sweep(const ibh_weighted *w, const BatchPtrs &bp, int nbatch,
     hipEvent_t ev0 = g_ev_start, ev1 = g_ev_stop;
     g_ev_start = g_ev_stop = nullptr;
     // launch timing: start = the sweep kernel begins, stop = the combine kernel ends (both belong to the apply)
-#define IBH_SW(F, I) hipExtLaunchKernelGGL((spmm_sweep_kernel<F, I, 0>), grid, dim3(SWEEP_NW * 64), lds, stream, ev0, nullptr, 0, sv, sb, lda, nvar, w->sweep_nslot, ldp, lg, nbatch)
-    if (full) { if (ident) IBH_SW(true, true); else IBH_SW(true, false); }
-    else { if (ident) IBH_SW(false, true); else IBH_SW(false, false); }
+#define IBH_SW(F, I) snprintf(w->last_sig, sizeof(w->last_sig), "%s", "spmm_sweep_kernel<" #F ", " #I ", 0>"); \
+                     hipExtLaunchKernelGGL((spmm_sweep_kernel<F, I, 0>), grid, dim3(SWEEP_NW * 64), lds, stream, ev0, nullptr, 0, sv, sb, lda, nvar, w->sweep_nslot, ldp, lg, nbatch)
+    if (full) { if (ident) { IBH_SW(true, true); } else { IBH_SW(true, false); } }
+    else { if (ident) { IBH_SW(false, true); } else { IBH_SW(false, false); } }
 #undef IBH_SW
     hipExtLaunchKernelGGL(sweep_combine_kernel, dim3((unsigned)ceil_div(w->nrow, 4), (unsigned)nfb, (unsigned)nbatch), dim3(256), 0, stream, nullptr, ev1, 0,
                        w->sweep_part.p, pstride, ldp, w->sweep_comb_ptr.p, w->sweep_comb_p.p, w->wM.p, fill,
@@ -1783,12 +1788,15 @@ void spmm_launch_pair(const ibh_weighted *first, const ibh_weighted *second, con
     BatchPtrs bp{};
     bp.x[0] = dA; bp.y[0] = dB1;
     const PairView pv{first->pair_w.p, first->pair_mask.p, first->pair_row.p, second->wM.p, dB2, (long)ldb2};
-    const int nw = get_tuning("rowgroup_waves", nvar >= 32 ? 8 : 4), tw = get_tuning("rowgroup_tw", first->nnz < (1 << 20) ? 32 : 64);
-#define IBH_RGP(N, TT) launch_rowgroup<N, 8, TT>(first, bp, 1, nvar, (long)lda, (long)ldb1, fill, stream, &pv)
+    // (the unit choices of launch_one_impl's row-group branch: the pair launch takes the same instantiations)
+    const int u = get_tuning("rowgroup_unroll", 8), nw = get_tuning("rowgroup_waves", nvar >= 32 ? 8 : 4);
+    const int tw = get_tuning("rowgroup_tw", first->nnz < (1 << 20) ? 32 : 64);
+#define IBH_RGP(N, UU, TT) launch_rowgroup<N, UU, TT>(first, bp, 1, nvar, (long)lda, (long)ldb1, fill, stream, &pv)
     if (use_grouptile(first, nvar)) {
         launch_grouptile_any(first, bp, 1, nvar, (long)lda, (long)ldb1, fill, stream, &pv);
-    } else if (nw == 8) { if (tw == 32) IBH_RGP(8, 32); else IBH_RGP(8, 64); }
-    else { if (tw == 32) IBH_RGP(4, 32); else IBH_RGP(4, 64); }
+    } else if (tw == 32) { if (nw == 8) { if (u <= 8) IBH_RGP(8, 8, 32); else IBH_RGP(8, 16, 32); } else { if (u <= 4) IBH_RGP(4, 4, 32); else IBH_RGP(4, 8, 32); } }
+    else if (nw == 8) { if (u <= 8) IBH_RGP(8, 8, 64); else IBH_RGP(8, 16, 64); }
+    else { if (u <= 4) IBH_RGP(4, 4, 64); else if (u <= 8) IBH_RGP(4, 8, 64); else IBH_RGP(4, 16, 64); }
 #undef IBH_RGP
     first->last_kernel = KERNEL_ROWGROUP;
     second->last_kernel = KERNEL_ROWGROUP;
@@ -1930,13 +1938,14 @@ static void launch_one_impl(const ibh_weighted *w, ApplyKernel kernel, const Bat
                 xld = p.ldt;
             }
 #define IBH_SR4(NT, GG, RA, XTT)                                                                                        \
+    snprintf(w->last_sig, sizeof(w->last_sig), "%s", "spmm_shortrow_kernel<" #NT ", " #GG ", " #RA ", " #XTT ">");      \
     hipExtLaunchKernelGGL((spmm_shortrow_kernel<NT, GG, RA, XTT>), grid, dim3(SR_THREADS), 0, stream, e_first, e_last, 0,  \
                           w->rowptr.p, w->colind.p, w->val.p, bq, (const double *)w->xt.p, xt_stride, xld, (long)ldb,       \
                           w->nrow, nvar, fper, w->wM.p, fill)
 #define IBH_SR(NT, GG)                                                                                          \
     do {                                                                                                        \
-        if (realign) { if (p.use_xt) IBH_SR4(NT, GG, true, true); else IBH_SR4(NT, GG, true, false); }          \
-        else { if (p.use_xt) IBH_SR4(NT, GG, false, true); else IBH_SR4(NT, GG, false, false); }                \
+        if (realign) { if (p.use_xt) { IBH_SR4(NT, GG, true, true); } else { IBH_SR4(NT, GG, true, false); } }  \
+        else { if (p.use_xt) { IBH_SR4(NT, GG, false, true); } else { IBH_SR4(NT, GG, false, false); } }        \
     } while (0)
             const bool nt = get_tuning("shortrow_nt", 1) != 0;
             if (g >= 16) { if (nt) IBH_SR(true, 16); else IBH_SR(false, 16); }

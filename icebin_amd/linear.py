@@ -409,7 +409,7 @@ class linear_Weighted:
         return buf.value.decode()
 
     def last_launch(self):
-        """The kernel instantiation of the last apply as rocprofv3 names it ("" when the kernel family does not record it)."""
+        """The kernel instantiation of the last apply as rocprofv3 names it ("" before the first apply)."""
         buf = C.create_string_buffer(64)
         check(lib().ibh_weighted_last_launch(self._h, buf, 64))
         return buf.value.decode()

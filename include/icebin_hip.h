@@ -398,7 +398,8 @@ int ibh_weighted_device_view_get(const ibh_weighted *w, ibh_weighted_device_view
 int ibh_weighted_set_kernel(ibh_weighted *w, const char *name_or_auto);   /* "auto", "rowblock", "shortrow", "rowdual", "colsweep", "rowgroup" */
 int ibh_weighted_last_kernel(const ibh_weighted *w, char *buf, int buflen);
 /* The kernel INSTANTIATION the last apply launched, spelled as rocprofv3 prints it ("spmm_rowblock_kernel<1, 1, 14, 8, false>",
- * "spmm_rowone_kernel<8, 14>"; "" for the other kernel families): bench.py checks it against the kernel a committed PMC profile
+ * "spmm_rowone_kernel<8, 14>", "spmm_shortrow_kernel<true, 8, false, true>", the band kernel "spmm_rowblock_kernel<2, 1, 4, 4, true>",
+ * "spmm_sweep_kernel<true, false, 0>"; "" before the first apply): bench.py checks it against the kernel a committed PMC profile
  * was taken on before quoting that profile's traffic. */
 int ibh_weighted_last_launch(const ibh_weighted *w, char *buf, int buflen);
 /* A launch option of THIS matrix (the apply-side keys of ibh_set_tuning: rowblock_*, rowone*, rowgroup_*, shortrow_*, sweep_*,

@@ -111,9 +111,8 @@ def test_missing_rccl_is_enotimpl_not_a_crash(lib):
     assert int(rc) == _capi.IBH_ENOTIMPL and "needs RCCL" in msg and "/nonexistent/librccl.so" in msg, r.stdout
 
 
-def test_no_apply_kernel_uses_scratch_memory(lib, tmp_path):
-    # a kernel that spills registers to scratch is slow whether or not the dispatch picks it: no instantiation in spmm.hip may.
-    # The code object's metadata lists every kernel with its private segment (scratch) size per lane.
+def spmm_code_object_notes(tmp_path):
+    """The metadata notes of spmm.o's gfx950 code object: every kernel with its resource usage."""
     import subprocess
     llvm = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin")
     obj = os.path.join(ROOT, "icebin_amd", "lib", "spmm.o")
@@ -121,9 +120,53 @@ def test_no_apply_kernel_uses_scratch_memory(lib, tmp_path):
     subprocess.run([os.path.join(llvm, "llvm-objcopy"), "--dump-section=.hip_fatbin=" + fatbin, obj, str(tmp_path / "host.o")], check=True)
     subprocess.run([os.path.join(llvm, "clang-offload-bundler"), "--unbundle", "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950",
                     "--input=" + fatbin, "--output=" + dev], check=True)
-    notes = subprocess.run([os.path.join(llvm, "llvm-readelf"), "--notes", dev], check=True, capture_output=True, text=True).stdout
+    return subprocess.run([os.path.join(llvm, "llvm-readelf"), "--notes", dev], check=True, capture_output=True, text=True).stdout
+
+
+def test_no_apply_kernel_uses_scratch_memory(lib, tmp_path):
+    # a kernel that spills registers to scratch is slow whether or not the dispatch picks it: no instantiation in spmm.hip may.
+    # The code object's metadata lists every kernel with its private segment (scratch) size per lane.
+    notes = spmm_code_object_notes(tmp_path)
     names = re.findall(r"^    \.name:\s+(\S+)", notes, re.M)
     sizes = [int(s) for s in re.findall(r"^    \.private_segment_fixed_size:\s+(\d+)", notes, re.M)]
     assert len(names) == len(sizes) and len(names) > 100, (len(names), len(sizes))
     spilling = [(n, s) for n, s in zip(names, sizes) if s != 0]
     assert not spilling, spilling
+
+
+def demangle_template_args(mangled):
+    """"_ZN3ibh20spmm_rowone_kernelILi8ELi14EEEvPKiS2_..." -> ("spmm_rowone_kernel", "<8, 14>"): the integer and bool template
+    arguments of a kernel in namespace ibh, spelled as the demangler (and ibh_weighted_last_launch) spells them."""
+    m = re.match(r"_ZN3ibh(\d+)", mangled)
+    if not m:
+        return None
+    n = int(m.group(1))
+    start = m.end()
+    name, rest = mangled[start:start + n], mangled[start + n:]
+    if not rest.startswith("I"):
+        return None
+    args = []
+    for a in re.finditer(r"L([ib])(n?\d+)E", rest[1:rest.index("EE") + 2]):
+        kind, v = a.group(1), a.group(2).replace("n", "-")
+        args.append(("true" if v == "1" else "false") if kind == "b" else v)
+    return name, "<" + ", ".join(args) + ">"
+
+
+def test_every_apply_kernel_has_a_recipe(lib, tmp_path):
+    # tests/apply_kernel_recipes.py holds one recipe per apply-kernel instantiation (tests/test_gpu_apply_kernels.py runs them all
+    # against an exact reference): a kernel instantiated without a recipe, or a recipe for a kernel no longer built, fails here
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    try:
+        import apply_kernel_recipes as akr
+    finally:
+        sys.path.pop(0)
+    notes = spmm_code_object_notes(tmp_path)
+    built = set()
+    for mangled in re.findall(r"^    \.name:\s+(\S+)", notes, re.M):
+        d = demangle_template_args(mangled)
+        if d and re.fullmatch(r"spmm_\w+_kernel", d[0]):
+            built.add(d[0] + d[1])
+    recipes = {r["name"] for r in akr.RECIPES}
+    assert built == recipes, ("built without a recipe", sorted(built - recipes), "recipe without a kernel", sorted(recipes - built))
+    print("%d apply-kernel instantiations, one recipe each" % len(built))
