@@ -33,8 +33,8 @@ def _stale(target, deps):
 
 
 def build_library(force=False, verbose=False, variant=None, extra_flags=()):
-    """variant/extra_flags: experiment builds (scratch/), e.g. variant="fatl", extra_flags=["-DFA_TIMELINE"]
-    -> lib/libicebin_hip_fatl.so, loaded with ICEBIN_HIP_LIB=<path>.  The product build takes neither."""
+    """variant/extra_flags: experiment builds (scratch/), e.g. variant="dbg", extra_flags=["-DMY_EXPERIMENT"]
+    -> lib/libicebin_hip_dbg.so, loaded with ICEBIN_HIP_LIB=<path>.  The product build takes neither."""
     os.makedirs(LIBDIR, exist_ok=True)
     hdrs = [os.path.join(CSRC, h) for h in HEADERS]
     objs, jobs = [], []

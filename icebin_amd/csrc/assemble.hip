@@ -61,6 +61,19 @@ static const MatSpec SPECS[] = {
     {"EvA", FAM_EVA,  LIST_EP, KEY_E, LIST_AP, KEY_A, TERM_E_A,     LIST_AP, 2},
     {"AvE", FAM_EVA,  LIST_AP, KEY_A, LIST_EP, KEY_E, TERM_A_E,     LIST_AP, 2},
 };
+// the sparse extent of a key's index space
+static int64_t key_extent(const ibh_regridder *g, int key) {
+    return key == KEY_A ? g->nA : key == KEY_E ? g->nA * (int64_t)g->nhc : key == KEY_I ? g->nI : g->nX;
+}
+// the elevation of exchange cell x's ice cell lies outside hcdefs: the message of linterp_1d_b, IceRegridder_L0.cpp:84-85
+[[noreturn]] static void fail_elevation_range(const ibh_regrid_matrices *rm, uint32_t x) {
+    const ibh_regridder *g = rm->rg;
+    int32_t ij[2];
+    IBH_HIP(hipMemcpy(ij, g->ex_indices.p + 2 * (size_t)x, sizeof(ij), hipMemcpyDeviceToHost));
+    double e = 0;
+    IBH_HIP(hipMemcpy(&e, rm->elevmaskI.p + ij[1], sizeof(double), hipMemcpyDeviceToHost));
+    fail(IBH_ERANGE, "Elevation %g out of bounds (%g, %g)", e < 0 ? 0.0 : e, g->hcdefs_h.front(), g->hcdefs_h.back());
+}
 
 struct RgView {
     const int32_t *exi;
@@ -862,7 +875,7 @@ static void build_csr_from_contributions(ibh_weighted *w, Triplets t, int nrow, 
     // (measured: always for ~1 contribution per row; with 2+ per row -- IvE -- only while the build is
     // launch-bound, at 35 M contributions the radix passes are cheaper than the per-row selection)
     if (!expect_local && nrow > 0 && t.n <= 8 * (size_t)nrow && (2 * t.n <= 3 * (size_t)nrow || t.n < (4u << 20)) &&
-        get_tuning("assemble_short_rows", 1) && build_csr_short_rows(w, t, nrow, ncol, row_out, st))
+        build_csr_short_rows(w, t, nrow, ncol, row_out, st))
         return;
     // Order analysis + piece sort, then (speculatively, on the data as it stands) the duplicate
     // flags and their scan: ONE host synchronisation returns both the analysis and nnz.  Only when a
@@ -2093,7 +2106,7 @@ bool build_groups_from_csr(const ibh_weighted *cw, hipStream_t st) {
     w->grp_col = std::move(it_col); w->grp_meta = std::move(it_meta); w->grp_v0 = std::move(it_v0); w->grp_v1 = std::move(it_v1);
     w->grp_nslot = maxns; w->grp_nitems = (int32_t)nitems;
     w->grp_n = ngrp;
-    if (get_tuning("grouptile_build", 1)) build_group_tiles(w, w->grp_ptr.p, ngrp, w->grp_col.p, w->grp_meta.p, w->grp_v0.p, w->grp_v1.p, nitems, st);
+    build_group_tiles(w, w->grp_ptr.p, ngrp, w->grp_col.p, w->grp_meta.p, w->grp_v0.p, w->grp_v1.p, nitems, st);
     return true;
 }
 
@@ -2148,9 +2161,6 @@ bool assemble_matrix(const ibh_regrid_matrices *rm, const char *spec_name, ibh_s
         w->band_eligible = 1; w->band_sA = g->hc_stride_A; w->band_sHC = g->hc_stride_HC;
     }
 
-    auto extent_of = [&](int key) -> int64_t {
-        return key == KEY_A ? g->nA : key == KEY_E ? g->nA * (int64_t)g->nhc : key == KEY_I ? g->nI : g->nX;
-    };
     // sorted exchange grid + dims shapes it covers: the plan-based fast path (fastasm.inl); smoothing and the
     // band structure work on intermediates of the general pipeline
     const bool bands_wanted = sp->row_key == KEY_E && (sp->col_key == KEY_I || sp->col_key == KEY_X) && get_tuning("assemble_bands", 0);
@@ -2167,7 +2177,7 @@ bool assemble_matrix(const ibh_regrid_matrices *rm, const char *spec_name, ibh_s
     // counters read back with ONE sync: [0] first out-of-range exchange cell, [1] new row keys,
     // [2] new column keys, [3] number of contributions
     // [first(rows) | first(cols) | counters] are one allocation, preset to 0xFF.. with one fill
-    const size_t er = (size_t)extent_of(sp->row_key), ec = (size_t)extent_of(sp->col_key);
+    const size_t er = (size_t)key_extent(g, sp->row_key), ec = (size_t)key_extent(g, sp->col_key);
     uint32_t *first_r = A.get<uint32_t>(er + ec + 4), *first_c = first_r + er;
     uint32_t *d_cnt = first_c + ec;
     uint32_t *d_err = d_cnt;
@@ -2176,9 +2186,9 @@ bool assemble_matrix(const ibh_regrid_matrices *rm, const char *spec_name, ibh_s
 
     // dense numbering in emission order; each user-visible set is numbered by exactly one Ur matrix
     // (RegridMatrices_Dynamic.cpp:75-81, 86-90, 178-183, 187-190, 270-277), so the two are independent.
-    Numbering rnum = number_set_prepare(rg, dims[0], extent_of(sp->row_key), sp->row_list, sp->row_key,
+    Numbering rnum = number_set_prepare(rg, dims[0], key_extent(g, sp->row_key), sp->row_list, sp->row_key,
                                         (sp->row_list == LIST_EP ? 2 : 1) * g->nX, 0, first_r, st);
-    Numbering cnum = number_set_prepare(rg, dims[1], extent_of(sp->col_key), sp->col_list, sp->col_key,
+    Numbering cnum = number_set_prepare(rg, dims[1], key_extent(g, sp->col_key), sp->col_list, sp->col_key,
                                         (sp->col_list == LIST_EP ? 2 : 1) * g->nX, 2, first_c, st);
     const int T = 256;
     const dim3 grid(g->nX ? ceil_div(g->nX, T) : 1);
@@ -2195,15 +2205,7 @@ bool assemble_matrix(const ibh_regrid_matrices *rm, const char *spec_name, ibh_s
     exclusive_scan3(pk, (size_t)g->nX, roff, coff, poff, d_cnt + 1, st);
     uint32_t h_cnt[4];
     readback_sync(h_cnt, d_cnt, sizeof(h_cnt), st);
-    const uint32_t err_x = h_cnt[0];
-    if (err_x != big) {
-        // message of linterp_1d_b, IceRegridder_L0.cpp:84-85
-        std::vector<int32_t> ij(2);
-        IBH_HIP(hipMemcpy(ij.data(), g->ex_indices.p + 2 * (size_t)err_x, 2 * sizeof(int32_t), hipMemcpyDeviceToHost));
-        double e = 0;
-        IBH_HIP(hipMemcpy(&e, rm->elevmaskI.p + ij[1], sizeof(double), hipMemcpyDeviceToHost));
-        fail(IBH_ERANGE, "Elevation %g out of bounds (%g, %g)", e < 0 ? 0.0 : e, g->hcdefs_h.front(), g->hcdefs_h.back());
-    }
+    if (h_cnt[0] != big) fail_elevation_range(rm, h_cnt[0]);
     for (Numbering *nb : {&rnum, &cnum}) {
         const uint32_t n_new = nb == &rnum ? h_cnt[1] : h_cnt[2];
         IBH_CHECK((int64_t)n_new <= nb->max_new, "internal: more new keys (%u) than reserved (%ld)", n_new, (long)nb->max_new);
@@ -2369,12 +2371,9 @@ void assemble_batch(const ibh_regrid_matrices *rm, int n, const char *const *spe
         out[j] = nullptr;
     }
     const ibh_regridder *g = rm->rg;
-    auto extent_of = [&](int key) -> int64_t {
-        return key == KEY_A ? g->nA : key == KEY_E ? g->nA * (int64_t)g->nhc : key == KEY_I ? g->nI : g->nX;
-    };
     auto readonly = [&](const Job &jb, int k) {          // a set no build ever changes: the identity over its whole extent
         const ibh_sparse_set *s = jb.d[k];
-        return s && s->identity && s->n == extent_of(k == 0 ? jb.sp->row_key : jb.sp->col_key);
+        return s && s->identity && s->n == key_extent(g, k == 0 ? jb.sp->row_key : jb.sp->col_key);
     };
     // wave of a job: one after the PRODUCER of each of its sets -- the first job of the batch that uses a set which is
     // still empty numbers it; the later users of that set only read it (fast path) and do not wait for each other

@@ -905,9 +905,6 @@ struct FaOut {
     // neither fills the chip, and a launch of its own costs what the work does)
     int psums_first;
     long psums_n;
-#ifdef FA_TIMELINE
-    long long *dbg;                 // scratch/r05/range_timeline.py: 8 stamps per range from thread 0
-#endif
 };
 __device__ __forceinline__ void fa_publish(const FaOut &o) {
     if (!o.pub_ticket) return;                                  // (uniform)
@@ -924,11 +921,6 @@ __device__ __forceinline__ void fa_publish(const FaOut &o) {
         }
     }
 }
-#ifdef FA_TIMELINE
-#define FA_STAMP(i) do { if (tid == 0) { tl[i] = (long long)__builtin_amdgcn_s_memtime(); } } while (0)
-#else
-#define FA_STAMP(i) do { } while (0)
-#endif
 // Mw of the ice cells with several exchange cells (k_fa_pelem<SUMS>'s job), EIGHT lanes per ice cell: every lane evaluates one of
 // the cell's <= 8 exchange cells, lane 0 of the group then adds the terms in the element's order (cells ascending, the two classes
 // of a cell by their dense ids) -- the same sequence of additions.  One thread per ice cell walked its cells one after the other,
@@ -1012,10 +1004,6 @@ __global__ __launch_bounds__(T, (T == 128 && !WITH_EP) ? 6 : 1) void k_fa_range(
         return;
     }
     const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-#ifdef FA_TIMELINE
-    long long tl[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#endif
-    FA_STAMP(0);
     const long x0 = pl.arng[r], x1 = pl.arng[r + 1];
     const int iA_r = rg.exi[2 * x0];                          // the atmosphere cell of the whole range
     const uint32_t eb = g.ebase[r];
@@ -1044,7 +1032,6 @@ __global__ __launch_bounds__(T, (T == 128 && !WITH_EP) ? 6 : 1) void k_fa_range(
     // values go to memory from here only when nothing later writes them: rows that are scaled are written once, scaled; the
     // terms of the column sums (SUMS: o.val is scratch) are not needed in memory at all when the range is in LDS
     const bool wglobal = !fits || (EMIT && !o.scale);
-    FA_STAMP(1);
     // CPT cells per thread and pass: their loads are issued in three staged rounds (exchange cell -> mask and
     // first-seen position of its ice cell -> dense id) before anything is consumed, so a pass pays the dependent
     // round trips once instead of once per 256 cells; the ranking then walks the CPT sub-chunks in x order.
@@ -1083,9 +1070,6 @@ __global__ __launch_bounds__(T, (T == 128 && !WITH_EP) ? 6 : 1) void k_fa_range(
                 } else didv[u] = iIv[u];
             } else didv[u] = p.fresh ? (int)pov[u] : (int)(x < x1 ? x : x1 - 1);
         }
-#ifdef FA_TIMELINE
-        if (cb == x0 && tid == 0) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); tl[2] = (long long)__builtin_amdgcn_s_memtime(); }
-#endif
 #pragma unroll
         for (int u = 0; u < CPT; ++u) {
             const long x = cb + (long)u * T + tid;
@@ -1115,7 +1099,6 @@ __global__ __launch_bounds__(T, (T == 128 && !WITH_EP) ? 6 : 1) void k_fa_range(
                 }
             }
         }
-        if (cb == x0) FA_STAMP(3);
 #pragma unroll
         for (int u = 0; u < CPT; ++u) {
             if (cb + (long)u * T >= x1) break;          // uniform: this sub-chunk lies past the range
@@ -1191,7 +1174,6 @@ __global__ __launch_bounds__(T, (T == 128 && !WITH_EP) ? 6 : 1) void k_fa_range(
             __syncthreads();
         }
     }
-    FA_STAMP(4);
     const uint32_t no = s_no < (uint32_t)FA_OLDMAX ? s_no : (uint32_t)FA_OLDMAX;
     if (s_no > (uint32_t)FA_OLDMAX && tid == 0) atomicOr(flags, (uint32_t)FA_ERR_OLDOVER);
     for (uint32_t e = tid; e < no; e += T) {            // inside a class the old ids are distinct: rank by counting
@@ -1205,7 +1187,6 @@ __global__ __launch_bounds__(T, (T == 128 && !WITH_EP) ? 6 : 1) void k_fa_range(
     }
     __threadfence_block();
     __syncthreads();
-    FA_STAMP(5);
     // Sequential sums (the order of spsparse sum()), one WAVE per segment: 64 values are loaded coalesced and the
     // chain is replayed from registers with v_readlane (every lane computes the identical sum), as k_seg_sums_wave
     // does; then the weights (k_weights) and, for the rows, the scaling.
@@ -1277,7 +1258,6 @@ __global__ __launch_bounds__(T, (T == 128 && !WITH_EP) ? 6 : 1) void k_fa_range(
             }
         }
     }
-    FA_STAMP(6);
     if (EMIT && r == pl.nAr - 1 && tid == 0) o.rowptr[g.gbase[pl.nAr]] = (int32_t)g.ebase[pl.nAr];      // rowptr[nrow] = nnz
     if (EMIT && o.scale) {
         __syncthreads();
@@ -1288,13 +1268,6 @@ __global__ __launch_bounds__(T, (T == 128 && !WITH_EP) ? 6 : 1) void k_fa_range(
         }
     }
     fa_publish(o);
-#ifdef FA_TIMELINE
-    if (tid == 0 && o.dbg) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        tl[7] = (long long)__builtin_amdgcn_s_memtime();
-        for (int i = 0; i < 8; ++i) o.dbg[(size_t)r * 8 + i] = tl[i];
-    }
-#endif
 }
 
 // ---- one thread per P element (ice cell or exchange cell): its <= 8 entries --------------------------
@@ -1306,13 +1279,6 @@ template <bool WITH_EP, int MODE, bool ANYORDER>
 __device__ __forceinline__ void fa_pelem_body(RgView rg, const PlanView &pl, const MatSpec &s, const FaG &g, const FaP &p, int merge, long np, const FaOut &o,
                                               uint32_t *__restrict__ rowlen, uint32_t *__restrict__ flags, int only_multi) {
     __shared__ double s_hc[WITH_EP ? HC_LDS : 1];
-#ifdef FA_TIMELINE
-    const long wid_tl = ((long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    auto PSTAMP = [&](int i) { if (MODE == FA_PEMIT && o.dbg) { const long long t = (long long)__builtin_amdgcn_s_memtime(); o.dbg[wid_tl * 8 + i] = t; } };
-#else
-    auto PSTAMP = [&](int) {};
-#endif
-    PSTAMP(0);
     stage_hc<WITH_EP>(rg, s_hc);
     long q = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= np) return;
@@ -1337,7 +1303,6 @@ __device__ __forceinline__ void fa_pelem_body(RgView rg, const PlanView &pl, con
     }
     if (d < 0) return;
     (void)flags;
-    PSTAMP(1);
     if (MODE == FA_PCOUNT && p.key == KEY_I && pl.icnt_pos) {
         // entries of an ice cell's row: one per group of duplicate exchange cells that contributes, times the elevation
         // classes its elevation lies between -- the groups are static (plan), the classes a function of the mask value
@@ -1406,7 +1371,6 @@ __device__ __forceinline__ void fa_pelem_body(RgView rg, const PlanView &pl, con
         if (KEEP && ne < FA_KEEP) { s_kt[ne][threadIdx.x] = t; s_kid[ne][threadIdx.x] = id; s_ka[ne][threadIdx.x] = (int)iA; }
         ++ne; sum = sum + t; sorted = sorted && id >= prev; prev = id;
     });
-    PSTAMP(2);
     if (MODE == FA_PCOUNT) { rowlen[d] = (uint32_t)ne; return; }
     if (MODE == FA_PSUMS) { o.Mw[d] = sum; return; }          // FAM_AEVI: Mw = colsum (:100); G numbered by this build: in order
     // FAM_IVAE rows: wM = rowsum, M = [1/wM] * T [* sApvA]
@@ -1448,7 +1412,6 @@ __device__ __forceinline__ void fa_pelem_body(RgView rg, const PlanView &pl, con
             last = best;
         }
     }
-    PSTAMP(3);
 }
 template <bool WITH_EP, int MODE, bool ANYORDER>
 __global__ __launch_bounds__(FA_T, (WITH_EP && MODE == 2) ? (ANYORDER ? 1 : 6) : 8) void k_fa_pelem(RgView rg, PlanView pl, MatSpec s, FaG g, FaP p, int merge, long np, FaOut o,
@@ -1488,6 +1451,31 @@ static const int32_t *set_inverse_table(ibh_sparse_set *set, int64_t extent, hip
     set->tab_n = set->n; set->tab_extent = extent;
     return set->tab.p;
 }
+// A set numbered by this build (fresh) takes the dense -> sparse table the build wrote.  A set that is only read -- identity /
+// pre-populated -- may be shared by builds running concurrently in a batch: its extent is written only when it changes.
+static void commit_set(ibh_sparse_set *set, bool fresh, int64_t extent, DevBuf<int64_t> &table, int n) {
+    if (!fresh) {
+        if (set->sparse_extent != extent) set->sparse_extent = extent;
+        return;
+    }
+    set->sparse_extent = extent;
+    if (n == 0) return;
+    set->host.clear(); set->host_n = 0; set->inv.clear(); set->inv_n = 0;
+    set->dev = std::move(table);
+    set->dev_n = set->n = n;
+    set->identity = false;
+}
+// The two sides of a matrix of the G/P builds (every family but EvA): G = the A / E side, counted and numbered by the ranges;
+// P = the I / X side, an element of which sees at most a few exchange cells
+struct FaRoles {
+    bool g_is_row;                  // AvI, EvI, AvX, EvX: G is the row side
+    ibh_sparse_set *gset, *pset;
+    int gkey, glist, pkey, plist;
+    int64_t gext, pext;             // the sparse extents of the two keys
+    int pmode;                      // fa_pset_mode of the P set
+    bool g_fresh;                   // the G set is numbered by this build; else pre-populated (E columns)
+    int merge;                      // 1: neither side is X, entries of the same (G, P) pair merge
+};
 __global__ void k_fa_init(uint32_t *cnt) {
     if (threadIdx.x < 8) cnt[threadIdx.x] = threadIdx.x == 0 ? 0xffffffffu : 0u;
 }
@@ -1593,7 +1581,7 @@ static bool fast_build_eva(const ibh_regrid_matrices *rm, const MatSpec *sp, ibh
     const bool e_is_row = sp->row_key == KEY_E;
     ibh_sparse_set *eset = dims[e_is_row ? 0 : 1], *aset = dims[e_is_row ? 1 : 0];
     if (eset->n != 0 || aset->n != 0 || eset == aset) return false;
-    const int64_t extE = gr->nA * (int64_t)gr->nhc, extA = gr->nA;
+    const int64_t extE = key_extent(gr, KEY_E), extA = key_extent(gr, KEY_A);
     Arena &A = arena();
     A.reset();
     const ibh_plan &P = gr->plan;
@@ -1635,13 +1623,7 @@ static bool fast_build_eva(const ibh_regrid_matrices *rm, const MatSpec *sp, ibh
     uint32_t h[8];
     auto check_counters = [&]() -> bool {
         readback_sync(h, d_cnt, sizeof(h), st);
-        if (h[0] != 0xffffffffu) {                              // message of linterp_1d_b, IceRegridder_L0.cpp:84-85
-            int32_t ij[2];
-            IBH_HIP(hipMemcpy(ij, gr->ex_indices.p + 2 * (size_t)h[0], sizeof(ij), hipMemcpyDeviceToHost));
-            double e = 0;
-            IBH_HIP(hipMemcpy(&e, rm->elevmaskI.p + ij[1], sizeof(double), hipMemcpyDeviceToHost));
-            fail(IBH_ERANGE, "Elevation %g out of bounds (%g, %g)", e < 0 ? 0.0 : e, gr->hcdefs_h.front(), gr->hcdefs_h.back());
-        }
+        if (h[0] != 0xffffffffu) fail_elevation_range(rm, h[0]);
         return h[1] == 0;
     };
     if (!check_counters()) return false;
@@ -1680,16 +1662,8 @@ static bool fast_build_eva(const ibh_regrid_matrices *rm, const MatSpec *sp, ibh
             hipLaunchKernelGGL(k_scale, dim3(ceil_div(nnz, T)), dim3(T), 0, st, row, w->colind.p, w->val.p, nnz, rowmul, colmul, scale ? 1 : 0, correctA ? 1 : 0);
         IBH_HIP(hipGetLastError());
     }
-    auto commit = [&](ibh_sparse_set *set, int64_t extent, DevBuf<int64_t> &table, int n) {
-        set->sparse_extent = extent;
-        if (n == 0) return;
-        set->host.clear(); set->host_n = 0; set->inv.clear(); set->inv_n = 0;
-        set->dev = std::move(table);
-        set->dev_n = set->n = n;
-        set->identity = false;
-    };
-    commit(eset, extE, etable, nE);
-    commit(aset, extA, atable, nA);
+    commit_set(eset, true, extE, etable, nE);
+    commit_set(aset, true, extA, atable, nA);
     IBH_HIP(hipStreamSynchronize(st));
     return true;
 }
@@ -1700,13 +1674,13 @@ static void fast_prewarm(const ibh_regrid_matrices *rm, const MatSpec *sp, ibh_s
     const ibh_regridder *gr = rm->rg;
     if (!get_tuning("assemble_fast", 1) || !ensure_plan(gr, st)) return;
     if (sp->family != FAM_IVAE || !dims[1] || dims[1]->n == 0 || dims[1]->identity || sp->col_key != KEY_E) return;
-    (void)set_inverse_table(dims[1], gr->nA * (int64_t)gr->nhc, st);
+    (void)set_inverse_table(dims[1], key_extent(gr, KEY_E), st);
     IBH_HIP(hipStreamSynchronize(st));
 }
 
-static bool stream_build(const ibh_regrid_matrices *rm, const MatSpec *sp, ibh_sparse_set *dims[2], int scale, int correctA,
+template <bool EP>
+static bool stream_build(const ibh_regrid_matrices *rm, const MatSpec *sp, const FaRoles &role, int scale, int correctA,
                          const RgView &rg, ibh_weighted *w, hipStream_t st, ibh_comm *comm);          // streamasm.inl
-// the first exchange cell of every range on the host (the sharded build deals ranges to ranks), copied once per plan
 // Per host thread (a thread's builds run one after the other on its stream): the status words of the chained scans and a ring of
 // counter slots {0xffffffff, 0, ...}.  The words carry a 4-bit epoch, so they are cleared every 15 builds; the ring is
 // initialised again when it has gone round (both stream-ordered, both amortised to nothing).
@@ -1765,6 +1739,7 @@ struct FaChainState {
 };
 static FaChainState &fa_chain_state() { static thread_local FaChainState s; return s; }
 
+// the first exchange cell of every range on the host (the sharded build deals ranges to ranks), copied once per plan
 static const std::vector<int32_t> &plan_arng_host(const ibh_regridder *g) {
     static std::mutex mu;
     std::lock_guard<std::mutex> lk(mu);
@@ -1775,30 +1750,17 @@ static const std::vector<int32_t> &plan_arng_host(const ibh_regridder *g) {
     }
     return P.arng_h;
 }
-// returns false when the fast path does not apply (nothing has been touched: the caller runs the general pipeline)
-static bool fast_build(const ibh_regrid_matrices *rm, const MatSpec *sp, ibh_sparse_set *dims[2], int scale, int correctA,
-                       const RgView &rg, ibh_weighted *w, hipStream_t st, ibh_comm *comm = nullptr) {
+// EP: the matrix has elevation-class entries (LIST_EP on one side)
+template <bool EP>
+static bool fast_build_gp(const ibh_regrid_matrices *rm, const MatSpec *sp, const FaRoles &role, int scale, int correctA,
+                          const RgView &rg, ibh_weighted *w, hipStream_t st, ibh_comm *comm) {
     const ibh_regridder *gr = rm->rg;
-    if (!get_tuning("assemble_fast", 1)) return false;
-    if (!ensure_plan(gr, st)) return false;
-    if (sp->family == FAM_EVA) return get_tuning("assemble_fast_eva", 1) && fast_build_eva(rm, sp, dims, scale, correctA, rg, w, st);
     // the sharded build; when it does not apply (the same on every rank: static conditions, exchanged flags) the ranks go on
     // to build the matrix redundantly
-    if (comm && comm_world(comm) > 1 && stream_build(rm, sp, dims, scale, correctA, rg, w, st, comm)) return true;
-    if (stream_build(rm, sp, dims, scale, correctA, rg, w, st, nullptr)) return true;       // large grids: the streamed build
-    const bool g_is_row = sp->family == FAM_AEVI;
-    ibh_sparse_set *gset = dims[g_is_row ? 0 : 1], *pset = dims[g_is_row ? 1 : 0];
-    const int gkey = g_is_row ? sp->row_key : sp->col_key, glist = g_is_row ? sp->row_list : sp->col_list;
-    const int pkey = g_is_row ? sp->col_key : sp->row_key, plist = g_is_row ? sp->col_list : sp->row_list;
-    auto extent_of = [&](int key) -> int64_t {
-        return key == KEY_A ? gr->nA : key == KEY_E ? gr->nA * (int64_t)gr->nhc : key == KEY_I ? gr->nI : gr->nX;
-    };
-    const int pmode = fa_pset_mode(pset, extent_of(pkey));
-    if (pmode < 0) return false;
-    const bool g_fresh = gset->n == 0;
-    if (!g_fresh && (gset->identity || gkey != KEY_E || g_is_row)) return false;      // pre-populated: E columns only
-    const bool uses_ep = sp->row_list == LIST_EP || sp->col_list == LIST_EP;
-    const int merge = (sp->row_key != KEY_X && sp->col_key != KEY_X) ? 1 : 0;
+    if (comm && comm_world(comm) > 1 && stream_build<EP>(rm, sp, role, scale, correctA, rg, w, st, comm)) return true;
+    if (stream_build<EP>(rm, sp, role, scale, correctA, rg, w, st, nullptr)) return true;       // large grids: the streamed build
+    const bool g_is_row = role.g_is_row, g_fresh = role.g_fresh;
+    const int merge = role.merge;
 
     Arena &A = arena();
     A.reset();
@@ -1808,21 +1770,20 @@ static bool fast_build(const ibh_regrid_matrices *rm, const MatSpec *sp, ibh_spa
     const long nX = gr->nX;
     const int T = FA_T, nAr = P.nAr;
     FaG g{};
-    g.key = gkey; g.list = glist; g.NC = gkey == KEY_E ? gr->nhc : 1;
+    g.key = role.gkey; g.list = role.glist; g.NC = role.gkey == KEY_E ? gr->nhc : 1;
     const size_t nrc = (size_t)nAr * g.NC;
     g.erank = A.get<int8_t>(nrc); g.ecntn = A.get<uint32_t>(nrc); g.ecnto = A.get<uint32_t>(nrc);
     g.r_ncls = A.get<uint32_t>((size_t)nAr); g.r_nent = A.get<uint32_t>((size_t)nAr);
     g.gbase = A.get<uint32_t>((size_t)nAr + 1); g.ebase = A.get<uint32_t>((size_t)nAr + 1);
-    const int64_t gext = extent_of(gkey);
-    if (!g_fresh) g.tab = set_inverse_table(gset, gext, st);
+    if (!g_fresh) g.tab = set_inverse_table(role.gset, role.gext, st);
     FaP p{};
-    p.key = pkey; p.list = plist; p.fresh = pmode;
+    p.key = role.pkey; p.list = role.plist; p.fresh = role.pmode;
     // counters read back with one sync: [0] first out-of-range cell, [1] fallback flags, [2] new P keys, [3] G classes, [4] entries
-    const bool stream_count = !uses_ep && g.NC == 1 && !g.tab && get_tuning("assemble_stream_count", nX >= (1l << 20) ? 1 : 0);
+    const bool stream_count = !EP && g.NC == 1 && !g.tab && get_tuning("assemble_stream_count", nX >= (1l << 20) ? 1 : 0);
     // small grids: the scans ride in the counting kernel (FaChain) and the counters come initialised from a ring of slots --
     // three launches fewer in a chain of seven to nine that is all a 5 km build costs
-    const bool optimistic = nX <= (1l << 20) && get_tuning("assemble_optimistic", 1);
-    const bool chained = optimistic && !stream_count && nrc < (1ul << FA_CH_NC) && get_tuning("assemble_chain", 1);
+    const bool optimistic = nX <= (1l << 20);
+    const bool chained = optimistic && !stream_count && nrc < (1ul << FA_CH_NC);
     FaChain chain{};
     uint32_t *d_cnt;
     uint32_t *rowlen_early = nullptr;
@@ -1832,21 +1793,21 @@ static bool fast_build(const ibh_regrid_matrices *rm, const MatSpec *sp, ibh_spa
         FaChainState &cs = fa_chain_state();
         d_cnt = cs.counters(st);
         // (row lengths of an I-row build on the identity ice set: counted and scanned by extra workgroups of the counting launch)
-        const bool pc = !g_is_row && pkey == KEY_I && !p.fresh && pl.icnt_pos && get_tuning("assemble_pcount_incount", 1);
-        const long pc_rows = pc ? (long)extent_of(pkey) : 0;
+        const bool pc = !g_is_row && role.pkey == KEY_I && !p.fresh && pl.icnt_pos;
+        const long pc_rows = pc ? (long)role.pext : 0;
         const int tshape_c = fa_shape == 0 ? 128 : fa_shape == 1 ? 256 : 1024;
         count_extra = pc ? ceil_div(pc_rows, tshape_c) : 0;
-        const bool ir = !g_is_row && pkey == KEY_I && p.fresh && pl.icnt_pos && get_tuning("assemble_irows_incount", 1);
+        const bool ir = !g_is_row && role.pkey == KEY_I && p.fresh && pl.icnt_pos;
         chain = FaChain{cs.words((size_t)nAr + (size_t)count_extra + (ir ? (size_t)nAr : 0), st), cs.epoch, d_cnt + 2, nullptr, 0u, nullptr, 0u, nullptr, 0u,
                         nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0l, 0, 0};
         if (ir) {                                               // (I rows on an ice set numbered by this build: the row pointer from the counting launch)
-            const size_t np_ub0 = (size_t)std::min<int64_t>(extent_of(pkey), nX);
+            const size_t np_ub0 = (size_t)std::min<int64_t>(role.pext, nX);
             w->rowptr.alloc(np_ub0 + 1);
             chain.ir_rowptr = reinterpret_cast<uint32_t *>(w->rowptr.p);
             chain.ir_tmp = A.get<uint32_t>((size_t)nX);
             chain.ir_status0 = nAr + count_extra;
         }
-        if (!g_is_row && pkey == KEY_X && !p.fresh && merge == 0 && get_tuning("assemble_xrows_incount", 1)) {
+        if (!g_is_row && role.pkey == KEY_X && !p.fresh && merge == 0) {
             // (X rows on the identity exchange-cell set: the row pointer falls out of the ranges' own look-back)
             w->rowptr.alloc((size_t)nX + 1);
             chain.xr_rowptr = reinterpret_cast<uint32_t *>(w->rowptr.p);
@@ -1855,20 +1816,20 @@ static bool fast_build(const ibh_regrid_matrices *rm, const MatSpec *sp, ibh_spa
             w->rowptr.alloc((size_t)pc_rows + 1);
             chain.pc_rowptr = reinterpret_cast<uint32_t *>(w->rowptr.p); chain.pc_n = pc_rows; chain.pc_first = nAr; chain.pc_status0 = nAr;
         }
-        if (!g_is_row && !g_fresh && gset->n > 0) {             // (what k_fa_zero_identity did in a launch of its own)
-            w->Mw.alloc((size_t)gset->n);
-            chain.zero2 = reinterpret_cast<uint32_t *>(w->Mw.p); chain.nzero2 = 2u * (unsigned)gset->n;
+        if (!g_is_row && !g_fresh && role.gset->n > 0) {           // (what k_fa_zero_identity did in a launch of its own)
+            w->Mw.alloc((size_t)role.gset->n);
+            chain.zero2 = reinterpret_cast<uint32_t *>(w->Mw.p); chain.nzero2 = 2u * (unsigned)role.gset->n;
         }
         // a fresh E set: the step's later builds (IvE, XvE on the dimE this EvI numbers: IceCoupler.cpp:361-377) look keys up in the
         // sparse -> dense table -- written here as the set is numbered instead of by two launches and a synchronisation later
-        if (g_fresh && gkey == KEY_E && gext < (1l << 22) && get_tuning("assemble_tab_out", 1)) {
-            gset->tab_n = -1;
-            gset->tab.alloc((size_t)gext);
-            chain.fill_m1 = gset->tab.p; chain.nfill = (unsigned)gext;
-            g.tab_out = gset->tab.p;
+        if (g_fresh && role.gkey == KEY_E && role.gext < (1l << 22)) {
+            role.gset->tab_n = -1;
+            role.gset->tab.alloc((size_t)role.gext);
+            chain.fill_m1 = role.gset->tab.p; chain.nfill = (unsigned)role.gext;
+            g.tab_out = role.gset->tab.p;
         }
         // what the later kernels want cleared, by the upper bounds the outputs are allocated with below
-        const size_t np_ub = p.fresh ? (size_t)std::min<int64_t>(extent_of(pkey), nX) : (size_t)extent_of(pkey);
+        const size_t np_ub = p.fresh ? (size_t)std::min<int64_t>(role.pext, nX) : (size_t)role.pext;
         if (g_is_row && !p.fresh && np_ub) {                    // Mw of an identity P set: members without entries stay 0
             w->Mw.alloc(np_ub);
             chain.zero = reinterpret_cast<uint32_t *>(w->Mw.p); chain.nzero = (unsigned)(2 * np_ub);
@@ -1887,8 +1848,7 @@ static bool fast_build(const ibh_regrid_matrices *rm, const MatSpec *sp, ibh_spa
         hipLaunchKernelGGL(k_fa_zero_counts, dim3(ceil_div(nAr, 256)), dim3(256), 0, st, g.r_ncls, g.ecntn, g.ecnto, nAr);
         hipLaunchKernelGGL(k_fa_count_stream<4>, dim3(ceil_div(nX, 1024)), dim3(256), 0, st, rg, pl, *sp, g, p, g_is_row ? 1 : 0, merge);
         hipLaunchKernelGGL(k_fa_count_fin, dim3(ceil_div(nAr, 256)), dim3(256), 0, st, g, nAr, d_cnt + 1);
-    } else if (uses_ep) FA_LAUNCH_COUNT(true, rg, pl, *sp, g, p, g_is_row ? 1 : 0, merge, d_cnt, d_cnt + 1, 0, chain);
-    else FA_LAUNCH_COUNT(false, rg, pl, *sp, g, p, g_is_row ? 1 : 0, merge, d_cnt, d_cnt + 1, 0, chain);
+    } else FA_LAUNCH_COUNT(EP, rg, pl, *sp, g, p, g_is_row ? 1 : 0, merge, d_cnt, d_cnt + 1, 0, chain);
     if (chained) {
         // (poff, gbase / ebase and the three totals were written by k_fa_count)
     } else if (p.fresh) exclusive_scan_u8(p.pflag, p.poff, (size_t)nX, d_cnt + 2, st);
@@ -1911,13 +1871,7 @@ static bool fast_build(const ibh_regrid_matrices *rm, const MatSpec *sp, ibh_spa
             IBH_HIP(hipStreamSynchronize(st));
             std::memcpy(h, fa_chain_state().h_cnt, sizeof(h));
         } else readback_sync(h, d_cnt, sizeof(h), st);
-        if (h[0] != 0xffffffffu) {                              // message of linterp_1d_b, IceRegridder_L0.cpp:84-85
-            int32_t ij[2];
-            IBH_HIP(hipMemcpy(ij, gr->ex_indices.p + 2 * (size_t)h[0], sizeof(ij), hipMemcpyDeviceToHost));
-            double e = 0;
-            IBH_HIP(hipMemcpy(&e, rm->elevmaskI.p + ij[1], sizeof(double), hipMemcpyDeviceToHost));
-            fail(IBH_ERANGE, "Elevation %g out of bounds (%g, %g)", e < 0 ? 0.0 : e, gr->hcdefs_h.front(), gr->hcdefs_h.back());
-        }
+        if (h[0] != 0xffffffffu) fail_elevation_range(rm, h[0]);
         if (h[1]) return false;                                 // a limit of the fast path was hit: general pipeline
         IBH_CHECK(h[4] < (1u << 31) && h[2] < (1u << 31), "matrix too large for int32 indices");
         return true;
@@ -1926,11 +1880,11 @@ static bool fast_build(const ibh_regrid_matrices *rm, const MatSpec *sp, ibh_spa
     // (<= 2 entries per exchange cell, <= NC rows per range) so that the counters are read back ONCE, with the final
     // synchronisation; large grids read them here and allocate exactly.
     if (!optimistic && !check_counters()) return false;
-    const uint32_t n_pnew = optimistic ? (uint32_t)std::min<int64_t>(extent_of(pkey), nX) : h[2];
+    const uint32_t n_pnew = optimistic ? (uint32_t)std::min<int64_t>(role.pext, nX) : h[2];
     const uint32_t n_g = optimistic ? (uint32_t)nrc : h[3];
-    const uint32_t nnz = optimistic ? (uint32_t)((uses_ep ? 2 : 1) * nX) : h[4];
-    int np_d = p.fresh ? (int)n_pnew : (int)extent_of(pkey);
-    int ng_d = g_fresh ? (int)n_g : gset->n;
+    const uint32_t nnz = optimistic ? (uint32_t)((EP ? 2 : 1) * nX) : h[4];
+    int np_d = p.fresh ? (int)n_pnew : (int)role.pext;
+    int ng_d = g_fresh ? (int)n_g : role.gset->n;
     // dims tables of the sets numbered by this build are written straight into the sets' device buffers
     DevBuf<int64_t> ptable, gtable;
     if (p.fresh) { ptable.alloc((size_t)np_d); p.to_sparse = ptable.p; }
@@ -1940,11 +1894,7 @@ static bool fast_build(const ibh_regrid_matrices *rm, const MatSpec *sp, ibh_spa
     w->rowptr.alloc((size_t)nrow + 1); w->colind.alloc(nnz); w->val.alloc(nnz);
     w->wM.alloc((size_t)nrow); w->Mw.alloc((size_t)ncol);
     FaOut o{w->rowptr.p, w->colind.p, w->val.p, w->wM.p, w->Mw.p, sp->family, scale, correctA, 0};
-#ifdef FA_TIMELINE
-    o.dbg = reinterpret_cast<long long *>(((unsigned long long)(unsigned)get_tuning("gt_dbg_hi", 0) << 32) | (unsigned)get_tuning("gt_dbg_lo", 0));
-#endif
     uint32_t *flags = d_cnt + 1;
-    const bool can_publish = chained && get_tuning("assemble_publish", 1);     // (chained => optimistic: the counters are read once, at the end)
     int range_extra = 0;                                        // workgroups of k_fa_range that do k_fa_psums8's work
     const long np_s = p.key == KEY_I ? gr->nI : nX;             // P elements by sparse index
     const dim3 gp(ceil_div(np_s, T));
@@ -1955,25 +1905,23 @@ static bool fast_build(const ibh_regrid_matrices *rm, const MatSpec *sp, ibh_spa
         if (ncol && !p.fresh && !chain.zero) IBH_HIP(hipMemsetAsync(w->Mw.p, 0, sizeof(double) * (size_t)ncol, st));
         bool sums_after = p.key == KEY_I && P.nmulti;
         FaOut ol = o;                                         // (the build's last kernel publishes the counters)
-        if (can_publish) { fa_chain_state().publish_into(ol, d_cnt, st); published = true; }
-        if (sums_after && chained && P.nmulti <= (1l << 20) && get_tuning("assemble_psums8", 1) && get_tuning("assemble_psums_inrange", 1)) {
+        // (chained => optimistic: the counters are read once, at the end)
+        if (chained) { fa_chain_state().publish_into(ol, d_cnt, st); published = true; }
+        if (sums_after && chained && P.nmulti <= (1l << 20)) {
             // small grids: the straddlers' Mw in extra workgroups of the range kernel's own launch
             const int tshape = fa_shape == 0 ? 128 : fa_shape == 1 ? 256 : 1024;
             range_extra = ceil_div(8 * (long)P.nmulti, tshape);
             ol.psums_first = nAr; ol.psums_n = (long)P.nmulti;
             sums_after = false;
         }
-        if (uses_ep) FA_LAUNCH_RANGE(true, true, rg, pl, *sp, g, p, merge, (sums_after ? o : ol), flags);
-        else FA_LAUNCH_RANGE(false, true, rg, pl, *sp, g, p, merge, (sums_after ? o : ol), flags);
+        FA_LAUNCH_RANGE(EP, true, rg, pl, *sp, g, p, merge, (sums_after ? o : ol), flags);
         range_extra = 0;
         if (sums_after) {                                     // Mw of the ice cells that straddle ranges (a few %)
             const dim3 gm(ceil_div(P.nmulti, T));
-            if (P.nmulti <= (1l << 20) && get_tuning("assemble_psums8", 1)) {     // few of them: eight lanes per ice cell
+            if (P.nmulti <= (1l << 20)) {                      // few of them: eight lanes per ice cell
                 const dim3 g8(ceil_div(8 * (long)P.nmulti, T));
-                if (uses_ep) hipLaunchKernelGGL((k_fa_psums8<true>), g8, dim3(T), 0, st, rg, pl, *sp, g, p, merge, (long)P.nmulti, ol);
-                else hipLaunchKernelGGL((k_fa_psums8<false>), g8, dim3(T), 0, st, rg, pl, *sp, g, p, merge, (long)P.nmulti, ol);
-            } else if (uses_ep) hipLaunchKernelGGL((k_fa_pelem<true, FA_PSUMS, false>), gm, dim3(T), 0, st, rg, pl, *sp, g, p, merge, (long)P.nmulti, ol, (uint32_t *)nullptr, flags, 0);
-            else hipLaunchKernelGGL((k_fa_pelem<false, FA_PSUMS, false>), gm, dim3(T), 0, st, rg, pl, *sp, g, p, merge, (long)P.nmulti, ol, (uint32_t *)nullptr, flags, 0);
+                hipLaunchKernelGGL((k_fa_psums8<EP>), g8, dim3(T), 0, st, rg, pl, *sp, g, p, merge, (long)P.nmulti, ol);
+            } else hipLaunchKernelGGL((k_fa_pelem<EP, FA_PSUMS, false>), gm, dim3(T), 0, st, rg, pl, *sp, g, p, merge, (long)P.nmulti, ol, (uint32_t *)nullptr, flags, 0);
         }
     } else {
         // rows = P: count -> scan -> emit per element; Mw (G columns) from the ranges through a scratch copy of the terms
@@ -1981,23 +1929,16 @@ static bool fast_build(const ibh_regrid_matrices *rm, const MatSpec *sp, ibh_spa
         if (optimistic && p.fresh && !rowlen_early) IBH_HIP(hipMemsetAsync(rowlen, 0, sizeof(uint32_t) * ((size_t)nrow + 1), st));   // rows beyond the real count
         if (pcount_done) {
             // (the row lengths were counted by extra workgroups of k_fa_count's launch)
-        } else if (uses_ep) hipLaunchKernelGGL((k_fa_pelem<true, FA_PCOUNT, false>), gp, dim3(T), 0, st, rg, pl, *sp, g, p, merge, np_s, o, rowlen, flags, 0);
-        else hipLaunchKernelGGL((k_fa_pelem<false, FA_PCOUNT, false>), gp, dim3(T), 0, st, rg, pl, *sp, g, p, merge, np_s, o, rowlen, flags, 0);
+        } else hipLaunchKernelGGL((k_fa_pelem<EP, FA_PCOUNT, false>), gp, dim3(T), 0, st, rg, pl, *sp, g, p, merge, np_s, o, rowlen, flags, 0);
         if (!pcount_done) exclusive_scan_u32(rowlen, reinterpret_cast<uint32_t *>(w->rowptr.p), (size_t)nrow, reinterpret_cast<uint32_t *>(w->rowptr.p) + nrow, st);
         // (a pre-populated G set may list the columns in another order: the variant with the per-row selection branch)
-        if (!g_fresh) {
-            if (uses_ep) hipLaunchKernelGGL((k_fa_pelem<true, FA_PEMIT, true>), gp, dim3(T), 0, st, rg, pl, *sp, g, p, merge, np_s, o, rowlen, flags, 0);
-            else hipLaunchKernelGGL((k_fa_pelem<false, FA_PEMIT, true>), gp, dim3(T), 0, st, rg, pl, *sp, g, p, merge, np_s, o, rowlen, flags, 0);
-        } else {
-            if (uses_ep) hipLaunchKernelGGL((k_fa_pelem<true, FA_PEMIT, false>), gp, dim3(T), 0, st, rg, pl, *sp, g, p, merge, np_s, o, rowlen, flags, 0);
-            else hipLaunchKernelGGL((k_fa_pelem<false, FA_PEMIT, false>), gp, dim3(T), 0, st, rg, pl, *sp, g, p, merge, np_s, o, rowlen, flags, 0);
-        }
+        if (!g_fresh) hipLaunchKernelGGL((k_fa_pelem<EP, FA_PEMIT, true>), gp, dim3(T), 0, st, rg, pl, *sp, g, p, merge, np_s, o, rowlen, flags, 0);
+        else hipLaunchKernelGGL((k_fa_pelem<EP, FA_PEMIT, false>), gp, dim3(T), 0, st, rg, pl, *sp, g, p, merge, np_s, o, rowlen, flags, 0);
         FaOut os = o;
         os.val = A.get<double>(nnz);
-        if (can_publish) { fa_chain_state().publish_into(os, d_cnt, st); published = true; }
+        if (chained) { fa_chain_state().publish_into(os, d_cnt, st); published = true; }
         if (!g_fresh && ncol && !chain.zero2) hipLaunchKernelGGL(k_fa_zero_identity, dim3(ceil_div(ncol, T)), dim3(T), 0, st, w->Mw.p, (long)ncol);   // columns of the shared set this mask does not touch
-        if (uses_ep) FA_LAUNCH_RANGE(true, false, rg, pl, *sp, g, p, merge, os, flags);
-        else FA_LAUNCH_RANGE(false, false, rg, pl, *sp, g, p, merge, os, flags);
+        FA_LAUNCH_RANGE(EP, false, rg, pl, *sp, g, p, merge, os, flags);
     }
     IBH_HIP(hipGetLastError());
     if (optimistic) {                                           // the one read-back of a small build: flags and the real sizes
@@ -2009,19 +1950,30 @@ static bool fast_build(const ibh_regrid_matrices *rm, const MatSpec *sp, ibh_spa
         w->wM.n = (size_t)w->nrow; w->Mw.n = (size_t)w->ncol;
         ptable.n = p.fresh ? (size_t)np_d : 0; gtable.n = g_fresh ? (size_t)ng_d : 0;
     }
-    auto commit = [&](ibh_sparse_set *set, int64_t extent, DevBuf<int64_t> &table, int n) {
-        set->sparse_extent = extent;
-        if (n == 0) return;
-        set->host.clear(); set->host_n = 0; set->inv.clear(); set->inv_n = 0;
-        set->dev = std::move(table);
-        set->dev_n = set->n = n;
-        set->identity = false;
-    };
-    // (a set that is only read -- identity / pre-populated -- may be shared by builds running concurrently in a batch:
-    // its extent is written only when it changes)
-    if (p.fresh) commit(pset, extent_of(pkey), ptable, np_d); else if (pset->sparse_extent != extent_of(pkey)) pset->sparse_extent = extent_of(pkey);
-    if (g_fresh) commit(gset, gext, gtable, ng_d); else if (gset->sparse_extent != gext) gset->sparse_extent = gext;
-    if (g.tab_out) { gset->tab_n = gset->n; gset->tab_extent = gext; }
+    commit_set(role.pset, p.fresh, role.pext, ptable, np_d);
+    commit_set(role.gset, g_fresh, role.gext, gtable, ng_d);
+    if (g.tab_out) { role.gset->tab_n = role.gset->n; role.gset->tab_extent = role.gext; }
     IBH_HIP(hipStreamSynchronize(st));
     return true;
+}
+// returns false when the fast path does not apply (nothing has been touched: the caller runs the general pipeline)
+static bool fast_build(const ibh_regrid_matrices *rm, const MatSpec *sp, ibh_sparse_set *dims[2], int scale, int correctA,
+                       const RgView &rg, ibh_weighted *w, hipStream_t st, ibh_comm *comm = nullptr) {
+    const ibh_regridder *gr = rm->rg;
+    if (!get_tuning("assemble_fast", 1)) return false;
+    if (!ensure_plan(gr, st)) return false;
+    if (sp->family == FAM_EVA) return get_tuning("assemble_fast_eva", 1) && fast_build_eva(rm, sp, dims, scale, correctA, rg, w, st);
+    FaRoles role;
+    role.g_is_row = sp->family == FAM_AEVI;
+    role.gset = dims[role.g_is_row ? 0 : 1]; role.pset = dims[role.g_is_row ? 1 : 0];
+    role.gkey = role.g_is_row ? sp->row_key : sp->col_key; role.glist = role.g_is_row ? sp->row_list : sp->col_list;
+    role.pkey = role.g_is_row ? sp->col_key : sp->row_key; role.plist = role.g_is_row ? sp->col_list : sp->row_list;
+    role.gext = key_extent(gr, role.gkey); role.pext = key_extent(gr, role.pkey);
+    role.pmode = fa_pset_mode(role.pset, role.pext);
+    if (role.pmode < 0) return false;
+    role.g_fresh = role.gset->n == 0;
+    if (!role.g_fresh && (role.gset->identity || role.gkey != KEY_E || role.g_is_row)) return false;      // pre-populated: E columns only
+    role.merge = (sp->row_key != KEY_X && sp->col_key != KEY_X) ? 1 : 0;
+    const bool uses_ep = sp->row_list == LIST_EP || sp->col_list == LIST_EP;
+    return uses_ep ? fast_build_gp<true>(rm, sp, role, scale, correctA, rg, w, st, comm) : fast_build_gp<false>(rm, sp, role, scale, correctA, rg, w, st, comm);
 }

@@ -114,76 +114,15 @@ __device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t *s_wave
     return wbase + inc - v;
 }
 
-// ---- scan ----------------------------------------------------------------------------------
-constexpr int SC_T = 256, SC_I = 8, SC_TILE = SC_T * SC_I;
-
-template <class IN>
-__global__ __launch_bounds__(SC_T) void scan_tile_sums(const IN *__restrict__ in, size_t n,
-                                                       uint32_t *__restrict__ sums) {
-    __shared__ uint32_t s_wave[SC_T / 64];
-    const size_t base = (size_t)blockIdx.x * SC_TILE;
-    uint32_t s = 0;
-#pragma unroll
-    for (int i = 0; i < SC_I; ++i) {
-        const size_t idx = base + (size_t)i * SC_T + threadIdx.x;
-        if (idx < n) s += in[idx];
-    }
-    uint32_t tot;
-    (void)block_excl_scan<SC_T>(s, s_wave, tot);
-    if (threadIdx.x == 0) sums[blockIdx.x] = tot;
-}
-
-__global__ __launch_bounds__(1024) void scan_sums_inplace(uint32_t *__restrict__ sums, int nb,
-                                                          uint32_t *__restrict__ total) {
-    __shared__ uint32_t s_wave[16];
-    uint32_t carry = 0;
-    for (int base = 0; base < nb; base += 1024) {
-        const int i = base + threadIdx.x;
-        const uint32_t v = i < nb ? sums[i] : 0u;
-        uint32_t tot;
-        const uint32_t ex = block_excl_scan<1024>(v, s_wave, tot);
-        if (i < nb) sums[i] = carry + ex;
-        carry += tot;
-    }
-    if (threadIdx.x == 0 && total) *total = carry;
-}
-
-template <class IN>
-__global__ __launch_bounds__(SC_T) void scan_tile_apply(const IN *in, uint32_t *out, size_t n,
-                                                        const uint32_t *__restrict__ offs) {
-    __shared__ uint32_t tile[SC_TILE + SC_T];   // +1 pad per 8: thread t owns tile[9t .. 9t+7]
-    __shared__ uint32_t s_wave[SC_T / 64];
-    const size_t base = (size_t)blockIdx.x * SC_TILE;
-#pragma unroll
-    for (int i = 0; i < SC_I; ++i) {
-        const int e = i * SC_T + threadIdx.x;
-        const size_t idx = base + e;
-        tile[e + (e >> 3)] = idx < n ? in[idx] : 0u;
-    }
-    __syncthreads();
-    uint32_t v[SC_I], sum = 0;
-#pragma unroll
-    for (int i = 0; i < SC_I; ++i) { v[i] = tile[threadIdx.x * 9 + i]; sum += v[i]; }
-    uint32_t tot;
-    uint32_t run = block_excl_scan<SC_T>(sum, s_wave, tot) + offs[blockIdx.x];
-#pragma unroll
-    for (int i = 0; i < SC_I; ++i) { tile[threadIdx.x * 9 + i] = run; run += v[i]; }
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < SC_I; ++i) {
-        const int e = i * SC_T + threadIdx.x;
-        const size_t idx = base + e;
-        if (idx < n) out[idx] = tile[e + (e >> 3)];
-    }
-}
-
-// ---- the same in ONE launch: chained scan (decoupled look-back) ---------------------------------------------------------------
+// ---- scan: ONE launch, chained (decoupled look-back) ----------------------------------------------------------------------------
 // Every tile's workgroup publishes its sum, wave 0 looks back over its predecessors 64 at a time -- a predecessor's word says
 // {sum of that tile alone} or {sum of everything up to and including it}; the first of the second kind ends the walk -- and
 // publishes the tile's own inclusive prefix.  Workgroups are dispatched in index order, so a tile only ever waits for tiles that are
 // already running or done.  A status word is one 64-bit value {sum, epoch << 2 | kind}, stored and loaded whole at device scope
 // (coherent across the XCDs' L2s); the epoch of the call makes every older word invalid, so the buffer is never cleared.  A 5 km
-// build makes three to eight scans of <= 182 k elements: two launches fewer each (~5 us apiece at that size, round 5).
+// build makes three to eight scans of <= 182 k elements: two launches fewer each than a tile-sums / scan / apply chain (~5 us apiece at
+// that size, round 5).
+constexpr int SC_T = 256, SC_I = 8, SC_TILE = SC_T * SC_I;
 namespace {
 struct ScanState {
     unsigned long long *status = nullptr;
@@ -269,32 +208,24 @@ static void exclusive_scan_any(const IN *in, uint32_t *out, size_t n, uint32_t *
     }
     const size_t nb = (n + SC_TILE - 1) / SC_TILE;
     IBH_CHECK(nb < (1ul << 31), "scan too large");
-    if (get_tuning("scan_chained", 1)) {
-        ScanState &ss = scan_state();
-        int dev = 0;
-        IBH_HIP(hipGetDevice(&dev));
-        if (ss.device != dev || ss.cap < nb) {                  // (the words of an older, smaller buffer die with it: a fresh one starts at zero)
-            if (ss.status) (void)hipFree(ss.status);
-            ss.cap = std::max<size_t>(nb, 4096) * 2;
-            IBH_HIP(hipMalloc(&ss.status, ss.cap * sizeof(unsigned long long)));
-            IBH_HIP(hipMemsetAsync(ss.status, 0, ss.cap * sizeof(unsigned long long), stream));
-            IBH_HIP(hipStreamSynchronize(stream));              // (other streams of this thread may scan next)
-            ss.device = dev; ss.epoch = 0;
-        }
-        if (++ss.epoch >= (1u << 30)) {                         // (the epoch field is 30 bits: start over on a cleared buffer)
-            IBH_HIP(hipDeviceSynchronize());
-            IBH_HIP(hipMemsetAsync(ss.status, 0, ss.cap * sizeof(unsigned long long), stream));
-            IBH_HIP(hipStreamSynchronize(stream));
-            ss.epoch = 1;
-        }
-        hipLaunchKernelGGL(scan_chained<IN>, dim3((unsigned)nb), dim3(SC_T), 0, stream, in, out, n, ss.status, ss.epoch, total);
-        IBH_HIP(hipGetLastError());
-        return;
+    ScanState &ss = scan_state();
+    int dev = 0;
+    IBH_HIP(hipGetDevice(&dev));
+    if (ss.device != dev || ss.cap < nb) {              // (the words of an older, smaller buffer die with it: a fresh one starts at zero)
+        if (ss.status) (void)hipFree(ss.status);
+        ss.cap = std::max<size_t>(nb, 4096) * 2;
+        IBH_HIP(hipMalloc(&ss.status, ss.cap * sizeof(unsigned long long)));
+        IBH_HIP(hipMemsetAsync(ss.status, 0, ss.cap * sizeof(unsigned long long), stream));
+        IBH_HIP(hipStreamSynchronize(stream));          // (other streams of this thread may scan next)
+        ss.device = dev; ss.epoch = 0;
     }
-    uint32_t *sums = arena().get<uint32_t>(nb);
-    hipLaunchKernelGGL(scan_tile_sums<IN>, dim3((unsigned)nb), dim3(SC_T), 0, stream, in, n, sums);
-    hipLaunchKernelGGL(scan_sums_inplace, dim3(1), dim3(1024), 0, stream, sums, (int)nb, total);
-    hipLaunchKernelGGL(scan_tile_apply<IN>, dim3((unsigned)nb), dim3(SC_T), 0, stream, in, out, n, sums);
+    if (++ss.epoch >= (1u << 30)) {                     // (the epoch field is 30 bits: start over on a cleared buffer)
+        IBH_HIP(hipDeviceSynchronize());
+        IBH_HIP(hipMemsetAsync(ss.status, 0, ss.cap * sizeof(unsigned long long), stream));
+        IBH_HIP(hipStreamSynchronize(stream));
+        ss.epoch = 1;
+    }
+    hipLaunchKernelGGL(scan_chained<IN>, dim3((unsigned)nb), dim3(SC_T), 0, stream, in, out, n, ss.status, ss.epoch, total);
     IBH_HIP(hipGetLastError());
 }
 void exclusive_scan_u32(const uint32_t *in, uint32_t *out, size_t n, uint32_t *total, hipStream_t stream) {

@@ -663,15 +663,7 @@ struct TileView {
     const double *ev;
     const int *ns, *slotrow;
     int ngrp;
-    long long *dbg;     // scratch/r05 timeline builds only (GT_TIMELINE): 16 stamps per workgroup
 };
-#ifdef GT_TIMELINE
-#define GT_STAMP(i) do { if (tv.dbg && threadIdx.x == 0 && blockIdx.y == 0) tv.dbg[(long)blockIdx.x * 16 + (i)] = (long long)__builtin_readcyclecounter(); } while (0)
-#define GT_STAMP_W(i) do { if (tv.dbg && lane == 0 && blockIdx.y == 0) tv.dbg[(long)blockIdx.x * 16 + (i)] = (long long)__builtin_readcyclecounter(); } while (0)
-#else
-#define GT_STAMP(i) do {} while (0)
-#define GT_STAMP_W(i) do {} while (0)
-#endif
 constexpr int GT_UNITS = 16;         // the SP bound above: a group's units (slot, part) number max(16, ns)
 constexpr int GT_TABP = 65;          // row stride of the epilogue's table of partial sums [unit][lane]
 template <int F, int SEG>
@@ -708,12 +700,10 @@ __global__ __launch_bounds__(NW * 64, 4) void spmm_grouptile_kernel(const TileVi
     if (!block_to_task(blockIdx.x, tv.ngrp, nfc, xcd_mode, g, fc)) return;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    GT_STAMP(0);
     const double *__restrict__ X = bp.x[blockIdx.y];
     double *__restrict__ Y = bp.y[blockIdx.y];
     const int t0 = tv.tptr[g], t1 = tv.tptr[g + 1], ns = tv.ns[g];
     const int nitems = tv.gptr[g + 1] - tv.gptr[g];
-    GT_STAMP(1 + 0 * (t0 + t1 + ns + nitems));
     const int ib = wave % NB, fg = wave / NB;           // this wave gathers items [64 ib, 64 ib + 64) for fields [FW fg, FW fg + FW)
     const int j = lane / F, f = lane % F;
     // parts per slot: the largest power of two with sp * ns <= GT_UNITS; this wave's units [ub, ue)
@@ -785,11 +775,8 @@ __global__ __launch_bounds__(NW * 64, 4) void spmm_grouptile_kernel(const TileVi
     }
     for (int t = t0; t < t1; ++t) {
         if (t != t0) __syncthreads();                   // every wave is done with the previous tile
-        if (t == t0) GT_STAMP(2); else if (t == t0 + 1) GT_STAMP(6);
         store_tile(t);
-        if (t == t0) GT_STAMP(3); else if (t == t0 + 1) GT_STAMP(7);
         __syncthreads();
-        if (t == t0) GT_STAMP(4); else if (t == t0 + 1) GT_STAMP(8);
         const int ep = ep_cur;
         if (t + 1 < t1) {
             const int c = c_nxt;
@@ -798,7 +785,6 @@ __global__ __launch_bounds__(NW * 64, 4) void spmm_grouptile_kernel(const TileVi
             load_tile(t + 1, c, __builtin_amdgcn_readlane(ep_cur, IBH_GSLOTS));
         }
         __builtin_amdgcn_sched_barrier(0);              // (the loads above fly while the tile is summed: nothing of them sinks below)
-        if (t == t0) GT_STAMP(13);
         // Unit o of this wave = steps [B[o], B[o + 1]) of the tile's list (a step = J entries x F fields), walked in batches of
         // 4 steps: lane 16 r + i fetches the item index 8 k of the entry that step i of the batch hands to sublane r / (F / 16) --
         // one LDS read per lane and batch; a DPP row broadcast folded into the address add then gives every step its X
@@ -812,7 +798,6 @@ __global__ __launch_bounds__(NW * 64, 4) void spmm_grouptile_kernel(const TileVi
             const int lb = __builtin_amdgcn_readlane(ep, sl) >> 2, nq = (__builtin_amdgcn_readlane(ep, sl + 1) >> 2) - lb;
             B[o] = (lb + ((nq * part) >> lsp)) * R;
         }
-        if (t == t0) { GT_STAMP(14); if (tv.dbg && threadIdx.x == 0 && blockIdx.y == 0) tv.dbg[(long)blockIdx.x * 16 + 15] = ((long long)(B[OS] - B[0]) << 32) | (unsigned)(B[1] - B[0]); }
 #pragma unroll
         for (int o = 0; o < OS; ++o) {
             for (int p0 = B[o]; p0 < B[o + 1]; p0 += 4) {
@@ -830,11 +815,8 @@ __global__ __launch_bounds__(NW * 64, 4) void spmm_grouptile_kernel(const TileVi
 #undef GT_FM
             }
         }
-        if (t == t0) GT_STAMP(5); else if (t == t0 + 1) GT_STAMP(9);
     }
-    GT_STAMP(10);
     __syncthreads();                                    // s_x is done: the partial sums take its place
-    GT_STAMP(11);
 #pragma unroll
     for (int o = 0; o < OS; ++o)
         if (ub + o < ue) {
@@ -873,7 +855,6 @@ __global__ __launch_bounds__(NW * 64, 4) void spmm_grouptile_kernel(const TileVi
             }
         }
     }
-    GT_STAMP(12);
 }
 
 constexpr int SR_THREADS = 256;
@@ -1330,10 +1311,7 @@ static void launch_grouptile(const ibh_weighted *w, const BatchPtrs &bp, int nba
     IBH_CHECK(nb < (1l << 31), "spmm grid too large (%ld blocks)", nb);
     IBH_CHECK((long)w->ncol * 8 < (1l << 31), "ncol too large for 32-bit buffer offsets");
     IBH_CHECK(w->grp_nslot <= NS && w->gt_seg == SEG, "row groups of %d rows / tiles of %d in a kernel for %d / %d", w->grp_nslot, w->gt_seg, NS, SEG);
-    TileView tv{w->grp_ptr.p, w->gt_ptr.p, w->gt_col.p, w->gt_ek.p, w->gt_eptr.p, w->gt_ev.p, w->grp_ns.p, w->grp_slotrow.p, w->grp_n, nullptr};
-#ifdef GT_TIMELINE
-    tv.dbg = reinterpret_cast<long long *>(((unsigned long long)(unsigned)get_tuning("gt_dbg_hi", 0) << 32) | (unsigned)get_tuning("gt_dbg_lo", 0));
-#endif
+    TileView tv{w->grp_ptr.p, w->gt_ptr.p, w->gt_col.p, w->gt_ek.p, w->gt_eptr.p, w->gt_ev.p, w->grp_ns.p, w->grp_slotrow.p, w->grp_n};
     constexpr size_t lds = grouptile_lds<F, SEG>();
     static_assert(lds <= 64 * 1024, "within the default dynamic-LDS limit");
     hipEvent_t ev0 = g_ev_start, ev1 = g_ev_stop;

@@ -1325,7 +1325,8 @@ __global__ void k_sa_unpack_mw(const int32_t *__restrict__ cidx, const double *_
     Mw[cidx[k]] = cval[k];
 }
 
-// false: not served here (nothing has been touched: fast_build's own kernels run next).
+// false: not served here (nothing has been touched: fast_build's own kernels run next).  role: the two sides, already past
+// fast_build's gates (the P set fresh or the identity, the G set fresh or pre-populated E columns).
 // comm != nullptr: the SHARDED build of ibh_regrid_matrices_matrix_d_sharded -- every rank of the communicator calls this with the
 // same arguments; rank k runs the passes over its share of the ranges (contiguous, balanced by exchange cells: the grid is sorted
 // by atmosphere cell, AbbrGrid.cpp:10-21, so a block of ranges is a block of rows of an A/E-row matrix), three exchanges make
@@ -1335,31 +1336,21 @@ __global__ void k_sa_unpack_mw(const int32_t *__restrict__ cidx, const double *_
 //   2. the code bytes and the P-key prefixes of every 64 cells (the "first-seen flags": a straddler's id is looked up in the slice
 //      of the rank that numbered its ice cell), the class ranks and row offsets of every range   (~1 byte per exchange cell)
 //   3. the pieces of the result: CSR, wM, Mw, the dims tables
-static bool stream_build(const ibh_regrid_matrices *rm, const MatSpec *sp, ibh_sparse_set *dims[2], int scale, int correctA,
+template <bool EP>
+static bool stream_build(const ibh_regrid_matrices *rm, const MatSpec *sp, const FaRoles &role, int scale, int correctA,
                          const RgView &rg, ibh_weighted *w, hipStream_t st, ibh_comm *comm) {
     const ibh_regridder *gr = rm->rg;
     const ibh_plan &P = gr->plan;
     const long nX = gr->nX;
     const int world = comm ? comm_world(comm) : 1, rank = comm ? comm_rank(comm) : 0;
-    if (sp->family == FAM_EVA) return false;
     if (!comm && !get_tuning("assemble_stream", nX >= (1l << 20) ? 1 : 0)) return false;
-    const bool g_is_row = sp->family == FAM_AEVI;
-    ibh_sparse_set *gset = dims[g_is_row ? 0 : 1], *pset = dims[g_is_row ? 1 : 0];
-    const int gkey = g_is_row ? sp->row_key : sp->col_key, glist = g_is_row ? sp->row_list : sp->col_list;
-    const int pkey = g_is_row ? sp->col_key : sp->row_key, plist = g_is_row ? sp->col_list : sp->row_list;
-    auto extent_of = [&](int key) -> int64_t {
-        return key == KEY_A ? gr->nA : key == KEY_E ? gr->nA * (int64_t)gr->nhc : key == KEY_I ? gr->nI : gr->nX;
-    };
-    const int pmode = fa_pset_mode(pset, extent_of(pkey));
-    if (pmode < 0) return false;
-    const bool g_fresh = gset->n == 0;
-    if (!g_fresh && (gset->identity || gkey != KEY_E || g_is_row)) return false;
-    const bool uses_ep = sp->row_list == LIST_EP || sp->col_list == LIST_EP;
-    if (uses_ep && (P.tiny || !P.icnt_nz.p)) return false;         // classes are counted by the sign of the area here
+    const bool g_is_row = role.g_is_row, g_fresh = role.g_fresh;
+    const int pmode = role.pmode, merge = role.merge;
+    if (EP && (P.tiny || !P.icnt_nz.p)) return false;             // classes are counted by the sign of the area here
     if (!P.icnt_pos.p) return false;
     // an I-row matrix on an identity ice set (the coupler's IvE, IceCoupler.cpp:462): its rows lie in ice-cell order, not in
     // first-seen order -- row lengths are scattered by ice cell and scanned over the ice cells
-    const bool by_ice = !g_is_row && pkey == KEY_I && pmode == 0;
+    const bool by_ice = !g_is_row && role.pkey == KEY_I && pmode == 0;
     // sharded: the pieces of a rank must be contiguous in every result array -- sets numbered by this build; at most 8 ranks (one
     // 256-byte read-back carries all counters).  An A/E-row matrix on an IDENTITY P set (the coupler's EvI / AvI over the identity
     // dimI, IceCoupler.cpp:366-377) is served too: its CSR pieces are contiguous as they are (an entry's column is its sparse
@@ -1370,13 +1361,12 @@ static bool stream_build(const ibh_regrid_matrices *rm, const MatSpec *sp, ibh_s
     // I rows on the identity dimI (its IvE, :462; by_ice): rows in ice-cell order -- the row lengths are merged before the row pointer
     // is scanned, the rows travel in first-seen order and are copied to their places (k_sa_pack_keys / k_sa_pack_rows).
     const bool ident_p = world > 1 && pmode == 0 && g_is_row;
-    const bool ident_x_rows = world > 1 && pmode == 0 && !g_is_row && pkey == KEY_X;
+    const bool ident_x_rows = world > 1 && pmode == 0 && !g_is_row && role.pkey == KEY_X;
     const bool ident_i_rows = world > 1 && by_ice;
-    const bool prepop_g = world > 1 && !g_fresh;                 // (an E column set: checked above)
+    const bool prepop_g = world > 1 && !g_fresh;                 // (an E column set: fast_build checks)
     if (world > 1 && ((pmode != 1 && !ident_p && !ident_x_rows && !ident_i_rows) || world > 8 || P.nAr < world)) return false;
     const bool pscan = pmode == 1 || ident_p || ident_i_rows;    // the P keys are numbered (first-seen ranks)
-    const int merge = (sp->row_key != KEY_X && sp->col_key != KEY_X) ? 1 : 0;
-    const int S = uses_ep ? 2 : 1;
+    const int S = EP ? 2 : 1;
     if (gr->nhc > 64) return false;
     const uint8_t *emc = elevmask_classes_impl(rm, st);          // (made when the object was created, or here by the first build)
     const bool rel32 = (int64_t)S * P.maxrange > 65535;
@@ -1410,17 +1400,16 @@ static bool stream_build(const ibh_regrid_matrices *rm, const MatSpec *sp, ibh_s
     PlanView pl3 = pl;                                           // (k_fa_pelem walks pl.mlist: here the ice cells that are no clean pairs)
     pl3.mlist = P.mlist3.p; pl3.nmulti = P.nmulti3;
     FaG g{};
-    g.key = gkey; g.list = glist; g.NC = gkey == KEY_E ? gr->nhc : 1;
+    g.key = role.gkey; g.list = role.glist; g.NC = role.gkey == KEY_E ? gr->nhc : 1;
     const size_t nrc = (size_t)nAr * g.NC;
     g.erank = A.get<int8_t>(nrc); g.ecntn = A.get<uint32_t>(nrc); g.ecnto = A.get<uint32_t>(nrc);
     g.r_ncls = A.get<uint32_t>((size_t)nAr); g.r_nent = A.get<uint32_t>((size_t)nAr);
     g.gbase = A.get<uint32_t>((size_t)nAr + 1); g.ebase = A.get<uint32_t>((size_t)nAr + 1);
-    const int64_t gext = extent_of(gkey);
-    if (!g_fresh) g.tab = set_inverse_table(gset, gext, st);
+    if (!g_fresh) g.tab = set_inverse_table(role.gset, role.gext, st);
     FaP p{};
-    p.key = pkey; p.list = plist; p.fresh = pmode;
+    p.key = role.pkey; p.list = role.plist; p.fresh = pmode;
     sb.code = A.get<uint8_t>((size_t)nW * 64);
-    if (uses_ep) sb.cls = A.get<uint8_t>((size_t)nW * 64);
+    if (EP) sb.cls = A.get<uint8_t>((size_t)nW * 64);
     if (!g_is_row) {
         sb.rl = A.get<uint8_t>((size_t)nW * 64);
         if (by_ice) {
@@ -1429,7 +1418,7 @@ static bool stream_build(const ibh_regrid_matrices *rm, const MatSpec *sp, ibh_s
         }
         if (!by_ice || world > 1) { sb.cntL = A.get<uint32_t>((size_t)nW + 1); sb.Lw = A.get<uint32_t>((size_t)nW + 1); }
     }
-    if (uses_ep) sb.rel = A.get_bytes((size_t)nX * S * (rel32 ? 4 : 2));
+    if (EP) sb.rel = A.get_bytes((size_t)nX * S * (rel32 ? 4 : 2));
     else {
         sb.cntE = A.get<uint8_t>((size_t)nW + 1); sb.cntO = A.get<uint8_t>((size_t)nW + 1);
         sb.Ew = A.get<uint32_t>((size_t)nW + 1); sb.Eow = A.get<uint32_t>((size_t)nW + 1);
@@ -1448,18 +1437,17 @@ static bool stream_build(const ibh_regrid_matrices *rm, const MatSpec *sp, ibh_s
         IBH_HIP(hipMemsetAsync(sb.pbits + gW1, 0, 8, st));
         if (!g_is_row) IBH_HIP(hipMemsetAsync(sb.cntL + gW1, 0, sizeof(uint32_t), st));
     }
-    if (!uses_ep) {      // (the scans of the entry counts are read AT the end of the last range too)
+    if (!EP) {           // (the scans of the entry counts are read AT the end of the last range too)
         IBH_HIP(hipMemsetAsync(sb.cntE + gW1, 0, 1, st));
         IBH_HIP(hipMemsetAsync(sb.cntO + gW1, 0, 1, st));
     }
     const dim3 gs(ceil_div(sb.gx1 - sb.gx0, (long)SA_TILE)), gr4(ceil_div(nr, 4));
-    if (uses_ep) hipLaunchKernelGGL((k_sa_flags<true>), gs, dim3(SA_T), 0, st, rg, pl, sb, pkey == KEY_X ? 1 : 0, p.fresh, plist, g_is_row ? 0 : 1, d_cnt, emc);
-    else hipLaunchKernelGGL((k_sa_flags<false>), gs, dim3(SA_T), 0, st, rg, pl, sb, pkey == KEY_X ? 1 : 0, p.fresh, plist, g_is_row ? 0 : 1, d_cnt, emc);
+    hipLaunchKernelGGL((k_sa_flags<EP>), gs, dim3(SA_T), 0, st, rg, pl, sb, role.pkey == KEY_X ? 1 : 0, p.fresh, role.plist, g_is_row ? 0 : 1, d_cnt, emc);
     const long mean = nX / std::max(nAr, 1);
     // (straddlers of a range ~ its perimeter: a range of ~10^3 cells has a few dozen, one of 10^4 a few hundred)
     const int forced_os = get_tuning("assemble_stream_oldseg", -1);
     const int oldseg = (forced_os == SA_OLDSEG_S || forced_os == SA_OLDSEG_L) ? forced_os : mean <= 2048 ? SA_OLDSEG_S : SA_OLDSEG_L;
-    if (uses_ep) {
+    if (EP) {
         // waves per range by the size of the ranges: one wave walks ~10^3 cells in a few round trips; longer ranges are cut
         const int forced = get_tuning("assemble_stream_wpr", -1);
         const int wpr = (forced == 1 || forced == 4 || forced == 16) ? forced : mean <= 1024 ? 1 : mean <= 4096 ? 4 : 16;
@@ -1481,7 +1469,7 @@ static bool stream_build(const ibh_regrid_matrices *rm, const MatSpec *sp, ibh_s
         const MsCh chL{lch ? (const void *)(sb.cntL + gW0) : nullptr, lch ? sb.Lw + gW0 : nullptr, world == 1 ? d_cnt + 5 : nullptr, lch ? nws : 0, 0, 0};
         const MsCh chG{g.r_ncls + sb.sr0, g.gbase + sb.sr0, d_cnt + 3, nr, 0, 1};
         const MsCh chN{g.r_nent + sb.sr0, g.ebase + sb.sr0, d_cnt + 4, nr, 0, 1};
-        if (uses_ep) {
+        if (EP) {
             const MsCh chs[4] = {chP, chL, chG, chN};
             sa_scan_channels(chs, 4, st);
         } else {
@@ -1506,19 +1494,13 @@ static bool stream_build(const ibh_regrid_matrices *rm, const MatSpec *sp, ibh_s
         err_x = std::min(err_x, hk[0]); fl |= hk[1];
         P0[k + 1] = P0[k] + hk[2]; G0[k + 1] = G0[k] + hk[3]; E0[k + 1] = E0[k] + hk[4]; L0[k + 1] = L0[k] + hk[5];
     }
-    if (err_x != 0xffffffffu) {                                  // message of linterp_1d_b, IceRegridder_L0.cpp:84-85
-        int32_t ij[2];
-        IBH_HIP(hipMemcpy(ij, gr->ex_indices.p + 2 * (size_t)err_x, sizeof(ij), hipMemcpyDeviceToHost));
-        double e = 0;
-        IBH_HIP(hipMemcpy(&e, rm->elevmaskI.p + ij[1], sizeof(double), hipMemcpyDeviceToHost));
-        fail(IBH_ERANGE, "Elevation %g out of bounds (%g, %g)", e < 0 ? 0.0 : e, gr->hcdefs_h.front(), gr->hcdefs_h.back());
-    }
+    if (err_x != 0xffffffffu) fail_elevation_range(rm, err_x);
     if (fl) return false;                                        // a limit of the fast path was hit (on some rank): general pipeline
     IBH_CHECK(E0[world] < (1u << 31) && P0[world] < (1u << 31), "matrix too large for int32 indices");
     const uint32_t *hme = hh + 8 * rank;
     const uint32_t nnz = (uint32_t)E0[world];
-    const int np_d = p.fresh ? (int)P0[world] : (int)extent_of(pkey);
-    const int ng_d = g_fresh ? (int)G0[world] : gset->n;
+    const int np_d = p.fresh ? (int)P0[world] : (int)role.pext;
+    const int ng_d = g_fresh ? (int)G0[world] : role.gset->n;
     // local -> global numbering of this rank's slice
     if (world > 1) hipLaunchKernelGGL(k_sa_shift, dim3(ceil_div(std::max<long>(nwl + 1, nr + 1), 256l)), dim3(256), 0, st, pscan ? sb.Pw : nullptr, g_is_row ? nullptr : sb.Lw,
                        gW0, nwl + 1, (uint32_t)(P0[rank] - hme[6]), (uint32_t)(L0[rank] - hme[7]), g.gbase, g.ebase, sb.sr0, nr, (uint32_t)G0[rank], (uint32_t)E0[rank]);
@@ -1569,22 +1551,20 @@ static bool stream_build(const ibh_regrid_matrices *rm, const MatSpec *sp, ibh_s
     const dim3 grl(ceil_div(nr, 4 * rows_R));
     double *sval = nullptr;
     int32_t *sdid = nullptr;
-    // cells per thread of the emit pass x workgroups (0 = one per tile).  The pass is bound by instruction issue and latency, not by
-    // bandwidth (ablation on the Antarctic AvI: 129 us with every load of cell data, every term and every store removed; stores +95,
-    // the first-seen lookup of the straddlers +45 after the bitmask change, +115 before): a workgroup that walks several tiles has the
-    // code bytes of its next tile in flight while it works.  Measured, a1h AvI / IvA / EvI / IvE ms, same box: 2 x full grid 0.645 /
+    // the emit pass: one cell per thread (four with 32-bit offsets), at most EMIT_BLOCKS workgroups.  The pass is bound by instruction
+    // issue and latency, not by bandwidth (ablation on the Antarctic AvI: 129 us with every load of cell data, every term and every
+    // store removed; stores +95, the first-seen lookup of the straddlers +45 after the bitmask change, +115 before): a workgroup that
+    // walks several tiles has the code bytes of its next tile in flight while it works.  Measured (cells per thread x workgroups), a1h
+    // AvI / IvA / EvI / IvE ms, same box: 2 x full grid 0.645 /
     // 0.915 / 1.216 / 1.604; 1 x full 0.704 / 0.919 / 1.228 / 1.555; 1 x 8192 0.636 / 0.878 / 1.135 / 1.470; 2 x 8192 0.642 / 0.926 /
     // 1.183 / 1.574; 4 x full 0.709 / 1.063 / 1.274 / 1.711
-    const int ecpt = get_tuning("assemble_stream_emit_cpt", 1);
+    constexpr long EMIT_BLOCKS = 8192;
     const long ncell = sb.gx1 - sb.gx0;
-    const long eblocks = get_tuning("assemble_stream_emit_blocks", 8192);
-    auto egrid = [&](int cpt) { const long full = ceil_div(ncell, (long)SA_T * cpt); return dim3((unsigned)(eblocks > 0 ? std::min(full, eblocks) : full)); };
-#define SA_LAUNCH_EMIT(EP, GR)                                                                                                  \
+    auto egrid = [&](int cpt) { const long full = ceil_div(ncell, (long)SA_T * cpt); return dim3((unsigned)std::min(full, EMIT_BLOCKS)); };
+#define SA_LAUNCH_EMIT(GR)                                                                                                      \
     do {                                                                                                                        \
         if (rel32) hipLaunchKernelGGL((k_sa_emit<EP, GR, uint32_t, 4>), egrid(4), dim3(SA_T), 0, st, rg, pl, *sp, g, p, sb, merge, o, sval, sdid); \
-        else if (ecpt == 2) hipLaunchKernelGGL((k_sa_emit<EP, GR, uint16_t, 2>), egrid(2), dim3(SA_T), 0, st, rg, pl, *sp, g, p, sb, merge, o, sval, sdid); \
-        else if (ecpt == 1) hipLaunchKernelGGL((k_sa_emit<EP, GR, uint16_t, 1>), egrid(1), dim3(SA_T), 0, st, rg, pl, *sp, g, p, sb, merge, o, sval, sdid); \
-        else hipLaunchKernelGGL((k_sa_emit<EP, GR, uint16_t, 4>), egrid(4), dim3(SA_T), 0, st, rg, pl, *sp, g, p, sb, merge, o, sval, sdid);       \
+        else hipLaunchKernelGGL((k_sa_emit<EP, GR, uint16_t, 1>), egrid(1), dim3(SA_T), 0, st, rg, pl, *sp, g, p, sb, merge, o, sval, sdid);       \
     } while (0)
     sb.end_row = nrow; sb.end_nnz = nnz;
     int32_t *kidx = nullptr;                                     // shared build, identity ice rows: the ice cell / row length of every P key, in first-seen order
@@ -1608,16 +1588,14 @@ static bool stream_build(const ibh_regrid_matrices *rm, const MatSpec *sp, ibh_s
     }
     if (g_is_row) {
         if (ncol && !p.fresh) IBH_HIP(hipMemsetAsync(w->Mw.p, 0, sizeof(double) * (size_t)ncol, st));
-        if (uses_ep) SA_LAUNCH_EMIT(true, true); else SA_LAUNCH_EMIT(false, true);
+        SA_LAUNCH_EMIT(true);
         if (p.key == KEY_I && P.npair) {                      // Mw of the ice cells across one GCM-cell edge
             const dim3 gp2(ceil_div(P.npair, 256));
-            if (uses_ep) hipLaunchKernelGGL((k_sa_pairs<true, true>), gp2, dim3(256), 0, st, rg, pl, *sp, g, p, sb, P.px1.p, P.px2.p, P.piI.p, P.pa1.p, P.pa2.p, P.npair, o);
-            else hipLaunchKernelGGL((k_sa_pairs<false, true>), gp2, dim3(256), 0, st, rg, pl, *sp, g, p, sb, P.px1.p, P.px2.p, P.piI.p, P.pa1.p, P.pa2.p, P.npair, o);
+            hipLaunchKernelGGL((k_sa_pairs<EP, true>), gp2, dim3(256), 0, st, rg, pl, *sp, g, p, sb, P.px1.p, P.px2.p, P.piI.p, P.pa1.p, P.pa2.p, P.npair, o);
         }
         if (p.key == KEY_I && P.nmulti3) {                    // ... and of the rest of the ice cells with several exchange cells
             const dim3 gm(ceil_div(P.nmulti3, T));
-            if (uses_ep) hipLaunchKernelGGL((k_fa_pelem<true, FA_PSUMS, false>), gm, dim3(T), 0, st, rg, pl3, *sp, g, p, merge, (long)P.nmulti3, o, (uint32_t *)nullptr, flags, 1);
-            else hipLaunchKernelGGL((k_fa_pelem<false, FA_PSUMS, false>), gm, dim3(T), 0, st, rg, pl3, *sp, g, p, merge, (long)P.nmulti3, o, (uint32_t *)nullptr, flags, 1);
+            hipLaunchKernelGGL((k_fa_pelem<EP, FA_PSUMS, false>), gm, dim3(T), 0, st, rg, pl3, *sp, g, p, merge, (long)P.nmulti3, o, (uint32_t *)nullptr, flags, 1);
         }
         if (rowsl) {
             if (oldseg == SA_OLDSEG_S) hipLaunchKernelGGL((k_sa_oldsort<SA_OLDSEG_S>), gr4, dim3(256), 0, st, g, o.colind, o.val, sb.sr0, sb.sr1);
@@ -1628,21 +1606,15 @@ static bool stream_build(const ibh_regrid_matrices *rm, const MatSpec *sp, ibh_s
         else hipLaunchKernelGGL((k_sa_rows1<true, SA_OLDSEG_L>), grq1, dim3(256), 0, st, rg, pl, g, o, (int32_t *)nullptr, sb.sr0, sb.sr1);
     } else {
         sval = A.get<double>(nnz); sdid = A.get<int32_t>(nnz);
-        if (uses_ep) SA_LAUNCH_EMIT(true, false); else SA_LAUNCH_EMIT(false, false);
+        SA_LAUNCH_EMIT(false);
         if (p.key == KEY_I && P.npair) {                      // the rows of the ice cells across one GCM-cell edge
             const dim3 gp2(ceil_div(P.npair, 256));
-            if (uses_ep) hipLaunchKernelGGL((k_sa_pairs<true, false>), gp2, dim3(256), 0, st, rg, pl, *sp, g, p, sb, P.px1.p, P.px2.p, P.piI.p, P.pa1.p, P.pa2.p, P.npair, o);
-            else hipLaunchKernelGGL((k_sa_pairs<false, false>), gp2, dim3(256), 0, st, rg, pl, *sp, g, p, sb, P.px1.p, P.px2.p, P.piI.p, P.pa1.p, P.pa2.p, P.npair, o);
+            hipLaunchKernelGGL((k_sa_pairs<EP, false>), gp2, dim3(256), 0, st, rg, pl, *sp, g, p, sb, P.px1.p, P.px2.p, P.piI.p, P.pa1.p, P.pa2.p, P.npair, o);
         }
         if (p.key == KEY_I && P.nmulti3) {                    // ... and of the rest of the ice cells with several exchange cells
             const dim3 gm(ceil_div(P.nmulti3, T));
-            if (!g_fresh) {
-                if (uses_ep) hipLaunchKernelGGL((k_fa_pelem<true, FA_PEMIT, true>), gm, dim3(T), 0, st, rg, pl3, *sp, g, p, merge, (long)P.nmulti3, o, (uint32_t *)nullptr, flags, 1);
-                else hipLaunchKernelGGL((k_fa_pelem<false, FA_PEMIT, true>), gm, dim3(T), 0, st, rg, pl3, *sp, g, p, merge, (long)P.nmulti3, o, (uint32_t *)nullptr, flags, 1);
-            } else {
-                if (uses_ep) hipLaunchKernelGGL((k_fa_pelem<true, FA_PEMIT, false>), gm, dim3(T), 0, st, rg, pl3, *sp, g, p, merge, (long)P.nmulti3, o, (uint32_t *)nullptr, flags, 1);
-                else hipLaunchKernelGGL((k_fa_pelem<false, FA_PEMIT, false>), gm, dim3(T), 0, st, rg, pl3, *sp, g, p, merge, (long)P.nmulti3, o, (uint32_t *)nullptr, flags, 1);
-            }
+            if (!g_fresh) hipLaunchKernelGGL((k_fa_pelem<EP, FA_PEMIT, true>), gm, dim3(T), 0, st, rg, pl3, *sp, g, p, merge, (long)P.nmulti3, o, (uint32_t *)nullptr, flags, 1);
+            else hipLaunchKernelGGL((k_fa_pelem<EP, FA_PEMIT, false>), gm, dim3(T), 0, st, rg, pl3, *sp, g, p, merge, (long)P.nmulti3, o, (uint32_t *)nullptr, flags, 1);
         }
         if (!g_fresh && ncol) hipLaunchKernelGGL(k_fa_zero_identity, dim3(ceil_div(ncol, T)), dim3(T), 0, st, w->Mw.p, (long)ncol);
         FaOut os = o;
@@ -1678,7 +1650,7 @@ static bool stream_build(const ibh_regrid_matrices *rm, const MatSpec *sp, ibh_s
             cval = A.get<double>((size_t)std::max<long>(npk, 1));
             if (g_is_row) {
                 if (sb.sx1 > sb.sx0)
-                    hipLaunchKernelGGL(k_sa_pack_mw, dim3((unsigned)ceil_div(sb.sx1 - sb.sx0, 256l)), dim3(256), 0, st, sb, pl.exI, pkey == KEY_X ? 1 : 0, w->Mw.p, cidx, cval);
+                    hipLaunchKernelGGL(k_sa_pack_mw, dim3((unsigned)ceil_div(sb.sx1 - sb.sx0, 256l)), dim3(256), 0, st, sb, pl.exI, role.pkey == KEY_X ? 1 : 0, w->Mw.p, cidx, cval);
             } else if (nr > 0)
                 hipLaunchKernelGGL(k_sa_pack_mw_g, dim3((unsigned)ceil_div((long)nr * g.NC, 256l)), dim3(256), 0, st, rg, pl, g, sb.sr0, sb.sr1, w->Mw.p, cidx, cval);
         }
@@ -1712,16 +1684,8 @@ static bool stream_build(const ibh_regrid_matrices *rm, const MatSpec *sp, ibh_s
                                (long)P0[rank + 1], nkeys, w->rowptr.p, w->colind.p, w->val.p, w->wM.p);
         if (pairs && npk) hipLaunchKernelGGL(k_sa_unpack_mw, dim3((unsigned)ceil_div(npk, 256l)), dim3(256), 0, st, cidx, cval, (long)Cl[rank], (long)Cl[rank + 1], npk, w->Mw.p);
     }
-    auto commit = [&](ibh_sparse_set *set, int64_t extent, DevBuf<int64_t> &table, int n) {
-        set->sparse_extent = extent;
-        if (n == 0) return;
-        set->host.clear(); set->host_n = 0; set->inv.clear(); set->inv_n = 0;
-        set->dev = std::move(table);
-        set->dev_n = set->n = n;
-        set->identity = false;
-    };
-    if (p.fresh) commit(pset, extent_of(pkey), ptable, np_d); else if (pset->sparse_extent != extent_of(pkey)) pset->sparse_extent = extent_of(pkey);
-    if (g_fresh) commit(gset, gext, gtable, ng_d); else if (gset->sparse_extent != gext) gset->sparse_extent = gext;
+    commit_set(role.pset, p.fresh, role.pext, ptable, np_d);
+    commit_set(role.gset, g_fresh, role.gext, gtable, ng_d);
     IBH_HIP(hipStreamSynchronize(st));
     w->built_fast = world > 1 ? 3 : 2;
     // (flags raised by the later kernels -- a straddler list that overflowed -- cannot differ from the count pass's; checked there)

@@ -25,8 +25,6 @@ for seed in range(first, first + count):
         icebin_amd.set_tuning("assemble_stream_rowsl", (seed // 3) % 2)
         icebin_amd.set_tuning("assemble_stream_rowsl_r", (1, 4, 16, 7)[(seed // 6) % 4])
         icebin_amd.set_tuning("assemble_stream_rows4", (seed // 12) % 2)
-        icebin_amd.set_tuning("assemble_stream_emit_blocks", (0, 1, 3, 8192)[(seed // 3) % 4])
-        icebin_amd.set_tuning("assemble_stream_emit_cpt", (1, 2, 4)[(seed // 9) % 3])
         nfast = 0
         for name in T.ALL:
             for scale, correctA in ((True, True), (False, False), (True, False)):
