@@ -106,6 +106,24 @@ static void make_identity(ibh_sparse_set *s, int64_t n) {
     s->identity = true;
 }
 
+// The ibh_selftest_* entries of the integer primitives run one primitive each on hipStreamPerThread (as the builds do: calls from concurrent host threads overlap).
+// Every result buffer carries SELFTEST_GUARD words after its end, filled with 0xA5 bytes beforehand: a primitive that writes past
+// its output fails the call.
+static constexpr size_t SELFTEST_GUARD = 64;
+template <class T> static T *selftest_alloc_guarded(Arena &A, size_t n, hipStream_t st) {
+    T *p = A.get<T>(n + SELFTEST_GUARD);
+    IBH_HIP(hipMemsetAsync(p + n, 0xA5, SELFTEST_GUARD * sizeof(T), st));
+    return p;
+}
+template <class T> static void selftest_download_guarded(T *host, const T *dev, size_t n, hipStream_t st, const char *what) {
+    std::vector<T> tmp(n + SELFTEST_GUARD);
+    IBH_HIP(hipMemcpyAsync(tmp.data(), dev, sizeof(T) * tmp.size(), hipMemcpyDeviceToHost, st));
+    IBH_HIP(hipStreamSynchronize(st));
+    const unsigned char *g = reinterpret_cast<const unsigned char *>(tmp.data() + n);
+    for (size_t i = 0; i < SELFTEST_GUARD * sizeof(T); ++i)
+        IBH_CHECK(g[i] == 0xA5, "%s: written past its end (byte %zu after element %zu)", what, i, n);
+    if (n) memcpy(host, tmp.data(), sizeof(T) * n);
+}
 }  // namespace ibh
 
 using namespace ibh;
@@ -710,6 +728,120 @@ int ibh_selftest_sort(const uint64_t *keys, int64_t n, int lo_bits, int hi_bits,
         if (n >= 2) IBH_HIP(hipMemcpyAsync(&h, info, sizeof(h), hipMemcpyDeviceToHost, st));
         IBH_HIP(hipMemcpyAsync(perm_out, alt ? v2 : v, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, st));
         IBH_HIP(hipStreamSynchronize(st));
+        *path_out = !(h.flags & ORD_FULL_DEC) ? 0 : h.maxlen <= (uint32_t)CS_BIG ? 1 : 2;
+    });
+}
+int ibh_selftest_scan(int kind, const void *in, int64_t n, uint32_t *out, uint32_t *total_out, int flags) {
+    return guarded([&] {
+        IBH_CHECK(kind >= 0 && kind <= 2, "unknown scan kind %d", kind);
+        IBH_CHECK(n >= 0 && n < (1ll << 31), "n = %lld out of range", (long long)n);
+        IBH_CHECK((n == 0 || (in && out)) && total_out, "null argument");
+        IBH_CHECK((flags & ~(IBH_SCAN_IN_PLACE | IBH_SCAN_FRESH_STATE | IBH_SCAN_NEAR_WRAP)) == 0, "unknown flags %#x", flags);
+        IBH_CHECK(!(flags & IBH_SCAN_IN_PLACE) || kind == 0, "an in-place scan is u32 only");
+        require_device();
+        hipStream_t st = hipStreamPerThread;
+        if (flags & IBH_SCAN_FRESH_STATE) scan_state_for_test(SCAN_STATE_FREE, st);
+        if (flags & IBH_SCAN_NEAR_WRAP) scan_state_for_test(SCAN_STATE_NEAR_WRAP, st);
+        Arena &A = arena();
+        A.reset();
+        const size_t m = (size_t)n, nout = kind == 2 ? 3 * m : m, ntot = kind == 2 ? 3 : 1;
+        uint32_t *d_out = selftest_alloc_guarded<uint32_t>(A, nout, st);
+        uint32_t *d_tot = A.get<uint32_t>(3);
+        IBH_HIP(hipMemsetAsync(d_tot, 0xA5, 3 * sizeof(uint32_t), st));       // a total that is not written fails the comparison
+        if (kind == 0) {
+            const uint32_t *d_in = d_out;
+            if (!(flags & IBH_SCAN_IN_PLACE)) d_in = A.get<uint32_t>(m);
+            if (m) IBH_HIP(hipMemcpyAsync(const_cast<uint32_t *>(d_in), in, sizeof(uint32_t) * m, hipMemcpyHostToDevice, st));
+            exclusive_scan_u32(d_in, d_out, m, d_tot, st);
+        } else if (kind == 1) {
+            uint8_t *d_in = A.get<uint8_t>(m);
+            if (m) IBH_HIP(hipMemcpyAsync(d_in, in, m, hipMemcpyHostToDevice, st));
+            exclusive_scan_u8(d_in, d_out, m, d_tot, st);
+        } else {
+            uint32_t *d_in = A.get<uint32_t>(m);
+            if (m) IBH_HIP(hipMemcpyAsync(d_in, in, sizeof(uint32_t) * m, hipMemcpyHostToDevice, st));
+            exclusive_scan3(d_in, m, d_out, d_out + m, d_out + 2 * m, d_tot, st);
+        }
+        IBH_HIP(hipGetLastError());
+        selftest_download_guarded(out, d_out, nout, st, "scan output");
+        IBH_HIP(hipMemcpyAsync(total_out, d_tot, sizeof(uint32_t) * ntot, hipMemcpyDeviceToHost, st));
+        IBH_HIP(hipStreamSynchronize(st));
+    });
+}
+int ibh_selftest_radix_sort(const uint64_t *keys, int64_t n, const int32_t *fields, int nfields, uint64_t *keys_out,
+                            uint32_t *perm_out) {
+    return guarded([&] {
+        IBH_CHECK(n >= 0 && n < (1ll << 31), "n = %lld out of range", (long long)n);
+        IBH_CHECK(n == 0 || (keys && keys_out && perm_out), "null argument");
+        IBH_CHECK(nfields >= 0 && nfields <= 8, "nfields = %d: 0 to 8 fields", nfields);
+        IBH_CHECK(nfields == 0 || fields, "null argument");
+        std::vector<KeyField> f((size_t)nfields);
+        for (int i = 0; i < nfields; ++i) {
+            const int shift = fields[2 * i], nbits = fields[2 * i + 1];
+            IBH_CHECK(nbits >= 1 && nbits <= 32, "field %d: nbits = %d not in [1, 32]", i, nbits);
+            IBH_CHECK(shift >= 0 && shift + nbits <= 64, "field %d: bits [%d, %d) outside the 64-bit key", i, shift, shift + nbits);
+            f[(size_t)i] = KeyField{shift, nbits};
+        }
+        require_device();
+        if (n == 0) return;
+        hipStream_t st = hipStreamPerThread;
+        Arena &A = arena();
+        A.reset();
+        const size_t m = (size_t)n;
+        uint64_t *k = selftest_alloc_guarded<uint64_t>(A, m, st), *k2 = selftest_alloc_guarded<uint64_t>(A, m, st);
+        uint32_t *v = selftest_alloc_guarded<uint32_t>(A, m, st), *v2 = selftest_alloc_guarded<uint32_t>(A, m, st);
+        IBH_HIP(hipMemcpyAsync(k, keys, sizeof(uint64_t) * m, hipMemcpyHostToDevice, st));
+        std::vector<uint32_t> iota(m);
+        for (size_t i = 0; i < m; ++i) iota[i] = (uint32_t)i;
+        IBH_HIP(hipMemcpyAsync(v, iota.data(), sizeof(uint32_t) * m, hipMemcpyHostToDevice, st));
+        const bool alt = radix_sort_pairs(k, k2, v, v2, m, f.data(), nfields, st);
+        IBH_HIP(hipGetLastError());
+        selftest_download_guarded(keys_out, alt ? k2 : k, m, st, "sorted keys");
+        selftest_download_guarded(perm_out, alt ? v2 : v, m, st, "sorted payload");
+    });
+}
+int ibh_selftest_order(const uint64_t *keys, int64_t n, int lo_bits, int hi_bits, int try_pieces, uint32_t *perm_out,
+                       uint32_t *info_out, int *path_out) {
+    return guarded([&] {
+        IBH_CHECK(n >= 0 && n < (1ll << 31), "n = %lld out of range", (long long)n);
+        IBH_CHECK(lo_bits >= 0 && lo_bits <= 32 && hi_bits >= 0 && hi_bits <= 32, "field widths (%d, %d) not in [0, 32]", lo_bits, hi_bits);
+        IBH_CHECK((n == 0 || (keys && perm_out)) && info_out && path_out, "null argument");
+        IBH_CHECK(try_pieces == 0 || try_pieces == 1, "try_pieces = %d", try_pieces);
+        const uint64_t lo_lim = lo_bits == 32 ? 1ull << 32 : 1ull << lo_bits, hi_lim = hi_bits == 32 ? 1ull << 32 : 1ull << hi_bits;
+        for (int64_t i = 0; i < n; ++i)
+            IBH_CHECK((keys[i] & 0xffffffffull) < lo_lim && (keys[i] >> 32) < hi_lim, "key %lld has bits outside its fields", (long long)i);
+        require_device();
+        memset(info_out, 0, 6 * sizeof(uint32_t));
+        *path_out = 0;
+        if (n == 0) return;
+        hipStream_t st = hipStreamPerThread;
+        Arena &A = arena();
+        A.reset();
+        const size_t m = (size_t)n;
+        uint64_t *k = selftest_alloc_guarded<uint64_t>(A, m, st), *k2 = selftest_alloc_guarded<uint64_t>(A, m, st);
+        uint32_t *v = selftest_alloc_guarded<uint32_t>(A, m, st), *v2 = selftest_alloc_guarded<uint32_t>(A, m, st);
+        OrderInfo *info = A.get<OrderInfo>(1);
+        IBH_HIP(hipMemsetAsync(info, 0, sizeof(OrderInfo), st));           // (adaptive_sort_pairs leaves it alone when n < 2)
+        IBH_HIP(hipMemcpyAsync(k, keys, sizeof(uint64_t) * m, hipMemcpyHostToDevice, st));
+        std::vector<uint32_t> iota(m);
+        for (size_t i = 0; i < m; ++i) iota[i] = (uint32_t)i;
+        IBH_HIP(hipMemcpyAsync(v, iota.data(), sizeof(uint32_t) * m, hipMemcpyHostToDevice, st));
+        bool alt = false;
+        if (try_pieces) {
+            alt = adaptive_sort_pairs(k, k2, v, v2, m, lo_bits, hi_bits, info, st);
+        } else {                // the flags-only analysis, then the radix sort it plans (assemble.hip, expect_local = false)
+            order_and_chunk_sort(k, v, m, info, st, false);
+            OrderInfo h;
+            readback_sync(&h, info, sizeof(h), st);
+            if (m >= 2 && !order_is_final(h)) alt = radix_after_analysis(h, k, k2, v, v2, m, lo_bits, hi_bits, st);
+        }
+        IBH_HIP(hipGetLastError());
+        OrderInfo h{};
+        IBH_HIP(hipMemcpyAsync(&h, info, sizeof(h), hipMemcpyDeviceToHost, st));
+        IBH_HIP(hipStreamSynchronize(st));
+        selftest_download_guarded(perm_out, alt ? v2 : v, m, st, "sorted payload");
+        const uint32_t f[6] = {h.flags, h.nchunks, h.maxlen, h.nsmall, h.nmid, h.nbig};
+        memcpy(info_out, f, sizeof(f));
         *path_out = !(h.flags & ORD_FULL_DEC) ? 0 : h.maxlen <= (uint32_t)CS_BIG ? 1 : 2;
     });
 }

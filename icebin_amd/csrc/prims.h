@@ -31,6 +31,11 @@ void exclusive_scan_u32(const uint32_t *in, uint32_t *out, size_t n, uint32_t *t
 // the same over byte-sized counts (flags: a quarter of the read traffic)
 void exclusive_scan_u8(const uint8_t *in, uint32_t *out, size_t n, uint32_t *total, hipStream_t stream);
 
+// Test hook of the one-launch scan's per-thread status buffer (ibh_selftest_scan): free it, or move its epoch to just before
+// the 30-bit rollover.  Not for product code.
+enum { SCAN_STATE_FREE = 1, SCAN_STATE_NEAR_WRAP = 2 };
+void scan_state_for_test(int op, hipStream_t stream);
+
 // Three exclusive scans in one pass over a packed stream: pk[i] bits [0,2) and [2,4) are flag pairs
 // (channel value = number of set flags), bits [4,6) a count 0..3.  totals3: device uint32[3].
 void exclusive_scan3(const uint32_t *pk, size_t n, uint32_t *o0, uint32_t *o1, uint32_t *o2, uint32_t *totals3,

@@ -200,14 +200,8 @@ __global__ __launch_bounds__(SC_T) void scan_chained(const IN *__restrict__ in, 
     }
 }
 
-template <class IN>
-static void exclusive_scan_any(const IN *in, uint32_t *out, size_t n, uint32_t *total, hipStream_t stream) {
-    if (n == 0) {
-        if (total) IBH_HIP(hipMemsetAsync(total, 0, sizeof(uint32_t), stream));
-        return;
-    }
-    const size_t nb = (n + SC_TILE - 1) / SC_TILE;
-    IBH_CHECK(nb < (1ul << 31), "scan too large");
+// This thread's status buffer on the current device, grown to hold at least nb tiles.
+static ScanState &scan_status_for(size_t nb, hipStream_t stream) {
     ScanState &ss = scan_state();
     int dev = 0;
     IBH_HIP(hipGetDevice(&dev));
@@ -219,6 +213,33 @@ static void exclusive_scan_any(const IN *in, uint32_t *out, size_t n, uint32_t *
         IBH_HIP(hipStreamSynchronize(stream));          // (other streams of this thread may scan next)
         ss.device = dev; ss.epoch = 0;
     }
+    return ss;
+}
+// Test hook (ibh_selftest_scan only): SCAN_STATE_FREE drops this thread's status buffer, so that the next scan allocates and clears
+// a new one; SCAN_STATE_NEAR_WRAP moves the epoch forward to 2^30 - 2, so that the next scan runs at the last epoch and the one after
+// it takes the rollover.  The epoch only ever moves forward: every epoch value is used once between two clears of the buffer.
+void scan_state_for_test(int op, hipStream_t stream) {
+    if (op == SCAN_STATE_FREE) {
+        ScanState &ss = scan_state();
+        if (ss.status) IBH_HIP(hipFree(ss.status));
+        ss = ScanState{};
+    } else if (op == SCAN_STATE_NEAR_WRAP) {
+        ScanState &ss = scan_status_for(1, stream);
+        ss.epoch = std::max(ss.epoch, (1u << 30) - 2);
+    } else {
+        IBH_CHECK(false, "unknown scan state operation %d", op);
+    }
+}
+
+template <class IN>
+static void exclusive_scan_any(const IN *in, uint32_t *out, size_t n, uint32_t *total, hipStream_t stream) {
+    if (n == 0) {
+        if (total) IBH_HIP(hipMemsetAsync(total, 0, sizeof(uint32_t), stream));
+        return;
+    }
+    const size_t nb = (n + SC_TILE - 1) / SC_TILE;
+    IBH_CHECK(nb < (1ul << 31), "scan too large");
+    ScanState &ss = scan_status_for(nb, stream);
     if (++ss.epoch >= (1u << 30)) {                     // (the epoch field is 30 bits: start over on a cleared buffer)
         IBH_HIP(hipDeviceSynchronize());
         IBH_HIP(hipMemsetAsync(ss.status, 0, ss.cap * sizeof(unsigned long long), stream));

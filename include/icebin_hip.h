@@ -433,6 +433,25 @@ int ibh_set_launch_events(void *start, void *stop);
  * fields below 2^hi_bits / 2^lo_bits.  *path_out: 0 already ordered, 1 pieces sorted in LDS,
  * 2 device-wide radix sort.  Used by tests/test_gpu_parity.py. */
 int ibh_selftest_sort(const uint64_t *keys, int64_t n, int lo_bits, int hi_bits, uint32_t *perm_out, int *path_out);
+/* Diagnostics of the assembly's integer primitives (prims.hip), one primitive per call on the calling thread's
+ * per-thread stream; host buffers in and out.  Used by tests/test_gpu_prims.py.
+ * ibh_selftest_scan: kind 0 = u32, 1 = u8 (in: n bytes), 2 = three-channel scan of packed words (out: 3n values,
+ * channel by channel; total_out: 3 values).  out[i] = sum of in[0..i) mod 2^32; *total_out = the sum of all n.
+ * flags: IBH_SCAN_IN_PLACE (u32 only: input and output are one device buffer), IBH_SCAN_FRESH_STATE (free the
+ * thread's scan status buffer first), IBH_SCAN_NEAR_WRAP (move the status epoch to 2^30 - 2 first, so that the
+ * call after this one takes the 30-bit rollover). */
+#define IBH_SCAN_IN_PLACE     1
+#define IBH_SCAN_FRESH_STATE  2
+#define IBH_SCAN_NEAR_WRAP    4
+int ibh_selftest_scan(int kind, const void *in, int64_t n, uint32_t *out, uint32_t *total_out, int flags);
+/* The device-wide stable radix sort by `nfields` (shift, nbits) pairs, least significant field first, with
+ * payload 0..n-1: the permuted keys (all 64 bits) and the payload. */
+int ibh_selftest_radix_sort(const uint64_t *keys, int64_t n, const int32_t *fields, int nfields, uint64_t *keys_out,
+                            uint32_t *perm_out);
+/* As ibh_selftest_sort, and also the analysis: info_out = {flags, nchunks, maxlen, nsmall, nmid, nbig}.  try_pieces = 0:
+ * the flags-only analysis followed by the radix sort it plans (the low field is skipped when it never decreases). */
+int ibh_selftest_order(const uint64_t *keys, int64_t n, int lo_bits, int hi_bits, int try_pieces, uint32_t *perm_out,
+                       uint32_t *info_out, int *path_out);
 /* Return the build workspaces of ALL host threads (the caller's and the library's worker threads') and
  * all cached device blocks to the driver (the library keeps freed device memory for reuse: a coupler
  * rebuilds the same matrices every step).  Call it while no build is in flight. */

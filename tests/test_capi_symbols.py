@@ -111,16 +111,20 @@ def test_missing_rccl_is_enotimpl_not_a_crash(lib):
     assert int(rc) == _capi.IBH_ENOTIMPL and "needs RCCL" in msg and "/nonexistent/librccl.so" in msg, r.stdout
 
 
-def spmm_code_object_notes(tmp_path):
-    """The metadata notes of spmm.o's gfx950 code object: every kernel with its resource usage."""
+def code_object_notes(tmp_path, name):
+    """The metadata notes of the gfx950 code object in icebin_amd/lib/<name>.o: every kernel with its resource usage."""
     import subprocess
     llvm = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin")
-    obj = os.path.join(ROOT, "icebin_amd", "lib", "spmm.o")
-    fatbin, dev = str(tmp_path / "spmm.hip_fatbin"), str(tmp_path / "spmm_gfx950.o")
+    obj = os.path.join(ROOT, "icebin_amd", "lib", name + ".o")
+    fatbin, dev = str(tmp_path / (name + ".hip_fatbin")), str(tmp_path / (name + "_gfx950.o"))
     subprocess.run([os.path.join(llvm, "llvm-objcopy"), "--dump-section=.hip_fatbin=" + fatbin, obj, str(tmp_path / "host.o")], check=True)
     subprocess.run([os.path.join(llvm, "clang-offload-bundler"), "--unbundle", "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950",
                     "--input=" + fatbin, "--output=" + dev], check=True)
     return subprocess.run([os.path.join(llvm, "llvm-readelf"), "--notes", dev], check=True, capture_output=True, text=True).stdout
+
+
+def spmm_code_object_notes(tmp_path):
+    return code_object_notes(tmp_path, "spmm")
 
 
 def test_no_apply_kernel_uses_scratch_memory(lib, tmp_path):
@@ -170,3 +174,77 @@ def test_every_apply_kernel_has_a_recipe(lib, tmp_path):
     recipes = {r["name"] for r in akr.RECIPES}
     assert built == recipes, ("built without a recipe", sorted(built - recipes), "recipe without a kernel", sorted(recipes - built))
     print("%d apply-kernel instantiations, one recipe each" % len(built))
+
+
+PRIMS_TYPE_ARGS = {"j": "unsigned int", "h": "unsigned char", "t": "unsigned short", "i": "int", "m": "unsigned long", "y": "unsigned long long"}
+
+
+def prims_kernel_name(mangled):
+    """"_ZN3ibh12scan_chainedIjEEvPKT_..." -> "scan_chained<unsigned int>", "_ZN3ibh13oa_chunk_sortILi8192ELi4096ELi1024EEEv..." ->
+    "oa_chunk_sort<8192, 4096, 1024>", "_ZN3ibh7rs_histEPKm..." -> "rs_hist": a kernel of namespace ibh as the demangler spells it
+    (integer and builtin-type template arguments; anything else gives None)."""
+    m = re.match(r"_ZN3ibh(\d+)", mangled)
+    if not m:
+        return None
+    n = int(m.group(1))
+    name, rest = mangled[m.end():m.end() + n], mangled[m.end() + n:]
+    if rest.startswith("E"):
+        return name
+    m = re.match(r"I((?:Li\d+E|[a-z])+)EE", rest)
+    if not m:
+        return None
+    args = [a[2:-1] if a.startswith("L") else PRIMS_TYPE_ARGS.get(a, a) for a in re.findall(r"Li\d+E|[a-z]", m.group(1))]
+    return name + "<" + ", ".join(args) + ">"
+
+
+def test_every_prims_kernel_is_exercised(lib, tmp_path):
+    # tests/prims_kernel_cases.py names, for every kernel in prims.o, the case of tests/test_gpu_prims.py that runs it against an exact
+    # reference: a kernel built without a case, or a case for a kernel no longer built, fails here
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    try:
+        import prims_kernel_cases as pkc
+    finally:
+        sys.path.pop(0)
+    mangled = re.findall(r"^    \.name:\s+(\S+)", code_object_notes(tmp_path, "prims"), re.M)
+    built = {prims_kernel_name(m) for m in mangled}
+    assert None not in built and len(built) == len(mangled), (sorted(mangled), sorted(map(str, built)))
+    assert built == set(pkc.CASES), ("built without a case", sorted(built - set(pkc.CASES)), "case without a kernel",
+                                     sorted(set(pkc.CASES) - built))
+    module = open(os.path.join(ROOT, "tests", "test_gpu_prims.py")).read()
+    for kernel, case in pkc.CASES.items():
+        assert re.search(r"^def %s\(" % case, module, re.M), (kernel, case)
+
+
+# the ibh_selftest_* entries of the integer primitives validate every argument before they touch a device
+def test_selftest_scan_rejects_bad_arguments(lib):
+    import numpy as np
+    x = np.zeros(4, np.uint32)
+    out, tot = np.zeros(16, np.uint32), np.zeros(3, np.uint32)
+    for kind, n, flags in ((3, 4, 0), (-1, 4, 0), (0, -1, 0), (0, 1 << 31, 0), (1, 4, 1), (2, 4, 1), (0, 4, 8)):
+        rc = lib.ibh_selftest_scan(kind, x.ctypes.data, n, out.ctypes.data, tot.ctypes.data, flags)
+        assert rc == _capi.IBH_EINVAL, (kind, n, flags, rc)
+    assert lib.ibh_selftest_scan(0, x.ctypes.data, 4, out.ctypes.data, None, 0) == _capi.IBH_EINVAL
+
+
+def test_selftest_radix_sort_rejects_bad_fields(lib):
+    import numpy as np
+    k, kout, perm = np.arange(10, dtype=np.uint64), np.zeros(10, np.uint64), np.zeros(10, np.uint32)
+    for fields in ([(0, 0)], [(0, 33)], [(40, 25)], [(33, 32)], [(-1, 4)], [(0, 4)] * 9):
+        f = np.asarray(fields, np.int32).reshape(-1)
+        rc = lib.ibh_selftest_radix_sort(k.ctypes.data, 10, f.ctypes.data, len(fields), kout.ctypes.data, perm.ctypes.data)
+        assert rc == _capi.IBH_EINVAL, (fields, rc)
+    f = np.asarray([0, 8], np.int32)
+    assert lib.ibh_selftest_radix_sort(k.ctypes.data, -1, f.ctypes.data, 1, kout.ctypes.data, perm.ctypes.data) == _capi.IBH_EINVAL
+
+
+def test_selftest_order_rejects_bad_arguments(lib):
+    import ctypes as C
+    import numpy as np
+    perm, info, path = np.zeros(2, np.uint32), np.zeros(6, np.uint32), C.c_int(-1)
+    for keys, lo, hi in (([1 << 40, 3], 20, 8), ([1 << 20, 3], 20, 12), ([3, 1], 33, 0), ([3, 1], 8, -1)):
+        k = np.asarray(keys, np.uint64)
+        rc = lib.ibh_selftest_order(k.ctypes.data, 2, lo, hi, 1, perm.ctypes.data, info.ctypes.data, C.byref(path))
+        assert rc == _capi.IBH_EINVAL, (keys, lo, hi, rc)
+    k = np.asarray([3, 1], np.uint64)
+    assert lib.ibh_selftest_order(k.ctypes.data, 2, 20, 12, 2, perm.ctypes.data, info.ctypes.data, C.byref(path)) == _capi.IBH_EINVAL
