@@ -117,6 +117,12 @@ _SIGS = {
                                                         C.c_int64, C.c_double, C.c_void_p]),
     "ibh_weighted_apply_sharded_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int64,
                                                    C.c_double, C.c_int32, C.c_void_p]),
+    "ibh_regrid_matrices_matrix_d_sharded_sigma": (C.c_int, [C.c_void_p, C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                                             C.c_void_p, C.POINTER(C.c_void_p)]),
+    "ibh_weighted_apply_many_sharded_conserve_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int64,
+                                                                 C.c_void_p, C.c_int64, C.c_double, C.c_int, C.c_void_p]),
+    "ibh_weighted_apply_sharded_conserve_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p,
+                                                            C.c_int64, C.c_double, C.c_int, C.c_int32, C.c_void_p]),
     "ibh_weighted_apply_transformed_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p,
                                                        C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_double,
                                                        C.c_void_p]),

@@ -1052,14 +1052,15 @@ __global__ void k_smooth_bin_count(SmoothView v, uint32_t *__restrict__ bincnt, 
     if (v.area[d] == 0.0) atomicMin(bad, d);          // "Area of cell %ld must be non-zero", smoother.cpp:89-90
     atomicAdd(&bincnt[smooth_bin(v, c)], 1u);
 }
-__global__ void k_smooth_bin_fill(SmoothView v, const uint32_t *__restrict__ binstart, uint32_t *__restrict__ cursor,
-                                  int32_t *__restrict__ members) {
+// the members of every bin in ascending dense row: key = bin (nbins: masked, sorted past the last bin), value = row, ordered by
+// the stable radix sort.  The direct and tile forms sum in member order, so the order must not depend on atomics: with it, every
+// build -- on one rank or shared by several -- gives the same bits.
+__global__ void k_smooth_bin_keys(SmoothView v, uint32_t nbins, uint64_t *__restrict__ keys, uint32_t *__restrict__ rows) {
     const int d = blockIdx.x * blockDim.x + threadIdx.x;
     if (d >= v.n) return;
     double c[3];
-    if (!smooth_tuple(v, d, c)) return;
-    const int b = smooth_bin(v, c);
-    members[binstart[b] + atomicAdd(&cursor[b], 1u)] = d;      // order inside a bin is irrelevant: triplets are sorted later
+    keys[d] = smooth_tuple(v, d, c) ? (uint64_t)smooth_bin(v, c) : (uint64_t)nbins;
+    rows[d] = (uint32_t)d;
 }
 // pass 0: count neighbours of cell d; pass 1: emit (d<<32|j, w) at off[d]
 template <int PASS>
@@ -1285,18 +1286,20 @@ __global__ __launch_bounds__(SMD_WAVES * 64) void k_smooth_direct(SmoothView v, 
 // row i holds column c iff a neighbour within two sigmas does, exactly the reference's structure; the sums are divided by the
 // denominator at the end.  The bin's column table (the distinct columns of all members of its 3 x 3 neighbourhood, ascending) comes from a
 // small pre-kernel; a compaction kernel turns (presence, table) into CSR rows.  Sums run in candidate order (bin by bin,
-// member by member), fixed: reproducible; entries agree with the oracle's ascending-j order to rounding (the test's 1e-12).
+// member by member, the members of a bin in ascending row: k_smooth_bin_keys), fixed: reproducible; entries agree with the
+// oracle's ascending-j order to rounding (the test's 1e-12).
 // More than SMT_KMAX columns around a bin, or a member row of M with more than SMT_ROWMAX entries: the triplet pipeline serves
 // the build.
 constexpr int SMT_KMAX = 128, SMT_ROWMAX = 8, SMT_HASH = 1024;
 struct SmtCand { double x, y, z, area; };
 // compact records in member (bin) order: position / elevation / area, and the member's row of M entry-major
 // (mcol[e * nmem + q], mval[...]): the tile kernel stages them with coalesced, independent loads
-__global__ void k_smt_pack(SmoothView v, const int32_t *__restrict__ members, int nmem, const int32_t *__restrict__ rowptr,
+// (the member positions [q0, q1): a rank of a shared build packs the candidates of its own bins only)
+__global__ void k_smt_pack(SmoothView v, const int32_t *__restrict__ members, int q0, int q1, int nmem, const int32_t *__restrict__ rowptr,
                            const int32_t *__restrict__ colind, const double *__restrict__ val, SmtCand *__restrict__ cand,
                            unsigned char *__restrict__ mne, int32_t *__restrict__ mcol, double *__restrict__ mval) {
-    const int q = blockIdx.x * blockDim.x + threadIdx.x;
-    if (q >= nmem) return;
+    const int q = q0 + (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (q >= q1) return;
     const int d = members[q];
     double c[3];
     (void)smooth_tuple(v, d, c);
@@ -1362,7 +1365,7 @@ __global__ __launch_bounds__(64) void k_smt_tile(SmoothView v, const uint32_t *_
                                                  const SmtCand *__restrict__ cand, const unsigned char *__restrict__ mne,
                                                  const int32_t *__restrict__ mcol, const double *__restrict__ mval, int nmem,
                                                  const int32_t *__restrict__ bincols, const int32_t *__restrict__ binK,
-                                                 const uint32_t *__restrict__ wstart, const int32_t *__restrict__ wavebin, int kstride,
+                                                 const uint32_t *__restrict__ wstart, const int32_t *__restrict__ wavebin, int w0, int kstride,
                                                  double *__restrict__ scratch, unsigned long long *__restrict__ pres, uint32_t *__restrict__ rowlen) {
     extern __shared__ double smt_lds[];
     double *acc = smt_lds;                                       // [K][64]
@@ -1371,7 +1374,7 @@ __global__ __launch_bounds__(64) void k_smt_tile(SmoothView v, const uint32_t *_
     int *s_cols = reinterpret_cast<int *>(s_val + 64 * SMT_ROWMAX);                  // [SMT_KMAX]
     unsigned char *s_slot = reinterpret_cast<unsigned char *>(s_cols + SMT_KMAX);    // [64][SMT_ROWMAX]
     unsigned char *s_ne = s_slot + 64 * SMT_ROWMAX;             // [64]
-    const int w = blockIdx.x, lane = threadIdx.x;
+    const int w = w0 + (int)blockIdx.x, lane = threadIdx.x;       // (w0: the first wave of a rank's bins in a shared build)
     const int b = wavebin[w], bx = b % v.nbx, by = b / v.nbx;
     const int K = binK[b];
     const uint32_t q0 = binstart[b] + (uint32_t)(w - (int)wstart[b]) * 64u, qend = binstart[b + 1];
@@ -1459,17 +1462,18 @@ __global__ __launch_bounds__(64) void k_smt_tile(SmoothView v, const uint32_t *_
         rowlen[members[q0 + lane]] = (uint32_t)(__popcll(p0) + __popcll(p1));
     }
 }
-__global__ void k_smt_emit(const uint32_t *__restrict__ binstart, const int32_t *__restrict__ members, int nmem, const uint32_t *__restrict__ wstart,
+// rows of the member positions [q0, q1) -> at orowptr[row] (mpos == nullptr), or packed in member order at mpos[q] (a shared build)
+__global__ void k_smt_emit(const uint32_t *__restrict__ binstart, const int32_t *__restrict__ members, int q0, int q1, const uint32_t *__restrict__ wstart,
                            const int32_t *__restrict__ memberbin, const int32_t *__restrict__ bincols, int kstride, const double *__restrict__ scratch,
-                           const unsigned long long *__restrict__ pres, const int32_t *__restrict__ orowptr, int32_t *__restrict__ ocol,
-                           double *__restrict__ oval) {
-    const int q = blockIdx.x * blockDim.x + threadIdx.x;
-    if (q >= nmem) return;
+                           const unsigned long long *__restrict__ pres, const int32_t *__restrict__ orowptr, const uint32_t *__restrict__ mpos,
+                           int32_t *__restrict__ ocol, double *__restrict__ oval) {
+    const int q = q0 + (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (q >= q1) return;
     const int b = memberbin[q];
     const uint32_t rel = (uint32_t)q - binstart[b];
     const size_t w = wstart[b] + rel / 64;
     const int lane = (int)(rel & 63u);
-    int o = orowptr[members[q]];
+    int o = mpos ? (int)mpos[q] : orowptr[members[q]];
     for (int half = 0; half < 2; ++half) {
         unsigned long long m = pres[2 * (size_t)q + half];
         while (m) {
@@ -1486,13 +1490,41 @@ __global__ void k_smt_memberbin(const uint32_t *__restrict__ binstart, int nbins
     const int b = blockIdx.x;
     for (uint32_t q = binstart[b] + threadIdx.x; q < binstart[b + 1]; q += blockDim.x) memberbin[q] = b;
 }
+// ---- the tile form shared by the ranks of a communicator: rank k smooths the rows of a contiguous range of bins, the rows
+// travel in member order (positions [binstart[b0], binstart[b1]) of the bins' members), every rank places them into the CSR
+// row lengths of this rank's member positions [q0, q1), in member order
+__global__ void k_smt_mlen(const int32_t *__restrict__ members, int q0, int q1, const uint32_t *__restrict__ rowlen, uint32_t *__restrict__ mlen) {
+    const int q = q0 + (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (q < q1) mlen[q] = rowlen[members[q]];
+}
+// ... and back by row, for all members (rows of masked cells stay empty)
+__global__ void k_smt_rowlen(const int32_t *__restrict__ members, int nmem, const uint32_t *__restrict__ mlen, uint32_t *__restrict__ rowlen) {
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q < nmem) rowlen[members[q]] = mlen[q];
+}
+// the row of member q, packed at mptr[q], to its place in the CSR
+__global__ void k_smt_place(const int32_t *__restrict__ members, int nmem, const uint32_t *__restrict__ mlen, const uint32_t *__restrict__ mptr,
+                            const int32_t *__restrict__ orowptr, const int32_t *__restrict__ pcol, const double *__restrict__ pval,
+                            int32_t *__restrict__ ocol, double *__restrict__ oval) {
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= nmem) return;
+    const uint32_t s = mptr[q], len = mlen[q];
+    const int o = orowptr[members[q]];
+    for (uint32_t e = 0; e < len; ++e) { ocol[o + e] = pcol[s + e]; oval[o + e] = pval[s + e]; }
+}
 
-static void smooth_matrix(ibh_weighted *w, const ibh_regrid_matrices *rm, const int64_t *row_s, const double sigma[3],
-                          hipStream_t st) {
-    const ibh_regridder *g = rm->rg;
-    IBH_CHECK(g->has_centroid, "smoothing (sigma != 0) needs the ice grid's centroid_xy (ibh_regridder_desc.I_centroid_xy)");
+static void smooth_check(const ibh_regrid_matrices *rm, const double sigma[3]) {
+    IBH_CHECK(rm->rg->has_centroid, "smoothing (sigma != 0) needs the ice grid's centroid_xy (ibh_regridder_desc.I_centroid_xy)");
     IBH_CHECK(sigma[0] > 0 && sigma[1] > 0 && sigma[2] > 0, "smoothing needs three positive sigmas, got (%g, %g, %g)", sigma[0], sigma[1], sigma[2]);
+}
+// comm (world > 1): every rank of the communicator calls this with the same matrix; the tile form is shared (w->built_fast = 3),
+// the direct form and the triplet pipeline run on every rank.  The result is the same bits on every rank and for every world.
+static void smooth_matrix(ibh_weighted *w, const ibh_regrid_matrices *rm, const int64_t *row_s, const double sigma[3],
+                          hipStream_t st, ibh_comm *comm = nullptr) {
+    const ibh_regridder *g = rm->rg;
+    smooth_check(rm, sigma);
     if (w->nrow == 0) return;
+    const int world = comm ? comm_world(comm) : 1, rank = comm ? comm_rank(comm) : 0;
     Arena &A = arena();
     const int T = 256, n = w->nrow;
     SmoothView v{row_s, rm->elevmaskI.p, g->I_centroid.p, w->wM.p, n, sigma[0], sigma[1], sigma[2],
@@ -1502,18 +1534,21 @@ static void smooth_matrix(ibh_weighted *w, const ibh_regrid_matrices *rm, const 
     if (v.nbx == 4096) v.bw = (g->cmax[0] - g->cmin[0]) / 4096.0 * (1 + 1e-12);     // never finer than 4096 bins: bins only grow
     if (v.nby == 4096) v.bh = (g->cmax[1] - g->cmin[1]) / 4096.0 * (1 + 1e-12);
     const size_t nbins = (size_t)v.nbx * v.nby;
-    uint32_t *binstart = A.get<uint32_t>(nbins + 1), *cursor = A.get<uint32_t>(nbins);
-    int32_t *members = A.get<int32_t>((size_t)n);
+    uint32_t *binstart = A.get<uint32_t>(nbins + 1);
+    uint64_t *bkeys = A.get<uint64_t>((size_t)n), *bkeys2 = A.get<uint64_t>((size_t)n);
+    uint32_t *brows = A.get<uint32_t>((size_t)n), *brows2 = A.get<uint32_t>((size_t)n);
     uint32_t *d_cnt = A.get<uint32_t>(4);
     int *d_bad = reinterpret_cast<int *>(d_cnt + 3);
     const int big = 0x7fffffff;
     IBH_HIP(hipMemsetAsync(binstart, 0, sizeof(uint32_t) * (nbins + 1), st));
-    IBH_HIP(hipMemsetAsync(cursor, 0, sizeof(uint32_t) * nbins, st));
     IBH_HIP(hipMemcpyAsync(d_bad, &big, sizeof(int), hipMemcpyHostToDevice, st));
     const dim3 grid(ceil_div(n, T));
     hipLaunchKernelGGL(k_smooth_bin_count, grid, dim3(T), 0, st, v, binstart, d_bad);
     exclusive_scan_u32(binstart, binstart, nbins + 1, nullptr, st);
-    hipLaunchKernelGGL(k_smooth_bin_fill, grid, dim3(T), 0, st, v, binstart, cursor, members);
+    hipLaunchKernelGGL(k_smooth_bin_keys, grid, dim3(T), 0, st, v, (uint32_t)nbins, bkeys, brows);
+    const KeyField bf{0, bits_for((uint64_t)nbins + 1)};
+    if (bf.nbits > 0 && radix_sort_pairs(bkeys, bkeys2, brows, brows2, (size_t)n, &bf, 1, st)) std::swap(brows, brows2);
+    const int32_t *members = reinterpret_cast<const int32_t *>(brows);      // [binstart[nbins]] unmasked rows, bin by bin
     // (measured: 2 x faster than the triplet pipeline at 20 km -- 0.50 against 1.08 ms, that one is launch-bound there --
     // but slower at 5 km, 13 against 12 ms: three passes of ~3600 candidate evaluations per row, each five gathers; the
     // direct form is therefore taken for small problems only.  `smooth_direct`: 1 always, 0 never, -1 by size.)
@@ -1537,6 +1572,15 @@ static void smooth_matrix(ibh_weighted *w, const ibh_regrid_matrices *rm, const 
             IBH_HIP(hipMemcpy(&sc, row_s + (int)h4[3], sizeof(int64_t), hipMemcpyDeviceToHost));
             fail(IBH_EINVAL, "Area of cell %ld must be non-zero", (long)sc);
         }
+        if (world > 1) {                // the overflow flag is taken by all ranks together (it is a whole-grid quantity: equal anyway)
+            double *d_fl = A.get<double>((size_t)world);
+            const double mine = (double)h4[1];
+            IBH_HIP(hipMemcpyAsync(d_fl + rank, &mine, sizeof(double), hipMemcpyHostToDevice, st));
+            comm_exchange_blocks(comm, d_fl, 1, 1, st);
+            std::vector<double> fl((size_t)world);
+            readback_sync(fl.data(), d_fl, sizeof(double) * (size_t)world, st);
+            for (double f : fl) h4[1] |= (uint32_t)f;
+        }
         if (h4[1] == 0) {
             const int nwaves = (int)h4[0], nmem = (int)h4[2];
             std::vector<int32_t> hK(nbins);
@@ -1553,8 +1597,42 @@ static void smooth_matrix(ibh_weighted *w, const ibh_regrid_matrices *rm, const 
             int32_t *mcol = A.get<int32_t>((size_t)std::max(nmem, 1) * SMT_ROWMAX);
             double *mval = A.get<double>((size_t)std::max(nmem, 1) * SMT_ROWMAX);
             DevBuf<int32_t> nrowptr((size_t)n + 1);
+            // this rank's share: bins [b0, b1), their member positions [m0, m1) and waves [w0, w1); the candidates [c0, c1) it packs
+            int b0 = 0, b1 = nb, m0 = 0, m1 = nmem, w0 = 0, w1 = nwaves, c0 = 0, c1 = nmem;
+            std::vector<uint32_t> hb;
+            std::vector<int> bs;
+            if (world > 1) {
+                // contiguous bin ranges balanced by work: a bin costs its members times the candidates of its 3 x 3 neighbourhood
+                hb.resize(nbins + 1);
+                IBH_HIP(hipMemcpy(hb.data(), binstart, sizeof(uint32_t) * (nbins + 1), hipMemcpyDeviceToHost));
+                std::vector<double> cw(nbins + 1, 0.0);
+                for (int b = 0; b < nb; ++b) {
+                    const int bx = b % v.nbx, by = b / v.nbx;
+                    const int x0 = std::max(bx - 1, 0), x1 = std::min(bx + 1, v.nbx - 1);
+                    double ncand = 0;
+                    for (int yy = std::max(by - 1, 0); yy <= std::min(by + 1, v.nby - 1); ++yy)
+                        ncand += (double)(hb[(size_t)yy * v.nbx + x1 + 1] - hb[(size_t)yy * v.nbx + x0]);
+                    cw[(size_t)b + 1] = cw[(size_t)b] + (double)(hb[(size_t)b + 1] - hb[(size_t)b]) * ncand;
+                }
+                bs.assign((size_t)world + 1, nb);
+                bs[0] = 0;
+                for (int r = 1; r < world; ++r)
+                    bs[(size_t)r] = std::max(bs[(size_t)r - 1],
+                                             (int)(std::lower_bound(cw.begin(), cw.end(), cw[nbins] * r / world) - cw.begin()));
+                auto waves_before = [&](int bb) {
+                    uint32_t s = 0;
+                    for (int b = 0; b < bb; ++b) s += (hb[(size_t)b + 1] - hb[(size_t)b] + 63) / 64;
+                    return (int)s;
+                };
+                b0 = bs[(size_t)rank]; b1 = bs[(size_t)rank + 1];
+                m0 = (int)hb[(size_t)b0]; m1 = (int)hb[(size_t)b1];
+                w0 = waves_before(b0); w1 = waves_before(b1);
+                c0 = (int)hb[(size_t)std::max(b0 - v.nbx - 1, 0)]; c1 = (int)hb[(size_t)std::min(b1 + v.nbx + 1, nb)];
+            }
             if (nmem) {
-                hipLaunchKernelGGL(k_smt_pack, dim3(ceil_div(nmem, T)), dim3(T), 0, st, v, members, nmem, w->rowptr.p, w->colind.p, w->val.p, cand, mne, mcol, mval);
+                if (c1 > c0)
+                    hipLaunchKernelGGL(k_smt_pack, dim3(ceil_div(c1 - c0, T)), dim3(T), 0, st, v, members, c0, c1, nmem, w->rowptr.p, w->colind.p, w->val.p,
+                                       cand, mne, mcol, mval);
                 hipLaunchKernelGGL(k_smt_wavebin, dim3(ceil_div(nb, T)), dim3(T), 0, st, wstart, binwaves, nb, wavebin);
                 hipLaunchKernelGGL(k_smt_memberbin, dim3(nb), dim3(64), 0, st, binstart, nb, memberbin);
                 const size_t lds = (size_t)kmax * 64 * 8 + 64 * sizeof(SmtCand) + 64 * SMT_ROWMAX * 8 + SMT_KMAX * 4 + 64 * SMT_ROWMAX + 64;
@@ -1567,18 +1645,61 @@ static void smooth_matrix(ibh_weighted *w, const ibh_regrid_matrices *rm, const 
                         raised[w->device & 63] = true;
                     }
                 }
-                hipLaunchKernelGGL(k_smt_tile, dim3(nwaves), dim3(64), lds, st, v, binstart, members, cand, mne, mcol, mval, nmem, bincols, binK,
-                                   wstart, wavebin, kmax, scratch, pres, rowlen);
+                if (w1 > w0)
+                    hipLaunchKernelGGL(k_smt_tile, dim3(w1 - w0), dim3(64), lds, st, v, binstart, members, cand, mne, mcol, mval, nmem, bincols, binK,
+                                       wstart, wavebin, w0, kmax, scratch, pres, rowlen);
             }
-            exclusive_scan_u32(rowlen, reinterpret_cast<uint32_t *>(nrowptr.p), (size_t)n, d_cnt, st);
-            readback_sync(h4, d_cnt, sizeof(h4), st);
-            const uint32_t nnz2 = h4[0];
-            IBH_CHECK(nnz2 < (1u << 31), "smoothed matrix too large (%u entries)", nnz2);
-            IBH_HIP(hipMemcpyAsync(nrowptr.p + n, d_cnt, sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
-            DevBuf<int32_t> ncol((size_t)nnz2);
-            DevBuf<double> nval((size_t)nnz2);
-            if (nmem) hipLaunchKernelGGL(k_smt_emit, dim3(ceil_div(nmem, T)), dim3(T), 0, st, binstart, members, nmem, wstart, memberbin, bincols, kmax, scratch,
-                                         pres, nrowptr.p, ncol.p, nval.p);
+            DevBuf<int32_t> ncol;
+            DevBuf<double> nval;
+            uint32_t nnz2 = 0;
+            if (world == 1) {
+                exclusive_scan_u32(rowlen, reinterpret_cast<uint32_t *>(nrowptr.p), (size_t)n, d_cnt, st);
+                readback_sync(h4, d_cnt, sizeof(h4), st);
+                nnz2 = h4[0];
+                IBH_CHECK(nnz2 < (1u << 31), "smoothed matrix too large (%u entries)", nnz2);
+                IBH_HIP(hipMemcpyAsync(nrowptr.p + n, d_cnt, sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+                ncol.alloc((size_t)nnz2); nval.alloc((size_t)nnz2);
+                if (nmem) hipLaunchKernelGGL(k_smt_emit, dim3(ceil_div(nmem, T)), dim3(T), 0, st, binstart, members, 0, nmem, wstart, memberbin, bincols, kmax, scratch,
+                                             pres, nrowptr.p, (const uint32_t *)nullptr, ncol.p, nval.p);
+            } else {
+                // every rank's rows reach every rank: the row lengths in member order (gatherv) -> the row pointer and the
+                // member-order offsets (scans) -> the rows packed in member order (gatherv) -> placed into the CSR
+                uint32_t *mlen = A.get<uint32_t>((size_t)nmem + 1), *mptr = A.get<uint32_t>((size_t)nmem + 1);
+                if (m1 > m0) hipLaunchKernelGGL(k_smt_mlen, dim3(ceil_div(m1 - m0, T)), dim3(T), 0, st, members, m0, m1, rowlen, mlen);
+                std::vector<int64_t> ol((size_t)world + 1), oc((size_t)world + 1), ov((size_t)world + 1);
+                for (int r = 0; r <= world; ++r) ol[(size_t)r] = 4 * (int64_t)hb[(size_t)bs[(size_t)r]];
+                {
+                    void *bases[1] = {mlen};
+                    const int64_t *offs[1] = {ol.data()};
+                    comm_gatherv(comm, 1, bases, offs, st);
+                }
+                if (nmem) hipLaunchKernelGGL(k_smt_rowlen, dim3(ceil_div(nmem, T)), dim3(T), 0, st, members, nmem, mlen, rowlen);
+                exclusive_scan_u32(rowlen, reinterpret_cast<uint32_t *>(nrowptr.p), (size_t)n, d_cnt, st);
+                exclusive_scan_u32(mlen, mptr, (size_t)nmem, mptr + nmem, st);
+                IBH_HIP(hipMemcpyAsync(nrowptr.p + n, d_cnt, sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+                std::vector<uint32_t> hp((size_t)world + 1);
+                for (int r = 0; r <= world; ++r)
+                    IBH_HIP(hipMemcpyAsync(&hp[(size_t)r], mptr + hb[(size_t)bs[(size_t)r]], sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+                IBH_HIP(hipStreamSynchronize(st));
+                nnz2 = hp[(size_t)world];
+                IBH_CHECK(nnz2 < (1u << 31), "smoothed matrix too large (%u entries)", nnz2);
+                for (int r = 0; r <= world; ++r) { oc[(size_t)r] = 4 * (int64_t)hp[(size_t)r]; ov[(size_t)r] = 8 * (int64_t)hp[(size_t)r]; }
+                DevBuf<int32_t> pcol((size_t)nnz2);
+                DevBuf<double> pval((size_t)nnz2);
+                if (m1 > m0) hipLaunchKernelGGL(k_smt_emit, dim3(ceil_div(m1 - m0, T)), dim3(T), 0, st, binstart, members, m0, m1, wstart, memberbin, bincols, kmax,
+                                                scratch, pres, (const int32_t *)nullptr, mptr, pcol.p, pval.p);
+                {
+                    void *bases[2] = {pcol.p, pval.p};
+                    const int64_t *offs[2] = {oc.data(), ov.data()};
+                    comm_gatherv(comm, 2, bases, offs, st);
+                }
+                ncol.alloc((size_t)nnz2); nval.alloc((size_t)nnz2);
+                if (nmem) hipLaunchKernelGGL(k_smt_place, dim3(ceil_div(nmem, T)), dim3(T), 0, st, members, nmem, mlen, mptr, nrowptr.p, pcol.p, pval.p,
+                                             ncol.p, nval.p);
+                IBH_HIP(hipGetLastError());
+                IBH_HIP(hipStreamSynchronize(st));          // (pcol / pval are freed on leaving this scope)
+                w->built_fast = 3;
+            }
             IBH_HIP(hipGetLastError());
             IBH_HIP(hipStreamSynchronize(st));
             w->rowptr = std::move(nrowptr); w->colind = std::move(ncol); w->val = std::move(nval);
@@ -2164,8 +2285,25 @@ bool assemble_matrix(const ibh_regrid_matrices *rm, const char *spec_name, ibh_s
     // sorted exchange grid + dims shapes it covers: the plan-based fast path (fastasm.inl); smoothing and the
     // band structure work on intermediates of the general pipeline
     const bool bands_wanted = sp->row_key == KEY_E && (sp->col_key == KEY_I || sp->col_key == KEY_X) && get_tuning("assemble_bands", 0);
-    if (!smooth && !bands_wanted && fast_build(rm, sp, dims, scale, correctA, rg, w.get(), st, comm)) {
+    // A SHARED smoothed build (comm): the unsmoothed matrix from the shared build -- the same bits as the general pipeline's --
+    // then the smoothing, shared as well, over the row cells of its own row set
+    if (smooth && comm) smooth_check(rm, sigma);
+    if ((!smooth || comm) && !bands_wanted && fast_build(rm, sp, dims, scale, correctA, rg, w.get(), st, comm)) {
         if (!w->built_fast) w->built_fast = 1;          // (2: the streamed build, set by stream_build)
+        if (smooth) {
+            w->built_fast = 1;                          // (3 again when the smoothing is shared as well)
+            const ibh_sparse_set *rs = dims[0];
+            DevBuf<int64_t> row_s;
+            if (rs->identity) {                         // (the coupler's dimI)
+                row_s.alloc((size_t)w->nrow);
+                hipLaunchKernelGGL(k_iota_i64, dim3(ceil_div(w->nrow, 256)), dim3(256), 0, st, row_s.p, (size_t)w->nrow);
+            } else if (rs->dev_n < w->nrow) {
+                rs->ensure_host();
+                row_s.alloc((size_t)w->nrow);
+                IBH_HIP(hipMemcpyAsync(row_s.p, rs->host.data(), sizeof(int64_t) * (size_t)w->nrow, hipMemcpyHostToDevice, st));
+            }
+            smooth_matrix(w.get(), rm, row_s.p ? row_s.p : rs->dev.p, sigma, st, comm);
+        }
         *out = w.release();
         return true;
     }
@@ -2274,7 +2412,7 @@ bool assemble_matrix(const ibh_regrid_matrices *rm, const char *spec_name, ibh_s
         hipLaunchKernelGGL(k_scale, dim3(ceil_div(nnz, T)), dim3(T), 0, st, row, w->colind.p, w->val.p, nnz, rowmul, colmul,
                            apply_row, apply_col);
     IBH_HIP(hipGetLastError());
-    if (smooth) smooth_matrix(w.get(), rm, rset.to_sparse, sigma, st);
+    if (smooth) smooth_matrix(w.get(), rm, rset.to_sparse, sigma, st, comm);
     // E-row matrices over ice / exchange columns: band structure for the apply (after the scaling: exact
     // copies of M).  Opt-in (ibh_set_tuning("assemble_bands", 1)): it costs +25-35 % of the build and
     // buys -16 % on a 1 km apply, nothing at 5 km -- right for a matrix that is applied to many field

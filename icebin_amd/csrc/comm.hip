@@ -319,8 +319,11 @@ int ibh_comm_wait(ibh_comm *c, void *stream) {
     });
 }
 
-int ibh_weighted_apply_sharded_device(const ibh_weighted *w, ibh_comm *c, const double *dA_local, int32_t nvar_local, int64_t lda,
-                                      double *dB_all, int64_t ldb, double fill, int32_t block_fields, void *stream) {
+// force_conservation: every rank holds whole fields, so the correction factor of a field is local -- applied to each field block
+// by the SpMM launch, before the block travels (spmm_launch_many; a conservative matrix ignores the flag)
+int ibh_weighted_apply_sharded_conserve_device(const ibh_weighted *w, ibh_comm *c, const double *dA_local, int32_t nvar_local, int64_t lda,
+                                               double *dB_all, int64_t ldb, double fill, int force_conservation, int32_t block_fields,
+                                               void *stream) {
     return guarded([&] {
         IBH_CHECK(w && c && nvar_local >= 0 && (nvar_local == 0 || (dA_local && dB_all)), "bad arguments");
         int dev = -1;
@@ -347,7 +350,7 @@ int ibh_weighted_apply_sharded_device(const ibh_weighted *w, ibh_comm *c, const 
         order_behind_flights(c, dB_all, dB_all + (int64_t)c->world * stride, st);
         for (int f0 = 0; f0 < nvar_local; f0 += bf) {
             const int nb = std::min(bf, nvar_local - f0);
-            spmm_launch(w, dA_local + (int64_t)f0 * lda, nb, lda, mine + (int64_t)f0 * ldb, ldb, fill, 0, st);
+            spmm_launch(w, dA_local + (int64_t)f0 * lda, nb, lda, mine + (int64_t)f0 * ldb, ldb, fill, force_conservation, st);
             if (c->world > 1) {
                 IBH_HIP(hipEventRecord(c->ready, st));
                 IBH_HIP(hipStreamWaitEvent(c->xs, c->ready, 0));
@@ -359,8 +362,14 @@ int ibh_weighted_apply_sharded_device(const ibh_weighted *w, ibh_comm *c, const 
     });
 }
 
-int ibh_weighted_apply_many_sharded_device(const ibh_weighted *w, ibh_comm *c, int32_t nbatch, const double *const *dA_local,
-                                           int32_t nvar_local, int64_t lda, double *const *dB_all, int64_t ldb, double fill, void *stream) {
+int ibh_weighted_apply_sharded_device(const ibh_weighted *w, ibh_comm *c, const double *dA_local, int32_t nvar_local, int64_t lda,
+                                      double *dB_all, int64_t ldb, double fill, int32_t block_fields, void *stream) {
+    return ibh_weighted_apply_sharded_conserve_device(w, c, dA_local, nvar_local, lda, dB_all, ldb, fill, 0, block_fields, stream);
+}
+
+int ibh_weighted_apply_many_sharded_conserve_device(const ibh_weighted *w, ibh_comm *c, int32_t nbatch, const double *const *dA_local,
+                                                    int32_t nvar_local, int64_t lda, double *const *dB_all, int64_t ldb, double fill,
+                                                    int force_conservation, void *stream) {
     return guarded([&] {
         IBH_CHECK(w && c && nbatch >= 0 && nvar_local >= 0 && (nbatch == 0 || nvar_local == 0 || (dA_local && dB_all)), "bad arguments");
         int dev = -1;
@@ -379,7 +388,7 @@ int ibh_weighted_apply_many_sharded_device(const ibh_weighted *w, ibh_comm *c, i
         const double *lo = dB_all[0], *hi = dB_all[0];
         for (int q = 0; q < nbatch; ++q) { lo = std::min<const double *>(lo, dB_all[q]); hi = std::max<const double *>(hi, dB_all[q] + (int64_t)c->world * stride); }
         order_behind_flights(c, lo, hi, st);
-        spmm_launch_many(w, nbatch, dA_local, nvar_local, lda, mine.data(), ldb, fill, 0, st);
+        spmm_launch_many(w, nbatch, dA_local, nvar_local, lda, mine.data(), ldb, fill, force_conservation, st);
         if (c->world > 1) {
             IBH_HIP(hipEventRecord(c->ready, st));
             IBH_HIP(hipStreamWaitEvent(c->xs, c->ready, 0));
@@ -387,6 +396,11 @@ int ibh_weighted_apply_many_sharded_device(const ibh_weighted *w, ibh_comm *c, i
             record_flight(c, lo, hi, st);
         }
     });
+}
+
+int ibh_weighted_apply_many_sharded_device(const ibh_weighted *w, ibh_comm *c, int32_t nbatch, const double *const *dA_local,
+                                           int32_t nvar_local, int64_t lda, double *const *dB_all, int64_t ldb, double fill, void *stream) {
+    return ibh_weighted_apply_many_sharded_conserve_device(w, c, nbatch, dA_local, nvar_local, lda, dB_all, ldb, fill, 0, stream);
 }
 
 }  // extern "C"

@@ -156,10 +156,13 @@ class FieldShardedApply:
     `ops` carries the stream/event plumbing (CudaOps on a GPU, HostOps under gloo) and
     `local_apply(x, y)` / `local_apply_many(xs, ys)` the rank-local SpMM writing into y: by default
     the C-ABI device apply of `weighted`; the CPU tests inject the oracle, so the buffer layout, the
-    group choreography and the collectives of THIS class run with world > 1 on gloo."""
+    group choreography and the collectives of THIS class run with world > 1 on gloo.
+
+    force_conservation: the default local applies correct every field of a non-conservative (smoothed) matrix, as
+    Weighted.apply(force_conservation=True) does -- the factor of a field is local to the rank that holds it."""
 
     def __init__(self, weighted, nf_total, group=None, device=None, steps_per_gather=1, ops=None,
-                 local_apply=None, local_apply_many=None, nrow=None, ncol=None):
+                 local_apply=None, local_apply_many=None, nrow=None, ncol=None, force_conservation=False):
         self.w, self.nf_total, self.group = weighted, nf_total, group
         self.world, self.rank = dist.get_world_size(group), dist.get_rank(group)
         self.f0, self.f1 = field_shard(nf_total, self.world, self.rank)
@@ -191,9 +194,10 @@ class FieldShardedApply:
             from . import _capi
             L = _capi.lib()
             h, check, nrow_, ld_ = weighted._h, _capi.check, nrow, ld
+            fc = int(bool(force_conservation))
 
             def local_apply(x_ptr, ldx, y, fill, stream_h):
-                rc = L.ibh_weighted_apply_device(h, C.c_void_p(x_ptr), nl, ldx, C.c_void_p(y.data_ptr()), ld_, fill, 0,
+                rc = L.ibh_weighted_apply_device(h, C.c_void_p(x_ptr), nl, ldx, C.c_void_p(y.data_ptr()), ld_, fill, fc,
                                                  C.c_void_p(stream_h))
                 if rc != 0:
                     check(rc)
@@ -202,7 +206,7 @@ class FieldShardedApply:
                 m = len(x_ptrs)
                 xa = (C.c_void_p * m)(*x_ptrs)
                 ya = (C.c_void_p * m)(*[y.data_ptr() for y in ys])
-                rc = L.ibh_weighted_apply_many_device(h, m, xa, nl, ldx, ya, ld_, fill, 0, C.c_void_p(stream_h))
+                rc = L.ibh_weighted_apply_many_device(h, m, xa, nl, ldx, ya, ld_, fill, fc, C.c_void_p(stream_h))
                 if rc != 0:
                     check(rc)
         self._apply, self._apply_many = local_apply, local_apply_many
@@ -400,9 +404,11 @@ class Communicator:
         self._capi.check(self._capi.lib().ibh_comm_wait(self._h, self._C.c_void_p(s)))
 
 
-def apply_sharded(weighted, comm, x_local, out_all=None, fill=float("nan"), block_fields=0, stream=None):
-    """ibh_weighted_apply_sharded_device: x_local [nvar_local, ncol_d] (torch.float64, CUDA) -> out_all
-    [world * nvar_local, nrow_d] on every rank (rows padded to 512 bytes when allocated here); complete after comm.wait()."""
+def apply_sharded(weighted, comm, x_local, out_all=None, fill=float("nan"), block_fields=0, stream=None, force_conservation=False):
+    """ibh_weighted_apply_sharded_conserve_device: x_local [nvar_local, ncol_d] (torch.float64, CUDA) -> out_all
+    [world * nvar_local, nrow_d] on every rank (rows padded to 512 bytes when allocated here); complete after comm.wait().
+    force_conservation: each rank corrects its own fields of a non-conservative (smoothed) matrix before they travel, as
+    Weighted.apply(force_conservation=True)."""
     import ctypes as C
     from . import _capi
     assert x_local.is_cuda and x_local.dtype == torch.float64 and x_local.dim() == 2 and x_local.stride(1) == 1
@@ -412,15 +418,16 @@ def apply_sharded(weighted, comm, x_local, out_all=None, fill=float("nan"), bloc
         out_all = torch.zeros((comm.world * nl, ld), dtype=torch.float64, device=x_local.device)[:, : weighted.nrow_d]
     assert out_all.shape == (comm.world * nl, weighted.nrow_d) and out_all.stride(1) == 1
     s = torch.cuda.current_stream(x_local.device).cuda_stream if stream is None else stream
-    _capi.check(_capi.lib().ibh_weighted_apply_sharded_device(
+    _capi.check(_capi.lib().ibh_weighted_apply_sharded_conserve_device(
         weighted._h, comm._h, C.c_void_p(x_local.data_ptr()), nl, max(x_local.stride(0), weighted.ncol_d), C.c_void_p(out_all.data_ptr()),
-        max(out_all.stride(0), weighted.nrow_d), float(fill), int(block_fields), C.c_void_p(s)))
+        max(out_all.stride(0), weighted.nrow_d), float(fill), int(bool(force_conservation)), int(block_fields), C.c_void_p(s)))
     return out_all
 
 
-def apply_many_sharded(weighted, comm, xs_local, outs_all, fill=float("nan"), stream=None):
-    """ibh_weighted_apply_many_sharded_device: len(xs_local) field batches through ONE SpMM launch and ONE grouped exchange;
-    outs_all: list of [world * nvar_local, nrow_d] result arrays (all with the same row stride)."""
+def apply_many_sharded(weighted, comm, xs_local, outs_all, fill=float("nan"), stream=None, force_conservation=False):
+    """ibh_weighted_apply_many_sharded_conserve_device: len(xs_local) field batches through ONE SpMM launch and ONE grouped
+    exchange; outs_all: list of [world * nvar_local, nrow_d] result arrays (all with the same row stride).  force_conservation:
+    as apply_sharded."""
     import ctypes as C
     from . import _capi
     nb = len(xs_local)
@@ -433,7 +440,8 @@ def apply_many_sharded(weighted, comm, xs_local, outs_all, fill=float("nan"), st
     xa = (C.c_void_p * nb)(*[x.data_ptr() for x in xs_local])
     oa = (C.c_void_p * nb)(*[o.data_ptr() for o in outs_all])
     s = torch.cuda.current_stream(xs_local[0].device).cuda_stream if stream is None else stream
-    _capi.check(_capi.lib().ibh_weighted_apply_many_sharded_device(weighted._h, comm._h, nb, xa, nl, lda, oa, ldb, float(fill), C.c_void_p(s)))
+    _capi.check(_capi.lib().ibh_weighted_apply_many_sharded_conserve_device(weighted._h, comm._h, nb, xa, nl, lda, oa, ldb, float(fill),
+                                                                            int(bool(force_conservation)), C.c_void_p(s)))
     return outs_all
 
 
@@ -441,13 +449,14 @@ class CabiFieldShardedApply:
     """The interface bench.py drives (FieldShardedApply: apply_ptr / apply_many_ptr / flush / wait / result) over the C-ABI
     path: ibh_weighted_apply_(many_)sharded_device on a Communicator -- the library calls RCCL itself, as a C++ host would use
     it.  Equal shards only; two alternating result arrays per group slot, so the exchange of group g overlaps the SpMMs of
-    group g+1 (the library orders work by the address ranges in flight)."""
+    group g+1 (the library orders work by the address ranges in flight).  force_conservation: as apply_sharded."""
 
-    def __init__(self, weighted, nf_total, comm, device, steps_per_gather=1):
+    def __init__(self, weighted, nf_total, comm, device, steps_per_gather=1, force_conservation=False):
         import ctypes as C
         from . import _capi
         self._C, self._capi, self._L = C, _capi, _capi.lib()
         self.w, self.comm, self.G = weighted, comm, int(steps_per_gather)
+        self.fc = int(bool(force_conservation))
         assert nf_total % comm.world == 0, "the C-ABI sharded apply takes equal shards"
         self.nl, self.nf_total = nf_total // comm.world, nf_total
         self.nrow, self.ncol = weighted.nrow_d, weighted.ncol_d
@@ -466,15 +475,17 @@ class CabiFieldShardedApply:
         assert 1 <= m <= self.G - slot
         xa = (C.c_void_p * m)(*x_ptrs)
         oa = (C.c_void_p * m)(*[self._out[g][slot + s].data_ptr() for s in range(m)])
-        self._capi.check(self._L.ibh_weighted_apply_many_sharded_device(self.w._h, self.comm._h, m, xa, self.nl, ldx, oa, self.ld, fill, self._stream()))
+        self._capi.check(self._L.ibh_weighted_apply_many_sharded_conserve_device(self.w._h, self.comm._h, m, xa, self.nl, ldx, oa, self.ld, fill,
+                                                                                 self.fc, self._stream()))
         self._i = i + m
         return g, slot
 
     def apply_ptr(self, x_ptr, ldx, fill=float("nan")):
         C, i = self._C, self._i
         g, slot = (i // self.G) & 1, i % self.G
-        self._capi.check(self._L.ibh_weighted_apply_sharded_device(self.w._h, self.comm._h, C.c_void_p(x_ptr), self.nl, ldx,
-                                                                   C.c_void_p(self._out[g][slot].data_ptr()), self.ld, fill, 0, self._stream()))
+        self._capi.check(self._L.ibh_weighted_apply_sharded_conserve_device(self.w._h, self.comm._h, C.c_void_p(x_ptr), self.nl, ldx,
+                                                                            C.c_void_p(self._out[g][slot].data_ptr()), self.ld, fill, self.fc, 0,
+                                                                            self._stream()))
         self._i = i + 1
         return g, slot
 

@@ -360,12 +360,26 @@ public:
                               double fill, void *stream, int block_fields = 0) const {
         check(ibh_weighted_apply_sharded_device(h_, comm.handle(), dA_local, nvar_local, lda, dB_all, ldb, fill, block_fields, stream));
     }
+    /** the same with apply_device's force_conservation: each rank corrects its own fields before they travel
+        (ibh_weighted_apply_sharded_conserve_device; a conservative matrix ignores the flag) */
+    void apply_sharded_device(Communicator const &comm, const double *dA_local, int nvar_local, long lda, double *dB_all, long ldb,
+                              double fill, bool force_conservation, void *stream, int block_fields = 0) const {
+        check(ibh_weighted_apply_sharded_conserve_device(h_, comm.handle(), dA_local, nvar_local, lda, dB_all, ldb, fill,
+                                                         force_conservation ? 1 : 0, block_fields, stream));
+    }
     /** several field batches: ONE SpMM launch, ONE grouped exchange (ibh_weighted_apply_many_sharded_device) */
     void apply_many_sharded_device(Communicator const &comm, std::vector<const double *> const &dA_local, int nvar_local, long lda,
                                    std::vector<double *> const &dB_all, long ldb, double fill, void *stream) const {
         if (dA_local.size() != dB_all.size()) throw Exception(IBH_EINVAL, "apply_many_sharded_device: batch lists differ in length");
         check(ibh_weighted_apply_many_sharded_device(h_, comm.handle(), (int32_t)dA_local.size(), dA_local.data(), nvar_local, lda,
                                                      dB_all.data(), ldb, fill, stream));
+    }
+    /** ... with force_conservation (ibh_weighted_apply_many_sharded_conserve_device) */
+    void apply_many_sharded_device(Communicator const &comm, std::vector<const double *> const &dA_local, int nvar_local, long lda,
+                                   std::vector<double *> const &dB_all, long ldb, double fill, bool force_conservation, void *stream) const {
+        if (dA_local.size() != dB_all.size()) throw Exception(IBH_EINVAL, "apply_many_sharded_device: batch lists differ in length");
+        check(ibh_weighted_apply_many_sharded_conserve_device(h_, comm.handle(), (int32_t)dA_local.size(), dA_local.data(), nvar_local,
+                                                              lda, dB_all.data(), ldb, fill, force_conservation ? 1 : 0, stream));
     }
     /** Device-resident variant: dA_b (nvar x lda) and dB_b (nvar x ldb) are HBM pointers; enqueues on stream. */
     void apply_device(const double *dA_b, int nvar, long lda, double *dB_b, long ldb, double fill,
@@ -455,13 +469,14 @@ public:
         return std::unique_ptr<linear::Weighted_Eigen>(new linear::Weighted_Eigen(w));
     }
     /** matrix_d with the ASSEMBLY shared by the ranks of `comm` (ibh_regrid_matrices_matrix_d_sharded): collective -- every rank
-        makes the same call -- and every rank receives the whole matrix, bitwise what matrix_d builds.  Smoothing is not shared
-        (params.sigma must be zero here). */
+        makes the same call -- and every rank receives the whole matrix, bitwise what matrix_d builds, smoothed by params.sigma
+        (IvA / IvE; ibh_regrid_matrices_matrix_d_sharded_sigma: the smoothing's spatial-tile form is shared too). */
     std::unique_ptr<linear::Weighted_Eigen> matrix_d_sharded(Communicator const &comm, std::string const &spec_name,
                                                              std::array<SparseSetT *, 2> dims, RegridParams const &params) const {
         ibh_weighted *w = nullptr;
-        check(ibh_regrid_matrices_matrix_d_sharded(h_, comm.handle(), spec_name.c_str(), dims[0] ? dims[0]->handle() : nullptr,
-                                                   dims[1] ? dims[1]->handle() : nullptr, params.scale, params.correctA, &w));
+        check(ibh_regrid_matrices_matrix_d_sharded_sigma(h_, comm.handle(), spec_name.c_str(), dims[0] ? dims[0]->handle() : nullptr,
+                                                         dims[1] ? dims[1]->handle() : nullptr, params.scale, params.correctA,
+                                                         params.sigma.data(), &w));
         return std::unique_ptr<linear::Weighted_Eigen>(new linear::Weighted_Eigen(w));
     }
     /** The matrices of one coupling step in one call (IceCoupler.cpp:361-468 builds EvI, AvI, IvE, XvE every step): the

@@ -44,14 +44,17 @@ class RegridMatrices:
         return linear_Weighted(h, keep=(self, dims))
 
 
-    def matrix_d_sharded(self, comm, spec_name, dims=(None, None), scale=True, correctA=False):
-        """ibh_regrid_matrices_matrix_d_sharded: matrix_d with the assembly shared by the ranks of `comm`
+    def matrix_d_sharded(self, comm, spec_name, dims=(None, None), scale=True, correctA=False, sigma=(0., 0., 0.)):
+        """ibh_regrid_matrices_matrix_d_sharded(_sigma): matrix_d with the assembly shared by the ranks of `comm`
         (icebin_amd.distributed.Communicator).  Collective -- every rank makes the same call -- and every rank receives the whole
-        matrix, bitwise what matrix_d builds."""
+        matrix, bitwise what matrix_d builds.  sigma != 0 (IvA / IvE): the smoothing is shared as well when it takes its
+        spatial-tile form (built_fast() == 3)."""
+        sig = np.asarray(sigma, np.float64)
         h = C.c_void_p()
         d0 = dims[0]._h if dims[0] is not None else None
         d1 = dims[1]._h if dims[1] is not None else None
-        check(lib().ibh_regrid_matrices_matrix_d_sharded(self._h, comm._h, spec_name.encode(), d0, d1, int(scale), int(correctA), C.byref(h)))
+        check(lib().ibh_regrid_matrices_matrix_d_sharded_sigma(self._h, comm._h, spec_name.encode(), d0, d1, int(scale), int(correctA),
+                                                              ptr(sig), C.byref(h)))
         return linear_Weighted(h, keep=(self, dims))
 
     def matrix_batch(self, jobs, sigma=None):

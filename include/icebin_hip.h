@@ -352,7 +352,8 @@ int ibh_comm_info(const ibh_comm *c, int *world, int *rank);
  * (0: chosen by size -- one exchange for KB-sized results, blocks of >= 8 fields and ~128 MB for the GB-sized results of
  * the I-row matrices) so that it overlaps the SpMM of the following block and of the following apply.  dB_all is complete once
  * ibh_comm_wait(c, s) has made stream s wait for the exchanges enqueued so far.  Same results as ibh_weighted_apply_device
- * on each rank's fields (bitwise), conservative matrices only (no force_conservation).
+ * on each rank's fields (bitwise), without the conservation correction: a smoothed (non-conservative) matrix needs
+ * ibh_weighted_apply_sharded_conserve_device.
  * ldb > nrow_d: a true leading dimension (a column view of a larger array) unless the communicator says otherwise -- every plane
  * travels by itself and nothing outside [0, nrow_d) of a plane is touched on any rank; ibh_comm_set_option(c, "planes_padded", 1)
  * declares the gap padding owned by the caller, the planes of a block then travel as one piece (fewer, larger transfers).
@@ -368,6 +369,16 @@ int ibh_weighted_apply_sharded_device(const ibh_weighted *w, ibh_comm *c, const 
 int ibh_weighted_apply_many_sharded_device(const ibh_weighted *w, ibh_comm *c, int32_t nbatch, const double *const *dA_local,
                                            int32_t nvar_local, int64_t lda, double *const *dB_all, int64_t ldb, double fill,
                                            void *stream);
+/* The two sharded applies with force_conservation (ibh_weighted_apply_device's): every rank holds whole fields, so the factor
+ * (Mw . A_k) / (wM . B_k) of field k is local -- each field block is corrected on its rank before it travels, no collective.
+ * Bitwise ibh_weighted_apply_device(force_conservation) on each rank's fields; a conservative matrix ignores the flag, and
+ * force_conservation = 0 is the call above. */
+int ibh_weighted_apply_sharded_conserve_device(const ibh_weighted *w, ibh_comm *c, const double *dA_local, int32_t nvar_local,
+                                               int64_t lda, double *dB_all, int64_t ldb, double fill, int force_conservation,
+                                               int32_t block_fields, void *stream);
+int ibh_weighted_apply_many_sharded_conserve_device(const ibh_weighted *w, ibh_comm *c, int32_t nbatch, const double *const *dA_local,
+                                                    int32_t nvar_local, int64_t lda, double *const *dB_all, int64_t ldb, double fill,
+                                                    int force_conservation, void *stream);
 int ibh_comm_wait(ibh_comm *c, void *stream);
 /* RegridMatrices_Dynamic::matrix_d with the ASSEMBLY shared by the ranks of a communicator (BASELINE.json config 5: "overlap
  * COO->CSR assembly + apply, 8 x MI355X"; the reference rebuilds its matrices every coupling step, IceCoupler.cpp:361-468, on one
@@ -382,9 +393,18 @@ int ibh_comm_wait(ibh_comm *c, void *stream);
  * is scanned, the rows travel in first-seen order and are copied to their places), a pre-populated dimE as the column set (looked
  * up in the table every rank has; the column sums travel as pairs) --, sorted grids, at most 8 ranks; anything else (EvA / AvE, a
  * pre-populated row set, unsorted grids) is built redundantly on every rank (same result).  ibh_weighted_built_fast reports 3 for a shared build.  A custom transport needs
- * ibh_comm_set_custom_gatherv. */
+ * ibh_comm_set_custom_gatherv.  No smoothing: ibh_regrid_matrices_matrix_d_sharded_sigma. */
 int ibh_regrid_matrices_matrix_d_sharded(const ibh_regrid_matrices *rm, ibh_comm *c, const char *spec, ibh_sparse_set *dim0,
                                          ibh_sparse_set *dim1, int scale, int correctA, ibh_weighted **out);
+/* The same with RegridParams' sigma (IvA / IvE smoothed, as the coupler's IvE, IceCoupler.cpp:461-463): bitwise
+ * ibh_regrid_matrices_matrix_d(..., sigma) on every rank, conservative = 0.  The unsmoothed matrix comes from the shared build
+ * above; the smoothing's spatial-tile form (grids of more than ibh_set_tuning "smooth_direct_max_rows" rows) is shared too --
+ * rank k smooths the rows of a contiguous range of spatial bins balanced by work, the rows travel through the gatherv --, its
+ * direct form and the triplet pipeline run on every rank.  ibh_weighted_built_fast: 3 when the smoothing was shared, 1 when it
+ * ran on every rank.  sigma NULL or zero: ibh_regrid_matrices_matrix_d_sharded.  Refusals as matrix_d: smoothing of an X-row
+ * matrix IBH_ENOTIMPL; a sigma component <= 0 or no ice-grid centroids IBH_EINVAL. */
+int ibh_regrid_matrices_matrix_d_sharded_sigma(const ibh_regrid_matrices *rm, ibh_comm *c, const char *spec, ibh_sparse_set *dim0,
+                                               ibh_sparse_set *dim1, int scale, int correctA, const double sigma[3], ibh_weighted **out);
 
 /* Device pointers of the CSR and weights, for callers that keep fields resident
  * (IceCoupler.cpp:408,445,456 read ->M and ->wM directly). */
