@@ -139,6 +139,15 @@ _SIGS = {
     "ibh_weighted_last_launch": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
     "ibh_set_tuning": (C.c_int, [C.c_char_p, C.c_int]),
     "ibh_release_cached_memory": (C.c_int, []),
+    "ibh_hntr_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_int32,
+                                 C.c_double, C.c_double, C.c_double]),
+    "ibh_hntr_destroy": (C.c_int, [C.c_void_p]),
+    "ibh_hntr_regrid_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p,
+                                        C.c_int64, C.c_int, C.c_double, C.c_double, C.c_void_p]),
+    "ibh_hntr_regrid_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p,
+                                      C.c_int64, C.c_int, C.c_double, C.c_double]),
+    "ibh_hntr_partition": (C.c_int, [C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_double, C.c_double]
+                           + [C.c_void_p] * 10),
     "ibh_selftest_sort": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int)]),
     "ibh_selftest_scan": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int]),
     "ibh_selftest_radix_sort": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),

@@ -85,7 +85,7 @@ void release_cached_memory() {
     pool().cached_bytes = 0;
 }
 
-static void require_device() {
+void require_device() {
     int n = 0;
     hipError_t e = hipGetDeviceCount(&n);
     if (e != hipSuccess || n <= 0)

@@ -5,7 +5,8 @@
 Same classes, method names, keyword names and defaults -- `import icebin; icebin.GCMRegridder(...)`,
 `.regrid_matrices(sheet, elevmaskI, scale=True, correctA=True, sigma=(0,0,0), conserve=True)`,
 `RegridMatrices.matrix(spec)` -> `linear_Weighted` with apply_M / apply_weight / apply_wM / apply_Mw / to_coo /
-get_weights / shape (ibmisc.linear_Weighted, sphinx/source/matrix_formats.rst:139-195) -- bound to the
+get_weights / shape (ibmisc.linear_Weighted, sphinx/source/matrix_formats.rst:139-195), and HntrSpec / Hntr
+(_icebin.pyx:180-227, the lat-lon regridder of slib/icebin/modele/hntr.hpp) -- bound to the
 header-only C++ host mirror (icebin_amd/host/icebin_hip.hpp), which calls the C-ABI of libicebin_hip.so.
 File arguments are IceBin files in the NetCDF-classic container of icebin_amd/ncio.py.
 """
@@ -299,3 +300,70 @@ def coo_multiply(M, xx, fill=np.nan, ignore_nan=False):
     """icebin.coo_multiply (coo_matvec, pylib/icebin_cython.cpp:158-192)."""
     from icebin_amd import linear
     return linear.coo_multiply(M, xx, fill=fill, ignore_nan=ignore_nan)
+
+
+# ============================================================
+# HntrSpec / Hntr (_icebin.pyx:180-227).  As in the reference the constructors take C `float`, so offi, dlat and DATMIS
+# are rounded through float32, and regrid takes 1-D arrays of Agrid.size (icebin_cython.cpp:202-212).  One deliberate
+# deviation: the reference's Hntr.regrid drops the B it computes and returns None (_icebin.pyx:226-227); this one
+# returns B.
+
+cdef class HntrSpec:
+    cdef cicebin.HntrSpec *cself
+
+    def __cinit__(self):
+        self.cself = NULL
+
+    def __dealloc__(HntrSpec self):
+        if self.cself != NULL:
+            del self.cself
+
+    def __init__(HntrSpec self, int im, int jm, float offi, float dlat):
+        self.cself = new cicebin.HntrSpec(im, jm, offi, dlat)
+
+    @property
+    def im(self):
+        return self.cself.im
+
+    @property
+    def jm(self):
+        return self.cself.jm
+
+    @property
+    def size(self):
+        return self.cself.size()
+
+    @property
+    def offi(self):
+        return self.cself.offi
+
+    @property
+    def dlat(self):
+        return self.cself.dlat
+
+
+cdef class Hntr:
+    cdef cicebin.Hntr *cself
+
+    def __cinit__(self):
+        self.cself = NULL
+
+    def __dealloc__(self):
+        if self.cself != NULL:
+            del self.cself
+
+    def __init__(self, double yp17, HntrSpec Bgrid, HntrSpec Agrid, float DATMIS):
+        self.cself = new cicebin.Hntr(17.17, Bgrid.cself[0], Agrid.cself[0], DATMIS)
+
+    def regrid(self, WTA, A, bool mean_polar):
+        """B = regrid of A weighted by WTA (both 1-D, Agrid.size); returns B (1-D, Bgrid.size)."""
+        cdef long nA = self.cself.Agrid.spec.size()
+        cdef double[::1] w = np.ascontiguousarray(WTA, np.float64)
+        cdef double[::1] a = np.ascontiguousarray(A, np.float64)
+        if w.shape[0] != nA or a.shape[0] != nA:
+            raise ValueError("WTA and A must be 1-D arrays of %d cells (got %d and %d)" % (nA, w.shape[0], a.shape[0]))
+        B = np.empty(self.cself.Bgrid.spec.size())
+        cdef double[::1] b = B
+        self.cself.regrid(cicebin.ArrayViewCD(&w[0], nA), cicebin.ArrayViewCD(&a[0], nA), cicebin.ArrayViewD(&b[0], b.shape[0]),
+                          mean_polar, 1.0, 0.0)
+        return B

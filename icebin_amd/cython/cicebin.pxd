@@ -17,6 +17,8 @@ cdef extern from "../host/icebin_hip.hpp" namespace "icebin":
     cdef cppclass ArrayViewCD "icebin::ArrayView<const double>":
         ArrayViewCD(const double *p, long n) except +
         ArrayViewCD(const double *p, long n0, long n1) except +
+    cdef cppclass ArrayViewD "icebin::ArrayView<double>":
+        ArrayViewD(double *p, long n) except +
 
     cdef cppclass ExchangeGrid:
         vector[int] indices
@@ -62,3 +64,22 @@ cdef extern from "../host/icebin_hip.hpp" namespace "icebin::cython":
                                         const double *elevmaskI, long elevmaskI_len, bool scale, bool correctA,
                                         double sigma_x, double sigma_y, double sigma_z, bool conserve) except +
     Weighted *RegridMatrices_matrix(RegridMatrices *cself, const string &spec_name) except +
+
+cdef extern from "../host/icebin_hip.hpp" namespace "icebin::modele":
+    # pylib/cicebin.pxd:123-139 (GridSpec.hpp:143-160, hntr.hpp:63-135)
+    cdef cppclass HntrSpec:
+        int im
+        int jm
+        double offi
+        double dlat
+        HntrSpec(int, int, double, double) except +
+        int size()
+
+    cdef cppclass HntrGrid:
+        HntrSpec spec
+
+    cdef cppclass Hntr:
+        HntrGrid Agrid
+        HntrGrid Bgrid
+        Hntr(double yp17, const HntrSpec &B, const HntrSpec &A, double DATMIS) except +
+        void regrid(const ArrayViewCD &WTA, const ArrayViewCD &A, const ArrayViewD &B, bool mean_polar, double wtm, double wtb) except +

@@ -5,4 +5,4 @@ try:    # one HIP runtime per process (see icebin_amd/_capi.py): load torch's co
 except ImportError:
     pass
 from _icebin import *  # noqa: F401,F403,E402
-from _icebin import GCMRegridder, RegridMatrices, linear_Weighted, coo_multiply  # noqa: F401,E402
+from _icebin import GCMRegridder, RegridMatrices, linear_Weighted, coo_multiply, HntrSpec, Hntr  # noqa: F401,E402

@@ -1,0 +1,129 @@
+"""Hntr: GISS's HNTR4 conservative regridder between two lat-lon grids (icebin::modele::Hntr,
+slib/icebin/modele/hntr.{hpp,cpp}), over the C-ABI of libicebin_hip.so (ibh_hntr_*).
+
+Fields are stored i-fastest (flat index IJ = IA + im*(JA-1)): numpy shape (jm, im) in C order, or a flat
+(im*jm,) vector; several fields stack as (nvar, im*jm) or (nvar, jm, im)."""
+import ctypes as C
+
+import numpy as np
+
+from . import _capi
+from ._capi import check, lib, ptr
+
+
+class HntrSpec:
+    """HntrSpec(im, jm, offi, dlat) (GridSpec.hpp:143-160): offi = cells from the date line to the western edge
+    of cell 1, dlat = minutes of latitude of a non-polar cell."""
+
+    def __init__(self, im, jm, offi, dlat):
+        self.im, self.jm = int(im), int(jm)
+        self.offi, self.dlat = float(offi), float(dlat)
+
+    @property
+    def size(self):
+        return self.im * self.jm
+
+    def __repr__(self):
+        return "HntrSpec(%d, %d, %r, %r)" % (self.im, self.jm, self.offi, self.dlat)
+
+
+def partition(Bspec, Aspec):
+    """The constructor's partition (hntr.cpp:63-168), computed on the host by ibh_hntr_partition (no GPU needed):
+    dict of SINA[jmA+1], SINB[jmB+1], IMIN, IMAX, FMIN, FMAX [imB], JMIN, JMAX, GMIN, GMAX [jmB] (1-based indices,
+    IMAX(imB) already += imA)."""
+    out = dict(SINA=np.zeros(Aspec.jm + 1), SINB=np.zeros(Bspec.jm + 1),
+               IMIN=np.zeros(Bspec.im, np.int32), IMAX=np.zeros(Bspec.im, np.int32),
+               FMIN=np.zeros(Bspec.im), FMAX=np.zeros(Bspec.im),
+               JMIN=np.zeros(Bspec.jm, np.int32), JMAX=np.zeros(Bspec.jm, np.int32),
+               GMIN=np.zeros(Bspec.jm), GMAX=np.zeros(Bspec.jm))
+    check(lib().ibh_hntr_partition(Aspec.im, Aspec.jm, Aspec.offi, Aspec.dlat, Bspec.im, Bspec.jm, Bspec.offi, Bspec.dlat,
+                                   *[ptr(out[k]) for k in ("SINA", "SINB", "IMIN", "IMAX", "FMIN", "FMAX", "JMIN", "JMAX", "GMIN",
+                                                           "GMAX")]))
+    return out
+
+
+class Hntr:
+    """Hntr(yp17, Bspec, Aspec, DATMIS=0) (hntr.hpp:114, hntr.cpp:63-79): yp17 is ignored, as in the reference.
+    Creating one uploads the partition to the current HIP device (IBH_ENODEVICE without one)."""
+
+    def __init__(self, yp17, Bgrid, Agrid, DATMIS=0.):
+        self.Bgrid, self.Agrid, self.DATMIS = Bgrid, Agrid, float(DATMIS)
+        h = C.c_void_p()
+        check(lib().ibh_hntr_create(C.byref(h), Agrid.im, Agrid.jm, Agrid.offi, Agrid.dlat, Bgrid.im, Bgrid.jm, Bgrid.offi,
+                                    Bgrid.dlat, self.DATMIS))
+        self._h = h
+
+    def __del__(self):
+        try:
+            _capi.destroy("ibh_hntr_destroy", getattr(self, "_h", None))
+        except Exception:      # interpreter shutdown
+            pass
+        self._h = None
+
+    def _planes(self, X, what):
+        X = np.asarray(X, np.float64)
+        nA = self.Agrid.size
+        if X.ndim == 1 or (X.ndim == 2 and X.shape == (self.Agrid.jm, self.Agrid.im)):
+            if X.size != nA:
+                raise ValueError("%s has %d cells, grid A has %d" % (what, X.size, nA))
+            return np.ascontiguousarray(X.reshape(1, nA)), True
+        X2 = X.reshape(X.shape[0], -1)
+        if X2.shape[1] != nA:
+            raise ValueError("%s: shape %s does not hold planes of %d cells" % (what, X.shape, nA))
+        return np.ascontiguousarray(X2), False
+
+    def regrid(self, WTA, A, mean_polar=False, wtm=1., wtb=0.):
+        """Hntr::regrid(WTA, A, B, mean_polar, wtm, wtb) (hntr.hpp:341-435): returns B.  A is one field ((size,) or
+        (jm, im)) or several ((nvar, size) or (nvar, jm, im)); WTA is one weight plane for all of them or one per
+        field.  One field comes back shaped like A on grid B, several as (nvar, Bgrid.size)."""
+        A2, single = self._planes(A, "A")
+        W2, _ = self._planes(WTA, "WTA")
+        nvar = A2.shape[0]
+        if W2.shape[0] not in (1, nvar):
+            raise ValueError("WTA has %d planes for %d fields" % (W2.shape[0], nvar))
+        nB = self.Bgrid.size
+        B = np.empty((nvar, nB))
+        if nvar:
+            check(lib().ibh_hntr_regrid_host(self._h, ptr(W2), 0 if W2.shape[0] == 1 else W2.shape[1], ptr(A2), nvar, A2.shape[1],
+                                             ptr(B), nB, int(bool(mean_polar)), float(wtm), float(wtb)))
+        if single:
+            return B[0].reshape(self.Bgrid.jm, self.Bgrid.im) if np.ndim(A) == 2 else B[0]
+        return B
+
+    def regrid_device(self, WTA, A, out=None, mean_polar=False, wtm=1., wtb=0., stream=None):
+        """The same on fields resident in HBM: torch.float64 CUDA tensors, A [nvar, Agrid.size] (row stride >= size),
+        WTA [Agrid.size] or [1, size] (shared) or [nvar, size]; only enqueues work on `stream` (default: torch's
+        current stream).  Returns out [nvar, Bgrid.size]."""
+        import torch
+        nA, nB = self.Agrid.size, self.Bgrid.size
+        assert A.is_cuda and A.dtype == torch.float64 and A.dim() == 2 and A.stride(1) == 1 and A.shape[1] == nA
+        nvar = A.shape[0]
+        W = WTA if WTA.dim() == 2 else WTA.reshape(1, -1)
+        assert W.is_cuda and W.dtype == torch.float64 and W.dim() == 2 and W.stride(1) == 1 and W.shape[1] == nA
+        assert W.shape[0] in (1, nvar)
+        if out is None:
+            out = torch.empty((nvar, (nB + 63) // 64 * 64), dtype=torch.float64, device=A.device)[:, :nB]
+        assert out.is_cuda and out.dtype == torch.float64 and out.dim() == 2 and out.shape == (nvar, nB) and out.stride(1) == 1
+        wta_ld, lda, ldb = device_strides(nvar, nA, nB, W.shape[0], W.stride(0), A.stride(0), out.stride(0))
+        s = torch.cuda.current_stream(A.device).cuda_stream if stream is None else stream
+        check(lib().ibh_hntr_regrid_device(self._h, C.c_void_p(W.data_ptr()), wta_ld, C.c_void_p(A.data_ptr()), nvar, lda,
+                                           C.c_void_p(out.data_ptr()), ldb, int(bool(mean_polar)), float(wtm), float(wtb),
+                                           C.c_void_p(s)))
+        return out
+
+
+def device_strides(nvar, nA, nB, wta_planes, wta_stride, a_stride, out_stride):
+    """(wta_ld, lda, ldb) for ibh_hntr_regrid_device from the plane strides of torch tensors.  A single plane's stride is
+    never read.  One weight plane, or planes broadcast with stride 0 (`w.expand(nvar, -1)`), is the shared weight
+    (wta_ld = 0).  Otherwise every stride must hold a whole plane: a smaller one (a broadcast A or out, an overlapping
+    as_strided view) would make the kernel read or write past the tensor, so it is refused before anything is launched."""
+    wta_ld = 0 if wta_planes == 1 or wta_stride == 0 else wta_stride
+    lda = nA if nvar == 1 else a_stride
+    ldb = nB if nvar == 1 else out_stride
+    if wta_ld and wta_ld < nA:
+        raise ValueError("WTA planes overlap: stride %d < %d cells" % (wta_ld, nA))
+    if lda < nA:
+        raise ValueError("A planes overlap: stride %d < %d cells" % (lda, nA))
+    if ldb < nB:
+        raise ValueError("out planes overlap: stride %d < %d cells" % (ldb, nB))
+    return wta_ld, lda, ldb

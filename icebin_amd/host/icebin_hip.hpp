@@ -4,6 +4,7 @@
 //   GCMRegridder_Standard::regrid_matrices()  (slib/icebin/GCMRegridder.hpp:290-293, 369-372)
 //   RegridMatrices_Dynamic::matrix_d()/matrix() (slib/icebin/RegridMatrices_Dynamic.hpp:51-59)
 //   linear::Weighted_Eigen::apply()           (call sites modele/merge_topo.cpp:65, icebin22m.cpp:153)
+//   modele::Hntr::regrid()                    (slib/icebin/modele/hntr.hpp:63-135; topo.cpp's lat-lon regrids)
 // can switch to this header and link libicebin_hip.so instead of ibmisc/spsparse/Eigen.
 // Differences, all forced by the absent third-party types:
 //   - blitz::Array<double,N>  -> icebin::ArrayView<double> (pointer + extents, row-major, borrowed)
@@ -725,6 +726,69 @@ inline ExchangeGrid make_exchange_grid(std::vector<double> const &xedges, std::v
     check(rc);
     return ex;
 }
+
+// ---- modele/hntr.hpp:63-135, GridSpec.hpp:143-160 ----------------------------------------------------
+namespace modele {
+/** HntrSpec(im, jm, offi, dlat) (GridSpec.hpp:143-160): offi = cells from the date line to the western edge of cell 1,
+    dlat = minutes of latitude of a non-polar cell; fields are i-fastest, IJ = IA + im*(JA-1). */
+struct HntrSpec {
+    int im, jm;
+    double offi, dlat;
+    HntrSpec() : im(-1), jm(-1), offi(0), dlat(0) {}
+    HntrSpec(int _im, int _jm, double _offi, double _dlat) : im(_im), jm(_jm), offi(_offi), dlat(_dlat) {}
+    int size() const { return im * jm; }
+};
+/** The part of HntrGrid (hntr.hpp:17-54) a caller of Hntr reads: hntr.Agrid.spec, hntr.Bgrid.spec. */
+struct HntrGrid {
+    HntrSpec spec;
+    HntrGrid() {}
+    explicit HntrGrid(HntrSpec const &s) : spec(s) {}
+};
+
+/** Hntr (hntr.hpp:63-135): the partition is computed and uploaded to the current HIP device by the constructor; regrid
+    runs on that device.  Owns a device handle: movable, not copyable. */
+class Hntr {
+    ibh_hntr *h_;
+public:
+    HntrGrid const Agrid;
+    HntrGrid const Bgrid;
+    double DATMIS;
+
+    /** Hntr(yp17, Bgrid, Agrid, DATMIS) (hntr.cpp:63-79); yp17 is ignored, as in the reference. */
+    Hntr(double /*yp17*/, HntrSpec const &_B, HntrSpec const &_A, double _DATMIS = 0.0)
+        : h_(nullptr), Agrid(_A), Bgrid(_B), DATMIS(_DATMIS) {
+        check(ibh_hntr_create(&h_, _A.im, _A.jm, _A.offi, _A.dlat, _B.im, _B.jm, _B.offi, _B.dlat, _DATMIS));
+    }
+    Hntr(Hntr const &) = delete;
+    Hntr &operator=(Hntr const &) = delete;
+    Hntr(Hntr &&o) noexcept : h_(o.h_), Agrid(o.Agrid), Bgrid(o.Bgrid), DATMIS(o.DATMIS) { o.h_ = nullptr; }
+    ~Hntr() { if (h_) ibh_hntr_destroy(h_); }
+
+    /** regrid(WTA, A, B, mean_polar, wtm, wtb) (hntr.hpp:204-211, :341-435) on host arrays of one field; the reference's
+        dimension check (:361-369) included. */
+    void regrid(ArrayView<const double> const &WTA, ArrayView<const double> const &A, ArrayView<double> const &B,
+                bool mean_polar = false, double wtm = 1.0, double wtb = 0.0) const {
+        if (WTA.size() != Agrid.spec.size() || A.size() != Agrid.spec.size() || B.size() != Bgrid.spec.size())
+            throw Exception(IBH_EINVAL, "Error in dimensions: (" + std::to_string(WTA.size()) + ", " + std::to_string(A.size()) + ", " +
+                                        std::to_string(B.size()) + ") vs. (" + std::to_string(Agrid.spec.size()) + ", " +
+                                        std::to_string(Bgrid.spec.size()) + ")");
+        check(ibh_hntr_regrid_host(h_, WTA.data, 0, A.data, 1, Agrid.spec.size(), B.data, Bgrid.spec.size(), mean_polar ? 1 : 0, wtm, wtb));
+    }
+    /** regrid(WTA, A, mean_polar) (hntr.hpp:214-218): allocates and returns B. */
+    std::vector<double> regrid(ArrayView<const double> const &WTA, ArrayView<const double> const &A, bool mean_polar = false) const {
+        std::vector<double> B((size_t)Bgrid.spec.size());
+        regrid(WTA, A, ArrayView<double>(B.data(), (long)B.size()), mean_polar);
+        return B;
+    }
+    /** Device overload: nvar fields resident in HBM, B[k*ldb + IJB] from A[k*lda + IJA]; the weight is one plane for all
+        fields (wta_ld = 0) or one per field.  A pure enqueue on `stream` (ibh_hntr_regrid_device). */
+    void regrid(const double *dWTA, long wta_ld, const double *dA, int nvar, long lda, double *dB, long ldb,
+                bool mean_polar = false, double wtm = 1.0, double wtb = 0.0, void *stream = nullptr) const {
+        check(ibh_hntr_regrid_device(h_, dWTA, wta_ld, dA, nvar, lda, dB, ldb, mean_polar ? 1 : 0, wtm, wtb, stream));
+    }
+    ibh_hntr *handle() const { return h_; }
+};
+}   // namespace modele
 
 // ---- pylib/icebin_cython.hpp:70-87 -----------------------------------------------------------
 namespace cython {

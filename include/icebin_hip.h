@@ -92,6 +92,37 @@ int ibh_exgrid_get(const ibh_exgrid *ex, int32_t *indices /* [2*nX] */, double *
 int ibh_exgrid_destroy(ibh_exgrid *ex);
 
 /* ------------------------------------------------------------------------- */
+/* Hntr: icebin::modele::Hntr (slib/icebin/modele/hntr.hpp:63-135, hntr.cpp:63-168), GISS's HNTR4 conservative
+ * regridder between two lat-lon grids.  A grid is HntrSpec(im, jm, offi, dlat) (GridSpec.hpp:143-160): offi = cells
+ * from the date line to the western edge of cell 1, dlat = minutes of latitude of a non-polar cell; fields are
+ * stored i-fastest, flat index IJ = IA + im*(JA-1) (numpy shape (jm, im)).
+ * ibh_hntr_create replaces Hntr(yp17, Bspec, Aspec, DATMIS) (hntr.cpp:63-79): the partition (partition_east_west,
+ * partition_north_south, hntr.cpp:84-168) is computed on the host with libm sin and uploaded once.  Specs need
+ * im, jm >= 1, dlat > 0, finite offi; a partition with an index outside [1, 2*imA] x [1, jmA] (the reference never
+ * checks; column windows count modulo whole turns of imA, as the reference's IA = 1 + (IAREV-1) % imA does) is
+ * IBH_EINVAL.  Allocates on the device: without one, IBH_ENODEVICE. */
+typedef struct ibh_hntr ibh_hntr;
+int ibh_hntr_create(ibh_hntr **out, int32_t imA, int32_t jmA, double offiA, double dlatA, int32_t imB, int32_t jmB,
+                    double offiB, double dlatB, double datmis);
+int ibh_hntr_destroy(ibh_hntr *h);
+/* Hntr::regrid(WTA, A, B, mean_polar, wtm, wtb) (hntr.hpp:204-244, RegridAccum and Hntr::regrid :341-435) on nvar
+ * fields at once: B[k*ldb + IJB] for k < nvar from A[k*lda + IJA] with the weight wtm*WTA + wtb, where WTA is one
+ * plane shared by every field (wta_ld = 0) or one plane per field (WTA[k*wta_ld + IJA]).  Cells whose covered weight
+ * is 0 get DATMIS; mean_polar replaces rows 1 and jmB by their mean (refused with jmB = 1, where the reference loops
+ * forever).  Bitwise the reference's loop order for every nvar; the gaps between planes are left untouched.
+ * _device: device pointers, a pure enqueue on `stream`.  _host: host arrays (copies over PCIe, synchronous). */
+int ibh_hntr_regrid_device(const ibh_hntr *h, const double *dWTA, int64_t wta_ld, const double *dA, int32_t nvar, int64_t lda,
+                           double *dB, int64_t ldb, int mean_polar, double wtm, double wtb, void *stream);
+int ibh_hntr_regrid_host(const ibh_hntr *h, const double *WTA, int64_t wta_ld, const double *A, int32_t nvar, int64_t lda,
+                         double *B, int64_t ldb, int mean_polar, double wtm, double wtb);
+/* The partition alone, host only (no device needed): SINA[jmA+1], SINB[jmB+1]; IMIN, IMAX, FMIN, FMAX [imB]
+ * (IMAX(imB) already += imA, as hntr.cpp:116 leaves it); JMIN, JMAX, GMIN, GMAX [jmB].  Indices are the reference's,
+ * 1-based; entry i of a per-column or per-row array belongs to IB or JB = i+1. */
+int ibh_hntr_partition(int32_t imA, int32_t jmA, double offiA, double dlatA, int32_t imB, int32_t jmB, double offiB,
+                       double dlatB, double *SINA, double *SINB, int32_t *IMIN, int32_t *IMAX, double *FMIN, double *FMAX,
+                       int32_t *JMIN, int32_t *JMAX, double *GMIN, double *GMAX);
+
+/* ------------------------------------------------------------------------- */
 /* Regridder: the state of GCMRegridder_Standard (GCMRegridder.hpp:207-302) and
  * one IceRegridder_L0 (IceRegridder.hpp:46-133) that the path reads, uploaded
  * to HBM once.  Replaces GCMRegridder_Standard::init + add_sheet
