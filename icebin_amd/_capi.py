@@ -148,6 +148,11 @@ _SIGS = {
                                       C.c_int64, C.c_int, C.c_double, C.c_double]),
     "ibh_hntr_partition": (C.c_int, [C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_double, C.c_double]
                            + [C.c_void_p] * 10),
+    "ibh_hntr_dxyp": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p]),
+    "ibh_hntr_triplets": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p,
+                                   C.c_void_p]),
+    "ibh_hntr_matrix_d": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                   C.POINTER(C.c_void_p)]),
     "ibh_selftest_sort": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int)]),
     "ibh_selftest_scan": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int]),
     "ibh_selftest_radix_sort": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),

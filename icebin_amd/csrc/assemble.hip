@@ -2609,6 +2609,47 @@ void weighted_from_coo_device(ibh_weighted *w, int nrow, int ncol, int64_t n, co
     IBH_HIP(hipStreamSynchronize(st));
 }
 
+// the sparse -> dense device table of a pre-populated set (fastasm.inl set_inverse_table: built once, cached in the set)
+const int32_t *set_dense_table(ibh_sparse_set *set, int64_t extent, hipStream_t st) { return set_inverse_table(set, extent, st); }
+
+// setFromTriplets from triplets already on the device (dense ids, input order) and the plain weights wM / Mw = spsparse
+// sum(M, dim, '+') (columns visited ascending, rows ascending inside): the general-dims path of the Hntr matrices (hntr.hip).
+// Enqueued on `st`; reads nothing back but nnz.  The arena is not reset: the caller's triplets may live there.
+void weighted_from_device_triplets(ibh_weighted *w, int nrow, int ncol, int64_t n, const int32_t *drow, const int32_t *dcol,
+                                   const double *dval, hipStream_t st) {
+    Arena &A = arena();
+    const int T = 256;
+    Triplets t;
+    t.n = (size_t)n;
+    t.keys = A.get<uint64_t>(t.n); t.keys_alt = A.get<uint64_t>(t.n);
+    t.idx = A.get<uint32_t>(t.n); t.idx_alt = A.get<uint32_t>(t.n);
+    t.term = A.get<double>(t.n);
+    if (n) {
+        IBH_HIP(hipMemcpyAsync(t.term, dval, sizeof(double) * t.n, hipMemcpyDeviceToDevice, st));
+        hipLaunchKernelGGL(k_coo_keys, dim3(ceil_div(n, T)), dim3(T), 0, st, drow, dcol, t.n, t.keys, t.idx);
+    }
+    int32_t *row = nullptr;
+    build_csr_from_contributions(w, t, nrow, ncol, &row, st);
+    const long nnz = w->nnz;
+    w->wM.alloc((size_t)nrow); w->Mw.alloc((size_t)ncol);
+    seg_sums<true>(w->rowptr.p, nullptr, w->val.p, nrow, nnz, w->wM.p, st);
+    if (nnz) {
+        uint64_t *ck = A.get<uint64_t>((size_t)nnz), *ck2 = A.get<uint64_t>((size_t)nnz);
+        uint32_t *ci = A.get<uint32_t>((size_t)nnz), *ci2 = A.get<uint32_t>((size_t)nnz);
+        hipLaunchKernelGGL(k_col_keys, dim3(ceil_div(nnz, T)), dim3(T), 0, st, w->colind.p, nnz, ck, ci);
+        KeyField f{0, bits_for((uint64_t)ncol)};
+        if (f.nbits > 0 && radix_sort_pairs(ck, ck2, ci, ci2, (size_t)nnz, &f, 1, st)) { std::swap(ck, ck2); std::swap(ci, ci2); }
+        int32_t *scol = A.get<int32_t>((size_t)nnz), *colptr = A.get<int32_t>((size_t)ncol + 1);
+        hipLaunchKernelGGL(k_keys_to_i32, dim3(ceil_div(nnz, T)), dim3(T), 0, st, ck, nnz, scol);
+        rowptr_from_rows(scol, nnz, ncol, colptr, st);
+        seg_sums<true>(colptr, ci, w->val.p, ncol, nnz, w->Mw.p, st);
+    } else {
+        if (nrow) IBH_HIP(hipMemsetAsync(w->wM.p, 0, sizeof(double) * (size_t)nrow, st));
+        if (ncol) IBH_HIP(hipMemsetAsync(w->Mw.p, 0, sizeof(double) * (size_t)ncol, st));
+    }
+    IBH_HIP(hipGetLastError());
+}
+
 // ---- E1vE0 (slib/icebin/e1ve0.cpp:55-106 compute_E1vE0c) ------------------------------------------------
 //   E1vE0c = diag(1 / sum_sheets Mw(XuE1)) * sum_sheets[ E1uX * (XvE0 - XvE1) ], consolidated,
 // XvE = diag(1/wM) * XuE.  Every exchange cell x has <= a handful of entries in XuE1 and XuE0, so the

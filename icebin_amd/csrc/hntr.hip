@@ -25,6 +25,7 @@
 #include <cmath>
 #include <memory>
 
+#include "assemble.h"
 #include "common.h"
 
 namespace ibh {
@@ -299,6 +300,11 @@ struct ibh_hntr {
     int wmax = 1;       // widest column window
     DevBuf<double> SINA, FMIN, FMAX, GMIN, GMAX;
     DevBuf<int32_t> IMIN, IMAX, JMIN, JMAX;
+    // for the matrix forms (ibh_hntr_triplets / ibh_hntr_matrix_d): the windows on the host (column windows shifted as on the
+    // device), dxyp of grid B, and the B cells whose windows hold each A row / each column position IAREV in [1, 2*imA]
+    std::vector<int32_t> hIMIN, hIMAX, hJMIN, hJMAX;
+    DevBuf<double> dxypB;
+    DevBuf<int32_t> jbr, ibr;       // [2*jmA] first / last JB (1-based) per JA; [2*2*imA] first / last IB per IAREV (lo > hi: none)
 };
 
 namespace ibh {
@@ -359,6 +365,579 @@ static void check_regrid_args(const ibh_hntr *h, const void *WTA, int64_t wta_ld
     IBH_CHECK(!mean_polar || h->jmB >= 2, "Hntr regrid: mean_polar needs jmB >= 2 (the reference loops forever on jmB=1)");
 }
 
+// ---- matrix forms (hntr.hpp:205-338 Hntr::matrix, OverlapMatAccum, ScaledRegridMatAccum; hntr.cpp:33-52 make_dxyp) ----
+// Hntr::matrix visits the included B cells in stream order (JB, then IB, ascending) and, inside a cell, JA from JMIN(JB) to
+// JMAX(JB), then IAREV from IMIN(IB) to IMAX(IB), with the term FG = F*G; the accumulators emit ((IJB-1, IJA-1), FG *
+// (1/WEIGHT) [* R2*dxyp(JB)]) once the cell's WEIGHT (the sum of its FG, in that order) is known.  On the device:
+//   count     one thread per B cell: its triplets (JMAX-JMIN+1) * (IMAX-IMIN+1), or its distinct columns (CSR)
+//   scan      prims' exclusive scan: the triplet offsets or the CSR row pointer
+//   weight    one lane per B cell: the WEIGHT chain in stream order (loads nothing but the partition), 1/WEIGHT stored
+//   fill      TPR lanes per row: the CSR in column order straight from the partition (no sort).  A window that wraps the
+//             date line becomes two ascending IA runs per A row, listed low run first; a column visited twice (a window wider
+//             than imA) is summed in stream order (IAREV = IA, then IA + imA), the first term assigned (setFromTriplets).
+//             Quads of entries aligned to the whole array are stored as int4 / 2 x double2.
+//   wM        one lane per row: the row's values again, from 0 in column order (spsparse sum(M, 0, '+')); no loads
+//   Mw        one thread per A column: the B cells whose windows hold it, rows ascending, from 0
+// All values are recomputed with the same expressions wherever they are needed, so fill, wM and Mw agree bit for bit.
+// Other dims (ADD_DENSE onto a partial set, TO_DENSE through a pre-populated or permuted one, transpose) take the triplets
+// through a first-seen numbering on the device and the assembly's setFromTriplets (weighted_from_device_triplets).
+static void hntr_dxyp(int im, int jm, double *dxyp) {
+    const double dLON = (2. * M_PI) / im;
+    const double dLAT = M_PI / jm;
+    for (int j = 1; j <= jm; ++j) {
+        const double SINS = sin(dLAT * (j - jm / 2 - 1));
+        const double SINN = sin(dLAT * (j - jm / 2));
+        dxyp[j - 1] = dLON * (SINN - SINS);
+    }
+}
+
+static void hntr_matrix_tables(ibh_hntr *h, HntrPartition const &p) {
+    // p: column windows already shifted
+    h->hIMIN = p.IMIN; h->hIMAX = p.IMAX; h->hJMIN = p.JMIN; h->hJMAX = p.JMAX;
+    std::vector<double> dx((size_t)h->jmB);
+    hntr_dxyp(h->imB, h->jmB, dx.data());
+    h->dxypB.upload(dx.data(), dx.size());
+    std::vector<int32_t> jbr(2 * (size_t)h->jmA), ibr(4 * (size_t)h->imA);
+    for (int ja = 0; ja < h->jmA; ++ja) { jbr[2 * ja] = 1 << 30; jbr[2 * ja + 1] = -1; }
+    for (int v = 0; v < 2 * h->imA; ++v) { ibr[2 * v] = 1 << 30; ibr[2 * v + 1] = -1; }
+    for (int jb = 1; jb <= h->jmB; ++jb)
+        for (int ja = p.JMIN[jb - 1]; ja <= p.JMAX[jb - 1]; ++ja) {
+            jbr[2 * (ja - 1)] = std::min(jbr[2 * (ja - 1)], jb);
+            jbr[2 * (ja - 1) + 1] = std::max(jbr[2 * (ja - 1) + 1], jb);
+        }
+    for (int ib = 1; ib <= h->imB; ++ib)
+        for (int v = p.IMIN[ib - 1]; v <= p.IMAX[ib - 1]; ++v) {
+            ibr[2 * (v - 1)] = std::min(ibr[2 * (v - 1)], ib);
+            ibr[2 * (v - 1) + 1] = std::max(ibr[2 * (v - 1) + 1], ib);
+        }
+    h->jbr.upload(jbr.data(), jbr.size());
+    h->ibr.upload(ibr.data(), ibr.size());
+}
+
+struct HmArgs {
+    const double *SINA, *FMIN, *FMAX, *GMIN, *GMAX, *dxyp;
+    const int32_t *IMIN, *IMAX, *JMIN, *JMAX, *jbr, *ibr;
+    const uint8_t *mask;        // includeB, nullptr: every cell
+    const double *winv;         // [nB] 1/WEIGHT of included cells
+    int imA, jmA, imB, jmB;
+    int overlap;
+    double R2;
+};
+// one B cell's part of the partition
+struct HmCell {
+    int imn, imx, jmn, jmx, W, D, lo;
+    double fmn, fmx, gmn, gmx, winv, s;
+};
+__device__ __forceinline__ bool hm_included(const HmArgs &a, long r) { return !a.mask || a.mask[r]; }
+__device__ __forceinline__ HmCell hm_cell(const HmArgs &a, int ib, int jb, bool with_w) {
+    HmCell c;
+    c.imn = a.IMIN[ib]; c.imx = a.IMAX[ib]; c.fmn = a.FMIN[ib]; c.fmx = a.FMAX[ib];
+    c.jmn = a.JMIN[jb]; c.jmx = a.JMAX[jb]; c.gmn = a.GMIN[jb]; c.gmx = a.GMAX[jb];
+    c.W = c.imx - c.imn + 1;
+    c.D = min(c.W, a.imA);
+    c.lo = c.imn > a.imA ? c.imn - a.imA : c.imn;
+    c.winv = with_w ? a.winv[(long)jb * a.imB + ib] : 0.;
+    c.s = a.overlap ? a.R2 * a.dxyp[jb] : 1.;
+    return c;
+}
+__device__ __forceinline__ double hm_G(const HmArgs &a, const HmCell &c, int JA) {
+    double G = a.SINA[JA] - a.SINA[JA - 1];
+    if (JA == c.jmn) G -= c.gmn;
+    if (JA == c.jmx) G -= c.gmx;
+    return G;
+}
+__device__ __forceinline__ double hm_F(const HmCell &c, int IAREV) {
+    double F = 1;
+    if (IAREV == c.imn) F -= c.fmn;
+    if (IAREV == c.imx) F -= c.fmx;
+    return F;
+}
+// the accumulators' value of one term: FG * (1/WEIGHT) [* (R2*dxyp(JB))], left to right
+__device__ __forceinline__ double hm_val(const HmArgs &a, const HmCell &c, double FG) {
+    const double v = FG * c.winv;
+    return a.overlap ? v * c.s : v;
+}
+// IA (1-based) of the k-th distinct column of an A row of the cell, columns ascending
+__device__ __forceinline__ int hm_col(const HmArgs &a, const HmCell &c, int k) {
+    if (c.W >= a.imA) return k + 1;
+    const int n2 = c.lo + c.W - 1 - a.imA;      // > 0: the window wraps, IA 1..n2 come first
+    if (n2 <= 0) return c.lo + k;
+    return k < n2 ? k + 1 : c.lo + (k - n2);
+}
+// the stored value at (cell, JA, IA): the terms of IAREV = IA, then IA + imA, that lie in the window, the first assigned
+__device__ __forceinline__ double hm_entry(const HmArgs &a, const HmCell &c, double G, int IA) {
+    double v = 0;
+    bool any = false;
+    if (IA >= c.imn && IA <= c.imx) { v = hm_val(a, c, hm_F(c, IA) * G); any = true; }
+    const int IA2 = IA + a.imA;
+    if (IA2 >= c.imn && IA2 <= c.imx) {
+        const double t = hm_val(a, c, hm_F(c, IA2) * G);
+        v = any ? v + t : t;
+    }
+    return v;
+}
+
+__global__ void k_hm_count(HmArgs a, int csr, uint32_t *__restrict__ cnt) {
+    const long r = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= (long)a.imB * a.jmB) return;
+    const int ib = (int)(r % a.imB), jb = (int)(r / a.imB);
+    uint32_t n = 0;
+    if (hm_included(a, r)) {
+        const int W = a.IMAX[ib] - a.IMIN[ib] + 1;
+        n = (uint32_t)(a.JMAX[jb] - a.JMIN[jb] + 1) * (uint32_t)(csr ? min(W, a.imA) : W);
+    }
+    cnt[r] = n;
+}
+
+__global__ void k_hm_weight(HmArgs a, double *__restrict__ winv) {
+    const long r = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= (long)a.imB * a.jmB || !hm_included(a, r)) return;
+    const HmCell c = hm_cell(a, (int)(r % a.imB), (int)(r / a.imB), false);
+    double WEIGHT = 0;
+    for (int JA = c.jmn; JA <= c.jmx; ++JA) {
+        const double G = hm_G(a, c, JA);
+        for (int IAREV = c.imn; IAREV <= c.imx; ++IAREV) WEIGHT += hm_F(c, IAREV) * G;
+    }
+    winv[r] = 1. / WEIGHT;
+}
+
+// rows handled by teams of TPR lanes (a power of two dividing 256)
+__device__ __forceinline__ bool hm_team(const HmArgs &a, int TPR, long &r, int &t) {
+    r = (long)blockIdx.x * (256 / TPR) + threadIdx.x / TPR;
+    t = threadIdx.x % TPR;
+    return r < (long)a.imB * a.jmB;
+}
+
+// stream-order triplets (iB, iA) sparse, 0-based, at offsets tptr[r]
+__global__ __launch_bounds__(256) void k_hm_triplets(HmArgs a, int TPR, const uint32_t *__restrict__ tptr, int32_t *__restrict__ iB,
+                                                     int32_t *__restrict__ iA, double *__restrict__ val) {
+    long r; int t;
+    if (!hm_team(a, TPR, r, t)) return;
+    const uint32_t p0 = tptr[r], p1 = tptr[r + 1];
+    if (p0 == p1) return;
+    const HmCell c = hm_cell(a, (int)(r % a.imB), (int)(r / a.imB), true);
+    for (uint32_t e = t; e < p1 - p0; e += TPR) {
+        const int jr = (int)(e / (uint32_t)c.W), k = (int)(e % (uint32_t)c.W);
+        const int JA = c.jmn + jr, IAREV = c.imn + k;
+        const int IA = IAREV > a.imA ? IAREV - a.imA : IAREV;
+        iB[p0 + e] = (int32_t)r;
+        iA[p0 + e] = (JA - 1) * a.imA + (IA - 1);
+        val[p0 + e] = hm_val(a, c, hm_F(c, IAREV) * hm_G(a, c, JA));
+    }
+}
+
+// the CSR in column order; quads of the whole array that lie inside the row are stored 16 bytes at a time
+__global__ __launch_bounds__(256) void k_hm_fill(HmArgs a, int TPR, const int32_t *__restrict__ rowptr, int32_t *__restrict__ colind,
+                                                 double *__restrict__ val) {
+    long r; int t;
+    if (!hm_team(a, TPR, r, t)) return;
+    const int p0 = rowptr[r], p1 = rowptr[r + 1];
+    if (p0 == p1) return;
+    const HmCell c = hm_cell(a, (int)(r % a.imB), (int)(r / a.imB), true);
+    // positions in 64 bits: p1 may be INT32_MAX, and base runs up to 4*TPR past it
+    for (long base = (p0 & ~3) + 4l * t; base < p1; base += 4l * TPR) {
+        const long q0 = max(base, (long)p0), q1 = min(base + 4, (long)p1);
+        int e = (int)(q0 - p0);
+        int jr = e / c.D, k = e - jr * c.D;
+        int cc[4] = {0, 0, 0, 0};
+        double vv[4] = {0, 0, 0, 0};
+        int JA = c.jmn + jr;
+        double G = hm_G(a, c, JA);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            if (base + u < q0 || base + u >= q1) continue;
+            const int IA = hm_col(a, c, k);
+            cc[u] = (JA - 1) * a.imA + (IA - 1);
+            vv[u] = hm_entry(a, c, G, IA);
+            if (++k == c.D) { k = 0; ++JA; if (JA <= c.jmx) G = hm_G(a, c, JA); }
+        }
+        if (q0 == base && q1 == base + 4) {
+            *reinterpret_cast<int4 *>(colind + base) = make_int4(cc[0], cc[1], cc[2], cc[3]);
+            *reinterpret_cast<double2 *>(val + base) = make_double2(vv[0], vv[1]);
+            *reinterpret_cast<double2 *>(val + base + 2) = make_double2(vv[2], vv[3]);
+        } else {
+            for (int u = 0; u < 4; ++u)
+                if (base + u >= q0 && base + u < q1) { colind[base + u] = cc[u]; val[base + u] = vv[u]; }
+        }
+    }
+}
+
+// wM: sum(M, 0, '+') of every row, from 0 in column order, recomputed (rows without entries: 0)
+__global__ void k_hm_rowsum(HmArgs a, double *__restrict__ wM) {
+    const long r = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= (long)a.imB * a.jmB) return;
+    double s = 0;
+    if (hm_included(a, r)) {
+        const HmCell c = hm_cell(a, (int)(r % a.imB), (int)(r / a.imB), true);
+        for (int JA = c.jmn; JA <= c.jmx; ++JA) {
+            const double G = hm_G(a, c, JA);
+            for (int k = 0; k < c.D; ++k) s = s + hm_entry(a, c, G, hm_col(a, c, k));
+        }
+    }
+    wM[r] = s;
+}
+
+// Mw: sum(M, 1, '+') of every A column: the B cells that hold it, JB then IB ascending, from 0.  The cells whose column
+// window holds IA + imA but not IA come after those that hold IA (windows are ordered), so the two IB ranges are walked
+// in turn, the second past the end of the first.
+__global__ void k_hm_colsum(HmArgs a, double *__restrict__ Mw) {
+    const long col = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (col >= (long)a.imA * a.jmA) return;
+    const int JA = (int)(col / a.imA) + 1, IA = (int)(col % a.imA) + 1;
+    const int jb0 = a.jbr[2 * (JA - 1)], jb1 = a.jbr[2 * (JA - 1) + 1];
+    const int i10 = a.ibr[2 * (IA - 1)], i11 = a.ibr[2 * (IA - 1) + 1];
+    const int i20 = max(a.ibr[2 * (IA - 1 + a.imA)], i11 + 1), i21 = a.ibr[2 * (IA - 1 + a.imA) + 1];
+    double s = 0;
+    for (int JB = jb0; JB <= jb1; ++JB) {
+        for (int pass = 0; pass < 2; ++pass) {
+            const int b0 = pass ? i20 : i10, b1 = pass ? i21 : i11;
+            for (int IB = b0; IB <= b1; ++IB) {
+                const long r = (long)(JB - 1) * a.imB + (IB - 1);
+                if (!hm_included(a, r)) continue;
+                const HmCell c = hm_cell(a, IB - 1, JB - 1, true);
+                s = s + hm_entry(a, c, hm_G(a, c, JA), IA);
+            }
+        }
+    }
+    Mw[col] = s;
+}
+
+// ---- first-seen numbering of one set (spsparse::SparseSet::add_dense in stream order), and the to-dense transforms ----
+// An entry's indices are transformed in order, B then A, and the entry stops at the first index that
+// TO_DENSE_IGNORE_MISSING drops: its A index is then neither numbered (ADD_DENSE) nor looked up (TO_DENSE).  So B is
+// numbered over every entry and A over the entries whose B index survived (`act`).
+struct HmSet {
+    long ident_n;               // >= 0: the old part is the identity on [0, ident_n)
+    const int32_t *tab;         // otherwise: old sparse -> dense (-1 missing), [extent]
+    int n_old, transform;
+    uint32_t *first;            // ADD_DENSE: [extent] smallest stream position naming a missing key
+    uint32_t *rank;             // ADD_DENSE: [n] exclusive scan of the new-key flags
+    const uint8_t *act;         // entries this set sees (nullptr: all)
+};
+__device__ __forceinline__ int hm_old(const HmSet &s, long key) {
+    if (s.ident_n >= 0) return key < s.ident_n ? (int)key : -1;
+    return s.tab[key];
+}
+__global__ void k_hm_first(HmSet s, const int32_t *__restrict__ key, long n) {
+    const long p = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p < n && (!s.act || s.act[p]) && hm_old(s, key[p]) < 0) atomicMin(&s.first[key[p]], (uint32_t)p);
+}
+__global__ void k_hm_newflag(HmSet s, const int32_t *__restrict__ key, long n, uint32_t *__restrict__ flag) {
+    const long p = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p < n) flag[p] = (!s.act || s.act[p]) && hm_old(s, key[p]) < 0 && s.first[key[p]] == (uint32_t)p ? 1u : 0u;
+}
+__device__ __forceinline__ int hm_dense(const HmSet &s, long key) {
+    const int d = hm_old(s, key);
+    if (d >= 0 || s.transform != IBH_ADD_DENSE) return d;
+    return s.n_old + (int)s.rank[s.first[key]];
+}
+// act[p]: the B index has a dense id; keep[p]: so has the A index of an active entry.  A key missing under TO_DENSE
+// raises *bad.
+__global__ void k_hm_gate(HmSet sb, const int32_t *__restrict__ iB, long n, uint8_t *__restrict__ act, uint32_t *__restrict__ bad) {
+    const long p = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    const int db = hm_dense(sb, iB[p]);
+    if (db < 0 && sb.transform == IBH_TO_DENSE) atomicOr(bad, 1u);
+    act[p] = db >= 0;
+}
+__global__ void k_hm_keep(HmSet sa, const int32_t *__restrict__ iA, long n, uint32_t *__restrict__ keep, uint32_t *__restrict__ bad) {
+    const long p = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    if (!sa.act[p]) { keep[p] = 0; return; }
+    const int da = hm_dense(sa, iA[p]);
+    if (da < 0 && sa.transform == IBH_TO_DENSE) atomicOr(bad, 1u);
+    keep[p] = da >= 0 ? 1u : 0u;
+}
+__global__ void k_hm_compact(HmSet sb, HmSet sa, const int32_t *__restrict__ iB, const int32_t *__restrict__ iA,
+                             const double *__restrict__ v, long n, const uint32_t *__restrict__ kpos, int transpose,
+                             int32_t *__restrict__ row, int32_t *__restrict__ col, double *__restrict__ val) {
+    const long p = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n || kpos[p + 1] == kpos[p]) return;
+    const int db = hm_dense(sb, iB[p]), da = hm_dense(sa, iA[p]);
+    const uint32_t q = kpos[p];
+    row[q] = transpose ? da : db;
+    col[q] = transpose ? db : da;
+    val[q] = v[p];
+}
+// new keys in first-seen order
+__global__ void k_hm_newkeys(const int32_t *__restrict__ key, long n, const uint32_t *__restrict__ rank, int64_t *__restrict__ out) {
+    const long p = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p < n && rank[p + 1] != rank[p]) out[rank[p]] = key[p];
+}
+__global__ void k_hm_iota(int64_t *p, long n) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) p[i] = i;
+}
+
+// the dense -> sparse table of a set's first n entries, in the arena
+static int64_t *hm_set_table(ibh_sparse_set *set, int n, hipStream_t st) {
+    int64_t *t = arena().get<int64_t>((size_t)n);
+    if (n == 0) return t;
+    if (set->identity) hipLaunchKernelGGL(k_hm_iota, dim3(ceil_div(n, 256)), dim3(256), 0, st, t, (long)n);
+    else if (set->dev_n >= n) IBH_HIP(hipMemcpyAsync(t, set->dev.p, sizeof(int64_t) * (size_t)n, hipMemcpyDeviceToDevice, st));
+    else {
+        set->ensure_host();
+        IBH_HIP(hipMemcpyAsync(t, set->host.data(), sizeof(int64_t) * (size_t)n, hipMemcpyHostToDevice, st));
+    }
+    return t;
+}
+
+static int hm_tpr(int64_t nnz, int64_t nrow) {
+    const int64_t avg = nrow ? nnz / nrow : 0;
+    int tpr = 4;
+    while (tpr < 256 && 4 * (int64_t)tpr < avg) tpr <<= 1;
+    return tpr;
+}
+
+// the number of triplets (or CSR entries) of the included cells, in 64 bits, from the host copy of the windows
+static int64_t hm_count_host(const ibh_hntr *h, const uint8_t *mask, bool csr) {
+    std::vector<int64_t> wi((size_t)h->imB);
+    for (int ib = 0; ib < h->imB; ++ib) {
+        const int64_t W = h->hIMAX[ib] - h->hIMIN[ib] + 1;
+        wi[ib] = csr ? std::min<int64_t>(W, h->imA) : W;
+    }
+    int64_t n = 0;
+    int64_t sw = 0;
+    if (!mask) for (int ib = 0; ib < h->imB; ++ib) sw += wi[ib];
+    for (int jb = 0; jb < h->jmB; ++jb) {
+        const int64_t nj = h->hJMAX[jb] - h->hJMIN[jb] + 1;
+        if (!mask) { n += nj * sw; continue; }
+        int64_t s = 0;
+        const uint8_t *m = mask + (size_t)jb * h->imB;
+        for (int ib = 0; ib < h->imB; ++ib) if (m[ib]) s += wi[ib];
+        n += nj * s;
+    }
+    return n;
+}
+
+static void hm_check_kind(int kind) { IBH_CHECK(kind == IBH_HNTR_OVERLAP || kind == IBH_HNTR_SCALED, "Hntr matrix: kind %d is not IBH_HNTR_OVERLAP or IBH_HNTR_SCALED", kind); }
+
+// Everything up to the triplets or the CSR: mask upload, count, scan, weights.  Returns the args; ptr = the scan [nB+1].
+static HmArgs hm_prepare(const ibh_hntr *h, int kind, double eq_rad, const uint8_t *includeB, bool csr, uint32_t *ptr,
+                         hipStream_t st) {
+    Arena &A = arena();
+    const long nB = (long)h->imB * h->jmB;
+    HmArgs a{};
+    a.SINA = h->SINA.p; a.FMIN = h->FMIN.p; a.FMAX = h->FMAX.p; a.GMIN = h->GMIN.p; a.GMAX = h->GMAX.p; a.dxyp = h->dxypB.p;
+    a.IMIN = h->IMIN.p; a.IMAX = h->IMAX.p; a.JMIN = h->JMIN.p; a.JMAX = h->JMAX.p; a.jbr = h->jbr.p; a.ibr = h->ibr.p;
+    a.imA = h->imA; a.jmA = h->jmA; a.imB = h->imB; a.jmB = h->jmB;
+    a.overlap = kind == IBH_HNTR_OVERLAP;
+    a.R2 = eq_rad * eq_rad;
+    if (includeB) {
+        uint8_t *m = A.get<uint8_t>((size_t)nB);
+        IBH_HIP(hipMemcpyAsync(m, includeB, (size_t)nB, hipMemcpyHostToDevice, st));
+        a.mask = m;
+    }
+    double *winv = A.get<double>((size_t)nB);
+    a.winv = winv;
+    hipLaunchKernelGGL(k_hm_count, dim3(ceil_div(nB, 256)), dim3(256), 0, st, a, (int)csr, ptr);
+    exclusive_scan_u32(ptr, ptr, (size_t)nB, ptr + nB, st);
+    hipLaunchKernelGGL(k_hm_weight, dim3(ceil_div(nB, 64)), dim3(64), 0, st, a, winv);
+    IBH_HIP(hipGetLastError());
+    return a;
+}
+
+static void hm_check(const ibh_hntr *h, int kind) {
+    IBH_CHECK(h != nullptr, "null Hntr handle");
+    hm_check_kind(kind);
+    int dev = -1;
+    IBH_HIP(hipGetDevice(&dev));
+    IBH_CHECK(dev == h->device, "Hntr handle belongs to device %d, current device is %d", h->device, dev);
+}
+
+// the set a matrix_d call uses for one side: the caller's (sparse extent -1 takes the grid's) or a fresh identity
+static void hm_check_transform(int transform, const char *which) {
+    IBH_CHECK(transform == IBH_ADD_DENSE || transform == IBH_TO_DENSE || transform == IBH_TO_DENSE_IGNORE_MISSING,
+              "Hntr matrix_d: transform %d of %s is not IBH_ADD_DENSE, IBH_TO_DENSE or IBH_TO_DENSE_IGNORE_MISSING", transform, which);
+}
+static ibh_sparse_set *hm_dims(ibh_sparse_set *set, int64_t extent, const char *which) {
+    if (!set) return nullptr;
+    IBH_CHECK(set->sparse_extent == -1 || set->sparse_extent == extent, "Hntr matrix_d: %s has sparse extent %lld, the grid %lld cells",
+              which, (long long)set->sparse_extent, (long long)extent);
+    IBH_CHECK(set->dense_extent() <= extent, "Hntr matrix_d: %s holds %d entries, more than the grid's %lld cells", which,
+              set->dense_extent(), (long long)extent);
+    if (!set->identity && set->host_n == set->n)
+        for (int32_t i = 0; i < set->n; ++i)
+            IBH_CHECK(set->host[(size_t)i] >= 0 && set->host[(size_t)i] < extent, "Hntr matrix_d: %s entry %lld outside [0, %lld)", which,
+                      (long long)set->host[(size_t)i], (long long)extent);
+    return set;
+}
+static bool hm_full_identity(const ibh_sparse_set *set, int64_t extent) {
+    return !set || (set->identity && set->n == extent);
+}
+
+struct HmNumber {
+    HmSet s{};
+    ibh_sparse_set *set = nullptr;
+    int64_t extent = 0;
+    uint32_t *flag = nullptr;       // [n+1]: new-key flags, then their exclusive scan (rank)
+};
+static HmNumber hm_number_prepare(ibh_sparse_set *set, int64_t extent, int transform, const int32_t *key, long n, const uint8_t *act,
+                                  hipStream_t st) {
+    Arena &A = arena();
+    HmNumber nb;
+    nb.set = set; nb.extent = extent;
+    HmSet &s = nb.s;
+    s.transform = transform;
+    s.act = act;
+    s.n_old = set ? set->n : (int)extent;
+    s.ident_n = -1;
+    if (!set || set->identity || s.n_old == 0) s.ident_n = s.n_old;        // an empty set: the identity on [0, 0)
+    else s.tab = set_dense_table(set, extent, st);
+    if (transform == IBH_ADD_DENSE) {
+        s.first = A.get<uint32_t>((size_t)extent);
+        IBH_HIP(hipMemsetAsync(s.first, 0xFF, sizeof(uint32_t) * (size_t)extent, st));
+        nb.flag = A.get<uint32_t>((size_t)n + 1);
+        if (n) {
+            hipLaunchKernelGGL(k_hm_first, dim3(ceil_div(n, 256)), dim3(256), 0, st, s, key, n);
+            hipLaunchKernelGGL(k_hm_newflag, dim3(ceil_div(n, 256)), dim3(256), 0, st, s, key, n, nb.flag);
+        }
+        exclusive_scan_u32(nb.flag, nb.flag, (size_t)n, nb.flag + n, st);
+        s.rank = nb.flag;
+    }
+    IBH_HIP(hipGetLastError());
+    return nb;
+}
+// the set's grown dense -> sparse table (old entries, then the new keys first-seen); empty when it gains nothing
+static DevBuf<int64_t> hm_number_grow(HmNumber &nb, const int32_t *key, long n, uint32_t n_new, hipStream_t st) {
+    DevBuf<int64_t> grown;
+    if (!nb.set || nb.s.transform != IBH_ADD_DENSE || n_new == 0) return grown;
+    const int n_old = nb.s.n_old;
+    grown.alloc((size_t)n_old + n_new);
+    const int64_t *old = hm_set_table(nb.set, n_old, st);
+    if (n_old) IBH_HIP(hipMemcpyAsync(grown.p, old, sizeof(int64_t) * (size_t)n_old, hipMemcpyDeviceToDevice, st));
+    hipLaunchKernelGGL(k_hm_newkeys, dim3(ceil_div(n, 256)), dim3(256), 0, st, key, n, nb.flag, grown.p + n_old);
+    IBH_HIP(hipGetLastError());
+    return grown;
+}
+// adopt the grown table (nothing here can fail): called only once everything else has succeeded
+static void hm_number_adopt(HmNumber &nb, DevBuf<int64_t> &grown) noexcept {
+    ibh_sparse_set *set = nb.set;
+    if (!set) return;
+    set->sparse_extent = nb.extent;
+    if (!grown.p) return;
+    if (set->identity) { set->host.clear(); set->host_n = 0; }
+    set->dev_n = set->n = (int32_t)grown.n;
+    set->dev = std::move(grown);
+    set->identity = false;
+}
+
+static void hntr_matrix(const ibh_hntr *h, int kind, double eq_rad, const uint8_t *includeB, ibh_sparse_set *dimB, int tB,
+                        ibh_sparse_set *dimA, int tA, int transpose, ibh_weighted **out) {
+    IBH_CHECK(out != nullptr, "null argument");
+    hm_check_kind(kind);
+    hm_check_transform(tB, "dimB");
+    hm_check_transform(tA, "dimA");
+    hm_check(h, kind);
+    const int64_t nB = (int64_t)h->imB * h->jmB, nA = (int64_t)h->imA * h->jmA;
+    dimB = hm_dims(dimB, nB, "dimB");
+    dimA = hm_dims(dimA, nA, "dimA");
+    IBH_CHECK(dimB == nullptr || dimB != dimA, "Hntr matrix_d: dimB and dimA must be distinct sets");
+    const bool fast = !transpose && hm_full_identity(dimB, nB) && hm_full_identity(dimA, nA);
+    const int64_t n = hm_count_host(h, includeB, fast);
+    IBH_CHECK(n <= INT32_MAX, "Hntr matrix_d: %lld entries exceed INT32_MAX (the row pointer is int32)", (long long)n);
+    hipStream_t st = nullptr;
+    Arena &A = arena();
+    A.reset();
+    std::unique_ptr<ibh_weighted> w(new ibh_weighted);
+    IBH_HIP(hipGetDevice(&w->device));
+    w->conservative = 1;
+    w->scaled = kind == IBH_HNTR_SCALED;
+    HmNumber nbB, nbA;          // the fast path numbers nothing: the sets only take their sparse extent
+    nbB.set = dimB; nbB.extent = nB;
+    nbA.set = dimA; nbA.extent = nA;
+    DevBuf<int64_t> grownB, grownA;
+    if (fast) {
+        w->nrow = (int32_t)nB; w->ncol = (int32_t)nA; w->nnz = n;
+        w->rowptr.alloc((size_t)nB + 1); w->colind.alloc((size_t)n); w->val.alloc((size_t)n);
+        w->wM.alloc((size_t)nB); w->Mw.alloc((size_t)nA);
+        uint32_t *ptr = reinterpret_cast<uint32_t *>(w->rowptr.p);
+        HmArgs a = hm_prepare(h, kind, eq_rad, includeB, true, ptr, st);
+        const int tpr = hm_tpr(n, nB);
+        if (n) hipLaunchKernelGGL(k_hm_fill, dim3(ceil_div(nB, 256 / tpr)), dim3(256), 0, st, a, tpr, w->rowptr.p, w->colind.p, w->val.p);
+        hipLaunchKernelGGL(k_hm_rowsum, dim3(ceil_div(nB, 64)), dim3(64), 0, st, a, w->wM.p);
+        hipLaunchKernelGGL(k_hm_colsum, dim3(ceil_div(nA, 256)), dim3(256), 0, st, a, w->Mw.p);
+        IBH_HIP(hipGetLastError());
+        IBH_HIP(hipStreamSynchronize(st));
+    } else {
+        uint32_t *ptr = A.get<uint32_t>((size_t)nB + 1);
+        HmArgs a = hm_prepare(h, kind, eq_rad, includeB, false, ptr, st);
+        int32_t *iB = A.get<int32_t>((size_t)n), *iA = A.get<int32_t>((size_t)n);
+        double *v = A.get<double>((size_t)n);
+        const int tpr = hm_tpr(n, nB);
+        if (n) hipLaunchKernelGGL(k_hm_triplets, dim3(ceil_div(nB, 256 / tpr)), dim3(256), 0, st, a, tpr, ptr, iB, iA, v);
+        uint32_t *keep = A.get<uint32_t>((size_t)n + 1), *bad = A.get<uint32_t>(1);
+        uint8_t *act = A.get<uint8_t>((size_t)n);
+        IBH_HIP(hipMemsetAsync(bad, 0, sizeof(uint32_t), st));
+        nbB = hm_number_prepare(dimB, nB, tB, iB, (long)n, nullptr, st);
+        if (n) hipLaunchKernelGGL(k_hm_gate, dim3(ceil_div(n, 256)), dim3(256), 0, st, nbB.s, iB, (long)n, act, bad);
+        nbA = hm_number_prepare(dimA, nA, tA, iA, (long)n, act, st);
+        if (n) hipLaunchKernelGGL(k_hm_keep, dim3(ceil_div(n, 256)), dim3(256), 0, st, nbA.s, iA, (long)n, keep, bad);
+        exclusive_scan_u32(keep, keep, (size_t)n, keep + n, st);
+        struct { uint32_t kept, bad, newB, newA; } rb{0, 0, 0, 0};
+        readback_sync(&rb.kept, keep + n, sizeof(uint32_t), st);
+        readback_sync(&rb.bad, bad, sizeof(uint32_t), st);
+        if (nbB.flag) readback_sync(&rb.newB, nbB.flag + n, sizeof(uint32_t), st);
+        if (nbA.flag) readback_sync(&rb.newA, nbA.flag + n, sizeof(uint32_t), st);
+        IBH_CHECK(!rb.bad, "Hntr matrix_d: a key is missing from a TO_DENSE set");
+        const int nrowB = (nbB.set ? nbB.s.n_old : (int)nB) + (int)rb.newB;
+        const int ncolA = (nbA.set ? nbA.s.n_old : (int)nA) + (int)rb.newA;
+        int32_t *row = A.get<int32_t>(rb.kept), *col = A.get<int32_t>(rb.kept);
+        double *val = A.get<double>(rb.kept);
+        if (n) hipLaunchKernelGGL(k_hm_compact, dim3(ceil_div(n, 256)), dim3(256), 0, st, nbB.s, nbA.s, iB, iA, v, (long)n, keep,
+                                  transpose, row, col, val);
+        IBH_HIP(hipGetLastError());
+        weighted_from_device_triplets(w.get(), transpose ? ncolA : nrowB, transpose ? nrowB : ncolA, rb.kept, row, col, val, st);
+        // both grown tables exist before either set changes: an error up to here leaves both sets as they were
+        grownB = hm_number_grow(nbB, iB, (long)n, rb.newB, st);
+        grownA = hm_number_grow(nbA, iA, (long)n, rb.newA, st);
+        IBH_HIP(hipStreamSynchronize(st));
+    }
+    std::unique_ptr<ibh_sparse_set> fresh[2];
+    for (int k = 0; k < 2; ++k)
+        if (!(k ? dimA : dimB)) {
+            fresh[k].reset(new ibh_sparse_set);
+            fresh[k]->sparse_extent = fresh[k]->n = (int32_t)(k ? nA : nB);
+            fresh[k]->identity = true;
+        }
+    hm_number_adopt(nbB, grownB);
+    hm_number_adopt(nbA, grownA);
+    const bool ownB = !dimB, ownA = !dimA;
+    ibh_sparse_set *dB = ownB ? fresh[0].release() : dimB, *dA = ownA ? fresh[1].release() : dimA;
+    w->dims[0] = transpose ? dA : dB; w->owns[0] = transpose ? ownA : ownB;
+    w->dims[1] = transpose ? dB : dA; w->owns[1] = transpose ? ownB : ownA;
+    *out = w.release();
+}
+
+static void hntr_triplets(const ibh_hntr *h, int kind, double eq_rad, const uint8_t *includeB, int64_t *n, int32_t *iB, int32_t *iA,
+                          double *val) {
+    hm_check_kind(kind);
+    IBH_CHECK(h != nullptr && n != nullptr, "null argument");
+    const int64_t cnt = hm_count_host(h, includeB, false);
+    *n = cnt;
+    IBH_CHECK(cnt <= INT32_MAX, "Hntr triplets: %lld entries exceed INT32_MAX", (long long)cnt);
+    if (!iB && !iA && !val) return;
+    IBH_CHECK(iB && iA && val, "Hntr triplets: iB, iA and val must all be given (or all NULL)");
+    hm_check(h, kind);
+    hipStream_t st = nullptr;
+    Arena &A = arena();
+    A.reset();
+    const long nB = (long)h->imB * h->jmB;
+    uint32_t *ptr = A.get<uint32_t>((size_t)nB + 1);
+    HmArgs a = hm_prepare(h, kind, eq_rad, includeB, false, ptr, st);
+    int32_t *dB = A.get<int32_t>((size_t)cnt), *dA = A.get<int32_t>((size_t)cnt);
+    double *dv = A.get<double>((size_t)cnt);
+    const int tpr = hm_tpr(cnt, nB);
+    if (cnt) hipLaunchKernelGGL(k_hm_triplets, dim3(ceil_div(nB, 256 / tpr)), dim3(256), 0, st, a, tpr, ptr, dB, dA, dv);
+    IBH_HIP(hipGetLastError());
+    if (cnt) {
+        IBH_HIP(hipMemcpyAsync(iB, dB, sizeof(int32_t) * (size_t)cnt, hipMemcpyDeviceToHost, st));
+        IBH_HIP(hipMemcpyAsync(iA, dA, sizeof(int32_t) * (size_t)cnt, hipMemcpyDeviceToHost, st));
+        IBH_HIP(hipMemcpyAsync(val, dv, sizeof(double) * (size_t)cnt, hipMemcpyDeviceToHost, st));
+    }
+    IBH_HIP(hipStreamSynchronize(st));
+}
+
 }  // namespace ibh
 
 extern "C" {
@@ -400,6 +979,7 @@ int ibh_hntr_create(ibh_hntr **out, int32_t imA, int32_t jmA, double offiA, doub
         h->GMAX.upload(p.GMAX.data(), p.GMAX.size()); h->IMIN.upload(p.IMIN.data(), p.IMIN.size());
         h->IMAX.upload(p.IMAX.data(), p.IMAX.size()); h->JMIN.upload(p.JMIN.data(), p.JMIN.size());
         h->JMAX.upload(p.JMAX.data(), p.JMAX.size());
+        hntr_matrix_tables(h.get(), p);
         IBH_HIP(hipStreamSynchronize(nullptr));
         *out = h.release();
     });
@@ -432,6 +1012,27 @@ int ibh_hntr_regrid_host(const ibh_hntr *h, const double *WTA, int64_t wta_ld, c
         IBH_HIP(hipMemcpy2DAsync(B, sizeof(double) * (size_t)ldb, dB.p, sizeof(double) * nB, sizeof(double) * nB, (size_t)nvar,
                                  hipMemcpyDeviceToHost, nullptr));
         IBH_HIP(hipStreamSynchronize(nullptr));
+    });
+}
+
+int ibh_hntr_dxyp(int32_t im, int32_t jm, double *dxyp) {
+    return guarded([&] {
+        IBH_CHECK(dxyp != nullptr, "null output array");
+        IBH_CHECK(im >= 1 && jm >= 1, "Hntr dxyp: im=%d jm=%d (both must be >= 1)", im, jm);
+        hntr_dxyp(im, jm, dxyp);
+    });
+}
+
+int ibh_hntr_triplets(const ibh_hntr *h, int kind, double eq_rad, const uint8_t *includeB, int64_t *n, int32_t *iB, int32_t *iA,
+                      double *val) {
+    return guarded([&] { hntr_triplets(h, kind, eq_rad, includeB, n, iB, iA, val); });
+}
+
+int ibh_hntr_matrix_d(const ibh_hntr *h, int kind, double eq_rad, const uint8_t *includeB, ibh_sparse_set *dimB, int tB,
+                      ibh_sparse_set *dimA, int tA, int transpose, ibh_weighted **out) {
+    return guarded([&] {
+        if (out) *out = nullptr;
+        hntr_matrix(h, kind, eq_rad, includeB, dimB, tB, dimA, tA, transpose, out);
     });
 }
 

@@ -10,6 +10,10 @@ import numpy as np
 from . import _capi
 from ._capi import check, lib, ptr
 
+# kinds of Hntr matrix (ibh_hntr_matrix_d) and the to-dense transforms of MakeDenseEigenT
+OVERLAP, SCALED = 0, 1
+ADD_DENSE, TO_DENSE, TO_DENSE_IGNORE_MISSING = 0, 1, 2
+
 
 class HntrSpec:
     """HntrSpec(im, jm, offi, dlat) (GridSpec.hpp:143-160): offi = cells from the date line to the western edge
@@ -40,6 +44,19 @@ def partition(Bspec, Aspec):
                                    *[ptr(out[k]) for k in ("SINA", "SINB", "IMIN", "IMAX", "FMIN", "FMAX", "JMIN", "JMAX", "GMIN",
                                                            "GMAX")]))
     return out
+
+
+def make_dxyp(spec):
+    """make_dxyp(spec) (hntr.cpp:33-52): the areas of grid rows on a unit sphere, [jm], host only (ibh_hntr_dxyp).  Index j-1
+    holds the reference's dxyp(j)."""
+    out = np.zeros(spec.jm)
+    check(lib().ibh_hntr_dxyp(spec.im, spec.jm, ptr(out)))
+    return out
+
+
+def _kind(kind):
+    k = {"overlap": OVERLAP, "scaled": SCALED}.get(kind, kind)
+    return int(k)
 
 
 class Hntr:
@@ -89,6 +106,48 @@ class Hntr:
         if single:
             return B[0].reshape(self.Bgrid.jm, self.Bgrid.im) if np.ndim(A) == 2 else B[0]
         return B
+
+    def _mask(self, includeB):
+        if includeB is None:
+            return None
+        m = np.ascontiguousarray(np.asarray(includeB).reshape(-1), np.uint8)
+        if m.size != self.Bgrid.size:
+            raise ValueError("includeB has %d entries, grid B has %d cells" % (m.size, self.Bgrid.size))
+        return m
+
+    def triplets(self, kind, eq_rad=1., includeB=None):
+        """The entries of Hntr::matrix in stream order (ibh_hntr_triplets): (iB, iA, val), 0-based sparse indices."""
+        m = self._mask(includeB)
+        n = C.c_int64()
+        mp = ptr(m) if m is not None else None
+        check(lib().ibh_hntr_triplets(self._h, _kind(kind), float(eq_rad), mp, C.byref(n), None, None, None))
+        iB, iA, val = np.zeros(n.value, np.int32), np.zeros(n.value, np.int32), np.zeros(n.value)
+        if n.value:
+            check(lib().ibh_hntr_triplets(self._h, _kind(kind), float(eq_rad), mp, C.byref(n), ptr(iB), ptr(iA), ptr(val)))
+        return iB, iA, val
+
+    def overlap(self, eq_rad, includeB=None):
+        """Hntr::overlap(accum, eq_rad, includeB) (hntr.hpp:284-291): what the accumulator receives, in order, as
+        (iB, iA, val); includeB is a boolean mask over grid B (the functor or DimClip evaluated), None for every cell."""
+        return self.triplets(OVERLAP, eq_rad, includeB)
+
+    def scaled_regrid_matrix(self, includeB=None):
+        """Hntr::scaled_regrid_matrix(accum, includeB) (hntr.hpp:327-336) as stream-order (iB, iA, val)."""
+        return self.triplets(SCALED, 1., includeB)
+
+    def matrix_d(self, kind, eq_rad=1., includeB=None, dims=(None, None), transforms=(ADD_DENSE, ADD_DENSE), transpose=False):
+        """MakeDenseEigenT(overlap | scaled_regrid_matrix, transforms, dims, 'T' if transpose else '.') as a linear_Weighted in
+        HBM (ibh_hntr_matrix_d).  kind: OVERLAP / SCALED or "overlap" / "scaled".  dims = (dimB, dimA): SparseSet (IN/OUT) or
+        None for a fresh identity set; transforms: per generator index (B, then A) ADD_DENSE, TO_DENSE or
+        TO_DENSE_IGNORE_MISSING; transpose swaps only the output (rows A, columns B)."""
+        from .linear import linear_Weighted
+        m = self._mask(includeB)
+        h = C.c_void_p()
+        dB = dims[0]._h if dims[0] is not None else None
+        dA = dims[1]._h if dims[1] is not None else None
+        check(lib().ibh_hntr_matrix_d(self._h, _kind(kind), float(eq_rad), ptr(m) if m is not None else None, dB, int(transforms[0]),
+                                      dA, int(transforms[1]), int(bool(transpose)), C.byref(h)))
+        return linear_Weighted(h, keep=(self, dims))
 
     def regrid_device(self, WTA, A, out=None, mean_polar=False, wtm=1., wtb=0., stream=None):
         """The same on fields resident in HBM: torch.float64 CUDA tensors, A [nvar, Agrid.size] (row stride >= size),

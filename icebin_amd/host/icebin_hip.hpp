@@ -5,6 +5,7 @@
 //   RegridMatrices_Dynamic::matrix_d()/matrix() (slib/icebin/RegridMatrices_Dynamic.hpp:51-59)
 //   linear::Weighted_Eigen::apply()           (call sites modele/merge_topo.cpp:65, icebin22m.cpp:153)
 //   modele::Hntr::regrid()                    (slib/icebin/modele/hntr.hpp:63-135; topo.cpp's lat-lon regrids)
+//   modele::Hntr::overlap() / scaled_regrid_matrix() (hntr.hpp:205-338; GCMRegridder_ModelE.cpp, topo.cpp, global_ec.cpp)
 // can switch to this header and link libicebin_hip.so instead of ibmisc/spsparse/Eigen.
 // Differences, all forced by the absent third-party types:
 //   - blitz::Array<double,N>  -> icebin::ArrayView<double> (pointer + extents, row-major, borrowed)
@@ -738,12 +739,36 @@ struct HntrSpec {
     HntrSpec(int _im, int _jm, double _offi, double _dlat) : im(_im), jm(_jm), offi(_offi), dlat(_dlat) {}
     int size() const { return im * jm; }
 };
-/** The part of HntrGrid (hntr.hpp:17-54) a caller of Hntr reads: hntr.Agrid.spec, hntr.Bgrid.spec. */
+/** make_dxyp(spec) (hntr.cpp:33-52): areas of the grid's rows on a unit sphere, 0-based storage [jm] (ibh_hntr_dxyp, host only). */
+inline std::vector<double> make_dxyp(HntrSpec const &spec) {
+    std::vector<double> d((size_t)(spec.jm > 0 ? spec.jm : 0));
+    check(ibh_hntr_dxyp(spec.im, spec.jm, d.data()));
+    return d;
+}
+/** The part of HntrGrid (hntr.hpp:17-54) a caller of Hntr reads: hntr.Agrid.spec, hntr.Bgrid.spec, and dxyp(j) with the
+    reference's 1-based (Fortran) indexing, j = 1..jm. */
 struct HntrGrid {
     HntrSpec spec;
+    std::vector<double> dxyp_;
     HntrGrid() {}
-    explicit HntrGrid(HntrSpec const &s) : spec(s) {}
+    explicit HntrGrid(HntrSpec const &s) : spec(s), dxyp_(make_dxyp(s)) {}
+    double dxyp(int j) const { return dxyp_.at((size_t)(j - 1)); }
 };
+
+/** DimClip (hntr.hpp:186-197): includes a B cell iff the set holds it. */
+struct DimClip {
+    SparseSetT const *dim;
+    explicit DimClip(SparseSetT const *_dim) : dim(_dim) {}
+    bool operator()(int ix) const { return dim->in_sparse(ix); }
+};
+/** The default includeB of the matrix forms: every B cell. */
+struct IncludeAll {
+    bool operator()(int) const { return true; }
+};
+/** spsparse's DenseTransform, per index of MakeDenseEigenT. */
+enum class DenseTransform { ADD_DENSE = IBH_ADD_DENSE, TO_DENSE = IBH_TO_DENSE, TO_DENSE_IGNORE_MISSING = IBH_TO_DENSE_IGNORE_MISSING };
+/** Which accumulator of Hntr::matrix: OverlapMatAccum (overlap) or ScaledRegridMatAccum (scaled_regrid_matrix). */
+enum class HntrMatrix { OVERLAP = IBH_HNTR_OVERLAP, SCALED = IBH_HNTR_SCALED };
 
 /** Hntr (hntr.hpp:63-135): the partition is computed and uploaded to the current HIP device by the constructor; regrid
     runs on that device.  Owns a device handle: movable, not copyable. */
@@ -787,6 +812,53 @@ public:
         check(ibh_hntr_regrid_device(h_, dWTA, wta_ld, dA, nvar, lda, dB, ldb, mean_polar ? 1 : 0, wtm, wtb, stream));
     }
     ibh_hntr *handle() const { return h_; }
+
+    /** overlap(accum, eq_rad, includeB) (hntr.hpp:284-291): accum.add({iB, iA}, FG * (1/WEIGHT) * (R2*dxyp(JB))) for every
+        term, in the reference's stream order, 0-based sparse indices.  includeB(IJB-1) is evaluated on the host for every B
+        cell first; the entries are computed on the device (ibh_hntr_triplets). */
+    template <class AccumT, class IncludeT = IncludeAll>
+    void overlap(AccumT &&accum, double eq_rad, IncludeT includeB = IncludeAll()) const {
+        feed(accum, HntrMatrix::OVERLAP, eq_rad, includeB);
+    }
+    /** scaled_regrid_matrix(accum, includeB) (hntr.hpp:327-336): the same with FG * (1/WEIGHT). */
+    template <class AccumT, class IncludeT = IncludeAll>
+    void scaled_regrid_matrix(AccumT &&accum, IncludeT includeB = IncludeAll()) const {
+        feed(accum, HntrMatrix::SCALED, 1.0, includeB);
+    }
+    /** MakeDenseEigenT(overlap | scaled_regrid_matrix, transforms, dims, transpose) (GCMRegridder_ModelE.cpp:92-121) as a
+        Weighted in HBM (ibh_hntr_matrix_d): dims = {dimB, dimA}, IN/OUT, nullptr for a fresh identity set owned by the result;
+        transforms per generator index (B, then A); transpose 'T' swaps only the output.  wM / Mw are the row / column sums. */
+    template <class IncludeT = IncludeAll>
+    std::unique_ptr<linear::Weighted> matrix_d(HntrMatrix kind, double eq_rad, std::array<SparseSetT *, 2> const &dims = {{nullptr, nullptr}},
+                                               std::array<DenseTransform, 2> const &transforms = {{DenseTransform::ADD_DENSE, DenseTransform::ADD_DENSE}},
+                                               char transpose = '.', IncludeT includeB = IncludeAll()) const {
+        std::vector<uint8_t> mask;
+        const uint8_t *m = include_mask(includeB, mask);
+        ibh_weighted *w = nullptr;
+        check(ibh_hntr_matrix_d(h_, (int)kind, eq_rad, m, dims[0] ? dims[0]->handle() : nullptr, (int)transforms[0],
+                                dims[1] ? dims[1]->handle() : nullptr, (int)transforms[1], transpose == 'T' ? 1 : 0, &w));
+        return std::unique_ptr<linear::Weighted>(new linear::Weighted(w));
+    }
+
+private:
+    const uint8_t *include_mask(IncludeAll const &, std::vector<uint8_t> &) const { return nullptr; }
+    template <class IncludeT>
+    const uint8_t *include_mask(IncludeT const &includeB, std::vector<uint8_t> &mask) const {
+        mask.resize((size_t)Bgrid.spec.size());
+        for (int i = 0; i < Bgrid.spec.size(); ++i) mask[(size_t)i] = includeB(i) ? 1 : 0;
+        return mask.data();
+    }
+    template <class AccumT, class IncludeT>
+    void feed(AccumT &accum, HntrMatrix kind, double eq_rad, IncludeT const &includeB) const {
+        std::vector<uint8_t> mask;
+        const uint8_t *m = include_mask(includeB, mask);
+        int64_t n = 0;
+        check(ibh_hntr_triplets(h_, (int)kind, eq_rad, m, &n, nullptr, nullptr, nullptr));
+        std::vector<int32_t> iB((size_t)n), iA((size_t)n);
+        std::vector<double> val((size_t)n);
+        if (n) check(ibh_hntr_triplets(h_, (int)kind, eq_rad, m, &n, iB.data(), iA.data(), val.data()));
+        for (size_t k = 0; k < (size_t)n; ++k) accum.add({iB[k], iA[k]}, val[k]);
+    }
 };
 }   // namespace modele
 

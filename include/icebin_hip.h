@@ -122,6 +122,44 @@ int ibh_hntr_partition(int32_t imA, int32_t jmA, double offiA, double dlatA, int
                        double dlatB, double *SINA, double *SINB, int32_t *IMIN, int32_t *IMAX, double *FMIN, double *FMAX,
                        int32_t *JMIN, int32_t *JMAX, double *GMIN, double *GMAX);
 
+/* Hntr's matrix forms (hntr.hpp:205-338: Hntr::matrix with OverlapMatAccum / ScaledRegridMatAccum; hntr.cpp:33-52
+ * make_dxyp).  The included B cells are visited in stream order: JB, then IB, ascending; inside a cell JA from JMIN(JB) to
+ * JMAX(JB), then IAREV from IMIN(IB) to IMAX(IB), IA = 1 + (IAREV-1) % imA, term FG = F*G.  Every term becomes the entry
+ * (IJB-1, IJA-1) with value FG * (1/WEIGHT) * (R2*dxyp(JB)) (IBH_HNTR_OVERLAP, R2 = eq_rad^2) or FG * (1/WEIGHT)
+ * (IBH_HNTR_SCALED), WEIGHT = the cell's FG summed in stream order.  includeB: host byte mask [imB*jmB] (NULL: every cell),
+ * what the reference's includeB functor or DimClip answers. */
+#define IBH_HNTR_OVERLAP 0
+#define IBH_HNTR_SCALED  1
+/* make_dxyp (hntr.cpp:33-52): dxyp[j-1] = dLON*(sin(dLAT*(j-jm/2)) - sin(dLAT*(j-jm/2-1))), dLON = 2pi/im, dLAT = pi/jm,
+ * jm/2 in integer division; offi and dlat play no part.  Host only, no device needed. */
+int ibh_hntr_dxyp(int32_t im, int32_t jm, double *dxyp /* [jm] */);
+/* The entries in stream order, for an arbitrary host accumulator (accum.add({iB, iA}, val)): iB, iA 0-based sparse.  With
+ * iB, iA and val all NULL only *n is set (host only); otherwise the three arrays hold *n entries.  More than INT32_MAX
+ * entries: IBH_EINVAL, with *n set, also when only asking for *n. */
+int ibh_hntr_triplets(const ibh_hntr *h, int kind, double eq_rad, const uint8_t *includeB, int64_t *n, int32_t *iB,
+                      int32_t *iA, double *val);
+/* Transforms of MakeDenseEigenT (spsparse): ADD_DENSE numbers keys first-seen in stream order, TO_DENSE fails with
+ * IBH_EINVAL on a key the set lacks, TO_DENSE_IGNORE_MISSING drops the entry.  An entry's indices are transformed in
+ * order, B then A, and the entry stops at the first index dropped: when TO_DENSE_IGNORE_MISSING drops its B index, its A
+ * index is neither numbered nor looked up. */
+#define IBH_ADD_DENSE               0
+#define IBH_TO_DENSE                1
+#define IBH_TO_DENSE_IGNORE_MISSING 2
+typedef struct ibh_weighted ibh_weighted;      /* declared with the Weighted entries below */
+/* MakeDenseEigenT(overlap | scaled_regrid_matrix, {tB, tA}, {dimB, dimA}, transpose ? 'T' : '.') as a Weighted in HBM
+ * (GCMRegridder_ModelE.cpp:92-121): transforms are given per generator index (B first, then A) whatever transpose is;
+ * transpose only swaps the output (rows A, columns B).  Duplicate entries (a window wider than imA visits one A column twice)
+ * are summed in stream order; columns ascend inside a row.  wM / Mw are the row / column sums, visited column-major
+ * (sum(M, dim, '+')); conservative = 1, scaled = 0 for the overlap and 1 for the scaled matrix.
+ * dimB / dimA are IN/OUT as in ibh_regrid_matrices_matrix_d and must outlive the result; NULL gives a fresh identity set over
+ * the whole grid, owned by the result.  A set whose sparse extent is -1 takes the grid's size; any other extent is IBH_EINVAL,
+ * as are a bad kind or transform and the same set on both sides.  More than INT32_MAX entries is IBH_EINVAL before anything
+ * is allocated.  On any error *out is NULL and both sets are as they were: new keys are adopted only once the matrix is built.
+ * With NULL or full identity dims and no transpose the CSR is built in place, without a sort; other dims go through a
+ * first-seen numbering on the device and setFromTriplets. */
+int ibh_hntr_matrix_d(const ibh_hntr *h, int kind, double eq_rad, const uint8_t *includeB, ibh_sparse_set *dimB, int tB,
+                      ibh_sparse_set *dimA, int tA, int transpose, ibh_weighted **out);
+
 /* ------------------------------------------------------------------------- */
 /* Regridder: the state of GCMRegridder_Standard (GCMRegridder.hpp:207-302) and
  * one IceRegridder_L0 (IceRegridder.hpp:46-133) that the path reads, uploaded

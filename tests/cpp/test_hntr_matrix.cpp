@@ -1,0 +1,96 @@
+// C++ test of the matrix forms of icebin::modele::Hntr in icebin_amd/host/icebin_hip.hpp, used the way
+// GCMRegridder_ModelE.cpp (compute_AOmvAAm, make_agridA) and topo.cpp use them: overlap / scaled_regrid_matrix into a
+// user accumulator, with and without a DimClip, and matrix_d into a Weighted.  The entries are written to
+// <outdir>/*.bin, which tests/test_cpp_hntr_matrix.py compares bitwise with the Python surface.
+// Exit code 0 = pass, 3 = no GPU (the no-fallback error path was verified instead).
+#include <array>
+#include <cstdio>
+#include <string>
+#include <vector>
+
+#include "../../icebin_amd/host/icebin_hip.hpp"
+
+using namespace icebin;
+using icebin::modele::DenseTransform;
+using icebin::modele::DimClip;
+using icebin::modele::Hntr;
+using icebin::modele::HntrMatrix;
+using icebin::modele::HntrSpec;
+
+#define REQUIRE(cond)                                                        \
+    do {                                                                     \
+        if (!(cond)) { std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); return 1; } \
+    } while (0)
+
+// a user accumulator in the reference's shape: add({iB, iA}, value)
+struct Collect {
+    std::vector<int> iB, iA;
+    std::vector<double> val;
+    void add(std::array<int, 2> const &ix, double v) { iB.push_back(ix[0]); iA.push_back(ix[1]); val.push_back(v); }
+};
+
+static bool dump(std::string const &path, std::vector<int> const &a, std::vector<int> const &b, std::vector<double> const &v) {
+    FILE *f = std::fopen(path.c_str(), "wb");
+    if (!f) return false;
+    const long n = (long)v.size();
+    bool ok = std::fwrite(&n, sizeof(n), 1, f) == 1 && std::fwrite(a.data(), sizeof(int), a.size(), f) == a.size() &&
+              std::fwrite(b.data(), sizeof(int), b.size(), f) == b.size() && std::fwrite(v.data(), sizeof(double), v.size(), f) == v.size();
+    return std::fclose(f) == 0 && ok;
+}
+
+// the clip set: B cells with (IJB * 7) % 3 != 0, added in ascending order (the Python side rebuilds the same mask)
+static bool clipped(int i) { return (i * 7) % 3 != 0; }
+
+int main(int argc, char **argv) {
+    const std::string out = argc > 1 ? argv[1] : ".";
+    const HntrSpec B(72, 46, 0.5, 240.), A(144, 90, 0.25, 120.);
+    try {
+        Hntr h(17.17, B, A);
+        // HntrGrid::dxyp, 1-based
+        REQUIRE(h.Bgrid.dxyp(1) == modele::make_dxyp(B)[0] && h.Bgrid.dxyp(B.jm) == modele::make_dxyp(B)[(size_t)B.jm - 1]);
+
+        Collect all;
+        h.overlap(all, 6371000.);
+        REQUIRE(!all.val.empty());
+        REQUIRE(dump(out + "/overlap.bin", all.iB, all.iA, all.val));
+
+        SparseSetT dimB(B.size());
+        for (int i = 0; i < B.size(); ++i)
+            if (clipped(i)) dimB.add_dense(i);
+        Collect clip;
+        h.scaled_regrid_matrix(clip, DimClip(&dimB));
+        REQUIRE(!clip.val.empty() && clip.val.size() < all.val.size());
+        for (int b : clip.iB) REQUIRE(clipped(b));
+        REQUIRE(dump(out + "/scaled_clip.bin", clip.iB, clip.iA, clip.val));
+
+        // compute_AOmvAAm's call: clipped B, A numbered first-seen, transposed
+        SparseSetT dimA;
+        auto M = h.matrix_d(HntrMatrix::OVERLAP, 6371000., {{&dimB, &dimA}},
+                            {{DenseTransform::TO_DENSE_IGNORE_MISSING, DenseTransform::ADD_DENSE}}, 'T', DimClip(&dimB));
+        REQUIRE(M->shape_d()[0] == dimA.dense_extent() && M->shape_d()[1] == dimB.dense_extent());
+        REQUIRE(dimA.dense_extent() > 0 && dimA.sparse_extent() == A.size());
+        REQUIRE(M->conservative && !M->scaled);
+        REQUIRE((long)M->wM().size() == dimA.dense_extent());
+        std::vector<int> r, c;
+        std::vector<double> v;
+        M->M_coo(r, c, v);
+        REQUIRE((long)v.size() == M->nnz());
+        REQUIRE(dump(out + "/matrix_T.bin", r, c, v));
+        std::vector<int> dA(dimA.to_sparse_all().begin(), dimA.to_sparse_all().end());
+        REQUIRE(dump(out + "/dimA.bin", dA, dA, std::vector<double>(dA.size(), 0.)));
+
+        // NULL dims: identity sets owned by the result
+        auto S = h.matrix_d(HntrMatrix::SCALED, 1.0);
+        REQUIRE(S->shape_d()[0] == B.size() && S->shape_d()[1] == A.size() && S->scaled);
+        REQUIRE(S->dim_to_sparse(0).size() == (size_t)B.size());
+    } catch (Exception const &e) {
+        if (e.code == IBH_ENODEVICE) {
+            std::printf("no GPU: %s (no CPU fallback)\n", e.what());
+            return 3;
+        }
+        std::printf("FAILED: exception %d: %s\n", e.code, e.what());
+        return 1;
+    }
+    std::printf("all checks passed\n");
+    return 0;
+}
