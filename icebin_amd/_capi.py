@@ -29,6 +29,12 @@ class RegridderDesc(C.Structure):
     ]
 
 
+class HntrRegridderDesc(C.Structure):
+    _fields_ = [("hntr", C.c_void_p), ("eq_rad", C.c_double), ("elevmaskI", C.c_void_p), ("nmask", C.c_int64),
+                ("mask_on_device", C.c_int32), ("stream", C.c_void_p), ("nhc", C.c_int32), ("hcdefs", C.c_void_p),
+                ("hc_stride_A", C.c_int64), ("hc_stride_HC", C.c_int64), ("interp_style", C.c_int32)]
+
+
 class ExgridDesc(C.Structure):
     _fields_ = [("nx", C.c_int32), ("ny", C.c_int32), ("xedges", C.c_void_p), ("yedges", C.c_void_p), ("x_fastest", C.c_int32),
                 ("npoly", C.c_int32), ("polyptr", C.c_void_p), ("vx", C.c_void_p), ("vy", C.c_void_p), ("iA", C.c_void_p)]
@@ -61,6 +67,10 @@ _SIGS = {
     "ibh_regridder_sizes": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                      C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
     "ibh_regridder_wA": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_void_p]),
+    "ibh_hntr_exgrid_count": (C.c_int, [C.POINTER(HntrRegridderDesc), C.POINTER(C.c_int64)]),
+    "ibh_regridder_create_hntr": (C.c_int, [C.POINTER(HntrRegridderDesc), C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "ibh_regridder_exgrid": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p]),
+    "ibh_regridder_agridA": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p]),
     "ibh_regrid_matrices_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p,
                                             C.POINTER(C.c_void_p)]),
     "ibh_regrid_matrices_create_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p,
@@ -76,6 +86,8 @@ _SIGS = {
     "ibh_weighted_from_csr": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "ibh_e1ve0_compute": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_void_p)]),
+    "ibh_weighted_make_I2vX": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_int64, C.c_void_p,
+                                        C.POINTER(C.c_void_p)]),
     "ibh_weighted_destroy": (C.c_int, [C.c_void_p]),
     "ibh_weighted_shape": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     "ibh_weighted_flags": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),

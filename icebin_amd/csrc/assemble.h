@@ -28,6 +28,8 @@ void weighted_from_device_triplets(ibh_weighted *w, int nrow, int ncol, int64_t 
                                    const double *dval, hipStream_t st);
 // compute_E1vE0c (e1ve0.cpp:55-106) on device; `out` comes with identity dims over nE.
 void e1ve0_compute(int nsheets, const ibh_weighted *const *XuE1s, const ibh_weighted *const *XuE0s, int64_t nE, ibh_weighted *out);
+// make_I2vX's products (global_ec.cpp:345-376): IvI2 = I2vI by columns (rows dense I); fills out's CSR, wM, Mw and flags
+void i2vx_compute(const ibh_weighted *IvI2, const ibh_weighted *IvX, ibh_weighted *out);
 // make_exchange_grid (gridgen/GridGen_Exchange.cpp:175-284) for a rectilinear XY ice grid (gridgen.hip)
 void exgrid_generate(const ibh_exgrid_desc *d, ibh_exgrid *out);
 }  // namespace ibh

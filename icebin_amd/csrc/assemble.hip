@@ -2842,4 +2842,96 @@ void e1ve0_compute(int nsheets, const ibh_weighted *const *XuE1s, const ibh_weig
     IBH_HIP(hipStreamSynchronize(st));
 }
 
+// ---- make_I2vX (modele/global_ec.cpp:345-376) -----------------------------------------------------------------------
+//   M  = (I2vI * diag(1/IvX.wM)) * IvX.M,   wM = (I2vI * diag(sum(I2vI, 1, '-'))) * IvX.wM
+// IvI2 is I2vI stored by its columns: row i (dense I) lists its I2 rows ascending, Eigen's storage order of column i.  Both
+// products sum over the dense I index ascending, so they are keyed sums with terms emitted in row order of IvI2: per I cell,
+// every (i2 of IvI2 row i) x (x of IvX row i) contributes (v * (1/wM_i)) * m to key (i2, x), and every i2 contributes
+// (v * (1/colsum_i)) * wM_i to key i2 -- the assembly machinery (contributions -> order -> sequential sums, first term
+// assigned) does the rest.  The column sum of I2vI runs over its rows ascending from 0, as spsparse's sum(M, 1, '-').
+__global__ void k_i2vx_count(const int32_t *__restrict__ r2, const int32_t *__restrict__ rx, int nI, uint32_t *__restrict__ cnt,
+                             unsigned long long *__restrict__ total) {
+    __shared__ unsigned long long part[4];
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    unsigned long long c = 0;
+    if (i < nI) {
+        c = (unsigned long long)(r2[i + 1] - r2[i]) * (unsigned long long)(rx[i + 1] - rx[i]);
+        cnt[i] = (uint32_t)c;
+    }
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x / 64] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long s = 0;
+        for (int w = 0; w < (int)(blockDim.x / 64); ++w) s += part[w];
+        if (s) atomicAdd(total, s);
+    }
+}
+__global__ void k_i2vx_terms(const int32_t *__restrict__ r2, const int32_t *__restrict__ c2, const double *__restrict__ v2,
+                             const int32_t *__restrict__ rx, const int32_t *__restrict__ cx, const double *__restrict__ vx,
+                             const double *__restrict__ wMx, int nI, const uint32_t *__restrict__ pos, Triplets m, Triplets w) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nI) return;
+    const int b2 = r2[i], e2 = r2[i + 1], bx = rx[i], ex = rx[i + 1];
+    if (b2 == e2) return;
+    double cs = 0;
+    for (int k = b2; k < e2; ++k) cs = cs + v2[k];
+    const double sI = 1. / cs;                 // sum(I2vI, 1, '-')
+    const double sX = 1. / wMx[i];             // 1. / IvX.wM
+    uint32_t p = pos[i];
+    for (int k = b2; k < e2; ++k) {
+        const uint64_t i2 = (uint64_t)(uint32_t)c2[k];
+        w.keys[k] = i2 << 32; w.idx[k] = (uint32_t)k; w.term[k] = (v2[k] * sI) * wMx[i];
+        const double L = v2[k] * sX;
+        for (int q = bx; q < ex; ++q, ++p) { m.keys[p] = (i2 << 32) | (uint32_t)cx[q]; m.idx[p] = p; m.term[p] = L * vx[q]; }
+    }
+}
+__global__ void k_i2vx_wM(const int32_t *__restrict__ rowptr, const double *__restrict__ val, int n, double *__restrict__ wM) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r < n) wM[r] = rowptr[r + 1] > rowptr[r] ? val[rowptr[r]] : 0.;
+}
+
+static Triplets triplets_in_arena(size_t n) {
+    Arena &A = arena();
+    Triplets t;
+    t.n = n;
+    t.keys = A.get<uint64_t>(n); t.keys_alt = A.get<uint64_t>(n);
+    t.idx = A.get<uint32_t>(n); t.idx_alt = A.get<uint32_t>(n);
+    t.term = A.get<double>(n);
+    return t;
+}
+
+void i2vx_compute(const ibh_weighted *IvI2, const ibh_weighted *IvX, ibh_weighted *out) {
+    IBH_CHECK(IvI2->nrow == IvX->nrow, "make_I2vX: I2vI has %d ice columns, IvX %d ice rows", IvI2->nrow, IvX->nrow);
+    hipStream_t st = nullptr;
+    Arena &A = arena();
+    A.reset();
+    const int T = 256, nI = IvX->nrow, nI2 = IvI2->ncol, nX = IvX->ncol;
+    uint32_t *pos = A.get<uint32_t>((size_t)nI + 1);
+    unsigned long long *tot = A.get<unsigned long long>(1);
+    IBH_HIP(hipMemsetAsync(tot, 0, sizeof(unsigned long long), st));
+    if (nI) hipLaunchKernelGGL(k_i2vx_count, dim3(ceil_div(nI, T)), dim3(T), 0, st, IvI2->rowptr.p, IvX->rowptr.p, nI, pos, tot);
+    IBH_HIP(hipGetLastError());
+    unsigned long long total = 0;
+    readback_sync(&total, tot, sizeof(total), st);
+    IBH_CHECK(total <= INT32_MAX, "make_I2vX: %llu product terms exceed INT32_MAX", total);
+    exclusive_scan_u32(pos, pos, (size_t)nI, pos + nI, st);
+    Triplets m = triplets_in_arena((size_t)total), w = triplets_in_arena((size_t)IvI2->nnz);
+    if (nI) hipLaunchKernelGGL(k_i2vx_terms, dim3(ceil_div(nI, T)), dim3(T), 0, st, IvI2->rowptr.p, IvI2->colind.p, IvI2->val.p,
+                               IvX->rowptr.p, IvX->colind.p, IvX->val.p, IvX->wM.p, nI, pos, m, w);
+    IBH_HIP(hipGetLastError());
+    int32_t *row = nullptr;
+    build_csr_from_contributions(out, m, nI2, nX, &row, st);
+    ibh_weighted wsum;
+    build_csr_from_contributions(&wsum, w, nI2, 1, &row, st);
+    out->wM.alloc((size_t)nI2);
+    if (nI2) hipLaunchKernelGGL(k_i2vx_wM, dim3(ceil_div(nI2, T)), dim3(T), 0, st, wsum.rowptr.p, wsum.val.p, nI2, out->wM.p);
+    out->Mw.alloc((size_t)nX);
+    if (nX) IBH_HIP(hipMemcpyAsync(out->Mw.p, IvX->Mw.p, sizeof(double) * (size_t)nX, hipMemcpyDeviceToDevice, st));
+    IBH_HIP(hipGetLastError());
+    IBH_HIP(hipStreamSynchronize(st));
+    out->conservative = IvX->conservative;
+    out->scaled = 0;
+}
+
 }  // namespace ibh

@@ -327,6 +327,27 @@ int ibh_regridder_wA(const ibh_regridder *g, int native, double fill, double *ou
     });
 }
 
+int ibh_regridder_exgrid(const ibh_regridder *g, int64_t *nX, int32_t *indices, double *overlaps) {
+    return guarded([&] {
+        IBH_CHECK(g && nX, "null argument");
+        *nX = g->nX;
+        if (!indices && !overlaps) return;
+        IBH_CHECK(indices && overlaps, "indices and overlaps must both be given (or both NULL)");
+        if (g->nX == 0) return;
+        g->ex_indices.download(indices, 2 * (size_t)g->nX);
+        g->ex_area.download(overlaps, (size_t)g->nX);
+    });
+}
+int ibh_regridder_agridA(const ibh_regridder *g, int32_t *nA_dense, int64_t *to_sparse, double *native_area, double *proj_area) {
+    return guarded([&] {
+        IBH_CHECK(g && nA_dense, "null argument");
+        *nA_dense = g->nA_dense;
+        if (to_sparse) std::copy(g->A_to_sparse.begin(), g->A_to_sparse.end(), to_sparse);
+        if (native_area) std::copy(g->A_native.begin(), g->A_native.end(), native_area);
+        if (proj_area) std::copy(g->A_proj.begin(), g->A_proj.end(), proj_area);
+    });
+}
+
 // ---- RegridMatrices ------------------------------------------------------------------------
 int ibh_regrid_matrices_create(const ibh_regridder *rg, const double *elevmaskI, int64_t n, int scale, int correctA,
                                const double sigma[3], ibh_regrid_matrices **out) {

@@ -295,6 +295,7 @@ using namespace ibh;
 
 struct ibh_hntr {
     int imA, jmA, imB, jmB;
+    double offiA, dlatA, offiB, dlatB;      // the grid specs, for make_grid_spec (ibh_regridder_create_hntr)
     double datmis;
     int device = 0, ncu = 256;
     int wmax = 1;       // widest column window
@@ -938,6 +939,368 @@ static void hntr_triplets(const ibh_hntr *h, int kind, double eq_rad, const uint
     IBH_HIP(hipStreamSynchronize(st));
 }
 
+// ---- global_ec: the exchange grid of Hntr's overlap under an ice mask (modele/global_ec.cpp:296-322 ExchAccum, :384-432
+// new_gcmA_standard) ------------------------------------------------------------------------------------------------------
+// Grid A of the handle is the ice grid, B the GCM grid.  The overlap's stream-order entries (iB, iA, v) whose ice cell has a
+// non-NaN mask are appended as exchange cells (iB, iA, v); WEIGHT (k_hm_weight, no includeB) sums every term of the B cell,
+// the mask only filters.  On the device:
+//   count     TPR lanes per B cell (grid-stride): the cell's kept terms (mask reads only), cnt[r]; a 64-bit grand total
+//   scan      prims' exclusive scan of cnt (only once the total is known to fit in int32)
+//   fill      TPR lanes per B cell: the terms in stream order, TPR at a time; a ballot over the team ranks the kept ones
+//   dims      dimA = the cells with cnt > 0 (a flag scan); dimI = ice cells first-seen in stream order (as k_hm_first)
+constexpr int HX_T = 256;
+__global__ __launch_bounds__(HX_T) void k_hx_count(HmArgs a, const double *__restrict__ mask, int TPR, uint32_t *__restrict__ cnt,
+                                                   unsigned long long *__restrict__ total) {
+    __shared__ unsigned long long part[HX_T / 64];
+    const long nB = (long)a.imB * a.jmB;
+    const int t = threadIdx.x % TPR;
+    const long teams = (long)gridDim.x * (HX_T / TPR);
+    unsigned long long acc = 0;
+    for (long r = (long)blockIdx.x * (HX_T / TPR) + threadIdx.x / TPR; r < nB; r += teams) {      // team-uniform trip counts
+        const int ib = (int)(r % a.imB), jb = (int)(r / a.imB);
+        const int imn = a.IMIN[ib], W = a.IMAX[ib] - imn + 1, jmn = a.JMIN[jb];
+        const uint32_t nt = (uint32_t)(a.JMAX[jb] - jmn + 1) * (uint32_t)W;
+        uint32_t n = 0;
+        for (uint32_t e = t; e < nt; e += TPR) {
+            const int JA = jmn + (int)(e / (uint32_t)W), IAREV = imn + (int)(e % (uint32_t)W);
+            const int IA = IAREV > a.imA ? IAREV - a.imA : IAREV;
+            n += isnan(mask[(long)(JA - 1) * a.imA + (IA - 1)]) ? 0u : 1u;
+        }
+        for (int o = TPR / 2; o > 0; o >>= 1) n += __shfl_xor(n, o, TPR);
+        if (t == 0) {
+            if (cnt) cnt[r] = n;
+            acc += n;
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x / 64] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long s = 0;
+        for (int w = 0; w < HX_T / 64; ++w) s += part[w];
+        if (s) atomicAdd(total, s);
+    }
+}
+
+// the exchange cells of B cell r at pos[r]: (iB, iI) pairs and their overlaps, stream order
+__global__ __launch_bounds__(HX_T) void k_hx_fill(HmArgs a, const double *__restrict__ mask, int TPR, const uint32_t *__restrict__ pos,
+                                                  int2 *__restrict__ idx, double *__restrict__ area) {
+    long r; int t;
+    if (!hm_team(a, TPR, r, t)) return;          // whole teams
+    const uint32_t p0 = pos[r], p1 = pos[r + 1];
+    if (p0 == p1) return;                         // whole teams
+    const HmCell c = hm_cell(a, (int)(r % a.imB), (int)(r / a.imB), true);
+    const uint32_t nt = (uint32_t)(c.jmx - c.jmn + 1) * (uint32_t)c.W;
+    const int tb = (threadIdx.x & 63) & ~(TPR - 1);
+    const unsigned long long tmask = TPR == 64 ? ~0ull : ((1ull << TPR) - 1);
+    const unsigned long long below = (1ull << t) - 1;
+    uint32_t p = p0;
+    for (uint32_t base = 0; base < nt; base += TPR) {
+        const uint32_t e = base + t;
+        int JA = 0, IAREV = 0;
+        long iI = 0;
+        bool keep = false;
+        if (e < nt) {
+            JA = c.jmn + (int)(e / (uint32_t)c.W);
+            IAREV = c.imn + (int)(e % (uint32_t)c.W);
+            const int IA = IAREV > a.imA ? IAREV - a.imA : IAREV;
+            iI = (long)(JA - 1) * a.imA + (IA - 1);
+            keep = !isnan(mask[iI]);
+        }
+        const unsigned long long b = (__ballot(keep) >> tb) & tmask;
+        if (keep) {
+            const uint32_t q = p + (uint32_t)__popcll(b & below);
+            idx[q] = make_int2((int)r, (int)iI);
+            area[q] = hm_val(a, c, hm_F(c, IAREV) * hm_G(a, c, JA));
+        }
+        p += (uint32_t)__popcll(b);
+    }
+}
+
+__global__ void k_hx_cellflag(const uint32_t *__restrict__ pos, long nB, uint32_t *__restrict__ flag) {
+    const long r = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r < nB) flag[r] = pos[r + 1] != pos[r] ? 1u : 0u;
+}
+__global__ void k_hx_cells(const uint32_t *__restrict__ rank, long nB, int64_t *__restrict__ to_sparse) {
+    const long r = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r < nB && rank[r + 1] != rank[r]) to_sparse[rank[r]] = r;
+}
+__global__ void k_hx_first(const int2 *__restrict__ idx, long n, uint32_t *__restrict__ first) {
+    const long p = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p < n) atomicMin(&first[idx[p].y], (uint32_t)p);
+}
+__global__ void k_hx_newflag(const int2 *__restrict__ idx, long n, const uint32_t *__restrict__ first, uint32_t *__restrict__ flag) {
+    const long p = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p < n) flag[p] = first[idx[p].y] == (uint32_t)p ? 1u : 0u;
+}
+__global__ void k_hx_newkeys(const int2 *__restrict__ idx, long n, const uint32_t *__restrict__ rank, int64_t *__restrict__ out) {
+    const long p = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p < n && rank[p + 1] != rank[p]) out[rank[p]] = idx[p].y;
+}
+
+static const ibh_hntr *hx_check_desc(const ibh_hntr_regridder_desc *d) {
+    IBH_CHECK(d != nullptr, "null argument");
+    const ibh_hntr *h = d->hntr;
+    IBH_CHECK(h != nullptr, "global_ec: null Hntr handle");
+    int dev = -1;
+    IBH_HIP(hipGetDevice(&dev));
+    IBH_CHECK(dev == h->device, "Hntr handle belongs to device %d, current device is %d", h->device, dev);
+    const int64_t nI = (int64_t)h->imA * h->jmA, nA = (int64_t)h->imB * h->jmB;
+    IBH_CHECK(d->elevmaskI != nullptr, "global_ec: null elevmaskI");
+    IBH_CHECK(d->nmask == nI, "global_ec: elevmaskI has %lld elements, the ice grid (Hntr grid A) has nI=%lld", (long long)d->nmask,
+              (long long)nI);
+    IBH_CHECK(d->nhc >= 0, "global_ec: negative nhc");
+    IBH_CHECK(nA * (int64_t)(d->nhc > 0 ? d->nhc : 1) < (1ll << 31), "global_ec: nE = nA*nhc = %lld overflows int32 dense ids",
+              (long long)(nA * (int64_t)d->nhc));
+    IBH_CHECK(d->interp_style == 0 || d->interp_style == 1, "unknown interp_style %d", d->interp_style);
+    if (d->nhc > 0) {
+        IBH_CHECK(d->hcdefs != nullptr, "null hcdefs");
+        for (int k = 1; k < d->nhc; ++k) IBH_CHECK(d->hcdefs[k] > d->hcdefs[k - 1], "hcdefs must be ascending");
+        const bool hc_slowest = d->hc_stride_A == 1 && d->hc_stride_HC == nA;
+        const bool hc_fastest = d->hc_stride_HC == 1 && d->hc_stride_A == d->nhc;
+        IBH_CHECK(hc_slowest || hc_fastest, "indexingHC strides (%ld,%ld) are neither (1,nA) nor (nhc,1)", (long)d->hc_stride_A,
+                  (long)d->hc_stride_HC);
+    }
+    IBH_CHECK(std::isfinite(d->eq_rad), "global_ec: eq_rad=%g is not finite", d->eq_rad);
+    return h;
+}
+
+// the device copy of the mask (the caller's pointer when it is on the device), on st
+static const double *hx_mask(const ibh_hntr_regridder_desc *d, int64_t nI, hipStream_t st) {
+    if (d->mask_on_device) return d->elevmaskI;
+    double *m = arena().get<double>((size_t)nI);
+    IBH_HIP(hipMemcpyAsync(m, d->elevmaskI, sizeof(double) * (size_t)nI, hipMemcpyHostToDevice, st));
+    return m;
+}
+
+static HmArgs hx_args(const ibh_hntr *h, double eq_rad) {
+    HmArgs a{};
+    a.SINA = h->SINA.p; a.FMIN = h->FMIN.p; a.FMAX = h->FMAX.p; a.GMIN = h->GMIN.p; a.GMAX = h->GMAX.p; a.dxyp = h->dxypB.p;
+    a.IMIN = h->IMIN.p; a.IMAX = h->IMAX.p; a.JMIN = h->JMIN.p; a.JMAX = h->JMAX.p; a.jbr = h->jbr.p; a.ibr = h->ibr.p;
+    a.imA = h->imA; a.jmA = h->jmA; a.imB = h->imB; a.jmB = h->jmB;
+    a.overlap = 1;
+    a.R2 = eq_rad * eq_rad;
+    return a;
+}
+
+// the kept terms in 64 bits (cnt != nullptr: also per B cell)
+static int64_t hx_count(const ibh_hntr *h, const HmArgs &a, const double *mask, uint32_t *cnt, int TPR, hipStream_t st) {
+    const long nB = (long)h->imB * h->jmB;
+    unsigned long long *tot = arena().get<unsigned long long>(1);
+    IBH_HIP(hipMemsetAsync(tot, 0, sizeof(unsigned long long), st));
+    const long blocks = std::min<long>(ceil_div(nB, HX_T / TPR), 16l * h->ncu);
+    hipLaunchKernelGGL(k_hx_count, dim3((unsigned)std::max(blocks, 1l)), dim3(HX_T), 0, st, a, mask, TPR, cnt, tot);
+    IBH_HIP(hipGetLastError());
+    unsigned long long n = 0;
+    readback_sync(&n, tot, sizeof(n), st);
+    return (int64_t)n;
+}
+
+// lanes per B cell: from the mean window size (a power of two, 4..64: a team lives inside one wave)
+static int hx_tpr(const ibh_hntr *h) {
+    return std::min(hm_tpr(hm_count_host(h, nullptr, false), (int64_t)h->imB * h->jmB), 64);
+}
+
+static void hntr_exgrid_count(const ibh_hntr_regridder_desc *d, int64_t *nX) {
+    IBH_CHECK(nX != nullptr, "null argument");
+    const ibh_hntr *h = hx_check_desc(d);
+    hipStream_t st = static_cast<hipStream_t>(d->stream);
+    Arena &A = arena();
+    A.reset();
+    const double *mask = hx_mask(d, (int64_t)h->imA * h->jmA, st);
+    *nX = hx_count(h, hx_args(h, d->eq_rad), mask, nullptr, hx_tpr(h), st);
+}
+
+// make_grid_spec (GridSpec.cpp:80-122) with pole_caps = false: lonb [im+1], latb [2*(jm/2)+1], degrees
+static void hx_grid_spec(int im, int jm, double offi, double dlat, std::vector<double> &lonb, std::vector<double> &latb) {
+    const double deg_by_im = 360. / (double)im;
+    lonb.clear(); latb.clear();
+    for (int i = 0; i < im; ++i) lonb.push_back(-180. + (offi + (double)i) * deg_by_im);
+    lonb.push_back(lonb[0] + 360.);
+    latb.push_back(0);
+    const double dlat_d = dlat / 60.;
+    for (int j = 1; j < jm / 2; ++j) {
+        const double lat = j * dlat_d;
+        latb.push_back(lat);
+        latb.push_back(-lat);
+    }
+    double lat = jm / 2 * dlat_d;
+    if (std::abs(lat - 90.) < 1.e-10) lat = 90.;
+    latb.push_back(lat);
+    latb.push_back(-lat);
+    std::sort(latb.begin(), latb.end());
+}
+
+static void regridder_create_hntr(const ibh_hntr_regridder_desc *d, ibh_sparse_set *dimA_out, ibh_sparse_set *dimI_out,
+                                  ibh_regridder **out) {
+    IBH_CHECK(out != nullptr, "null argument");
+    const ibh_hntr *h = hx_check_desc(d);
+    // make_grid_spec(hspecA) has 2*(jm/2) rows: an odd jm would leave the last GCM row without boundaries.  (The reference
+    // also refuses an odd im there; its areas are well defined, so an odd im is accepted.)
+    IBH_CHECK(h->jmB % 2 == 0, "global_ec: the GCM grid (Hntr grid B) has jm=%d; make_grid_spec needs an even jm", h->jmB);
+    IBH_CHECK(!dimA_out || dimA_out->n == 0, "global_ec: dimA_out must be an empty set");
+    IBH_CHECK(!dimI_out || dimI_out->n == 0, "global_ec: dimI_out must be an empty set");
+    IBH_CHECK(!dimA_out || dimA_out != dimI_out, "global_ec: dimA_out and dimI_out must be distinct sets");
+    const int64_t nI = (int64_t)h->imA * h->jmA, nB = (int64_t)h->imB * h->jmB;
+    hipStream_t st = static_cast<hipStream_t>(d->stream);
+    Arena &A = arena();
+    A.reset();
+    const HmArgs a0 = hx_args(h, d->eq_rad);
+    const double *mask = hx_mask(d, nI, st);
+    const int tpr = hx_tpr(h);
+    // the kept cells in 64 bits before anything is allocated; when every term of the overlap fits in int32 the per-cell
+    // counts come from the same pass (the mask is read once for the counts)
+    uint32_t *pos = nullptr;
+    if (hm_count_host(h, nullptr, false) <= INT32_MAX) pos = A.get<uint32_t>((size_t)nB + 1);
+    const int64_t nX = hx_count(h, a0, mask, pos, tpr, st);
+    // the bound of ibh_regridder_create (capi.hip): nX < 2^31 - 1
+    IBH_CHECK(nX < INT32_MAX, "global_ec: %lld exchange cells exceed the regridder's limit (INT32_MAX - 1)", (long long)nX);
+
+    std::unique_ptr<ibh_regridder> g(new ibh_regridder);
+    g->device = h->device;
+    g->nX = nX; g->nI = nI; g->nA = nB; g->nhc = d->nhc;
+    g->interp_style = d->interp_style; g->hc_stride_A = d->hc_stride_A; g->hc_stride_HC = d->hc_stride_HC;
+    g->hcdefs_h.assign(d->hcdefs, d->hcdefs + d->nhc);
+    g->hcdefs.upload(d->hcdefs, (size_t)d->nhc, st);
+    // count again per cell, scan, weights, fill
+    if (!pos) {
+        pos = A.get<uint32_t>((size_t)nB + 1);
+        hx_count(h, a0, mask, pos, tpr, st);
+    }
+    exclusive_scan_u32(pos, pos, (size_t)nB, pos + nB, st);
+    HmArgs a = a0;
+    double *winv = A.get<double>((size_t)nB);
+    a.winv = winv;
+    hipLaunchKernelGGL(k_hm_weight, dim3(ceil_div(nB, 64)), dim3(64), 0, st, a, winv);
+    g->ex_indices.alloc(2 * (size_t)nX);
+    g->ex_area.alloc((size_t)nX);
+    int2 *idx = reinterpret_cast<int2 *>(g->ex_indices.p);
+    if (nX) hipLaunchKernelGGL(k_hx_fill, dim3(ceil_div(nB, HX_T / tpr)), dim3(HX_T), 0, st, a, mask, tpr, pos, idx, g->ex_area.p);
+    // dimA: the B cells with exchange cells, ascending
+    uint32_t *rank = A.get<uint32_t>((size_t)nB + 1);
+    hipLaunchKernelGGL(k_hx_cellflag, dim3(ceil_div(nB, HX_T)), dim3(HX_T), 0, st, pos, (long)nB, rank);
+    exclusive_scan_u32(rank, rank, (size_t)nB, rank + nB, st);
+    uint32_t nAd = 0;
+    readback_sync(&nAd, rank + nB, sizeof(nAd), st);
+    DevBuf<int64_t> dA((size_t)nAd);
+    if (nAd) hipLaunchKernelGGL(k_hx_cells, dim3(ceil_div(nB, HX_T)), dim3(HX_T), 0, st, rank, (long)nB, dA.p);
+    // dimI: first-seen
+    DevBuf<int64_t> dI;
+    uint32_t nId = 0;
+    if (dimI_out) {
+        uint32_t *first = A.get<uint32_t>((size_t)nI), *flag = A.get<uint32_t>((size_t)nX + 1);
+        IBH_HIP(hipMemsetAsync(first, 0xFF, sizeof(uint32_t) * (size_t)nI, st));
+        if (nX) {
+            hipLaunchKernelGGL(k_hx_first, dim3(ceil_div(nX, HX_T)), dim3(HX_T), 0, st, idx, (long)nX, first);
+            hipLaunchKernelGGL(k_hx_newflag, dim3(ceil_div(nX, HX_T)), dim3(HX_T), 0, st, idx, (long)nX, first, flag);
+        }
+        exclusive_scan_u32(flag, flag, (size_t)nX, flag + nX, st);
+        readback_sync(&nId, flag + nX, sizeof(nId), st);
+        dI.alloc((size_t)nId);
+        if (nX) hipLaunchKernelGGL(k_hx_newkeys, dim3(ceil_div(nX, HX_T)), dim3(HX_T), 0, st, idx, (long)nX, flag, dI.p);
+    }
+    IBH_HIP(hipGetLastError());
+    // agridA on the host: make_abbr_grid's areas (GridGen_LonLat.cpp:234-275) from make_grid_spec(hspecA, false)
+    g->nA_dense = (int32_t)nAd;
+    g->A_to_sparse.resize(nAd);
+    dA.download(g->A_to_sparse.data(), nAd, st);
+    std::vector<double> lonb, latb;
+    hx_grid_spec(h->imB, h->jmB, h->offiB, h->dlatB, lonb, latb);
+    const double D2R = M_PI / 180.0;
+    const double D2R_R2 = D2R * d->eq_rad * d->eq_rad;
+    std::vector<double> dxyp((size_t)h->jmB);
+    for (int j = 0; j < h->jmB; ++j) dxyp[j] = sin(latb[j + 1]) - sin(latb[j]);      // degrees into sin, as the reference
+    g->A_native.resize(nAd);
+    std::vector<double> ratio((size_t)nB, 0.0);
+    for (uint32_t id = 0; id < nAd; ++id) {
+        const int64_t s = g->A_to_sparse[id];
+        const int i = (int)(s % h->imB), j = (int)(s / h->imB);
+        g->A_native[id] = dxyp[j] * (lonb[i + 1] - lonb[i]) * D2R_R2;
+        const double r = g->A_native[id] / g->A_native[id];      // projected area == native (IceRegridder.cpp:106-108)
+        IBH_CHECK(std::isfinite(r) && r > 0, "global_ec: GCM cell %ld: native/proj area ratio %g is not positive", (long)s, r);
+        ratio[(size_t)s] = r;
+    }
+    g->A_proj = g->A_native;
+    g->A_ratio_s.upload(ratio.data(), ratio.size(), st);
+    IBH_HIP(hipStreamSynchronize(st));
+    // nothing below can fail: adopt the sets
+    if (dimA_out) {
+        dimA_out->sparse_extent = nB;
+        dimA_out->identity = false;
+        dimA_out->host = g->A_to_sparse; dimA_out->host_n = (int32_t)nAd;
+        dimA_out->dev = std::move(dA); dimA_out->dev_n = (int32_t)nAd;
+        dimA_out->n = (int32_t)nAd;
+        dimA_out->inv.clear(); dimA_out->inv_n = 0; dimA_out->tab_n = -1;
+    }
+    if (dimI_out) {
+        dimI_out->sparse_extent = nI;
+        dimI_out->identity = false;
+        dimI_out->host.clear(); dimI_out->host_n = 0;
+        dimI_out->dev = std::move(dI); dimI_out->dev_n = (int32_t)nId;
+        dimI_out->n = (int32_t)nId;
+        dimI_out->inv.clear(); dimI_out->inv_n = 0; dimI_out->tab_n = -1;
+    }
+    *out = g.release();
+}
+
+// make_I2vX (modele/global_ec.cpp:345-376): I2vI from the Hntr overlap (as I2vI's columns: no transpose), then the products
+// on the device (assemble.hip i2vx_compute).  dimI2 is numbered on a copy that replaces it only once everything succeeded.
+static void make_i2vx(const ibh_weighted *IvX, const ibh_hntr *h, double eq_rad, const uint8_t *includeI, int64_t nincl,
+                      ibh_sparse_set *dimI2, ibh_weighted **out) {
+    IBH_CHECK(out != nullptr && IvX != nullptr, "null argument");
+    hm_check(h, IBH_HNTR_OVERLAP);
+    IBH_CHECK(IvX->device == h->device, "make_I2vX: IvX and the Hntr handle live on different devices");
+    ibh_sparse_set *dimI = IvX->dims[0], *dimX = IvX->dims[1];
+    const int64_t nI = (int64_t)h->imB * h->jmB, nI2 = (int64_t)h->imA * h->jmA;
+    IBH_CHECK(dimI && dimX, "make_I2vX: IvX has no dims");
+    IBH_CHECK(dimI->sparse_extent == nI, "make_I2vX: IvX's ice dim has sparse extent %lld, the Hntr handle's grid B (hspecI) %lld cells",
+              (long long)dimI->sparse_extent, (long long)nI);
+    IBH_CHECK(dimI->n == IvX->nrow, "make_I2vX: IvX's ice dim holds %d entries, IvX has %d rows", dimI->n, IvX->nrow);
+    IBH_CHECK(includeI == nullptr || nincl == nI, "make_I2vX: includeI has %lld entries, the ice grid %lld cells", (long long)nincl,
+              (long long)nI);
+    IBH_CHECK(dimI2 == nullptr || (dimI2 != dimI && dimI2 != dimX), "make_I2vX: dimI2 must be a set of its own");
+    IBH_CHECK(dimI2 == nullptr || dimI2->sparse_extent == -1 || dimI2->sparse_extent == nI2,
+              "make_I2vX: dimI2 has sparse extent %lld, the Hntr handle's grid A (hspecI2) %lld cells",
+              (long long)(dimI2 ? dimI2->sparse_extent : 0), (long long)nI2);
+    std::unique_ptr<ibh_sparse_set> tmp(new ibh_sparse_set);
+    if (dimI2) {
+        tmp->sparse_extent = dimI2->sparse_extent;
+        tmp->identity = dimI2->identity;
+        tmp->n = dimI2->n;
+        if (!dimI2->identity && dimI2->n) { dimI2->ensure_host(); tmp->host = dimI2->host; tmp->host_n = dimI2->n; }
+    }
+    ibh_weighted *raw = nullptr;
+    hntr_matrix(h, IBH_HNTR_OVERLAP, eq_rad, includeI, dimI, IBH_TO_DENSE_IGNORE_MISSING, tmp.get(), IBH_ADD_DENSE, 0, &raw);
+    std::unique_ptr<ibh_weighted> IvI2(raw);
+    std::unique_ptr<ibh_weighted> w(new ibh_weighted);
+    w->device = h->device;
+    i2vx_compute(IvI2.get(), IvX, w.get());
+    std::unique_ptr<ibh_sparse_set> xcopy;
+    if (IvX->owns[1]) {
+        xcopy.reset(new ibh_sparse_set);
+        xcopy->sparse_extent = dimX->sparse_extent;
+        xcopy->identity = dimX->identity;
+        xcopy->n = dimX->n;
+        if (!dimX->identity && dimX->n) { dimX->ensure_host(); xcopy->host = dimX->host; xcopy->host_n = dimX->n; }
+    }
+    IvI2.reset();
+    // nothing below can fail
+    if (dimI2) {
+        dimI2->sparse_extent = tmp->sparse_extent;
+        dimI2->identity = tmp->identity;
+        dimI2->host = std::move(tmp->host); dimI2->host_n = tmp->host_n;
+        dimI2->dev = std::move(tmp->dev); dimI2->dev_n = tmp->dev_n;
+        dimI2->n = tmp->n;
+        dimI2->inv.clear(); dimI2->inv_n = 0; dimI2->tab_n = -1;
+        w->dims[0] = dimI2; w->owns[0] = false;
+    } else {
+        w->dims[0] = tmp.release(); w->owns[0] = true;
+    }
+    if (xcopy) { w->dims[1] = xcopy.release(); w->owns[1] = true; }
+    else { w->dims[1] = dimX; w->owns[1] = false; }
+    *out = w.release();
+}
+
 }  // namespace ibh
 
 extern "C" {
@@ -966,6 +1329,7 @@ int ibh_hntr_create(ibh_hntr **out, int32_t imA, int32_t jmA, double offiA, doub
         require_device();
         std::unique_ptr<ibh_hntr> h(new ibh_hntr);
         h->imA = imA; h->jmA = jmA; h->imB = imB; h->jmB = jmB; h->datmis = datmis;
+        h->offiA = offiA; h->dlatA = dlatA; h->offiB = offiB; h->dlatB = dlatB;
         IBH_HIP(hipGetDevice(&h->device));
         IBH_HIP(hipDeviceGetAttribute(&h->ncu, hipDeviceAttributeMultiprocessorCount, h->device));
         const int shift = hntr_column_shift(p, imA);
@@ -1033,6 +1397,30 @@ int ibh_hntr_matrix_d(const ibh_hntr *h, int kind, double eq_rad, const uint8_t 
     return guarded([&] {
         if (out) *out = nullptr;
         hntr_matrix(h, kind, eq_rad, includeB, dimB, tB, dimA, tA, transpose, out);
+    });
+}
+
+}  // extern "C"
+
+extern "C" {
+
+int ibh_weighted_make_I2vX(const ibh_weighted *IvX, const ibh_hntr *hIvI2, double eq_rad, const uint8_t *includeI, int64_t nincl,
+                           ibh_sparse_set *dimI2, ibh_weighted **out) {
+    return guarded([&] {
+        if (out) *out = nullptr;
+        make_i2vx(IvX, hIvI2, eq_rad, includeI, nincl, dimI2, out);
+    });
+}
+
+int ibh_hntr_exgrid_count(const ibh_hntr_regridder_desc *desc, int64_t *nX) {
+    return guarded([&] { hntr_exgrid_count(desc, nX); });
+}
+
+int ibh_regridder_create_hntr(const ibh_hntr_regridder_desc *desc, ibh_sparse_set *dimA_out, ibh_sparse_set *dimI_out,
+                              ibh_regridder **out) {
+    return guarded([&] {
+        if (out) *out = nullptr;
+        regridder_create_hntr(desc, dimA_out, dimI_out, out);
     });
 }
 

@@ -17,6 +17,7 @@
 #pragma once
 #include <array>
 #include <cmath>
+#include <cstdio>
 #include <cstdint>
 #include <map>
 #include <memory>
@@ -569,6 +570,25 @@ public:
         sheets_.push_back(std::move(sheet));
         return ix;
     }
+    /** add_sheet for a regridder already built on the device (ibh_regridder_create_hntr; modele/global_ec.cpp:418-427): takes
+        ownership of `built`; the host copies ncio() writes are read back from it. */
+    size_t add_sheet(std::string const &name, ibh_regridder *built, int interp_style) {
+        std::unique_ptr<IceRegridder> sheet(new IceRegridder);
+        sheet->h_ = built;
+        int64_t nI = 0, nX = 0;
+        check(ibh_regridder_sizes(built, nullptr, nullptr, &nI, &nX, nullptr));
+        sheet->_name = name; sheet->_nI = (long)nI; sheet->_nX = (long)nX; sheet->interp_style = interp_style;
+        sheet->aexgrid_.indices.resize(2 * (size_t)nX); sheet->aexgrid_.overlaps.resize((size_t)nX);
+        check(ibh_regridder_exgrid(built, &nX, sheet->aexgrid_.indices.data(), sheet->aexgrid_.overlaps.data()));
+        int32_t nAd = 0;
+        check(ibh_regridder_agridA(built, &nAd, nullptr, nullptr, nullptr));
+        sheet->gridA_proj_area_.resize((size_t)nAd);
+        check(ibh_regridder_agridA(built, &nAd, nullptr, nullptr, sheet->gridA_proj_area_.data()));
+        size_t ix = sheets_.size();
+        sheets_index_[name] = ix;
+        sheets_.push_back(std::move(sheet));
+        return ix;
+    }
     /** GCMRegridder_Standard::ncio(ncio, vname) (GCMRegridder.cpp:104-150, AbbrGrid.cpp:23-29,167-194, IceRegridder.cpp:75-90): the
         IceBin input file -- `<v>.info` {correctA, sheets}, `<v>.agridA.*`, `<v>.indexingHC`, `<v>.hcdefs(<v>.nhc)`, and per sheet
         `<v>.<sheet>.info` {name, interp_style}, `.gridA_proj_area`, `.agridI.*`, `.aexgrid.indices / .overlaps`.  Reading builds
@@ -860,6 +880,73 @@ private:
         for (size_t k = 0; k < (size_t)n; ++k) accum.add({iB[k], iA[k]}, val[k]);
     }
 };
+
+/** hcdefs of global_ec (modele/global_ec.cpp:403-407): elev = lo, lo+skip, ... while elev <= hi, accumulated by addition. */
+inline std::vector<double> make_hcdefs(double ec_lo, double ec_hi, double ec_skip) {
+    std::vector<double> hcdefs;
+    for (double elev = ec_lo; elev <= ec_hi; elev += ec_skip) hcdefs.push_back(elev);
+    return hcdefs;
+}
+
+/** new_gcmA_standard (modele/global_ec.cpp:384-432): Hntr(17.17, hspecA, hspecI).overlap(ExchAccum(...), eq_rad) under the
+    ice mask, built on the device (ibh_regridder_create_hntr) into a GCMRegridder_Standard with one sheet "globalI";
+    indexingHC {1, nA} (HC slowest).  dimA / dimI, if given (empty), receive _dimA and _dimI. */
+inline std::unique_ptr<GCMRegridder_Standard> new_gcmA_standard(HntrSpec const &hspecA, HntrSpec const &hspecI,
+                                                                ArrayView<const double> const &elevmaskI, std::vector<double> hcdefs,
+                                                                bool correctA, double eq_rad, int interp_style = InterpStyle::Z_INTERP,
+                                                                SparseSetT *dimA = nullptr, SparseSetT *dimI = nullptr) {
+    Hntr hntr(17.17, hspecA, hspecI);
+    ibh_hntr_regridder_desc d{};
+    d.hntr = hntr.handle(); d.eq_rad = eq_rad;
+    d.elevmaskI = elevmaskI.data; d.nmask = elevmaskI.size();
+    d.nhc = (int32_t)hcdefs.size(); d.hcdefs = hcdefs.data();
+    d.hc_stride_A = 1; d.hc_stride_HC = hspecA.size();
+    d.interp_style = interp_style;
+    ibh_regridder *rg = nullptr;
+    check(ibh_regridder_create_hntr(&d, dimA ? dimA->handle() : nullptr, dimI ? dimI->handle() : nullptr, &rg));
+    std::unique_ptr<ibh_regridder, int (*)(ibh_regridder *)> owned(rg, ibh_regridder_destroy);     // until the sheet owns it
+    AbbrGrid a;
+    int32_t nAd = 0;
+    check(ibh_regridder_agridA(rg, &nAd, nullptr, nullptr, nullptr));
+    std::vector<int64_t> a2s((size_t)nAd);
+    a.native_area.resize((size_t)nAd);
+    check(ibh_regridder_agridA(rg, &nAd, a2s.data(), a.native_area.data(), nullptr));
+    a.sparse_extent = hspecA.size();
+    a.dim_to_sparse.assign(a2s.begin(), a2s.end());
+    a.name = "A";
+    std::unique_ptr<GCMRegridder_Standard> gcmA(new GCMRegridder_Standard);
+    gcmA->init(std::move(a), std::move(hcdefs), {{1, (long)hspecA.size()}}, correctA);
+    gcmA->add_sheet("globalI", owned.release(), interp_style);
+    return gcmA;
+}
+
+/** make_I2vX (modele/global_ec.cpp:345-376): IvX (IvE or IvA) onto the plottable grid hspecI2, through
+    Hntr(17.17, hspecI, hspecI2).overlap(eq_rad, ElevMaskClip(elevmaskI)) (ibh_weighted_make_I2vX).  dims {dimI2, dimX}; dimI2
+    must outlive the result. */
+inline std::unique_ptr<linear::Weighted_Eigen> make_I2vX(linear::Weighted_Eigen const &IvX, HntrSpec const &hspecI,
+                                                         HntrSpec const &hspecI2, ArrayView<const double> const &elevmaskI,
+                                                         SparseSetT &dimI2, double eq_rad) {
+    Hntr hntr_IvI2(17.17, hspecI, hspecI2);
+    std::vector<uint8_t> incl((size_t)elevmaskI.size());
+    for (size_t i = 0; i < incl.size(); ++i) incl[i] = std::isnan(elevmaskI.data[i]) ? 0 : 1;
+    ibh_weighted *w = nullptr;
+    check(ibh_weighted_make_I2vX(IvX.handle(), hntr_IvI2.handle(), eq_rad, incl.data(), (int64_t)incl.size(), dimI2.handle(), &w));
+    return std::unique_ptr<linear::Weighted_Eigen>(new linear::Weighted_Eigen(w));
+}
+
+/** check_negative (modele/global_ec.cpp:440-463): prints every negative weight and matrix entry, then throws if there was one. */
+inline void check_negative(linear::Weighted_Eigen const &mat, std::string const &name) {
+    bool neg = false;
+    std::array<std::vector<double> const *, 2> const weights{{&mat.wM(), &mat.Mw()}};
+    for (int j = 0; j < 2; ++j) {
+        auto const &wt = *weights[(size_t)j];
+        for (size_t i = 0; i < wt.size(); ++i)
+            if (wt[i] < 0) { printf("wt[%d](%d) = %g\n", j, (int)i, wt[i]); neg = true; }
+    }
+    for (auto const &t : mat.M.triplets())
+        if (t.value < 0) { printf("%s(%d,%d)=%g\n", name.c_str(), t.row, t.col, t.value); neg = true; }
+    if (neg) throw Exception(IBH_EINVAL, "Negative values found in matrix or weights for " + name);
+}
 }   // namespace modele
 
 // ---- pylib/icebin_cython.hpp:70-87 -----------------------------------------------------------

@@ -197,6 +197,44 @@ int ibh_regridder_sizes(const ibh_regridder *rg, int64_t *nA, int64_t *nE, int64
  * out[nA] = fill, then out[A_to_sparse[id]] = native or projected area. */
 int ibh_regridder_wA(const ibh_regridder *rg, int native, double fill, double *out /* [nA] */);
 
+/* global_ec: a regridder built in place from Hntr's overlap under an ice mask (modele/global_ec.cpp:296-322 ExchAccum,
+ * :384-432 new_gcmA_standard; gridgen/GridGen_LonLat.cpp:234-275 make_abbr_grid; GridSpec.cpp:80-122 make_grid_spec;
+ * IceRegridder.cpp:93-119).  The Hntr handle has A = the ice grid and B = the GCM grid.  Every stream-order entry
+ * (iB, iA, v) of its IBH_HNTR_OVERLAP form (WEIGHT summed over every term of the B cell) whose ice cell has a non-NaN
+ * elevmaskI becomes the exchange cell (iA_gcm = iB, iI = iA, area = v), appended in stream order: sorted by GCM cell, and a
+ * window wider than imA gives two cells for one ice column (ExchangeGrid::add appends).  agridA holds the GCM cells with at
+ * least one exchange cell, ascending (ADD_DENSE in stream order); its native area restates make_abbr_grid from
+ * make_grid_spec(hspecA, pole_caps = false) with the reference's degree quirk:
+ *   native[id] = ((sin(latb[j+1]) - sin(latb[j])) * (lonb[i+1] - lonb[i])) * ((D2R * eq_rad) * eq_rad),
+ * latb and lonb in DEGREES passed to sin, D2R = M_PI/180.  Projected area = native (no projection, IceRegridder.cpp:106-108),
+ * so the correctA ratio is exactly 1, also where the quirk area is negative.  The GCM grid needs an even jm (the grid
+ * spec of an odd jm has jm-1 rows); an odd im, which make_grid_spec refuses, is accepted. */
+typedef struct ibh_hntr_regridder_desc {
+    const ibh_hntr *hntr;          /* A = ice (hspecI), B = GCM (hspecA)                          */
+    double          eq_rad;
+    const double   *elevmaskI;     /* [nmask] = [imA*jmA]; NaN = no ice                           */
+    int64_t         nmask;
+    int32_t         mask_on_device;/* elevmaskI is a device pointer (read on `stream`)            */
+    void           *stream;
+    int32_t         nhc;
+    const double   *hcdefs;        /* [nhc] ascending                                             */
+    int64_t         hc_stride_A, hc_stride_HC;     /* as in ibh_regridder_desc; global_ec: 1, nA   */
+    int32_t         interp_style;  /* 0 Z_INTERP, 1 ELEV_CLASS_INTERP                             */
+} ibh_hntr_regridder_desc;
+/* The number of exchange cells the mask keeps, in 64 bits, counted on the device; allocates nothing but a word. */
+int ibh_hntr_exgrid_count(const ibh_hntr_regridder_desc *desc, int64_t *nX);
+/* Count, scan and fill on the device; the regridder is what ibh_regridder_create builds from the same arrays (no
+ * centroids).  INT32_MAX exchange cells or more (ibh_regridder_create's limit), nE = nA*nhc >= 2^31 or a mask of the wrong length is IBH_EINVAL before
+ * anything is allocated.  dimA_out / dimI_out (may be NULL) must be empty sets; they receive the GCM cells of agridA
+ * (ascending) and the ice cells in first-seen stream order (_dimA, _dimI of new_gcmA_standard).  On error *out is NULL and
+ * both sets are as they were. */
+int ibh_regridder_create_hntr(const ibh_hntr_regridder_desc *desc, ibh_sparse_set *dimA_out, ibh_sparse_set *dimI_out,
+                              ibh_regridder **out);
+/* Copy-outs of a regridder's state: the exchange grid (indices [2*nX] interleaved (iA, iI), overlaps [nX]; with both
+ * NULL only *nX is set) and agridA ([nA_dense] each; *nA_dense is always set, and each non-NULL array is filled). */
+int ibh_regridder_exgrid(const ibh_regridder *rg, int64_t *nX, int32_t *indices, double *overlaps);
+int ibh_regridder_agridA(const ibh_regridder *rg, int32_t *nA_dense, int64_t *to_sparse, double *native_area, double *proj_area);
+
 /* ------------------------------------------------------------------------- */
 /* Weighted: ibmisc::linear::Weighted_Eigen {dims, M, wM, Mw, conservative,
  * scaled} (RegridMatrices_Dynamic.cpp:63-65,100,115,123,421).  M lives in HBM
@@ -265,6 +303,21 @@ int ibh_weighted_destroy(ibh_weighted *w);
  * by (iE1, iE0), duplicates summed; wM = Mw = 1): the reference returns the same tuples as a TupleList. */
 int ibh_e1ve0_compute(int32_t nsheets, const ibh_weighted *const *XuE1s, const ibh_weighted *const *XuE0s,
                       int64_t nE, ibh_weighted **out);
+
+/* make_I2vX (modele/global_ec.cpp:345-376): IvX (IvE or IvA, dims {dimI, dimX}) mapped onto a coarser lat-lon grid I2.
+ * hIvI2 is Hntr(hspecI as B, hspecI2 as A); includeI the host byte mask [nI] (!isnan(elevmaskI); NULL: every cell).
+ *   I2vI = MakeDenseEigenT(overlap(eq_rad, includeI), {TO_DENSE_IGNORE_MISSING, ADD_DENSE}, {dimI, dimI2}, 'T')
+ *   M    = (I2vI * diag(1/IvX.wM)) * IvX.M        left factor rounded once per element; every output entry sums its terms
+ *                                                 over the dense I index ascending, the first assigned (Eigen's
+ *                                                 conservative sparse product)
+ *   wM   = (I2vI * diag(sum(I2vI, 1, '-'))) * IvX.wM   column sums of I2vI (rows ascending, from 0), inverted; the product
+ *                                                 sums over I ascending from 0
+ *   Mw   = IvX.Mw; conservative from IvX, scaled = 0; dims {dimI2, IvX's dims[1]}.
+ * dimI2 (IN/OUT, must outlive the result; NULL: a fresh set owned by the result) is numbered first-seen; IvX's dims[1] is
+ * shared when IvX does not own it, else copied.  A grid or mask that does not match IvX's ice dim is IBH_EINVAL; on any
+ * error *out is NULL and dimI2 is as it was. */
+int ibh_weighted_make_I2vX(const ibh_weighted *IvX, const ibh_hntr *hIvI2, double eq_rad, const uint8_t *includeI, int64_t nincl,
+                           ibh_sparse_set *dimI2, ibh_weighted **out);
 
 /* Public members of Weighted_Eigen, read back to host. */
 int ibh_weighted_shape(const ibh_weighted *w, int32_t *nrow_d, int32_t *ncol_d, int64_t *nnz);
