@@ -248,3 +248,56 @@ def test_selftest_order_rejects_bad_arguments(lib):
         assert rc == _capi.IBH_EINVAL, (keys, lo, hi, rc)
     k = np.asarray([3, 1], np.uint64)
     assert lib.ibh_selftest_order(k.ctypes.data, 2, 20, 12, 2, perm.ctypes.data, info.ctypes.data, C.byref(path)) == _capi.IBH_EINVAL
+
+
+def assembly_kernel_name(mangled):
+    """"_ZN3ibh9k_sa_emitILb1ELb0EjLi4EEEv..." -> "k_sa_emit<true, false, unsigned int, 4>": prims_kernel_name's spelling, with bool
+    template arguments as well."""
+    m = re.match(r"_ZN3ibh(\d+)", mangled)
+    if not m:
+        return None
+    n = int(m.group(1))
+    name, rest = mangled[m.end():m.end() + n], mangled[m.end() + n:]
+    if rest.startswith("E"):
+        return name
+    m = re.match(r"I((?:Li\d+E|Lb[01]E|[a-z])+)EE", rest)
+    if not m:
+        return None
+    args = []
+    for a in re.findall(r"Li\d+E|Lb[01]E|[a-z]", m.group(1)):
+        if a.startswith("Lb"):
+            args.append("true" if a[2] == "1" else "false")
+        elif a.startswith("L"):
+            args.append(a[2:-1])
+        else:
+            args.append(PRIMS_TYPE_ARGS.get(a, a))
+    return name + "<" + ", ".join(args) + ">"
+
+
+def test_every_sorted_grid_assembly_kernel_has_a_case(lib, tmp_path):
+    # tests/assembly_limit_cases.py names, for every kernel of the sorted-grid builds in assemble.o (the static plan k_plan_*, the
+    # per-range build k_fa_*, the streamed build k_sa_*), a test that launches it: a kernel built without a case, or a case for a
+    # kernel no longer built, fails here; so does a test named there that does not exist
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    try:
+        import assembly_limit_cases as alc
+    finally:
+        sys.path.pop(0)
+    mangled = [m for m in re.findall(r"^    \.name:\s+(\S+)", code_object_notes(tmp_path, "assemble"), re.M)
+               if re.match(r"_ZN3ibh\d+k_(plan|fa|sa)_", m)]
+    built = {assembly_kernel_name(m) for m in mangled}
+    assert None not in built and len(built) == len(mangled) and len(built) > 80, (sorted(mangled), sorted(map(str, built)))
+    named = set(alc.KERNELS) | set(alc.UNREACHABLE)
+    assert not set(alc.KERNELS) & set(alc.UNREACHABLE)
+    assert built == named, ("built without a case", sorted(built - named), "case without a kernel", sorted(named - built))
+    modules = {}
+    for kernel, test in alc.KERNELS.items():
+        module, func = test.split("::")
+        if module not in modules:
+            modules[module] = open(os.path.join(ROOT, "tests", module)).read()
+        base = func.split("[")[0]
+        assert re.search(r"^def %s\(" % base, modules[module], re.M), (kernel, test)
+        if "[" in func:
+            case = func[func.index("[") + 1:-1]
+            assert module == "test_gpu_assembly_limits.py" and case in {c["name"] for c in alc.CASES}, (kernel, test)

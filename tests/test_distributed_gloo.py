@@ -456,6 +456,10 @@ def _worker_asm_sharded(rank, world, port, q, configs=("g5", "g20"), stage_mb=64
                 sys.path.insert(0, os.path.join(ROOT, "tests"))
                 import test_gpu_parity
                 g, em = test_gpu_parity._random_grid(int(config[5:]), force_sorted=True)
+            elif config.startswith("limits:"):          # a grid of tests/assembly_limit_cases.py (32-bit positions)
+                sys.path.insert(0, os.path.join(ROOT, "tests"))
+                import assembly_limit_cases as alc
+                g, em = alc.build_grid(next(c for c in alc.CASES if c["name"] == config[7:])["grid"])
             else:
                 g = syn.make_grids(config)
                 em = syn.dome_elevmask(g)
