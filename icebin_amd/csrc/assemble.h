@@ -21,8 +21,6 @@ void assemble_batch(const ibh_regrid_matrices *rm, int n, const char *const *spe
 // Eigen setFromTriplets (to_eigen_M, eigen_types.cpp:9-34) on device: fills w's CSR from host COO.
 void weighted_from_coo_device(ibh_weighted *w, int nrow, int ncol, int64_t n, const int32_t *row, const int32_t *col,
                               const double *val);
-// sparse -> dense table (-1: missing) of a pre-populated set on the device, cached in the set (assemble.hip)
-const int32_t *set_dense_table(ibh_sparse_set *set, int64_t extent, hipStream_t st);
 // setFromTriplets from DEVICE triplets (dense ids, input order) plus wM / Mw = sum(M, dim, '+'), enqueued on st (assemble.hip)
 void weighted_from_device_triplets(ibh_weighted *w, int nrow, int ncol, int64_t n, const int32_t *drow, const int32_t *dcol,
                                    const double *dval, hipStream_t st);

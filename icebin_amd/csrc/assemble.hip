@@ -19,6 +19,7 @@
 #include "assemble.h"
 #include "prims.h"
 #include "sweep_kernel.inl"
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
@@ -218,6 +219,108 @@ __global__ void k_scatter_existing(int32_t *tab, const int64_t *to_sparse, int n
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) tab[to_sparse[i]] = i;
 }
+}  // namespace ibh
+
+// ibh_sparse_set (common.h)
+ibh_sparse_set::ibh_sparse_set(const ibh_sparse_set &o) : sparse_extent_(o.sparse_extent_), n_(o.n_), identity_(o.identity_) {
+    if (identity_ || !n_) return;
+    const int64_t *t = o.to_sparse_host();
+    host_.assign(t, t + n_);
+    host_n_ = n_;
+}
+void ibh_sparse_set::assign_host(int64_t sparse_extent, const int64_t *keys, int32_t n) {
+    std::vector<int64_t> sorted(keys, keys + n);
+    std::sort(sorted.begin(), sorted.end());
+    for (int32_t i = 0; i < n; ++i) {
+        IBH_CHECK(sorted[(size_t)i] >= 0 && (sparse_extent < 0 || sorted[(size_t)i] < sparse_extent),
+                  "sparse index %ld outside extent %ld", (long)sorted[(size_t)i], (long)sparse_extent);
+        IBH_CHECK(i == 0 || sorted[(size_t)i] != sorted[(size_t)i - 1], "duplicate sparse index %ld", (long)sorted[(size_t)i]);
+    }
+    *this = ibh_sparse_set(sparse_extent);
+    host_.assign(keys, keys + n);
+    n_ = host_n_ = n;
+}
+int32_t ibh_sparse_set::add_dense_host(int64_t key) {
+    IBH_CHECK(key >= 0 && (sparse_extent_ < 0 || key < sparse_extent_), "sparse index %ld outside extent %ld", (long)key, (long)sparse_extent_);
+    if (identity_ && key < n_) return (int32_t)key;
+    ensure_inverse();                       // materialises an identity prefix on the host
+    auto it = inv_.find(key);
+    if (it != inv_.end()) return it->second;
+    IBH_CHECK(n_ < 0x7fffffff, "dense extent overflows int32");
+    identity_ = false;
+    host_.push_back(key);
+    inv_[key] = n_;
+    host_n_ = inv_n_ = ++n_;                // the device copy (entries [0, dev_n_)) is completed by the next build
+    return n_ - 1;
+}
+int32_t ibh_sparse_set::to_dense(int64_t key) const {
+    if (identity_) return key >= 0 && key < n_ ? (int32_t)key : -1;
+    ensure_inverse();
+    auto it = inv_.find(key);
+    return it == inv_.end() ? -1 : it->second;
+}
+void ibh_sparse_set::ensure_host() const {
+    if (host_n_ >= n_) return;
+    host_.resize((size_t)n_);
+    if (identity_) {
+        for (int32_t i = host_n_; i < n_; ++i) host_[(size_t)i] = i;
+    } else {
+        if (dev_n_ < n_) ibh::fail(IBH_EINVAL, "internal: sparse set has no valid copy of entries [%d,%d)", host_n_, n_);
+        IBH_HIP(hipMemcpy(host_.data() + host_n_, dev_.p + host_n_, sizeof(int64_t) * (size_t)(n_ - host_n_), hipMemcpyDeviceToHost));
+    }
+    host_n_ = n_;
+}
+void ibh_sparse_set::check_entries_within(int64_t extent, const char *what) const {
+    IBH_CHECK(n_ <= extent, "%s holds %d entries, more than its extent of %lld", what, n_, (long long)extent);
+    if (identity_ || host_n_ < n_) return;          // (entries on the device only were checked when they were numbered)
+    for (int32_t i = 0; i < n_; ++i)
+        IBH_CHECK(host_[(size_t)i] >= 0 && host_[(size_t)i] < extent, "%s entry %lld outside [0, %lld)", what,
+                  (long long)host_[(size_t)i], (long long)extent);
+}
+void ibh_sparse_set::copy_to_sparse(int64_t *dst, int n, hipStream_t st) const {
+    if (n == 0) return;
+    if (identity_) {
+        hipLaunchKernelGGL(ibh::k_iota_i64, dim3(ibh::ceil_div(n, 256)), dim3(256), 0, st, dst, (size_t)n);
+    } else if (dev_n_ >= n) {
+        IBH_HIP(hipMemcpyAsync(dst, dev_.p, sizeof(int64_t) * (size_t)n, hipMemcpyDeviceToDevice, st));
+    } else {
+        ensure_host();
+        IBH_HIP(hipMemcpyAsync(dst, host_.data(), sizeof(int64_t) * (size_t)n, hipMemcpyHostToDevice, st));
+    }
+}
+const int64_t *ibh_sparse_set::device_to_sparse(int n, hipStream_t st) const {
+    if (n > 0 && on_device(n)) return dev_.p;
+    int64_t *t = ibh::arena().get<int64_t>((size_t)n);
+    copy_to_sparse(t, n, st);
+    return t;
+}
+const int32_t *ibh_sparse_set::device_to_dense(int64_t extent, hipStream_t st) {
+    if (tab_n_ == n_ && tab_extent_ == extent && tab_.p) return tab_.p;
+    const int T = 256;
+    tab_.alloc((size_t)extent);
+    if (dev_n_ < n_) {                      // complete the device copy of the dense -> sparse table first
+        ibh::DevBuf<int64_t> grown((size_t)n_);
+        copy_to_sparse(grown.p, n_, st);
+        IBH_HIP(hipStreamSynchronize(st));
+        dev_ = std::move(grown);
+        dev_n_ = n_;
+    }
+    hipLaunchKernelGGL(ibh::k_fill_i32, dim3(ibh::ceil_div(extent, T)), dim3(T), 0, st, tab_.p, (size_t)extent, -1);
+    hipLaunchKernelGGL(ibh::k_scatter_existing, dim3(ibh::ceil_div(n_, T)), dim3(T), 0, st, tab_.p, dev_.p, n_);
+    tab_n_ = n_; tab_extent_ = extent;
+    return tab_.p;
+}
+void ibh_sparse_set::adopt_device(ibh::DevBuf<int64_t> &&table, int32_t n, int64_t extent) noexcept {
+    set_sparse_extent(extent);
+    if (n <= n_) return;
+    // the host copy and the inverse map hold a prefix of the table and stay valid; the device inverse table does not
+    dev_ = std::move(table);
+    dev_n_ = n_ = n;
+    identity_ = false;
+    tab_n_ = -1;
+}
+
+namespace ibh {
 
 // The generator passes handle BOTH sets of a matrix (rows and columns) per exchange-cell visit:
 //   pass 1 (k_first2)  first[key] = smallest emission position 2x+j naming the key (atomicMin)
@@ -336,18 +439,12 @@ struct Numbering {
 static Numbering number_set_prepare(const RgView &rg, ibh_sparse_set *set, int64_t sparse_extent, int list, int key,
                                     int64_t max_new, int pkshift, uint32_t *first_storage, hipStream_t st) {
     Arena &A = arena();
-    set->sparse_extent = sparse_extent;                       // set_sparse_extent, RegridMatrices_Dynamic.cpp:69-72
+    set->set_sparse_extent(sparse_extent);                   // set_sparse_extent, RegridMatrices_Dynamic.cpp:69-72
+    set->check_entries_within(sparse_extent, "dims");
     Numbering nb;
     nb.set = set;
     DeviceSet &ds = nb.ds;
     ds.n_old = set->dense_extent();
-    if (set->identity) {
-        IBH_CHECK(ds.n_old <= sparse_extent, "identity dims larger than sparse extent");
-    } else if (set->host_n == ds.n_old) {
-        for (int32_t i = 0; i < ds.n_old; ++i)
-            IBH_CHECK(set->host[(size_t)i] >= 0 && set->host[(size_t)i] < sparse_extent, "dims entry %ld outside sparse extent %ld",
-                      (long)set->host[(size_t)i], (long)sparse_extent);
-    }
     IBH_CHECK(sparse_extent < 0xffffffffll, "sparse extent %ld does not fit 32 bits", (long)sparse_extent);
     if (max_new > sparse_extent - ds.n_old) max_new = sparse_extent - ds.n_old;
     nb.max_new = max_new;
@@ -357,41 +454,29 @@ static Numbering number_set_prepare(const RgView &rg, ibh_sparse_set *set, int64
     SetArgs &a = nb.args;
     a.list = list; a.key = key; a.base = ds.n_old; a.to_sparse = ds.to_sparse; a.pkshift = pkshift;
     a.ident_n = -1; a.tab = nullptr;
-    if (ds.n_old) {
-        if (set->identity) {
-            a.ident_n = ds.n_old;
-            hipLaunchKernelGGL(k_iota_i64, dim3(ceil_div(ds.n_old, T)), dim3(T), 0, st, ds.to_sparse, (size_t)ds.n_old);
-        } else {
-            if (set->dev_n == ds.n_old)
-                IBH_HIP(hipMemcpyAsync(ds.to_sparse, set->dev.p, sizeof(int64_t) * (size_t)ds.n_old, hipMemcpyDeviceToDevice, st));
-            else {
-                set->ensure_host();
-                IBH_HIP(hipMemcpyAsync(ds.to_sparse, set->host.data(), sizeof(int64_t) * (size_t)ds.n_old, hipMemcpyHostToDevice, st));
-            }
-            int32_t *tab = A.get<int32_t>((size_t)sparse_extent);
-            hipLaunchKernelGGL(k_fill_i32, dim3(ceil_div(sparse_extent, T)), dim3(T), 0, st, tab, (size_t)sparse_extent, -1);
-            hipLaunchKernelGGL(k_scatter_existing, dim3(ceil_div(ds.n_old, T)), dim3(T), 0, st, tab, ds.to_sparse, ds.n_old);
-            a.tab = tab;
-        }
+    set->copy_to_sparse(ds.to_sparse, ds.n_old, st);
+    if (ds.n_old && set->identity()) {
+        a.ident_n = ds.n_old;
+    } else if (ds.n_old) {
+        int32_t *tab = A.get<int32_t>((size_t)sparse_extent);
+        hipLaunchKernelGGL(k_fill_i32, dim3(ceil_div(sparse_extent, T)), dim3(T), 0, st, tab, (size_t)sparse_extent, -1);
+        hipLaunchKernelGGL(k_scatter_existing, dim3(ceil_div(ds.n_old, T)), dim3(T), 0, st, tab, ds.to_sparse, ds.n_old);
+        a.tab = tab;
     }
     ds.n = ds.n_old;
-    a.enabled = !(set->identity && ds.n_old == sparse_extent);      // an identity set that covers everything gains nothing
+    a.enabled = !(set->identity() && ds.n_old == sparse_extent);    // an identity set that covers everything gains nothing
     a.first = first_storage;            // [sparse_extent], preset to 0xFFFFFFFF by the caller (one fill for both sets)
     return nb;
 }
 
 static void number_set_finish(Numbering &nb, uint32_t n_new, hipStream_t st) {
     DeviceSet &ds = nb.ds;
-    ibh_sparse_set *set = nb.set;
     if (!nb.args.enabled || n_new == 0) return;
     ds.n = ds.n_old + (int)n_new;
     // the set keeps its table on the device; the host copy is completed only when somebody asks
     DevBuf<int64_t> grown((size_t)ds.n);
     IBH_HIP(hipMemcpyAsync(grown.p, ds.to_sparse, sizeof(int64_t) * (size_t)ds.n, hipMemcpyDeviceToDevice, st));
-    if (set->identity) { set->host.clear(); set->host_n = 0; }     // an identity prefix was never materialised
-    set->dev = std::move(grown);
-    set->dev_n = set->n = ds.n;
-    set->identity = false;
+    nb.set->adopt_device(std::move(grown), ds.n, nb.set->sparse_extent());
 }
 
 // ---- contributions ---------------------------------------------------------------------------
@@ -609,6 +694,26 @@ __global__ void k_keys_to_i32(const uint64_t *__restrict__ keys, long n, int32_t
     const long u = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (u < n) out[u] = (int32_t)keys[u];
 }
+// cs[c] = spsparse sum(M, 1, '+') of column c of w's CSR: the entries ordered by column (a stable radix sort keeps the rows of a
+// column ascending), then summed per column.  Enqueued on st.
+static void col_sums_by_sort(const ibh_weighted *w, int ncol, double *cs, hipStream_t st) {
+    const long nnz = w->nnz;
+    if (!nnz) {
+        if (ncol) IBH_HIP(hipMemsetAsync(cs, 0, sizeof(double) * (size_t)ncol, st));
+        return;
+    }
+    Arena &A = arena();
+    const int T = 256;
+    uint64_t *ck = A.get<uint64_t>((size_t)nnz), *ck2 = A.get<uint64_t>((size_t)nnz);
+    uint32_t *ci = A.get<uint32_t>((size_t)nnz), *ci2 = A.get<uint32_t>((size_t)nnz);
+    hipLaunchKernelGGL(k_col_keys, dim3(ceil_div(nnz, T)), dim3(T), 0, st, w->colind.p, nnz, ck, ci);
+    KeyField f{0, bits_for((uint64_t)ncol)};
+    if (f.nbits > 0 && radix_sort_pairs(ck, ck2, ci, ci2, (size_t)nnz, &f, 1, st)) { std::swap(ck, ck2); std::swap(ci, ci2); }
+    int32_t *scol = A.get<int32_t>((size_t)nnz), *colptr = A.get<int32_t>((size_t)ncol + 1);
+    hipLaunchKernelGGL(k_keys_to_i32, dim3(ceil_div(nnz, T)), dim3(T), 0, st, ck, nnz, scol);
+    rowptr_from_rows(scol, nnz, ncol, colptr, st);
+    seg_sums<true>(colptr, ci, w->val.p, ncol, nnz, cs, st);
+}
 
 // ---- column sums for matrices with short columns (AvI, EvI, AvX, EvX, AvE: <= a few rows per column) ----
 // spsparse sum(M, 1, '+') visits a column in ascending row order.  Instead of reordering all nnz
@@ -757,6 +862,15 @@ __global__ void k_scale(const int32_t *__restrict__ row, const int32_t *__restri
 
 // ---- shared: sorted (row,col,idx) contributions -> Weighted CSR ---------------------------------
 struct Triplets { uint64_t *keys, *keys_alt; uint32_t *idx, *idx_alt; double *term; size_t n; };
+static Triplets triplets_in_arena(size_t n) {
+    Arena &A = arena();
+    Triplets t;
+    t.n = n;
+    t.keys = A.get<uint64_t>(n); t.keys_alt = A.get<uint64_t>(n);
+    t.idx = A.get<uint32_t>(n); t.idx_alt = A.get<uint32_t>(n);
+    t.term = A.get<double>(n);
+    return t;
+}
 
 // ---- contributions -> CSR for matrices with short rows (IvA, IvE, XvA, XvE: 1-8 contributions per row) ----
 // No ordering of the whole list: contributions are dropped into per-row slots (integer atomics: the
@@ -1773,12 +1887,8 @@ static void smooth_matrix(ibh_weighted *w, const ibh_regrid_matrices *rm, const 
     exclusive_scan_u32(pcnt, pcnt, ns, d_cnt + 1, st);
     IBH_HIP(hipMemcpyAsync(h, d_cnt, sizeof(h), hipMemcpyDeviceToHost, st));
     IBH_HIP(hipStreamSynchronize(st));
-    Triplets t;
-    t.n = h[1];
-    IBH_CHECK(t.n < (1ul << 31), "smoothed matrix too large (%zu products)", t.n);
-    t.keys = A.get<uint64_t>(t.n); t.keys_alt = A.get<uint64_t>(t.n);
-    t.idx = A.get<uint32_t>(t.n); t.idx_alt = A.get<uint32_t>(t.n);
-    t.term = A.get<double>(t.n);
+    IBH_CHECK(h[1] < (1ul << 31), "smoothed matrix too large (%zu products)", (size_t)h[1]);
+    Triplets t = triplets_in_arena(h[1]);
     if (ns) hipLaunchKernelGGL(k_smooth_prod_emit, dim3(ceil_div(ns, T)), dim3(T), 0, st, sk, si, wraw, denom, ns, w->rowptr.p,
                                w->colind.p, w->val.p, pcnt, t.keys, t.idx, t.term);
     IBH_HIP(hipGetLastError());
@@ -1802,7 +1912,7 @@ void build_bands_from_csr(const ibh_weighted *cw, hipStream_t st) {
     ibh_weighted *w = const_cast<ibh_weighted *>(cw);
     if (!w->band_eligible || w->band_n > 0 || w->nnz == 0 || w->nrow == 0 || w->ncol >= (1 << 28)) return;
     const ibh_sparse_set *rset = w->dims[0];
-    if (!rset || rset->identity || rset->dev_n < w->nrow) return;         // the row keys must be on the device
+    if (!rset || !rset->on_device(w->nrow)) return;                       // the row keys must be on the device
     Arena &A = arena();
     A.reset();
     const int T = 256, nrow = w->nrow, ncol = w->ncol;
@@ -1820,7 +1930,7 @@ void build_bands_from_csr(const ibh_weighted *cw, hipStream_t st) {
     exclusive_scan_u32(cntc, colptr, (size_t)ncol, colptr + ncol, st);
     hipLaunchKernelGGL(k_col_scatter, dim3(ceil_div(nnz, T)), dim3(T), 0, st, row, w->colind.p, nnz, colptr, fillc, lrow, lidx);
     uint32_t *d_nb = A.get<uint32_t>(1);
-    build_bands(w, rg, rset->dev.p, row, colptr, lrow, lidx, d_nb, st);
+    build_bands(w, rg, rset->device_to_sparse(nrow, st), row, colptr, lrow, lidx, d_nb, st);
     uint32_t nb = 0;
     readback_sync(&nb, d_nb, sizeof(uint32_t), st);
     w->band_n = nb;
@@ -2015,7 +2125,6 @@ bool build_sweep_from_csr(const ibh_weighted *cw, hipStream_t st) {
 // more than IBH_GSLOTS rows or a column more than two entries in one group.  Host synchronisations for sizes; runs once per
 // matrix (ibh_weighted_prepare, or lazily from a later apply).
 constexpr uint32_t GRP_HAS0 = 1u << 16, GRP_HAS1 = 1u << 17;
-static const int64_t *dims_device_table(ibh_sparse_set *set, int n, hipStream_t st);
 __global__ void k_rg_rowkeys(RgView rg, const int64_t *__restrict__ row_s, int nrow, uint64_t *__restrict__ keys, uint32_t *__restrict__ idx) {
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= nrow) return;
@@ -2174,7 +2283,7 @@ bool build_groups_from_csr(const ibh_weighted *cw, hipStream_t st) {
     A.reset();
     const int T = 256, nrow = w->nrow;
     const long nnz = w->nnz;
-    const int64_t *row_s = dims_device_table(w->dims[0], nrow, st);       // the row keys (a caller-supplied set may live on the host only)
+    const int64_t *row_s = w->dims[0]->device_to_sparse(nrow, st);     // the row keys (a caller-supplied set may live on the host only)
     RgView rg{};
     rg.sA = w->band_sA; rg.sHC = w->band_sHC;
     uint32_t *d_cnt = A.get<uint32_t>(8);
@@ -2292,17 +2401,7 @@ bool assemble_matrix(const ibh_regrid_matrices *rm, const char *spec_name, ibh_s
         if (!w->built_fast) w->built_fast = 1;          // (2: the streamed build, set by stream_build)
         if (smooth) {
             w->built_fast = 1;                          // (3 again when the smoothing is shared as well)
-            const ibh_sparse_set *rs = dims[0];
-            DevBuf<int64_t> row_s;
-            if (rs->identity) {                         // (the coupler's dimI)
-                row_s.alloc((size_t)w->nrow);
-                hipLaunchKernelGGL(k_iota_i64, dim3(ceil_div(w->nrow, 256)), dim3(256), 0, st, row_s.p, (size_t)w->nrow);
-            } else if (rs->dev_n < w->nrow) {
-                rs->ensure_host();
-                row_s.alloc((size_t)w->nrow);
-                IBH_HIP(hipMemcpyAsync(row_s.p, rs->host.data(), sizeof(int64_t) * (size_t)w->nrow, hipMemcpyHostToDevice, st));
-            }
-            smooth_matrix(w.get(), rm, row_s.p ? row_s.p : rs->dev.p, sigma, st, comm);
+            smooth_matrix(w.get(), rm, dims[0]->device_to_sparse(w->nrow, st), sigma, st, comm);
         }
         *out = w.release();
         return true;
@@ -2350,11 +2449,7 @@ bool assemble_matrix(const ibh_regrid_matrices *rm, const char *spec_name, ibh_s
         IBH_CHECK((int64_t)nb->ds.n_old + n_new < (1ll << 31), "dense extent overflows int32");
     }
     const uint32_t ncontrib = h_cnt[3];
-    Triplets t;
-    t.n = ncontrib;
-    t.keys = A.get<uint64_t>(t.n); t.keys_alt = A.get<uint64_t>(t.n);
-    t.idx = A.get<uint32_t>(t.n); t.idx_alt = A.get<uint32_t>(t.n);
-    t.term = A.get<double>(t.n);
+    Triplets t = triplets_in_arena(ncontrib);
     // emit also records the new keys' dense -> sparse entries, so it runs even with no contributions
     if (uses_ep) hipLaunchKernelGGL(k_contrib_emit<true>, grid, dim3(T), 0, st, rg, *sp, rnum.args, cnum.args, pk, poff, t.keys, t.idx, t.term);
     else hipLaunchKernelGGL(k_contrib_emit<false>, grid, dim3(T), 0, st, rg, *sp, rnum.args, cnum.args, pk, poff, t.keys, t.idx, t.term);
@@ -2389,18 +2484,8 @@ bool assemble_matrix(const ibh_regrid_matrices *rm, const char *spec_name, ibh_s
         hipLaunchKernelGGL(k_col_scatter, dim3(ceil_div(nnz, T)), dim3(T), 0, st, row, w->colind.p, nnz, colptr, fillc, lrow, lidx);
         hipLaunchKernelGGL(k_col_sums, dim3(ceil_div(ncol, T)), dim3(T), 0, st, colptr, ncol, lrow, lidx, w->val.p, cs, nlong, longcols);
         hipLaunchKernelGGL(k_col_sums_long, dim3(256), dim3(T), 0, st, colptr, lrow, lidx, w->val.p, cs, nlong, longcols);
-    } else if (nnz) {
-        uint64_t *ck = A.get<uint64_t>((size_t)nnz), *ck2 = A.get<uint64_t>((size_t)nnz);
-        uint32_t *ci = A.get<uint32_t>((size_t)nnz), *ci2 = A.get<uint32_t>((size_t)nnz);
-        hipLaunchKernelGGL(k_col_keys, dim3(ceil_div(nnz, T)), dim3(T), 0, st, w->colind.p, nnz, ck, ci);
-        KeyField f{0, bits_for((uint64_t)ncol)};
-        if (f.nbits > 0 && radix_sort_pairs(ck, ck2, ci, ci2, (size_t)nnz, &f, 1, st)) { std::swap(ck, ck2); std::swap(ci, ci2); }
-        int32_t *scol = A.get<int32_t>((size_t)nnz), *colptr = A.get<int32_t>((size_t)ncol + 1);
-        hipLaunchKernelGGL(k_keys_to_i32, dim3(ceil_div(nnz, T)), dim3(T), 0, st, ck, nnz, scol);
-        rowptr_from_rows(scol, nnz, ncol, colptr, st);
-        seg_sums<true>(colptr, ci, w->val.p, ncol, nnz, cs, st);
-    } else if (ncol) {
-        IBH_HIP(hipMemsetAsync(cs, 0, sizeof(double) * (size_t)ncol, st));
+    } else {
+        col_sums_by_sort(w.get(), ncol, cs, st);
     }
     FinalizeArgs fa{sp->family, scale, correctA, sp->row_key, sp->col_key, nrow, ncol, rset.to_sparse, cset.to_sparse,
                     rs, cs, w->wM.p, w->Mw.p, rowmul, colmul};
@@ -2511,14 +2596,14 @@ void assemble_batch(const ibh_regrid_matrices *rm, int n, const char *const *spe
     const ibh_regridder *g = rm->rg;
     auto readonly = [&](const Job &jb, int k) {          // a set no build ever changes: the identity over its whole extent
         const ibh_sparse_set *s = jb.d[k];
-        return s && s->identity && s->n == key_extent(g, k == 0 ? jb.sp->row_key : jb.sp->col_key);
+        return s && s->identity() && s->n() == key_extent(g, k == 0 ? jb.sp->row_key : jb.sp->col_key);
     };
     // wave of a job: one after the PRODUCER of each of its sets -- the first job of the batch that uses a set which is
     // still empty numbers it; the later users of that set only read it (fast path) and do not wait for each other
     for (int j = 0; j < n; ++j)
         for (int a = 0; a < 2; ++a) {
             const ibh_sparse_set *s = jobs[(size_t)j].d[a];
-            if (!s || s->n != 0 || readonly(jobs[(size_t)j], a)) continue;
+            if (!s || s->n() != 0 || readonly(jobs[(size_t)j], a)) continue;
             for (int i = 0; i < j; ++i)
                 if (jobs[(size_t)i].d[0] == s || jobs[(size_t)i].d[1] == s) {      // i is the producer (the first user)
                     jobs[(size_t)j].wave = std::max(jobs[(size_t)j].wave, jobs[(size_t)i].wave + 1);
@@ -2587,66 +2672,41 @@ __global__ void k_coo_keys(const int32_t *__restrict__ row, const int32_t *__res
     size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (k < n) { keys[k] = ((uint64_t)(uint32_t)row[k] << 32) | (uint32_t)col[k]; idx[k] = (uint32_t)k; }
 }
+// Eigen setFromTriplets of n triplets (dense ids, input order): the indices on the device, the values copied from `val` by `kind`
+static void csr_from_triplets(ibh_weighted *w, int nrow, int ncol, int64_t n, const int32_t *drow, const int32_t *dcol, const double *val,
+                              hipMemcpyKind kind, hipStream_t st) {
+    Triplets t = triplets_in_arena((size_t)n);
+    if (n) {
+        IBH_HIP(hipMemcpyAsync(t.term, val, sizeof(double) * t.n, kind, st));
+        hipLaunchKernelGGL(k_coo_keys, dim3(ceil_div(n, 256)), dim3(256), 0, st, drow, dcol, t.n, t.keys, t.idx);
+    }
+    int32_t *row = nullptr;
+    build_csr_from_contributions(w, t, nrow, ncol, &row, st);
+}
 void weighted_from_coo_device(ibh_weighted *w, int nrow, int ncol, int64_t n, const int32_t *row, const int32_t *col,
                               const double *val) {
     hipStream_t st = nullptr;
     Arena &A = arena();
     A.reset();
-    Triplets t;
-    t.n = (size_t)n;
-    t.keys = A.get<uint64_t>(t.n); t.keys_alt = A.get<uint64_t>(t.n);
-    t.idx = A.get<uint32_t>(t.n); t.idx_alt = A.get<uint32_t>(t.n);
-    t.term = A.get<double>(t.n);
-    int32_t *drow = A.get<int32_t>(t.n), *dcol = A.get<int32_t>(t.n);
+    int32_t *drow = A.get<int32_t>((size_t)n), *dcol = A.get<int32_t>((size_t)n);
     if (n) {
-        IBH_HIP(hipMemcpyAsync(drow, row, sizeof(int32_t) * t.n, hipMemcpyHostToDevice, st));
-        IBH_HIP(hipMemcpyAsync(dcol, col, sizeof(int32_t) * t.n, hipMemcpyHostToDevice, st));
-        IBH_HIP(hipMemcpyAsync(t.term, val, sizeof(double) * t.n, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_coo_keys, dim3(ceil_div(n, 256)), dim3(256), 0, st, drow, dcol, t.n, t.keys, t.idx);
+        IBH_HIP(hipMemcpyAsync(drow, row, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, st));
+        IBH_HIP(hipMemcpyAsync(dcol, col, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, st));
     }
-    int32_t *r = nullptr;
-    build_csr_from_contributions(w, t, nrow, ncol, &r, st);
+    csr_from_triplets(w, nrow, ncol, n, drow, dcol, val, hipMemcpyHostToDevice, st);
     IBH_HIP(hipStreamSynchronize(st));
 }
-
-// the sparse -> dense device table of a pre-populated set (fastasm.inl set_inverse_table: built once, cached in the set)
-const int32_t *set_dense_table(ibh_sparse_set *set, int64_t extent, hipStream_t st) { return set_inverse_table(set, extent, st); }
 
 // setFromTriplets from triplets already on the device (dense ids, input order) and the plain weights wM / Mw = spsparse
 // sum(M, dim, '+') (columns visited ascending, rows ascending inside): the general-dims path of the Hntr matrices (hntr.hip).
 // Enqueued on `st`; reads nothing back but nnz.  The arena is not reset: the caller's triplets may live there.
 void weighted_from_device_triplets(ibh_weighted *w, int nrow, int ncol, int64_t n, const int32_t *drow, const int32_t *dcol,
                                    const double *dval, hipStream_t st) {
-    Arena &A = arena();
-    const int T = 256;
-    Triplets t;
-    t.n = (size_t)n;
-    t.keys = A.get<uint64_t>(t.n); t.keys_alt = A.get<uint64_t>(t.n);
-    t.idx = A.get<uint32_t>(t.n); t.idx_alt = A.get<uint32_t>(t.n);
-    t.term = A.get<double>(t.n);
-    if (n) {
-        IBH_HIP(hipMemcpyAsync(t.term, dval, sizeof(double) * t.n, hipMemcpyDeviceToDevice, st));
-        hipLaunchKernelGGL(k_coo_keys, dim3(ceil_div(n, T)), dim3(T), 0, st, drow, dcol, t.n, t.keys, t.idx);
-    }
-    int32_t *row = nullptr;
-    build_csr_from_contributions(w, t, nrow, ncol, &row, st);
-    const long nnz = w->nnz;
+    csr_from_triplets(w, nrow, ncol, n, drow, dcol, dval, hipMemcpyDeviceToDevice, st);
     w->wM.alloc((size_t)nrow); w->Mw.alloc((size_t)ncol);
-    seg_sums<true>(w->rowptr.p, nullptr, w->val.p, nrow, nnz, w->wM.p, st);
-    if (nnz) {
-        uint64_t *ck = A.get<uint64_t>((size_t)nnz), *ck2 = A.get<uint64_t>((size_t)nnz);
-        uint32_t *ci = A.get<uint32_t>((size_t)nnz), *ci2 = A.get<uint32_t>((size_t)nnz);
-        hipLaunchKernelGGL(k_col_keys, dim3(ceil_div(nnz, T)), dim3(T), 0, st, w->colind.p, nnz, ck, ci);
-        KeyField f{0, bits_for((uint64_t)ncol)};
-        if (f.nbits > 0 && radix_sort_pairs(ck, ck2, ci, ci2, (size_t)nnz, &f, 1, st)) { std::swap(ck, ck2); std::swap(ci, ci2); }
-        int32_t *scol = A.get<int32_t>((size_t)nnz), *colptr = A.get<int32_t>((size_t)ncol + 1);
-        hipLaunchKernelGGL(k_keys_to_i32, dim3(ceil_div(nnz, T)), dim3(T), 0, st, ck, nnz, scol);
-        rowptr_from_rows(scol, nnz, ncol, colptr, st);
-        seg_sums<true>(colptr, ci, w->val.p, ncol, nnz, w->Mw.p, st);
-    } else {
-        if (nrow) IBH_HIP(hipMemsetAsync(w->wM.p, 0, sizeof(double) * (size_t)nrow, st));
-        if (ncol) IBH_HIP(hipMemsetAsync(w->Mw.p, 0, sizeof(double) * (size_t)ncol, st));
-    }
+    seg_sums<true>(w->rowptr.p, nullptr, w->val.p, nrow, w->nnz, w->wM.p, st);
+    if (!w->nnz && nrow) IBH_HIP(hipMemsetAsync(w->wM.p, 0, sizeof(double) * (size_t)nrow, st));
+    col_sums_by_sort(w, ncol, w->Mw.p, st);
     IBH_HIP(hipGetLastError());
 }
 
@@ -2741,22 +2801,6 @@ __global__ void k_fill_f64(double *p, size_t n, double v) {
     if (i < n) p[i] = v;
 }
 
-static const int64_t *dims_device_table(ibh_sparse_set *set, int n, hipStream_t st) {
-    // dense -> sparse table of a matrix's dims on the device (an identity set is materialised in the arena)
-    Arena &A = arena();
-    int64_t *t = A.get<int64_t>((size_t)n);
-    if (set->identity) {
-        hipLaunchKernelGGL(k_iota_i64, dim3(ceil_div(n, 256)), dim3(256), 0, st, t, (size_t)n);
-    } else if (set->dev_n >= n) {
-        IBH_HIP(hipMemcpyAsync(t, set->dev.p, sizeof(int64_t) * (size_t)n, hipMemcpyDeviceToDevice, st));
-    } else {
-        set->ensure_host();
-        IBH_HIP(hipMemcpyAsync(t, set->host.data(), sizeof(int64_t) * (size_t)n, hipMemcpyHostToDevice, st));
-        IBH_HIP(hipStreamSynchronize(st));
-    }
-    return t;
-}
-
 void e1ve0_compute(int nsheets, const ibh_weighted *const *XuE1s, const ibh_weighted *const *XuE0s, int64_t nE, ibh_weighted *out) {
     IBH_CHECK(nsheets >= 1 && XuE1s && XuE0s && out, "bad arguments");
     IBH_CHECK(nE > 0 && nE < (1ll << 31), "nE=%ld out of range", (long)nE);
@@ -2770,19 +2814,19 @@ void e1ve0_compute(int nsheets, const ibh_weighted *const *XuE1s, const ibh_weig
     for (int s = 0; s < nsheets; ++s) {
         const ibh_weighted *w1 = XuE1s[s], *w0 = XuE0s[s];
         IBH_CHECK(w1 && w0, "null matrix for sheet %d", s);
-        IBH_CHECK(w1->dims[1]->sparse_extent <= nE && w0->dims[1]->sparse_extent <= nE, "sheet %d: E extent exceeds nE", s);
-        const int64_t nX = w1->dims[0]->sparse_extent;
-        IBH_CHECK(nX == w0->dims[0]->sparse_extent && nX >= 0 && nX < (1ll << 31), "sheet %d: XuE1 and XuE0 disagree on nX", s);
+        IBH_CHECK(w1->dims[1]->sparse_extent() <= nE && w0->dims[1]->sparse_extent() <= nE, "sheet %d: E extent exceeds nE", s);
+        const int64_t nX = w1->dims[0]->sparse_extent();
+        IBH_CHECK(nX == w0->dims[0]->sparse_extent() && nX >= 0 && nX < (1ll << 31), "sheet %d: XuE1 and XuE0 disagree on nX", s);
         XuEView v[2];
         const ibh_weighted *ws[2] = {w1, w0};
         for (int k = 0; k < 2; ++k) {
             const ibh_weighted *w = ws[k];
-            v[k] = XuEView{w->rowptr.p, w->colind.p, w->val.p, w->wM.p, dims_device_table(w->dims[1], w->ncol, st), nullptr, w->nrow};
-            const bool ident = w->dims[0]->identity && w->dims[0]->n >= w->nrow;
+            v[k] = XuEView{w->rowptr.p, w->colind.p, w->val.p, w->wM.p, w->dims[1]->device_to_sparse(w->ncol, st), nullptr, w->nrow};
+            const bool ident = w->dims[0]->identity() && w->dims[0]->n() >= w->nrow;
             if (!ident) {
                 int32_t *rm = A.get<int32_t>((size_t)nX);
                 IBH_HIP(hipMemsetAsync(rm, 0xFF, sizeof(int32_t) * (size_t)nX, st));
-                const int64_t *rs = dims_device_table(w->dims[0], w->nrow, st);
+                const int64_t *rs = w->dims[0]->device_to_sparse(w->nrow, st);
                 if (w->nrow) hipLaunchKernelGGL(k_scatter_rowmap, dim3(ceil_div(w->nrow, T)), dim3(T), 0, st, rs, w->nrow, rm);
                 v[k].rowmap = rm;
             }
@@ -2798,11 +2842,7 @@ void e1ve0_compute(int nsheets, const ibh_weighted *const *XuE1s, const ibh_weig
         uint32_t h[2];
         readback_sync(h, d_total, sizeof(h), st);
         IBH_CHECK(!h[1], "E1vE0: an XuE row has more than %d entries", E1_MAXROW);
-        Triplets t;
-        t.n = h[0];
-        t.keys = A.get<uint64_t>(t.n); t.keys_alt = A.get<uint64_t>(t.n);
-        t.idx = A.get<uint32_t>(t.n); t.idx_alt = A.get<uint32_t>(t.n);
-        t.term = A.get<double>(t.n);
+        Triplets t = triplets_in_arena(h[0]);
         if (t.n) hipLaunchKernelGGL(k_e1ve0<1>, grid, dim3(T), 0, st, v[0], v[1], (long)nX, cnt, pos, t.keys, t.idx, t.term, too_long);
         IBH_HIP(hipGetLastError());
         std::unique_ptr<ibh_weighted> loc(new ibh_weighted);
@@ -2818,13 +2858,10 @@ void e1ve0_compute(int nsheets, const ibh_weighted *const *XuE1s, const ibh_weig
         out->rowptr = std::move(locals[0]->rowptr); out->colind = std::move(locals[0]->colind); out->val = std::move(locals[0]->val);
         out->nnz = locals[0]->nnz;
     } else {
-        Triplets t;
-        t.n = 0;
-        for (auto &loc : locals) t.n += (size_t)loc->nnz;
-        IBH_CHECK(t.n < (1ul << 31), "E1vE0 too large");
-        t.keys = A.get<uint64_t>(t.n); t.keys_alt = A.get<uint64_t>(t.n);
-        t.idx = A.get<uint32_t>(t.n); t.idx_alt = A.get<uint32_t>(t.n);
-        t.term = A.get<double>(t.n);
+        size_t nt = 0;
+        for (auto &loc : locals) nt += (size_t)loc->nnz;
+        IBH_CHECK(nt < (1ul << 31), "E1vE0 too large");
+        Triplets t = triplets_in_arena(nt);
         uint32_t base = 0;
         for (auto &loc : locals) {          // sheet-major emission order: equal (iE1, iE0) are summed in sheet order
             hipLaunchKernelGGL(k_csr_to_contrib, dim3(ceil_div(nE, T)), dim3(T), 0, st, loc->rowptr.p, loc->colind.p, loc->val.p, (int)nE,
@@ -2889,16 +2926,6 @@ __global__ void k_i2vx_terms(const int32_t *__restrict__ r2, const int32_t *__re
 __global__ void k_i2vx_wM(const int32_t *__restrict__ rowptr, const double *__restrict__ val, int n, double *__restrict__ wM) {
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r < n) wM[r] = rowptr[r + 1] > rowptr[r] ? val[rowptr[r]] : 0.;
-}
-
-static Triplets triplets_in_arena(size_t n) {
-    Arena &A = arena();
-    Triplets t;
-    t.n = n;
-    t.keys = A.get<uint64_t>(n); t.keys_alt = A.get<uint64_t>(n);
-    t.idx = A.get<uint32_t>(n); t.idx_alt = A.get<uint32_t>(n);
-    t.term = A.get<double>(n);
-    return t;
 }
 
 void i2vx_compute(const ibh_weighted *IvI2, const ibh_weighted *IvX, ibh_weighted *out) {

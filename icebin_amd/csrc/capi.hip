@@ -100,12 +100,6 @@ static void check_weighted_device(const ibh_weighted *w) {
     IBH_CHECK(dev == w->device, "Weighted handle belongs to device %d, current device is %d", w->device, dev);
 }
 
-static void make_identity(ibh_sparse_set *s, int64_t n) {
-    s->sparse_extent = n;
-    s->n = (int32_t)n;
-    s->identity = true;
-}
-
 // The ibh_selftest_* entries of the integer primitives run one primitive each on hipStreamPerThread (as the builds do: calls from concurrent host threads overlap).
 // Every result buffer carries SELFTEST_GUARD words after its end, filled with 0xA5 bytes beforehand: a primitive that writes past
 // its output fails the call.
@@ -149,16 +143,14 @@ int ibh_set_device(int device) {
 int ibh_sparse_set_create(int64_t sparse_extent, ibh_sparse_set **out) {
     return guarded([&] {
         IBH_CHECK(out != nullptr, "null argument");
-        auto *s = new ibh_sparse_set;
-        s->sparse_extent = sparse_extent;
-        *out = s;
+        *out = new ibh_sparse_set(sparse_extent);
     });
 }
 int ibh_sparse_set_create_identity(int64_t n, ibh_sparse_set **out) {
     return guarded([&] {
         IBH_CHECK(out != nullptr && n >= 0 && n < (1ll << 31), "bad identity set size %ld", (long)n);
         auto *s = new ibh_sparse_set;
-        make_identity(s, n);
+        s->make_identity(n);
         *out = s;
     });
 }
@@ -166,58 +158,35 @@ int ibh_sparse_set_from_array(int64_t sparse_extent, const int64_t *to_sparse, i
     return guarded([&] {
         IBH_CHECK(out != nullptr && n >= 0 && (n == 0 || to_sparse != nullptr), "bad arguments");
         std::unique_ptr<ibh_sparse_set> s(new ibh_sparse_set);
-        s->sparse_extent = sparse_extent;
-        s->host.assign(to_sparse, to_sparse + n);
-        s->n = s->host_n = n;
-        std::vector<int64_t> sorted(s->host);
-        std::sort(sorted.begin(), sorted.end());
-        for (int32_t i = 0; i < n; ++i) {
-            IBH_CHECK(sorted[(size_t)i] >= 0 && (sparse_extent < 0 || sorted[(size_t)i] < sparse_extent),
-                      "sparse index %ld outside extent %ld", (long)sorted[(size_t)i], (long)sparse_extent);
-            IBH_CHECK(i == 0 || sorted[(size_t)i] != sorted[(size_t)i - 1], "duplicate sparse index %ld", (long)sorted[(size_t)i]);
-        }
+        s->assign_host(sparse_extent, to_sparse, n);
         *out = s.release();
     });
 }
 int ibh_sparse_set_destroy(ibh_sparse_set *s) { delete s; return IBH_OK; }
 int ibh_sparse_set_sparse_extent(const ibh_sparse_set *s, int64_t *out) {
-    return guarded([&] { IBH_CHECK(s && out, "null argument"); *out = s->sparse_extent; });
+    return guarded([&] { IBH_CHECK(s && out, "null argument"); *out = s->sparse_extent(); });
 }
 int ibh_sparse_set_dense_extent(const ibh_sparse_set *s, int32_t *out) {
     return guarded([&] { IBH_CHECK(s && out, "null argument"); *out = s->dense_extent(); });
 }
 int ibh_sparse_set_to_sparse(const ibh_sparse_set *s, int64_t *out) {
     return guarded([&] {
-        IBH_CHECK(s && (out || s->n == 0), "null argument");
-        s->ensure_host();
-        std::copy(s->host.begin(), s->host.begin() + s->n, out);
+        IBH_CHECK(s && (out || s->n() == 0), "null argument");
+        const int64_t *t = s->to_sparse_host();
+        std::copy(t, t + s->n(), out);
     });
 }
 
 int ibh_sparse_set_to_dense(const ibh_sparse_set *s, int64_t sparse, int32_t *dense) {
     return guarded([&] {
         IBH_CHECK(s && dense, "null argument");
-        if (s->identity) { *dense = sparse >= 0 && sparse < s->n ? (int32_t)sparse : -1; return; }
-        s->ensure_inverse();
-        auto it = s->inv.find(sparse);
-        *dense = it == s->inv.end() ? -1 : it->second;
+        *dense = s->to_dense(sparse);
     });
 }
 int ibh_sparse_set_add_dense(ibh_sparse_set *s, int64_t sparse, int32_t *dense) {
     return guarded([&] {
         IBH_CHECK(s && dense, "null argument");
-        IBH_CHECK(sparse >= 0 && (s->sparse_extent < 0 || sparse < s->sparse_extent), "sparse index %ld outside extent %ld",
-                  (long)sparse, (long)s->sparse_extent);
-        if (s->identity && sparse < s->n) { *dense = (int32_t)sparse; return; }
-        s->ensure_inverse();                     // materialises an identity prefix on the host
-        auto it = s->inv.find(sparse);
-        if (it != s->inv.end()) { *dense = it->second; return; }
-        IBH_CHECK(s->n < 0x7fffffff, "dense extent overflows int32");
-        s->identity = false;
-        s->host.push_back(sparse);
-        s->inv[sparse] = s->n;
-        *dense = s->n++;
-        s->host_n = s->inv_n = s->n;             // the device copy (entries [0, dev_n)) is completed by the next build
+        *dense = s->add_dense_host(sparse);
     });
 }
 
@@ -447,8 +416,8 @@ static std::unique_ptr<ibh_weighted> new_loaded(int32_t nrow, int32_t ncol, cons
     w->nrow = nrow; w->ncol = ncol;
     w->conservative = conservative; w->scaled = scaled;
     for (int k = 0; k < 2; ++k) { w->dims[k] = new ibh_sparse_set; w->owns[k] = true; }
-    make_identity(w->dims[0], nrow);
-    make_identity(w->dims[1], ncol);
+    w->dims[0]->make_identity(nrow);
+    w->dims[1]->make_identity(ncol);
     w->wM.upload(wM, (size_t)nrow);
     w->Mw.upload(Mw, (size_t)ncol);
     return w;
@@ -494,7 +463,7 @@ int ibh_e1ve0_compute(int32_t nsheets, const ibh_weighted *const *XuE1s, const i
         for (int s = 0; s < nsheets; ++s) { check_weighted_device(XuE1s[s]); check_weighted_device(XuE0s[s]); }
         std::unique_ptr<ibh_weighted> w(new ibh_weighted);
         IBH_HIP(hipGetDevice(&w->device));
-        for (int k = 0; k < 2; ++k) { w->dims[k] = new ibh_sparse_set; w->owns[k] = true; make_identity(w->dims[k], nE); }
+        for (int k = 0; k < 2; ++k) { w->dims[k] = new ibh_sparse_set; w->owns[k] = true; w->dims[k]->make_identity(nE); }
         e1ve0_compute(nsheets, XuE1s, XuE0s, nE, w.get());
         *out = w.release();
     });
@@ -519,7 +488,7 @@ int ibh_weighted_flags(const ibh_weighted *w, int *conservative, int *scaled) {
 int ibh_weighted_dim(const ibh_weighted *w, int k, int64_t *sparse_extent, int32_t *dense_extent) {
     return guarded([&] {
         IBH_CHECK(w && (k == 0 || k == 1), "bad argument");
-        if (sparse_extent) *sparse_extent = w->dims[k]->sparse_extent;
+        if (sparse_extent) *sparse_extent = w->dims[k]->sparse_extent();
         if (dense_extent) *dense_extent = k == 0 ? w->nrow : w->ncol;
     });
 }
@@ -529,8 +498,8 @@ int ibh_weighted_dim_to_sparse(const ibh_weighted *w, int k, int64_t *out) {
         // a shared dims set may have grown after this matrix was built: report this matrix's extent
         const int32_t n = k == 0 ? w->nrow : w->ncol;
         IBH_CHECK(n == 0 || out, "null output");
-        w->dims[k]->ensure_host();
-        std::copy(w->dims[k]->host.begin(), w->dims[k]->host.begin() + n, out);
+        const int64_t *t = w->dims[k]->to_sparse_host();
+        std::copy(t, t + n, out);
     });
 }
 int ibh_weighted_get_wM(const ibh_weighted *w, double *out) {

@@ -118,39 +118,70 @@ inline int bits_for(uint64_t n) {   // bits needed to represent values in [0, n)
 }  // namespace ibh
 
 // ---- handle layouts (opaque to the C-ABI user) ----------------------------------------------
+// A SparseSet (spsparse::SparseSet): the dense -> sparse table of a matrix dimension, in first-seen order.  A matrix build
+// appends on the DEVICE; the host copy is completed lazily (ensure_host) so that a 10^7-entry dims table never crosses PCIe
+// unless a caller actually reads it.  The copies and caches are changed by the members alone, so each decides in one place
+// which of them stay valid (the longer ones: assemble.hip, "dense numbering").
 struct ibh_sparse_set {
-    int64_t sparse_extent = -1;
-    int32_t n = 0;                       // dense extent
-    bool identity = false;               // to_sparse[i] == i for i < n; neither copy is materialised until asked for
-    // dense -> sparse table in first-seen order.  A matrix build appends on the DEVICE; the host copy
-    // is completed lazily (ensure_host) so that a 10^7-entry dims table never crosses PCIe unless a
-    // caller actually reads it.
-    mutable std::vector<int64_t> host;   // entries [0, host_n) valid
-    mutable int32_t host_n = 0;
-    ibh::DevBuf<int64_t> dev;            // entries [0, dev_n) valid
-    int32_t dev_n = 0;
-    ibh::DevBuf<int32_t> tab;            // device sparse -> dense table (-1 missing) of entries [0, tab_n), built on demand
-    int32_t tab_n = -1;
-    int64_t tab_extent = -1;
-    mutable std::unordered_map<int64_t, int32_t> inv;    // sparse -> dense of entries [0, inv_n): host-side to_dense / add_dense
-    mutable int32_t inv_n = 0;
+  public:
+    ibh_sparse_set() = default;
+    explicit ibh_sparse_set(int64_t sparse_extent) : sparse_extent_(sparse_extent) {}
+    ibh_sparse_set(const ibh_sparse_set &o);            // the entries only: no device copy, no caches
+    ibh_sparse_set &operator=(ibh_sparse_set &&o) = default;
+
+    int32_t n() const { return n_; }
+    int32_t dense_extent() const { return n_; }
+    int64_t sparse_extent() const { return sparse_extent_; }
+    bool identity() const { return identity_; }
+
+    // host side (the C-ABI's SparseSet calls)
+    void make_identity(int64_t n) { *this = ibh_sparse_set(n); n_ = (int32_t)n; identity_ = true; }
+    void assign_host(int64_t sparse_extent, const int64_t *keys, int32_t n);
+    int32_t add_dense_host(int64_t key);
+    int32_t to_dense(int64_t key) const;                // -1: missing
+    const int64_t *to_sparse_host() const { ensure_host(); return host_.data(); }
+    void ensure_host() const;
     void ensure_inverse() const {
         ensure_host();
-        for (int32_t i = inv_n; i < n; ++i) inv[host[(size_t)i]] = i;
-        inv_n = n;
+        for (int32_t i = inv_n_; i < n_; ++i) inv_[host_[(size_t)i]] = i;
+        inv_n_ = n_;
     }
-    int32_t dense_extent() const { return n; }
-    void ensure_host() const {
-        if (host_n >= n) return;
-        host.resize((size_t)n);
-        if (identity) {
-            for (int32_t i = host_n; i < n; ++i) host[(size_t)i] = i;
-        } else {
-            if (dev_n < n) ibh::fail(IBH_EINVAL, "internal: sparse set has no valid copy of entries [%d,%d)", host_n, n);
-            IBH_HIP(hipMemcpy(host.data() + host_n, dev.p + host_n, sizeof(int64_t) * (size_t)(n - host_n), hipMemcpyDeviceToHost));
-        }
-        host_n = n;
-    }
+    // every entry the host holds lies in [0, extent), and there are no more entries than that; `what` names the set in the error
+    void check_entries_within(int64_t extent, const char *what) const;
+
+    // device side.  A set only READ by a build -- identity, pre-populated -- may be shared by builds running concurrently
+    // (assemble_batch): the extent is written only when it changes, and a table that adds nothing changes nothing else.
+    void set_sparse_extent(int64_t extent) { if (sparse_extent_ != extent) sparse_extent_ = extent; }
+    // dense -> sparse of the first n entries into dst, enqueued on st: iota for an identity set, else the device copy, else an
+    // upload of the host copy.  No synchronisation: the source is the set's own host copy, which every caller leaves alone
+    // until it has synchronised the stream (they all read counts back, or synchronise, before returning or changing the set).
+    void copy_to_sparse(int64_t *dst, int n, hipStream_t st) const;
+    // the same table: the set's own device buffer when it holds the n entries, else a copy in the arena
+    const int64_t *device_to_sparse(int n, hipStream_t st) const;
+    bool on_device(int n) const { return !identity_ && dev_n_ >= n; }     // the first n entries are in the set's own device buffer
+    // sparse -> dense (-1 missing) over [0, extent) on the device, built on demand and cached until the set changes
+    const int32_t *device_to_dense(int64_t extent, hipStream_t st);
+    // a build that writes that table itself (fastasm.inl): the buffer, then -- once the set has taken the build's entries --
+    // the mark that it is valid
+    int32_t *device_to_dense_for_write(int64_t extent) { tab_n_ = -1; tab_.alloc((size_t)extent); return tab_.p; }
+    void mark_device_to_dense_written(int64_t extent) { tab_n_ = n_; tab_extent_ = extent; }
+    // the set becomes table[0, n) over `extent`: the present entries followed by new ones (a set numbered by a build).  With
+    // n <= dense extent nothing is new: only the extent is taken.  Cannot fail.
+    void adopt_device(ibh::DevBuf<int64_t> &&table, int32_t n, int64_t extent) noexcept;
+
+  private:
+    int64_t sparse_extent_ = -1;
+    int32_t n_ = 0;                         // dense extent
+    bool identity_ = false;                 // to_sparse[i] == i for i < n; neither copy is materialised until asked for
+    mutable std::vector<int64_t> host_;     // entries [0, host_n_) valid
+    mutable int32_t host_n_ = 0;
+    ibh::DevBuf<int64_t> dev_;              // entries [0, dev_n_) valid
+    int32_t dev_n_ = 0;
+    ibh::DevBuf<int32_t> tab_;              // device sparse -> dense table (-1 missing) of entries [0, tab_n_), built on demand
+    int32_t tab_n_ = -1;
+    int64_t tab_extent_ = -1;
+    mutable std::unordered_map<int64_t, int32_t> inv_;   // sparse -> dense of entries [0, inv_n_): host-side to_dense / add_dense
+    mutable int32_t inv_n_ = 0;
 };
 
 // Mask-independent structure of one exchange grid (fastasm.inl): built once, on the device, the first

@@ -1428,43 +1428,11 @@ __global__ void k_fa_zero_identity(double *__restrict__ w, long n) {
 // Which dims shapes the fast path serves: a G set (A / E) that is fresh or -- E columns only -- pre-populated
 // (the coupler's shared dimE); a P set (I / X) that is fresh or the identity over the whole extent.
 static int fa_pset_mode(const ibh_sparse_set *set, int64_t extent) {       // 1 fresh, 0 identity-complete, -1 unsupported
-    if (set->n == 0) return 1;
-    if (set->identity && set->n == extent) return 0;
+    if (set->n() == 0) return 1;
+    if (set->identity() && set->n() == extent) return 0;
     return -1;
 }
 
-// sparse -> dense table of a pre-populated set on the device, cached in the set (valid while the set has not grown)
-static const int32_t *set_inverse_table(ibh_sparse_set *set, int64_t extent, hipStream_t st) {
-    if (set->tab_n == set->n && set->tab_extent == extent && set->tab.p) return set->tab.p;
-    const int T = 256;
-    set->tab.alloc((size_t)extent);
-    if (set->dev_n < set->n) {                                  // complete the device copy of the dense -> sparse table first
-        set->ensure_host();
-        DevBuf<int64_t> grown((size_t)set->n);
-        IBH_HIP(hipMemcpyAsync(grown.p, set->host.data(), sizeof(int64_t) * (size_t)set->n, hipMemcpyHostToDevice, st));
-        IBH_HIP(hipStreamSynchronize(st));
-        set->dev = std::move(grown);
-        set->dev_n = set->n;
-    }
-    hipLaunchKernelGGL(k_fill_i32, dim3(ceil_div(extent, T)), dim3(T), 0, st, set->tab.p, (size_t)extent, -1);
-    hipLaunchKernelGGL(k_scatter_existing, dim3(ceil_div(set->n, T)), dim3(T), 0, st, set->tab.p, set->dev.p, set->n);
-    set->tab_n = set->n; set->tab_extent = extent;
-    return set->tab.p;
-}
-// A set numbered by this build (fresh) takes the dense -> sparse table the build wrote.  A set that is only read -- identity /
-// pre-populated -- may be shared by builds running concurrently in a batch: its extent is written only when it changes.
-static void commit_set(ibh_sparse_set *set, bool fresh, int64_t extent, DevBuf<int64_t> &table, int n) {
-    if (!fresh) {
-        if (set->sparse_extent != extent) set->sparse_extent = extent;
-        return;
-    }
-    set->sparse_extent = extent;
-    if (n == 0) return;
-    set->host.clear(); set->host_n = 0; set->inv.clear(); set->inv_n = 0;
-    set->dev = std::move(table);
-    set->dev_n = set->n = n;
-    set->identity = false;
-}
 // The two sides of a matrix of the G/P builds (every family but EvA): G = the A / E side, counted and numbered by the ranges;
 // P = the I / X side, an element of which sees at most a few exchange cells
 struct FaRoles {
@@ -1580,7 +1548,7 @@ static bool fast_build_eva(const ibh_regrid_matrices *rm, const MatSpec *sp, ibh
     const ibh_regridder *gr = rm->rg;
     const bool e_is_row = sp->row_key == KEY_E;
     ibh_sparse_set *eset = dims[e_is_row ? 0 : 1], *aset = dims[e_is_row ? 1 : 0];
-    if (eset->n != 0 || aset->n != 0 || eset == aset) return false;
+    if (eset->n() != 0 || aset->n() != 0 || eset == aset) return false;
     const int64_t extE = key_extent(gr, KEY_E), extA = key_extent(gr, KEY_A);
     Arena &A = arena();
     A.reset();
@@ -1662,8 +1630,8 @@ static bool fast_build_eva(const ibh_regrid_matrices *rm, const MatSpec *sp, ibh
             hipLaunchKernelGGL(k_scale, dim3(ceil_div(nnz, T)), dim3(T), 0, st, row, w->colind.p, w->val.p, nnz, rowmul, colmul, scale ? 1 : 0, correctA ? 1 : 0);
         IBH_HIP(hipGetLastError());
     }
-    commit_set(eset, true, extE, etable, nE);
-    commit_set(aset, true, extA, atable, nA);
+    eset->adopt_device(std::move(etable), nE, extE);
+    aset->adopt_device(std::move(atable), nA, extA);
     IBH_HIP(hipStreamSynchronize(st));
     return true;
 }
@@ -1673,8 +1641,8 @@ static bool fast_build_eva(const ibh_regrid_matrices *rm, const MatSpec *sp, ibh
 static void fast_prewarm(const ibh_regrid_matrices *rm, const MatSpec *sp, ibh_sparse_set *dims[2], hipStream_t st) {
     const ibh_regridder *gr = rm->rg;
     if (!get_tuning("assemble_fast", 1) || !ensure_plan(gr, st)) return;
-    if (sp->family != FAM_IVAE || !dims[1] || dims[1]->n == 0 || dims[1]->identity || sp->col_key != KEY_E) return;
-    (void)set_inverse_table(dims[1], key_extent(gr, KEY_E), st);
+    if (sp->family != FAM_IVAE || !dims[1] || dims[1]->n() == 0 || dims[1]->identity() || sp->col_key != KEY_E) return;
+    (void)dims[1]->device_to_dense(key_extent(gr, KEY_E), st);
     IBH_HIP(hipStreamSynchronize(st));
 }
 
@@ -1775,7 +1743,7 @@ static bool fast_build_gp(const ibh_regrid_matrices *rm, const MatSpec *sp, cons
     g.erank = A.get<int8_t>(nrc); g.ecntn = A.get<uint32_t>(nrc); g.ecnto = A.get<uint32_t>(nrc);
     g.r_ncls = A.get<uint32_t>((size_t)nAr); g.r_nent = A.get<uint32_t>((size_t)nAr);
     g.gbase = A.get<uint32_t>((size_t)nAr + 1); g.ebase = A.get<uint32_t>((size_t)nAr + 1);
-    if (!g_fresh) g.tab = set_inverse_table(role.gset, role.gext, st);
+    if (!g_fresh) g.tab = role.gset->device_to_dense(role.gext, st);
     FaP p{};
     p.key = role.pkey; p.list = role.plist; p.fresh = role.pmode;
     // counters read back with one sync: [0] first out-of-range cell, [1] fallback flags, [2] new P keys, [3] G classes, [4] entries
@@ -1816,17 +1784,15 @@ static bool fast_build_gp(const ibh_regrid_matrices *rm, const MatSpec *sp, cons
             w->rowptr.alloc((size_t)pc_rows + 1);
             chain.pc_rowptr = reinterpret_cast<uint32_t *>(w->rowptr.p); chain.pc_n = pc_rows; chain.pc_first = nAr; chain.pc_status0 = nAr;
         }
-        if (!g_is_row && !g_fresh && role.gset->n > 0) {           // (what k_fa_zero_identity did in a launch of its own)
-            w->Mw.alloc((size_t)role.gset->n);
-            chain.zero2 = reinterpret_cast<uint32_t *>(w->Mw.p); chain.nzero2 = 2u * (unsigned)role.gset->n;
+        if (!g_is_row && !g_fresh && role.gset->n() > 0) {           // (what k_fa_zero_identity did in a launch of its own)
+            w->Mw.alloc((size_t)role.gset->n());
+            chain.zero2 = reinterpret_cast<uint32_t *>(w->Mw.p); chain.nzero2 = 2u * (unsigned)role.gset->n();
         }
         // a fresh E set: the step's later builds (IvE, XvE on the dimE this EvI numbers: IceCoupler.cpp:361-377) look keys up in the
         // sparse -> dense table -- written here as the set is numbered instead of by two launches and a synchronisation later
         if (g_fresh && role.gkey == KEY_E && role.gext < (1l << 22)) {
-            role.gset->tab_n = -1;
-            role.gset->tab.alloc((size_t)role.gext);
-            chain.fill_m1 = role.gset->tab.p; chain.nfill = (unsigned)role.gext;
-            g.tab_out = role.gset->tab.p;
+            g.tab_out = role.gset->device_to_dense_for_write(role.gext);
+            chain.fill_m1 = g.tab_out; chain.nfill = (unsigned)role.gext;
         }
         // what the later kernels want cleared, by the upper bounds the outputs are allocated with below
         const size_t np_ub = p.fresh ? (size_t)std::min<int64_t>(role.pext, nX) : (size_t)role.pext;
@@ -1884,7 +1850,7 @@ static bool fast_build_gp(const ibh_regrid_matrices *rm, const MatSpec *sp, cons
     const uint32_t n_g = optimistic ? (uint32_t)nrc : h[3];
     const uint32_t nnz = optimistic ? (uint32_t)((EP ? 2 : 1) * nX) : h[4];
     int np_d = p.fresh ? (int)n_pnew : (int)role.pext;
-    int ng_d = g_fresh ? (int)n_g : role.gset->n;
+    int ng_d = g_fresh ? (int)n_g : role.gset->n();
     // dims tables of the sets numbered by this build are written straight into the sets' device buffers
     DevBuf<int64_t> ptable, gtable;
     if (p.fresh) { ptable.alloc((size_t)np_d); p.to_sparse = ptable.p; }
@@ -1950,9 +1916,9 @@ static bool fast_build_gp(const ibh_regrid_matrices *rm, const MatSpec *sp, cons
         w->wM.n = (size_t)w->nrow; w->Mw.n = (size_t)w->ncol;
         ptable.n = p.fresh ? (size_t)np_d : 0; gtable.n = g_fresh ? (size_t)ng_d : 0;
     }
-    commit_set(role.pset, p.fresh, role.pext, ptable, np_d);
-    commit_set(role.gset, g_fresh, role.gext, gtable, ng_d);
-    if (g.tab_out) { role.gset->tab_n = role.gset->n; role.gset->tab_extent = role.gext; }
+    role.pset->adopt_device(std::move(ptable), np_d, role.pext);
+    role.gset->adopt_device(std::move(gtable), ng_d, role.gext);
+    if (g.tab_out) role.gset->mark_device_to_dense_written(role.gext);
     IBH_HIP(hipStreamSynchronize(st));
     return true;
 }
@@ -1971,8 +1937,8 @@ static bool fast_build(const ibh_regrid_matrices *rm, const MatSpec *sp, ibh_spa
     role.gext = key_extent(gr, role.gkey); role.pext = key_extent(gr, role.pkey);
     role.pmode = fa_pset_mode(role.pset, role.pext);
     if (role.pmode < 0) return false;
-    role.g_fresh = role.gset->n == 0;
-    if (!role.g_fresh && (role.gset->identity || role.gkey != KEY_E || role.g_is_row)) return false;      // pre-populated: E columns only
+    role.g_fresh = role.gset->n() == 0;
+    if (!role.g_fresh && (role.gset->identity() || role.gkey != KEY_E || role.g_is_row)) return false;      // pre-populated: E columns only
     role.merge = (sp->row_key != KEY_X && sp->col_key != KEY_X) ? 1 : 0;
     const bool uses_ep = sp->row_list == LIST_EP || sp->col_list == LIST_EP;
     return uses_ep ? fast_build_gp<true>(rm, sp, role, scale, correctA, rg, w, st, comm) : fast_build_gp<false>(rm, sp, role, scale, correctA, rg, w, st, comm);

@@ -619,13 +619,19 @@ __device__ __forceinline__ int hm_old(const HmSet &s, long key) {
     if (s.ident_n >= 0) return key < s.ident_n ? (int)key : -1;
     return s.tab[key];
 }
-__global__ void k_hm_first(HmSet s, const int32_t *__restrict__ key, long n) {
+// the key of stream position p is key[p * stride]: stride 1 for the triplets' own index arrays, 2 for the ice index (.y) of
+// global_ec's exchange indices
+__global__ void k_hm_first(HmSet s, const int32_t *__restrict__ key, int stride, long n) {
     const long p = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p < n && (!s.act || s.act[p]) && hm_old(s, key[p]) < 0) atomicMin(&s.first[key[p]], (uint32_t)p);
+    if (p >= n || (s.act && !s.act[p])) return;
+    const int32_t k = key[p * stride];
+    if (hm_old(s, k) < 0) atomicMin(&s.first[k], (uint32_t)p);
 }
-__global__ void k_hm_newflag(HmSet s, const int32_t *__restrict__ key, long n, uint32_t *__restrict__ flag) {
+__global__ void k_hm_newflag(HmSet s, const int32_t *__restrict__ key, int stride, long n, uint32_t *__restrict__ flag) {
     const long p = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p < n) flag[p] = (!s.act || s.act[p]) && hm_old(s, key[p]) < 0 && s.first[key[p]] == (uint32_t)p ? 1u : 0u;
+    if (p >= n) return;
+    const int32_t k = key[p * stride];
+    flag[p] = (!s.act || s.act[p]) && hm_old(s, k) < 0 && s.first[k] == (uint32_t)p ? 1u : 0u;
 }
 __device__ __forceinline__ int hm_dense(const HmSet &s, long key) {
     const int d = hm_old(s, key);
@@ -661,26 +667,10 @@ __global__ void k_hm_compact(HmSet sb, HmSet sa, const int32_t *__restrict__ iB,
     val[q] = v[p];
 }
 // new keys in first-seen order
-__global__ void k_hm_newkeys(const int32_t *__restrict__ key, long n, const uint32_t *__restrict__ rank, int64_t *__restrict__ out) {
+__global__ void k_hm_newkeys(const int32_t *__restrict__ key, int stride, long n, const uint32_t *__restrict__ rank,
+                             int64_t *__restrict__ out) {
     const long p = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p < n && rank[p + 1] != rank[p]) out[rank[p]] = key[p];
-}
-__global__ void k_hm_iota(int64_t *p, long n) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) p[i] = i;
-}
-
-// the dense -> sparse table of a set's first n entries, in the arena
-static int64_t *hm_set_table(ibh_sparse_set *set, int n, hipStream_t st) {
-    int64_t *t = arena().get<int64_t>((size_t)n);
-    if (n == 0) return t;
-    if (set->identity) hipLaunchKernelGGL(k_hm_iota, dim3(ceil_div(n, 256)), dim3(256), 0, st, t, (long)n);
-    else if (set->dev_n >= n) IBH_HIP(hipMemcpyAsync(t, set->dev.p, sizeof(int64_t) * (size_t)n, hipMemcpyDeviceToDevice, st));
-    else {
-        set->ensure_host();
-        IBH_HIP(hipMemcpyAsync(t, set->host.data(), sizeof(int64_t) * (size_t)n, hipMemcpyHostToDevice, st));
-    }
-    return t;
+    if (p < n && rank[p + 1] != rank[p]) out[rank[p]] = key[p * stride];
 }
 
 static int hm_tpr(int64_t nnz, int64_t nrow) {
@@ -753,45 +743,39 @@ static void hm_check_transform(int transform, const char *which) {
 }
 static ibh_sparse_set *hm_dims(ibh_sparse_set *set, int64_t extent, const char *which) {
     if (!set) return nullptr;
-    IBH_CHECK(set->sparse_extent == -1 || set->sparse_extent == extent, "Hntr matrix_d: %s has sparse extent %lld, the grid %lld cells",
-              which, (long long)set->sparse_extent, (long long)extent);
-    IBH_CHECK(set->dense_extent() <= extent, "Hntr matrix_d: %s holds %d entries, more than the grid's %lld cells", which,
-              set->dense_extent(), (long long)extent);
-    if (!set->identity && set->host_n == set->n)
-        for (int32_t i = 0; i < set->n; ++i)
-            IBH_CHECK(set->host[(size_t)i] >= 0 && set->host[(size_t)i] < extent, "Hntr matrix_d: %s entry %lld outside [0, %lld)", which,
-                      (long long)set->host[(size_t)i], (long long)extent);
+    IBH_CHECK(set->sparse_extent() == -1 || set->sparse_extent() == extent, "Hntr matrix_d: %s has sparse extent %lld, the grid %lld cells",
+              which, (long long)set->sparse_extent(), (long long)extent);
+    set->check_entries_within(extent, (std::string("Hntr matrix_d: ") + which).c_str());
     return set;
 }
 static bool hm_full_identity(const ibh_sparse_set *set, int64_t extent) {
-    return !set || (set->identity && set->n == extent);
+    return !set || (set->identity() && set->n() == extent);
 }
 
 struct HmNumber {
     HmSet s{};
     ibh_sparse_set *set = nullptr;
-    int64_t extent = 0;
     uint32_t *flag = nullptr;       // [n+1]: new-key flags, then their exclusive scan (rank)
 };
-static HmNumber hm_number_prepare(ibh_sparse_set *set, int64_t extent, int transform, const int32_t *key, long n, const uint8_t *act,
-                                  hipStream_t st) {
+static HmNumber hm_number_prepare(ibh_sparse_set *set, int64_t extent, int transform, const int32_t *key, int stride, long n,
+                                  const uint8_t *act, hipStream_t st) {
     Arena &A = arena();
     HmNumber nb;
-    nb.set = set; nb.extent = extent;
+    nb.set = set;
     HmSet &s = nb.s;
     s.transform = transform;
     s.act = act;
-    s.n_old = set ? set->n : (int)extent;
+    s.n_old = set ? set->n() : (int)extent;
     s.ident_n = -1;
-    if (!set || set->identity || s.n_old == 0) s.ident_n = s.n_old;        // an empty set: the identity on [0, 0)
-    else s.tab = set_dense_table(set, extent, st);
+    if (!set || set->identity() || s.n_old == 0) s.ident_n = s.n_old;      // an empty set: the identity on [0, 0)
+    else s.tab = set->device_to_dense(extent, st);
     if (transform == IBH_ADD_DENSE) {
         s.first = A.get<uint32_t>((size_t)extent);
         IBH_HIP(hipMemsetAsync(s.first, 0xFF, sizeof(uint32_t) * (size_t)extent, st));
         nb.flag = A.get<uint32_t>((size_t)n + 1);
         if (n) {
-            hipLaunchKernelGGL(k_hm_first, dim3(ceil_div(n, 256)), dim3(256), 0, st, s, key, n);
-            hipLaunchKernelGGL(k_hm_newflag, dim3(ceil_div(n, 256)), dim3(256), 0, st, s, key, n, nb.flag);
+            hipLaunchKernelGGL(k_hm_first, dim3(ceil_div(n, 256)), dim3(256), 0, st, s, key, stride, n);
+            hipLaunchKernelGGL(k_hm_newflag, dim3(ceil_div(n, 256)), dim3(256), 0, st, s, key, stride, n, nb.flag);
         }
         exclusive_scan_u32(nb.flag, nb.flag, (size_t)n, nb.flag + n, st);
         s.rank = nb.flag;
@@ -799,28 +783,17 @@ static HmNumber hm_number_prepare(ibh_sparse_set *set, int64_t extent, int trans
     IBH_HIP(hipGetLastError());
     return nb;
 }
-// the set's grown dense -> sparse table (old entries, then the new keys first-seen); empty when it gains nothing
-static DevBuf<int64_t> hm_number_grow(HmNumber &nb, const int32_t *key, long n, uint32_t n_new, hipStream_t st) {
+// the set's grown dense -> sparse table (old entries, then the new keys first-seen); empty when it gains nothing.  The set takes
+// it (adopt_device) only once everything else has succeeded.
+static DevBuf<int64_t> hm_number_grow(HmNumber &nb, const int32_t *key, int stride, long n, uint32_t n_new, hipStream_t st) {
     DevBuf<int64_t> grown;
     if (!nb.set || nb.s.transform != IBH_ADD_DENSE || n_new == 0) return grown;
     const int n_old = nb.s.n_old;
     grown.alloc((size_t)n_old + n_new);
-    const int64_t *old = hm_set_table(nb.set, n_old, st);
-    if (n_old) IBH_HIP(hipMemcpyAsync(grown.p, old, sizeof(int64_t) * (size_t)n_old, hipMemcpyDeviceToDevice, st));
-    hipLaunchKernelGGL(k_hm_newkeys, dim3(ceil_div(n, 256)), dim3(256), 0, st, key, n, nb.flag, grown.p + n_old);
+    nb.set->copy_to_sparse(grown.p, n_old, st);
+    hipLaunchKernelGGL(k_hm_newkeys, dim3(ceil_div(n, 256)), dim3(256), 0, st, key, stride, n, nb.flag, grown.p + n_old);
     IBH_HIP(hipGetLastError());
     return grown;
-}
-// adopt the grown table (nothing here can fail): called only once everything else has succeeded
-static void hm_number_adopt(HmNumber &nb, DevBuf<int64_t> &grown) noexcept {
-    ibh_sparse_set *set = nb.set;
-    if (!set) return;
-    set->sparse_extent = nb.extent;
-    if (!grown.p) return;
-    if (set->identity) { set->host.clear(); set->host_n = 0; }
-    set->dev_n = set->n = (int32_t)grown.n;
-    set->dev = std::move(grown);
-    set->identity = false;
 }
 
 static void hntr_matrix(const ibh_hntr *h, int kind, double eq_rad, const uint8_t *includeB, ibh_sparse_set *dimB, int tB,
@@ -845,8 +818,6 @@ static void hntr_matrix(const ibh_hntr *h, int kind, double eq_rad, const uint8_
     w->conservative = 1;
     w->scaled = kind == IBH_HNTR_SCALED;
     HmNumber nbB, nbA;          // the fast path numbers nothing: the sets only take their sparse extent
-    nbB.set = dimB; nbB.extent = nB;
-    nbA.set = dimA; nbA.extent = nA;
     DevBuf<int64_t> grownB, grownA;
     if (fast) {
         w->nrow = (int32_t)nB; w->ncol = (int32_t)nA; w->nnz = n;
@@ -870,9 +841,9 @@ static void hntr_matrix(const ibh_hntr *h, int kind, double eq_rad, const uint8_
         uint32_t *keep = A.get<uint32_t>((size_t)n + 1), *bad = A.get<uint32_t>(1);
         uint8_t *act = A.get<uint8_t>((size_t)n);
         IBH_HIP(hipMemsetAsync(bad, 0, sizeof(uint32_t), st));
-        nbB = hm_number_prepare(dimB, nB, tB, iB, (long)n, nullptr, st);
+        nbB = hm_number_prepare(dimB, nB, tB, iB, 1, (long)n, nullptr, st);
         if (n) hipLaunchKernelGGL(k_hm_gate, dim3(ceil_div(n, 256)), dim3(256), 0, st, nbB.s, iB, (long)n, act, bad);
-        nbA = hm_number_prepare(dimA, nA, tA, iA, (long)n, act, st);
+        nbA = hm_number_prepare(dimA, nA, tA, iA, 1, (long)n, act, st);
         if (n) hipLaunchKernelGGL(k_hm_keep, dim3(ceil_div(n, 256)), dim3(256), 0, st, nbA.s, iA, (long)n, keep, bad);
         exclusive_scan_u32(keep, keep, (size_t)n, keep + n, st);
         struct { uint32_t kept, bad, newB, newA; } rb{0, 0, 0, 0};
@@ -890,19 +861,18 @@ static void hntr_matrix(const ibh_hntr *h, int kind, double eq_rad, const uint8_
         IBH_HIP(hipGetLastError());
         weighted_from_device_triplets(w.get(), transpose ? ncolA : nrowB, transpose ? nrowB : ncolA, rb.kept, row, col, val, st);
         // both grown tables exist before either set changes: an error up to here leaves both sets as they were
-        grownB = hm_number_grow(nbB, iB, (long)n, rb.newB, st);
-        grownA = hm_number_grow(nbA, iA, (long)n, rb.newA, st);
+        grownB = hm_number_grow(nbB, iB, 1, (long)n, rb.newB, st);
+        grownA = hm_number_grow(nbA, iA, 1, (long)n, rb.newA, st);
         IBH_HIP(hipStreamSynchronize(st));
     }
     std::unique_ptr<ibh_sparse_set> fresh[2];
     for (int k = 0; k < 2; ++k)
         if (!(k ? dimA : dimB)) {
             fresh[k].reset(new ibh_sparse_set);
-            fresh[k]->sparse_extent = fresh[k]->n = (int32_t)(k ? nA : nB);
-            fresh[k]->identity = true;
+            fresh[k]->make_identity(k ? nA : nB);
         }
-    hm_number_adopt(nbB, grownB);
-    hm_number_adopt(nbA, grownA);
+    if (dimB) dimB->adopt_device(std::move(grownB), (int32_t)grownB.n, nB);
+    if (dimA) dimA->adopt_device(std::move(grownA), (int32_t)grownA.n, nA);
     const bool ownB = !dimB, ownA = !dimA;
     ibh_sparse_set *dB = ownB ? fresh[0].release() : dimB, *dA = ownA ? fresh[1].release() : dimA;
     w->dims[0] = transpose ? dA : dB; w->owns[0] = transpose ? ownA : ownB;
@@ -1025,19 +995,6 @@ __global__ void k_hx_cells(const uint32_t *__restrict__ rank, long nB, int64_t *
     const long r = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (r < nB && rank[r + 1] != rank[r]) to_sparse[rank[r]] = r;
 }
-__global__ void k_hx_first(const int2 *__restrict__ idx, long n, uint32_t *__restrict__ first) {
-    const long p = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p < n) atomicMin(&first[idx[p].y], (uint32_t)p);
-}
-__global__ void k_hx_newflag(const int2 *__restrict__ idx, long n, const uint32_t *__restrict__ first, uint32_t *__restrict__ flag) {
-    const long p = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p < n) flag[p] = first[idx[p].y] == (uint32_t)p ? 1u : 0u;
-}
-__global__ void k_hx_newkeys(const int2 *__restrict__ idx, long n, const uint32_t *__restrict__ rank, int64_t *__restrict__ out) {
-    const long p = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p < n && rank[p + 1] != rank[p]) out[rank[p]] = idx[p].y;
-}
-
 static const ibh_hntr *hx_check_desc(const ibh_hntr_regridder_desc *d) {
     IBH_CHECK(d != nullptr, "null argument");
     const ibh_hntr *h = d->hntr;
@@ -1138,8 +1095,8 @@ static void regridder_create_hntr(const ibh_hntr_regridder_desc *d, ibh_sparse_s
     // make_grid_spec(hspecA) has 2*(jm/2) rows: an odd jm would leave the last GCM row without boundaries.  (The reference
     // also refuses an odd im there; its areas are well defined, so an odd im is accepted.)
     IBH_CHECK(h->jmB % 2 == 0, "global_ec: the GCM grid (Hntr grid B) has jm=%d; make_grid_spec needs an even jm", h->jmB);
-    IBH_CHECK(!dimA_out || dimA_out->n == 0, "global_ec: dimA_out must be an empty set");
-    IBH_CHECK(!dimI_out || dimI_out->n == 0, "global_ec: dimI_out must be an empty set");
+    IBH_CHECK(!dimA_out || dimA_out->n() == 0, "global_ec: dimA_out must be an empty set");
+    IBH_CHECK(!dimI_out || dimI_out->n() == 0, "global_ec: dimI_out must be an empty set");
     IBH_CHECK(!dimA_out || dimA_out != dimI_out, "global_ec: dimA_out and dimI_out must be distinct sets");
     const int64_t nI = (int64_t)h->imA * h->jmA, nB = (int64_t)h->imB * h->jmB;
     hipStream_t st = static_cast<hipStream_t>(d->stream);
@@ -1184,20 +1141,14 @@ static void regridder_create_hntr(const ibh_hntr_regridder_desc *d, ibh_sparse_s
     readback_sync(&nAd, rank + nB, sizeof(nAd), st);
     DevBuf<int64_t> dA((size_t)nAd);
     if (nAd) hipLaunchKernelGGL(k_hx_cells, dim3(ceil_div(nB, HX_T)), dim3(HX_T), 0, st, rank, (long)nB, dA.p);
-    // dimI: first-seen
+    // dimI: first-seen over the ice index (.y) of the exchange indices
     DevBuf<int64_t> dI;
     uint32_t nId = 0;
     if (dimI_out) {
-        uint32_t *first = A.get<uint32_t>((size_t)nI), *flag = A.get<uint32_t>((size_t)nX + 1);
-        IBH_HIP(hipMemsetAsync(first, 0xFF, sizeof(uint32_t) * (size_t)nI, st));
-        if (nX) {
-            hipLaunchKernelGGL(k_hx_first, dim3(ceil_div(nX, HX_T)), dim3(HX_T), 0, st, idx, (long)nX, first);
-            hipLaunchKernelGGL(k_hx_newflag, dim3(ceil_div(nX, HX_T)), dim3(HX_T), 0, st, idx, (long)nX, first, flag);
-        }
-        exclusive_scan_u32(flag, flag, (size_t)nX, flag + nX, st);
-        readback_sync(&nId, flag + nX, sizeof(nId), st);
-        dI.alloc((size_t)nId);
-        if (nX) hipLaunchKernelGGL(k_hx_newkeys, dim3(ceil_div(nX, HX_T)), dim3(HX_T), 0, st, idx, (long)nX, flag, dI.p);
+        const int32_t *iI = reinterpret_cast<const int32_t *>(idx) + 1;
+        HmNumber nb = hm_number_prepare(dimI_out, nI, IBH_ADD_DENSE, iI, 2, (long)nX, nullptr, st);
+        readback_sync(&nId, nb.flag + nX, sizeof(nId), st);
+        dI = hm_number_grow(nb, iI, 2, (long)nX, nId, st);
     }
     IBH_HIP(hipGetLastError());
     // agridA on the host: make_abbr_grid's areas (GridGen_LonLat.cpp:234-275) from make_grid_spec(hspecA, false)
@@ -1224,22 +1175,8 @@ static void regridder_create_hntr(const ibh_hntr_regridder_desc *d, ibh_sparse_s
     g->A_ratio_s.upload(ratio.data(), ratio.size(), st);
     IBH_HIP(hipStreamSynchronize(st));
     // nothing below can fail: adopt the sets
-    if (dimA_out) {
-        dimA_out->sparse_extent = nB;
-        dimA_out->identity = false;
-        dimA_out->host = g->A_to_sparse; dimA_out->host_n = (int32_t)nAd;
-        dimA_out->dev = std::move(dA); dimA_out->dev_n = (int32_t)nAd;
-        dimA_out->n = (int32_t)nAd;
-        dimA_out->inv.clear(); dimA_out->inv_n = 0; dimA_out->tab_n = -1;
-    }
-    if (dimI_out) {
-        dimI_out->sparse_extent = nI;
-        dimI_out->identity = false;
-        dimI_out->host.clear(); dimI_out->host_n = 0;
-        dimI_out->dev = std::move(dI); dimI_out->dev_n = (int32_t)nId;
-        dimI_out->n = (int32_t)nId;
-        dimI_out->inv.clear(); dimI_out->inv_n = 0; dimI_out->tab_n = -1;
-    }
+    if (dimA_out) dimA_out->adopt_device(std::move(dA), (int32_t)nAd, nB);
+    if (dimI_out) dimI_out->adopt_device(std::move(dI), (int32_t)nId, nI);
     *out = g.release();
 }
 
@@ -1253,45 +1190,27 @@ static void make_i2vx(const ibh_weighted *IvX, const ibh_hntr *h, double eq_rad,
     ibh_sparse_set *dimI = IvX->dims[0], *dimX = IvX->dims[1];
     const int64_t nI = (int64_t)h->imB * h->jmB, nI2 = (int64_t)h->imA * h->jmA;
     IBH_CHECK(dimI && dimX, "make_I2vX: IvX has no dims");
-    IBH_CHECK(dimI->sparse_extent == nI, "make_I2vX: IvX's ice dim has sparse extent %lld, the Hntr handle's grid B (hspecI) %lld cells",
-              (long long)dimI->sparse_extent, (long long)nI);
-    IBH_CHECK(dimI->n == IvX->nrow, "make_I2vX: IvX's ice dim holds %d entries, IvX has %d rows", dimI->n, IvX->nrow);
+    IBH_CHECK(dimI->sparse_extent() == nI, "make_I2vX: IvX's ice dim has sparse extent %lld, the Hntr handle's grid B (hspecI) %lld cells",
+              (long long)dimI->sparse_extent(), (long long)nI);
+    IBH_CHECK(dimI->n() == IvX->nrow, "make_I2vX: IvX's ice dim holds %d entries, IvX has %d rows", dimI->n(), IvX->nrow);
     IBH_CHECK(includeI == nullptr || nincl == nI, "make_I2vX: includeI has %lld entries, the ice grid %lld cells", (long long)nincl,
               (long long)nI);
     IBH_CHECK(dimI2 == nullptr || (dimI2 != dimI && dimI2 != dimX), "make_I2vX: dimI2 must be a set of its own");
-    IBH_CHECK(dimI2 == nullptr || dimI2->sparse_extent == -1 || dimI2->sparse_extent == nI2,
+    IBH_CHECK(dimI2 == nullptr || dimI2->sparse_extent() == -1 || dimI2->sparse_extent() == nI2,
               "make_I2vX: dimI2 has sparse extent %lld, the Hntr handle's grid A (hspecI2) %lld cells",
-              (long long)(dimI2 ? dimI2->sparse_extent : 0), (long long)nI2);
-    std::unique_ptr<ibh_sparse_set> tmp(new ibh_sparse_set);
-    if (dimI2) {
-        tmp->sparse_extent = dimI2->sparse_extent;
-        tmp->identity = dimI2->identity;
-        tmp->n = dimI2->n;
-        if (!dimI2->identity && dimI2->n) { dimI2->ensure_host(); tmp->host = dimI2->host; tmp->host_n = dimI2->n; }
-    }
+              (long long)(dimI2 ? dimI2->sparse_extent() : 0), (long long)nI2);
+    std::unique_ptr<ibh_sparse_set> tmp(dimI2 ? new ibh_sparse_set(*dimI2) : new ibh_sparse_set);
     ibh_weighted *raw = nullptr;
     hntr_matrix(h, IBH_HNTR_OVERLAP, eq_rad, includeI, dimI, IBH_TO_DENSE_IGNORE_MISSING, tmp.get(), IBH_ADD_DENSE, 0, &raw);
     std::unique_ptr<ibh_weighted> IvI2(raw);
     std::unique_ptr<ibh_weighted> w(new ibh_weighted);
     w->device = h->device;
     i2vx_compute(IvI2.get(), IvX, w.get());
-    std::unique_ptr<ibh_sparse_set> xcopy;
-    if (IvX->owns[1]) {
-        xcopy.reset(new ibh_sparse_set);
-        xcopy->sparse_extent = dimX->sparse_extent;
-        xcopy->identity = dimX->identity;
-        xcopy->n = dimX->n;
-        if (!dimX->identity && dimX->n) { dimX->ensure_host(); xcopy->host = dimX->host; xcopy->host_n = dimX->n; }
-    }
+    std::unique_ptr<ibh_sparse_set> xcopy(IvX->owns[1] ? new ibh_sparse_set(*dimX) : nullptr);
     IvI2.reset();
     // nothing below can fail
     if (dimI2) {
-        dimI2->sparse_extent = tmp->sparse_extent;
-        dimI2->identity = tmp->identity;
-        dimI2->host = std::move(tmp->host); dimI2->host_n = tmp->host_n;
-        dimI2->dev = std::move(tmp->dev); dimI2->dev_n = tmp->dev_n;
-        dimI2->n = tmp->n;
-        dimI2->inv.clear(); dimI2->inv_n = 0; dimI2->tab_n = -1;
+        *dimI2 = std::move(*tmp);
         w->dims[0] = dimI2; w->owns[0] = false;
     } else {
         w->dims[0] = tmp.release(); w->owns[0] = true;

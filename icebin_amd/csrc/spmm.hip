@@ -1716,12 +1716,10 @@ void weighted_pair_prepare(const ibh_weighted *first, const ibh_weighted *second
     const ibh_sparse_set *d1 = first->dims[0], *d2 = second->dims[1];
     const bool same_numbering = d1 == d2 || !d1 || !d2;
     if (same_numbering) IBH_CHECK(second->ncol == first->nrow, "pair: extents differ (%d columns, %d rows)", second->ncol, first->nrow);
-    else {
-        if (d1->sparse_extent != d2->sparse_extent)
-            fail(IBH_ENOTIMPL, "pair: the second matrix's columns (extent %ld) are not the first one's rows (extent %ld)",
-                 (long)d2->sparse_extent, (long)d1->sparse_extent);
-        d1->ensure_inverse(); d2->ensure_host();
-    }
+    else if (d1->sparse_extent() != d2->sparse_extent())
+        fail(IBH_ENOTIMPL, "pair: the second matrix's columns (extent %ld) are not the first one's rows (extent %ld)",
+             (long)d2->sparse_extent(), (long)d1->sparse_extent());
+    const int64_t *cols2 = same_numbering ? nullptr : d2->to_sparse_host();     // the second matrix's columns, sparse
     std::vector<double> pw((size_t)ngrp * IBH_GSLOTS, 0.0);
     std::vector<uint32_t> pm((size_t)ngrp, 0u);
     std::vector<int32_t> pr((size_t)ngrp, -1);
@@ -1731,9 +1729,8 @@ void weighted_pair_prepare(const ibh_weighted *first, const ibh_weighted *second
         for (int k = rp2[(size_t)a]; k < rp2[(size_t)a + 1]; ++k) {
             int r1 = ci2[(size_t)k];
             if (!same_numbering) {
-                const auto it = d1->inv.find(d2->host[(size_t)r1]);
-                if (it == d1->inv.end()) fail(IBH_ENOTIMPL, "pair: a column of the second matrix is no row of the first");
-                r1 = it->second;
+                r1 = d1->to_dense(cols2[(size_t)r1]);
+                if (r1 < 0) fail(IBH_ENOTIMPL, "pair: a column of the second matrix is no row of the first");
             }
             IBH_CHECK(r1 >= 0 && r1 < first->nrow, "pair: column out of range");
             const int g = where_g[(size_t)r1], sl = where_s[(size_t)r1];

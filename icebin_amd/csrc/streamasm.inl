@@ -1405,7 +1405,7 @@ static bool stream_build(const ibh_regrid_matrices *rm, const MatSpec *sp, const
     g.erank = A.get<int8_t>(nrc); g.ecntn = A.get<uint32_t>(nrc); g.ecnto = A.get<uint32_t>(nrc);
     g.r_ncls = A.get<uint32_t>((size_t)nAr); g.r_nent = A.get<uint32_t>((size_t)nAr);
     g.gbase = A.get<uint32_t>((size_t)nAr + 1); g.ebase = A.get<uint32_t>((size_t)nAr + 1);
-    if (!g_fresh) g.tab = set_inverse_table(role.gset, role.gext, st);
+    if (!g_fresh) g.tab = role.gset->device_to_dense(role.gext, st);
     FaP p{};
     p.key = role.pkey; p.list = role.plist; p.fresh = pmode;
     sb.code = A.get<uint8_t>((size_t)nW * 64);
@@ -1500,7 +1500,7 @@ static bool stream_build(const ibh_regrid_matrices *rm, const MatSpec *sp, const
     const uint32_t *hme = hh + 8 * rank;
     const uint32_t nnz = (uint32_t)E0[world];
     const int np_d = p.fresh ? (int)P0[world] : (int)role.pext;
-    const int ng_d = g_fresh ? (int)G0[world] : role.gset->n;
+    const int ng_d = g_fresh ? (int)G0[world] : role.gset->n();
     // local -> global numbering of this rank's slice
     if (world > 1) hipLaunchKernelGGL(k_sa_shift, dim3(ceil_div(std::max<long>(nwl + 1, nr + 1), 256l)), dim3(256), 0, st, pscan ? sb.Pw : nullptr, g_is_row ? nullptr : sb.Lw,
                        gW0, nwl + 1, (uint32_t)(P0[rank] - hme[6]), (uint32_t)(L0[rank] - hme[7]), g.gbase, g.ebase, sb.sr0, nr, (uint32_t)G0[rank], (uint32_t)E0[rank]);
@@ -1684,8 +1684,8 @@ static bool stream_build(const ibh_regrid_matrices *rm, const MatSpec *sp, const
                                (long)P0[rank + 1], nkeys, w->rowptr.p, w->colind.p, w->val.p, w->wM.p);
         if (pairs && npk) hipLaunchKernelGGL(k_sa_unpack_mw, dim3((unsigned)ceil_div(npk, 256l)), dim3(256), 0, st, cidx, cval, (long)Cl[rank], (long)Cl[rank + 1], npk, w->Mw.p);
     }
-    commit_set(role.pset, p.fresh, role.pext, ptable, np_d);
-    commit_set(role.gset, g_fresh, role.gext, gtable, ng_d);
+    role.pset->adopt_device(std::move(ptable), np_d, role.pext);
+    role.gset->adopt_device(std::move(gtable), ng_d, role.gext);
     IBH_HIP(hipStreamSynchronize(st));
     w->built_fast = world > 1 ? 3 : 2;
     // (flags raised by the later kernels -- a straddler list that overflowed -- cannot differ from the count pass's; checked there)

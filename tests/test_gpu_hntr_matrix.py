@@ -247,6 +247,42 @@ def test_ignore_missing_b_stops_the_entry():
     assert w2.nnz == w.nnz
 
 
+def test_one_set_grown_and_read_every_way():
+    """One SparseSet through every way it is grown and read: looked up on the device (which builds and caches its device
+    sparse -> dense table), grown on the device, grown on the host, looked up on the device again.  The last lookup must
+    see the host's key at dense id dense_extent - 1."""
+    from icebin_amd import SparseSet
+    b, a = "72x46_east", "144x90_east"
+    h = hntr(b, a)
+    nB, nA = spec(b).size, spec(a).size
+    trip = triplets_ref(spec(b), spec(a), "overlap", R_EARTH)
+    keys = sorted(np.random.default_rng(23).choice(nA, nA // 4, replace=False).tolist())
+    S, L = SparseSet(nA, keys), list(keys)
+
+    def build(includeB, tA):
+        t = trip if includeB is None else triplets_ref(spec(b), spec(a), "overlap", R_EARTH, includeB)
+        ref_l = [[], L]
+        ref = dense_ref(*t, nB, nA, ref_l, (0, tA), False)          # appends to L under ADD_DENSE
+        w = h.matrix_d("overlap", R_EARTH, includeB=includeB, dims=(SparseSet(), S), transforms=(0, tA))
+        check_matrix(w, ref, (ref_l[0], L))
+        assert np.array_equal(S.to_sparse(), L) and S.dense_extent() == len(L)
+        return w
+
+    build(None, 2)                                  # 1. TO_DENSE_IGNORE_MISSING on the pre-populated set
+    south = np.arange(nB) < nB // 2
+    n1 = len(L)
+    build(south, 0)                                 # 2. ADD_DENSE on the device, the southern half of B only
+    assert len(L) > n1
+    have = set(L)
+    k = next(int(x) for x in trip[1] if int(x) not in have)         # an A cell only the northern half reaches
+    assert S.add_dense(k) == len(L)                 # 3. on the host
+    L.append(k)
+    assert np.array_equal(S.to_sparse(), L)
+    w = build(None, 2)                              # 4. TO_DENSE_IGNORE_MISSING again: entries of k land in the last column
+    _, c, _ = w.coo_dense()
+    assert np.any(c == S.dense_extent() - 1)
+
+
 @pytest.mark.parametrize("transpose", [False, True])
 def test_caller_owned_identity_sets(transpose):
     """SparseSet.identity(n) over the whole grid, passed in: the in-place build (no transpose) or the general one; the

@@ -312,6 +312,27 @@ def test_prepopulated_and_shared_dims():
     np.testing.assert_array_equal(dimE2.to_sparse()[:len(some)], some)
 
 
+def test_prepopulated_dimE_grown_on_the_host_between_builds():
+    """The coupler's dimE numbered on the device by EvI, then grown on the host, then read as a pre-populated set by IvE and
+    XvE (through its device sparse -> dense table, which must follow the host's growth)."""
+    g, em, mm, rg = setup("g50")
+    rm = mm.regrid_matrices("greenland", em)
+    nE = g["nA"] * 40
+    dimI, dimE = icebin_amd.SparseSet.identity(g["nI"]), icebin_amd.SparseSet(nE)
+    odimI, odimE = orc.SparseSet(g["nI"], init=np.arange(g["nI"])), orc.SparseSet(nE)
+    assert_same_weighted(rm.matrix_d("EvI", (dimE, dimI), scale=False, correctA=False),
+                         rg.matrix_d("EvI", em, (odimE, odimI), scale=False, correctA=False), "EvI")
+    k = int(np.setdiff1d(np.arange(nE), dimE.to_sparse())[0])
+    assert dimE.add_dense(k) == odimE.add_dense(k) == dimE.dense_extent() - 1
+    w = rm.matrix_d("IvE", (dimI, dimE), scale=True, correctA=True)
+    assert_same_weighted(w, rg.matrix_d("IvE", em, (odimI, odimE), scale=True, correctA=True), "IvE after the host's add_dense")
+    assert w.ncol_d == dimE.dense_extent()
+    dimX, odimX = icebin_amd.SparseSet.identity(len(g["ex_area"])), orc.SparseSet(len(g["ex_area"]), init=np.arange(len(g["ex_area"])))
+    assert_same_weighted(rm.matrix_d("XvE", (dimX, dimE), scale=False, correctA=True),
+                         rg.matrix_d("XvE", em, (odimX, odimE), scale=False, correctA=True), "XvE after the host's add_dense")
+    np.testing.assert_array_equal(dimE.to_sparse(), odimE.to_sparse())
+
+
 def test_errors_mirror_reference():
     g, em, mm, rg = setup("tiny")
     rm = mm.regrid_matrices("greenland", em)
