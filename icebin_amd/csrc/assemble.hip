@@ -1111,8 +1111,9 @@ __global__ void k_band_ptr(const int32_t *__restrict__ rowptr, int nrow, long nn
     const int k = rowptr[r];
     bptr[r] = k < nnz ? (int32_t)dpos[k] : (int32_t)*d_total;
 }
-// colptr/lrow/lidx: the per-column slots built for the column sums.  *d_total receives the number of band entries.
-static void build_bands(ibh_weighted *w, const RgView &rg, const int64_t *row_s, const int32_t *row, const uint32_t *colptr,
+// colptr/lrow/lidx: the per-column slots built for the column sums.  *d_total receives the number of band entries: the caller
+// reads it back into Bands::n.
+static Bands build_bands(const ibh_weighted *w, const RgView &rg, const int64_t *row_s, const int32_t *row, const uint32_t *colptr,
                         const int32_t *lrow, const uint32_t *lidx, uint32_t *d_total, hipStream_t st) {
     Arena &A = arena();
     const int T = 256;
@@ -1122,13 +1123,16 @@ static void build_bands(ibh_weighted *w, const RgView &rg, const int64_t *row_s,
     int32_t *partner = A.get<int32_t>((size_t)nnz);
     hipLaunchKernelGGL(k_band_roles, dim3(ceil_div(ncol, T)), dim3(T), 0, st, rg, row_s, colptr, ncol, lrow, lidx, lower, partner);
     exclusive_scan_u32(lower, dpos, (size_t)nnz, d_total, st);
-    w->band_ptr.alloc((size_t)nrow + 1); w->band_rb1.alloc((size_t)nrow);
-    w->band_col.alloc((size_t)nnz); w->band_v0.alloc((size_t)nnz); w->band_v1.alloc((size_t)nnz);       // upper bound; >= nnz/2 are used
-    IBH_HIP(hipMemsetAsync(w->band_rb1.p, 0xFF, sizeof(int32_t) * (size_t)nrow, st));
+    Bands b;
+    b.nrow = nrow;
+    b.ptr.alloc((size_t)nrow + 1); b.rb1.alloc((size_t)nrow);
+    b.col.alloc((size_t)nnz); b.v0.alloc((size_t)nnz); b.v1.alloc((size_t)nnz);       // upper bound; >= nnz/2 are used
+    IBH_HIP(hipMemsetAsync(b.rb1.p, 0xFF, sizeof(int32_t) * (size_t)nrow, st));
     hipLaunchKernelGGL(k_band_emit, dim3(ceil_div(nnz, T)), dim3(T), 0, st, row, w->colind.p, w->val.p, nnz, lower, dpos, partner,
-                       w->band_col.p, w->band_v0.p, w->band_v1.p, w->band_rb1.p);
-    hipLaunchKernelGGL(k_band_ptr, dim3(ceil_div(nrow + 1, T)), dim3(T), 0, st, w->rowptr.p, nrow, nnz, dpos, d_total, w->band_ptr.p);
+                       b.col.p, b.v0.p, b.v1.p, b.rb1.p);
+    hipLaunchKernelGGL(k_band_ptr, dim3(ceil_div(nrow + 1, T)), dim3(T), 0, st, w->rowptr.p, nrow, nnz, dpos, d_total, b.ptr.p);
     IBH_HIP(hipGetLastError());
+    return b;
 }
 
 // ---- smoothing (sigma != 0): M <- smoothI * M  (smoother.cpp:8-99, RegridMatrices_Dynamic.cpp:237-248) ------
@@ -1908,11 +1912,10 @@ __global__ void k_expand_rows(const int32_t *__restrict__ rowptr, int nrow, int3
     const int r = blockIdx.x;                         // one workgroup per row: rows of E matrices hold 10^1..10^4 entries
     for (int k = rowptr[r] + threadIdx.x; k < rowptr[r + 1]; k += blockDim.x) row[k] = r;
 }
-void build_bands_from_csr(const ibh_weighted *cw, hipStream_t st) {
-    ibh_weighted *w = const_cast<ibh_weighted *>(cw);
-    if (!w->band_eligible || w->band_n > 0 || w->nnz == 0 || w->nrow == 0 || w->ncol >= (1 << 28)) return;
+Bands build_bands_from_csr(const ibh_weighted *w, hipStream_t st) {
+    if (!w->band_eligible || w->nnz == 0 || w->nrow == 0 || w->ncol >= (1 << 28)) return {};
     const ibh_sparse_set *rset = w->dims[0];
-    if (!rset || !rset->on_device(w->nrow)) return;                       // the row keys must be on the device
+    if (!rset || !rset->on_device(w->nrow)) return {};                    // the row keys must be on the device
     Arena &A = arena();
     A.reset();
     const int T = 256, nrow = w->nrow, ncol = w->ncol;
@@ -1930,10 +1933,11 @@ void build_bands_from_csr(const ibh_weighted *cw, hipStream_t st) {
     exclusive_scan_u32(cntc, colptr, (size_t)ncol, colptr + ncol, st);
     hipLaunchKernelGGL(k_col_scatter, dim3(ceil_div(nnz, T)), dim3(T), 0, st, row, w->colind.p, nnz, colptr, fillc, lrow, lidx);
     uint32_t *d_nb = A.get<uint32_t>(1);
-    build_bands(w, rg, rset->device_to_sparse(nrow, st), row, colptr, lrow, lidx, d_nb, st);
+    Bands b = build_bands(w, rg, rset->device_to_sparse(nrow, st), row, colptr, lrow, lidx, d_nb, st);
     uint32_t nb = 0;
     readback_sync(&nb, d_nb, sizeof(uint32_t), st);
-    w->band_n = nb;
+    b.n = nb;
+    return b;
 }
 
 // ---- column-sweep structure (sweep_kernel.inl) of a matrix with short columns, from its CSR --------------------------
@@ -2021,9 +2025,9 @@ __global__ void k_sw_combkeys(const int32_t *__restrict__ urow, int nuniq, uint6
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k < nuniq) { ck[k] = (uint64_t)(uint32_t)urow[k]; cv[k] = (uint32_t)k; }
 }
-bool build_sweep_from_csr(const ibh_weighted *cw, hipStream_t st) {
-    ibh_weighted *w = const_cast<ibh_weighted *>(cw);
-    if (w->sweep_ntask > 0 || w->nnz == 0 || w->nrow == 0 || w->nnz >= (1ll << 31) - 64) return false;
+Sweep build_sweep_from_csr(const ibh_weighted *w, hipStream_t st) {
+    if (w->nnz == 0 || w->nrow == 0 || w->nnz >= (1ll << 31) - 64) return {};
+    Sweep s;
     Arena &A = arena();
     A.reset();
     const int T = 256, nrow = w->nrow, ncol = w->ncol;
@@ -2047,7 +2051,7 @@ bool build_sweep_from_csr(const ibh_weighted *cw, hipStream_t st) {
     readback_sync(h, d_cnt, sizeof(h), st);
     const long nitems = (long)h[0];
     const int nblk = (int)((nitems + 63) / 64);
-    if (nitems <= 0 || (long)nblk * 64 >= (1ll << 31)) return false;
+    if (nitems <= 0 || (long)nblk * 64 >= (1ll << 31)) return {};
     // tasks and their local row tables; tb halves until every task touches <= SWEEP_MAX_SLOTS rows
     int tb = get_tuning("sweep_tb", 0);
     if (tb <= 0) {                                  // the largest power of two <= 16 that leaves >= 1024 tasks (two per CU and round: measured at
@@ -2061,7 +2065,7 @@ bool build_sweep_from_csr(const ibh_weighted *cw, hipStream_t st) {
     uint8_t *eslot = A.get<uint8_t>((size_t)nnz);
     int ntask = 0, nuniq = 0, maxns = 0;
     for (;; tb /= 2) {
-        if (tb < 1) return false;                   // 64 items touch more rows than the kernel's table holds
+        if (tb < 1) return {};                   // 64 items touch more rows than the kernel's table holds
         ntask = ceil_div(nblk, tb);
         uint64_t *a = tk, *b2 = tk2;
         uint32_t *av = tv, *bv = tv2;
@@ -2070,31 +2074,31 @@ bool build_sweep_from_csr(const ibh_weighted *cw, hipStream_t st) {
         if (radix_sort_pairs(a, b2, av, bv, (size_t)nnz, tf, 2, st)) { std::swap(a, b2); std::swap(av, bv); }
         hipLaunchKernelGGL(k_sw_uniq, dim3(ceil_div(nnz, T)), dim3(T), 0, st, a, nnz, u);
         exclusive_scan_u32(u, uscan, (size_t)nnz, d_cnt + 1, st);
-        w->sweep_task_p0.alloc((size_t)ntask + 1); w->sweep_task_ns.alloc((size_t)ntask + 1);
-        hipLaunchKernelGGL(k_sw_taskfirst, dim3(ceil_div(nnz, T)), dim3(T), 0, st, a, u, uscan, nnz, w->sweep_task_p0.p, urow);
+        s.task_p0.alloc((size_t)ntask + 1); s.task_ns.alloc((size_t)ntask + 1);
+        hipLaunchKernelGGL(k_sw_taskfirst, dim3(ceil_div(nnz, T)), dim3(T), 0, st, a, u, uscan, nnz, s.task_p0.p, urow);
         readback_sync(h, d_cnt, sizeof(h), st);
         nuniq = (int)h[1];
         IBH_HIP(hipMemsetAsync(d_cnt + 2, 0, sizeof(uint32_t), st));
-        hipLaunchKernelGGL(k_sw_task_ns, dim3(ceil_div(ntask, T)), dim3(T), 0, st, w->sweep_task_p0.p, ntask, nuniq, w->sweep_task_ns.p, d_cnt + 2);
+        hipLaunchKernelGGL(k_sw_task_ns, dim3(ceil_div(ntask, T)), dim3(T), 0, st, s.task_p0.p, ntask, nuniq, s.task_ns.p, d_cnt + 2);
         readback_sync(h, d_cnt, sizeof(h), st);
         maxns = (int)h[2];
         // LDS per workgroup = tile (33 KB) + 4 waves x maxns x 512 B: <= 22 slots keep two workgroups on a CU, <= 9 three
         const int soft = get_tuning("sweep_soft_slots", 22);
         if (getenv("IBH_SWEEP_DEBUG")) fprintf(stderr, "sweep: nitems %ld nblk %d tb %d ntask %d nuniq %d maxns %d\n", nitems, nblk, tb, ntask, nuniq, maxns);
         if (maxns <= SWEEP_MAX_SLOTS && (maxns <= soft || tb == 1)) {
-            hipLaunchKernelGGL(k_sw_slots, dim3(ceil_div(nnz, T)), dim3(T), 0, st, a, av, u, uscan, nnz, w->sweep_task_p0.p, eslot);
+            hipLaunchKernelGGL(k_sw_slots, dim3(ceil_div(nnz, T)), dim3(T), 0, st, a, av, u, uscan, nnz, s.task_p0.p, eslot);
             break;
         }
     }
     // items
-    w->sweep_col.alloc((size_t)nblk * 64);
-    w->sweep_meta.alloc((size_t)nblk * 64); w->sweep_v0.alloc((size_t)nblk * 64); w->sweep_v1.alloc((size_t)nblk * 64);
-    IBH_HIP(hipMemsetAsync(w->sweep_col.p, 0, sizeof(int32_t) * (size_t)nblk * 64, st));
-    IBH_HIP(hipMemsetAsync(w->sweep_meta.p, 0, sizeof(uint32_t) * (size_t)nblk * 64, st));
-    IBH_HIP(hipMemsetAsync(w->sweep_v0.p, 0, sizeof(double) * (size_t)nblk * 64, st));
-    IBH_HIP(hipMemsetAsync(w->sweep_v1.p, 0, sizeof(double) * (size_t)nblk * 64, st));
-    hipLaunchKernelGGL(k_sw_items, dim3(ceil_div(nnz, T)), dim3(T), 0, st, keys, idx, ih, iscan, nnz, eslot, w->val.p, w->sweep_col.p,
-                       w->sweep_meta.p, w->sweep_v0.p, w->sweep_v1.p, d_cnt + 5);
+    s.col.alloc((size_t)nblk * 64);
+    s.meta.alloc((size_t)nblk * 64); s.v0.alloc((size_t)nblk * 64); s.v1.alloc((size_t)nblk * 64);
+    IBH_HIP(hipMemsetAsync(s.col.p, 0, sizeof(int32_t) * (size_t)nblk * 64, st));
+    IBH_HIP(hipMemsetAsync(s.meta.p, 0, sizeof(uint32_t) * (size_t)nblk * 64, st));
+    IBH_HIP(hipMemsetAsync(s.v0.p, 0, sizeof(double) * (size_t)nblk * 64, st));
+    IBH_HIP(hipMemsetAsync(s.v1.p, 0, sizeof(double) * (size_t)nblk * 64, st));
+    hipLaunchKernelGGL(k_sw_items, dim3(ceil_div(nnz, T)), dim3(T), 0, st, keys, idx, ih, iscan, nnz, eslot, w->val.p, s.col.p,
+                       s.meta.p, s.v0.p, s.v1.p, d_cnt + 5);
     // combine lists: the distinct (task, row) pairs by row, tasks ascending inside a row
     uint64_t *ck = A.get<uint64_t>((size_t)nuniq), *ck2 = A.get<uint64_t>((size_t)nuniq);
     uint32_t *cv = A.get<uint32_t>((size_t)nuniq), *cv2 = A.get<uint32_t>((size_t)nuniq);
@@ -2103,25 +2107,25 @@ bool build_sweep_from_csr(const ibh_weighted *cw, hipStream_t st) {
     if (cf.nbits > 0 && radix_sort_pairs(ck, ck2, cv, cv2, (size_t)nuniq, &cf, 1, st)) { std::swap(ck, ck2); std::swap(cv, cv2); }
     int32_t *srow = A.get<int32_t>((size_t)nuniq);
     hipLaunchKernelGGL(k_keys_to_i32, dim3(ceil_div(nuniq, T)), dim3(T), 0, st, ck, (long)nuniq, srow);
-    w->sweep_comb_ptr.alloc((size_t)nrow + 1); w->sweep_comb_p.alloc((size_t)nuniq);
-    rowptr_from_rows(srow, (long)nuniq, nrow, w->sweep_comb_ptr.p, st);
-    IBH_HIP(hipMemcpyAsync(w->sweep_comb_p.p, cv, sizeof(uint32_t) * (size_t)nuniq, hipMemcpyDeviceToDevice, st));
+    s.comb_ptr.alloc((size_t)nrow + 1); s.comb_p.alloc((size_t)nuniq);
+    rowptr_from_rows(srow, (long)nuniq, nrow, s.comb_ptr.p, st);
+    IBH_HIP(hipMemcpyAsync(s.comb_p.p, cv, sizeof(uint32_t) * (size_t)nuniq, hipMemcpyDeviceToDevice, st));
     IBH_HIP(hipGetLastError());
     readback_sync(h, d_cnt, sizeof(h), st);         // (the arena is reused by the next build)
-    w->sweep_ident = (h[5] == 0 && nitems == (long)ncol) ? 1 : 0;
-    if (w->sweep_ident) w->sweep_col.release();     // column = item index: the list is never read
-    w->sweep_tb = tb; w->sweep_nitems = (int32_t)nitems;
-    w->sweep_nprow = nuniq;
-    w->sweep_nblk = nblk;
-    w->sweep_nslot = maxns < 1 ? 1 : maxns;
-    w->sweep_ntask = ntask;
-    return true;
+    s.ident = (h[5] == 0 && nitems == (long)ncol) ? 1 : 0;
+    if (s.ident) s.col.release();     // column = item index: the list is never read
+    s.tb = tb; s.nitems = (int32_t)nitems;
+    s.nprow = nuniq;
+    s.nblk = nblk;
+    s.nslot = maxns < 1 ? 1 : maxns;
+    s.ntask = ntask;
+    return s;
 }
 
 // ---- row-group structure (spmm.hip rowgroup) of an E-row matrix, from its CSR -------------------------------------------
 // A group = the rows whose keys decode to the same GCM cell (its elevation classes), in ascending row order: slot s of
 // group g.  The group's entries are ordered by column and paired per column into items (an ice cell lies between two classes
-// of a GCM cell: one item with both weights).  Exact copies of M's values.  Declined (false, nothing kept) when a group has
+// of a GCM cell: one item with both weights).  Exact copies of M's values.  Declined (an unbuilt value) when a group has
 // more than IBH_GSLOTS rows or a column more than two entries in one group.  Host synchronisations for sizes; runs once per
 // matrix (ibh_weighted_prepare, or lazily from a later apply).
 constexpr uint32_t GRP_HAS0 = 1u << 16, GRP_HAS1 = 1u << 17;
@@ -2238,8 +2242,8 @@ __global__ __launch_bounds__(SEG) void k_gt_build(const int32_t *__restrict__ ti
     if (k < IBH_GSLOTS)
         for (int e = s_end[k]; e < s_pend[k]; ++e) { gt_ek[e0 + e] = (uint16_t)(SEG * 8); gt_ev[e0 + e] = 0.0; }
 }
-static void build_group_tiles(ibh_weighted *w, const int32_t *d_grp_ptr, int ngrp, const int32_t *it_col, const uint32_t *it_meta,
-                              const double *it_v0, const double *it_v1, long nitems, hipStream_t st) {
+static RowGroups::Tiles build_group_tiles(const int32_t *d_grp_ptr, int ngrp, const int32_t *it_col, const uint32_t *it_meta,
+                                          const double *it_v0, const double *it_v1, long nitems, hipStream_t st) {
     // Tiles of 256 items walked by eight waves, or of 128 by four: many small groups (the Antarctic sheet under a half-degree grid:
     // ~600 items per GCM cell, tens of thousands of cells) leave less of a small tile empty and keep more workgroups on a CU --
     // measured, 128 fields: 3.62 against 3.76 ms; few or large groups (1 km Greenland: 3 400 items per cell) take the large one
@@ -2253,32 +2257,31 @@ static void build_group_tiles(ibh_weighted *w, const int32_t *d_grp_ptr, int ngr
     long nt = 0;
     for (int g = 0; g < ngrp; ++g) { tp[(size_t)g] = (int32_t)nt; nt += ((long)gp[(size_t)g + 1] - gp[(size_t)g] + seg - 1) / seg; }
     tp[(size_t)ngrp] = (int32_t)nt;
-    if (nt <= 0 || nt * ecap >= (1l << 31)) return;
+    if (nt <= 0 || nt * ecap >= (1l << 31)) return {};
     std::vector<int32_t> tg((size_t)nt), ti((size_t)nt);
     for (int g = 0; g < ngrp; ++g)
         for (int t = tp[(size_t)g], i = gp[(size_t)g]; t < tp[(size_t)g + 1]; ++t, i += seg) { tg[(size_t)t] = g; ti[(size_t)t] = i; }
-    DevBuf<int32_t> d_tg((size_t)nt), d_ti((size_t)nt), gt_ptr((size_t)ngrp + 1), gt_col((size_t)nt * seg);
-    DevBuf<uint16_t> gt_ek((size_t)nt * ecap), gt_eptr((size_t)nt * IBH_GT_EP);
-    DevBuf<double> gt_ev((size_t)nt * ecap);
-    d_tg.upload(tg.data(), tg.size(), st); d_ti.upload(ti.data(), ti.size(), st); gt_ptr.upload(tp.data(), tp.size(), st);
-    gt_ek.zero(st); gt_ev.zero(st);
+    RowGroups::Tiles t;
+    DevBuf<int32_t> d_tg((size_t)nt), d_ti((size_t)nt);
+    t.ptr.alloc((size_t)ngrp + 1); t.col.alloc((size_t)nt * seg);
+    t.ek.alloc((size_t)nt * ecap); t.eptr.alloc((size_t)nt * IBH_GT_EP); t.ev.alloc((size_t)nt * ecap);
+    d_tg.upload(tg.data(), tg.size(), st); d_ti.upload(ti.data(), ti.size(), st); t.ptr.upload(tp.data(), tp.size(), st);
+    t.ek.zero(st); t.ev.zero(st);
     if (seg == 128)
-        hipLaunchKernelGGL(k_gt_build<128>, dim3((unsigned)nt), dim3(128), 0, st, d_tg.p, d_ti.p, d_grp_ptr, it_col, it_meta, it_v0, it_v1, gt_col.p,
-                           gt_ek.p, gt_ev.p, gt_eptr.p);
+        hipLaunchKernelGGL(k_gt_build<128>, dim3((unsigned)nt), dim3(128), 0, st, d_tg.p, d_ti.p, d_grp_ptr, it_col, it_meta, it_v0, it_v1, t.col.p,
+                           t.ek.p, t.ev.p, t.eptr.p);
     else
-        hipLaunchKernelGGL(k_gt_build<256>, dim3((unsigned)nt), dim3(256), 0, st, d_tg.p, d_ti.p, d_grp_ptr, it_col, it_meta, it_v0, it_v1, gt_col.p,
-                           gt_ek.p, gt_ev.p, gt_eptr.p);
+        hipLaunchKernelGGL(k_gt_build<256>, dim3((unsigned)nt), dim3(256), 0, st, d_tg.p, d_ti.p, d_grp_ptr, it_col, it_meta, it_v0, it_v1, t.col.p,
+                           t.ek.p, t.ev.p, t.eptr.p);
     IBH_HIP(hipGetLastError());
     IBH_HIP(hipStreamSynchronize(st));              // (the host vectors and the tile maps die here)
-    w->gt_ptr = std::move(gt_ptr); w->gt_col = std::move(gt_col); w->gt_ek = std::move(gt_ek); w->gt_eptr = std::move(gt_eptr);
-    w->gt_ev = std::move(gt_ev);
-    w->gt_seg = seg;
-    w->gt_ntile = (int32_t)nt;
+    t.seg = seg;
+    t.ntile = (int32_t)nt;
+    return t;
 }
-bool build_groups_from_csr(const ibh_weighted *cw, hipStream_t st) {
-    ibh_weighted *w = const_cast<ibh_weighted *>(cw);
-    if (w->grp_n > 0 || !w->band_eligible || w->nnz == 0 || w->nrow == 0 || w->nnz >= (1ll << 31) - 64) return false;
-    if (!w->dims[0]) return false;
+RowGroups build_groups_from_csr(const ibh_weighted *w, hipStream_t st) {
+    if (!w->band_eligible || w->nnz == 0 || w->nrow == 0 || w->nnz >= (1ll << 31) - 64) return {};
+    if (!w->dims[0]) return {};
     Arena &A = arena();
     A.reset();
     const int T = 256, nrow = w->nrow;
@@ -2300,14 +2303,15 @@ bool build_groups_from_csr(const ibh_weighted *cw, hipStream_t st) {
     uint32_t h[8];
     readback_sync(h, d_cnt, sizeof(h), st);
     const int ngrp = (int)h[0];
-    if (ngrp <= 0) return false;
+    if (ngrp <= 0) return {};
     int32_t *gstart = A.get<int32_t>((size_t)ngrp);
     int32_t *grp_of_row = A.get<int32_t>((size_t)nrow), *slot_of_row = A.get<int32_t>((size_t)nrow);
-    DevBuf<int32_t> slotrow((size_t)ngrp * IBH_GSLOTS), grp_ns((size_t)ngrp), grp_ptr((size_t)ngrp + 1);
-    IBH_HIP(hipMemsetAsync(slotrow.p, 0, sizeof(int32_t) * (size_t)ngrp * IBH_GSLOTS, st));
+    RowGroups g;
+    g.slotrow.alloc((size_t)ngrp * IBH_GSLOTS); g.ns.alloc((size_t)ngrp); g.ptr.alloc((size_t)ngrp + 1);
+    IBH_HIP(hipMemsetAsync(g.slotrow.p, 0, sizeof(int32_t) * (size_t)ngrp * IBH_GSLOTS, st));
     hipLaunchKernelGGL(k_rg_gstart, dim3(ceil_div(nrow, T)), dim3(T), 0, st, rh, rhs, nrow, gstart);
-    hipLaunchKernelGGL(k_rg_slots, dim3(ceil_div(nrow, T)), dim3(T), 0, st, rh, rhs, ri, nrow, ngrp, gstart, grp_of_row, slot_of_row, slotrow.p,
-                       grp_ns.p, d_cnt + 1);
+    hipLaunchKernelGGL(k_rg_slots, dim3(ceil_div(nrow, T)), dim3(T), 0, st, rh, rhs, ri, nrow, ngrp, gstart, grp_of_row, slot_of_row, g.slotrow.p,
+                       g.ns.p, d_cnt + 1);
     // entries by (group, column): stable, so the two entries of a column keep their row (= slot) order
     uint64_t *keys = A.get<uint64_t>((size_t)nnz), *keys2 = A.get<uint64_t>((size_t)nnz);
     uint32_t *idx = A.get<uint32_t>((size_t)nnz), *idx2 = A.get<uint32_t>((size_t)nnz);
@@ -2322,22 +2326,18 @@ bool build_groups_from_csr(const ibh_weighted *cw, hipStream_t st) {
     const int maxns = (int)h[1];
     const long nitems = (long)h[2];
     if (getenv("IBH_SWEEP_DEBUG")) fprintf(stderr, "groups: nrow %d ngrp %d maxns %d nitems %ld bad %u\n", nrow, ngrp, maxns, nitems, h[3]);
-    if (maxns > IBH_GSLOTS || h[3] != 0 || nitems <= 0) return false;
-    DevBuf<int32_t> it_col((size_t)nitems);
-    DevBuf<uint32_t> it_meta((size_t)nitems);
-    DevBuf<double> it_v0((size_t)nitems), it_v1((size_t)nitems);
+    if (maxns > IBH_GSLOTS || h[3] != 0 || nitems <= 0) return {};
+    g.col.alloc((size_t)nitems); g.meta.alloc((size_t)nitems); g.v0.alloc((size_t)nitems); g.v1.alloc((size_t)nitems);
     int32_t *it_grp = A.get<int32_t>((size_t)nitems);
-    hipLaunchKernelGGL(k_rg_items, dim3(ceil_div(nnz, T)), dim3(T), 0, st, keys, idx, ih, ihs, nnz, erow, slot_of_row, w->val.p, it_col.p, it_meta.p,
-                       it_v0.p, it_v1.p, it_grp);
-    rowptr_from_rows(it_grp, nitems, ngrp, grp_ptr.p, st);
+    hipLaunchKernelGGL(k_rg_items, dim3(ceil_div(nnz, T)), dim3(T), 0, st, keys, idx, ih, ihs, nnz, erow, slot_of_row, w->val.p, g.col.p, g.meta.p,
+                       g.v0.p, g.v1.p, it_grp);
+    rowptr_from_rows(it_grp, nitems, ngrp, g.ptr.p, st);
     IBH_HIP(hipGetLastError());
     IBH_HIP(hipStreamSynchronize(st));              // (the arena is reused by the next build)
-    w->grp_ptr = std::move(grp_ptr); w->grp_ns = std::move(grp_ns); w->grp_slotrow = std::move(slotrow);
-    w->grp_col = std::move(it_col); w->grp_meta = std::move(it_meta); w->grp_v0 = std::move(it_v0); w->grp_v1 = std::move(it_v1);
-    w->grp_nslot = maxns; w->grp_nitems = (int32_t)nitems;
-    w->grp_n = ngrp;
-    build_group_tiles(w, w->grp_ptr.p, ngrp, w->grp_col.p, w->grp_meta.p, w->grp_v0.p, w->grp_v1.p, nitems, st);
-    return true;
+    g.nslot = maxns; g.nitems = (int32_t)nitems;
+    g.n = ngrp;
+    g.tiles = build_group_tiles(g.ptr.p, ngrp, g.col.p, g.meta.p, g.v0.p, g.v1.p, nitems, st);
+    return g;
 }
 
 #include "fastasm.inl"
@@ -2507,9 +2507,10 @@ bool assemble_matrix(const ibh_regrid_matrices *rm, const char *spec_name, ibh_s
     uint32_t nband_entries = 0;
     if (want_bands) {
         uint32_t *d_nb = A.get<uint32_t>(1);
-        build_bands(w.get(), rg, rset.to_sparse, row, colptr, lrow, lidx, d_nb, st);
+        Bands b = build_bands(w.get(), rg, rset.to_sparse, row, colptr, lrow, lidx, d_nb, st);
         readback_sync(&nband_entries, d_nb, sizeof(uint32_t), st);
-        w->band_n = nband_entries;
+        b.n = nband_entries;
+        w->st.bands = std::move(b);
     } else {
         IBH_HIP(hipStreamSynchronize(st));
     }

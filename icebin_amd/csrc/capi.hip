@@ -683,20 +683,20 @@ int ibh_weighted_set_kernel(ibh_weighted *w, const char *name) {
 int ibh_weighted_last_kernel(const ibh_weighted *w, char *buf, int buflen) {
     return guarded([&] {
         IBH_CHECK(w && buf && buflen > 0, "bad argument");
-        snprintf(buf, (size_t)buflen, "%s", w->last_kernel == KERNEL_AUTO ? "none" : kernel_names[w->last_kernel]);
+        snprintf(buf, (size_t)buflen, "%s", w->st.last_kernel == KERNEL_AUTO ? "none" : kernel_names[w->st.last_kernel]);
     });
 }
 int ibh_weighted_last_launch(const ibh_weighted *w, char *buf, int buflen) {
     return guarded([&] {
         IBH_CHECK(w && buf && buflen > 0, "bad arguments");
-        snprintf(buf, (size_t)buflen, "%s", w->last_sig);
+        snprintf(buf, (size_t)buflen, "%s", w->st.last_sig);
     });
 }
 int ibh_weighted_set_option(ibh_weighted *w, const char *key, int value) {
     return guarded([&] {
         IBH_CHECK(w && key, "null argument");
-        if (value == INT32_MIN) w->opts.erase(key);
-        else w->opts[key] = value;
+        if (value == INT32_MIN) w->st.opts.erase(key);
+        else w->st.opts[key] = value;
     });
 }
 int ibh_weighted_built_fast(const ibh_weighted *w, int *out) {

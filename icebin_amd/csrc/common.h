@@ -106,7 +106,7 @@ struct DevBuf {
 
 inline int ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
 constexpr int IBH_GSLOTS = 32;      // most rows (elevation classes of one GCM cell) in a row group (spmm.hip rowgroup)
-// tiles of a row group (spmm.hip grouptile): seg = items (distinct columns) of a tile, 256 or 128 by the matrix (ibh_weighted::gt_seg)
+// tiles of a row group (spmm.hip grouptile): seg = items (distinct columns) of a tile, 256 or 128 by the matrix (RowGroups::Tiles::seg)
 constexpr int ibh_gt_ecap(int seg) { return 2 * seg + 4 * IBH_GSLOTS; }   // entries of a tile: <= 2 per item, every slot's list padded to a multiple of 4
 constexpr int IBH_GT_EP = IBH_GSLOTS + 2;   // u16 entry offsets of a tile: one per slot + the end, padded to whole dwords
 inline int bits_for(uint64_t n) {   // bits needed to represent values in [0, n)
@@ -263,7 +263,108 @@ inline uint64_t next_weighted_uid() {
 }
 // the apply kernel families (spmm.hip), as ibh_weighted_set_kernel / ibh_weighted_last_kernel name them (capi.hip)
 enum ApplyKernel { KERNEL_AUTO = 0, KERNEL_ROWBLOCK = 1, KERNEL_SHORTROW, KERNEL_ROWDUAL, KERNEL_COLSWEEP, KERNEL_ROWGROUP };
+
+// ---- apply structures: optional copies of a matrix's entries in the order one apply kernel family wants them ------------------
+// Each is a value that owns its buffers: a builder (assemble.hip) fills a local one and returns it, `x = {}` empties it,
+// built() says whether it exists.
+
+// rowdual (EvI, EvX): the CSR filtered to one entry per (GCM cell, ice cell) carrying the weights of BOTH elevation classes
+// the cell lies between (assemble.hip build_bands); band r = row r
+struct Bands {
+    int64_t n = 0;                          // band entries, 0: not built
+    int32_t nrow = 0;                       // bands = rows of the matrix
+    DevBuf<int32_t> ptr, col, rb1;          // [nrow+1]; [n] column | bit30 lower exists | bit31 upper exists; [nrow]
+    DevBuf<double> v0, v1;                  // [n] lower-class / upper-class weight
+    bool built() const { return n > 0; }
+    // partial sums of an apply: [2: lower, upper][nbatch][nvar][part_ld()]
+    long part_ld() const { return ((long)nrow + 63) & ~63l; }
+    long part_stride(int nvar) const { return (long)nvar * part_ld(); }      // one batch's lower (or upper) sums
+    size_t part_count(int nvar, int nbatch) const { return 2 * (size_t)nbatch * (size_t)part_stride(nvar); }
+};
+
+// fields per lane group of the sweep, as a power of two: 64 (one batch per wave row) from 33 fields; below, the next power of
+// two >= 8 so that 64 >> lg batches share the lanes
+inline int sweep_lg(int nvar) { return nvar > 32 ? 6 : nvar > 16 ? 5 : nvar > 8 ? 4 : 3; }
+// colsweep (EvI, EvX, and AvI, AvX in batched launches; sweep_kernel.inl): the entries in column order, paired per column into
+// items, 64 items a block, tb blocks a task with its local row table (assemble.hip build_sweep_from_csr)
+struct Sweep {
+    int32_t ntask = 0, nblk = 0, nprow = 0, nslot = 0;      // ntask == 0: not built
+    int32_t tb = 0, nitems = 0, ident = 0;                  // blocks per task, items, column == item index
+    DevBuf<int32_t> task_p0, task_ns, col;
+    DevBuf<uint32_t> meta;
+    DevBuf<double> v0, v1;
+    DevBuf<int32_t> comb_ptr, comb_p;       // [nrow+1], [nprow]: the partial-sum rows that make up row r, in task order
+    bool built() const { return ntask > 0; }
+    // partial sums of an apply: [slices of 64 lanes, a lane = (batch, field)][nprow][part_ld()]
+    long part_ld(int nvar) const { return sweep_lg(nvar) == 6 ? (long)ceil_div(nvar, 64) * 64 : 64; }
+    long part_stride(int nvar) const { return (long)nprow * part_ld(nvar); }
+    size_t part_count(int nvar, int nbatch) const {
+        const int lg = sweep_lg(nvar);
+        return (size_t)(lg == 6 ? nbatch : ceil_div(nbatch, 64 >> lg)) * (size_t)part_stride(nvar);
+    }
+};
+
+// fused pair (ibh_weighted_pair_prepare): a second matrix whose every row reads rows of ONE group of this matrix only (AvE
+// after EvI: a GCM cell's value is a combination of that cell's elevation classes) rides in the row-group kernel's epilogue.
+// w[g * IBH_GSLOTS + s]: the second matrix's weight of slot s of group g (mask[g] bit s: it has one); row[g]: the second
+// matrix's row fed by group g, -1 none.
+struct Pair {
+    const ibh_weighted *second = nullptr;   // named by (address, uid); nullptr: not built
+    uint64_t uid = 0;
+    DevBuf<double> w;
+    DevBuf<uint32_t> mask;
+    DevBuf<int32_t> row;
+    bool built() const { return second != nullptr; }
+};
+
+// rowgroup (EvI, EvX; spmm.hip): the rows of one GCM cell (its elevation classes) form a GROUP; the group's entries are
+// listed once per distinct column, ascending, as ITEMS {col, meta = slot0 | slot1 << 8 | has-bits, v0, v1} -- the column set
+// of a group is the AvI row of its GCM cell, so X is gathered once per (GCM cell, ice cell) instead of once per class; slot s
+// of group g is row slotrow[g * IBH_GSLOTS + s] (assemble.hip build_groups_from_csr).
+struct RowGroups {
+    int32_t n = 0, nslot = 0, nitems = 0;           // groups (0: not built), most rows in a group, items
+    DevBuf<int32_t> ptr, ns, slotrow, col;          // [n+1] items of a group; [n] rows of a group; [n*IBH_GSLOTS]; [nitems]
+    DevBuf<uint32_t> meta;
+    DevBuf<double> v0, v1;
+    // grouptile (spmm.hip): the items of a group cut into TILES of seg columns; per tile the columns (padded by repeating
+    // the last) and the entries sorted by (slot, column) as {8 x local item index, weight} with u16 offsets per slot -- the rows
+    // of the CSR restricted to the tile, in CSR order.  Entries of tile t start at ibh_gt_ecap(seg) * t.
+    struct Tiles {
+        int32_t ntile = 0, seg = 0;                 // 0: not built
+        DevBuf<int32_t> ptr, col;                   // [n+1] tiles of a group; [ntile * seg]
+        DevBuf<uint16_t> ek, eptr;                  // [ntile * ecap]; [ntile * IBH_GT_EP]
+        DevBuf<double> ev;                          // [ntile * ecap]
+        bool built() const { return ntile > 0; }
+    };
+    Tiles tiles;                                    // the tiles and a pairing index the group table: they exist, and go, with it
+    Pair pair;
+    bool built() const { return n > 0; }
+};
+
+// What the applies keep beside a matrix: the structures (with one flag each: a build that was declined or failed is not tried
+// again), the per-apply scratch, and what the last apply launched.
+struct ApplyState {
+    Bands bands;
+    Sweep sweep;
+    RowGroups groups;
+    bool bands_tried = false, sweep_tried = false, groups_tried = false;
+    struct Scratch {
+        DevBuf<double> scratch, tbuf, rowsum1;      // apply_transformed: fields + small transform, and M*1 (row sums) for the offset term
+        DevBuf<double> consv;                       // force_conservation: the two dot products per variable [2*nvar] + chunk sums
+        DevBuf<double> xt;                          // shortrow: transposed copy of the (small) input fields
+        DevBuf<double> band_part, sweep_part;       // partial sums of one launch (Bands::part_count, Sweep::part_count)
+        DevBuf<int32_t> rowperm;                    // rows by descending length (batched rowblock launches)
+        bool have_rowsum1 = false, have_rowperm = false;
+    } scr;
+    int64_t napply = 0;                             // applies the matrix has seen (the lazy builds wait for the second)
+    ApplyKernel last_kernel = KERNEL_AUTO;          // KERNEL_AUTO: no apply yet
+    char last_sig[64] = {0};    // the kernel instantiation the last apply launched, as rocprofv3 names it (every apply kernel family records it)
+    // per-handle launch options (ibh_weighted_set_option): looked up before the process-wide ibh_set_tuning map by every apply of
+    // THIS matrix, so two host threads tuning different handles do not interfere
+    std::unordered_map<std::string, int> opts;
+};
 }  // namespace ibh
+// The matrix proper is immutable once it is built; `st` is the cache the applies keep beside it.
 struct ibh_weighted {
     const uint64_t uid = ibh::next_weighted_uid();     // never reused: a pairing names its second matrix by (address, uid)
     int device = 0;
@@ -275,67 +376,12 @@ struct ibh_weighted {
     bool owns[2] = {false, false};
     int conservative = 1, scaled = 1;
     int built_fast = 0;                 // assembled by the plan-based fast path (fastasm.inl); introspection only
-    // SpMM dispatch
-    ibh::ApplyKernel kernel_override = ibh::KERNEL_AUTO;
-    mutable char last_sig[64] = {0};    // the kernel instantiation the last apply launched, as rocprofv3 names it (every apply kernel family records it)
-    // per-handle launch options (ibh_weighted_set_option): looked up before the process-wide ibh_set_tuning map by every apply of
-    // THIS matrix, so two host threads tuning different handles do not interfere
-    mutable std::unordered_map<std::string, int> opts;
-    mutable ibh::ApplyKernel last_kernel = ibh::KERNEL_AUTO;     // KERNEL_AUTO: no apply yet
-    // apply_transformed: scratch fields + small transform, and M*1 (row sums) for the offset term
-    mutable ibh::DevBuf<double> scratch, tbuf, rowsum1;
-    mutable ibh::DevBuf<double> consv;  // force_conservation: the two dot products per variable [2*nvar] + chunk sums
-    mutable ibh::DevBuf<double> xt;     // shortrow: transposed copy of the (small) input fields
-    // rowdual (EvI, EvX): the CSR filtered to one entry per (GCM cell, ice cell) carrying the weights of
-    // BOTH elevation classes the cell lies between (assemble.hip build_bands); band r = row r
-    mutable int64_t band_n = 0;         // number of band entries, 0: not built
-    mutable ibh::DevBuf<int32_t> band_ptr, band_col, band_rb1;   // [nrow+1]; [band_n] column | bit30 lower exists | bit31 upper exists; [nrow]
-    mutable ibh::DevBuf<double> band_v0, band_v1;                // [band_n] lower-class / upper-class weight
-    // E-row matrices over ice / exchange columns can get the band structure later, from their CSR (ensure_bands):
-    // how the row keys decode into (GCM cell, class), and how many applies the matrix has seen
+    ibh::ApplyKernel kernel_override = ibh::KERNEL_AUTO;     // SpMM dispatch (ibh_weighted_set_kernel)
+    // E-row matrices over ice / exchange columns can get row groups, a column sweep or bands from their CSR (spmm.hip
+    // build_structures): set by the matrix build, with how the row keys decode into (GCM cell, class)
     int band_eligible = 0;
     int64_t band_sA = 0, band_sHC = 0;
-    mutable int band_tried = 0;
-    mutable int64_t napply = 0;
-    mutable ibh::DevBuf<double> band_part;               // per-apply partial sums [2][nvar][nrow padded]
-    // colsweep (EvI, EvX; sweep_kernel.inl): the entries in column order, paired per column into items, 64 items a block,
-    // tb blocks a task with its local row table; built lazily from the CSR (assemble.hip build_sweep_from_csr)
-    mutable int sweep_tried = 0;
-    mutable int32_t sweep_ntask = 0, sweep_nblk = 0, sweep_nprow = 0, sweep_nslot = 0;   // ntask == 0: not built
-    mutable int32_t sweep_tb = 0, sweep_nitems = 0, sweep_ident = 0;                      // blocks per task, items, column == item index
-    mutable ibh::DevBuf<int32_t> sweep_task_p0, sweep_task_ns, sweep_col;
-    mutable ibh::DevBuf<uint32_t> sweep_meta;
-    mutable ibh::DevBuf<double> sweep_v0, sweep_v1;
-    mutable ibh::DevBuf<int32_t> sweep_comb_ptr, sweep_comb_p;     // [nrow+1], [nprow]: the partial-sum rows that make up row r, in task order
-    mutable ibh::DevBuf<double> sweep_part;              // per-apply partial sums [nbatch][nprow][fields padded to 64]
-    // rowgroup (EvI, EvX; spmm.hip): the rows of one GCM cell (its elevation classes) form a GROUP; the group's entries are
-    // listed once per distinct column, ascending, as ITEMS {col, meta = slot0 | slot1 << 8 | has-bits, v0, v1} -- the column
-    // set of a group is the AvI row of its GCM cell, so X is gathered once per (GCM cell, ice cell) instead of once per class;
-    // slot s of group g is row grp_slotrow[g * IBH_GSLOTS + s].  Built from the CSR (assemble.hip build_groups_from_csr).
-    mutable int grp_tried = 0;
-    // fused pair (ibh_weighted_pair_prepare): a second matrix whose every row reads rows of ONE group of this matrix only (AvE
-    // after EvI: a GCM cell's value is a combination of that cell's elevation classes) rides in the row-group kernel's epilogue.
-    // pair_w[g * IBH_GSLOTS + s]: the second matrix's weight of slot s of group g (pair_mask[g] bit s: it has one);
-    // pair_row[g]: the second matrix's row fed by group g, -1 none.
-    mutable const ibh_weighted *pair_second = nullptr;
-    mutable uint64_t pair_uid = 0;
-    mutable ibh::DevBuf<double> pair_w;
-    mutable ibh::DevBuf<uint32_t> pair_mask;
-    mutable ibh::DevBuf<int32_t> pair_row;
-    mutable int32_t grp_n = 0, grp_nslot = 0, grp_nitems = 0;          // groups (0: not built), most rows in a group, items
-    mutable ibh::DevBuf<int32_t> grp_ptr, grp_ns, grp_slotrow, grp_col; // [grp_n+1] items of a group; [grp_n] rows of a group; [grp_n*IBH_GSLOTS]; [nitems]
-    mutable ibh::DevBuf<uint32_t> grp_meta;
-    mutable ibh::DevBuf<double> grp_v0, grp_v1;
-    // grouptile (spmm.hip): the items of a group cut into TILES of gt_seg columns; per tile the columns (padded by repeating
-    // the last) and the entries sorted by (slot, column) as {8 x local item index, weight} with u16 offsets per slot -- the rows of
-    // the CSR restricted to the tile, in CSR order.  Entries of tile t start at ibh_gt_ecap(gt_seg) * t.
-    mutable int32_t gt_ntile = 0, gt_seg = 0;            // 0: not built
-    mutable ibh::DevBuf<int32_t> gt_ptr, gt_col;         // [grp_n+1] tiles of a group; [gt_ntile * gt_seg]
-    mutable ibh::DevBuf<uint16_t> gt_ek, gt_eptr;        // [gt_ntile * ecap]; [gt_ntile * IBH_GT_EP]
-    mutable ibh::DevBuf<double> gt_ev;                   // [gt_ntile * ecap]
-    mutable bool have_rowsum1 = false;
-    mutable ibh::DevBuf<int32_t> rowperm;                // rows by descending length (batched rowblock launches)
-    mutable bool have_rowperm = false;
+    mutable ibh::ApplyState st;
     ~ibh_weighted() {
         for (int k = 0; k < 2; ++k)
             if (owns[k]) delete dims[k];
@@ -360,18 +406,18 @@ void spmm_launch(const ibh_weighted *w, const double *dA, int nvar, int64_t lda,
 void spmm_launch_many(const ibh_weighted *w, int nbatch, const double *const *dA, int nvar, int64_t lda,
                       double *const *dB, int64_t ldb, double fill, int force_conservation, hipStream_t stream);
 void weighted_reserve(const ibh_weighted *w, int nvar);
-void weighted_prepare(const ibh_weighted *w, int nvar, int nbatch);
+// groups_asked: the caller needs the row groups whatever the rules say, and no other structure (weighted_pair_prepare)
+void weighted_prepare(const ibh_weighted *w, int nvar, int nbatch, bool groups_asked = false);
 void weighted_pair_prepare(const ibh_weighted *first, const ibh_weighted *second, int nvar);
 void spmm_launch_pair(const ibh_weighted *first, const ibh_weighted *second, const double *dA, int nvar, int64_t lda, double *dB1,
                       int64_t ldb1, double *dB2, int64_t ldb2, double fill, hipStream_t stream);
 void spmm_launch_chain(const ibh_weighted *first, const ibh_weighted *second, const ibh_weighted *third, const double *dA, int nvar, int64_t lda,
                        double *dB1, int64_t ldb1, double *dB2, int64_t ldb2, double *dB3, int64_t ldb3, double fill, hipStream_t stream);
-// assemble.hip: the band structure of an E-row matrix from its CSR (same result as building it with the matrix)
-void build_bands_from_csr(const ibh_weighted *w, hipStream_t st);
-// assemble.hip: the column-sweep structure of an E-row matrix from its CSR (sweep_kernel.inl); false: not representable
-bool build_sweep_from_csr(const ibh_weighted *w, hipStream_t st);
-// assemble.hip: the row-group structure of an E-row matrix from its CSR (spmm.hip rowgroup); false: not representable
-bool build_groups_from_csr(const ibh_weighted *w, hipStream_t st);
+// assemble.hip: the apply structures of a matrix from its CSR; an unbuilt value: the matrix is not eligible or the structure not
+// representable.  The handle is only read: the caller keeps what it gets.
+Bands build_bands_from_csr(const ibh_weighted *w, hipStream_t st);      // (same result as building them with the matrix)
+Sweep build_sweep_from_csr(const ibh_weighted *w, hipStream_t st);
+RowGroups build_groups_from_csr(const ibh_weighted *w, hipStream_t st); // (with their tiles, where those fit)
 void matvec_legacy_launch(const ibh_weighted *w, const double *dx, int nvar, int64_t ldx, double *dy, int64_t ldy,
                           int ignore_nan, hipStream_t stream);
 void spmm_transformed_launch(const ibh_weighted *w, const double *dA, int nvar_in, int64_t lda, const double *T,

@@ -49,9 +49,9 @@ struct HandleScope {
     ~HandleScope() { tl_handle = prev; }
 };
 int get_tuning(const char *key, int dflt) {
-    if (tl_handle && !tl_handle->opts.empty()) {
-        auto it = tl_handle->opts.find(key);
-        if (it != tl_handle->opts.end()) return it->second;
+    if (tl_handle && !tl_handle->st.opts.empty()) {
+        auto it = tl_handle->st.opts.find(key);
+        if (it != tl_handle->st.opts.end()) return it->second;
     }
     Tuning &t = tuning();
     std::lock_guard<std::mutex> lk(t.mu);
@@ -481,8 +481,9 @@ struct GroupView {
     const double *v0, *v1;
     int ngrp, nslot;
 };
+static GroupView group_view(const RowGroups &g) { return {g.ptr.p, g.ns.p, g.slotrow.p, g.col.p, g.meta.p, g.v0.p, g.v1.p, g.n, g.nslot}; }
 constexpr unsigned RG_HAS0 = 1u << 16, RG_HAS1 = 1u << 17;
-// PAIR: a second matrix applied to this one's result in the epilogue (ibh_weighted_apply_pair_device; see ibh_weighted::pair_*)
+// PAIR: a second matrix applied to this one's result in the epilogue (ibh_weighted_apply_pair_device; see ibh::Pair)
 struct PairView {
     const double *w;
     const unsigned *mask;
@@ -491,6 +492,7 @@ struct PairView {
     double *Y2;
     long ldy2;
 };
+static PairView pair_view(const Pair &p, double *Y2, long ldy2) { return {p.w.p, p.mask.p, p.row.p, p.second->wM.p, Y2, ldy2}; }
 template <int NW, int U, int TW, bool PAIR = false>
 __global__ __launch_bounds__(NW * 64) void spmm_rowgroup_kernel(const GroupView gv, const BatchPtrs bp, long ldx, int ncol, long ldy, int nf,
                                                                int nfc, int xcd_mode, const double *__restrict__ wM, double fill,
@@ -664,6 +666,9 @@ struct TileView {
     const int *ns, *slotrow;
     int ngrp;
 };
+static TileView tile_view(const RowGroups &g) {
+    return {g.ptr.p, g.tiles.ptr.p, g.tiles.col.p, g.tiles.ek.p, g.tiles.eptr.p, g.tiles.ev.p, g.ns.p, g.slotrow.p, g.n};
+}
 constexpr int GT_UNITS = 16;         // the SP bound above: a group's units (slot, part) number max(16, ns)
 constexpr int GT_TABP = 65;          // row stride of the epilogue's table of partial sums [unit][lane]
 template <int F, int SEG>
@@ -1144,12 +1149,15 @@ void ensure_rowsum1(const ibh_weighted *w, hipStream_t stream);
 // and synchronises the device): ibh_weighted_reserve() sizes it up front; an apply that still finds a
 // buffer too small grows it after a device synchronisation (an earlier apply may be reading the old
 // block), or fails when its stream is being captured.
+static bool is_capturing(hipStream_t stream) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (stream) IBH_HIP(hipStreamIsCapturing(stream, &cs));
+    return cs != hipStreamCaptureStatusNone;
+}
 template <class T>
 static void grow_scratch(DevBuf<T> &b, size_t count, hipStream_t stream, const char *what) {
     if (b.p && count * sizeof(T) <= b.granted) { b.n = count; return; }
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (stream) IBH_HIP(hipStreamIsCapturing(stream, &cs));
-    IBH_CHECK(cs == hipStreamCaptureStatusNone,
+    IBH_CHECK(!is_capturing(stream),
               "apply inside a stream capture needs %zu more bytes of %s scratch: call ibh_weighted_reserve() before capturing",
               count * sizeof(T), what);
     if (b.p) IBH_HIP(hipDeviceSynchronize());
@@ -1171,15 +1179,14 @@ __global__ void rowperm_kernel(const int *__restrict__ rowptr, int nrow, int *__
     perm[rank] = r;
 }
 static bool ensure_rowperm(const ibh_weighted *w, hipStream_t stream) {
-    if (w->have_rowperm) return true;
+    ApplyState::Scratch &scr = w->st.scr;
+    if (scr.have_rowperm) return true;
     if (w->nrow > LPT_MAX_ROWS || w->nrow < 2) return false;
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (stream) IBH_HIP(hipStreamIsCapturing(stream, &cs));
-    if (cs != hipStreamCaptureStatusNone && !(w->rowperm.p && (size_t)w->nrow * sizeof(int) <= w->rowperm.granted)) return false;
-    grow_scratch(w->rowperm, (size_t)w->nrow, stream, "row-order");
-    hipLaunchKernelGGL(rowperm_kernel, dim3(ceil_div(w->nrow, 256)), dim3(256), 0, stream, w->rowptr.p, w->nrow, w->rowperm.p);
+    if (is_capturing(stream) && !(scr.rowperm.p && (size_t)w->nrow * sizeof(int) <= scr.rowperm.granted)) return false;
+    grow_scratch(scr.rowperm, (size_t)w->nrow, stream, "row-order");
+    hipLaunchKernelGGL(rowperm_kernel, dim3(ceil_div(w->nrow, 256)), dim3(256), 0, stream, w->rowptr.p, w->nrow, scr.rowperm.p);
     IBH_HIP(hipGetLastError());
-    w->have_rowperm = true;
+    scr.have_rowperm = true;
     return true;
 }
 
@@ -1228,12 +1235,12 @@ static void launch_rowblock(const ibh_weighted *w, const BatchPtrs &bp, int nbat
     }
     const dim3 grid((unsigned)nb, (unsigned)ceil_div(nbatch, qi));
     const int *rowperm = nullptr;
-    if (nbatch > 1 && get_tuning("rowblock_lpt", 0) && ensure_rowperm(w, stream)) rowperm = w->rowperm.p;
+    if (nbatch > 1 && get_tuning("rowblock_lpt", 0) && ensure_rowperm(w, stream)) rowperm = w->st.scr.rowperm.p;
     hipEvent_t ev0 = g_ev_start, ev1 = g_ev_stop;
     g_ev_start = g_ev_stop = nullptr;
 #define IBH_RB(U)                                                                                        \
     do {                                                                                                 \
-        snprintf(w->last_sig, sizeof(w->last_sig), "spmm_rowblock_kernel<%d, %d, %d, %d, false>", FPW, WK, (int)(U), NW);  \
+        snprintf(w->st.last_sig, sizeof(w->st.last_sig), "spmm_rowblock_kernel<%d, %d, %d, %d, false>", FPW, WK, (int)(U), NW);  \
         hipExtLaunchKernelGGL((spmm_rowblock_kernel<FPW, WK, U, NW>), grid, dim3(NW * 64), 0, stream, ev0, ev1, 0,  \
                               w->rowptr.p, w->colind.p, w->val.p, bp, nbatch, qi, lda, w->ncol, ldb, w->nrow, nvar, nfc, xcd_mode, w->wM.p, fill, \
                               (const double *)nullptr, (double *)nullptr, (const int *)rowperm, 0l);     \
@@ -1262,7 +1269,7 @@ static void launch_rowone(const ibh_weighted *w, const double *X, double *Y, int
     IBH_CHECK((long)w->ncol * 8 < (1l << 31), "ncol too large for 32-bit buffer offsets");
     hipEvent_t ev0 = g_ev_start, ev1 = g_ev_stop;
     g_ev_start = g_ev_stop = nullptr;
-    snprintf(w->last_sig, sizeof(w->last_sig), "spmm_rowone_kernel<%d, %d>", NW, U);
+    snprintf(w->st.last_sig, sizeof(w->st.last_sig), "spmm_rowone_kernel<%d, %d>", NW, U);
     hipExtLaunchKernelGGL((spmm_rowone_kernel<NW, U>), dim3((unsigned)nb), dim3(NW * 64), 0, stream, ev0, ev1, 0, w->rowptr.p, w->colind.p,
                           w->val.p, X, Y, lda, w->ncol, ldb, w->nrow, nvar, nfc, xcd_mode, w->wM.p, fill);
     IBH_HIP(hipGetLastError());
@@ -1274,11 +1281,11 @@ static void launch_rowgroup(const ibh_weighted *w, const BatchPtrs &bp, int nbat
 {
     const int nfc = ceil_div(nvar, NW);
     int xcd_mode;
-    const long nb = rowblock_grid(w->grp_n, nfc, xcd_mode);
+    const GroupView gv = group_view(w->st.groups);
+    const long nb = rowblock_grid(gv.ngrp, nfc, xcd_mode);
     IBH_CHECK(nb < (1l << 31), "spmm grid too large (%ld blocks)", nb);
     IBH_CHECK((long)w->ncol * 8 < (1l << 31), "ncol too large for 32-bit buffer offsets");
-    GroupView gv{w->grp_ptr.p, w->grp_ns.p, w->grp_slotrow.p, w->grp_col.p, w->grp_meta.p, w->grp_v0.p, w->grp_v1.p, w->grp_n, w->grp_nslot};
-    const size_t lds = (size_t)(3 * U * 64 + NW * w->grp_nslot * TW) * sizeof(double);
+    const size_t lds = (size_t)(3 * U * 64 + NW * gv.nslot * TW) * sizeof(double);
     hipEvent_t ev0 = g_ev_start, ev1 = g_ev_stop;
     g_ev_start = g_ev_stop = nullptr;
     if (lds > 64 * 1024) {                               // beyond the default dynamic-LDS limit: raise it once per device
@@ -1290,7 +1297,7 @@ static void launch_rowgroup(const ibh_weighted *w, const BatchPtrs &bp, int nbat
             raised[w->device & 63] = true;
         }
     }
-    snprintf(w->last_sig, sizeof(w->last_sig), "spmm_rowgroup_kernel<%d, %d, %d, %s>", NW, U, TW, pair ? "true" : "false");
+    snprintf(w->st.last_sig, sizeof(w->st.last_sig), "spmm_rowgroup_kernel<%d, %d, %d, %s>", NW, U, TW, pair ? "true" : "false");
     if (pair) {
         IBH_CHECK(lds <= 64 * 1024 && nbatch == 1, "fused pair apply: %zu bytes of LDS / %d batches not supported", lds, nbatch);
         hipExtLaunchKernelGGL((spmm_rowgroup_kernel<NW, U, TW, true>), dim3((unsigned)nb, 1u), dim3(NW * 64), lds, stream, ev0, ev1, 0, gv, bp,
@@ -1307,16 +1314,17 @@ static void launch_grouptile(const ibh_weighted *w, const BatchPtrs &bp, int nba
 {
     const int nfc = ceil_div(nvar, F);
     int xcd_mode;
-    const long nb = rowblock_grid(w->grp_n, nfc, xcd_mode);
+    const RowGroups &grp = w->st.groups;
+    const long nb = rowblock_grid(grp.n, nfc, xcd_mode);
     IBH_CHECK(nb < (1l << 31), "spmm grid too large (%ld blocks)", nb);
     IBH_CHECK((long)w->ncol * 8 < (1l << 31), "ncol too large for 32-bit buffer offsets");
-    IBH_CHECK(w->grp_nslot <= NS && w->gt_seg == SEG, "row groups of %d rows / tiles of %d in a kernel for %d / %d", w->grp_nslot, w->gt_seg, NS, SEG);
-    TileView tv{w->grp_ptr.p, w->gt_ptr.p, w->gt_col.p, w->gt_ek.p, w->gt_eptr.p, w->gt_ev.p, w->grp_ns.p, w->grp_slotrow.p, w->grp_n};
+    IBH_CHECK(grp.nslot <= NS && grp.tiles.seg == SEG, "row groups of %d rows / tiles of %d in a kernel for %d / %d", grp.nslot, grp.tiles.seg, NS, SEG);
+    const TileView tv = tile_view(grp);
     constexpr size_t lds = grouptile_lds<F, SEG>();
     static_assert(lds <= 64 * 1024, "within the default dynamic-LDS limit");
     hipEvent_t ev0 = g_ev_start, ev1 = g_ev_stop;
     g_ev_start = g_ev_stop = nullptr;
-    snprintf(w->last_sig, sizeof(w->last_sig), "spmm_grouptile_kernel<%d, %d, %d, %d, %s>", F, NS, SEG, NW, pair ? "true" : "false");
+    snprintf(w->st.last_sig, sizeof(w->st.last_sig), "spmm_grouptile_kernel<%d, %d, %d, %d, %s>", F, NS, SEG, NW, pair ? "true" : "false");
     if (pair) {
         IBH_CHECK(nbatch == 1, "fused pair apply: %d batches not supported", nbatch);
         hipExtLaunchKernelGGL((spmm_grouptile_kernel<F, NS, SEG, NW, true>), dim3((unsigned)nb, 1u), dim3(NW * 64), lds, stream, ev0, ev1, 0, tv, bp,
@@ -1331,8 +1339,8 @@ static void launch_grouptile(const ibh_weighted *w, const BatchPtrs &bp, int nba
 static void launch_grouptile_any(const ibh_weighted *w, const BatchPtrs &bp, int nbatch, int nvar, long lda, long ldb, double fill, hipStream_t stream,
                                  const PairView *pair = nullptr)
 {
-    const bool few = w->grp_nslot <= 16;
-    if (w->gt_seg == 128) {
+    const bool few = w->st.groups.nslot <= 16;
+    if (w->st.groups.tiles.seg == 128) {
         if (few) launch_grouptile<16, 16, 128, 4>(w, bp, nbatch, nvar, lda, ldb, fill, stream, pair);
         else launch_grouptile<16, 32, 128, 4>(w, bp, nbatch, nvar, lda, ldb, fill, stream, pair);
     } else {
@@ -1345,7 +1353,7 @@ static void launch_grouptile_any(const ibh_weighted *w, const BatchPtrs &bp, int
 // Greenland (4 M entries) 64 fields 218 against 220 us, 16 fields 82 against 74; 5 km (166 k entries: latency-bound, three
 // tiles in sequence per GCM cell) 12.4 against 7.6 and 18.1 against 17.4 us.  ibh_set_tuning("rowgroup_form", 0 / 1) forces one.
 static bool use_grouptile(const ibh_weighted *w, int nvar) {
-    if (w->gt_ntile <= 0) return false;
+    if (!w->st.groups.tiles.built()) return false;
     const int form = get_tuning("rowgroup_form", -1);
     if (form >= 0) return form == 1;
     return w->nnz >= (1l << 24) || (w->nnz >= (1l << 21) && nvar >= 48);
@@ -1364,10 +1372,6 @@ __global__ void dual_combine_kernel(const double *__restrict__ P0, const double 
     bp.y[q][(long)f * ldy + r] = wM[r] == 0.0 ? fill : t;
 }
 
-static size_t band_part_count(const ibh_weighted *w, int nvar, int nbatch) {
-    const long ldp = ((long)w->nrow + 63) & ~63l;
-    return 2 * (size_t)nbatch * (size_t)nvar * (size_t)ldp;
-}
 template <int FPW>
 static void launch_rowdual(const ibh_weighted *w, const BatchPtrs &bp, int nbatch, int nvar, long lda, long ldb,
                            double fill, hipStream_t stream)
@@ -1378,33 +1382,30 @@ static void launch_rowdual(const ibh_weighted *w, const BatchPtrs &bp, int nbatc
     const long nb = rowblock_grid(w->nrow, nfc, xcd_mode);
     IBH_CHECK(nb < (1l << 31), "spmm grid too large (%ld blocks)", nb);
     IBH_CHECK((long)w->ncol * 8 < (1l << 31), "ncol too large for 32-bit buffer offsets");
-    const long ldp = ((long)w->nrow + 63) & ~63l;
-    const long pstride = (long)nvar * ldp;                       // one batch's lower (or upper) partial sums
-    grow_scratch(w->band_part, band_part_count(w, nvar, nbatch), stream, "band");
-    double *P0 = w->band_part.p, *P1 = P0 + (size_t)nbatch * (size_t)pstride;
+    const Bands &bands = w->st.bands;
+    const long ldp = bands.part_ld(), pstride = bands.part_stride(nvar);
+    grow_scratch(w->st.scr.band_part, bands.part_count(nvar, nbatch), stream, "band");
+    double *P0 = w->st.scr.band_part.p, *P1 = P0 + (size_t)nbatch * (size_t)pstride;
     int unroll = get_tuning("rowdual_unroll", 0);
     if (unroll <= 0) {
-        const double mean = w->nrow ? (double)w->band_n / (double)w->nrow / 64.0 : 1.0;
+        const double mean = w->nrow ? (double)bands.n / (double)w->nrow / 64.0 : 1.0;
         unroll = mean > 4.0 ? 8 : mean > 2.0 ? 4 : mean > 1.0 ? 2 : 1;
     }
     BatchPtrs bq{};
     for (int q = 0; q < nbatch; ++q) { bq.x[q] = bp.x[q]; bq.y[q] = P0 + (size_t)q * (size_t)pstride; }
     const dim3 grid((unsigned)nb, (unsigned)nbatch);
 #define IBH_RD(U)                                                                                                  \
-    snprintf(w->last_sig, sizeof(w->last_sig), "spmm_rowblock_kernel<%d, 1, %d, %d, true>", FPW, (int)(U), NW);     \
+    snprintf(w->st.last_sig, sizeof(w->st.last_sig), "spmm_rowblock_kernel<%d, 1, %d, %d, true>", FPW, (int)(U), NW);     \
     hipLaunchKernelGGL((spmm_rowblock_kernel<FPW, 1, U, NW, true>), grid, dim3(NW * 64), 0, stream,                 \
-                       w->band_ptr.p, w->band_col.p, w->band_v0.p, bq, nbatch, 1, lda, w->ncol, ldp, w->nrow, nvar, nfc, xcd_mode, \
-                       w->wM.p, fill, w->band_v1.p, P1, (const int *)nullptr, pstride)
+                       bands.ptr.p, bands.col.p, bands.v0.p, bq, nbatch, 1, lda, w->ncol, ldp, w->nrow, nvar, nfc, xcd_mode,       \
+                       w->wM.p, fill, bands.v1.p, P1, (const int *)nullptr, pstride)
     if (unroll == 1) { IBH_RD(1); } else if (unroll == 2) { IBH_RD(2); } else if (unroll == 8) { IBH_RD(8); } else { IBH_RD(4); }
 #undef IBH_RD
     hipLaunchKernelGGL(dual_combine_kernel, dim3((unsigned)ceil_div(w->nrow, 256), (unsigned)nvar, (unsigned)nbatch), dim3(256), 0, stream,
-                       P0, P1, ldp, pstride, w->band_rb1.p, w->wM.p, fill, bp, ldb, w->nrow, nvar);
+                       P0, P1, ldp, pstride, bands.rb1.p, w->wM.p, fill, bp, ldb, w->nrow, nvar);
     IBH_HIP(hipGetLastError());
 }
 
-// fields per lane group of the sweep: 64 (one batch per wave row) from 33 fields; below, the next power of two >= 8 so that
-// 64 / nfl batches share the lanes
-static int sweep_lg(int nvar) { return nvar > 32 ? 6 : nvar > 16 ? 5 : nvar > 8 ? 4 : 3; }
 // lanes of the sweep that carry a (batch, field) pair for nvar fields in launches of nbatch
 static int sweep_lanes(int nvar, int nbatch) { return nvar > 32 ? 64 : nvar * std::min(nbatch, 64 >> sweep_lg(nvar)); }
 // ---- colsweep (sweep_kernel.inl): E-row matrices, >= 32 fields ------------------------------------------------
@@ -1441,29 +1442,23 @@ __global__ __launch_bounds__(256) void sweep_combine_kernel(const double *__rest
     for (; k < k1; ++k) tot += p[(long)comb_p[k] * ldp];
     bp.y[q][(long)f * ldy + r] = wM[r] == 0.0 ? fill : tot;
 }
-// fields per lane group of the sweep: 64 (one batch per wave row) from 33 fields; below, the next power of two >= 8 so that
-// 64 / nfl batches share the lanes
-static size_t sweep_part_count(const ibh_weighted *w, int nvar, int nbatch) {
-    const int lg = sweep_lg(nvar);
-    const size_t slices = lg == 6 ? (size_t)nbatch : (size_t)ceil_div(nbatch, 64 >> lg);
-    const size_t ldp = lg == 6 ? (size_t)ceil_div(nvar, 64) * 64 : 64;
-    return slices * (size_t)w->sweep_nprow * ldp;
-}
+static SweepView sweep_view(const Sweep &s) { return {s.task_p0.p, s.task_ns.p, s.col.p, s.meta.p, s.v0.p, s.v1.p, s.tb, s.nblk, s.nitems}; }
 static void launch_sweep(const ibh_weighted *w, const BatchPtrs &bp, int nbatch, int nvar, long lda, long ldb, double fill,
                          hipStream_t stream)
 {
+    const Sweep &sweep = w->st.sweep;
+    DevBuf<double> &part = w->st.scr.sweep_part;
     const int lg = sweep_lg(nvar), G = 64 >> lg;
     const int nfb = lg == 6 ? ceil_div(nvar, 64) : 1, nz = lg == 6 ? nbatch : ceil_div(nbatch, G);
-    const long ldp = (long)nfb * 64, pstride = (long)w->sweep_nprow * ldp;
-    grow_scratch(w->sweep_part, sweep_part_count(w, nvar, nbatch), stream, "column-sweep");
-    SweepView sv{w->sweep_task_p0.p, w->sweep_task_ns.p, w->sweep_col.p, w->sweep_meta.p, w->sweep_v0.p, w->sweep_v1.p,
-                 w->sweep_tb, w->sweep_nblk, w->sweep_nitems};
+    const long ldp = sweep.part_ld(nvar), pstride = sweep.part_stride(nvar);
+    grow_scratch(part, sweep.part_count(nvar, nbatch), stream, "column-sweep");
+    const SweepView sv = sweep_view(sweep);
     SweepBatch sb{};
     for (int q = 0; q < nbatch; ++q) sb.x[q] = bp.x[q];
-    for (int zz = 0; zz < nz; ++zz) sb.p[zz] = w->sweep_part.p + (size_t)zz * (size_t)pstride;
-    const size_t lds = sweep_lds_bytes(w->sweep_nslot);
+    for (int zz = 0; zz < nz; ++zz) sb.p[zz] = part.p + (size_t)zz * (size_t)pstride;
+    const size_t lds = sweep_lds_bytes(sweep.nslot);
     const bool full = lg == 6 ? nvar % 64 == 0 : (nvar == (1 << lg) && nbatch % G == 0);
-    const bool ident = w->sweep_ident != 0;
+    const bool ident = sweep.ident != 0;
     const void *fn = full ? (ident ? reinterpret_cast<const void *>(spmm_sweep_kernel<true, true, 0>) : reinterpret_cast<const void *>(spmm_sweep_kernel<true, false, 0>))
                           : (ident ? reinterpret_cast<const void *>(spmm_sweep_kernel<false, true, 0>) : reinterpret_cast<const void *>(spmm_sweep_kernel<false, false, 0>));
     if (lds > 64 * 1024) {                               // beyond the default dynamic-LDS limit: raise it once per device and variant
@@ -1476,17 +1471,17 @@ static void launch_sweep(const ibh_weighted *w, const BatchPtrs &bp, int nbatch,
             raised[dev][var] = true;
         }
     }
-    const dim3 grid((unsigned)w->sweep_ntask, (unsigned)nfb, (unsigned)nz);
+    const dim3 grid((unsigned)sweep.ntask, (unsigned)nfb, (unsigned)nz);
     hipEvent_t ev0 = g_ev_start, ev1 = g_ev_stop;
     g_ev_start = g_ev_stop = nullptr;
     // launch timing: start = the sweep kernel begins, stop = the combine kernel ends (both belong to the apply)
-#define IBH_SW(F, I) snprintf(w->last_sig, sizeof(w->last_sig), "%s", "spmm_sweep_kernel<" #F ", " #I ", 0>"); \
-                     hipExtLaunchKernelGGL((spmm_sweep_kernel<F, I, 0>), grid, dim3(SWEEP_NW * 64), lds, stream, ev0, nullptr, 0, sv, sb, lda, nvar, w->sweep_nslot, ldp, lg, nbatch)
+#define IBH_SW(F, I) snprintf(w->st.last_sig, sizeof(w->st.last_sig), "%s", "spmm_sweep_kernel<" #F ", " #I ", 0>"); \
+                     hipExtLaunchKernelGGL((spmm_sweep_kernel<F, I, 0>), grid, dim3(SWEEP_NW * 64), lds, stream, ev0, nullptr, 0, sv, sb, lda, nvar, sweep.nslot, ldp, lg, nbatch)
     if (full) { if (ident) { IBH_SW(true, true); } else { IBH_SW(true, false); } }
     else { if (ident) { IBH_SW(false, true); } else { IBH_SW(false, false); } }
 #undef IBH_SW
     hipExtLaunchKernelGGL(sweep_combine_kernel, dim3((unsigned)ceil_div(w->nrow, 4), (unsigned)nfb, (unsigned)nbatch), dim3(256), 0, stream, nullptr, ev1, 0,
-                       w->sweep_part.p, pstride, ldp, w->sweep_comb_ptr.p, w->sweep_comb_p.p, w->wM.p, fill,
+                       part.p, pstride, ldp, sweep.comb_ptr.p, sweep.comb_p.p, w->wM.p, fill,
                        bp, ldb, w->nrow, nvar, lg);
     IBH_HIP(hipGetLastError());
 }
@@ -1494,7 +1489,7 @@ static void launch_sweep(const ibh_weighted *w, const BatchPtrs &bp, int nbatch,
 // which kernel serves (w, nvar)
 static ApplyKernel pick_kernel(const ibh_weighted *w, int nvar, int nbatch = 1) {
     ApplyKernel kernel = w->kernel_override;
-    if (kernel == KERNEL_COLSWEEP && w->sweep_ntask == 0) kernel = KERNEL_AUTO;       // no column-sweep structure: the automatic choice
+    if (kernel == KERNEL_COLSWEEP && !w->st.sweep.built()) kernel = KERNEL_AUTO;      // no column-sweep structure: the automatic choice
     if (kernel == KERNEL_AUTO) {
         // rowblock = one workgroup per (row, field chunk): for FEW LONG rows.  Many rows of 6..63 entries (a smoothed IvE:
         // 76 k rows of ~16) are thread-per-row work (measured, 5 km smoothed IvE, 16 fields: 220 us as rowblock)
@@ -1511,19 +1506,19 @@ static ApplyKernel pick_kernel(const ibh_weighted *w, int nvar, int nbatch = 1) 
         // (round 4, the Antarctic sheet -- 17.6 / 35.2 M entries -- one apply per launch: AvI, 128 fields, sweep 3 131 against 3 654 us;
         // EvI, 16 fields, row groups 641 against 812 (bands) / 747 (rows) / 1 994 us (sweep): scratch/kernel_choice.py)
         const bool huge = w->nnz >= (1l << 24);
-        const bool sweep_ok = w->sweep_ntask > 0 && sweep_lanes(nvar, nbatch) >= get_tuning("sweep_min_nvar", 32) && get_tuning("sweep_auto", 1) &&
+        const bool sweep_ok = w->st.sweep.built() && sweep_lanes(nvar, nbatch) >= get_tuning("sweep_min_nvar", 32) && get_tuning("sweep_auto", 1) &&
                               (w->band_eligible || nbatch >= get_tuning("sweep_min_batch", 4) || (huge && nvar >= 128));
-        const bool grp_ok = w->grp_n > 0 && nvar >= 4 && get_tuning("rowgroup_auto", 1);
+        const bool grp_ok = w->st.groups.built() && nvar >= 4 && get_tuning("rowgroup_auto", 1);
         // (round 5: on matrices of 2^24 entries and more the tiled row groups beat the sweep in batched launches of few fields too --
         // the Antarctic EvI, 16 fields, batches of 4: bench.py 0.487 of peak through the sweep, measured again below)
-        const bool tiles_win = w->gt_ntile > 0 && w->nnz >= (1l << 24) && get_tuning("rowgroup_form", -1) != 0;
+        const bool tiles_win = w->st.groups.tiles.built() && w->nnz >= (1l << 24) && get_tuning("rowgroup_form", -1) != 0;
         if (grp_ok && (nvar >= 32 || !sweep_ok || tiles_win)) kernel = KERNEL_ROWGROUP;
         else if (sweep_ok) kernel = KERNEL_COLSWEEP;
     }
-    if (kernel == KERNEL_ROWGROUP && w->grp_n == 0) kernel = KERNEL_ROWBLOCK;             // no row groups were built for this matrix
-    if (kernel == KERNEL_ROWBLOCK && w->kernel_override == KERNEL_AUTO && w->band_n > 0 && nvar >= 4 && get_tuning("rowdual_auto", 1))
+    if (kernel == KERNEL_ROWGROUP && !w->st.groups.built()) kernel = KERNEL_ROWBLOCK;     // no row groups were built for this matrix
+    if (kernel == KERNEL_ROWBLOCK && w->kernel_override == KERNEL_AUTO && w->st.bands.built() && nvar >= 4 && get_tuning("rowdual_auto", 1))
         kernel = KERNEL_ROWDUAL;
-    if (kernel == KERNEL_ROWDUAL && w->band_n == 0) kernel = KERNEL_ROWBLOCK;            // no bands were built for this matrix
+    if (kernel == KERNEL_ROWDUAL && !w->st.bands.built()) kernel = KERNEL_ROWBLOCK;       // no bands were built for this matrix
     return kernel;
 }
 struct ShortrowPlan { int fper, g, use_xt, ldt; bool one_entry, big; };
@@ -1567,17 +1562,17 @@ static ShortrowPlan shortrow_plan(const ibh_weighted *w, int nvar, int nbatch = 
 // `seen` = the matrix has been applied before (an apply builds on the SECOND call only: the coupler's one build : one apply
 // must not pay for a structure it never reuses; ibh_weighted_prepare builds at once).
 static bool wants_sweep(const ibh_weighted *w, int nvar, int nbatch, bool seen) {
-    if (w->sweep_tried || w->sweep_ntask > 0) return false;
+    if (w->st.sweep_tried || w->st.sweep.built()) return false;
     if (w->kernel_override == KERNEL_COLSWEEP) return true;
     const bool long_rows = w->nrow > 0 && (double)w->nnz / (double)w->nrow >= 64.0 && w->nnz <= 2 * (int64_t)w->ncol;      // AvI, AvX
-    const bool e_rows = w->band_eligible && (nvar < 32 || (w->grp_tried && w->grp_n == 0) || !get_tuning("rowgroup_auto", 1));
+    const bool e_rows = w->band_eligible && (nvar < 32 || (w->st.groups_tried && !w->st.groups.built()) || !get_tuning("rowgroup_auto", 1));
     const bool huge_wide = w->nnz >= (1l << 24) && nvar >= 128;      // (one launch of >= 128 fields on the Antarctic AvI: see launch_kernel_for)
     return (e_rows || (long_rows && (nbatch >= get_tuning("sweep_min_batch", 4) || huge_wide))) && w->kernel_override == KERNEL_AUTO && seen &&
            sweep_lanes(nvar, nbatch) >= get_tuning("sweep_min_nvar", 32) && get_tuning("sweep_auto", 1) &&
            (double)w->nnz * sweep_lanes(nvar, nbatch) >= (double)get_tuning("sweep_min_work", 64 << 20);
 }
 static bool wants_bands(const ibh_weighted *w, int nvar, bool seen) {
-    return w->band_eligible && !w->band_tried && w->band_n == 0 && w->sweep_ntask == 0 && seen && w->kernel_override == KERNEL_AUTO && nvar >= 4 &&
+    return w->band_eligible && !w->st.bands_tried && !w->st.bands.built() && !w->st.sweep.built() && seen && w->kernel_override == KERNEL_AUTO && nvar >= 4 &&
            (double)w->nnz * nvar >= (double)get_tuning("rowdual_min_work", 128 << 20) && get_tuning("rowdual_auto", 1);
 }
 // Row groups (rowgroup kernel) of an E-row matrix: bandwidth-sized matrices applied to >= 32 fields get them like the sweep
@@ -1589,73 +1584,54 @@ static bool wants_bands(const ibh_weighted *w, int nvar, bool seen) {
 static bool sweep_sized(const ibh_weighted *w, int nvar, int nbatch) {
     return (double)w->nnz * std::max(sweep_lanes(nvar, nbatch), std::min(nvar, 64)) >= (double)get_tuning("sweep_min_work", 64 << 20);
 }
-static bool wants_groups(const ibh_weighted *w, int nvar, int nbatch, long seen) {
-    if (!w->band_eligible || w->grp_tried || w->grp_n > 0) return false;
-    if (w->kernel_override == KERNEL_ROWGROUP) return true;
+static bool wants_groups(const ibh_weighted *w, int nvar, int nbatch, long seen, bool asked) {
+    if (!w->band_eligible || w->st.groups_tried || w->st.groups.built()) return false;
+    if (asked || w->kernel_override == KERNEL_ROWGROUP) return true;
     if (w->kernel_override != KERNEL_AUTO || nvar < 4 || !get_tuning("rowgroup_auto", 1)) return false;
     // (bandwidth-sized matrices: from 32 fields -- fewer fields per launch share the lanes of the column sweep when launches are
     // batched; a single launch of a 2^24-entry matrix takes the groups from 4 fields on)
     if (sweep_sized(w, nvar, nbatch)) return (nvar >= 32 || (nbatch < 4 && w->nnz >= (1l << 24))) && seen >= 1;
     return seen >= get_tuning("rowgroup_after", 1 << 30);
 }
-static void drop_groups(const ibh_weighted *w) {
-    w->grp_n = 0;
-    w->pair_second = nullptr;                                 // (a pairing indexes the group table)
-    w->grp_ptr.release(); w->grp_ns.release(); w->grp_slotrow.release(); w->grp_col.release(); w->grp_meta.release();
-    w->grp_v0.release(); w->grp_v1.release();
-    w->gt_ntile = 0; w->gt_seg = 0;
-    w->gt_ptr.release(); w->gt_col.release(); w->gt_ek.release(); w->gt_eptr.release(); w->gt_ev.release();
-}
-static void drop_sweep(const ibh_weighted *w) {
-    w->sweep_ntask = 0;
-    w->sweep_task_p0.release(); w->sweep_task_ns.release(); w->sweep_col.release(); w->sweep_meta.release();
-    w->sweep_v0.release(); w->sweep_v1.release(); w->sweep_comb_ptr.release(); w->sweep_comb_p.release();
-}
-static void drop_bands(const ibh_weighted *w) {
-    w->band_n = 0;
-    w->band_ptr.release(); w->band_col.release(); w->band_rb1.release(); w->band_v0.release(); w->band_v1.release();
-}
 // A structure that cannot be built (out of memory, not representable) is no reason to fail an apply the row-by-row kernel
 // serves: the failure is swallowed, the structure marked as tried, the matrix keeps its kernel.  Never inside a capture.
-static void build_structures(const ibh_weighted *w, int nvar, int nbatch, bool seen, hipStream_t stream, long nseen = 1l << 30) {
+// `groups_asked`: the caller needs the row groups whatever the rules say (ibh_weighted_pair_prepare), and nothing else.
+static void build_structures(const ibh_weighted *w, int nvar, int nbatch, bool seen, hipStream_t stream, long nseen = 1l << 30,
+                             bool groups_asked = false) {
+    ApplyState &st = w->st;
     const long ns = seen ? nseen : 0;
-    if (!wants_groups(w, nvar, nbatch, ns) && !wants_sweep(w, nvar, nbatch, seen) && !wants_bands(w, nvar, seen)) return;
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (stream) IBH_HIP(hipStreamIsCapturing(stream, &cs));
-    if (cs != hipStreamCaptureStatusNone) return;
-    if (wants_groups(w, nvar, nbatch, ns)) {
-        w->grp_tried = 1;
-        try { (void)build_groups_from_csr(w, stream); }
-        catch (const Error &) { (void)hipGetLastError(); drop_groups(w); }
-    }
-    if (wants_sweep(w, nvar, nbatch, seen)) {           // (also: an E-row matrix whose groups were declined just now)
-        w->sweep_tried = 1;
-        try { (void)build_sweep_from_csr(w, stream); }
-        catch (const Error &) { (void)hipGetLastError(); drop_sweep(w); }
-    }
-    if (w->grp_n == 0 && wants_bands(w, nvar, seen)) {
-        w->band_tried = 1;
-        try { build_bands_from_csr(w, stream); }
-        catch (const Error &) { (void)hipGetLastError(); drop_bands(w); }
-    }
+    auto groups = [&] { return wants_groups(w, nvar, nbatch, ns, groups_asked); };
+    auto sweep = [&] { return !groups_asked && wants_sweep(w, nvar, nbatch, seen); };
+    auto bands = [&] { return !groups_asked && !st.groups.built() && wants_bands(w, nvar, seen); };
+    if ((!groups() && !sweep() && !bands()) || is_capturing(stream)) return;
+    // (a builder hands over a finished structure or none: nothing to undo when it throws)
+    auto attempt = [](bool &tried, auto &&build) {
+        tried = true;
+        try { build(); } catch (const Error &) { (void)hipGetLastError(); }
+    };
+    if (groups()) attempt(st.groups_tried, [&] { st.groups = build_groups_from_csr(w, stream); });
+    if (sweep()) attempt(st.sweep_tried, [&] { st.sweep = build_sweep_from_csr(w, stream); });      // (also: an E-row matrix whose groups were declined just now)
+    if (bands()) attempt(st.bands_tried, [&] { st.bands = build_bands_from_csr(w, stream); });
 }
 
 // Scratch of every kernel that applies of (nvar, <= nbatch per launch) can pick -- all of them: a later
 // ibh_weighted_set_kernel, or a tuning change, must not turn a captured apply into an allocation.
+static size_t consv_count(const ibh_weighted *w, int nvar) { return 2 * (size_t)nvar + weight_dot_scratch(std::max(w->nrow, w->ncol), nvar); }
 static void size_scratch(const ibh_weighted *w, int nvar, int nbatch) {
-    if (w->band_n > 0) grow_scratch(w->band_part, band_part_count(w, nvar, nbatch), nullptr, "band");
-    if (w->sweep_ntask > 0) grow_scratch(w->sweep_part, sweep_part_count(w, nvar, nbatch), nullptr, "column-sweep");
+    ApplyState &st = w->st;
+    if (st.bands.built()) grow_scratch(st.scr.band_part, st.bands.part_count(nvar, nbatch), nullptr, "band");
+    if (st.sweep.built()) grow_scratch(st.scr.sweep_part, st.sweep.part_count(nvar, nbatch), nullptr, "column-sweep");
     if (pick_kernel(w, nvar, nbatch) == KERNEL_SHORTROW || pick_kernel(w, nvar, 1) == KERNEL_SHORTROW || w->kernel_override == KERNEL_AUTO) {
         for (int nb : {1, nbatch}) {
             const ShortrowPlan p = shortrow_plan(w, nvar, nb);
             const int qmax = std::max(1, get_tuning("shortrow_many", w->nrow >= (1 << 19) ? 1 : IBH_MAX_BATCH));
             if (p.use_xt && (pick_kernel(w, nvar, nb) == KERNEL_SHORTROW || w->kernel_override == KERNEL_SHORTROW))
-                grow_scratch(w->xt, (size_t)w->ncol * (size_t)p.ldt * (size_t)std::min(qmax, nb), nullptr, "transposed-input");
+                grow_scratch(st.scr.xt, (size_t)w->ncol * (size_t)p.ldt * (size_t)std::min(qmax, nb), nullptr, "transposed-input");
         }
     }
-    grow_scratch(w->consv, 2 * (size_t)nvar + weight_dot_scratch(std::max(w->nrow, w->ncol), nvar), nullptr, "conservation");
+    grow_scratch(st.scr.consv, consv_count(w, nvar), nullptr, "conservation");
     // apply_transformed: the small side holds nvar fields
-    grow_scratch(w->scratch, (size_t)nvar * (size_t)std::min(w->nrow, w->ncol), nullptr, "transform");
+    grow_scratch(st.scr.scratch, (size_t)nvar * (size_t)std::min(w->nrow, w->ncol), nullptr, "transform");
     ensure_rowsum1(w, nullptr);
     if (get_tuning("rowblock_lpt", 0)) (void)ensure_rowperm(w, nullptr);
 }
@@ -1666,11 +1642,11 @@ void weighted_reserve(const ibh_weighted *w, int nvar) {
     size_scratch(w, nvar, 1);
 }
 
-void weighted_prepare(const ibh_weighted *w, int nvar, int nbatch) {
+void weighted_prepare(const ibh_weighted *w, int nvar, int nbatch, bool groups_asked) {
     HandleScope hs_(w);
     if (nvar <= 0 || nbatch <= 0 || w->nrow == 0) return;
     const int nb = std::min(nbatch, IBH_MAX_BATCH);           // deeper batches are split into launches of IBH_MAX_BATCH
-    build_structures(w, nvar, nb, true, nullptr);
+    build_structures(w, nvar, nb, true, nullptr, 1l << 30, groups_asked);
     size_scratch(w, nvar, nb);
     IBH_HIP(hipStreamSynchronize(nullptr));
 }
@@ -1686,19 +1662,15 @@ void weighted_pair_prepare(const ibh_weighted *first, const ibh_weighted *second
     IBH_CHECK(first->device == second->device, "pair: matrices live on different devices");
     IBH_CHECK(second->ncol == first->nrow || second->dims[1], "pair: the second matrix's columns are not the first one's rows");
     IBH_CHECK(second->nnz <= (1 << 22), "pair: the second matrix is too large (%ld entries) to be paired on the host", (long)second->nnz);
-    first->pair_second = nullptr;
-    if (first->grp_n == 0) {                                  // row groups first (small matrices get them from an explicit request only)
-        const ApplyKernel keep = first->kernel_override;
-        const_cast<ibh_weighted *>(first)->kernel_override = KERNEL_ROWGROUP;
-        try { weighted_prepare(first, nvar > 0 ? nvar : 16, 1); } catch (...) { const_cast<ibh_weighted *>(first)->kernel_override = keep; throw; }
-        const_cast<ibh_weighted *>(first)->kernel_override = keep;
-    }
-    if (first->grp_n == 0) fail(IBH_ENOTIMPL, "pair: the first matrix has no row groups (not an elevation-class-row matrix, or its structure was declined)");
-    const int ngrp = first->grp_n;
+    RowGroups &grp = first->st.groups;
+    grp.pair = {};
+    if (!grp.built()) weighted_prepare(first, nvar > 0 ? nvar : 16, 1, true);       // row groups first (small matrices get them from an explicit request only)
+    if (!grp.built()) fail(IBH_ENOTIMPL, "pair: the first matrix has no row groups (not an elevation-class-row matrix, or its structure was declined)");
+    const int ngrp = grp.n;
     std::vector<int32_t> slotrow((size_t)ngrp * IBH_GSLOTS), gns((size_t)ngrp), rp2((size_t)second->nrow + 1), ci2((size_t)second->nnz);
     std::vector<double> v2((size_t)second->nnz);
-    IBH_HIP(hipMemcpy(slotrow.data(), first->grp_slotrow.p, slotrow.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-    IBH_HIP(hipMemcpy(gns.data(), first->grp_ns.p, gns.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    IBH_HIP(hipMemcpy(slotrow.data(), grp.slotrow.p, slotrow.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    IBH_HIP(hipMemcpy(gns.data(), grp.ns.p, gns.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
     IBH_HIP(hipMemcpy(rp2.data(), second->rowptr.p, rp2.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
     if (second->nnz) {
         IBH_HIP(hipMemcpy(ci2.data(), second->colind.p, ci2.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
@@ -1742,19 +1714,41 @@ void weighted_pair_prepare(const ibh_weighted *first, const ibh_weighted *second
         if (pr[(size_t)grp] >= 0) fail(IBH_ENOTIMPL, "pair: two rows of the second matrix read the same group of the first");
         pr[(size_t)grp] = a;
     }
-    first->pair_w.alloc(pw.size()); first->pair_mask.alloc(pm.size()); first->pair_row.alloc(pr.size());
-    IBH_HIP(hipMemcpy(first->pair_w.p, pw.data(), pw.size() * sizeof(double), hipMemcpyHostToDevice));
-    IBH_HIP(hipMemcpy(first->pair_mask.p, pm.data(), pm.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    IBH_HIP(hipMemcpy(first->pair_row.p, pr.data(), pr.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    first->pair_second = second;
-    first->pair_uid = second->uid;
+    Pair pair;
+    pair.w.alloc(pw.size()); pair.mask.alloc(pm.size()); pair.row.alloc(pr.size());
+    IBH_HIP(hipMemcpy(pair.w.p, pw.data(), pw.size() * sizeof(double), hipMemcpyHostToDevice));
+    IBH_HIP(hipMemcpy(pair.mask.p, pm.data(), pm.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    IBH_HIP(hipMemcpy(pair.row.p, pr.data(), pr.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    pair.second = second;
+    pair.uid = second->uid;
+    grp.pair = std::move(pair);
+}
+
+// The row-group apply in whichever form and instantiation serves (w, nvar); `pair`: with the second matrix of a fused pair in
+// the epilogue.
+static void launch_rowgroup_any(const ibh_weighted *w, const BatchPtrs &bp, int nbatch, int nvar, long lda, long ldb, double fill, hipStream_t stream,
+                                const PairView *pair = nullptr)
+{
+    if (use_grouptile(w, nvar)) return launch_grouptile_any(w, bp, nbatch, nvar, lda, ldb, fill, stream, pair);
+    // 8 waves (fields) share a staged segment from 32 fields (5 km, 64 fields: 17.1 against 19.3 us with 4)
+    const int u = get_tuning("rowgroup_unroll", 8), nw = get_tuning("rowgroup_waves", nvar >= 32 ? 8 : 4);
+    // class tables of half width (two lanes per entry) for the small matrices: all workgroups of a 5 km launch fit the LDS at
+    // once -- 16 applies per launch 13.5 -> 12.3 us (64 fields), 3.96 -> 3.37 (16 fields), one launch unchanged (17.6 / 17.8);
+    // at 1 km the doubled atomic instructions cost 223 -> 238 us.  By the matrix alone, so one apply and a batch agree bitwise.
+    const int tw = get_tuning("rowgroup_tw", w->nnz < (1 << 20) ? 32 : 64);
+#define IBH_RG(N, UU, TT) launch_rowgroup<N, UU, TT>(w, bp, nbatch, nvar, lda, ldb, fill, stream, pair)
+    if (tw == 32) { if (nw == 8) { if (u <= 8) IBH_RG(8, 8, 32); else IBH_RG(8, 16, 32); } else { if (u <= 4) IBH_RG(4, 4, 32); else IBH_RG(4, 8, 32); } }
+    else if (nw == 8) { if (u <= 8) IBH_RG(8, 8, 64); else IBH_RG(8, 16, 64); }
+    else { if (u <= 4) IBH_RG(4, 4, 64); else if (u <= 8) IBH_RG(4, 8, 64); else IBH_RG(4, 16, 64); }
+#undef IBH_RG
 }
 
 void spmm_launch_pair(const ibh_weighted *first, const ibh_weighted *second, const double *dA, int nvar, int64_t lda, double *dB1,
                       int64_t ldb1, double *dB2, int64_t ldb2, double fill, hipStream_t stream)
 {
     HandleScope hs_(first);
-    IBH_CHECK(first->pair_second == second && first->pair_uid == second->uid && first->grp_n > 0,
+    const Pair &pair = first->st.groups.pair;
+    IBH_CHECK(pair.second == second && pair.uid == second->uid && first->st.groups.built(),
               "pair apply: call ibh_weighted_pair_prepare(first, second, nvar) first");
     if (nvar <= 0 || first->nrow == 0) return;
     IBH_CHECK(lda >= first->ncol && ldb1 >= first->nrow && ldb2 >= second->nrow, "pair apply: leading dimensions (%ld, %ld, %ld) too small",
@@ -1762,20 +1756,11 @@ void spmm_launch_pair(const ibh_weighted *first, const ibh_weighted *second, con
     IBH_CHECK(first->conservative && second->conservative, "pair apply: smoothed (non-conservative) matrices take separate applies");
     BatchPtrs bp{};
     bp.x[0] = dA; bp.y[0] = dB1;
-    const PairView pv{first->pair_w.p, first->pair_mask.p, first->pair_row.p, second->wM.p, dB2, (long)ldb2};
-    // (the unit choices of launch_one_impl's row-group branch: the pair launch takes the same instantiations)
-    const int u = get_tuning("rowgroup_unroll", 8), nw = get_tuning("rowgroup_waves", nvar >= 32 ? 8 : 4);
-    const int tw = get_tuning("rowgroup_tw", first->nnz < (1 << 20) ? 32 : 64);
-#define IBH_RGP(N, UU, TT) launch_rowgroup<N, UU, TT>(first, bp, 1, nvar, (long)lda, (long)ldb1, fill, stream, &pv)
-    if (use_grouptile(first, nvar)) {
-        launch_grouptile_any(first, bp, 1, nvar, (long)lda, (long)ldb1, fill, stream, &pv);
-    } else if (tw == 32) { if (nw == 8) { if (u <= 8) IBH_RGP(8, 8, 32); else IBH_RGP(8, 16, 32); } else { if (u <= 4) IBH_RGP(4, 4, 32); else IBH_RGP(4, 8, 32); } }
-    else if (nw == 8) { if (u <= 8) IBH_RGP(8, 8, 64); else IBH_RGP(8, 16, 64); }
-    else { if (u <= 4) IBH_RGP(4, 4, 64); else if (u <= 8) IBH_RGP(4, 8, 64); else IBH_RGP(4, 16, 64); }
-#undef IBH_RGP
-    first->last_kernel = KERNEL_ROWGROUP;
-    second->last_kernel = KERNEL_ROWGROUP;
-    ++first->napply; ++second->napply;
+    const PairView pv = pair_view(pair, dB2, (long)ldb2);
+    launch_rowgroup_any(first, bp, 1, nvar, (long)lda, (long)ldb1, fill, stream, &pv);
+    first->st.last_kernel = KERNEL_ROWGROUP;
+    second->st.last_kernel = KERNEL_ROWGROUP;
+    ++first->st.napply; ++second->st.napply;
 }
 // B1 = first * A, B2 = second * B1 (the fused pair), B3 = third * B2: the chain ice -> elevation classes -> atmosphere -> ice of
 // BASELINE config 3 (EvI, AvE, IvA): the pair launch and the third matrix's apply, stream-ordered.
@@ -1809,19 +1794,7 @@ static void launch_one_impl(const ibh_weighted *w, ApplyKernel kernel, const Bat
                             int64_t ldb, double fill, hipStream_t stream)
 {
     if (kernel == KERNEL_ROWGROUP) {
-        // 8 waves (fields) share a staged segment from 32 fields (5 km, 64 fields: 17.1 against 19.3 us with 4)
-        const int u = get_tuning("rowgroup_unroll", 8), nw = get_tuning("rowgroup_waves", nvar >= 32 ? 8 : 4);
-        // class tables of half width (two lanes per entry) for the small matrices: all workgroups of a 5 km launch fit the LDS at
-        // once -- 16 applies per launch 13.5 -> 12.3 us (64 fields), 3.96 -> 3.37 (16 fields), one launch unchanged (17.6 / 17.8);
-        // at 1 km the doubled atomic instructions cost 223 -> 238 us.  By the matrix alone, so one apply and a batch agree bitwise.
-        const int tw = get_tuning("rowgroup_tw", w->nnz < (1 << 20) ? 32 : 64);
-#define IBH_RG(N, UU, TT) launch_rowgroup<N, UU, TT>(w, bp, nbatch, nvar, (long)lda, (long)ldb, fill, stream)
-        if (use_grouptile(w, nvar)) {
-            launch_grouptile_any(w, bp, nbatch, nvar, (long)lda, (long)ldb, fill, stream);
-        } else if (tw == 32) { if (nw == 8) { if (u <= 8) IBH_RG(8, 8, 32); else IBH_RG(8, 16, 32); } else { if (u <= 4) IBH_RG(4, 4, 32); else IBH_RG(4, 8, 32); } }
-        else if (nw == 8) { if (u <= 8) IBH_RG(8, 8, 64); else IBH_RG(8, 16, 64); }
-        else { if (u <= 4) IBH_RG(4, 4, 64); else if (u <= 8) IBH_RG(4, 8, 64); else IBH_RG(4, 16, 64); }
-#undef IBH_RG
+        launch_rowgroup_any(w, bp, nbatch, nvar, (long)lda, (long)ldb, fill, stream);
     } else if (kernel == KERNEL_COLSWEEP) {
         launch_sweep(w, bp, nbatch, nvar, (long)lda, (long)ldb, fill, stream);
     } else if (kernel == KERNEL_ROWDUAL) {
@@ -1877,15 +1850,14 @@ static void launch_one_impl(const ibh_weighted *w, ApplyKernel kernel, const Bat
         const ShortrowPlan p = shortrow_plan(w, nvar, nbatch);
         const int fper = p.fper, g = p.g;
         const long xt_stride = (long)w->ncol * p.ldt;
+        DevBuf<double> &xt = w->st.scr.xt;
         // GB-sized results: deep launches cost the L2 locality of the row slices (measured at 1 km: 148 us per apply alone,
         // 181 us sixteen deep); they go out a few batches at a time
         int qmax = std::max(1, get_tuning("shortrow_many", w->nrow >= (1 << 19) ? 1 : IBH_MAX_BATCH));
-        if (p.use_xt && qmax > 1 && (size_t)xt_stride * sizeof(double) * (size_t)std::min(qmax, nbatch) > w->xt.granted) {
+        if (p.use_xt && qmax > 1 && (size_t)xt_stride * sizeof(double) * (size_t)std::min(qmax, nbatch) > xt.granted) {
             // the transposed copies of a deep launch do not fit the scratch the handle owns: grow it -- unless the stream is
             // being captured (no allocation there): then as many batches per launch as fit
-            hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-            if (stream) IBH_HIP(hipStreamIsCapturing(stream, &cs));
-            if (cs != hipStreamCaptureStatusNone) qmax = std::max(1, (int)(w->xt.granted / ((size_t)xt_stride * sizeof(double))));
+            if (is_capturing(stream)) qmax = std::max(1, (int)(xt.granted / ((size_t)xt_stride * sizeof(double))));
         }
         hipEvent_t ev0 = g_ev_start, ev1 = g_ev_stop;
         g_ev_start = g_ev_stop = nullptr;
@@ -1898,7 +1870,7 @@ static void launch_one_impl(const ibh_weighted *w, ApplyKernel kernel, const Bat
                 bq.x[q] = bp.x[q0 + q]; bq.y[q] = bp.y[q0 + q];
                 misaligned = misaligned || (reinterpret_cast<uintptr_t>(bq.y[q]) & 63) != 0;
             }
-            if (p.use_xt) grow_scratch(w->xt, (size_t)xt_stride * (size_t)nq, stream, "transposed-input");
+            if (p.use_xt) grow_scratch(xt, (size_t)xt_stride * (size_t)nq, stream, "transposed-input");
             // planes of B that do not start on 64-byte lines are re-aligned through LDS (see the kernel)
             const bool realign = get_tuning("shortrow_realign", -1) >= 0 ? get_tuning("shortrow_realign", -1) != 0
                                : misaligned && w->nrow >= (1 << 18);   // below: latency-bound, the two extra barriers cost more
@@ -1908,14 +1880,14 @@ static void launch_one_impl(const ibh_weighted *w, ApplyKernel kernel, const Bat
             long xld = (long)lda;
             if (p.use_xt) {
                 hipExtLaunchKernelGGL(transpose_fields_kernel, dim3((unsigned)ceil_div(w->ncol, 64), (unsigned)(p.ldt / 16), (unsigned)nq), dim3(256), 0, stream,
-                                      e_first, nullptr, 0, bq, (long)lda, nvar, w->ncol, w->xt.p, p.ldt, xt_stride);
+                                      e_first, nullptr, 0, bq, (long)lda, nvar, w->ncol, xt.p, p.ldt, xt_stride);
                 e_first = nullptr;
                 xld = p.ldt;
             }
 #define IBH_SR4(NT, GG, RA, XTT)                                                                                        \
-    snprintf(w->last_sig, sizeof(w->last_sig), "%s", "spmm_shortrow_kernel<" #NT ", " #GG ", " #RA ", " #XTT ">");      \
+    snprintf(w->st.last_sig, sizeof(w->st.last_sig), "%s", "spmm_shortrow_kernel<" #NT ", " #GG ", " #RA ", " #XTT ">");      \
     hipExtLaunchKernelGGL((spmm_shortrow_kernel<NT, GG, RA, XTT>), grid, dim3(SR_THREADS), 0, stream, e_first, e_last, 0,  \
-                          w->rowptr.p, w->colind.p, w->val.p, bq, (const double *)w->xt.p, xt_stride, xld, (long)ldb,       \
+                          w->rowptr.p, w->colind.p, w->val.p, bq, (const double *)xt.p, xt_stride, xld, (long)ldb,       \
                           w->nrow, nvar, fper, w->wM.p, fill)
 #define IBH_SR(NT, GG)                                                                                          \
     do {                                                                                                        \
@@ -1947,16 +1919,16 @@ void spmm_launch_many(const ibh_weighted *w, int nbatch, const double *const *dA
     // ... or, with >= 32 fields, the column-sweep structure (sweep_kernel.inl): every X element read once, in whole lines.
     // This is the one place where an apply synchronises and allocates: ibh_weighted_prepare() does it up front,
     // ibh_set_tuning("lazy_structures", 0) switches it off.
-    if (get_tuning("lazy_structures", 1)) build_structures(w, nvar, std::min(nbatch, IBH_MAX_BATCH), w->napply >= 1, stream, (long)w->napply);
-    ++w->napply;
+    if (get_tuning("lazy_structures", 1)) build_structures(w, nvar, std::min(nbatch, IBH_MAX_BATCH), w->st.napply >= 1, stream, (long)w->st.napply);
+    ++w->st.napply;
     ApplyKernel kernel = pick_kernel(w, nvar, nbatch);
     // the column sweep addresses a wave's 16 field planes through one buffer descriptor (32-bit offsets)
     if (kernel == KERNEL_COLSWEEP && ((uint64_t)16 * (uint64_t)lda * 8 + (uint64_t)w->ncol * 8 >= (1ull << 32)))
-        kernel = w->band_n > 0 ? KERNEL_ROWDUAL : KERNEL_ROWBLOCK;
-    w->last_kernel = kernel;
-    w->last_sig[0] = 0;
+        kernel = w->st.bands.built() ? KERNEL_ROWDUAL : KERNEL_ROWBLOCK;
+    w->st.last_kernel = kernel;
+    w->st.last_sig[0] = 0;
     const bool correct = !w->conservative && force_conservation;
-    if (correct) grow_scratch(w->consv, 2 * (size_t)nvar + weight_dot_scratch(std::max(w->nrow, w->ncol), nvar), stream, "conservation");
+    if (correct) grow_scratch(w->st.scr.consv, consv_count(w, nvar), stream, "conservation");
     for (int b0 = 0; b0 < nbatch; b0 += IBH_MAX_BATCH) {
         const int nb = std::min(IBH_MAX_BATCH, nbatch - b0);
         BatchPtrs bp{};
@@ -1969,7 +1941,7 @@ void spmm_launch_many(const ibh_weighted *w, int nbatch, const double *const *dA
             // factor_k = (Mw . A_k) / (wM . B_k); rows with wM == 0 hold `fill` and are skipped.  The two
             // dot products live in handle-owned scratch: stream-ordered, no allocation, no host sync.
             for (int q = 0; q < nb; ++q) {
-                double *T = w->consv.p;
+                double *T = w->st.scr.consv.p;
                 weight_dot_launch(w->Mw.p, w->ncol, bp.x[q], nvar, lda, T, T + 2 * nvar, stream);
                 weight_dot_launch(w->wM.p, w->nrow, bp.y[q], nvar, ldb, T + nvar, T + 2 * nvar, stream);
                 dim3 grid((unsigned)ceil_div(w->nrow, 256), (unsigned)nvar);
@@ -2074,12 +2046,13 @@ __global__ void rowsum_kernel(const int *__restrict__ rowptr, const double *__re
     if (lane == 0) out[r] = acc;
 }
 void ensure_rowsum1(const ibh_weighted *w, hipStream_t stream) {
-    if (w->have_rowsum1 || w->nrow == 0) return;
-    grow_scratch(w->rowsum1, (size_t)w->nrow, stream, "row-sum");
+    ApplyState::Scratch &scr = w->st.scr;
+    if (scr.have_rowsum1 || w->nrow == 0) return;
+    grow_scratch(scr.rowsum1, (size_t)w->nrow, stream, "row-sum");
     hipLaunchKernelGGL(rowsum_kernel, dim3(ceil_div((long)w->nrow * 64, 256)), dim3(256), 0, stream, w->rowptr.p, w->val.p,
-                       w->nrow, w->rowsum1.p);
+                       w->nrow, scr.rowsum1.p);
     IBH_HIP(hipGetLastError());
-    w->have_rowsum1 = true;
+    scr.have_rowsum1 = true;
 }
 
 void spmm_transformed_launch(const ibh_weighted *w, const double *dA, int nvar_in, int64_t lda, const double *T,
@@ -2090,6 +2063,7 @@ void spmm_transformed_launch(const ibh_weighted *w, const double *dA, int nvar_i
     IBH_CHECK(lda >= w->ncol && ldb >= w->nrow, "apply_transformed: leading dimensions too small");
     const size_t ntb = (size_t)nvar_in * nvar_out + nvar_out;
     const bool inl = ntb <= (size_t)TB_MAX;
+    ApplyState::Scratch &scr = w->st.scr;
     TransformArgs ta;
     const double *dT = nullptr;
     if (inl) {
@@ -2100,11 +2074,11 @@ void spmm_transformed_launch(const ibh_weighted *w, const double *dA, int nvar_i
         std::vector<double> tb(ntb);
         std::copy(T, T + (size_t)nvar_in * nvar_out, tb.begin());
         std::copy(b, b + nvar_out, tb.begin() + (size_t)nvar_in * nvar_out);
-        grow_scratch(w->tbuf, ntb, stream, "transform-coefficient");
+        grow_scratch(scr.tbuf, ntb, stream, "transform-coefficient");
         IBH_HIP(hipStreamSynchronize(stream));      // an earlier apply may still read tbuf
-        IBH_HIP(hipMemcpyAsync(w->tbuf.p, tb.data(), sizeof(double) * ntb, hipMemcpyHostToDevice, stream));
+        IBH_HIP(hipMemcpyAsync(scr.tbuf.p, tb.data(), sizeof(double) * ntb, hipMemcpyHostToDevice, stream));
         IBH_HIP(hipStreamSynchronize(stream));      // tb is a stack-lifetime staging buffer
-        dT = w->tbuf.p;
+        dT = scr.tbuf.p;
     }
     auto transform = [&](const double *in, long ldin, const double *scale, const double *wM, double *out, long ldout, int n) {
         dim3 grid((unsigned)ceil_div(n, 256), (unsigned)nvar_out);
@@ -2114,15 +2088,15 @@ void spmm_transformed_launch(const ibh_weighted *w, const double *dA, int nvar_i
     };
     if (w->ncol <= w->nrow) {
         // inputs are the small side: X' = V*T + b, then B = M * X'
-        grow_scratch(w->scratch, (size_t)nvar_out * (size_t)w->ncol, stream, "transform");
-        transform(dA, (long)lda, nullptr, nullptr, w->scratch.p, (long)w->ncol, w->ncol);
-        spmm_launch(w, w->scratch.p, nvar_out, w->ncol, dB, ldb, fill, 0, stream);
+        grow_scratch(scr.scratch, (size_t)nvar_out * (size_t)w->ncol, stream, "transform");
+        transform(dA, (long)lda, nullptr, nullptr, scr.scratch.p, (long)w->ncol, w->ncol);
+        spmm_launch(w, scr.scratch.p, nvar_out, w->ncol, dB, ldb, fill, 0, stream);
     } else {
         // outputs are the small side: Z = M * V, then B = T^T Z + b * (M * 1), rows with wM == 0 -> fill
         ensure_rowsum1(w, stream);
-        grow_scratch(w->scratch, (size_t)nvar_in * (size_t)w->nrow, stream, "transform");
-        spmm_launch(w, dA, nvar_in, lda, w->scratch.p, w->nrow, 0.0, 0, stream);
-        transform(w->scratch.p, (long)w->nrow, w->rowsum1.p, w->wM.p, dB, (long)ldb, w->nrow);
+        grow_scratch(scr.scratch, (size_t)nvar_in * (size_t)w->nrow, stream, "transform");
+        spmm_launch(w, dA, nvar_in, lda, scr.scratch.p, w->nrow, 0.0, 0, stream);
+        transform(scr.scratch.p, (long)w->nrow, scr.rowsum1.p, w->wM.p, dB, (long)ldb, w->nrow);
     }
 }
 
