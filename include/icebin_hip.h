@@ -92,6 +92,46 @@ int ibh_exgrid_get(const ibh_exgrid *ex, int32_t *indices /* [2*nX] */, double *
 int ibh_exgrid_destroy(ibh_exgrid *ex);
 
 /* ------------------------------------------------------------------------- */
+/* L1 ice grids: a triangle mesh carrying piecewise-linear fields (GridParameterization::L1; the reference serves them in
+ * Python only, pylib/icebin/element_l1.py).  The mesh handle holds the vertices and the elements (three vertex ids each,
+ * counter-clockwise) in HBM.  Creation checks on the device that every id lies in [0, nvert) and that every element has a
+ * strictly positive signed area; otherwise IBH_EINVAL, and the message names the first offending element (the reference's
+ * np.linalg.solve raises on a degenerate element, element_l1.py:27-51). */
+typedef struct ibh_l1_mesh ibh_l1_mesh;
+int ibh_l1_mesh_create(int32_t nvert, const double *vx, const double *vy, int32_t ntri, const int32_t *tri /* [3*ntri] */,
+                       ibh_l1_mesh **out);
+int ibh_l1_mesh_destroy(ibh_l1_mesh *mesh);
+/* The exchange grid of a mesh: one cell per (GCM cell, element) overlap of positive area, holding (iA, iTri), the area and
+ * the overlap polygon (counter-clockwise, 3..19 vertices, mesh coordinates), sorted by (iA, iTri).  Generated here
+ * (make_exchange_grid, slib/icebin/gridgen/GridGen_Exchange.cpp:175-284, for triangles: polygons as in ibh_exgrid_desc --
+ * convex, counter-clockwise, projected, 3..16 vertices, ascending iA; more vertices is IBH_EINVAL) or taken from the
+ * caller as the reference's exgrid.cells carry it (element_l1.py:96-148 reads cellX.vertices, .i, .j): any order, sorted
+ * here by (iA, iTri), ties in input order.  The area is Cell::proj_area (Grid.cpp:42-70) of the stored polygon, summed
+ * with the polygon's vertex 0 as the origin.  Two calls on the same input give the same bytes. */
+typedef struct ibh_l1_exgrid ibh_l1_exgrid;
+int ibh_l1_exgrid_generate(const ibh_l1_mesh *mesh, int32_t npoly, const int32_t *polyptr /* [npoly+1] */, const double *px,
+                           const double *py, const int64_t *iA /* [npoly] */, ibh_l1_exgrid **out);
+int ibh_l1_exgrid_from_polygons(int64_t nX, const int32_t *iA, const int32_t *iTri, const int32_t *vptr /* [nX+1] */,
+                                const double *qx, const double *qy, ibh_l1_exgrid **out);
+int ibh_l1_exgrid_size(const ibh_l1_exgrid *ex, int64_t *nX, int64_t *nq /* polygon vertices in all; may be NULL */);
+/* any of the arrays may be NULL */
+int ibh_l1_exgrid_get(const ibh_l1_exgrid *ex, int32_t *indices /* [2*nX] */, double *areas /* [nX] */,
+                      int32_t *vptr /* [nX+1] */, double *qx /* [nq] */, double *qy /* [nq] */);
+int ibh_l1_exgrid_destroy(ibh_l1_exgrid *ex);
+/* compute_AvI (element_l1.py:96-148): per exchange cell the integrals of the element's three basis functions over the
+ * cell's polygon (integrate_subelement, element_l1.py:27-93, evaluated in the element's own frame), as three triplets
+ * (iA, tri[3*iTri+k], value_k), summed per (row, column) in stream order -- ascending exchange cell, then k, the first
+ * term assigned.  which = "AvI": rows over nA, columns over the mesh's vertices; "IvA": the transpose, same values.
+ * Identity dims, wM = row sums over ascending column, Mw = column sums over ascending row, conservative; scale != 0:
+ * M = diag(1/wM) M with wM and Mw unchanged (fA = (1/weightsA) AvI fI, element_l1.py:100-102).  There is no ice mask.
+ * The terms variant copies out the 3*nX triplets themselves, before any summing. */
+typedef struct ibh_weighted ibh_weighted;      /* declared with the Weighted entries below */
+int ibh_l1_terms(const ibh_l1_exgrid *ex, const ibh_l1_mesh *mesh, int64_t nA, const char *which, int32_t *row, int32_t *col,
+                 double *val);
+int ibh_l1_matrix(const ibh_l1_exgrid *ex, const ibh_l1_mesh *mesh, int64_t nA, const char *which, int scale,
+                  ibh_weighted **out);
+
+/* ------------------------------------------------------------------------- */
 /* Hntr: icebin::modele::Hntr (slib/icebin/modele/hntr.hpp:63-135, hntr.cpp:63-168), GISS's HNTR4 conservative
  * regridder between two lat-lon grids.  A grid is HntrSpec(im, jm, offi, dlat) (GridSpec.hpp:143-160): offi = cells
  * from the date line to the western edge of cell 1, dlat = minutes of latitude of a non-polar cell; fields are
