@@ -40,6 +40,23 @@ class ExgridDesc(C.Structure):
                 ("npoly", C.c_int32), ("polyptr", C.c_void_p), ("vx", C.c_void_p), ("vy", C.c_void_p), ("iA", C.c_void_p)]
 
 
+class StereParams(C.Structure):
+    _fields_ = [("lat_0", C.c_double), ("lon_0", C.c_double), ("lat_ts", C.c_double), ("k_0", C.c_double), ("x_0", C.c_double),
+                ("y_0", C.c_double), ("a", C.c_double), ("b", C.c_double), ("has_lat_ts", C.c_int32)]
+
+
+class LonLatCellsDesc(C.Structure):
+    _fields_ = [("nlonb", C.c_int32), ("nlatb", C.c_int32), ("lonb", C.c_void_p), ("latb", C.c_void_p), ("indices", C.c_int32 * 2),
+                ("south_pole", C.c_int32), ("north_pole", C.c_int32), ("points_in_side", C.c_int32), ("eq_rad", C.c_double),
+                ("nrealised", C.c_int64), ("realised", C.c_void_p), ("proj", C.POINTER(StereParams)), ("keep_lonlat", C.c_int32)]
+
+
+class LonLatRegridderDesc(C.Structure):
+    _fields_ = [("cells", C.c_void_p), ("nx", C.c_int32), ("ny", C.c_int32), ("xedges", C.c_void_p), ("yedges", C.c_void_p),
+                ("x_fastest", C.c_int32), ("nhc", C.c_int32), ("hcdefs", C.c_void_p), ("hc_stride_A", C.c_int64),
+                ("hc_stride_HC", C.c_int64), ("interp_style", C.c_int32)]
+
+
 class DeviceView(C.Structure):
     _fields_ = [("nrow", C.c_int32), ("ncol", C.c_int32), ("nnz", C.c_int64), ("rowptr", C.c_void_p),
                 ("colind", C.c_void_p), ("val", C.c_void_p), ("wM", C.c_void_p), ("Mw", C.c_void_p)]
@@ -175,6 +192,14 @@ _SIGS = {
     "ibh_l1_exgrid_destroy": (C.c_int, [C.c_void_p]),
     "ibh_l1_terms": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_char_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ibh_l1_matrix": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_char_p, C.c_int, C.POINTER(C.c_void_p)]),
+    "ibh_parse_sproj": (C.c_int, [C.c_char_p, C.POINTER(StereParams)]),
+    "ibh_lonlat_project": (C.c_int, [C.POINTER(StereParams), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ibh_lonlat_cells_create": (C.c_int, [C.POINTER(LonLatCellsDesc), C.POINTER(C.c_void_p)]),
+    "ibh_lonlat_cells_size": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "ibh_lonlat_cells_get": (C.c_int, [C.c_void_p] * 9),
+    "ibh_lonlat_cells_destroy": (C.c_int, [C.c_void_p]),
+    "ibh_exgrid_generate_lonlat": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]),
+    "ibh_regridder_create_lonlat": (C.c_int, [C.POINTER(LonLatRegridderDesc), C.c_void_p, C.POINTER(C.c_void_p)]),
     "ibh_selftest_sort": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int)]),
     "ibh_selftest_scan": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int]),
     "ibh_selftest_radix_sort": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),

@@ -30,4 +30,7 @@ void e1ve0_compute(int nsheets, const ibh_weighted *const *XuE1s, const ibh_weig
 void i2vx_compute(const ibh_weighted *IvI2, const ibh_weighted *IvX, ibh_weighted *out);
 // make_exchange_grid (gridgen/GridGen_Exchange.cpp:175-284) for a rectilinear XY ice grid (gridgen.hip)
 void exgrid_generate(const ibh_exgrid_desc *d, ibh_exgrid *out);
+// the same from polygons already in HBM (d_*: device arrays, ascending iA; edges on the host), through the streamed clip
+void exgrid_generate_polys(int nx, int ny, const double *xedges, const double *yedges, int x_fastest, int npoly, const int32_t *d_polyptr,
+                           const double *d_vx, const double *d_vy, const int64_t *d_iA, ibh_exgrid *out, hipStream_t st);
 }  // namespace ibh

@@ -748,6 +748,92 @@ inline ExchangeGrid make_exchange_grid(std::vector<double> const &xedges, std::v
     return ex;
 }
 
+// ---- from grid specs: GridSpec.hpp:180-247, gridgen/GridGen_LonLat.cpp:109-232 ----------------------------------------------
+/** GridSpec_LonLat (GridSpec.hpp:180-247): boundaries in degrees, indices by decreasing stride ({1,0}: index = j*nlon + i). */
+struct GridSpec_LonLat {
+    std::vector<double> lonb, latb;
+    std::vector<int> indices{1, 0};
+    bool south_pole = false, north_pole = false;
+    int points_in_side = 1;
+    double eq_rad = 6371000.;
+    int nlon() const { return (int)lonb.size() - 1; }
+    int nlat() const { return (int)latb.size() - 1 + (south_pole ? 1 : 0) + (north_pole ? 1 : 0); }
+};
+/** The `sproj` string of an XY grid spec, parsed (ibh_parse_sproj): proj=stere only; an unknown key throws, named. */
+inline ibh_stere_params parse_sproj(std::string const &sproj) {
+    ibh_stere_params p{};
+    check(ibh_parse_sproj(sproj.c_str(), &p));
+    return p;
+}
+/** The realised cells of a lon/lat spec in HBM, projected (ibh_lonlat_cells): make_grid for the cells `realised` lists
+    (strictly ascending sparse indices), with native and projected areas. */
+class LonLatCells {
+    ibh_lonlat_cells *h_ = nullptr;
+public:
+    LonLatCells(GridSpec_LonLat const &spec, std::vector<long> const &realised, std::string const &sproj) {
+        ibh_stere_params p = parse_sproj(sproj);
+        std::vector<int64_t> r(realised.begin(), realised.end());
+        ibh_lonlat_cells_desc d{};
+        d.nlonb = (int32_t)spec.lonb.size(); d.nlatb = (int32_t)spec.latb.size(); d.lonb = spec.lonb.data(); d.latb = spec.latb.data();
+        if (spec.indices.size() != 2) throw std::runtime_error("GridSpec_LonLat: indices must have two entries");
+        d.indices[0] = spec.indices[0]; d.indices[1] = spec.indices[1];
+        d.south_pole = spec.south_pole; d.north_pole = spec.north_pole; d.points_in_side = spec.points_in_side; d.eq_rad = spec.eq_rad;
+        d.nrealised = (int64_t)r.size(); d.realised = r.data(); d.proj = &p;
+        check(ibh_lonlat_cells_create(&d, &h_));
+    }
+    ~LonLatCells() { ibh_lonlat_cells_destroy(h_); }
+    LonLatCells(LonLatCells const &) = delete;
+    LonLatCells &operator=(LonLatCells const &) = delete;
+    ibh_lonlat_cells *handle() const { return h_; }
+    long ncell() const { int32_t n = 0; check(ibh_lonlat_cells_size(h_, &n, nullptr, nullptr)); return n; }
+    long nA() const { int64_t n = 0; check(ibh_lonlat_cells_size(h_, nullptr, nullptr, &n)); return (long)n; }
+};
+/** make_exchange_grid under those cells (ibh_exgrid_generate_lonlat): any number of vertices per cell. */
+inline ExchangeGrid make_exchange_grid_lonlat(LonLatCells const &cells, std::vector<double> const &xedges, std::vector<double> const &yedges,
+                                              bool x_fastest) {
+    ibh_exgrid *h = nullptr;
+    check(ibh_exgrid_generate_lonlat(cells.handle(), (int32_t)xedges.size() - 1, (int32_t)yedges.size() - 1, xedges.data(), yedges.data(),
+                                     x_fastest, &h));
+    ExchangeGrid ex;
+    int64_t n = 0;
+    int rc = ibh_exgrid_size(h, &n);
+    if (rc == IBH_OK) { ex.indices.resize((size_t)(2 * n)); ex.overlaps.resize((size_t)n); rc = ibh_exgrid_get(h, ex.indices.data(), ex.overlaps.data()); }
+    ibh_exgrid_destroy(h);
+    check(rc);
+    return ex;
+}
+/** From grid specs to a GCMRegridder_Standard with one sheet, built on the device (ibh_regridder_create_lonlat); indexingHC
+    {1, nA} (HC slowest). */
+inline std::unique_ptr<GCMRegridder_Standard> regridder_from_specs(GridSpec_LonLat const &spec, std::vector<long> const &realised,
+                                                                   std::vector<double> const &xedges, std::vector<double> const &yedges,
+                                                                   bool x_fastest, std::string const &sproj, std::vector<double> hcdefs,
+                                                                   bool correctA = true, int interp_style = InterpStyle::Z_INTERP,
+                                                                   std::string const &sheet_name = "ice") {
+    LonLatCells cells(spec, realised, sproj);
+    const long nA = cells.nA();
+    ibh_lonlat_regridder_desc d{};
+    d.cells = cells.handle();
+    d.nx = (int32_t)xedges.size() - 1; d.ny = (int32_t)yedges.size() - 1; d.xedges = xedges.data(); d.yedges = yedges.data();
+    d.x_fastest = x_fastest; d.nhc = (int32_t)hcdefs.size(); d.hcdefs = hcdefs.data();
+    d.hc_stride_A = 1; d.hc_stride_HC = nA; d.interp_style = interp_style;
+    ibh_regridder *rg = nullptr;
+    check(ibh_regridder_create_lonlat(&d, nullptr, &rg));
+    std::unique_ptr<ibh_regridder, int (*)(ibh_regridder *)> owned(rg, ibh_regridder_destroy);     // until the sheet owns it
+    AbbrGrid a;
+    int32_t nAd = 0;
+    check(ibh_regridder_agridA(rg, &nAd, nullptr, nullptr, nullptr));
+    std::vector<int64_t> a2s((size_t)nAd);
+    a.native_area.resize((size_t)nAd);
+    check(ibh_regridder_agridA(rg, &nAd, a2s.data(), a.native_area.data(), nullptr));
+    a.sparse_extent = nA;
+    a.dim_to_sparse.assign(a2s.begin(), a2s.end());
+    a.name = "A";
+    std::unique_ptr<GCMRegridder_Standard> gcm(new GCMRegridder_Standard);
+    gcm->init(std::move(a), std::move(hcdefs), {{1, nA}}, correctA);
+    gcm->add_sheet(sheet_name, owned.release(), interp_style);
+    return gcm;
+}
+
 // ---- modele/hntr.hpp:63-135, GridSpec.hpp:143-160 ----------------------------------------------------
 namespace modele {
 /** HntrSpec(im, jm, offi, dlat) (GridSpec.hpp:143-160): offi = cells from the date line to the western edge of cell 1,

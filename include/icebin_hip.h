@@ -72,7 +72,8 @@ int ibh_sparse_set_add_dense(ibh_sparse_set *s, int64_t sparse, int32_t *dense);
 /* Exchange-grid generation: make_exchange_grid (slib/icebin/gridgen/GridGen_Exchange.cpp:175-284) for a
  * rectilinear ice grid in the projected plane (gridgen/searise_grid.cpp) under convex GCM-cell polygons
  * whose vertices the caller has projected to that plane (OGrid, GridGen_Exchange.cpp:120-166; counter-
- * clockwise, 3..16 vertices, ascending iA).  Every non-empty overlap becomes one exchange cell
+ * clockwise, 3 or more vertices, ascending iA; up to 16 vertices run the array clip, more the streamed one, and
+ * ibh_set_tuning("gridgen_stream_clip", 0 | 1) forces one).  Every non-empty overlap becomes one exchange cell
  * (iA, iI, area) with area = Cell::proj_area of the overlap polygon (Grid.cpp:42-70); cells come out
  * sorted by (iA, iI) like ExchangeGrid's constructor leaves them (AbbrGrid.cpp:10-21).  The result
  * stays in HBM; ibh_exgrid_get copies it out (the layout ibh_regridder_desc takes). */
@@ -274,6 +275,70 @@ int ibh_regridder_create_hntr(const ibh_hntr_regridder_desc *desc, ibh_sparse_se
  * NULL only *nX is set) and agridA ([nA_dense] each; *nA_dense is always set, and each non-NULL array is filled). */
 int ibh_regridder_exgrid(const ibh_regridder *rg, int64_t *nX, int32_t *indices, double *overlaps);
 int ibh_regridder_agridA(const ibh_regridder *rg, int32_t *nA_dense, int64_t *to_sparse, double *native_area, double *proj_area);
+
+/* ------------------------------------------------------------------------- */
+/* From grid specs: the realised cells of a GridSpec_LonLat (gridgen/GridGen_LonLat.cpp:109-232), projected to the ice
+ * grid's plane with proj.4's `stere` (the only projection the reference's grid generators name), their native areas
+ * (graticule_area_exact / polar_graticule_area_exact, :79-102) and projected areas (Cell::proj_area, Grid.cpp:42-71), all
+ * computed on the device and kept in HBM; then the exchange grid and the regridder from them without a host copy.
+ *
+ * ibh_parse_sproj: "+proj=stere +lat_0=.. +lon_0=.. [+lat_ts=..] [+k=.. | +k_0=..] [+x_0=..] [+y_0=..] [+ellps=WGS84 |
+ * +datum=WGS84 | +a=.. +b=.. | +R=..] [+units=m] [+no_defs]" (the leading '+' is optional).  Any other key or value is
+ * IBH_EINVAL and the message names the key.  WGS84: a = 6378137, 1/f = 298.257223563; no ellipsoid given: WGS84. */
+typedef struct ibh_stere_params {
+    double  lat_0, lon_0;           /* degrees                                                   */
+    double  lat_ts;                 /* degrees; read only when has_lat_ts                        */
+    double  k_0, x_0, y_0;          /* scale factor; false easting / northing, metres            */
+    double  a, b;                   /* semi-axes, metres; a == b: a sphere                       */
+    int32_t has_lat_ts;
+} ibh_stere_params;
+int ibh_parse_sproj(const char *sproj, ibh_stere_params *out);
+/* (lon, lat) in degrees -> (x, y) in metres for n points, host arrays, evaluated on the device with the function the cell
+ * kernels use. */
+int ibh_lonlat_project(const ibh_stere_params *proj, int64_t n, const double *lon, const double *lat, double *x, double *y);
+
+typedef struct ibh_lonlat_cells_desc {
+    int32_t        nlonb, nlatb;    /* entries of lonb (= nlon + 1) and of latb                  */
+    const double  *lonb, *latb;     /* cell boundaries, degrees, ascending                       */
+    int32_t        indices[2];      /* {0,1}: index = i*nlat + j; {1,0}: index = j*nlon + i      */
+    int32_t        south_pole, north_pole;       /* the grid has that cap                        */
+    int32_t        points_in_side;  /* >= 1: points per side of a cell (and per lonb interval of a cap) */
+    double         eq_rad;          /* radius for the native areas, metres                       */
+    int64_t        nrealised;
+    const int64_t *realised;        /* [nrealised] sparse indices of the cells to realise, strictly ascending */
+    const ibh_stere_params *proj;
+    int32_t        keep_lonlat;     /* also keep the unprojected vertices (tests)                */
+} ibh_lonlat_cells_desc;
+/* nlat = nlatb - 1 + south_pole + north_pole; an ordinary cell (ilon, ilat) has i = ilon, j = ilat + south_pole; the south
+ * cap has index 0 and the north cap nlat*nlon + nlon - 1 (pole.j = nlat(), :180-182: one row past the last), so the sparse
+ * extent nA is nlon*nlat without a north cap and nlon*(nlat + 1) with one.  A realised index that is no cell of the spec, an
+ * unsorted list, points_in_side < 1 or non-ascending boundaries is IBH_EINVAL; on error *out is NULL. */
+typedef struct ibh_lonlat_cells ibh_lonlat_cells;
+int ibh_lonlat_cells_create(const ibh_lonlat_cells_desc *desc, ibh_lonlat_cells **out);
+int ibh_lonlat_cells_size(const ibh_lonlat_cells *cells, int32_t *ncell, int64_t *nvert, int64_t *nA);
+/* Copy-out (tests): every non-NULL array is filled.  iA, native_area, proj_area [ncell]; polyptr [ncell+1]; vx, vy [nvert];
+ * lon, lat [nvert] only for a handle created with keep_lonlat. */
+int ibh_lonlat_cells_get(const ibh_lonlat_cells *cells, int64_t *iA, int32_t *polyptr, double *vx, double *vy, double *native_area,
+                         double *proj_area, double *lon, double *lat);
+int ibh_lonlat_cells_destroy(ibh_lonlat_cells *cells);
+/* ibh_exgrid_generate under these cells: the polygons are read where they lie, through the streamed clip (no vertex limit). */
+int ibh_exgrid_generate_lonlat(const ibh_lonlat_cells *cells, int32_t nx, int32_t ny, const double *xedges, const double *yedges,
+                               int32_t x_fastest, ibh_exgrid **out);
+/* The regridder of that exchange grid, what ibh_regridder_create builds from the copied-out arrays: agridA = the realised
+ * cells (ascending) with their native areas, A_proj_area their projected areas, nA as above, nI = nx*ny, I_centroid_xy the
+ * cell centres (.5 * (e[k] + e[k+1])).  dimA_out (may be NULL) must be an empty set and receives the realised cells.  On error
+ * *out is NULL and dimA_out is as it was. */
+typedef struct ibh_lonlat_regridder_desc {
+    const ibh_lonlat_cells *cells;
+    int32_t        nx, ny;
+    const double  *xedges, *yedges; /* [nx+1], [ny+1] ice-cell edges, ascending                  */
+    int32_t        x_fastest;
+    int32_t        nhc;
+    const double  *hcdefs;          /* [nhc] ascending                                           */
+    int64_t        hc_stride_A, hc_stride_HC;    /* as in ibh_regridder_desc                     */
+    int32_t        interp_style;    /* 0 Z_INTERP, 1 ELEV_CLASS_INTERP                           */
+} ibh_lonlat_regridder_desc;
+int ibh_regridder_create_lonlat(const ibh_lonlat_regridder_desc *desc, ibh_sparse_set *dimA_out, ibh_regridder **out);
 
 /* ------------------------------------------------------------------------- */
 /* Weighted: ibmisc::linear::Weighted_Eigen {dims, M, wM, Mw, conservative,
