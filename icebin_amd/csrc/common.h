@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/icebin_hip.h"
+#include "apply_plan.h"
 
 namespace ibh {
 
@@ -104,10 +105,6 @@ struct DevBuf {
     void zero(hipStream_t s = nullptr) { if (n) IBH_HIP(hipMemsetAsync(p, 0, n * sizeof(T), s)); }
 };
 
-inline int ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
-constexpr int IBH_GSLOTS = 32;      // most rows (elevation classes of one GCM cell) in a row group (spmm.hip rowgroup)
-// tiles of a row group (spmm.hip grouptile): seg = items (distinct columns) of a tile, 256 or 128 by the matrix (RowGroups::Tiles::seg)
-constexpr int ibh_gt_ecap(int seg) { return 2 * seg + 4 * IBH_GSLOTS; }   // entries of a tile: <= 2 per item, every slot's list padded to a multiple of 4
 constexpr int IBH_GT_EP = IBH_GSLOTS + 2;   // u16 entry offsets of a tile: one per slot + the end, padded to whole dwords
 inline int bits_for(uint64_t n) {   // bits needed to represent values in [0, n)
     int b = 0;
@@ -261,8 +258,6 @@ inline uint64_t next_weighted_uid() {
     static std::atomic<uint64_t> n{0};
     return ++n;
 }
-// the apply kernel families (spmm.hip), as ibh_weighted_set_kernel / ibh_weighted_last_kernel name them (capi.hip)
-enum ApplyKernel { KERNEL_AUTO = 0, KERNEL_ROWBLOCK = 1, KERNEL_SHORTROW, KERNEL_ROWDUAL, KERNEL_COLSWEEP, KERNEL_ROWGROUP };
 
 // ---- apply structures: optional copies of a matrix's entries in the order one apply kernel family wants them ------------------
 // Each is a value that owns its buffers: a builder (assemble.hip) fills a local one and returns it, `x = {}` empties it,
@@ -277,14 +272,11 @@ struct Bands {
     DevBuf<double> v0, v1;                  // [n] lower-class / upper-class weight
     bool built() const { return n > 0; }
     // partial sums of an apply: [2: lower, upper][nbatch][nvar][part_ld()]
-    long part_ld() const { return ((long)nrow + 63) & ~63l; }
+    long part_ld() const { return band_part_ld(nrow); }
     long part_stride(int nvar) const { return (long)nvar * part_ld(); }      // one batch's lower (or upper) sums
-    size_t part_count(int nvar, int nbatch) const { return 2 * (size_t)nbatch * (size_t)part_stride(nvar); }
+    size_t part_count(int nvar, int nbatch) const { return band_part_count(nrow, nvar, nbatch); }
 };
 
-// fields per lane group of the sweep, as a power of two: 64 (one batch per wave row) from 33 fields; below, the next power of
-// two >= 8 so that 64 >> lg batches share the lanes
-inline int sweep_lg(int nvar) { return nvar > 32 ? 6 : nvar > 16 ? 5 : nvar > 8 ? 4 : 3; }
 // colsweep (EvI, EvX, and AvI, AvX in batched launches; sweep_kernel.inl): the entries in column order, paired per column into
 // items, 64 items a block, tb blocks a task with its local row table (assemble.hip build_sweep_from_csr)
 struct Sweep {
@@ -296,12 +288,9 @@ struct Sweep {
     DevBuf<int32_t> comb_ptr, comb_p;       // [nrow+1], [nprow]: the partial-sum rows that make up row r, in task order
     bool built() const { return ntask > 0; }
     // partial sums of an apply: [slices of 64 lanes, a lane = (batch, field)][nprow][part_ld()]
-    long part_ld(int nvar) const { return sweep_lg(nvar) == 6 ? (long)ceil_div(nvar, 64) * 64 : 64; }
+    long part_ld(int nvar) const { return sweep_part_ld(nvar); }
     long part_stride(int nvar) const { return (long)nprow * part_ld(nvar); }
-    size_t part_count(int nvar, int nbatch) const {
-        const int lg = sweep_lg(nvar);
-        return (size_t)(lg == 6 ? nbatch : ceil_div(nbatch, 64 >> lg)) * (size_t)part_stride(nvar);
-    }
+    size_t part_count(int nvar, int nbatch) const { return sweep_part_count(nprow, nvar, nbatch); }
 };
 
 // fused pair (ibh_weighted_pair_prepare): a second matrix whose every row reads rows of ONE group of this matrix only (AvE
@@ -362,6 +351,14 @@ struct ApplyState {
     // per-handle launch options (ibh_weighted_set_option): looked up before the process-wide ibh_set_tuning map by every apply of
     // THIS matrix, so two host threads tuning different handles do not interfere
     std::unordered_map<std::string, int> opts;
+    void fill(MatrixFacts &f) const {               // the structures' part of what the choice reads (facts_of)
+        f.bands_built = bands.built(); f.bands_tried = bands_tried; f.bands_n = bands.n;
+        f.sweep_built = sweep.built(); f.sweep_tried = sweep_tried;
+        f.sweep_ntask = sweep.ntask; f.sweep_nprow = sweep.nprow; f.sweep_nslot = sweep.nslot; f.sweep_ident = sweep.ident;
+        f.groups_built = groups.built(); f.groups_tried = groups_tried; f.groups_n = groups.n; f.groups_nslot = groups.nslot;
+        f.tiles_built = groups.tiles.built(); f.tiles_seg = groups.tiles.seg;
+        f.napply = napply;
+    }
 };
 }  // namespace ibh
 // The matrix proper is immutable once it is built; `st` is the cache the applies keep beside it.
@@ -387,6 +384,16 @@ struct ibh_weighted {
             if (owns[k]) delete dims[k];
     }
 };
+
+namespace ibh {
+inline MatrixFacts facts_of(const ibh_weighted &w) {
+    MatrixFacts f;
+    f.nrow = w.nrow; f.ncol = w.ncol; f.nnz = w.nnz;
+    f.band_eligible = w.band_eligible != 0; f.conservative = w.conservative != 0; f.kernel_override = w.kernel_override;
+    w.st.fill(f);
+    return f;
+}
+}  // namespace ibh
 
 struct ibh_exgrid {
     int64_t nX = 0;

@@ -28,6 +28,7 @@
 #include "sweep_kernel.inl"
 #include <hip/hip_ext.h>
 #include <mutex>
+#include <set>
 
 namespace ibh {
 
@@ -671,8 +672,6 @@ static TileView tile_view(const RowGroups &g) {
 }
 constexpr int GT_UNITS = 16;         // the SP bound above: a group's units (slot, part) number max(16, ns)
 constexpr int GT_TABP = 65;          // row stride of the epilogue's table of partial sums [unit][lane]
-template <int F, int SEG>
-constexpr size_t grouptile_lds() { return (size_t)F * (SEG + 2) * 8 + ibh_gt_ecap(SEG) * 10 + 256; }     // (+ slack: a batch reads a few steps past its run)
 // sums of the two 32-lane halves of a wave: lo = lanes 0..31, hi = lanes 32..63, each in the order wave_sum adds a wave whose
 // other half is zero
 __device__ __forceinline__ void wave_half_sums(double v, double &lo, double &hi) {
@@ -862,7 +861,6 @@ __global__ __launch_bounds__(NW * 64, 4) void spmm_grouptile_kernel(const TileVi
     }
 }
 
-constexpr int SR_THREADS = 256;
 
 // XT[c*ldt + f] = X[f*ldx + c]; pad columns f in [nf, ldt) are zeroed (read for tail fields, never stored)
 __global__ void transpose_fields_kernel(const BatchPtrs bp, long ldx, int nf, int ncol,
@@ -893,7 +891,6 @@ __global__ void transpose_fields_kernel(const BatchPtrs bp, long ldx, int nf, in
 // computes 256 rows but OWNS, per plane, the line-aligned run of <= 255 rows that starts at the first
 // 64-byte boundary at or after its first row (consecutive workgroups advance by 248 rows, so the
 // runs tile the plane exactly); values cross lanes through LDS and every wave stores whole lines.
-constexpr int SR_STEP = SR_THREADS - 8;
 // XT: X is read from its transpose XT[c, f] (row stride ldx = fields padded to 16): the G fields of
 // one entry are 8*G contiguous bytes per lane, fetched with 16-byte loads.  With the field-major X a
 // wave gather touches up to 64 lines PER FIELD when the lanes' columns differ (IvE: the elevation
@@ -1190,175 +1187,6 @@ static bool ensure_rowperm(const ibh_weighted *w, hipStream_t stream) {
     return true;
 }
 
-static long rowblock_grid(int nrow, int nfc, int &xcd_mode) {
-    xcd_mode = (nfc % 8 == 0 || nfc == 1 || nfc == 2 || nfc == 4) ? 1 : 0;
-    xcd_mode = get_tuning("rowblock_xcd_mode", xcd_mode);
-    if (xcd_mode == 1 && !(nfc % 8 == 0 || nfc == 1 || nfc == 2 || nfc == 4)) xcd_mode = 0;
-    long nb = ((long)nrow * nfc + 7) & ~7l;
-    if (xcd_mode == 1) {
-        if (nfc < 8) {                        // 8/nfc XCDs per chunk, each a row range of <= ceil(nrow/m) rows
-            const int m = 8 / nfc;
-            nb = 8l * ((nrow + m - 1) / m + 1);
-        } else nb = (long)nrow * nfc;         // nfc % 8 == 0
-    }
-    return nb;
-}
-
-template <int FPW, int WK, int NW>
-static void launch_rowblock(const ibh_weighted *w, const BatchPtrs &bp, int nbatch, int nvar, long lda, long ldb,
-                            double fill, hipStream_t stream)
-{
-    constexpr int FB = FPW * (NW / WK);
-    const int nfc = ceil_div(nvar, FB);
-    int xcd_mode;
-    const long nb = rowblock_grid(w->nrow, nfc, xcd_mode);
-    IBH_CHECK(nb < (1l << 31), "spmm grid too large (%ld blocks)", nb);
-    IBH_CHECK((long)w->ncol * 8 < (1l << 31), "ncol too large for 32-bit buffer offsets");
-    // loads in flight per lane and field: enough 64-entry slots to cover a typical row in one batch
-    int unroll = get_tuning("rowblock_unroll", 0);
-    if (unroll == 0) {
-        const double mean = w->nrow ? (double)w->nnz / (double)w->nrow / (64.0 * WK) : 1.0;
-        // (a row is one partly filled batch when the unroll overshoots it: 5 km EvI, 2.1 passes of 64 per row, 26.2 / 18.4 us
-        // with four loads in flight, 23.6 / 16.6 with two)
-        unroll = mean > 6.0 ? 8 : mean > 3.0 ? 4 : mean > 1.5 ? 2 : 1;
-        // one field per wave: the weights are read when the gathers land, a slot in flight holds two registers -> a row of up to
-        // 896 entries in ONE batch of 14 gathers per lane (measured, 5 km AvI, 32 applies per launch: 7.31 -> 7.03 us per apply;
-        // 12 or 16 are slower: 8.5 / 7.4)
-        if (FPW == 1 && WK == 1 && NW == 8 && mean > 8.0 && mean <= 14.0) unroll = 14;
-    }
-    // batches per workgroup: the staged row segment and the prologue are shared by qi batches
-    int qi = 1;
-    if (nbatch > 1) {
-        qi = get_tuning("rowblock_many_qi", 0);
-        if (qi <= 0) qi = nbatch >= 4 ? 2 : 1;       // measured at the 5 km headline shape: depth 16 7.5 (qi 2) / 8.2 (qi 1) / 8.0 us (qi 8)
-        if (qi > nbatch) qi = nbatch;
-    }
-    const dim3 grid((unsigned)nb, (unsigned)ceil_div(nbatch, qi));
-    const int *rowperm = nullptr;
-    if (nbatch > 1 && get_tuning("rowblock_lpt", 0) && ensure_rowperm(w, stream)) rowperm = w->st.scr.rowperm.p;
-    hipEvent_t ev0 = g_ev_start, ev1 = g_ev_stop;
-    g_ev_start = g_ev_stop = nullptr;
-#define IBH_RB(U)                                                                                        \
-    do {                                                                                                 \
-        snprintf(w->st.last_sig, sizeof(w->st.last_sig), "spmm_rowblock_kernel<%d, %d, %d, %d, false>", FPW, WK, (int)(U), NW);  \
-        hipExtLaunchKernelGGL((spmm_rowblock_kernel<FPW, WK, U, NW>), grid, dim3(NW * 64), 0, stream, ev0, ev1, 0,  \
-                              w->rowptr.p, w->colind.p, w->val.p, bp, nbatch, qi, lda, w->ncol, ldb, w->nrow, nvar, nfc, xcd_mode, w->wM.p, fill, \
-                              (const double *)nullptr, (double *)nullptr, (const int *)rowperm, 0l);     \
-    } while (0)
-    if (unroll == 1) IBH_RB(1);
-    else if (unroll == 2) IBH_RB(2);
-    else if (unroll == 8) IBH_RB(8);
-    else if (unroll > 8 && FPW == 1 && WK == 1) {      // one batch covers a whole row of <= 768 / 896 / 1024 entries
-        // (4 waves: a lane stages twice the entries of a segment, and 12..16 gathers no longer fit 64 registers: they spill; 8)
-        if constexpr (FPW == 1 && WK == 1 && NW == 8) {
-            if (unroll <= 12) IBH_RB(12); else if (unroll <= 14) IBH_RB(14); else IBH_RB(16);
-        } else IBH_RB(8);
-    }
-    else IBH_RB(4);
-#undef IBH_RB
-    IBH_HIP(hipGetLastError());
-}
-
-template <int NW, int U>
-static void launch_rowone(const ibh_weighted *w, const double *X, double *Y, int nvar, long lda, long ldb, double fill, hipStream_t stream)
-{
-    const int nfc = ceil_div(nvar, NW);
-    int xcd_mode;
-    const long nb = rowblock_grid(w->nrow, nfc, xcd_mode);
-    IBH_CHECK(nb < (1l << 31), "spmm grid too large (%ld blocks)", nb);
-    IBH_CHECK((long)w->ncol * 8 < (1l << 31), "ncol too large for 32-bit buffer offsets");
-    hipEvent_t ev0 = g_ev_start, ev1 = g_ev_stop;
-    g_ev_start = g_ev_stop = nullptr;
-    snprintf(w->st.last_sig, sizeof(w->st.last_sig), "spmm_rowone_kernel<%d, %d>", NW, U);
-    hipExtLaunchKernelGGL((spmm_rowone_kernel<NW, U>), dim3((unsigned)nb), dim3(NW * 64), 0, stream, ev0, ev1, 0, w->rowptr.p, w->colind.p,
-                          w->val.p, X, Y, lda, w->ncol, ldb, w->nrow, nvar, nfc, xcd_mode, w->wM.p, fill);
-    IBH_HIP(hipGetLastError());
-}
-
-template <int NW, int U, int TW>
-static void launch_rowgroup(const ibh_weighted *w, const BatchPtrs &bp, int nbatch, int nvar, long lda, long ldb, double fill, hipStream_t stream,
-                            const PairView *pair = nullptr)
-{
-    const int nfc = ceil_div(nvar, NW);
-    int xcd_mode;
-    const GroupView gv = group_view(w->st.groups);
-    const long nb = rowblock_grid(gv.ngrp, nfc, xcd_mode);
-    IBH_CHECK(nb < (1l << 31), "spmm grid too large (%ld blocks)", nb);
-    IBH_CHECK((long)w->ncol * 8 < (1l << 31), "ncol too large for 32-bit buffer offsets");
-    const size_t lds = (size_t)(3 * U * 64 + NW * gv.nslot * TW) * sizeof(double);
-    hipEvent_t ev0 = g_ev_start, ev1 = g_ev_stop;
-    g_ev_start = g_ev_stop = nullptr;
-    if (lds > 64 * 1024) {                               // beyond the default dynamic-LDS limit: raise it once per device
-        static std::mutex mu;
-        static bool raised[64] = {};
-        std::lock_guard<std::mutex> lk(mu);
-        if (!raised[w->device & 63]) {
-            IBH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(spmm_rowgroup_kernel<NW, U, TW>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            raised[w->device & 63] = true;
-        }
-    }
-    snprintf(w->st.last_sig, sizeof(w->st.last_sig), "spmm_rowgroup_kernel<%d, %d, %d, %s>", NW, U, TW, pair ? "true" : "false");
-    if (pair) {
-        IBH_CHECK(lds <= 64 * 1024 && nbatch == 1, "fused pair apply: %zu bytes of LDS / %d batches not supported", lds, nbatch);
-        hipExtLaunchKernelGGL((spmm_rowgroup_kernel<NW, U, TW, true>), dim3((unsigned)nb, 1u), dim3(NW * 64), lds, stream, ev0, ev1, 0, gv, bp,
-                              lda, w->ncol, ldb, nvar, nfc, xcd_mode, w->wM.p, fill, *pair);
-    } else
-        hipExtLaunchKernelGGL((spmm_rowgroup_kernel<NW, U, TW>), dim3((unsigned)nb, (unsigned)nbatch), dim3(NW * 64), lds, stream, ev0, ev1, 0, gv, bp,
-                              lda, w->ncol, ldb, nvar, nfc, xcd_mode, w->wM.p, fill, PairView{});
-    IBH_HIP(hipGetLastError());
-}
-
-template <int F, int NS, int SEG, int NW>
-static void launch_grouptile(const ibh_weighted *w, const BatchPtrs &bp, int nbatch, int nvar, long lda, long ldb, double fill, hipStream_t stream,
-                             const PairView *pair = nullptr)
-{
-    const int nfc = ceil_div(nvar, F);
-    int xcd_mode;
-    const RowGroups &grp = w->st.groups;
-    const long nb = rowblock_grid(grp.n, nfc, xcd_mode);
-    IBH_CHECK(nb < (1l << 31), "spmm grid too large (%ld blocks)", nb);
-    IBH_CHECK((long)w->ncol * 8 < (1l << 31), "ncol too large for 32-bit buffer offsets");
-    IBH_CHECK(grp.nslot <= NS && grp.tiles.seg == SEG, "row groups of %d rows / tiles of %d in a kernel for %d / %d", grp.nslot, grp.tiles.seg, NS, SEG);
-    const TileView tv = tile_view(grp);
-    constexpr size_t lds = grouptile_lds<F, SEG>();
-    static_assert(lds <= 64 * 1024, "within the default dynamic-LDS limit");
-    hipEvent_t ev0 = g_ev_start, ev1 = g_ev_stop;
-    g_ev_start = g_ev_stop = nullptr;
-    snprintf(w->st.last_sig, sizeof(w->st.last_sig), "spmm_grouptile_kernel<%d, %d, %d, %d, %s>", F, NS, SEG, NW, pair ? "true" : "false");
-    if (pair) {
-        IBH_CHECK(nbatch == 1, "fused pair apply: %d batches not supported", nbatch);
-        hipExtLaunchKernelGGL((spmm_grouptile_kernel<F, NS, SEG, NW, true>), dim3((unsigned)nb, 1u), dim3(NW * 64), lds, stream, ev0, ev1, 0, tv, bp,
-                              lda, w->ncol, ldb, nvar, nfc, xcd_mode, w->wM.p, fill, *pair);
-    } else
-        hipExtLaunchKernelGGL((spmm_grouptile_kernel<F, NS, SEG, NW, false>), dim3((unsigned)nb, (unsigned)nbatch), dim3(NW * 64), lds, stream, ev0, ev1, 0,
-                              tv, bp, lda, w->ncol, ldb, nvar, nfc, xcd_mode, w->wM.p, fill, PairView{});
-    IBH_HIP(hipGetLastError());
-}
-// (rows per group, tile size) -> instantiation; 16 fields per workgroup (32 lost everywhere it was measured: 1 km 269 against 218 us,
-// the Antarctic sheet 3.67 against 3.62 ms, 5 km 22 against 18 us)
-static void launch_grouptile_any(const ibh_weighted *w, const BatchPtrs &bp, int nbatch, int nvar, long lda, long ldb, double fill, hipStream_t stream,
-                                 const PairView *pair = nullptr)
-{
-    const bool few = w->st.groups.nslot <= 16;
-    if (w->st.groups.tiles.seg == 128) {
-        if (few) launch_grouptile<16, 16, 128, 4>(w, bp, nbatch, nvar, lda, ldb, fill, stream, pair);
-        else launch_grouptile<16, 32, 128, 4>(w, bp, nbatch, nvar, lda, ldb, fill, stream, pair);
-    } else {
-        if (few) launch_grouptile<16, 16, 256, 8>(w, bp, nbatch, nvar, lda, ldb, fill, stream, pair);
-        else launch_grouptile<16, 32, 256, 8>(w, bp, nbatch, nvar, lda, ldb, fill, stream, pair);
-    }
-}
-// Which form of the row groups: the tiles (grouptile) for bandwidth-sized matrices -- measured, one apply per launch, tiles
-// against LDS atomics: the Antarctic sheet (35 M entries) 16 fields 503 against 672 us, 128 fields 3.62 against 4.34 ms; 1 km
-// Greenland (4 M entries) 64 fields 218 against 220 us, 16 fields 82 against 74; 5 km (166 k entries: latency-bound, three
-// tiles in sequence per GCM cell) 12.4 against 7.6 and 18.1 against 17.4 us.  ibh_set_tuning("rowgroup_form", 0 / 1) forces one.
-static bool use_grouptile(const ibh_weighted *w, int nvar) {
-    if (!w->st.groups.tiles.built()) return false;
-    const int form = get_tuning("rowgroup_form", -1);
-    if (form >= 0) return form == 1;
-    return w->nnz >= (1l << 24) || (w->nnz >= (1l << 21) && nvar >= 48);
-}
-
 // B[f, r] = lower-class sum of band r + upper-class sum of the band below it (rb1[r], -1: none)
 __global__ void dual_combine_kernel(const double *__restrict__ P0, const double *__restrict__ P1, long ldp, long pstride,
                                     const int *__restrict__ rb1, const double *__restrict__ wM, double fill,
@@ -1372,42 +1200,6 @@ __global__ void dual_combine_kernel(const double *__restrict__ P0, const double 
     bp.y[q][(long)f * ldy + r] = wM[r] == 0.0 ? fill : t;
 }
 
-template <int FPW>
-static void launch_rowdual(const ibh_weighted *w, const BatchPtrs &bp, int nbatch, int nvar, long lda, long ldb,
-                           double fill, hipStream_t stream)
-{
-    constexpr int NW = 4, FB = FPW * NW;
-    const int nfc = ceil_div(nvar, FB);
-    int xcd_mode;
-    const long nb = rowblock_grid(w->nrow, nfc, xcd_mode);
-    IBH_CHECK(nb < (1l << 31), "spmm grid too large (%ld blocks)", nb);
-    IBH_CHECK((long)w->ncol * 8 < (1l << 31), "ncol too large for 32-bit buffer offsets");
-    const Bands &bands = w->st.bands;
-    const long ldp = bands.part_ld(), pstride = bands.part_stride(nvar);
-    grow_scratch(w->st.scr.band_part, bands.part_count(nvar, nbatch), stream, "band");
-    double *P0 = w->st.scr.band_part.p, *P1 = P0 + (size_t)nbatch * (size_t)pstride;
-    int unroll = get_tuning("rowdual_unroll", 0);
-    if (unroll <= 0) {
-        const double mean = w->nrow ? (double)bands.n / (double)w->nrow / 64.0 : 1.0;
-        unroll = mean > 4.0 ? 8 : mean > 2.0 ? 4 : mean > 1.0 ? 2 : 1;
-    }
-    BatchPtrs bq{};
-    for (int q = 0; q < nbatch; ++q) { bq.x[q] = bp.x[q]; bq.y[q] = P0 + (size_t)q * (size_t)pstride; }
-    const dim3 grid((unsigned)nb, (unsigned)nbatch);
-#define IBH_RD(U)                                                                                                  \
-    snprintf(w->st.last_sig, sizeof(w->st.last_sig), "spmm_rowblock_kernel<%d, 1, %d, %d, true>", FPW, (int)(U), NW);     \
-    hipLaunchKernelGGL((spmm_rowblock_kernel<FPW, 1, U, NW, true>), grid, dim3(NW * 64), 0, stream,                 \
-                       bands.ptr.p, bands.col.p, bands.v0.p, bq, nbatch, 1, lda, w->ncol, ldp, w->nrow, nvar, nfc, xcd_mode,       \
-                       w->wM.p, fill, bands.v1.p, P1, (const int *)nullptr, pstride)
-    if (unroll == 1) { IBH_RD(1); } else if (unroll == 2) { IBH_RD(2); } else if (unroll == 8) { IBH_RD(8); } else { IBH_RD(4); }
-#undef IBH_RD
-    hipLaunchKernelGGL(dual_combine_kernel, dim3((unsigned)ceil_div(w->nrow, 256), (unsigned)nvar, (unsigned)nbatch), dim3(256), 0, stream,
-                       P0, P1, ldp, pstride, bands.rb1.p, w->wM.p, fill, bp, ldb, w->nrow, nvar);
-    IBH_HIP(hipGetLastError());
-}
-
-// lanes of the sweep that carry a (batch, field) pair for nvar fields in launches of nbatch
-static int sweep_lanes(int nvar, int nbatch) { return nvar > 32 ? 64 : nvar * std::min(nbatch, 64 >> sweep_lg(nvar)); }
 // ---- colsweep (sweep_kernel.inl): E-row matrices, >= 32 fields ------------------------------------------------
 // Y[f, r] = the partial sums of the tasks that touch row r (comb_p[comb_ptr[r] .. comb_ptr[r+1])), in task order; rows no
 // task touches are 0, rows with wM == 0 hold `fill` (mask_result, IceCoupler.cpp:186-201).
@@ -1443,156 +1235,147 @@ __global__ __launch_bounds__(256) void sweep_combine_kernel(const double *__rest
     bp.y[q][(long)f * ldy + r] = wM[r] == 0.0 ? fill : tot;
 }
 static SweepView sweep_view(const Sweep &s) { return {s.task_p0.p, s.task_ns.p, s.col.p, s.meta.p, s.v0.p, s.v1.p, s.tb, s.nblk, s.nitems}; }
-static void launch_sweep(const ibh_weighted *w, const BatchPtrs &bp, int nbatch, int nvar, long lda, long ldb, double fill,
-                         hipStream_t stream)
-{
+
+// ---- launching a plan (apply_plan.h) --------------------------------------------------------------------------------------------
+// One launcher per instantiation, in the order of apply_plan.h's lists; launch_plan walks a plan: scratch, the launch events, the
+// grid check, the LDS limit and the name of the launch happen there, once.
+struct Launch {
+    const ibh_weighted *w; const ApplyPlan &p; const BatchPtrs &bp;
+    int nbatch, nvar; long lda, ldb; double fill; hipStream_t stream; const PairView *pair;
+    hipEvent_t ev0, ev1;            // launch timing (ibh_set_launch_events): attached to the first and the last dispatch of the apply
+    dim3 grid() const { return dim3(p.grid[0], p.grid[1], p.grid[2]); }
+};
+struct Launcher { const void *kernel; void (*run)(const Launch &); };
+
+template <int F, int NS, int SEG, int NW, bool PAIR>
+static void run_grouptile(const Launch &l) {
+    const RowGroups &grp = l.w->st.groups;
+    IBH_CHECK(grp.nslot <= NS && grp.tiles.seg == SEG, "row groups of %d rows / tiles of %d in a kernel for %d / %d", grp.nslot, grp.tiles.seg, NS, SEG);
+    static_assert(grouptile_lds(F, SEG) <= 64 * 1024, "within the default dynamic-LDS limit");
+    IBH_CHECK(!PAIR || l.nbatch == 1, "fused pair apply: %d batches not supported", l.nbatch);
+    hipExtLaunchKernelGGL((spmm_grouptile_kernel<F, NS, SEG, NW, PAIR>), l.grid(), dim3(NW * 64), l.p.lds, l.stream, l.ev0, l.ev1, 0, tile_view(grp), l.bp,
+                          l.lda, l.w->ncol, l.ldb, l.nvar, l.p.nfc, l.p.xcd_mode, l.w->wM.p, l.fill, PAIR ? *l.pair : PairView{});
+}
+template <bool FULL, bool IDENT>
+static void run_sweep(const Launch &l) {
+    const ibh_weighted *w = l.w;
     const Sweep &sweep = w->st.sweep;
-    DevBuf<double> &part = w->st.scr.sweep_part;
-    const int lg = sweep_lg(nvar), G = 64 >> lg;
-    const int nfb = lg == 6 ? ceil_div(nvar, 64) : 1, nz = lg == 6 ? nbatch : ceil_div(nbatch, G);
-    const long ldp = sweep.part_ld(nvar), pstride = sweep.part_stride(nvar);
-    grow_scratch(part, sweep.part_count(nvar, nbatch), stream, "column-sweep");
-    const SweepView sv = sweep_view(sweep);
+    const int lg = sweep_lg(l.nvar);
+    const long ldp = sweep.part_ld(l.nvar), pstride = sweep.part_stride(l.nvar);
+    double *part = w->st.scr.sweep_part.p;
     SweepBatch sb{};
-    for (int q = 0; q < nbatch; ++q) sb.x[q] = bp.x[q];
-    for (int zz = 0; zz < nz; ++zz) sb.p[zz] = part.p + (size_t)zz * (size_t)pstride;
-    const size_t lds = sweep_lds_bytes(sweep.nslot);
-    const bool full = lg == 6 ? nvar % 64 == 0 : (nvar == (1 << lg) && nbatch % G == 0);
-    const bool ident = sweep.ident != 0;
-    const void *fn = full ? (ident ? reinterpret_cast<const void *>(spmm_sweep_kernel<true, true, 0>) : reinterpret_cast<const void *>(spmm_sweep_kernel<true, false, 0>))
-                          : (ident ? reinterpret_cast<const void *>(spmm_sweep_kernel<false, true, 0>) : reinterpret_cast<const void *>(spmm_sweep_kernel<false, false, 0>));
-    if (lds > 64 * 1024) {                               // beyond the default dynamic-LDS limit: raise it once per device and variant
-        static std::mutex mu;
-        static bool raised[64][4] = {};
-        std::lock_guard<std::mutex> lk(mu);
-        const int dev = w->device & 63, var = (full ? 2 : 0) + (ident ? 1 : 0);
-        if (!raised[dev][var]) {
-            IBH_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            raised[dev][var] = true;
-        }
+    for (int q = 0; q < l.nbatch; ++q) sb.x[q] = l.bp.x[q];
+    for (unsigned zz = 0; zz < l.p.grid[2]; ++zz) sb.p[zz] = part + (size_t)zz * (size_t)pstride;
+    // launch timing: start = the sweep kernel begins, stop = the combine kernel ends (both belong to the apply)
+    hipExtLaunchKernelGGL((spmm_sweep_kernel<FULL, IDENT, 0>), l.grid(), dim3(SWEEP_NW * 64), l.p.lds, l.stream, l.ev0, nullptr, 0, sweep_view(sweep), sb,
+                          l.lda, l.nvar, sweep.nslot, ldp, lg, l.nbatch);
+    hipExtLaunchKernelGGL(sweep_combine_kernel, dim3((unsigned)ceil_div(w->nrow, 4), l.p.grid[1], (unsigned)l.nbatch), dim3(256), 0, l.stream, nullptr, l.ev1, 0,
+                          part, pstride, ldp, sweep.comb_ptr.p, sweep.comb_p.p, w->wM.p, l.fill, l.bp, l.ldb, w->nrow, l.nvar, lg);
+}
+template <int NW, int U, int TW, bool PAIR>
+static void run_rowgroup(const Launch &l) {
+    IBH_CHECK(!PAIR || (l.p.lds <= 64 * 1024 && l.nbatch == 1), "fused pair apply: %zu bytes of LDS / %d batches not supported", l.p.lds, l.nbatch);
+    hipExtLaunchKernelGGL((spmm_rowgroup_kernel<NW, U, TW, PAIR>), l.grid(), dim3(NW * 64), l.p.lds, l.stream, l.ev0, l.ev1, 0, group_view(l.w->st.groups), l.bp,
+                          l.lda, l.w->ncol, l.ldb, l.nvar, l.p.nfc, l.p.xcd_mode, l.w->wM.p, l.fill, PAIR ? *l.pair : PairView{});
+}
+// bands + combine: the events are recorded around the sequence
+template <int FPW, int WK, int U, int NW, bool DUAL>
+static void run_rowdual(const Launch &l) {
+    const ibh_weighted *w = l.w;
+    const Bands &bands = w->st.bands;
+    const long ldp = bands.part_ld(), pstride = bands.part_stride(l.nvar);
+    double *P0 = w->st.scr.band_part.p, *P1 = P0 + (size_t)l.nbatch * (size_t)pstride;
+    BatchPtrs bq{};
+    for (int q = 0; q < l.nbatch; ++q) { bq.x[q] = l.bp.x[q]; bq.y[q] = P0 + (size_t)q * (size_t)pstride; }
+    if (l.ev0) IBH_HIP(hipEventRecord(l.ev0, l.stream));
+    hipLaunchKernelGGL((spmm_rowblock_kernel<FPW, WK, U, NW, DUAL>), l.grid(), dim3(NW * 64), 0, l.stream, bands.ptr.p, bands.col.p, bands.v0.p, bq, l.nbatch, 1,
+                       l.lda, w->ncol, ldp, w->nrow, l.nvar, l.p.nfc, l.p.xcd_mode, w->wM.p, l.fill, bands.v1.p, P1, (const int *)nullptr, pstride);
+    hipLaunchKernelGGL(dual_combine_kernel, dim3((unsigned)ceil_div(w->nrow, 256), (unsigned)l.nvar, (unsigned)l.nbatch), dim3(256), 0, l.stream,
+                       P0, P1, ldp, pstride, bands.rb1.p, w->wM.p, l.fill, l.bp, l.ldb, w->nrow, l.nvar);
+    if (l.ev1) IBH_HIP(hipEventRecord(l.ev1, l.stream));
+}
+template <int NW, int U>
+static void run_rowone(const Launch &l) {
+    const ibh_weighted *w = l.w;
+    hipExtLaunchKernelGGL((spmm_rowone_kernel<NW, U>), l.grid(), dim3(NW * 64), 0, l.stream, l.ev0, l.ev1, 0, w->rowptr.p, w->colind.p, w->val.p,
+                          l.bp.x[0], l.bp.y[0], l.lda, w->ncol, l.ldb, w->nrow, l.nvar, l.p.nfc, l.p.xcd_mode, w->wM.p, l.fill);
+}
+template <int FPW, int WK, int U, int NW, bool DUAL>
+static void run_rowblock(const Launch &l) {
+    const ibh_weighted *w = l.w;
+    const int *rowperm = l.p.lpt && ensure_rowperm(w, l.stream) ? w->st.scr.rowperm.p : nullptr;
+    hipExtLaunchKernelGGL((spmm_rowblock_kernel<FPW, WK, U, NW, DUAL>), l.grid(), dim3(NW * 64), 0, l.stream, l.ev0, l.ev1, 0, w->rowptr.p, w->colind.p, w->val.p,
+                          l.bp, l.nbatch, l.p.qi, l.lda, w->ncol, l.ldb, w->nrow, l.nvar, l.p.nfc, l.p.xcd_mode, w->wM.p, l.fill,
+                          (const double *)nullptr, (double *)nullptr, rowperm, 0l);
+}
+// the I-row path: the events go to its first and last dispatch (transposed input + row kernel)
+template <bool NT, int G, bool REALIGN, bool XT>
+static void run_shortrow(const Launch &l) {
+    const ibh_weighted *w = l.w;
+    DevBuf<double> &xt = w->st.scr.xt;
+    const long xt_stride = (long)w->ncol * l.p.ldt;
+    hipEvent_t e_first = l.ev0;
+    if (XT) {
+        grow_scratch(xt, (size_t)xt_stride * (size_t)l.nbatch, l.stream, "transposed-input");
+        hipExtLaunchKernelGGL(transpose_fields_kernel, dim3((unsigned)ceil_div(w->ncol, 64), (unsigned)(l.p.ldt / 16), (unsigned)l.nbatch), dim3(256), 0, l.stream,
+                              e_first, nullptr, 0, l.bp, l.lda, l.nvar, w->ncol, xt.p, l.p.ldt, xt_stride);
+        e_first = nullptr;
     }
-    const dim3 grid((unsigned)sweep.ntask, (unsigned)nfb, (unsigned)nz);
+    hipExtLaunchKernelGGL((spmm_shortrow_kernel<NT, G, REALIGN, XT>), l.grid(), dim3(SR_THREADS), 0, l.stream, e_first, l.ev1, 0, w->rowptr.p, w->colind.p, w->val.p,
+                          l.bp, (const double *)xt.p, xt_stride, XT ? (long)l.p.ldt : l.lda, l.ldb, w->nrow, l.nvar, l.p.fper, w->wM.p, l.fill);
+}
+#define IBH_L_GT(...) {(const void *)spmm_grouptile_kernel<__VA_ARGS__>, run_grouptile<__VA_ARGS__>},
+#define IBH_L_SW(...) {(const void *)spmm_sweep_kernel<__VA_ARGS__, 0>, run_sweep<__VA_ARGS__>},
+#define IBH_L_RG(...) {(const void *)spmm_rowgroup_kernel<__VA_ARGS__>, run_rowgroup<__VA_ARGS__>},
+#define IBH_L_RD(...) {(const void *)spmm_rowblock_kernel<__VA_ARGS__>, run_rowdual<__VA_ARGS__>},
+#define IBH_L_R1(...) {(const void *)spmm_rowone_kernel<__VA_ARGS__>, run_rowone<__VA_ARGS__>},
+#define IBH_L_RB(...) {(const void *)spmm_rowblock_kernel<__VA_ARGS__>, run_rowblock<__VA_ARGS__>},
+#define IBH_L_SR(...) {(const void *)spmm_shortrow_kernel<__VA_ARGS__>, run_shortrow<__VA_ARGS__>},
+static const Launcher RUN_GROUPTILE[] = {IBH_GROUPTILE_INSTS(IBH_L_GT)}, RUN_SWEEP[] = {IBH_SWEEP_INSTS(IBH_L_SW)}, RUN_ROWGROUP[] = {IBH_ROWGROUP_INSTS(IBH_L_RG)},
+                      RUN_ROWDUAL[] = {IBH_ROWDUAL_INSTS(IBH_L_RD)}, RUN_ROWONE[] = {IBH_ROWONE_INSTS(IBH_L_R1)}, RUN_ROWBLOCK[] = {IBH_ROWBLOCK_INSTS(IBH_L_RB)},
+                      RUN_SHORTROW[] = {IBH_SHORTROW_INSTS(IBH_L_SR)};
+static const Launcher *const RUN[T_COUNT] = {RUN_GROUPTILE, RUN_SWEEP, RUN_ROWGROUP, RUN_ROWDUAL, RUN_ROWONE, RUN_ROWBLOCK, RUN_SHORTROW};
+
+// nbatch <= IBH_MAX_BATCH batches by plan p (of the same nbatch), p.per_launch at a time
+static void launch_plan(const ibh_weighted *w, const MatrixFacts &f, ApplyPlan p, const BatchPtrs &bp, int nbatch, int nvar, long lda, long ldb, double fill,
+                        hipStream_t stream, const PairView *pair = nullptr)
+{
+    ApplyState::Scratch &scr = w->st.scr;
+    if (p.band_part) grow_scratch(scr.band_part, p.band_part, stream, "band");
+    if (p.sweep_part) grow_scratch(scr.sweep_part, p.sweep_part, stream, "column-sweep");
+    // the transposed copies of a deep launch do not fit the scratch the handle owns: the launcher grows it -- unless the stream is
+    // being captured (no allocation there): then as many batches per launch as fit
+    if (p.xt * sizeof(double) > scr.xt.granted && p.per_launch > 1 && is_capturing(stream)) clamp_shortrow(p, f, nbatch, scr.xt.granted);
     hipEvent_t ev0 = g_ev_start, ev1 = g_ev_stop;
     g_ev_start = g_ev_stop = nullptr;
-    // launch timing: start = the sweep kernel begins, stop = the combine kernel ends (both belong to the apply)
-#define IBH_SW(F, I) snprintf(w->st.last_sig, sizeof(w->st.last_sig), "%s", "spmm_sweep_kernel<" #F ", " #I ", 0>"); \
-                     hipExtLaunchKernelGGL((spmm_sweep_kernel<F, I, 0>), grid, dim3(SWEEP_NW * 64), lds, stream, ev0, nullptr, 0, sv, sb, lda, nvar, sweep.nslot, ldp, lg, nbatch)
-    if (full) { if (ident) { IBH_SW(true, true); } else { IBH_SW(true, false); } }
-    else { if (ident) { IBH_SW(false, true); } else { IBH_SW(false, false); } }
-#undef IBH_SW
-    hipExtLaunchKernelGGL(sweep_combine_kernel, dim3((unsigned)ceil_div(w->nrow, 4), (unsigned)nfb, (unsigned)nbatch), dim3(256), 0, stream, nullptr, ev1, 0,
-                       part.p, pstride, ldp, sweep.comb_ptr.p, sweep.comb_p.p, w->wM.p, fill,
-                       bp, ldb, w->nrow, nvar, lg);
+    for (int q0 = 0; q0 < nbatch; q0 += p.per_launch) {
+        const int nq = std::min(p.per_launch, nbatch - q0);
+        BatchPtrs bq{};
+        bool misaligned = (ldb & 7) != 0;
+        for (int q = 0; q < nq; ++q) {
+            bq.x[q] = bp.x[q0 + q]; bq.y[q] = bp.y[q0 + q];
+            misaligned = misaligned || (reinterpret_cast<uintptr_t>(bq.y[q]) & 63) != 0;
+        }
+        if (p.family == KERNEL_SHORTROW) align_shortrow(p, f, nvar, misaligned, nq);
+        IBH_CHECK(p.inst >= 0 && p.inst < INSTS[p.table].n, "no apply kernel for this plan (table %d)", p.table);
+        IBH_CHECK(p.nblocks < (1l << 31), "spmm grid too large (%ld blocks)", p.nblocks);
+        IBH_CHECK(p.table == T_SHORTROW || p.table == T_SWEEP || (long)w->ncol * 8 < (1l << 31), "ncol too large for 32-bit buffer offsets");
+        const Launcher &run = RUN[p.table][p.inst];
+        if (p.lds > 64 * 1024) {                             // beyond the default dynamic-LDS limit: raise it once per device and kernel
+            static std::mutex mu;
+            static std::set<std::pair<int, const void *>> raised;
+            std::lock_guard<std::mutex> lk(mu);
+            if (!raised.count({w->device, run.kernel})) {
+                IBH_HIP(hipFuncSetAttribute(run.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+                raised.insert({w->device, run.kernel});
+            }
+        }
+        snprintf(w->st.last_sig, sizeof(w->st.last_sig), "%s", INSTS[p.table].v[p.inst].sig);
+        run.run(Launch{w, p, bq, nq, nvar, lda, ldb, fill, stream, pair, q0 == 0 ? ev0 : nullptr, q0 + p.per_launch >= nbatch ? ev1 : nullptr});
+    }
     IBH_HIP(hipGetLastError());
 }
 
-// which kernel serves (w, nvar)
-static ApplyKernel pick_kernel(const ibh_weighted *w, int nvar, int nbatch = 1) {
-    ApplyKernel kernel = w->kernel_override;
-    if (kernel == KERNEL_COLSWEEP && !w->st.sweep.built()) kernel = KERNEL_AUTO;      // no column-sweep structure: the automatic choice
-    if (kernel == KERNEL_AUTO) {
-        // rowblock = one workgroup per (row, field chunk): for FEW LONG rows.  Many rows of 6..63 entries (a smoothed IvE:
-        // 76 k rows of ~16) are thread-per-row work (measured, 5 km smoothed IvE, 16 fields: 220 us as rowblock)
-        const double mean = w->nrow ? (double)w->nnz / (double)w->nrow : 0.0;
-        const bool few_rows = w->nrow <= get_tuning("rowblock_max_short_rows", 16384);
-        kernel = (mean >= 64.0 || (few_rows && mean >= (double)get_tuning("rowblock_min_mean_nnz", 6))) ? KERNEL_ROWBLOCK : KERNEL_SHORTROW;
-    }
-    // E-row matrices (EvI, EvX), once the structure exists: the row groups (every X element gathered once per GCM cell; measured
-    // against the sweep at 1 km, 64 fields: 221 against 247 us one launch per apply, 199 against 203-223 batched) -- except
-    // batched launches of FEWER than 32 fields, where the batches share the lanes of the column sweep (1 km, 16 fields, 16 per
-    // launch: 51 against 63 us per apply).  The other long-row matrices (AvI, AvX) take the sweep in batched launches only
-    // (1 km, 64 fields: 167 against 173 us per apply 32 deep, but 193 against 183 us one launch per apply).
-    if (kernel == KERNEL_ROWBLOCK && w->kernel_override == KERNEL_AUTO) {
-        // (round 4, the Antarctic sheet -- 17.6 / 35.2 M entries -- one apply per launch: AvI, 128 fields, sweep 3 131 against 3 654 us;
-        // EvI, 16 fields, row groups 641 against 812 (bands) / 747 (rows) / 1 994 us (sweep): scratch/kernel_choice.py)
-        const bool huge = w->nnz >= (1l << 24);
-        const bool sweep_ok = w->st.sweep.built() && sweep_lanes(nvar, nbatch) >= get_tuning("sweep_min_nvar", 32) && get_tuning("sweep_auto", 1) &&
-                              (w->band_eligible || nbatch >= get_tuning("sweep_min_batch", 4) || (huge && nvar >= 128));
-        const bool grp_ok = w->st.groups.built() && nvar >= 4 && get_tuning("rowgroup_auto", 1);
-        // (round 5: on matrices of 2^24 entries and more the tiled row groups beat the sweep in batched launches of few fields too --
-        // the Antarctic EvI, 16 fields, batches of 4: bench.py 0.487 of peak through the sweep, measured again below)
-        const bool tiles_win = w->st.groups.tiles.built() && w->nnz >= (1l << 24) && get_tuning("rowgroup_form", -1) != 0;
-        if (grp_ok && (nvar >= 32 || !sweep_ok || tiles_win)) kernel = KERNEL_ROWGROUP;
-        else if (sweep_ok) kernel = KERNEL_COLSWEEP;
-    }
-    if (kernel == KERNEL_ROWGROUP && !w->st.groups.built()) kernel = KERNEL_ROWBLOCK;     // no row groups were built for this matrix
-    if (kernel == KERNEL_ROWBLOCK && w->kernel_override == KERNEL_AUTO && w->st.bands.built() && nvar >= 4 && get_tuning("rowdual_auto", 1))
-        kernel = KERNEL_ROWDUAL;
-    if (kernel == KERNEL_ROWDUAL && !w->st.bands.built()) kernel = KERNEL_ROWBLOCK;       // no bands were built for this matrix
-    return kernel;
-}
-struct ShortrowPlan { int fper, g, use_xt, ldt; bool one_entry, big; };
-static ShortrowPlan shortrow_plan(const ibh_weighted *w, int nvar, int nbatch = 1) {
-    // fields per thread.  At 1 km (1.9 M rows) the stores dominate and 16-32 fields per thread amortise the row's CSR reads.
-    // Small problems (5 km: 76 k rows): round-2 sweep with the batched kernel (scratch/one_matrix.py, us per 64-field apply,
-    // one launch / 16 per launch): one entry per row (IvA) 8 fields x transposed input 12.1 / 7.0 (4 fields, field-major:
-    // 13.2 / 9.7); 2-3 entries (IvE) 16 fields 16.5 / 9.9, 32 fields 19.2 / 9.5 -- more fields per thread pay in deep launches.
-    ShortrowPlan p;
-    p.one_entry = (double)w->nnz <= 1.5 * (double)w->nrow;
-    p.big = w->nrow >= (1 << 19);
-    // (2-3 entries, one launch of <= 32 fields: 4 fields per thread, field-major 8.2 us against 14.2 through the transposed copy)
-    // (32 fields: 13.7 against 16.0; rows of 2-3 entries only: a smoothed IvE -- ~16 entries per row -- needs the lines of the
-    // transposed copy: 59.6 against 143 us at 16 fields)
-    const bool few_fields_once = nbatch < 4 && nvar <= 32 && (double)w->nnz <= 4.0 * (double)w->nrow;
-    const int small_multi = nbatch >= 4 ? 32 : few_fields_once ? 4 : 16;
-    // (round 3, kernel durations by dispatch events instead of wall time: ONE launch of a one-entry matrix at 5 km is fastest
-    // field-major with 4 fields per thread -- 64 fields 13.2 us against 15.8 through the transposed copy, whose second
-    // launch costs more than its lines save; 16 fields 5.6 against 6.8; deep launches keep the transposed form: 7.0)
-    const int small_one = w->nrow >= 16384 ? (nbatch >= 4 ? 8 : nvar >= 64 ? 16 : 4) : 4;
-    // (round 4, the Antarctic sheet -- 17.2 M one-entry rows, results of 2.2 / 17.6 GB: groups of 4 fields and, from ~100 fields on,
-    // 32 fields per thread: 16 fields 579 -> 546 us, 128 fields 4 761 -> 3 829 us = 0.45 -> 0.56 of 8 TB/s; scratch/tune_shortrow.py)
-    const bool huge = w->nrow >= (1 << 23);
-    p.fper = get_tuning("shortrow_fper", p.big ? (p.one_entry ? (huge && nvar >= 96 ? 32 : 16) : 32) : (p.one_entry ? small_one : small_multi));
-    if (p.fper < 1) p.fper = 1;
-    p.g = get_tuning("shortrow_group", p.big ? (p.one_entry ? (huge ? 4 : 8) : 4) : (p.fper >= 8 ? 8 : 4));
-    if (p.g > p.fper) p.g = p.fper;
-    // transposed input: the G fields of an entry are 8*G contiguous bytes per lane (one line per entry instead of one per
-    // field): 5 km IvE 26.9 -> 18.5 us, 1 km IvE 302 -> 183 us, 1 km IvA 207 -> 176 us, 5 km IvA 13.2 -> 12.1 us
-    p.use_xt = get_tuning("shortrow_xt", -1);
-    // (one-entry matrices: the extra launch costs more than it saves for tiny matrices -- EvA: 4.9 -> 8.9 us -- and for a
-    // single launch of few fields -- 5 km IvA, 16 fields: 7.5 -> 9.3 us)
-    if (p.use_xt < 0) p.use_xt = ((!p.one_entry && !(few_fields_once && !p.big)) || p.big || (w->nrow >= 16384 && nbatch >= 4)) ? 1 : 0;
-    if (p.fper % p.g != 0 || (p.g & 1)) p.use_xt = 0;
-    p.ldt = (nvar + 15) & ~15;
-    return p;
-}
-
-// ---- lazily built apply structures (column sweep, bands) ---------------------------------------------------
-// Which structure applies of (nvar fields, nbatch per launch) would use, by the rules the apply path has always had;
-// `seen` = the matrix has been applied before (an apply builds on the SECOND call only: the coupler's one build : one apply
-// must not pay for a structure it never reuses; ibh_weighted_prepare builds at once).
-static bool wants_sweep(const ibh_weighted *w, int nvar, int nbatch, bool seen) {
-    if (w->st.sweep_tried || w->st.sweep.built()) return false;
-    if (w->kernel_override == KERNEL_COLSWEEP) return true;
-    const bool long_rows = w->nrow > 0 && (double)w->nnz / (double)w->nrow >= 64.0 && w->nnz <= 2 * (int64_t)w->ncol;      // AvI, AvX
-    const bool e_rows = w->band_eligible && (nvar < 32 || (w->st.groups_tried && !w->st.groups.built()) || !get_tuning("rowgroup_auto", 1));
-    const bool huge_wide = w->nnz >= (1l << 24) && nvar >= 128;      // (one launch of >= 128 fields on the Antarctic AvI: see launch_kernel_for)
-    return (e_rows || (long_rows && (nbatch >= get_tuning("sweep_min_batch", 4) || huge_wide))) && w->kernel_override == KERNEL_AUTO && seen &&
-           sweep_lanes(nvar, nbatch) >= get_tuning("sweep_min_nvar", 32) && get_tuning("sweep_auto", 1) &&
-           (double)w->nnz * sweep_lanes(nvar, nbatch) >= (double)get_tuning("sweep_min_work", 64 << 20);
-}
-static bool wants_bands(const ibh_weighted *w, int nvar, bool seen) {
-    return w->band_eligible && !w->st.bands_tried && !w->st.bands.built() && !w->st.sweep.built() && seen && w->kernel_override == KERNEL_AUTO && nvar >= 4 &&
-           (double)w->nnz * nvar >= (double)get_tuning("rowdual_min_work", 128 << 20) && get_tuning("rowdual_auto", 1);
-}
-// Row groups (rowgroup kernel) of an E-row matrix: bandwidth-sized matrices applied to >= 32 fields get them like the sweep
-// always got its structure -- on the SECOND apply, or at once in ibh_weighted_prepare; with fewer fields such a matrix takes the
-// sweep (batches share its lanes).  Small matrices (5 km: the sweep is latency-bound there) get them from ibh_weighted_prepare
-// only: the structure costs about as much as the matrix build itself, and an apply that switched kernels on its own would change
-// the rounding of later results against earlier ones (ibh_set_tuning("rowgroup_after", n) asks for exactly that, from the
-// n-th apply on).
-static bool sweep_sized(const ibh_weighted *w, int nvar, int nbatch) {
-    return (double)w->nnz * std::max(sweep_lanes(nvar, nbatch), std::min(nvar, 64)) >= (double)get_tuning("sweep_min_work", 64 << 20);
-}
-static bool wants_groups(const ibh_weighted *w, int nvar, int nbatch, long seen, bool asked) {
-    if (!w->band_eligible || w->st.groups_tried || w->st.groups.built()) return false;
-    if (asked || w->kernel_override == KERNEL_ROWGROUP) return true;
-    if (w->kernel_override != KERNEL_AUTO || nvar < 4 || !get_tuning("rowgroup_auto", 1)) return false;
-    // (bandwidth-sized matrices: from 32 fields -- fewer fields per launch share the lanes of the column sweep when launches are
-    // batched; a single launch of a 2^24-entry matrix takes the groups from 4 fields on)
-    if (sweep_sized(w, nvar, nbatch)) return (nvar >= 32 || (nbatch < 4 && w->nnz >= (1l << 24))) && seen >= 1;
-    return seen >= get_tuning("rowgroup_after", 1 << 30);
-}
 // A structure that cannot be built (out of memory, not representable) is no reason to fail an apply the row-by-row kernel
 // serves: the failure is swallowed, the structure marked as tried, the matrix keeps its kernel.  Never inside a capture.
 // `groups_asked`: the caller needs the row groups whatever the rules say (ibh_weighted_pair_prepare), and nothing else.
@@ -1600,9 +1383,9 @@ static void build_structures(const ibh_weighted *w, int nvar, int nbatch, bool s
                              bool groups_asked = false) {
     ApplyState &st = w->st;
     const long ns = seen ? nseen : 0;
-    auto groups = [&] { return wants_groups(w, nvar, nbatch, ns, groups_asked); };
-    auto sweep = [&] { return !groups_asked && wants_sweep(w, nvar, nbatch, seen); };
-    auto bands = [&] { return !groups_asked && !st.groups.built() && wants_bands(w, nvar, seen); };
+    auto groups = [&] { return wants_groups(facts_of(*w), nvar, nbatch, ns, groups_asked); };
+    auto sweep = [&] { return !groups_asked && wants_sweep(facts_of(*w), nvar, nbatch, seen); };
+    auto bands = [&] { return !groups_asked && !st.groups.built() && wants_bands(facts_of(*w), nvar, seen); };
     if ((!groups() && !sweep() && !bands()) || is_capturing(stream)) return;
     // (a builder hands over a finished structure or none: nothing to undo when it throws)
     auto attempt = [](bool &tried, auto &&build) {
@@ -1614,32 +1397,30 @@ static void build_structures(const ibh_weighted *w, int nvar, int nbatch, bool s
     if (bands()) attempt(st.bands_tried, [&] { st.bands = build_bands_from_csr(w, stream); });
 }
 
-// Scratch of every kernel that applies of (nvar, <= nbatch per launch) can pick -- all of them: a later
-// ibh_weighted_set_kernel, or a tuning change, must not turn a captured apply into an allocation.
+// Scratch of the launches that applies of (nvar, <= nbatch per launch) can make, by the family the rules pick and by those whose structure exists: a
+// later set_kernel or tuning change must not turn a captured apply into an allocation.  (Shortrow's transposed input: where shortrow is the pick only.)
 static size_t consv_count(const ibh_weighted *w, int nvar) { return 2 * (size_t)nvar + weight_dot_scratch(std::max(w->nrow, w->ncol), nvar); }
 static void size_scratch(const ibh_weighted *w, int nvar, int nbatch) {
-    ApplyState &st = w->st;
-    if (st.bands.built()) grow_scratch(st.scr.band_part, st.bands.part_count(nvar, nbatch), nullptr, "band");
-    if (st.sweep.built()) grow_scratch(st.scr.sweep_part, st.sweep.part_count(nvar, nbatch), nullptr, "column-sweep");
-    if (pick_kernel(w, nvar, nbatch) == KERNEL_SHORTROW || pick_kernel(w, nvar, 1) == KERNEL_SHORTROW || w->kernel_override == KERNEL_AUTO) {
-        for (int nb : {1, nbatch}) {
-            const ShortrowPlan p = shortrow_plan(w, nvar, nb);
-            const int qmax = std::max(1, get_tuning("shortrow_many", w->nrow >= (1 << 19) ? 1 : IBH_MAX_BATCH));
-            if (p.use_xt && (pick_kernel(w, nvar, nb) == KERNEL_SHORTROW || w->kernel_override == KERNEL_SHORTROW))
-                grow_scratch(st.scr.xt, (size_t)w->ncol * (size_t)p.ldt * (size_t)std::min(qmax, nb), nullptr, "transposed-input");
+    ApplyState::Scratch &scr = w->st.scr;
+    const MatrixFacts f = facts_of(*w);
+    for (int nb : {1, nbatch})
+        for (ApplyKernel k : {plan_apply(f, nvar, nb, false).family, KERNEL_ROWDUAL, KERNEL_COLSWEEP}) {
+            if ((k == KERNEL_ROWDUAL && !f.bands_built) || (k == KERNEL_COLSWEEP && !f.sweep_built)) continue;
+            const ApplyPlan p = plan_launch(f, k, nvar, nb, false);
+            if (p.band_part) grow_scratch(scr.band_part, p.band_part, nullptr, "band");
+            if (p.sweep_part) grow_scratch(scr.sweep_part, p.sweep_part, nullptr, "column-sweep");
+            if (p.xt) grow_scratch(scr.xt, p.xt, nullptr, "transposed-input");
         }
-    }
-    grow_scratch(st.scr.consv, consv_count(w, nvar), nullptr, "conservation");
+    grow_scratch(scr.consv, consv_count(w, nvar), nullptr, "conservation");
     // apply_transformed: the small side holds nvar fields
-    grow_scratch(st.scr.scratch, (size_t)nvar * (size_t)std::min(w->nrow, w->ncol), nullptr, "transform");
+    grow_scratch(scr.scratch, (size_t)nvar * (size_t)std::min(w->nrow, w->ncol), nullptr, "transform");
     ensure_rowsum1(w, nullptr);
     if (get_tuning("rowblock_lpt", 0)) (void)ensure_rowperm(w, nullptr);
 }
 
 void weighted_reserve(const ibh_weighted *w, int nvar) {
     HandleScope hs_(w);
-    if (nvar <= 0) return;
-    size_scratch(w, nvar, 1);
+    if (nvar > 0) size_scratch(w, nvar, 1);
 }
 
 void weighted_prepare(const ibh_weighted *w, int nvar, int nbatch, bool groups_asked) {
@@ -1650,7 +1431,6 @@ void weighted_prepare(const ibh_weighted *w, int nvar, int nbatch, bool groups_a
     size_scratch(w, nvar, nb);
     IBH_HIP(hipStreamSynchronize(nullptr));
 }
-
 // ---- fused pair: B1 = first * A, B2 = second * B1 in one launch (BASELINE config 3: EvI then AvE) --------------------------------
 // Possible when every row of `second` reads rows of ONE row group of `first` only -- AvE after EvI: the value of a GCM cell is a
 // combination of that cell's own elevation classes -- so the group's workgroup has all inputs of the second row in hand when
@@ -1724,25 +1504,6 @@ void weighted_pair_prepare(const ibh_weighted *first, const ibh_weighted *second
     grp.pair = std::move(pair);
 }
 
-// The row-group apply in whichever form and instantiation serves (w, nvar); `pair`: with the second matrix of a fused pair in
-// the epilogue.
-static void launch_rowgroup_any(const ibh_weighted *w, const BatchPtrs &bp, int nbatch, int nvar, long lda, long ldb, double fill, hipStream_t stream,
-                                const PairView *pair = nullptr)
-{
-    if (use_grouptile(w, nvar)) return launch_grouptile_any(w, bp, nbatch, nvar, lda, ldb, fill, stream, pair);
-    // 8 waves (fields) share a staged segment from 32 fields (5 km, 64 fields: 17.1 against 19.3 us with 4)
-    const int u = get_tuning("rowgroup_unroll", 8), nw = get_tuning("rowgroup_waves", nvar >= 32 ? 8 : 4);
-    // class tables of half width (two lanes per entry) for the small matrices: all workgroups of a 5 km launch fit the LDS at
-    // once -- 16 applies per launch 13.5 -> 12.3 us (64 fields), 3.96 -> 3.37 (16 fields), one launch unchanged (17.6 / 17.8);
-    // at 1 km the doubled atomic instructions cost 223 -> 238 us.  By the matrix alone, so one apply and a batch agree bitwise.
-    const int tw = get_tuning("rowgroup_tw", w->nnz < (1 << 20) ? 32 : 64);
-#define IBH_RG(N, UU, TT) launch_rowgroup<N, UU, TT>(w, bp, nbatch, nvar, lda, ldb, fill, stream, pair)
-    if (tw == 32) { if (nw == 8) { if (u <= 8) IBH_RG(8, 8, 32); else IBH_RG(8, 16, 32); } else { if (u <= 4) IBH_RG(4, 4, 32); else IBH_RG(4, 8, 32); } }
-    else if (nw == 8) { if (u <= 8) IBH_RG(8, 8, 64); else IBH_RG(8, 16, 64); }
-    else { if (u <= 4) IBH_RG(4, 4, 64); else if (u <= 8) IBH_RG(4, 8, 64); else IBH_RG(4, 16, 64); }
-#undef IBH_RG
-}
-
 void spmm_launch_pair(const ibh_weighted *first, const ibh_weighted *second, const double *dA, int nvar, int64_t lda, double *dB1,
                       int64_t ldb1, double *dB2, int64_t ldb2, double fill, hipStream_t stream)
 {
@@ -1757,7 +1518,8 @@ void spmm_launch_pair(const ibh_weighted *first, const ibh_weighted *second, con
     BatchPtrs bp{};
     bp.x[0] = dA; bp.y[0] = dB1;
     const PairView pv = pair_view(pair, dB2, (long)ldb2);
-    launch_rowgroup_any(first, bp, 1, nvar, (long)lda, (long)ldb1, fill, stream, &pv);
+    const MatrixFacts f = facts_of(*first);
+    launch_plan(first, f, plan_apply(f, nvar, 1, true), bp, 1, nvar, (long)lda, (long)ldb1, fill, stream, &pv);
     first->st.last_kernel = KERNEL_ROWGROUP;
     second->st.last_kernel = KERNEL_ROWGROUP;
     ++first->st.napply; ++second->st.napply;
@@ -1773,138 +1535,6 @@ void spmm_launch_chain(const ibh_weighted *first, const ibh_weighted *second, co
     spmm_launch(third, dB2, nvar, ldb2, dB3, ldb3, fill, 0, stream);
 }
 
-static void launch_one_impl(const ibh_weighted *w, ApplyKernel kernel, const BatchPtrs &bp, int nbatch, int nvar, int64_t lda,
-                            int64_t ldb, double fill, hipStream_t stream);
-static void launch_one(const ibh_weighted *w, ApplyKernel kernel, const BatchPtrs &bp, int nbatch, int nvar, int64_t lda,
-                       int64_t ldb, double fill, hipStream_t stream)
-{
-    // launch timing (ibh_set_launch_events): the single-kernel paths attach the events to their dispatch, the I-row path
-    // to its first and last one (transposed input + row kernel); bands + combine records them around the sequence
-    if (kernel == KERNEL_ROWDUAL && g_ev_start && g_ev_stop) {
-        hipEvent_t ev0 = g_ev_start, ev1 = g_ev_stop;
-        g_ev_start = g_ev_stop = nullptr;
-        IBH_HIP(hipEventRecord(ev0, stream));
-        launch_one_impl(w, kernel, bp, nbatch, nvar, lda, ldb, fill, stream);
-        IBH_HIP(hipEventRecord(ev1, stream));
-        return;
-    }
-    launch_one_impl(w, kernel, bp, nbatch, nvar, lda, ldb, fill, stream);
-}
-static void launch_one_impl(const ibh_weighted *w, ApplyKernel kernel, const BatchPtrs &bp, int nbatch, int nvar, int64_t lda,
-                            int64_t ldb, double fill, hipStream_t stream)
-{
-    if (kernel == KERNEL_ROWGROUP) {
-        launch_rowgroup_any(w, bp, nbatch, nvar, (long)lda, (long)ldb, fill, stream);
-    } else if (kernel == KERNEL_COLSWEEP) {
-        launch_sweep(w, bp, nbatch, nvar, (long)lda, (long)ldb, fill, stream);
-    } else if (kernel == KERNEL_ROWDUAL) {
-        const long pairs = (long)w->nrow * nvar;
-        const int fpw = get_tuning("rowdual_fpw", pairs >= 4 * 8192 ? 4 : pairs >= 2 * 8192 ? 2 : 1);
-        if (fpw >= 4) launch_rowdual<4>(w, bp, nbatch, nvar, (long)lda, (long)ldb, fill, stream);
-        else if (fpw == 2) launch_rowdual<2>(w, bp, nbatch, nvar, (long)lda, (long)ldb, fill, stream);
-        else launch_rowdual<1>(w, bp, nbatch, nvar, (long)lda, (long)ldb, fill, stream);
-    } else if (kernel == KERNEL_ROWBLOCK) {
-        int fpw = get_tuning(nbatch > 1 ? "rowblock_many_fpw" : "rowblock_fpw", 0), wk = get_tuning("rowblock_wk", 0);
-        if (fpw == 0 || wk == 0) {
-            // enough workgroups to give every CU ~8: small problems are latency-bound and want many
-            // small tasks, big ones amortise the staged row segment over more fields
-            const long pairs = (long)w->nrow * nvar;
-            if (nvar >= 16 && pairs >= 4 * 8192) { fpw = 4; wk = 1; }
-            else if (nvar >= 8 && pairs >= 2 * 8192) { fpw = 2; wk = 1; }
-            else if (nvar >= 4) { fpw = 1; wk = 1; }
-            else if (nvar >= 2) { fpw = 1; wk = 2; }
-            else { fpw = 1; wk = 4; }
-        }
-        // deep batched launches: 8 waves (8 fields) per workgroup halve the workgroup count per batch
-        // (measured at the 5 km headline shape, depth 16: 7.36 against 7.51 us per apply)
-        // one apply per launch, >= 8 fields, rows of a few hundred entries: the lean kernel (same bits as rowblock with wk == 1)
-        const double mean_len = w->nrow ? (double)w->nnz / (double)w->nrow : 0.0;
-        const int rowone = get_tuning("rowone", nbatch == 1 && wk == 1 && nvar >= 32 && mean_len >= 192.0 && mean_len <= 1024.0 ? 1 : 0);
-        if (rowone && nbatch == 1 && wk == 1) {
-            int u = get_tuning("rowone_unroll", mean_len > 768.0 ? 16 : 14), nw = get_tuning("rowone_waves", 8);
-            const double *X1 = bp.x[0];
-            double *Y1 = bp.y[0];
-#define IBH_R1(N, UU) launch_rowone<N, UU>(w, X1, Y1, nvar, (long)lda, (long)ldb, fill, stream)
-            // (4 waves: a lane stages twice the entries, and 16 gathers no longer fit 64 registers: they spill; 14)
-            if (nw == 4) { if (u <= 8) IBH_R1(4, 8); else if (u <= 12) IBH_R1(4, 12); else IBH_R1(4, 14); }
-            else { if (u <= 8) IBH_R1(8, 8); else if (u <= 12) IBH_R1(8, 12); else if (u <= 14) IBH_R1(8, 14); else IBH_R1(8, 16); }
-#undef IBH_R1
-            return;
-        }
-        const int nw = get_tuning("rowblock_waves", nbatch >= 8 && fpw == 1 && wk == 1 ? 8 : 4);
-#define IBH_L(F, K, N) launch_rowblock<F, K, N>(w, bp, nbatch, nvar, (long)lda, (long)ldb, fill, stream)
-        if (nw == 8 && wk == 1) {
-            if (fpw == 1) IBH_L(1, 1, 8); else if (fpw == 2) IBH_L(2, 1, 8); else IBH_L(4, 1, 8);
-        } else if (fpw == 4 && wk == 1) IBH_L(4, 1, 4);
-        else if (fpw == 8 && wk == 1) IBH_L(8, 1, 4);
-        else if (fpw == 2 && wk == 1) IBH_L(2, 1, 4);
-        else if (fpw == 1 && wk == 1) IBH_L(1, 1, 4);
-        else if (fpw == 4 && wk == 2) IBH_L(4, 2, 4);
-        else if (fpw == 2 && wk == 2) IBH_L(2, 2, 4);
-        else if (fpw == 1 && wk == 2) IBH_L(1, 2, 4);
-        else if (fpw == 2 && wk == 4) IBH_L(2, 4, 4);
-        else if (fpw == 4 && wk == 4) IBH_L(4, 4, 4);
-        else IBH_L(1, 4, 4);
-#undef IBH_L
-    } else {                                                    // KERNEL_SHORTROW
-        const ShortrowPlan p = shortrow_plan(w, nvar, nbatch);
-        const int fper = p.fper, g = p.g;
-        const long xt_stride = (long)w->ncol * p.ldt;
-        DevBuf<double> &xt = w->st.scr.xt;
-        // GB-sized results: deep launches cost the L2 locality of the row slices (measured at 1 km: 148 us per apply alone,
-        // 181 us sixteen deep); they go out a few batches at a time
-        int qmax = std::max(1, get_tuning("shortrow_many", w->nrow >= (1 << 19) ? 1 : IBH_MAX_BATCH));
-        if (p.use_xt && qmax > 1 && (size_t)xt_stride * sizeof(double) * (size_t)std::min(qmax, nbatch) > xt.granted) {
-            // the transposed copies of a deep launch do not fit the scratch the handle owns: grow it -- unless the stream is
-            // being captured (no allocation there): then as many batches per launch as fit
-            if (is_capturing(stream)) qmax = std::max(1, (int)(xt.granted / ((size_t)xt_stride * sizeof(double))));
-        }
-        hipEvent_t ev0 = g_ev_start, ev1 = g_ev_stop;
-        g_ev_start = g_ev_stop = nullptr;
-        for (int q0 = 0; q0 < nbatch; q0 += qmax) {
-            const int nq = std::min(qmax, nbatch - q0);
-            hipEvent_t e_first = q0 == 0 ? ev0 : nullptr, e_last = q0 + qmax >= nbatch ? ev1 : nullptr;
-            BatchPtrs bq{};
-            bool misaligned = (ldb & 7) != 0;
-            for (int q = 0; q < nq; ++q) {
-                bq.x[q] = bp.x[q0 + q]; bq.y[q] = bp.y[q0 + q];
-                misaligned = misaligned || (reinterpret_cast<uintptr_t>(bq.y[q]) & 63) != 0;
-            }
-            if (p.use_xt) grow_scratch(xt, (size_t)xt_stride * (size_t)nq, stream, "transposed-input");
-            // planes of B that do not start on 64-byte lines are re-aligned through LDS (see the kernel)
-            const bool realign = get_tuning("shortrow_realign", -1) >= 0 ? get_tuning("shortrow_realign", -1) != 0
-                               : misaligned && w->nrow >= (1 << 18);   // below: latency-bound, the two extra barriers cost more
-            const long nblk = (long)ceil_div(w->nrow, realign ? SR_STEP : SR_THREADS) * ceil_div(nvar, fper);
-            IBH_CHECK(nblk < (1l << 31), "spmm grid too large (%ld blocks)", nblk);
-            dim3 grid((unsigned)nblk, (unsigned)nq);
-            long xld = (long)lda;
-            if (p.use_xt) {
-                hipExtLaunchKernelGGL(transpose_fields_kernel, dim3((unsigned)ceil_div(w->ncol, 64), (unsigned)(p.ldt / 16), (unsigned)nq), dim3(256), 0, stream,
-                                      e_first, nullptr, 0, bq, (long)lda, nvar, w->ncol, xt.p, p.ldt, xt_stride);
-                e_first = nullptr;
-                xld = p.ldt;
-            }
-#define IBH_SR4(NT, GG, RA, XTT)                                                                                        \
-    snprintf(w->st.last_sig, sizeof(w->st.last_sig), "%s", "spmm_shortrow_kernel<" #NT ", " #GG ", " #RA ", " #XTT ">");      \
-    hipExtLaunchKernelGGL((spmm_shortrow_kernel<NT, GG, RA, XTT>), grid, dim3(SR_THREADS), 0, stream, e_first, e_last, 0,  \
-                          w->rowptr.p, w->colind.p, w->val.p, bq, (const double *)xt.p, xt_stride, xld, (long)ldb,       \
-                          w->nrow, nvar, fper, w->wM.p, fill)
-#define IBH_SR(NT, GG)                                                                                          \
-    do {                                                                                                        \
-        if (realign) { if (p.use_xt) { IBH_SR4(NT, GG, true, true); } else { IBH_SR4(NT, GG, true, false); } }  \
-        else { if (p.use_xt) { IBH_SR4(NT, GG, false, true); } else { IBH_SR4(NT, GG, false, false); } }        \
-    } while (0)
-            const bool nt = get_tuning("shortrow_nt", 1) != 0;
-            if (g >= 16) { if (nt) IBH_SR(true, 16); else IBH_SR(false, 16); }
-            else if (g >= 8) { if (nt) IBH_SR(true, 8); else IBH_SR(false, 8); }
-            else { if (nt) IBH_SR(true, 4); else IBH_SR(false, 4); }
-#undef IBH_SR4
-#undef IBH_SR
-        }
-        IBH_HIP(hipGetLastError());
-    }
-}
-
 void spmm_launch_many(const ibh_weighted *w, int nbatch, const double *const *dA, int nvar, int64_t lda,
                       double *const *dB, int64_t ldb, double fill, int force_conservation, hipStream_t stream)
 {
@@ -1912,20 +1542,15 @@ void spmm_launch_many(const ibh_weighted *w, int nbatch, const double *const *dA
     if (nvar <= 0 || w->nrow == 0 || nbatch <= 0) return;
     IBH_CHECK(lda >= w->ncol && ldb >= w->nrow, "apply: leading dimensions (%ld, %ld) smaller than (%d, %d)",
               (long)lda, (long)ldb, w->ncol, w->nrow);
-    // An E-row matrix that is applied again gets its band structure now (every ice cell carries the weights of BOTH
-    // classes it lies between and is read once instead of twice): pays for a matrix that meets many field batches, not
-    // for the coupler's one build : one apply, hence on the second apply and only for bandwidth-sized work (measured, 64
-    // fields: 1 km EvI 292 -> 255 us; at 5 km the extra combine pass costs more than the halved traffic saves, 18.5 -> 21.9).
-    // ... or, with >= 32 fields, the column-sweep structure (sweep_kernel.inl): every X element read once, in whole lines.
+    // A matrix that is applied again gets the structures its applies want now (wants_bands, wants_sweep, wants_groups: apply_plan.h).
     // This is the one place where an apply synchronises and allocates: ibh_weighted_prepare() does it up front,
     // ibh_set_tuning("lazy_structures", 0) switches it off.
     if (get_tuning("lazy_structures", 1)) build_structures(w, nvar, std::min(nbatch, IBH_MAX_BATCH), w->st.napply >= 1, stream, (long)w->st.napply);
     ++w->st.napply;
-    ApplyKernel kernel = pick_kernel(w, nvar, nbatch);
-    // the column sweep addresses a wave's 16 field planes through one buffer descriptor (32-bit offsets)
-    if (kernel == KERNEL_COLSWEEP && ((uint64_t)16 * (uint64_t)lda * 8 + (uint64_t)w->ncol * 8 >= (1ull << 32)))
-        kernel = w->st.bands.built() ? KERNEL_ROWDUAL : KERNEL_ROWBLOCK;
-    w->st.last_kernel = kernel;
+    const MatrixFacts f = facts_of(*w);
+    // the family is chosen once, by the whole call's nbatch; a last launch of fewer batches keeps it and plans its own shape
+    ApplyPlan plan = plan_apply(f, nvar, nbatch, false, lda);
+    w->st.last_kernel = plan.family;
     w->st.last_sig[0] = 0;
     const bool correct = !w->conservative && force_conservation;
     if (correct) grow_scratch(w->st.scr.consv, consv_count(w, nvar), stream, "conservation");
@@ -1936,7 +1561,8 @@ void spmm_launch_many(const ibh_weighted *w, int nbatch, const double *const *dA
             IBH_CHECK(dA[b0 + q] && dB[b0 + q], "apply: null field pointer in batch %d", b0 + q);
             bp.x[q] = dA[b0 + q]; bp.y[q] = dB[b0 + q];
         }
-        launch_one(w, kernel, bp, nb, nvar, lda, ldb, fill, stream);
+        if (nb != std::min(nbatch, IBH_MAX_BATCH)) plan = plan_launch(f, plan.family, nvar, nb, false);
+        launch_plan(w, f, plan, bp, nb, nvar, (long)lda, (long)ldb, fill, stream);
         if (correct) {
             // factor_k = (Mw . A_k) / (wM . B_k); rows with wM == 0 hold `fill` and are skipped.  The two
             // dot products live in handle-owned scratch: stream-ordered, no allocation, no host sync.

@@ -19,16 +19,10 @@
 // a padded zero (0*NaN must not leak into a row).  Design notes and measurements: DESIGN.md K1d.
 #pragma once
 #include <hip/hip_runtime.h>
-
-#ifndef IBH_MAX_BATCH
-#define IBH_MAX_BATCH 32
-#endif
+#include "apply_plan.h"      // IBH_MAX_BATCH, SWEEP_CB / SWEEP_NW / SWEEP_TS, sweep_lds_bytes
 
 namespace ibh {
 
-constexpr int SWEEP_CB = 64;             // columns per block
-constexpr int SWEEP_NW = 4;              // waves per workgroup
-constexpr int SWEEP_TS = SWEEP_CB + 1;   // padded tile row
 // One ITEM per column (a column with more than two entries: several): the column, and <= 2 of its entries:
 // meta = slot0 | slot1 << 8 | has0 << 16 | has1 << 17 (0: empty slot), v0, v1 the two values.  Items are packed: block b =
 // items [64 b, 64 b + 64) (the last block of the matrix may be short), task t = blocks [t tb, t tb + tb): no descriptors.
@@ -45,8 +39,6 @@ struct SweepBatch {
     const double *x[IBH_MAX_BATCH];
     double *p[IBH_MAX_BATCH];  // partial sums [nprow][ldp]
 };
-
-inline size_t sweep_lds_bytes(int nslot) { return ((size_t)64 * SWEEP_TS + (size_t)SWEEP_NW * nslot * 64 + 2 * SWEEP_CB) * 8; }
 
 __device__ __forceinline__ int sweep_xcd_contiguous(int b, int nb) {
     const int q = nb >> 3, rem = nb & 7;

@@ -1,4 +1,4 @@
-"""One recipe per apply-kernel instantiation of icebin_amd/csrc/spmm.hip: how to make an apply launch exactly that kernel.
+"""One recipe per apply-kernel instantiation of icebin_amd/csrc/spmm.hip (listed in apply_plan.h): how to make an apply launch exactly that kernel.
 
 A plain module (no tests, no fixtures): tests/test_capi_symbols.py checks that the names below are exactly the apply kernels the
 code object holds, tests/test_gpu_apply_kernels.py runs every recipe on the GPU against an exact row-by-row reference.
