@@ -7,3 +7,4 @@ from ._capi import IcebinHipError, device_count  # noqa: F401
 from .linear import SparseSet, compute_E1vE0c, coo_multiply, linear_Weighted, nc_read_weighted, set_tuning  # noqa: F401
 from .regrid import GCMRegridder, RegridMatrices, from_synthetic  # noqa: F401
 from .hntr import Hntr, HntrSpec  # noqa: F401
+from .multivec import VectorMultivec, concatenate  # noqa: F401

@@ -62,6 +62,10 @@ class DeviceView(C.Structure):
                 ("colind", C.c_void_p), ("val", C.c_void_p), ("wM", C.c_void_p), ("Mw", C.c_void_p)]
 
 
+class MultivecDeviceView(C.Structure):
+    _fields_ = [("n", C.c_int64), ("nvar", C.c_int32), ("index", C.c_void_p), ("weights", C.c_void_p), ("vals", C.c_void_p)]
+
+
 _SIGS = {
     "ibh_version": (C.c_int, []),
     "ibh_device_count": (C.c_int, [C.POINTER(C.c_int)]),
@@ -157,6 +161,25 @@ _SIGS = {
                                                        C.c_void_p]),
     "ibh_weighted_apply_weight_host": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p]),
     "ibh_weighted_device_view_get": (C.c_int, [C.c_void_p, C.POINTER(DeviceView)]),
+    "ibh_multivec_create": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p)]),
+    "ibh_multivec_destroy": (C.c_int, [C.c_void_p]),
+    "ibh_multivec_size": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
+    "ibh_multivec_clear": (C.c_int, [C.c_void_p]),
+    "ibh_multivec_reserve": (C.c_int, [C.c_void_p, C.c_int64]),
+    "ibh_multivec_add_host": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ibh_multivec_get": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ibh_multivec_device_view_get": (C.c_int, [C.c_void_p, C.POINTER(MultivecDeviceView)]),
+    "ibh_multivec_append_weighted_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p]),
+    "ibh_multivec_append": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "ibh_multivec_concatenate": (C.c_int, [C.c_int32, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "ibh_multivec_to_dense_scale": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "ibh_multivec_to_dense": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
+    "ibh_multivec_update_dense": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
+    "ibh_sparse_set_add_dense_multivec": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ibh_multivec_densify_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "ibh_multivec_append_weighted_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64]),
+    "ibh_multivec_to_dense_scale_host": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p]),
+    "ibh_multivec_to_dense_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_int64, C.c_int64]),
     "ibh_weighted_set_kernel": (C.c_int, [C.c_void_p, C.c_char_p]),
     "ibh_weighted_last_kernel": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
     "ibh_event_create": (C.c_int, [C.POINTER(C.c_void_p)]),

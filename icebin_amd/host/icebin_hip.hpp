@@ -15,6 +15,7 @@
 //     everytrace::Exception (slib/icebin/error.hpp:28).
 // Header-only; C++14.
 #pragma once
+#include <algorithm>
 #include <array>
 #include <cmath>
 #include <cstdio>
@@ -392,6 +393,88 @@ public:
 };
 typedef Weighted Weighted_Eigen;      // the concrete type callers name (RegridMatrices_Dynamic.hpp:27)
 }   // namespace linear
+
+// ---- multivec.hpp:16-71 ----------------------------------------------------------------------
+/** icebin::VectorMultivec, resident in HBM (ibh_multivec).  index / weights / vals are read back on demand; the members
+    with the reference's names take host arrays like its blitz arrays, the *_device ones take HBM pointers and a stream. */
+class VectorMultivec {
+    ibh_multivec *h_;
+    explicit VectorMultivec(ibh_multivec *h) : h_(h) {}
+    friend VectorMultivec concatenate(std::vector<VectorMultivec const *> const &vecs);
+public:
+    explicit VectorMultivec(int _nvar) : h_(nullptr) { check(ibh_multivec_create(_nvar, &h_)); }
+    VectorMultivec(VectorMultivec const &) = delete;
+    VectorMultivec &operator=(VectorMultivec const &) = delete;
+    VectorMultivec(VectorMultivec &&o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+    ~VectorMultivec() { if (h_) ibh_multivec_destroy(h_); }
+    ibh_multivec *handle() const { return h_; }
+
+    int nvar() const { int32_t v; check(ibh_multivec_size(h_, nullptr, &v)); return v; }
+    size_t size() const { int64_t n; check(ibh_multivec_size(h_, &n, nullptr)); return (size_t)n; }
+    void clear() { check(ibh_multivec_clear(h_)); }
+    void reserve(size_t n) { check(ibh_multivec_reserve(h_, (int64_t)n)); }
+
+    /** add(ix, val, weight) (multivec.cpp:8-13); the array form adds n entries with one copy. */
+    void add(long ix, double const *val, double weight) { int64_t i = ix; check(ibh_multivec_add_host(h_, 1, &i, &weight, val)); }
+    void add(long ix, std::vector<double> const &val, double weight) { add(ix, val.data(), weight); }
+    void add(size_t n, int64_t const *ix, double const *weight, double const *val) { check(ibh_multivec_add_host(h_, (int64_t)n, ix, weight, val)); }
+
+    std::vector<long> index() const {
+        std::vector<int64_t> t(size());
+        check(ibh_multivec_get(h_, t.data(), nullptr, nullptr));
+        return std::vector<long>(t.begin(), t.end());
+    }
+    std::vector<double> weights() const { std::vector<double> t(size()); check(ibh_multivec_get(h_, nullptr, t.data(), nullptr)); return t; }
+    std::vector<double> vals() const { std::vector<double> t(size() * (size_t)nvar()); check(ibh_multivec_get(h_, nullptr, nullptr, t.data())); return t; }
+    /** val(varix, ix) (multivec.hpp:55-56); reads the values back: for a loop, take vals() once. */
+    double val(int varix, long ix) const { return vals().at((size_t)ix * (size_t)nvar() + (size_t)varix); }
+
+    /** "Sparsify while appending" (IceCoupler.cpp:447-458) from the field-major product of M: host array / HBM pointer. */
+    void append_weighted(linear::Weighted const &M, double const *B_b, int nvar_, long ldb) {
+        check(ibh_multivec_append_weighted_host(h_, M.handle(), B_b, nvar_, ldb));
+    }
+    void append_weighted_device(linear::Weighted const &M, double const *dB_b, int nvar_, long ldb, void *stream) {
+        check(ibh_multivec_append_weighted_device(h_, M.handle(), dB_b, nvar_, ldb, stream));
+    }
+    void append(VectorMultivec const &other) { check(ibh_multivec_append(h_, other.h_)); }
+
+    /** to_dense_scale(scaleE) (multivec.cpp:35-50): scaleE's length is nE. */
+    void to_dense_scale(std::vector<double> &scaleE) const { check(ibh_multivec_to_dense_scale_host(h_, (int64_t)scaleE.size(), scaleE.data())); }
+    void to_dense_scale_device(long nE, double *d_scale, void *stream) const { check(ibh_multivec_to_dense_scale(h_, nE, d_scale, stream)); }
+    /** to_dense (multivec.cpp:55-81), all variables at once: [nvar x nE] field-major; and the reference's one-variable form,
+        which computes them all and keeps one. */
+    std::vector<double> to_dense(std::vector<double> const &scaleE, double fill) const {
+        std::vector<double> out((size_t)nvar() * scaleE.size());
+        check(ibh_multivec_to_dense_host(h_, scaleE.data(), fill, out.data(), (int64_t)scaleE.size(), (int64_t)scaleE.size()));
+        return out;
+    }
+    void to_dense(int ivar, std::vector<double> const &scaleE, double fill, std::vector<double> &denseE) const {
+        if (denseE.size() != scaleE.size()) throw Exception(IBH_EINVAL, "to_dense: denseE and scaleE differ in length");
+        if (ivar < 0 || ivar >= nvar()) throw Exception(IBH_EINVAL, "to_dense: no variable " + std::to_string(ivar));
+        std::vector<double> all = to_dense(scaleE, fill);
+        std::copy(all.begin() + (long)ivar * (long)scaleE.size(), all.begin() + ((long)ivar + 1) * (long)scaleE.size(), denseE.begin());
+    }
+    void to_dense_device(double const *d_scale, double fill, double *d_out, long ld, long nE, void *stream) const {
+        check(ibh_multivec_to_dense(h_, d_scale, fill, d_out, ld, nE, stream));
+    }
+    /** The in-place merge into the GCM's arrays (modele/GCMCoupler_ModelE.cpp:864-892), HBM pointers. */
+    void update_dense(double const *d_scale, double *d_out, long ld, long nE, void *stream) const {
+        check(ibh_multivec_update_dense(h_, d_scale, d_out, ld, nE, stream));
+    }
+    /** dimE0->add_dense of every index in entry order (IceCoupler.cpp:294-300), then the densified array (:306-314), HBM pointer. */
+    void add_dense_to(SparseSetT &dim, void *stream = nullptr) const { check(ibh_sparse_set_add_dense_multivec(dim.handle(), h_, stream)); }
+    void densify(SparseSetT const &dim, double *d_out, long ld, void *stream) const {
+        check(ibh_multivec_densify_device(h_, dim.handle(), d_out, ld, stream));
+    }
+};
+/** concatenate (multivec.cpp:15-33). */
+inline VectorMultivec concatenate(std::vector<VectorMultivec const *> const &vecs) {
+    std::vector<ibh_multivec const *> hs;
+    for (VectorMultivec const *v : vecs) hs.push_back(v->handle());
+    ibh_multivec *h = nullptr;
+    check(ibh_multivec_concatenate((int32_t)hs.size(), hs.data(), &h));
+    return VectorMultivec(h);
+}
 
 // ---- AbbrGrid.hpp:40-89 ----------------------------------------------------------------------
 class ExchangeGrid {

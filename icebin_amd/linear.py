@@ -69,6 +69,10 @@ class SparseSet:
         check(lib().ibh_sparse_set_to_dense(self._h, int(sparse), C.byref(d)))
         return d.value >= 0
 
+    def add_dense_multivec(self, mv, stream=None):
+        """add_dense of every index of a VectorMultivec in entry order, on the device (IceCoupler.cpp:294-300)."""
+        check(lib().ibh_sparse_set_add_dense_multivec(self._h, mv._h, C.c_void_p(stream)))
+
 
 class linear_Weighted:
     """A regrid matrix M plus its two weight vectors, resident in HBM.

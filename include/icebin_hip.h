@@ -641,6 +641,78 @@ typedef struct ibh_weighted_device_view {
 } ibh_weighted_device_view;
 int ibh_weighted_device_view_get(const ibh_weighted *w, ibh_weighted_device_view *out);
 
+/* ------------------------------------------------------------------------- */
+/* VectorMultivec: icebin::VectorMultivec (slib/icebin/multivec.hpp:16-69), the parallel sparse vectors the coupler
+ * exchanges with the GCM, resident in HBM.  Layout as the reference's (multivec.hpp:25-31, :55-56): index int64[n],
+ * weights double[n], vals double[n * nvar] with vals[ix * nvar + ivar].  Fewer than 2^31 entries.  Capacity grows
+ * geometrically; after ibh_multivec_reserve(mv, n) appends up to n entries in all allocate nothing.
+ *
+ * Order of arithmetic: every sum over entries naming the same cell runs in ENTRY order, one product then one add, no
+ * contraction, no floating-point atomics: each result is the reference loop's, bit for bit.  The merge calls
+ * (to_dense_scale, to_dense, update_dense) share a grouping of the entries by index that the handle keeps until the
+ * vector changes.
+ *
+ * Errors: an index < 0 or >= nE is IBH_EINVAL and the message names the entry (icebin_error, multivec.cpp:43,67).  The
+ * check is one status word read back, so ibh_multivec_to_dense_scale / _to_dense / _update_dense SYNCHRONISE THE STREAM
+ * ONCE when they group the entries (the first of them after a change; later ones only enqueue), and
+ * ibh_multivec_densify_device / ibh_sparse_set_add_dense_multivec synchronise it like a matrix build.  On error the
+ * output's contents are unspecified and the handle is unchanged. */
+typedef struct ibh_multivec ibh_multivec;
+/* VectorMultivec(nvar) (multivec.hpp:36); nvar < 1 is IBH_EINVAL.  size() (:39).  clear: n = 0, the capacity is kept. */
+int ibh_multivec_create(int32_t nvar, ibh_multivec **out);
+int ibh_multivec_destroy(ibh_multivec *mv);
+int ibh_multivec_size(const ibh_multivec *mv, int64_t *n, int32_t *nvar);       /* either may be NULL */
+int ibh_multivec_clear(ibh_multivec *mv);
+int ibh_multivec_reserve(ibh_multivec *mv, int64_t n);
+/* add() (multivec.cpp:8-13) for n entries at once, from host arrays: index[n], weights[n], vals[n * nvar]. */
+int ibh_multivec_add_host(ibh_multivec *mv, int64_t n, const int64_t *index, const double *weights, const double *vals);
+/* The public members index, weights, vals (multivec.hpp:25-29) copied to the host (any may be NULL), or as device
+ * pointers, valid until the next call that appends. */
+int ibh_multivec_get(const ibh_multivec *mv, int64_t *index, double *weights, double *vals);
+typedef struct ibh_multivec_device_view {
+    int64_t n; int32_t nvar;
+    const int64_t *index; const double *weights, *vals;
+} ibh_multivec_device_view;
+int ibh_multivec_device_view_get(const ibh_multivec *mv, ibh_multivec_device_view *out);
+/* "Sparsify while appending to the global VectorMultivec" (IceCoupler.cpp:447-458): one entry per dense row jj of w,
+ * rows ascending: index = w's dims[0] to_sparse(jj), weight = wM(jj), values = dB_b[ivar * ldb + jj], the field-major
+ * result of an apply of w (the transpose the reference's comment speaks of).  EVERY row is appended, as there; the
+ * reference's gcm_ivalsX is a plain Eigen product, which a caller gets by passing fill = 0 to the apply.
+ * nvar != the vector's is IBH_EINVAL.  A pure enqueue on `stream` when the capacity suffices. */
+int ibh_multivec_append_weighted_device(ibh_multivec *mv, const ibh_weighted *w, const double *dB_b, int32_t nvar, int64_t ldb,
+                                        void *stream);
+/* concatenate() (multivec.cpp:15-33): the entries of `other` behind mv's / of mvs[0..k) in order into a new vector.
+ * k == 0 or differing nvar is IBH_EINVAL (:19-20, :29-30).  Device copies on the default stream. */
+int ibh_multivec_append(ibh_multivec *mv, const ibh_multivec *other);
+int ibh_multivec_concatenate(int32_t k, const ibh_multivec *const *mvs, ibh_multivec **out);
+/* to_dense_scale() (multivec.cpp:35-50): d_scale[nE] (device) = 0, += weights in entry order, then 1/x of EVERY
+ * element: a cell no entry names holds +inf. */
+int ibh_multivec_to_dense_scale(const ibh_multivec *mv, int64_t nE, double *d_scale, void *stream);
+/* to_dense() (multivec.cpp:55-81) for all variables at once: d_out[ivar * ld + iE] (device).  The reference's rule is kept
+ * as it is: a cell starts untouched (NaN); per entry p = val * scale[iE]; a NaN running value BECOMES p, else p is added;
+ * a cell that ends NaN gets `fill`.  So a NaN term is forgotten once another follows it, and a trailing one (or a zero
+ * weight sum, 0 * inf) becomes `fill`. */
+int ibh_multivec_to_dense(const ibh_multivec *mv, const double *d_scale, double fill, double *d_out, int64_t ld, int64_t nE,
+                          void *stream);
+/* The in-place update of the GCM's arrays (modele/GCMCoupler_ModelE.cpp:864-892): the cells the entries name are set to
+ * 0.0, then += val * scale[iE] in entry order; all other cells keep their contents.  The (j,i) / (ihc,j,i) index
+ * arithmetic and the clearing of a whole elevation-class column (:918) are ModelE's and stay with the caller. */
+int ibh_multivec_update_dense(const ibh_multivec *mv, const double *d_scale, double *d_out, int64_t ld, int64_t nE, void *stream);
+/* dimE0->add_dense(index[i]) for every entry in order (IceCoupler.cpp:294-300), on the device: a pre-populated set is
+ * appended to, first-seen.  An index < 0 or beyond the set's sparse extent is IBH_EINVAL and leaves the set as it was. */
+int ibh_sparse_set_add_dense_multivec(ibh_sparse_set *set, const ibh_multivec *mv, void *stream);
+/* Densify onto a set (IceCoupler.cpp:306-314): d_out[nvar x dense_extent] (device, row stride ld) = 0, then
+ * d_out[ivar * ld + to_dense(index[i])] += val(ivar, i) in entry order; the weights are not used.  An index the set
+ * lacks is IBH_EINVAL (to_dense raises there, :310). */
+int ibh_multivec_densify_device(const ibh_multivec *mv, const ibh_sparse_set *set, double *d_out, int64_t ld, void *stream);
+/* Host-array forms of three of the calls above, for a caller that holds no device arrays (the blitz arrays of
+ * multivec.cpp:35-81 and the Eigen product of IceCoupler.cpp:445-458 live on the host): the arrays are copied to the
+ * device, the device call runs on the default stream, the result is copied back.  Same bits, same refusals. */
+int ibh_multivec_append_weighted_host(ibh_multivec *mv, const ibh_weighted *w, const double *B_b, int32_t nvar, int64_t ldb);
+int ibh_multivec_to_dense_scale_host(const ibh_multivec *mv, int64_t nE, double *scale /* [nE] */);
+int ibh_multivec_to_dense_host(const ibh_multivec *mv, const double *scale, double fill, double *out /* [nvar x ld] */, int64_t ld,
+                               int64_t nE);
+
 /* Tuning / introspection (not part of the reference interface). */
 int ibh_weighted_set_kernel(ibh_weighted *w, const char *name_or_auto);   /* "auto", "rowblock", "shortrow", "rowdual", "colsweep", "rowgroup" */
 int ibh_weighted_last_kernel(const ibh_weighted *w, char *buf, int buflen);
