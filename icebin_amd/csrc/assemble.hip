@@ -2698,6 +2698,12 @@ void weighted_from_coo_device(ibh_weighted *w, int nrow, int ncol, int64_t n, co
     IBH_HIP(hipStreamSynchronize(st));
 }
 
+void csr_from_device_triplets(ibh_weighted *w, int nrow, int ncol, int64_t n, const int32_t *drow, const int32_t *dcol,
+                              const double *dval, hipStream_t st) {
+    csr_from_triplets(w, nrow, ncol, n, drow, dcol, dval, hipMemcpyDeviceToDevice, st);
+    IBH_HIP(hipGetLastError());
+}
+
 // setFromTriplets from triplets already on the device (dense ids, input order) and the plain weights wM / Mw = spsparse
 // sum(M, dim, '+') (columns visited ascending, rows ascending inside): the general-dims path of the Hntr matrices (hntr.hip).
 // Enqueued on `st`; reads nothing back but nnz.  The arena is not reset: the caller's triplets may live there.

@@ -282,6 +282,15 @@ cdef class GCMRegridder:
             self._add_sheet_arrays(name, int(gridI["nI"]), exgrid["indices"], exgrid["overlaps"], proj, interp_style,
                                    gridI.get("centroid_xy"))
 
+    def to_modele(self, focean=None, hspecO=None, eq_rad=None):
+        """Returns a new GCMRegridder object, suitable for use with ModelE (_icebin.pyx:128-147).
+
+        focean: (foceanAOp, foceanAOm) [OPTIONAL]
+            Use this ocean in GCMRegridder_ModelE.
+        hspecO, eq_rad: the HntrSpec of this regridder's grid (ModelE's ocean grid) and the earth's radius, which the
+            reference reads from the grid file."""
+        return _to_modele(self, focean, hspecO, eq_rad)
+
     def regrid_matrices(self, str sheet_name, elevmaskI, bool scale=True, bool correctA=True, sigma=(0, 0, 0), conserve=True):
         """_icebin.pyx:164-175 (`conserve` is accepted and, as in icebin_cython.cpp:215-236, not used)."""
         if sheet_name not in self._sheets:
@@ -367,3 +376,59 @@ cdef class Hntr:
         self.cself.regrid(cicebin.ArrayViewCD(&w[0], nA), cicebin.ArrayViewCD(&a[0], nA), cicebin.ArrayViewD(&b[0], b.shape[0]),
                           mean_polar, 1.0, 0.0)
         return B
+
+
+cdef class GCMRegridder_ModelE:
+    """What GCMRegridder.to_modele returns: GCMRegridder_WrapE (modele/GCMRegridder_ModelE.hpp:206-251) with nA, nE, nhc and
+    regrid_matrices of a GCMRegridder."""
+    cdef cicebin.GCMRegridder_WrapE *cself
+    cdef object _gcmO
+
+    def __cinit__(self):
+        self.cself = NULL
+
+    def __dealloc__(self):
+        if self.cself != NULL:
+            del self.cself
+
+    @property
+    def nA(self):
+        return self.cself.nA()
+
+    @property
+    def nE(self):
+        return self.cself.nE()
+
+    @property
+    def nhc(self):
+        return self.cself.nhc()
+
+    def wA(self, sheet_name, snative, fill=0.):
+        raise NotImplementedError("wA on the ModelE regridder is not supported")
+
+    def regrid_matrices(self, str sheet_name, elevmaskI, bool scale=True, bool correctA=True, sigma=(0, 0, 0), conserve=True):
+        cdef double[::1] em = np.ascontiguousarray(np.asarray(elevmaskI, np.float64).reshape(-1))
+        cdef cicebin.RegridMatrices *crm = cicebin.new_regrid_matrices_modele(
+            self.cself, sheet_name.encode(), &em[0] if em.shape[0] else NULL, em.shape[0], scale, correctA,
+            sigma[0], sigma[1], sigma[2], conserve)
+        cdef RegridMatrices rm = RegridMatrices()
+        rm.cself = crm
+        rm._keep = self
+        return rm
+
+
+def _to_modele(GCMRegridder gcmO, focean, hspecO, eq_rad):
+    if hspecO is None or eq_rad is None:
+        raise RuntimeError("make_gridA() requires specO have a Hntr source")       # GCMRegridder_ModelE.cpp:40-41
+    cdef HntrSpec spec = hspecO
+    cdef GCMRegridder_ModelE ret = GCMRegridder_ModelE()
+    ret.cself = cicebin.new_GCMRegridder_WrapE(gcmO.cself, spec.cself[0], eq_rad)
+    ret._gcmO = gcmO
+    cdef double[::1] fp, fm
+    if focean is not None:
+        fp = np.ascontiguousarray(np.asarray(focean[0], np.float64).reshape(-1))
+        fm = np.ascontiguousarray(np.asarray(focean[1], np.float64).reshape(-1))
+        if fp.shape[0] != fm.shape[0] or fp.shape[0] == 0:
+            raise ValueError("focean: two arrays of the ocean grid's size")
+        cicebin.GCMRegridder_WrapE_set_focean(ret.cself, &fp[0], &fm[0], fp.shape[0])
+    return ret

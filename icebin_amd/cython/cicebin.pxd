@@ -83,3 +83,16 @@ cdef extern from "../host/icebin_hip.hpp" namespace "icebin::modele":
         HntrGrid Bgrid
         Hntr(double yp17, const HntrSpec &B, const HntrSpec &A, double DATMIS) except +
         void regrid(const ArrayViewCD &WTA, const ArrayViewCD &A, const ArrayViewD &B, bool mean_polar, double wtm, double wtb) except +
+
+    # modele/GCMRegridder_ModelE.hpp:206-251
+    cdef cppclass GCMRegridder_WrapE:
+        unsigned long nA() except +
+        unsigned long nE() except +
+        unsigned int nhc() except +
+
+cdef extern from "../host/icebin_hip.hpp" namespace "icebin::cython":
+    GCMRegridder_WrapE *new_GCMRegridder_WrapE(GCMRegridder_Standard *gcmO, const HntrSpec &hspecO, double eq_rad) except +
+    void GCMRegridder_WrapE_set_focean(GCMRegridder_WrapE *cself, const double *foceanAOp, const double *foceanAOm, long n) except +
+    RegridMatrices *new_regrid_matrices_modele(const GCMRegridder_WrapE *gcm, const string &sheet_name,
+                                               const double *elevmaskI, long elevmaskI_len, bool scale, bool correctA,
+                                               double sigma_x, double sigma_y, double sigma_z, bool conserve) except +

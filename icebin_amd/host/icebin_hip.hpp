@@ -542,6 +542,7 @@ public:
     RegridMatrices_Dynamic(IceRegridder const *_ice_regridder, ibh_regrid_matrices *h, RegridParams const &params)
         : RegridMatrices(params), h_(h), ice_regridder(_ice_regridder) {}
     ~RegridMatrices_Dynamic() { if (h_) ibh_regrid_matrices_destroy(h_); }
+    ibh_regrid_matrices *handle() const { return h_; }
 
     /** matrix_d(spec_name, dims, params): ignores this->params() (RegridMatrices_Dynamic.hpp:51-54).
         dims may be pre-populated and are appended to; they must outlive the result. */
@@ -1116,6 +1117,111 @@ inline void check_negative(linear::Weighted_Eigen const &mat, std::string const 
         if (t.value < 0) { printf("%s(%d,%d)=%g\n", name.c_str(), t.row, t.col, t.value); neg = true; }
     if (neg) throw Exception(IBH_EINVAL, "Negative values found in matrix or weights for " + name);
 }
+
+// ---- modele/GCMRegridder_ModelE.hpp ------------------------------------------------------------------
+/** make_hntrA (modele/hntr.cpp:232-241): the atmosphere grid is exactly twice as coarse as the ocean grid. */
+inline HntrSpec make_hntrA(HntrSpec const &hntrO) {
+    if ((hntrO.im % 2 != 0) || (hntrO.jm % 2 != 0))
+        throw Exception(IBH_EINVAL, "Ocean grid must have even number of gridcells for im and jm (vs. " + std::to_string(hntrO.im) + " " +
+                                        std::to_string(hntrO.jm) + ")");
+    return HntrSpec(hntrO.im / 2, hntrO.jm / 2, hntrO.offi * 0.5, hntrO.dlat * 2.);
+}
+
+/** What GCMRegridder_ModelE::regrid_matrices returns (GCMRegridder_ModelE.cpp:487-571): AvI EvI AvX EvX IvA IvE XvA XvE, the
+    aliases EAmvIp AAmvIp IpvEAm IpvAAm and the test matrices AOmvAAm / AAmvAOm, on the atmosphere grid.  Holds the O-grid
+    matrices it is composed from (the reference's rm->tmp.take(rmO)). */
+class RegridMatrices_ModelE : public RegridMatrices {
+    ibh_modele_matrices *h_;
+    std::unique_ptr<RegridMatrices_Dynamic> rmO_;
+public:
+    RegridMatrices_ModelE(ibh_modele_matrices *h, std::unique_ptr<RegridMatrices_Dynamic> &&rmO, RegridParams const &params)
+        : RegridMatrices(params), h_(h), rmO_(std::move(rmO)) {}
+    ~RegridMatrices_ModelE() { if (h_) ibh_modele_matrices_destroy(h_); }
+    RegridMatrices_ModelE(RegridMatrices_ModelE const &) = delete;
+    RegridMatrices_ModelE &operator=(RegridMatrices_ModelE const &) = delete;
+
+    /** matrix_d(spec_name, dims, params): params.correctA is ignored, as compute_XAmvGp / compute_GpvXAm ignore it; dims may
+        be pre-populated, are appended to and must outlive the result. */
+    std::unique_ptr<linear::Weighted_Eigen> matrix_d(std::string const &spec_name, std::array<SparseSetT *, 2> dims,
+                                                     RegridParams const &params) const {
+        if (params.smooth()) throw Exception(IBH_ENOTIMPL, "smoothing through the ModelE regridder is not supported");
+        ibh_weighted *w = nullptr;
+        check(ibh_modele_matrices_matrix_d(h_, spec_name.c_str(), dims[0] ? dims[0]->handle() : nullptr,
+                                           dims[1] ? dims[1]->handle() : nullptr, params.scale, &w));
+        return std::unique_ptr<linear::Weighted_Eigen>(new linear::Weighted_Eigen(w));
+    }
+    std::unique_ptr<linear::Weighted> matrix(std::string const &spec_name) const override {
+        return matrix_d(spec_name, {{nullptr, nullptr}}, params());
+    }
+};
+
+/** GCMRegridder_ModelE (GCMRegridder_ModelE.hpp:102-200): gcmO regrids between (AOp, EOp, Ip) on ModelE's ocean grid; this
+    class hands out the matrices between (AAm, EAm, Ip).  The reference reads the ocean HntrSpec and the earth's radius from
+    gcmO's grid spec; here the caller names them (global_ecO, the base-ice file, must be empty: out of scope). */
+class GCMRegridder_ModelE {
+    HntrSpec hspecO_;
+    double eq_rad_;
+public:
+    std::shared_ptr<GCMRegridder_Standard> const gcmO;
+
+    GCMRegridder_ModelE(std::string const &_global_ecO, std::shared_ptr<GCMRegridder_Standard> const &_gcmO, HntrSpec const &hspecO,
+                        double eq_rad)
+        : hspecO_(hspecO), eq_rad_(eq_rad), gcmO(_gcmO) {
+        if (!_global_ecO.empty()) throw Exception(IBH_ENOTIMPL, "GCMRegridder_ModelE: the global_ecO file is not supported");
+        make_hntrA(hspecO);
+        if ((unsigned long)hspecO.size() != gcmO->nA())
+            throw Exception(IBH_EINVAL, "GCMRegridder_ModelE: hspecO has " + std::to_string(hspecO.size()) + " cells, gcmO " +
+                                            std::to_string(gcmO->nA()));
+    }
+    unsigned int nhc() const { return gcmO->nhc(); }
+    unsigned long nA() const { return gcmO->nA() / 4; }
+    unsigned long nE() const { return gcmO->nE() / 4; }
+    HntrSpec const &hspecO() const { return hspecO_; }
+    HntrSpec hspecA() const { return make_hntrA(hspecO_); }
+    double eq_rad() const { return eq_rad_; }
+
+    /** make_agridA (GCMRegridder_ModelE.cpp:57-78): the realised atmosphere cells, first-seen in Hntr's stream order. */
+    std::vector<long> agridA_dim(int sheet_index) const {
+        std::vector<int64_t> a((size_t)nA());
+        int32_t n = 0;
+        check(ibh_modele_agridA(gcmO->ice_regridder(sheet_index)->handle(), hspecO_.im, hspecO_.jm, hspecO_.offi, hspecO_.dlat, &n, a.data()));
+        return std::vector<long>(a.begin(), a.begin() + n);
+    }
+
+    /** regrid_matrices(sheet_index, foceanAOp, foceanAOm, elevmaskI, params) (GCMRegridder_ModelE.hpp:180-186): the arrays are
+        copied. */
+    std::unique_ptr<RegridMatrices_ModelE> regrid_matrices(int sheet_index, ArrayView<const double> const &foceanAOp,
+                                                           ArrayView<const double> const &foceanAOm,
+                                                           ArrayView<const double> const &elevmaskI,
+                                                           RegridParams const &params = RegridParams()) const {
+        if (foceanAOp.size() != foceanAOm.size()) throw Exception(IBH_EINVAL, "foceanAOp and foceanAOm differ in length");
+        auto rmO = gcmO->regrid_matrices(sheet_index, elevmaskI, params);
+        ibh_modele_matrices *h = nullptr;
+        check(ibh_modele_matrices_create(rmO->handle(), hspecO_.im, hspecO_.jm, hspecO_.offi, hspecO_.dlat, eq_rad_, foceanAOp.data,
+                                         foceanAOm.data, foceanAOp.size(), &h));
+        return std::unique_ptr<RegridMatrices_ModelE>(new RegridMatrices_ModelE(h, std::move(rmO), params));
+    }
+};
+
+/** GCMRegridder_WrapE (GCMRegridder_ModelE.hpp:206-251): a GCMRegridder_ModelE with the two ocean fractions it is used with
+    (sparse O indexing; zero until set), so that regrid_matrices has GCMRegridder's signature. */
+class GCMRegridder_WrapE {
+public:
+    std::unique_ptr<GCMRegridder_ModelE> gcmA;
+    std::vector<double> foceanOp, foceanOm;
+
+    explicit GCMRegridder_WrapE(std::unique_ptr<GCMRegridder_ModelE> &&_gcmA)
+        : gcmA(std::move(_gcmA)), foceanOp(gcmA->gcmO->nA(), 0.), foceanOm(gcmA->gcmO->nA(), 0.) {}
+    GCMRegridder_WrapE(std::unique_ptr<GCMRegridder_ModelE> &&_gcmA, std::vector<double> _foceanOp, std::vector<double> _foceanOm)
+        : gcmA(std::move(_gcmA)), foceanOp(std::move(_foceanOp)), foceanOm(std::move(_foceanOm)) {}
+    unsigned int nhc() const { return gcmA->nhc(); }
+    unsigned long nA() const { return gcmA->nA(); }
+    unsigned long nE() const { return gcmA->nE(); }
+    std::unique_ptr<RegridMatrices_ModelE> regrid_matrices(int sheet_index, ArrayView<const double> const &elevmaskI,
+                                                           RegridParams const &params = RegridParams()) const {
+        return gcmA->regrid_matrices(sheet_index, ArrayView<const double>(foceanOp), ArrayView<const double>(foceanOm), elevmaskI, params);
+    }
+};
 }   // namespace modele
 
 // ---- pylib/icebin_cython.hpp:70-87 -----------------------------------------------------------
@@ -1133,6 +1239,24 @@ inline RegridMatrices *new_regrid_matrices(GCMRegridder_Standard const *gcm, std
 /** RegridMatrices_matrix(cself, spec_name) (icebin_cython.cpp:195-198) */
 inline linear::Weighted *RegridMatrices_matrix(RegridMatrices *cself, std::string const &spec_name) {
     return cself->matrix(spec_name).release();
+}
+/** new_GCMRegridder_WrapE(global_ecO, gcmO) (icebin_cython.cpp, used by GCMRegridder.to_modele, _icebin.pyx:128-147): gcmO is
+    BORROWED -- the Python object that owns it is kept alive by the wrapper's Python object. */
+inline modele::GCMRegridder_WrapE *new_GCMRegridder_WrapE(GCMRegridder_Standard *gcmO, modele::HntrSpec const &hspecO, double eq_rad) {
+    std::shared_ptr<GCMRegridder_Standard> borrowed(gcmO, [](GCMRegridder_Standard *) {});
+    return new modele::GCMRegridder_WrapE(
+        std::unique_ptr<modele::GCMRegridder_ModelE>(new modele::GCMRegridder_ModelE("", borrowed, hspecO, eq_rad)));
+}
+inline void GCMRegridder_WrapE_set_focean(modele::GCMRegridder_WrapE *cself, const double *foceanAOp, const double *foceanAOm, long n) {
+    cself->foceanOp.assign(foceanAOp, foceanAOp + n);
+    cself->foceanOm.assign(foceanAOm, foceanAOm + n);
+}
+inline RegridMatrices *new_regrid_matrices_modele(modele::GCMRegridder_WrapE const *gcm, std::string const &sheet_name,
+                                                  const double *elevmaskI, long elevmaskI_len, bool scale, bool correctA,
+                                                  double sigma_x, double sigma_y, double sigma_z, bool /*conserve*/) {
+    auto sheet_index = gcm->gcmA->gcmO->sheet_index(sheet_name);
+    return gcm->regrid_matrices((int)sheet_index, ArrayView<const double>(elevmaskI, elevmaskI_len),
+                                RegridParams(scale, correctA, {{sigma_x, sigma_y, sigma_z}})).release();
 }
 }   // namespace cython
 

@@ -424,6 +424,41 @@ int ibh_e1ve0_compute(int32_t nsheets, const ibh_weighted *const *XuE1s, const i
 int ibh_weighted_make_I2vX(const ibh_weighted *IvX, const ibh_hntr *hIvI2, double eq_rad, const uint8_t *includeI, int64_t nincl,
                            ibh_sparse_set *dimI2, ibh_weighted **out);
 
+/* ------------------------------------------------------------------------- */
+/* ModelE's regridder: GCMRegridder_ModelE::regrid_matrices (slib/icebin/modele/GCMRegridder_ModelE.cpp:487-571).  rmO holds
+ * the matrices on ModelE's OCEAN grid O = HntrSpec(imO, jmO, offiO, dlatO); the atmosphere grid A is make_hntrA(O) =
+ * HntrSpec(imO/2, jmO/2, offiO/2, 2*dlatO) (modele/hntr.cpp:232-241).  foceanAOp / foceanAOm [nO], sparse O indexing: the
+ * ocean fraction the ice model sees (may be fractional) and the one ModelE sees (0 or 1); both are copied.  rmO must outlive
+ * the result.  IBH_EINVAL before anything is allocated: odd imO or jmO, imO*jmO != nA of the regridder, nO != nA, an
+ * indexingHC that is neither (stride_A, stride_HC) = (1, nO) nor (nhc, 1) -- the A grid keeps the order with nA_A =
+ * (imO/2)*(jmO/2) in place of nO (:451-456).  A non-zero sigma in rmO: IBH_ENOTIMPL. */
+typedef struct ibh_modele_matrices ibh_modele_matrices;
+int ibh_modele_matrices_create(const ibh_regrid_matrices *rmO, int32_t imO, int32_t jmO, double offiO, double dlatO, double eq_rad,
+                               const double *foceanAOp, const double *foceanAOm, int64_t nO, ibh_modele_matrices **out);
+/* matrix_d of that object.  spec in {AvI EvI AvX EvX} (compute_XAmvGp, :318-368; aliases AAmvIp EAmvIp), {IvA IvE XvA XvE}
+ * (compute_GpvXAm, :379-433; aliases IpvAAm IpvEAm), both through ComputeXAmvGp_Helper (:168-280), or the test matrices
+ * AOmvAAm / AAmvAOm (:92-121, Hntr's clipped overlap: see ibh_hntr_matrix_d; for both, dim0 is dimAOm, which also clips,
+ * and dim1 dimAAm, as the reference passes them; conservative = 1); any other name: IBH_ENOKEY.  The sets are
+ * numbered as the reference numbers them: the ice / exchange set by the first O-grid build (Av{G}, scale = false, correctA =
+ * true), the atmosphere set by the Hntr stream (raw_EOvEA's for E), whichever side they stand on.  conservative = 0, scaled =
+ * scale; XAmvGp: wM = wXAm, Mw = XOpvIp.Mw; GpvXAm: wM = XOpvIp.Mw, Mw = wXAm.  Every product sums its terms over the dense
+ * inner index ascending, the first assigned, each operand rounded before the product.
+ * dim0 / dim1 are IN/OUT as in ibh_regrid_matrices_matrix_d and must outlive the result; NULL: a fresh set owned by the
+ * result.  A set with sparse extent -1 takes nA_A, nE_A = nA_A*nhc, nI or nX; any other extent is IBH_EINVAL.  A cell of the
+ * O-grid build whose foceanAOm is neither 0 nor 1 is IBH_EINVAL and the message names the cell (topo.cpp:70-71); an Hntr
+ * overlap below 1e-8 in magnitude is IBH_EINVAL (topo.cpp:138-139).  On any error *out is NULL and both sets are as they were. */
+int ibh_modele_matrices_matrix_d(const ibh_modele_matrices *mm, const char *spec, ibh_sparse_set *dim0, ibh_sparse_set *dim1,
+                                 int scale, ibh_weighted **out);
+int ibh_modele_matrices_destroy(ibh_modele_matrices *mm);
+/* make_agridA (:57-78): the cells of A under the realised cells of rgO's grid, first-seen in Hntr's stream order.
+ * *nA_dense is always set; to_sparse (may be NULL) receives that many indices (at most (imO/2)*(jmO/2)). */
+int ibh_modele_agridA(const ibh_regridder *rgO, int32_t imO, int32_t jmO, double offiO, double dlatO, int32_t *nA_dense,
+                      int64_t *to_sparse);
+/* Diagnostic: the sparse product the ModelE matrices are composed with, alone.  C = L * R for two matrices in HBM (columns
+ * ascending inside a row, L's columns = R's rows): C(r, c) sums L(r, k) * R(k, c) over k ascending, the first term assigned;
+ * an entry exists wherever a term does.  Identity dims, wM = Mw = 0, flags of L.  Used by tests/test_gpu_modele.py. */
+int ibh_selftest_csr_product(const ibh_weighted *L, const ibh_weighted *R, ibh_weighted **out);
+
 /* Public members of Weighted_Eigen, read back to host. */
 int ibh_weighted_shape(const ibh_weighted *w, int32_t *nrow_d, int32_t *ncol_d, int64_t *nnz);
 int ibh_weighted_flags(const ibh_weighted *w, int *conservative, int *scaled);
