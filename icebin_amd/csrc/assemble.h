@@ -24,7 +24,7 @@ void weighted_from_coo_device(ibh_weighted *w, int nrow, int ncol, int64_t n, co
 // setFromTriplets from DEVICE triplets (dense ids, input order) plus wM / Mw = sum(M, dim, '+'), enqueued on st (assemble.hip)
 void weighted_from_device_triplets(ibh_weighted *w, int nrow, int ncol, int64_t n, const int32_t *drow, const int32_t *dcol,
                                    const double *dval, hipStream_t st);
-// the same without the weights: only w's CSR (modele.hip's products and re-numbered copies)
+// the same without the weights: only w's CSR (csrops.hip: the products and re-numbered copies)
 void csr_from_device_triplets(ibh_weighted *w, int nrow, int ncol, int64_t n, const int32_t *drow, const int32_t *dcol,
                               const double *dval, hipStream_t st);
 // compute_E1vE0c (e1ve0.cpp:55-106) on device; `out` comes with identity dims over nE.

@@ -17,6 +17,7 @@
 // no FMA contraction (this file is compiled with -ffp-contract=off), so the
 // CSR structure, dims, wM, Mw and M are bit-identical to the oracle.
 #include "assemble.h"
+#include "csrops.h"
 #include "prims.h"
 #include "sweep_kernel.inl"
 #include <algorithm>
@@ -276,6 +277,10 @@ void ibh_sparse_set::check_entries_within(int64_t extent, const char *what) cons
     for (int32_t i = 0; i < n_; ++i)
         IBH_CHECK(host_[(size_t)i] >= 0 && host_[(size_t)i] < extent, "%s entry %lld outside [0, %lld)", what,
                   (long long)host_[(size_t)i], (long long)extent);
+}
+void ibh_sparse_set::check_extent(int64_t extent, const char *what) const {
+    IBH_CHECK(sparse_extent_ == -1 || sparse_extent_ == extent, "%s has sparse extent %lld, the grid %lld cells", what,
+              (long long)sparse_extent_, (long long)extent);
 }
 void ibh_sparse_set::copy_to_sparse(int64_t *dst, int n, hipStream_t st) const {
     if (n == 0) return;
@@ -1908,7 +1913,8 @@ static void smooth_matrix(ibh_weighted *w, const ibh_regrid_matrices *rm, const 
 
 // The same structure for a matrix that already exists (either assembly path; spmm.hip calls this when an E-row matrix is
 // applied again and again): per-column slots from the CSR, then build_bands.  One synchronisation (the band count).
-__global__ void k_expand_rows(const int32_t *__restrict__ rowptr, int nrow, int32_t *__restrict__ row) {
+// (csrops.h's expand_rows gives a thread a row: for the short rows of the GCM-grid matrices)
+__global__ void k_expand_long_rows(const int32_t *__restrict__ rowptr, int nrow, int32_t *__restrict__ row) {
     const int r = blockIdx.x;                         // one workgroup per row: rows of E matrices hold 10^1..10^4 entries
     for (int k = rowptr[r] + threadIdx.x; k < rowptr[r + 1]; k += blockDim.x) row[k] = r;
 }
@@ -1923,7 +1929,7 @@ Bands build_bands_from_csr(const ibh_weighted *w, hipStream_t st) {
     RgView rg{};
     rg.sA = w->band_sA; rg.sHC = w->band_sHC;
     int32_t *row = A.get<int32_t>((size_t)nnz);
-    hipLaunchKernelGGL(k_expand_rows, dim3(nrow), dim3(T), 0, st, w->rowptr.p, nrow, row);
+    hipLaunchKernelGGL(k_expand_long_rows, dim3(nrow), dim3(T), 0, st, w->rowptr.p, nrow, row);
     uint32_t *colptr = A.get<uint32_t>((size_t)ncol + 1);
     uint32_t *cntc = A.get<uint32_t>(2 * (size_t)ncol + 1), *fillc = cntc + ncol;
     int32_t *lrow = A.get<int32_t>((size_t)nnz);
@@ -2378,12 +2384,11 @@ bool assemble_matrix(const ibh_regrid_matrices *rm, const char *spec_name, ibh_s
     RgView rg{g->ex_indices.p, g->ex_area.p, rm->elevmaskI.p, g->hcdefs.p, g->A_ratio_s.p, g->nX, g->nA,
               g->nhc, g->interp_style, g->hc_stride_A, g->hc_stride_HC};
 
-    std::unique_ptr<ibh_weighted> w(new ibh_weighted);
-    IBH_HIP(hipGetDevice(&w->device));
+    auto w = new_weighted();
     ibh_sparse_set *dims[2] = {dim0, dim1};
     for (int k = 0; k < 2; ++k) {
-        if (!dims[k]) { dims[k] = new ibh_sparse_set; w->owns[k] = true; }
-        w->dims[k] = dims[k];
+        w->dims[k] = dims[k] ? DimRef::borrowed(dims[k]) : DimRef::owned(std::make_unique<ibh_sparse_set>());
+        dims[k] = w->dims[k].get();
     }
     w->conservative = 1;              // :63, :167 (no smoothing), :258
     w->scaled = scale;                // :421
@@ -2406,10 +2411,7 @@ bool assemble_matrix(const ibh_regrid_matrices *rm, const char *spec_name, ibh_s
         *out = w.release();
         return true;
     }
-    if (fast_only) {
-        for (int k = 0; k < 2; ++k) if (w->owns[k]) { delete dims[k]; w->owns[k] = false; w->dims[k] = nullptr; }
-        return false;
-    }
+    if (fast_only) return false;
     A.reset();
     // counters read back with ONE sync: [0] first out-of-range exchange cell, [1] new row keys,
     // [2] new column keys, [3] number of contributions
@@ -2786,14 +2788,6 @@ __global__ void k_add_by_sparse(const double *__restrict__ v, const int64_t *__r
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) { const int64_t s = to_sparse[i]; acc[s] = acc[s] + v[i]; }       // sparse ids of one matrix are distinct
 }
-__global__ void k_scale_rows_inv(const int32_t *__restrict__ rowptr, int nrow, double *__restrict__ val, const double *__restrict__ sum) {
-    const int r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= nrow) return;
-    const int b = rowptr[r], e = rowptr[r + 1];
-    if (b == e) return;
-    const double s = 1. / sum[r];
-    for (int k = b; k < e; ++k) val[k] = val[k] * s;          // ii->value() *= sE1(iE1)
-}
 __global__ void k_csr_to_contrib(const int32_t *__restrict__ rowptr, const int32_t *__restrict__ colind, const double *__restrict__ val,
                                  int nrow, uint32_t base, uint64_t *__restrict__ keys, uint32_t *__restrict__ idx, double *__restrict__ term) {
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
@@ -2858,8 +2852,7 @@ void e1ve0_compute(int nsheets, const ibh_weighted *const *XuE1s, const ibh_weig
         locals.push_back(std::move(loc));
     }
     // scale by 1 / (sum over sheets of Mw(XuE1)), then consolidate across sheets
-    for (auto &loc : locals)
-        hipLaunchKernelGGL(k_scale_rows_inv, dim3(ceil_div(nE, T)), dim3(T), 0, st, loc->rowptr.p, (int)nE, loc->val.p, sE1);
+    for (auto &loc : locals) scale_rows_recip(loc->rowptr.p, (int)nE, sE1, loc->val.p, st);     // ii->value() *= sE1(iE1)
     IBH_HIP(hipGetLastError());
     if (locals.size() == 1) {
         out->rowptr = std::move(locals[0]->rowptr); out->colind = std::move(locals[0]->colind); out->val = std::move(locals[0]->val);
@@ -2895,21 +2888,13 @@ void e1ve0_compute(int nsheets, const ibh_weighted *const *XuE1s, const ibh_weig
 // assigned) does the rest.  The column sum of I2vI runs over its rows ascending from 0, as spsparse's sum(M, 1, '-').
 __global__ void k_i2vx_count(const int32_t *__restrict__ r2, const int32_t *__restrict__ rx, int nI, uint32_t *__restrict__ cnt,
                              unsigned long long *__restrict__ total) {
-    __shared__ unsigned long long part[4];
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     unsigned long long c = 0;
     if (i < nI) {
         c = (unsigned long long)(r2[i + 1] - r2[i]) * (unsigned long long)(rx[i + 1] - rx[i]);
         cnt[i] = (uint32_t)c;
     }
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x / 64] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long s = 0;
-        for (int w = 0; w < (int)(blockDim.x / 64); ++w) s += part[w];
-        if (s) atomicAdd(total, s);
-    }
+    add_to_launch_total(c, total);
 }
 __global__ void k_i2vx_terms(const int32_t *__restrict__ r2, const int32_t *__restrict__ c2, const double *__restrict__ v2,
                              const int32_t *__restrict__ rx, const int32_t *__restrict__ cx, const double *__restrict__ vx,

@@ -92,12 +92,15 @@ void require_device() {
         fail(IBH_ENODEVICE, "no HIP device available (%s); libicebin_hip has no CPU fallback",
              e == hipSuccess ? "device count is 0" : hipGetErrorString(e));
 }
+void check_current_device(int device, const char *what) {
+    int dev = -1;
+    IBH_HIP(hipGetDevice(&dev));
+    IBH_CHECK(dev == device, "%s belongs to device %d, current device is %d", what, device, dev);
+}
 
 static void check_weighted_device(const ibh_weighted *w) {
     IBH_CHECK(w != nullptr, "null Weighted handle");
-    int dev = -1;
-    IBH_HIP(hipGetDevice(&dev));
-    IBH_CHECK(dev == w->device, "Weighted handle belongs to device %d, current device is %d", w->device, dev);
+    check_current_device(w->device, "Weighted handle");
 }
 
 // The ibh_selftest_* entries of the integer primitives run one primitive each on hipStreamPerThread (as the builds do: calls from concurrent host threads overlap).
@@ -324,9 +327,7 @@ int ibh_regrid_matrices_create(const ibh_regridder *rg, const double *elevmaskI,
         IBH_CHECK(rg && elevmaskI && out, "null argument");
         // np_to_blitz shape check {nI}, icebin_cython.cpp:231
         IBH_CHECK(n == rg->nI, "elevmaskI has %ld elements, the ice grid has nI=%ld", (long)n, (long)rg->nI);
-        int dev = -1;
-        IBH_HIP(hipGetDevice(&dev));
-        IBH_CHECK(dev == rg->device, "regridder belongs to device %d, current device is %d", rg->device, dev);
+        check_current_device(rg->device, "regridder");
         std::unique_ptr<ibh_regrid_matrices> rm(new ibh_regrid_matrices);
         rm->rg = rg;
         rm->scale = scale; rm->correctA = correctA;
@@ -342,9 +343,7 @@ int ibh_regrid_matrices_create_device(const ibh_regridder *rg, const double *d_e
     return guarded([&] {
         IBH_CHECK(rg && d_elevmaskI && out, "null argument");
         IBH_CHECK(n == rg->nI, "elevmaskI has %ld elements, the ice grid has nI=%ld", (long)n, (long)rg->nI);
-        int dev = -1;
-        IBH_HIP(hipGetDevice(&dev));
-        IBH_CHECK(dev == rg->device, "regridder belongs to device %d, current device is %d", rg->device, dev);
+        check_current_device(rg->device, "regridder");
         std::unique_ptr<ibh_regrid_matrices> rm(new ibh_regrid_matrices);
         rm->rg = rg;
         rm->scale = scale; rm->correctA = correctA;
@@ -359,11 +358,7 @@ int ibh_regrid_matrices_create_device(const ibh_regridder *rg, const double *d_e
 }
 int ibh_regrid_matrices_destroy(ibh_regrid_matrices *rm) { delete rm; return IBH_OK; }
 
-static void check_rm_device(const ibh_regrid_matrices *rm) {
-    int dev = -1;
-    IBH_HIP(hipGetDevice(&dev));
-    IBH_CHECK(dev == rm->rg->device, "regridder belongs to device %d, current device is %d", rm->rg->device, dev);
-}
+static void check_rm_device(const ibh_regrid_matrices *rm) { check_current_device(rm->rg->device, "regridder"); }
 int ibh_regrid_matrices_matrix_d(const ibh_regrid_matrices *rm, const char *spec, ibh_sparse_set *dim0,
                                  ibh_sparse_set *dim1, int scale, int correctA, const double sigma[3],
                                  ibh_weighted **out) {
@@ -411,13 +406,10 @@ static std::unique_ptr<ibh_weighted> new_loaded(int32_t nrow, int32_t ncol, cons
     require_device();
     IBH_CHECK(nrow >= 0 && ncol >= 0, "negative shape");
     IBH_CHECK((nrow == 0 || wM) && (ncol == 0 || Mw), "null weight vector");
-    std::unique_ptr<ibh_weighted> w(new ibh_weighted);
-    IBH_HIP(hipGetDevice(&w->device));
+    auto w = new_weighted();
     w->nrow = nrow; w->ncol = ncol;
     w->conservative = conservative; w->scaled = scaled;
-    for (int k = 0; k < 2; ++k) { w->dims[k] = new ibh_sparse_set; w->owns[k] = true; }
-    w->dims[0]->make_identity(nrow);
-    w->dims[1]->make_identity(ncol);
+    w->dims[0] = DimRef::owned_identity(nrow); w->dims[1] = DimRef::owned_identity(ncol);
     w->wM.upload(wM, (size_t)nrow);
     w->Mw.upload(Mw, (size_t)ncol);
     return w;
@@ -461,9 +453,8 @@ int ibh_e1ve0_compute(int32_t nsheets, const ibh_weighted *const *XuE1s, const i
         IBH_CHECK(out && nsheets >= 1 && XuE1s && XuE0s, "bad arguments");
         require_device();
         for (int s = 0; s < nsheets; ++s) { check_weighted_device(XuE1s[s]); check_weighted_device(XuE0s[s]); }
-        std::unique_ptr<ibh_weighted> w(new ibh_weighted);
-        IBH_HIP(hipGetDevice(&w->device));
-        for (int k = 0; k < 2; ++k) { w->dims[k] = new ibh_sparse_set; w->owns[k] = true; w->dims[k]->make_identity(nE); }
+        auto w = new_weighted();
+        w->dims[0] = DimRef::owned_identity(nE); w->dims[1] = DimRef::owned_identity(nE);
         e1ve0_compute(nsheets, XuE1s, XuE0s, nE, w.get());
         *out = w.release();
     });

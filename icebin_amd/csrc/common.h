@@ -8,6 +8,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <stdexcept>
 #include <string>
@@ -28,6 +29,12 @@ struct Error : std::exception {
 };
 [[noreturn]] void fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
 void set_last_error(const char *msg);
+// the status of a C-ABI call made from inside the library, as this call's own error
+inline void rethrow(int rc) { if (rc != IBH_OK) throw Error(rc, ibh_last_error()); }
+// there is a HIP device at all, else IBH_ENODEVICE: the library has no CPU fallback (defined in capi.hip, like the next one)
+void require_device();
+// a handle made on `device` is used on it: "<what> belongs to device %d, current device is %d"
+void check_current_device(int device, const char *what);
 
 #define IBH_HIP(expr)                                                                       \
     do {                                                                                    \
@@ -145,6 +152,8 @@ struct ibh_sparse_set {
     }
     // every entry the host holds lies in [0, extent), and there are no more entries than that; `what` names the set in the error
     void check_entries_within(int64_t extent, const char *what) const;
+    // the sparse extent is unset (-1) or `extent`, the cells of the grid the set is used for
+    void check_extent(int64_t extent, const char *what) const;
 
     // device side.  A set only READ by a build -- identity, pre-populated -- may be shared by builds running concurrently
     // (assemble_batch): the extent is written only when it changes, and a table that adds nothing changes nothing else.
@@ -360,6 +369,57 @@ struct ApplyState {
         f.napply = napply;
     }
 };
+
+// One dimension of a matrix: its set, and whether the matrix owns it (and deletes it with itself) or the caller does.  Made
+// by the named constructors alone, which are the cases there are.
+class DimRef {
+  public:
+    DimRef() = default;
+    DimRef(DimRef &&o) noexcept : set_(o.set_), owns_(o.owns_) { o.set_ = nullptr; o.owns_ = false; }
+    DimRef &operator=(DimRef &&o) noexcept { std::swap(set_, o.set_); std::swap(owns_, o.owns_); return *this; }
+    ~DimRef() { if (owns_) delete set_; }
+    static DimRef borrowed(ibh_sparse_set *callers) { return DimRef(callers, false); }
+    static DimRef owned(std::unique_ptr<ibh_sparse_set> set) { return DimRef(set.release(), true); }
+    static DimRef owned_identity(int64_t n) {
+        DimRef d = owned(std::make_unique<ibh_sparse_set>());
+        d->make_identity(n);
+        return d;
+    }
+    // the same set for a second matrix: the caller's is shared, one that `src`'s matrix owns is copied (the second matrix may
+    // outlive the first)
+    static DimRef borrow_or_copy(const DimRef &src) {
+        return src.owns_ ? owned(std::make_unique<ibh_sparse_set>(*src.set_)) : borrowed(src.set_);
+    }
+    ibh_sparse_set *get() const { return set_; }
+    ibh_sparse_set *operator->() const { return set_; }
+    operator ibh_sparse_set *() const { return set_; }
+
+  private:
+    DimRef(ibh_sparse_set *set, bool owns) : set_(set), owns_(owns) {}
+    ibh_sparse_set *set_ = nullptr;
+    bool owns_ = false;
+};
+
+// The set a build numbers in place of the caller's (null: nobody's): a copy of the caller's entries, or a fresh set.  The
+// caller's own set is untouched until commit(), which the build calls once nothing can fail any more and which cannot fail.
+class WorkingSet {
+  public:
+    explicit WorkingSet(ibh_sparse_set *callers)
+        : callers_(callers), work_(callers ? std::make_unique<ibh_sparse_set>(*callers) : std::make_unique<ibh_sparse_set>()) {}
+    ibh_sparse_set *get() const { return work_.get(); }
+    ibh_sparse_set *operator->() const { return work_.get(); }
+    ibh_sparse_set &operator*() const { return *work_; }
+    // the caller's set takes the entries and the matrix borrows it; without one the matrix owns the working set
+    DimRef commit() noexcept {
+        if (!callers_) return DimRef::owned(std::move(work_));
+        *callers_ = std::move(*work_);
+        return DimRef::borrowed(callers_);
+    }
+
+  private:
+    ibh_sparse_set *callers_;
+    std::unique_ptr<ibh_sparse_set> work_;
+};
 }  // namespace ibh
 // The matrix proper is immutable once it is built; `st` is the cache the applies keep beside it.
 struct ibh_weighted {
@@ -369,8 +429,7 @@ struct ibh_weighted {
     int64_t nnz = 0;
     ibh::DevBuf<int32_t> rowptr, colind;
     ibh::DevBuf<double> val, wM, Mw;
-    ibh_sparse_set *dims[2] = {nullptr, nullptr};
-    bool owns[2] = {false, false};
+    ibh::DimRef dims[2];
     int conservative = 1, scaled = 1;
     int built_fast = 0;                 // assembled by the plan-based fast path (fastasm.inl); introspection only
     ibh::ApplyKernel kernel_override = ibh::KERNEL_AUTO;     // SpMM dispatch (ibh_weighted_set_kernel)
@@ -379,10 +438,6 @@ struct ibh_weighted {
     int band_eligible = 0;
     int64_t band_sA = 0, band_sHC = 0;
     mutable ibh::ApplyState st;
-    ~ibh_weighted() {
-        for (int k = 0; k < 2; ++k)
-            if (owns[k]) delete dims[k];
-    }
 };
 
 namespace ibh {
@@ -392,6 +447,12 @@ inline MatrixFacts facts_of(const ibh_weighted &w) {
     f.band_eligible = w.band_eligible != 0; f.conservative = w.conservative != 0; f.kernel_override = w.kernel_override;
     w.st.fill(f);
     return f;
+}
+// a fresh handle on the current device
+inline std::unique_ptr<ibh_weighted> new_weighted() {
+    std::unique_ptr<ibh_weighted> w(new ibh_weighted);
+    IBH_HIP(hipGetDevice(&w->device));
+    return w;
 }
 }  // namespace ibh
 

@@ -1,0 +1,51 @@
+// csrops.h -- small algebra on CSR matrices that are already in HBM (csrops.hip): the sparse product, re-numbered copies, the
+// transpose, and row / vector scalings.  Each piece exists once; the matrix builds outside the exchange-grid assembly (modele.hip,
+// l1.hip, hntr.hip, E1vE0 and I2vX in assemble.hip) compose them.  Everything is enqueued on the caller's stream and uses the
+// calling thread's arena; what waits for the device says so.
+#pragma once
+#include "common.h"
+
+namespace ibh {
+
+struct Csr { const int32_t *rowptr, *colind; const double *val; int nrow; };
+inline Csr view(const ibh_weighted &w) { return Csr{w.rowptr.p, w.colind.p, w.val.p, w.nrow}; }
+
+// out's CSR = L * R as Eigen's conservative sparse product sums it (csrops.hip); resets the arena, one host wait
+void csr_product(const ibh_weighted &L, const ibh_weighted &R, ibh_weighted *out, hipStream_t st);
+// crop_mvp (GCMRegridder_ModelE.cpp:285-307) along the rows / the columns; one host wait each
+//   rows: row m of out is row d_src[m] of `in` (-1: none), its values d_rs[d_src[m]] * v (d_rs may be null)
+//   cols: column k of `in` becomes d_map[k] (-1: dropped), values (d_rs[row] * v) * d_cs[d_map[k]], either factor may be null
+void crop_rows(const ibh_weighted &in, const int32_t *d_src, int nout, const double *d_rs, ibh_weighted *out, hipStream_t st);
+void crop_cols(const ibh_weighted &in, const int32_t *d_map, int ncol_out, const double *d_rs, const double *d_cs, ibh_weighted *out,
+               hipStream_t st);
+// out's CSR = the transpose of in's (rows few and short: a matrix over the GCM grids); resets the arena
+void transpose_csr(const ibh_weighted &in, ibh_weighted *out, hipStream_t st);
+// row[e] = the row of entry e, one thread per row (short rows)
+void expand_rows(const int32_t *rowptr, int nrow, int32_t *row, hipStream_t st);
+// out = 1 / in (out is allocated);  out = a * b;  out[i] = in[idx[i]]
+void recip(const double *in, int n, DevBuf<double> &out, hipStream_t st);
+void mul(const double *a, const double *b, int n, double *out, hipStream_t st);
+void gather(const double *in, const int32_t *idx, long n, double *out, hipStream_t st);
+// diag(s) * M in place: val = s[row] * val
+void scale_rows(const int32_t *rowptr, int nrow, const double *s, double *val, hipStream_t st);
+// diag(1 / sum) * M in place: one reciprocal per row, val = val * (1 / sum[row]); rows without entries are skipped (their
+// sum may be 0)
+void scale_rows_recip(const int32_t *rowptr, int nrow, const double *sum, double *val, hipStream_t st);
+
+#ifdef __HIPCC__
+// Adds this thread's count into a per-launch total: wave shuffle, one partial per wave in LDS, one atomic per block.  Every
+// thread of the block calls it (it synchronises the block); blocks of at most 256 threads.
+__device__ inline void add_to_launch_total(unsigned long long c, unsigned long long *__restrict__ total) {
+    __shared__ unsigned long long part[4];
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x / 64] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long s = 0;
+        for (int w = 0; w < (int)(blockDim.x / 64); ++w) s += part[w];
+        if (s) atomicAdd(total, s);
+    }
+}
+#endif
+
+}  // namespace ibh

@@ -1,0 +1,241 @@
+// csrops.hip -- the generic CSR pieces (csrops.h).  Arithmetic notes: every product is rounded where it is written (the library
+// is compiled with -ffp-contract=off), and sums run in the order the comments give.
+#include "assemble.h"
+#include "csrops.h"
+#include "prims.h"
+
+namespace ibh {
+namespace {
+
+// ---- C = L * R -------------------------------------------------------------------------------------------------------------
+// Eigen's conservative sparse product: C(r, c) = sum_k L(r, k) * R(k, c) over k ascending, the first term assigned.  Row r of
+// L lists its k ascending, so walking it and, per k, row k of R emits the terms of every (r, c) in that order; a stable
+// ordering by (r, c) and sequential sums of equal keys (csr_from_device_triplets: setFromTriplets) finish it.
+__global__ void k_prod_count(Csr L, const int32_t *__restrict__ Rptr, uint32_t *__restrict__ cnt, unsigned long long *__restrict__ total) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    unsigned long long c = 0;
+    if (r < L.nrow) {
+        for (int e = L.rowptr[r]; e < L.rowptr[r + 1]; ++e) {
+            const int k = L.colind[e];
+            c += (unsigned long long)(Rptr[k + 1] - Rptr[k]);
+        }
+        cnt[r] = (uint32_t)c;
+    }
+    add_to_launch_total(c, total);
+}
+// LANES lanes per row of L: 1 for short rows of R (ice rows: a term or two), 64 where a row of R is an O cell's ice cells
+template <int LANES>
+__global__ void k_prod_emit(Csr L, Csr R, const uint32_t *__restrict__ pos, int32_t *__restrict__ row, int32_t *__restrict__ col,
+                            double *__restrict__ term) {
+    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long r = t / LANES;
+    const int lane = (int)(t % LANES);
+    if (r >= L.nrow) return;
+    uint32_t p = pos[r];
+    for (int e = L.rowptr[r]; e < L.rowptr[r + 1]; ++e) {
+        const int k = L.colind[e];
+        const double l = L.val[e];
+        const int b = R.rowptr[k], n = R.rowptr[k + 1] - b;
+        for (int q = lane; q < n; q += LANES) {
+            row[p + q] = (int32_t)r; col[p + q] = R.colind[b + q]; term[p + q] = l * R.val[b + q];
+        }
+        p += (uint32_t)n;
+    }
+}
+}  // namespace
+void csr_product(const ibh_weighted &L, const ibh_weighted &R, ibh_weighted *out, hipStream_t st) {
+    IBH_CHECK(L.ncol == R.nrow, "product: L has %d columns, R %d rows", L.ncol, R.nrow);
+    Arena &A = arena();
+    A.reset();
+    const int T = 256, n = L.nrow;
+    uint32_t *pos = A.get<uint32_t>((size_t)n + 1);
+    unsigned long long *tot = A.get<unsigned long long>(1);
+    IBH_HIP(hipMemsetAsync(tot, 0, sizeof(unsigned long long), st));
+    if (n) hipLaunchKernelGGL(k_prod_count, dim3(ceil_div(n, T)), dim3(T), 0, st, view(L), R.rowptr.p, pos, tot);
+    IBH_HIP(hipGetLastError());
+    unsigned long long total = 0;
+    readback_sync(&total, tot, sizeof(total), st);          // the one host wait of the product
+    IBH_CHECK(total <= INT32_MAX, "product: %llu terms exceed INT32_MAX", total);
+    exclusive_scan_u32(pos, pos, (size_t)n, pos + n, st);
+    int32_t *row = A.get<int32_t>((size_t)total), *col = A.get<int32_t>((size_t)total);
+    double *term = A.get<double>((size_t)total);
+    if (n && total) {
+        if (total >= 8ull * (unsigned long long)n)
+            hipLaunchKernelGGL(k_prod_emit<64>, dim3(ceil_div((long)n * 64, T)), dim3(T), 0, st, view(L), view(R), pos, row, col, term);
+        else
+            hipLaunchKernelGGL(k_prod_emit<1>, dim3(ceil_div(n, T)), dim3(T), 0, st, view(L), view(R), pos, row, col, term);
+    }
+    IBH_HIP(hipGetLastError());
+    csr_from_device_triplets(out, L.nrow, R.ncol, (int64_t)total, row, col, term, st);
+}
+
+namespace {
+// ---- crop_mvp (GCMRegridder_ModelE.cpp:285-307) ----------------------------------------------------------------------------
+// index 0: row m of the result is row src[m] of `in` (-1: none), its values rounded once as rs[src[m]] * v (rs may be null).
+// One wave per row: a row is an O cell's (or elevation class's) ice cells.
+__global__ void k_crop_rows_count(const int32_t *__restrict__ inptr, const int32_t *__restrict__ src, int nout, uint32_t *__restrict__ cnt) {
+    const int m = blockIdx.x * blockDim.x + threadIdx.x;
+    if (m < nout) cnt[m] = src[m] >= 0 ? (uint32_t)(inptr[src[m] + 1] - inptr[src[m]]) : 0u;
+}
+__global__ void k_crop_rows_fill(Csr in, const int32_t *__restrict__ src, const double *__restrict__ rs, int nout,
+                                 const int32_t *__restrict__ outptr, int32_t *__restrict__ col, double *__restrict__ val) {
+    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long m = t >> 6;
+    const int lane = (int)(t & 63);
+    if (m >= nout || src[m] < 0) return;
+    const int p = src[m], b = in.rowptr[p], n = in.rowptr[p + 1] - b, o = outptr[m];
+    const double s = rs ? rs[p] : 1.;
+    for (int q = lane; q < n; q += 64) {
+        col[o + q] = in.colind[b + q];
+        val[o + q] = rs ? s * in.val[b + q] : in.val[b + q];
+    }
+}
+// index 1: column k of `in` becomes map[k] (-1: the entry is dropped); value (rs[i] * v) * cs[map[k]], each factor optional and
+// each product rounded.  One thread per row (an ice or exchange cell: a few entries), which then puts its columns in
+// ascending order again by insertion (map is one-to-one: no ties).
+__global__ void k_crop_cols_count(Csr in, const int32_t *__restrict__ map, uint32_t *__restrict__ cnt) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= in.nrow) return;
+    uint32_t c = 0;
+    for (int e = in.rowptr[i]; e < in.rowptr[i + 1]; ++e) c += map[in.colind[e]] >= 0 ? 1u : 0u;
+    cnt[i] = c;
+}
+__global__ void k_crop_cols_fill(Csr in, const int32_t *__restrict__ map, const double *__restrict__ rs, const double *__restrict__ cs,
+                                 const int32_t *__restrict__ outptr, int32_t *__restrict__ col, double *__restrict__ val) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= in.nrow) return;
+    const int o = outptr[i];
+    int n = 0;
+    for (int e = in.rowptr[i]; e < in.rowptr[i + 1]; ++e) {
+        const int k = map[in.colind[e]];
+        if (k < 0) continue;
+        double v = in.val[e];
+        if (rs) v = rs[i] * v;
+        if (cs) v = v * cs[k];
+        int q = n++;
+        for (; q > 0 && col[o + q - 1] > k; --q) { col[o + q] = col[o + q - 1]; val[o + q] = val[o + q - 1]; }
+        col[o + q] = k; val[o + q] = v;
+    }
+}
+// rowptr = scan(cnt) with the total at the end; returns nnz (one host wait)
+int64_t finish_rowptr(uint32_t *cnt, int nrow, ibh_weighted *out, hipStream_t st) {
+    out->rowptr.alloc((size_t)nrow + 1);
+    uint32_t *ptr = reinterpret_cast<uint32_t *>(out->rowptr.p);
+    exclusive_scan_u32(cnt, ptr, (size_t)nrow, ptr + nrow, st);
+    uint32_t nnz = 0;
+    readback_sync(&nnz, ptr + nrow, sizeof(nnz), st);
+    IBH_CHECK(nnz < (1u << 31), "nnz overflows int32");
+    out->nnz = nnz;
+    out->colind.alloc(nnz); out->val.alloc(nnz);
+    return nnz;
+}
+}  // namespace
+// d_src: device int32 [nout]
+void crop_rows(const ibh_weighted &in, const int32_t *d_src, int nout, const double *d_rs, ibh_weighted *out, hipStream_t st) {
+    Arena &A = arena();
+    const int T = 256;
+    uint32_t *cnt = A.get<uint32_t>((size_t)nout);
+    if (nout) hipLaunchKernelGGL(k_crop_rows_count, dim3(ceil_div(nout, T)), dim3(T), 0, st, in.rowptr.p, d_src, nout, cnt);
+    out->nrow = nout; out->ncol = in.ncol;
+    if (finish_rowptr(cnt, nout, out, st))
+        hipLaunchKernelGGL(k_crop_rows_fill, dim3(ceil_div((long)nout * 64, T)), dim3(T), 0, st, view(in), d_src, d_rs, nout, out->rowptr.p,
+                           out->colind.p, out->val.p);
+    IBH_HIP(hipGetLastError());
+}
+void crop_cols(const ibh_weighted &in, const int32_t *d_map, int ncol_out, const double *d_rs, const double *d_cs, ibh_weighted *out,
+               hipStream_t st) {
+    Arena &A = arena();
+    const int T = 256, n = in.nrow;
+    uint32_t *cnt = A.get<uint32_t>((size_t)n);
+    if (n) hipLaunchKernelGGL(k_crop_cols_count, dim3(ceil_div(n, T)), dim3(T), 0, st, view(in), d_map, cnt);
+    out->nrow = n; out->ncol = ncol_out;
+    if (finish_rowptr(cnt, n, out, st))
+        hipLaunchKernelGGL(k_crop_cols_fill, dim3(ceil_div(n, T)), dim3(T), 0, st, view(in), d_map, d_rs, d_cs, out->rowptr.p, out->colind.p,
+                           out->val.p);
+    IBH_HIP(hipGetLastError());
+}
+
+// ---- the small vectors and row scalings ---------------------------------------------------------------------------------------
+namespace {
+__global__ void k_recip(const double *__restrict__ in, int n, double *__restrict__ out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = 1. / in[i];
+}
+__global__ void k_mul(const double *__restrict__ a, const double *__restrict__ b, int n, double *__restrict__ out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = a[i] * b[i];
+}
+__global__ void k_gather(const double *__restrict__ in, const int32_t *__restrict__ idx, long n, double *__restrict__ out) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = in[idx[i]];
+}
+__global__ void k_scale_rows(const int32_t *__restrict__ rowptr, int nrow, const double *__restrict__ s, double *__restrict__ val) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= nrow) return;
+    for (int e = rowptr[r]; e < rowptr[r + 1]; ++e) val[e] = s[r] * val[e];
+}
+__global__ void k_scale_rows_recip(const int32_t *__restrict__ rowptr, int nrow, double *__restrict__ val, const double *__restrict__ sum) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= nrow) return;
+    const int b = rowptr[r], e = rowptr[r + 1];
+    if (b == e) return;
+    const double s = 1. / sum[r];
+    for (int k = b; k < e; ++k) val[k] = val[k] * s;
+}
+__global__ void k_expand_rows(const int32_t *__restrict__ rowptr, int nrow, int32_t *__restrict__ row) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= nrow) return;
+    for (int e = rowptr[r]; e < rowptr[r + 1]; ++e) row[e] = r;
+}
+}  // namespace
+void recip(const double *in, int n, DevBuf<double> &out, hipStream_t st) {
+    out.alloc((size_t)n);
+    if (n) hipLaunchKernelGGL(k_recip, dim3(ceil_div(n, 256)), dim3(256), 0, st, in, n, out.p);
+}
+void mul(const double *a, const double *b, int n, double *out, hipStream_t st) {
+    if (n) hipLaunchKernelGGL(k_mul, dim3(ceil_div(n, 256)), dim3(256), 0, st, a, b, n, out);
+}
+void gather(const double *in, const int32_t *idx, long n, double *out, hipStream_t st) {
+    if (n) hipLaunchKernelGGL(k_gather, dim3(ceil_div(n, 256)), dim3(256), 0, st, in, idx, n, out);
+}
+void scale_rows(const int32_t *rowptr, int nrow, const double *s, double *val, hipStream_t st) {
+    if (nrow) hipLaunchKernelGGL(k_scale_rows, dim3(ceil_div(nrow, 256)), dim3(256), 0, st, rowptr, nrow, s, val);
+}
+void scale_rows_recip(const int32_t *rowptr, int nrow, const double *sum, double *val, hipStream_t st) {
+    if (nrow) hipLaunchKernelGGL(k_scale_rows_recip, dim3(ceil_div(nrow, 256)), dim3(256), 0, st, rowptr, nrow, val, sum);
+}
+void expand_rows(const int32_t *rowptr, int nrow, int32_t *row, hipStream_t st) {
+    if (nrow) hipLaunchKernelGGL(k_expand_rows, dim3(ceil_div(nrow, 256)), dim3(256), 0, st, rowptr, nrow, row);
+}
+void transpose_csr(const ibh_weighted &in, ibh_weighted *out, hipStream_t st) {
+    Arena &A = arena();
+    A.reset();
+    int32_t *row = A.get<int32_t>((size_t)in.nnz);
+    expand_rows(in.rowptr.p, in.nrow, row, st);
+    IBH_HIP(hipGetLastError());
+    csr_from_device_triplets(out, in.ncol, in.nrow, in.nnz, in.colind.p, row, in.val.p, st);
+}
+
+}  // namespace ibh
+
+using namespace ibh;
+extern "C" {
+
+int ibh_selftest_csr_product(const ibh_weighted *L, const ibh_weighted *R, ibh_weighted **out) {
+    if (out) *out = nullptr;
+    return guarded([&] {
+        IBH_CHECK(L && R && out, "null argument");
+        require_device();
+        hipStream_t st = hipStreamPerThread;
+        auto w = new_weighted();
+        csr_product(*L, *R, w.get(), st);
+        w->wM.alloc((size_t)w->nrow); w->wM.zero(st);
+        w->Mw.alloc((size_t)w->ncol); w->Mw.zero(st);
+        IBH_HIP(hipStreamSynchronize(st));
+        w->conservative = L->conservative; w->scaled = L->scaled;
+        w->dims[0] = DimRef::owned_identity(w->nrow); w->dims[1] = DimRef::owned_identity(w->ncol);
+        *out = w.release();
+    });
+}
+
+}  // extern "C"

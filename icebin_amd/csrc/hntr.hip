@@ -30,8 +30,6 @@
 
 namespace ibh {
 
-void require_device();      // capi.hip
-
 constexpr int HNTR_LDS = 5056;      // most doubles of LDS per workgroup: with the row windows, 40 KiB (four workgroups per CU)
 constexpr int HNTR_LDS_SMALL = 2496;    // the same for 20 KiB (eight workgroups per CU)
 constexpr int HNTR_STAGE = 32;      // doubles a lane holds between its global loads and its LDS writes
@@ -354,9 +352,7 @@ static void hntr_regrid(const ibh_hntr *h, const double *dWTA, int64_t wta_ld, c
 static void check_regrid_args(const ibh_hntr *h, const void *WTA, int64_t wta_ld, const void *A, int32_t nvar, int64_t lda,
                               const void *B, int64_t ldb, int mean_polar) {
     IBH_CHECK(h != nullptr, "null Hntr handle");
-    int dev = -1;
-    IBH_HIP(hipGetDevice(&dev));
-    IBH_CHECK(dev == h->device, "Hntr handle belongs to device %d, current device is %d", h->device, dev);
+    check_current_device(h->device, "Hntr handle");
     const int64_t nA = (int64_t)h->imA * h->jmA, nB = (int64_t)h->imB * h->jmB;
     IBH_CHECK(nvar >= 0 && (nvar == 0 || (WTA && A && B)), "Hntr regrid: bad arguments (nvar=%d or a null array)", nvar);
     IBH_CHECK(lda >= nA && ldb >= nB, "Hntr regrid: leading dimensions too small (lda=%lld < %lld or ldb=%lld < %lld)",
@@ -731,9 +727,7 @@ static HmArgs hm_prepare(const ibh_hntr *h, int kind, double eq_rad, const uint8
 static void hm_check(const ibh_hntr *h, int kind) {
     IBH_CHECK(h != nullptr, "null Hntr handle");
     hm_check_kind(kind);
-    int dev = -1;
-    IBH_HIP(hipGetDevice(&dev));
-    IBH_CHECK(dev == h->device, "Hntr handle belongs to device %d, current device is %d", h->device, dev);
+    check_current_device(h->device, "Hntr handle");
 }
 
 // the set a matrix_d call uses for one side: the caller's (sparse extent -1 takes the grid's) or a fresh identity
@@ -743,9 +737,9 @@ static void hm_check_transform(int transform, const char *which) {
 }
 static ibh_sparse_set *hm_dims(ibh_sparse_set *set, int64_t extent, const char *which) {
     if (!set) return nullptr;
-    IBH_CHECK(set->sparse_extent() == -1 || set->sparse_extent() == extent, "Hntr matrix_d: %s has sparse extent %lld, the grid %lld cells",
-              which, (long long)set->sparse_extent(), (long long)extent);
-    set->check_entries_within(extent, (std::string("Hntr matrix_d: ") + which).c_str());
+    const std::string what = std::string("Hntr matrix_d: ") + which;
+    set->check_extent(extent, what.c_str());
+    set->check_entries_within(extent, what.c_str());
     return set;
 }
 static bool hm_full_identity(const ibh_sparse_set *set, int64_t extent) {
@@ -813,8 +807,7 @@ static void hntr_matrix(const ibh_hntr *h, int kind, double eq_rad, const uint8_
     hipStream_t st = nullptr;
     Arena &A = arena();
     A.reset();
-    std::unique_ptr<ibh_weighted> w(new ibh_weighted);
-    IBH_HIP(hipGetDevice(&w->device));
+    auto w = new_weighted();
     w->conservative = 1;
     w->scaled = kind == IBH_HNTR_SCALED;
     HmNumber nbB, nbA;          // the fast path numbers nothing: the sets only take their sparse extent
@@ -865,18 +858,12 @@ static void hntr_matrix(const ibh_hntr *h, int kind, double eq_rad, const uint8_
         grownA = hm_number_grow(nbA, iA, 1, (long)n, rb.newA, st);
         IBH_HIP(hipStreamSynchronize(st));
     }
-    std::unique_ptr<ibh_sparse_set> fresh[2];
-    for (int k = 0; k < 2; ++k)
-        if (!(k ? dimA : dimB)) {
-            fresh[k].reset(new ibh_sparse_set);
-            fresh[k]->make_identity(k ? nA : nB);
-        }
+    // the fresh identities first (they allocate), then the caller's sets take their tables: that cannot fail
+    DimRef dB = dimB ? DimRef::borrowed(dimB) : DimRef::owned_identity(nB), dA = dimA ? DimRef::borrowed(dimA) : DimRef::owned_identity(nA);
     if (dimB) dimB->adopt_device(std::move(grownB), (int32_t)grownB.n, nB);
     if (dimA) dimA->adopt_device(std::move(grownA), (int32_t)grownA.n, nA);
-    const bool ownB = !dimB, ownA = !dimA;
-    ibh_sparse_set *dB = ownB ? fresh[0].release() : dimB, *dA = ownA ? fresh[1].release() : dimA;
-    w->dims[0] = transpose ? dA : dB; w->owns[0] = transpose ? ownA : ownB;
-    w->dims[1] = transpose ? dB : dA; w->owns[1] = transpose ? ownB : ownA;
+    w->dims[transpose ? 1 : 0] = std::move(dB);
+    w->dims[transpose ? 0 : 1] = std::move(dA);
     *out = w.release();
 }
 
@@ -999,9 +986,7 @@ static const ibh_hntr *hx_check_desc(const ibh_hntr_regridder_desc *d) {
     IBH_CHECK(d != nullptr, "null argument");
     const ibh_hntr *h = d->hntr;
     IBH_CHECK(h != nullptr, "global_ec: null Hntr handle");
-    int dev = -1;
-    IBH_HIP(hipGetDevice(&dev));
-    IBH_CHECK(dev == h->device, "Hntr handle belongs to device %d, current device is %d", h->device, dev);
+    check_current_device(h->device, "Hntr handle");
     const int64_t nI = (int64_t)h->imA * h->jmA, nA = (int64_t)h->imB * h->jmB;
     IBH_CHECK(d->elevmaskI != nullptr, "global_ec: null elevmaskI");
     IBH_CHECK(d->nmask == nI, "global_ec: elevmaskI has %lld elements, the ice grid (Hntr grid A) has nI=%lld", (long long)d->nmask,
@@ -1199,24 +1184,16 @@ static void make_i2vx(const ibh_weighted *IvX, const ibh_hntr *h, double eq_rad,
     IBH_CHECK(dimI2 == nullptr || dimI2->sparse_extent() == -1 || dimI2->sparse_extent() == nI2,
               "make_I2vX: dimI2 has sparse extent %lld, the Hntr handle's grid A (hspecI2) %lld cells",
               (long long)(dimI2 ? dimI2->sparse_extent() : 0), (long long)nI2);
-    std::unique_ptr<ibh_sparse_set> tmp(dimI2 ? new ibh_sparse_set(*dimI2) : new ibh_sparse_set);
+    WorkingSet workI2(dimI2);
     ibh_weighted *raw = nullptr;
-    hntr_matrix(h, IBH_HNTR_OVERLAP, eq_rad, includeI, dimI, IBH_TO_DENSE_IGNORE_MISSING, tmp.get(), IBH_ADD_DENSE, 0, &raw);
+    hntr_matrix(h, IBH_HNTR_OVERLAP, eq_rad, includeI, dimI, IBH_TO_DENSE_IGNORE_MISSING, workI2.get(), IBH_ADD_DENSE, 0, &raw);
     std::unique_ptr<ibh_weighted> IvI2(raw);
-    std::unique_ptr<ibh_weighted> w(new ibh_weighted);
-    w->device = h->device;
+    auto w = new_weighted();           // (hm_check: the handle's device)
     i2vx_compute(IvI2.get(), IvX, w.get());
-    std::unique_ptr<ibh_sparse_set> xcopy(IvX->owns[1] ? new ibh_sparse_set(*dimX) : nullptr);
+    w->dims[1] = DimRef::borrow_or_copy(IvX->dims[1]);
     IvI2.reset();
     // nothing below can fail
-    if (dimI2) {
-        *dimI2 = std::move(*tmp);
-        w->dims[0] = dimI2; w->owns[0] = false;
-    } else {
-        w->dims[0] = tmp.release(); w->owns[0] = true;
-    }
-    if (xcopy) { w->dims[1] = xcopy.release(); w->owns[1] = true; }
-    else { w->dims[1] = dimX; w->owns[1] = false; }
+    w->dims[0] = workI2.commit();
     *out = w.release();
 }
 

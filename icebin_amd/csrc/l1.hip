@@ -19,11 +19,10 @@
 //    assembly's setFromTriplets (weighted_from_device_triplets): duplicates summed in stream order with the first term assigned,
 //    wM / Mw in the canonical order.
 #include "assemble.h"
+#include "csrops.h"
 #include "prims.h"
 
 namespace ibh {
-void require_device();      // capi.hip
-
 constexpr int L1_MAXV = 16;              // vertices of a GCM-cell polygon
 constexpr int L1_CLIPV = L1_MAXV + 3;    // vertices of an exchange polygon: a triangle gains at most one per half-plane
 constexpr int L1_LANES = 64;             // lanes of a clip block: one wave, 2 x 2 x L1_CLIPV doubles of LDS per lane
@@ -451,15 +450,6 @@ __global__ void k_l1_check_indices(const int32_t *__restrict__ indices, int nX, 
     const int a = indices[2 * (size_t)x], t = indices[2 * (size_t)x + 1];
     if (a < 0 || a >= nA || t < 0 || t >= ntri) atomicMin(first_bad, (uint32_t)x);
 }
-// M = diag(1 / wM) M  (fA = (1/weightsA) AvI fI, element_l1.py:100-102); rows without entries are left alone
-__global__ void k_l1_scale_rows(const int32_t *__restrict__ rowptr, int nrow, const double *__restrict__ wM, double *__restrict__ val) {
-    const int r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= nrow) return;
-    const int b = rowptr[r], e = rowptr[r + 1];
-    if (b == e) return;
-    const double s = 1. / wM[r];
-    for (int k = b; k < e; ++k) val[k] = val[k] * s;
-}
 
 static void l1_matrix(const ibh_l1_exgrid *ex, const ibh_l1_mesh *m, int64_t nA, const char *which, int scale, ibh_weighted **out,
                       int32_t *trow, int32_t *tcol, double *tval) {
@@ -498,20 +488,16 @@ static void l1_matrix(const ibh_l1_exgrid *ex, const ibh_l1_mesh *m, int64_t nA,
         IBH_HIP(hipStreamSynchronize(st));
         return;
     }
-    std::unique_ptr<ibh_weighted> w(new ibh_weighted);
-    IBH_HIP(hipGetDevice(&w->device));
+    auto w = new_weighted();
     w->conservative = 1;
     w->scaled = scale ? 1 : 0;
     const int nrow = swap ? m->nvert : (int)nA, ncol = swap ? (int)nA : m->nvert;
     weighted_from_device_triplets(w.get(), nrow, ncol, (int64_t)n, row, col, val, st);
-    if (scale && w->nnz) hipLaunchKernelGGL(k_l1_scale_rows, dim3(ceil_div(nrow, 256)), dim3(256), 0, st, w->rowptr.p, nrow, w->wM.p, w->val.p);
+    // M = diag(1 / wM) M  (fA = (1/weightsA) AvI fI, element_l1.py:100-102); rows without entries are left alone
+    if (scale && w->nnz) scale_rows_recip(w->rowptr.p, nrow, w->wM.p, w->val.p, st);
     IBH_HIP(hipGetLastError());
     IBH_HIP(hipStreamSynchronize(st));
-    for (int k = 0; k < 2; ++k) {
-        std::unique_ptr<ibh_sparse_set> s(new ibh_sparse_set);
-        s->make_identity(k ? ncol : nrow);
-        w->dims[k] = s.release(); w->owns[k] = true;
-    }
+    w->dims[0] = DimRef::owned_identity(nrow); w->dims[1] = DimRef::owned_identity(ncol);
     *out = w.release();
 }
 

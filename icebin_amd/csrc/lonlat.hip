@@ -45,8 +45,6 @@ struct ibh_lonlat_cells {
 
 namespace ibh {
 
-void require_device();      // capi.hip
-
 constexpr double LL_D2R = M_PI / 180.0;
 constexpr double LL_HALFPI = M_PI / 2, LL_FORTPI = M_PI / 4;
 

@@ -11,10 +11,6 @@
 #include "prims.h"
 #include <memory>
 
-namespace ibh {
-void require_device();      // capi.hip
-}
-
 struct ibh_multivec {
     int device = 0;
     int32_t nvar = 0;
@@ -541,9 +537,6 @@ int ibh_multivec_densify_device(const ibh_multivec *mv, const ibh_sparse_set *se
 }
 
 // ---- host-array forms (a caller without device arrays of its own: the C++ mirror's to_dense_scale / to_dense / add) ----------
-static void rethrow(int rc) {
-    if (rc != IBH_OK) fail(rc, "%s", ibh_last_error());
-}
 int ibh_multivec_append_weighted_host(ibh_multivec *mv, const ibh_weighted *w, const double *B_b, int32_t nvar, int64_t ldb) {
     return guarded([&] {
         IBH_CHECK(w != nullptr, "null Weighted handle");

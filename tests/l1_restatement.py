@@ -98,7 +98,7 @@ def assemble(row, col, val, nrow, ncol):
 
 
 def scale_rows(rowptr, val, wM):
-    """M = diag(1/wM) M as k_l1_scale_rows does it: one reciprocal per row, one product per entry."""
+    """M = diag(1/wM) M as scale_rows_recip (csrops.hip) does it: one reciprocal per row, one product per entry."""
     out = val.copy()
     for r in range(len(rowptr) - 1):
         if rowptr[r + 1] > rowptr[r]:

@@ -224,6 +224,29 @@ def test_make_I2vX_bitwise(name):
     i2vx_check(gcm, I, I2, em, "IvA" if name == "IvE" else "IvE", dimI2)
 
 
+def test_I2vX_outlives_the_IvX_it_was_made_from():
+    """IvX made with dims of its own owns its X set, so I2vX takes a copy of it and not the pointer: with IvX destroyed,
+    I2vX's columns still read back and the matrix applies; they are the columns of the same build on a caller's X set,
+    which I2vX shares."""
+    import gc
+    from icebin_amd import SparseSet, global_ec
+    A, I, I2 = spec("4x5"), spec("1deg"), spec("2x2.5")
+    em = mask("random", I.size, 11)
+    rm = global_ec.gcm_from_hntr(A, I, em, global_ec.hcdefs(0., 3000., 500.), True, R).regrid_matrices("globalI", em, scale=False,
+                                                                                                      correctA=True)
+    IvX = rm.matrix_d("IvA", (None, None), scale=False, correctA=True)
+    out = global_ec.make_I2vX(IvX, I, I2, em, None, R)
+    out._keep = ()          # the wrapper's own reference to IvX
+    del IvX
+    gc.collect()
+    dimX = SparseSet()
+    out2 = global_ec.make_I2vX(rm.matrix_d("IvA", (SparseSet(), dimX), scale=False, correctA=True), I, I2, em, None, R)
+    assert out.ncol_d == out2.ncol_d > 0
+    assert np.array_equal(out.dim(1), out2.dim(1)) and np.array_equal(out2.dim(1), dimX.to_sparse())
+    x = np.random.default_rng(2).random(out.ncol_d)
+    assert np.array_equal(bits(out.apply(x)), bits(out2.apply(x)))
+
+
 def test_ncio_round_trip(tmp_path):
     from icebin_amd import GCMRegridder, global_ec
     A, I = spec("72x46_east"), spec("144x90_east")

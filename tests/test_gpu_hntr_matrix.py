@@ -230,6 +230,21 @@ def test_matrix_d_transforms_and_sets(transpose):
                     assert dB.sparse_extent() == nB and dA.sparse_extent() == nA
 
 
+@pytest.mark.parametrize("transpose", [False, True])
+def test_failed_matrix_d_leaves_both_sets_alone(transpose):
+    """A key missing from a TO_DENSE set is found after dimA's ADD_DENSE numbering was prepared and before either set adopts
+    anything: both sets keep their entries and their unset (-1) sparse extent."""
+    from icebin_amd import IcebinHipError, SparseSet
+    from icebin_amd.hntr import ADD_DENSE, TO_DENSE
+    h = hntr("8x4", "16x8")
+    dimB, dimA = SparseSet(-1, [3, 17]), SparseSet(-1, [5])
+    with pytest.raises(IcebinHipError, match="missing from a TO_DENSE set") as e:
+        h.matrix_d("overlap", R_EARTH, dims=(dimB, dimA), transforms=(TO_DENSE, ADD_DENSE), transpose=transpose)
+    assert e.value.code == -1       # IBH_EINVAL
+    assert np.array_equal(dimB.to_sparse(), [3, 17]) and np.array_equal(dimA.to_sparse(), [5])
+    assert dimB.sparse_extent() == -1 and dimA.sparse_extent() == -1
+
+
 def test_ignore_missing_b_stops_the_entry():
     """B dropped by TO_DENSE_IGNORE_MISSING: the entry's A index is neither numbered (ADD_DENSE) nor looked up (TO_DENSE)."""
     from icebin_amd import SparseSet

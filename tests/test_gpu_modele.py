@@ -197,6 +197,70 @@ def test_product_primitive(shape):
     assert np.array_equal(wrp, rp) and np.array_equal(wci, ci) and np.array_equal(bits(wv), bits(v))
 
 
+def own_dims_matrix(maker):
+    """One matrix with dims of its own from `maker`, on the smallest input its own tests build -> (matrix, identity sets promised)."""
+    import icebin_amd
+    from icebin_amd import linear_Weighted
+    from icebin_amd._capi import check, lib
+    rng = np.random.default_rng(3)
+    if maker in ("from_csr", "from_coo", "csr_product"):
+        L, Rm = random_rows(rng, 5, 7, [2, 0, 3]), random_rows(rng, 7, 4, [1, 2])
+        if maker == "from_csr":
+            return to_weighted(L, 7), True
+        if maker == "from_coo":
+            row = np.repeat(np.arange(5), [len(r) for r in L])
+            col, val = [c for r in L for c, _ in r], [x for r in L for _, x in r]
+            return linear_Weighted.from_coo((5, 7), row, col, val, np.zeros(5), np.zeros(7)), True
+        wl, wr = to_weighted(L, 7), to_weighted(Rm, 4)
+        h = C.c_void_p()
+        check(lib().ibh_selftest_csr_product(wl._h, wr._h, C.byref(h)))
+        return linear_Weighted(h), True
+    if maker == "e1ve0":
+        from icebin_amd import from_synthetic, synthetic
+        g = synthetic.make_grids("g20")
+        XvE = from_synthetic(g).regrid_matrices("greenland", synthetic.dome_elevmask(g), scale=False,
+                                               correctA=True).matrix_d("XvE", scale=False, correctA=True)
+        return icebin_amd.compute_E1vE0c([XvE], [XvE], g["nA"] * len(g["hcdefs"])), True
+    if maker == "l1":
+        import l1_restatement
+        from icebin_amd import l1
+        c = l1_restatement.load_case("four_tri_a1")
+        ex = l1.exchange_grid_from_polygons(c["ex_iA"], c["ex_iTri"], vptr=c["ex_vptr"], qx=c["ex_qx"], qy=c["ex_qy"])
+        return l1.compute_AvI(ex, int(c["nA"]), l1.Mesh(c["vx"], c["vy"], c["tri"]), scale=True), True
+    if maker == "hntr":
+        from test_gpu_hntr_matrix import hntr
+        return hntr("8x4", "16x8").matrix_d("overlap", R), True
+    if "hntr-Z" not in _cases:
+        _cases["hntr-Z"] = hntr_case("Z_INTERP")
+    case = _cases["hntr-Z"]
+    return case.modele(*case.ocean("om1")).regrid_matrices(case.sheet, case.em).matrix_d("AvI"), False
+
+
+@pytest.mark.parametrize("maker", ["from_csr", "from_coo", "e1ve0", "csr_product", "l1", "hntr", "modele"])
+def test_every_maker_hands_out_readable_own_dims(maker):
+    """A matrix made without caller's sets owns its two: they read back with the dense extents (nrow, ncol), as arange where
+    the maker promises identity sets and as distinct keys inside the sparse extent otherwise, and destroying the handle (which
+    deletes them) and building the same matrix again gives the same sets."""
+    from icebin_amd._capi import check, lib
+    seen = None
+    for _ in range(2):
+        w, identity = own_dims_matrix(maker)
+        dims = []
+        for k, n in enumerate((w.nrow_d, w.ncol_d)):
+            dense = C.c_int32(-1)
+            check(lib().ibh_weighted_dim(w._h, k, None, C.byref(dense)))
+            d = w.dim(k)
+            assert dense.value == n == len(d) and n > 0
+            if identity:
+                assert np.array_equal(d, np.arange(n)) and w.sparse_extent(k) == n
+            else:
+                assert len(np.unique(d)) == n and d.min() >= 0 and d.max() < w.sparse_extent(k)
+            dims.append(d.copy())
+        assert seen is None or all(np.array_equal(a, b) for a, b in zip(seen, dims))
+        seen = dims
+        del w
+
+
 @pytest.mark.parametrize("name", ["AvI", "IvA"])
 def test_apply_M_conserves(case, name):
     """The project's gate: |sum wM y - sum Mw x| / |sum Mw x| < 1e-13 (math.fsum) with force_conservation."""
