@@ -8,4 +8,5 @@ from .linear import SparseSet, compute_E1vE0c, coo_multiply, linear_Weighted, nc
 from .regrid import GCMRegridder, RegridMatrices, from_synthetic  # noqa: F401
 from .hntr import Hntr, HntrSpec  # noqa: F401
 from .multivec import VectorMultivec, concatenate  # noqa: F401
-from .modele import GCMRegridder_ModelE, RegridMatrices_ModelE, make_hntrA  # noqa: F401
+from .modele import (EOpvAOpResult, GCMRegridder_ModelE, RegridMatrices_ModelE, UI_GLOBALICE, UI_LOCALICE,  # noqa: F401
+                     compute_AAmvEAm, compute_EOpvAOp_merged, make_hntrA)

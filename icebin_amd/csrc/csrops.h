@@ -28,6 +28,8 @@ void mul(const double *a, const double *b, int n, double *out, hipStream_t st);
 void gather(const double *in, const int32_t *idx, long n, double *out, hipStream_t st);
 // diag(s) * M in place: val = s[row] * val
 void scale_rows(const int32_t *rowptr, int nrow, const double *s, double *val, hipStream_t st);
+// M * diag(d) in place: val = val * d[col], each product rounded on its own
+void scale_cols(const int32_t *colind, int64_t nnz, const double *d, double *val, hipStream_t st);
 // diag(1 / sum) * M in place: one reciprocal per row, val = val * (1 / sum[row]); rows without entries are skipped (their
 // sum may be 0)
 void scale_rows_recip(const int32_t *rowptr, int nrow, const double *sum, double *val, hipStream_t st);

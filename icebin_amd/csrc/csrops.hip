@@ -174,6 +174,10 @@ __global__ void k_scale_rows(const int32_t *__restrict__ rowptr, int nrow, const
     if (r >= nrow) return;
     for (int e = rowptr[r]; e < rowptr[r + 1]; ++e) val[e] = s[r] * val[e];
 }
+__global__ void k_scale_cols(const int32_t *__restrict__ colind, long nnz, const double *__restrict__ d, double *__restrict__ val) {
+    const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e < nnz) val[e] = val[e] * d[colind[e]];
+}
 __global__ void k_scale_rows_recip(const int32_t *__restrict__ rowptr, int nrow, double *__restrict__ val, const double *__restrict__ sum) {
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= nrow) return;
@@ -200,6 +204,9 @@ void gather(const double *in, const int32_t *idx, long n, double *out, hipStream
 }
 void scale_rows(const int32_t *rowptr, int nrow, const double *s, double *val, hipStream_t st) {
     if (nrow) hipLaunchKernelGGL(k_scale_rows, dim3(ceil_div(nrow, 256)), dim3(256), 0, st, rowptr, nrow, s, val);
+}
+void scale_cols(const int32_t *colind, int64_t nnz, const double *d, double *val, hipStream_t st) {
+    if (nnz) hipLaunchKernelGGL(k_scale_cols, dim3(ceil_div(nnz, 256)), dim3(256), 0, st, colind, (long)nnz, d, val);
 }
 void scale_rows_recip(const int32_t *rowptr, int nrow, const double *sum, double *val, hipStream_t st) {
     if (nrow) hipLaunchKernelGGL(k_scale_rows_recip, dim3(ceil_div(nrow, 256)), dim3(256), 0, st, rowptr, nrow, val, sum);

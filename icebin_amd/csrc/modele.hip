@@ -13,6 +13,7 @@
 #include "assemble.h"
 #include "common.h"
 #include "csrops.h"
+#include "modele_parts.h"
 #include "prims.h"
 
 struct ibh_modele_matrices {
@@ -57,8 +58,15 @@ T *to_arena(const std::vector<T> &h, hipStream_t st) {
 template <class T>
 void upload(DevBuf<T> &b, const std::vector<T> &h, hipStream_t st) { b.alloc(h.size()); b.upload(h.data(), h.size(), st); }
 
-// Hntr's overlap triplets (B cell, A cell, area) of the B cells in includeB, on the host: count, then fetch
-struct HostTriplets { std::vector<int32_t> iB, iA; std::vector<double> v; };
+std::unique_ptr<ibh_weighted> o_matrix(const ibh_modele_matrices *mm, const char *name, ibh_sparse_set *d0, ibh_sparse_set *d1, int correctA) {
+    const double zero[3] = {0, 0, 0};
+    ibh_weighted *w = nullptr;
+    assemble_matrix(mm->rmO, name, d0, d1, 0, correctA, zero, &w);
+    return std::unique_ptr<ibh_weighted>(w);
+}
+}  // namespace
+
+// ---- the topo.cpp helpers (modele_parts.h): ComputeXAmvGp_Helper (:168-280) below and globalave.hip compose them -------------
 HostTriplets hntr_overlap_triplets(const ibh_hntr *h, double eq_rad, const uint8_t *includeB) {
     HostTriplets t;
     int64_t ns = 0;
@@ -68,19 +76,13 @@ HostTriplets hntr_overlap_triplets(const ibh_hntr *h, double eq_rad, const uint8
     return t;
 }
 
-std::unique_ptr<ibh_weighted> o_matrix(const ibh_modele_matrices *mm, const char *name, ibh_sparse_set *d0, ibh_sparse_set *d1, int correctA) {
-    const double zero[3] = {0, 0, 0};
-    ibh_weighted *w = nullptr;
-    assemble_matrix(mm->rmO, name, d0, d1, 0, correctA, zero, &w);
-    return std::unique_ptr<ibh_weighted>(w);
+void scaled_matvec(const ibh_weighted &M, const double *d, const double *w, double *y, hipStream_t st) {
+    if (M.nrow) hipLaunchKernelGGL(k_scaled_matvec, dim3(ceil_div(M.nrow, 256)), dim3(256), 0, st, view(M), d, w, y);
+    IBH_HIP(hipGetLastError());
 }
 
-// ---- ComputeXAmvGp_Helper (:168-280) in its steps, and the two generators (:318-368, :379-433) ---------------------------------
-// compute_wAOm (topo.cpp:84-109) with scaled_AOmvAOp (topo.cpp:50-81): AOpvIp with correctA numbers dimAOp (and dimGp); dimAOm
-// is the cells of dimAOp that ModelE calls land, aop2aom the dense AOp -> dense AOm map (-1: ocean for ModelE)
-void compute_wAOm(const ibh_modele_matrices *mm, const char *nameAvG, ibh_sparse_set &dimGp, ibh_sparse_set &dimAOp,
+void compute_wAOm(const double *foceanAOp, const double *foceanAOm, int64_t nO, const double *d_wAOp, const ibh_sparse_set &dimAOp,
                   ibh_sparse_set &dimAOm, std::vector<int32_t> &aop2aom, DevBuf<double> &wAOm, hipStream_t st) {
-    auto AOpvIp_c = o_matrix(mm, nameAvG, &dimAOp, &dimGp, 1);
     const int nAOp = dimAOp.n();
     const int64_t *ts = dimAOp.to_sparse_host();
     std::vector<int64_t> keys;
@@ -88,10 +90,10 @@ void compute_wAOm(const ibh_modele_matrices *mm, const char *nameAvG, ibh_sparse
     std::vector<int32_t> src;
     aop2aom.assign((size_t)nAOp, -1);
     for (int d = 0; d < nAOp; ++d)          // dimAOm: the cells of dimAOp, in dense order, that ModelE calls land
-        if (mm->foceanAOm[(size_t)ts[d]] == 0) { aop2aom[(size_t)d] = (int32_t)keys.size(); keys.push_back(ts[d]); }
+        if (foceanAOm[(size_t)ts[d]] == 0) { aop2aom[(size_t)d] = (int32_t)keys.size(); keys.push_back(ts[d]); }
     inv_fcont.assign(keys.size(), 0.); src.assign(keys.size(), -1);
     for (int d = 0; d < nAOp; ++d) {        // scaled_AOmvAOp (topo.cpp:50-81)
-        const double fcont_p = 1.0 - mm->foceanAOp[(size_t)ts[d]], fcont_m = 1.0 - mm->foceanAOm[(size_t)ts[d]];
+        const double fcont_p = 1.0 - foceanAOp[(size_t)ts[d]], fcont_m = 1.0 - foceanAOm[(size_t)ts[d]];
         if (fcont_m == 0.0) continue;
         if (fcont_m != 1.0) fail(IBH_EINVAL, "fcont_m[%ld] = %g, must be 0 or 1", (long)ts[d], fcont_m);
         if (fcont_p == 0.0) continue;
@@ -99,29 +101,26 @@ void compute_wAOm(const ibh_modele_matrices *mm, const char *nameAvG, ibh_sparse
         if (k < 0) continue;                // (fcont_m == 1 means foceanAOm == 0: always in dimAOm)
         inv_fcont[(size_t)k] = 1. / fcont_p; src[(size_t)k] = d;
     }
-    dimAOm.assign_host(mm->nO, keys.data(), (int32_t)keys.size());
+    dimAOm.assign_host(nO, keys.data(), (int32_t)keys.size());
     arena().reset();
     const int nAOm = dimAOm.n();
     wAOm.alloc((size_t)nAOm);
     const double *d_inv = to_arena(inv_fcont, st);
     const int32_t *d_src = to_arena(src, st);
-    if (nAOm) hipLaunchKernelGGL(k_wAOm, dim3(ceil_div(nAOm, 256)), dim3(256), 0, st, d_inv, d_src, AOpvIp_c->wM.p, nAOm, wAOm.p);
+    if (nAOm) hipLaunchKernelGGL(k_wAOm, dim3(ceil_div(nAOm, 256)), dim3(256), 0, st, d_inv, d_src, d_wAOp, nAOm, wAOm.p);
     IBH_HIP(hipGetLastError());
-    IBH_HIP(hipStreamSynchronize(st));      // the host vectors and AOpvIp_c go away here
+    IBH_HIP(hipStreamSynchronize(st));      // the host vectors (and the caller's d_wAOp) may go away here
 }
 
-// compute_EOmvAOm_unscaled (topo.cpp:211-240): EOpvAOp visited by columns, rows ascending inside; kept where the column is a
-// cell of dimAOm; dimEOm numbered first-seen.  Then wEOm = EOmvAOm * diag(sum(EOmvAOm, 1, '-')) * wAOm (:226-228), on the device
-// and, for raw_EOvEA's "weight != 0" test, on the host.
-void compute_EOmvAOm_unscaled(const ibh_modele_matrices *mm, const ibh_sparse_set &dimAOm, const DevBuf<double> &wAOm,
-                              ibh_sparse_set &dimEOm, DevBuf<double> &wEOm, std::vector<double> &wEOm_h, hipStream_t st) {
-    ibh_sparse_set dimEOp2, dimAOp2;
-    auto EOpvAOp = o_matrix(mm, "EvA", &dimEOp2, &dimAOp2, 0);
-    const int nE2 = EOpvAOp->nrow, nA2 = EOpvAOp->ncol, nAOm = dimAOm.n();
-    const long nnz2 = (long)EOpvAOp->nnz;
+void compute_EOmvAOm_unscaled(const ibh_weighted &EOpvAOp, const ibh_sparse_set &dimEOp2, const ibh_sparse_set &dimAOp2,
+                              const ibh_sparse_set &dimAOm, const DevBuf<double> &wAOm, int64_t extentEOm, ibh_sparse_set &dimEOm,
+                              ibh_weighted *EOmvAOm_out, DevBuf<double> *EOmvAOms_out, DevBuf<double> &wEOm, std::vector<double> &wEOm_h,
+                              hipStream_t st) {
+    const int nE2 = EOpvAOp.nrow, nA2 = EOpvAOp.ncol, nAOm = dimAOm.n();
+    const long nnz2 = (long)EOpvAOp.nnz;
     std::vector<int32_t> rp((size_t)nE2 + 1), ci((size_t)nnz2);
-    EOpvAOp->rowptr.download(rp.data(), (size_t)nE2 + 1, st);
-    EOpvAOp->colind.download(ci.data(), (size_t)nnz2, st);
+    EOpvAOp.rowptr.download(rp.data(), (size_t)nE2 + 1, st);
+    EOpvAOp.colind.download(ci.data(), (size_t)nnz2, st);
     std::vector<int32_t> colptr((size_t)nA2 + 1, 0), by_col((size_t)nnz2), row_of((size_t)nnz2);
     for (long e = 0; e < nnz2; ++e) ++colptr[(size_t)ci[(size_t)e] + 1];
     for (int c = 0; c < nA2; ++c) colptr[(size_t)c + 1] += colptr[(size_t)c];
@@ -130,7 +129,7 @@ void compute_EOmvAOm_unscaled(const ibh_modele_matrices *mm, const ibh_sparse_se
         for (int r = 0; r < nE2; ++r)
             for (int e = rp[(size_t)r]; e < rp[(size_t)r + 1]; ++e) { by_col[(size_t)fill[(size_t)ci[(size_t)e]]++] = e; row_of[(size_t)e] = r; }
     }
-    dimEOm.set_sparse_extent(mm->nO * mm->nhc);
+    dimEOm.set_sparse_extent(extentEOm);
     std::vector<int32_t> trow, tcol, tsrc;
     const int64_t *tsE2 = dimEOp2.to_sparse_host(), *tsA2 = dimAOp2.to_sparse_host();
     for (int c = 0; c < nA2; ++c) {
@@ -143,35 +142,35 @@ void compute_EOmvAOm_unscaled(const ibh_modele_matrices *mm, const ibh_sparse_se
     }
     const int nEOm = dimEOm.n();
     const long nt = (long)trow.size();
-    ibh_weighted EOmvAOm;
-    DevBuf<double> EOmvAOms;
+    ibh_weighted local;
+    DevBuf<double> local_s;
+    ibh_weighted &EOmvAOm = EOmvAOm_out ? *EOmvAOm_out : local;
+    DevBuf<double> &EOmvAOms = EOmvAOms_out ? *EOmvAOms_out : local_s;
     arena().reset();
     const int32_t *d_row = to_arena(trow, st), *d_col = to_arena(tcol, st), *d_src = to_arena(tsrc, st);
     double *d_val = arena().get<double>((size_t)nt);
-    gather(EOpvAOp->val.p, d_src, nt, d_val, st);
+    gather(EOpvAOp.val.p, d_src, nt, d_val, st);
     weighted_from_device_triplets(&EOmvAOm, nEOm, nAOm, nt, d_row, d_col, d_val, st);
     recip(EOmvAOm.Mw.p, nAOm, EOmvAOms, st);
     wEOm.alloc((size_t)nEOm);
-    if (nEOm) hipLaunchKernelGGL(k_scaled_matvec, dim3(ceil_div(nEOm, 256)), dim3(256), 0, st, view(EOmvAOm), EOmvAOms.p, wAOm.p, wEOm.p);
-    IBH_HIP(hipGetLastError());
+    scaled_matvec(EOmvAOm, EOmvAOms.p, wAOm.p, wEOm.p, st);
     wEOm_h.resize((size_t)nEOm);
     wEOm.download(wEOm_h.data(), (size_t)nEOm, st);     // (synchronises: the host vectors and matrices above are free)
 }
 
-// raw_EOvEA (topo.cpp:112-204), by its columns: Hntr's O -> A overlap clipped by dimAOm (includeO), every entry expanded over
-// the elevation classes; numbers dimEAm
-std::unique_ptr<ibh_weighted> raw_EOvEA(const ibh_modele_matrices *mm, const std::vector<uint8_t> &includeO, const ibh_sparse_set &dimEOm,
-                                        const DevBuf<double> &wEOm, const std::vector<double> &wEOm_h, ibh_sparse_set &dimEAm,
+std::unique_ptr<ibh_weighted> raw_EOvEA(const ibh_hntr *hntr, double eq_rad, const std::vector<uint8_t> &includeO,
+                                        const ibh_sparse_set &dimEOm, const DevBuf<double> &wEOm, const std::vector<double> &wEOm_h,
+                                        int32_t nhc, int64_t sA_O, int64_t sHC_O, int64_t sA_A, int64_t sHC_A, ibh_sparse_set &dimEAm,
                                         hipStream_t st) {
-    const HostTriplets s = hntr_overlap_triplets(mm->hntr, mm->eq_rad, includeO.data());
+    const HostTriplets s = hntr_overlap_triplets(hntr, eq_rad, includeO.data());
     std::vector<int32_t> trow, tcol;
     for (size_t p = 0; p < s.v.size(); ++p) {
         if (std::abs(s.v[p]) < 1e-8) fail(IBH_EINVAL, "Found a stray overlap; what should we do about it?");
-        for (int ihc = 0; ihc < mm->nhc; ++ihc) {
-            const int dEO = dimEOm.to_dense(s.iB[p] * mm->sA_O + ihc * mm->sHC_O);
+        for (int ihc = 0; ihc < nhc; ++ihc) {
+            const int dEO = dimEOm.to_dense(s.iB[p] * sA_O + ihc * sHC_O);
             if (dEO < 0 || wEOm_h[(size_t)dEO] == 0) continue;
             trow.push_back(dEO);
-            tcol.push_back(dimEAm.add_dense_host(s.iA[p] * mm->sA_A + ihc * mm->sHC_A));
+            tcol.push_back(dimEAm.add_dense_host(s.iA[p] * sA_A + ihc * sHC_A));
         }
     }
     const long ne = (long)trow.size();
@@ -185,18 +184,21 @@ std::unique_ptr<ibh_weighted> raw_EOvEA(const ibh_modele_matrices *mm, const std
     return EOmvEAm;
 }
 
+namespace {
 // dimXAm, dimGp: the caller's sets (copies: the caller's own change only when the matrix is built).  XvG: true = XAmvGp.
 void modele_matrix(const ibh_modele_matrices *mm, char gridX, char gridG, bool XvG, int scale, ibh_sparse_set &dimXAm,
                    ibh_sparse_set &dimGp, ibh_weighted *ret) {
     hipStream_t st = hipStreamPerThread;
-    const int T = 256;
     const char nameAvG[4] = {'A', 'v', gridG, 0}, nameXvG[4] = {gridX, 'v', gridG, 0}, nameGvX[4] = {gridG, 'v', gridX, 0};
     const int64_t nO = mm->nO;
 
     ibh_sparse_set dimAOp, dimAOm, dimEOp, dimEOm;
     DevBuf<double> wAOm;
     std::vector<int32_t> aop2aom;
-    compute_wAOm(mm, nameAvG, dimGp, dimAOp, dimAOm, aop2aom, wAOm, st);
+    {   // AOpvIp with correctA numbers dimAOp (and dimGp); its wM is wAOp
+        auto AOpvIp_c = o_matrix(mm, nameAvG, &dimAOp, &dimGp, 1);
+        compute_wAOm(mm->foceanAOp.data(), mm->foceanAOm.data(), nO, AOpvIp_c->wM.p, dimAOp, dimAOm, aop2aom, wAOm, st);
+    }
     const int nAOm = dimAOm.n();
     std::vector<uint8_t> includeO((size_t)nO, 0);           // DimClip(&dimAOm)
     for (int k = 0; k < nAOm; ++k) includeO[(size_t)dimAOm.to_sparse_host()[k]] = 1;
@@ -211,9 +213,14 @@ void modele_matrix(const ibh_modele_matrices *mm, char gridX, char gridG, bool X
         dimXOp = &dimEOp; dimXOm = &dimEOm;
         XOpvIp = o_matrix(mm, nameXvG, &dimEOp, &dimGp, 0);
         std::vector<double> wEOm_h;
-        compute_EOmvAOm_unscaled(mm, dimAOm, wAOm, dimEOm, wEOm, wEOm_h, st);
+        {
+            ibh_sparse_set dimEOp2, dimAOp2;
+            auto EOpvAOp = o_matrix(mm, "EvA", &dimEOp2, &dimAOp2, 0);
+            compute_EOmvAOm_unscaled(*EOpvAOp, dimEOp2, dimAOp2, dimAOm, wAOm, nO * mm->nhc, dimEOm, nullptr, nullptr, wEOm, wEOm_h, st);
+        }
         wXOm = wEOm.p;
-        XOmvXAm = raw_EOvEA(mm, includeO, dimEOm, wEOm, wEOm_h, dimXAm, st);
+        XOmvXAm = raw_EOvEA(mm->hntr, mm->eq_rad, includeO, dimEOm, wEOm, wEOm_h, mm->nhc, mm->sA_O, mm->sHC_O, mm->sA_A, mm->sHC_A,
+                            dimXAm, st);
     } else {
         XOpvIp = o_matrix(mm, nameXvG, &dimAOp, &dimGp, 0);
         IBH_HIP(hipStreamSynchronize(st));
@@ -233,8 +240,7 @@ void modele_matrix(const ibh_modele_matrices *mm, char gridX, char gridG, bool X
     ibh_weighted XAmvXOm;
     transpose_csr(*XOmvXAm, &XAmvXOm, st);
     wXAm.alloc((size_t)nXAm);
-    if (nXAm) hipLaunchKernelGGL(k_scaled_matvec, dim3(ceil_div(nXAm, T)), dim3(T), 0, st, view(XAmvXOm), XAmvXOms.p, wXOm, wXAm.p);
-    IBH_HIP(hipGetLastError());
+    scaled_matvec(XAmvXOm, XAmvXOms.p, wXOm, wXAm.p, st);
 
     // dense XOp <-> dense XOm
     std::vector<int32_t> op2om((size_t)nXOp, -1), om2op((size_t)nXOm, -1);

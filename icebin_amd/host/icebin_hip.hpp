@@ -764,6 +764,9 @@ public:
         return it->second;
     }
     IceRegridder const *ice_regridder(size_t ix) const { return sheets_.at(ix).get(); }
+    /** ice_regridders().index.size() and the strides of indexingHC: iE = iA*stride_A + ihc*stride_HC */
+    size_t nsheets() const { return sheets_.size(); }
+    std::array<long, 2> indexingHC_strides() const { return {{hc_stride_A_, hc_stride_HC_}}; }
 
     /** regrid_matrices(sheet_index, elevmaskI, params = RegridParams()) (GCMRegridder.hpp:290-293;
         RegridMatrices_Dynamic.cpp:334-402).  elevmaskI is copied. */
@@ -1155,14 +1158,117 @@ public:
     }
 };
 
+// ---- modele/merge_topo.hpp, modele/topo.hpp: the library functions behind global_AvE ---------------
+enum { UI_LOCALICE = 1, UI_GLOBALICE = 2 };      // modele/grids.hpp:44-46
+
+/** The base (global) ice EOpvAOp of the global_ecO file, UNSCALED, as COO arrays in sparse indices over `shape` (the order of
+    the arrays is the order the merge reads them in), its elevation classes and the strides of its indexingHC. */
+struct EOpvAOpBase {
+    std::vector<double> hcdefs;
+    std::vector<int64_t> iE, iO;
+    std::vector<double> val;
+    std::array<long, 2> shape = {{0, 0}};
+    std::array<long, 2> indexingHC_strides = {{1, 0}};      // {1, 0}: {1, nO}
+    bool empty() const { return hcdefs.empty() && val.empty(); }
+};
+
+/** EOpvAOpResult (modele/merge_topo.hpp): the merged EOpvAOp over {dimEOp, dimAOp} (unscaled; its Mw is wAOp), the first row
+    key of the base ice, the elevation classes it stacks and indexingHC as strides plus extents. */
+struct EOpvAOpResult {
+    std::unique_ptr<SparseSetT> dimEOp;
+    std::unique_ptr<linear::Weighted_Eigen> EOpvAOp;
+    long offsetE = 0;
+    std::vector<double> hcdefs;
+    std::vector<int16_t> underice_hc;
+    std::array<long, 2> indexingHC_strides = {{1, 0}};
+    std::array<long, 2> indexingHC_extents = {{0, 0}};       // {nO, nhc}
+};
+
+/** compute_EOpvAOp_merged and, with squash_ecs, squash_ECs (modele/merge_topo.cpp:375-527; ibh_modele_merge_EOpvAOp).  gcmO: the
+    ice sheets on the ocean grid; emIs: one elevmask per sheet, in sheet order (:405-411 builds each sheet's EvA from them).
+    dimAOp is appended to and must outlive the result.  The reference's `errors` vector is never filled there and is not
+    mirrored; squash_ECs is reached through the flag. */
+inline EOpvAOpResult compute_EOpvAOp_merged(SparseSetT &dimAOp, EOpvAOpBase const &base, GCMRegridder_Standard const *gcmO,
+                                            std::vector<ArrayView<const double>> const &emIs, bool use_global_ice, bool use_local_ice,
+                                            bool squash_ecs) {
+    if (emIs.size() != gcmO->nsheets())
+        throw Exception(IBH_EINVAL, "compute_EOpvAOp_merged: " + std::to_string(emIs.size()) + " ice masks for " +
+                                        std::to_string(gcmO->nsheets()) + " sheets");
+    const long nO = (long)gcmO->nA();
+    std::vector<std::unique_ptr<RegridMatrices_Dynamic>> rmOs;
+    std::vector<const ibh_regrid_matrices *> hs;
+    for (size_t k = 0; k < emIs.size(); ++k) {
+        rmOs.push_back(gcmO->regrid_matrices((int)k, emIs[k], RegridParams(false, false, {{0., 0., 0.}})));
+        hs.push_back(rmOs.back()->handle());
+    }
+    EOpvAOpResult ret;
+    ret.dimEOp.reset(new SparseSetT);
+    ret.hcdefs.resize(gcmO->nhc() + base.hcdefs.size());
+    ret.underice_hc.resize(ret.hcdefs.size());
+    const std::array<long, 2> sO = gcmO->indexingHC_strides();
+    const long sAb = base.indexingHC_strides[1] ? base.indexingHC_strides[0] : sO[0];
+    const long sHCb = base.indexingHC_strides[1] ? base.indexingHC_strides[1] : sO[1];
+    ibh_weighted *w = nullptr;
+    int64_t offsetE = 0, sA = 0, sHC = 0;
+    int32_t nhc = 0;
+    check(ibh_modele_merge_EOpvAOp(hs.data(), (int)hs.size(), nO, base.shape[0], base.shape[1], (int64_t)base.val.size(), base.iE.data(),
+                                   base.iO.data(), base.val.data(), base.hcdefs.data(), (int32_t)base.hcdefs.size(), sAb, sHCb,
+                                   use_global_ice, use_local_ice, squash_ecs, dimAOp.handle(), ret.dimEOp->handle(), &w, &offsetE, &nhc,
+                                   ret.hcdefs.data(), ret.underice_hc.data(), &sA, &sHC));
+    ret.EOpvAOp.reset(new linear::Weighted_Eigen(w));
+    ret.offsetE = (long)offsetE;
+    ret.hcdefs.resize((size_t)nhc); ret.underice_hc.resize((size_t)nhc);
+    ret.indexingHC_strides = {{(long)sA, (long)sHC}};
+    ret.indexingHC_extents = {{nO, (long)nhc}};
+    return ret;
+}
+
+/** _compute_AAmvEAm_EIGEN (modele/topo.cpp:242-347; ibh_modele_AAmvEAm): AAmvEAm of a given EOpvAOp over {dimEOp, dimAOp} on the
+    atmosphere grid make_hntrA(hntrO).  indexingHCO / indexingHCA: {stride_A, stride_HC}; nhc: the class extent of both.  dims =
+    {dimAAm, dimEAm} may be pre-populated, are appended to and must outlive the result (nullptr: owned by the result). */
+inline std::unique_ptr<linear::Weighted_Eigen> _compute_AAmvEAm_EIGEN(std::array<SparseSetT *, 2> dims, bool scale, double eq_rad,
+                                                                      HntrSpec const &hntrO, std::array<long, 2> indexingHCO,
+                                                                      std::array<long, 2> indexingHCA, int nhc,
+                                                                      ArrayView<const double> const &foceanAOp,
+                                                                      ArrayView<const double> const &foceanAOm,
+                                                                      linear::Weighted_Eigen const &EOpvAOp, SparseSetT const &dimEOp,
+                                                                      SparseSetT const &dimAOp) {
+    if (foceanAOp.size() != foceanAOm.size()) throw Exception(IBH_EINVAL, "foceanAOp and foceanAOm differ in length");
+    ibh_weighted *w = nullptr;
+    check(ibh_modele_AAmvEAm(EOpvAOp.handle(), dimEOp.handle(), dimAOp.handle(), hntrO.im, hntrO.jm, hntrO.offi, hntrO.dlat, eq_rad, nhc,
+                             indexingHCO[0], indexingHCO[1], indexingHCA[0], indexingHCA[1], foceanAOp.data, foceanAOm.data,
+                             foceanAOp.size(), scale, dims[0] ? dims[0]->handle() : nullptr, dims[1] ? dims[1]->handle() : nullptr, &w));
+    return std::unique_ptr<linear::Weighted_Eigen>(new linear::Weighted_Eigen(w));
+}
+/** _compute_AAmvEAm (topo.cpp:349-374): the same with sets of its own; M_coo / dim_to_sparse / wM / Mw of the result give the
+    reference's to_tuple form.  nhc and the indexings are what make_topoa.cpp:131-135 passes: every merged class, in the order
+    of the merged indexingHC on both grids. */
+inline std::unique_ptr<linear::Weighted_Eigen> _compute_AAmvEAm(bool scale, double eq_rad, HntrSpec const &hntrO,
+                                                                ArrayView<const double> const &foceanAOp,
+                                                                ArrayView<const double> const &foceanAOm, EOpvAOpResult const &eo,
+                                                                SparseSetT const &dimAOp) {
+    const int nhc = (int)eo.hcdefs.size();
+    const long nA = (long)hntrO.size() / 4;
+    const bool hc_slowest = eo.indexingHC_strides[1] >= eo.indexingHC_strides[0];
+    const std::array<long, 2> sA = hc_slowest ? std::array<long, 2>{{1, nA}} : std::array<long, 2>{{(long)nhc, 1}};
+    return _compute_AAmvEAm_EIGEN({{nullptr, nullptr}}, scale, eq_rad, hntrO, eo.indexingHC_strides, sA, nhc, foceanAOp, foceanAOm, *eo.EOpvAOp,
+                                  *eo.dimEOp, dimAOp);
+}
+
 /** GCMRegridder_ModelE (GCMRegridder_ModelE.hpp:102-200): gcmO regrids between (AOp, EOp, Ip) on ModelE's ocean grid; this
     class hands out the matrices between (AAm, EAm, Ip).  The reference reads the ocean HntrSpec and the earth's radius from
-    gcmO's grid spec; here the caller names them (global_ecO, the base-ice file, must be empty: out of scope). */
+    gcmO's grid spec; here the caller names them.  The base ice of the global_ecO file comes in memory (EOpvAOpBase); the file
+    name must be empty (the zlib / NetCDF-4 containers are out of scope). */
 class GCMRegridder_ModelE {
     HntrSpec hspecO_;
     double eq_rad_;
+    EOpvAOpBase base_;
 public:
     std::shared_ptr<GCMRegridder_Standard> const gcmO;
+
+    /** The form with the base ice in memory (the global_ecO file's EOpvAOp_base and hcdefs, :458-480): what global_AvE merges in. */
+    GCMRegridder_ModelE(EOpvAOpBase base, std::shared_ptr<GCMRegridder_Standard> const &_gcmO, HntrSpec const &hspecO, double eq_rad)
+        : GCMRegridder_ModelE("", _gcmO, hspecO, eq_rad) { base_ = std::move(base); }
 
     GCMRegridder_ModelE(std::string const &_global_ecO, std::shared_ptr<GCMRegridder_Standard> const &_gcmO, HntrSpec const &hspecO,
                         double eq_rad)
@@ -1179,6 +1285,27 @@ public:
     HntrSpec const &hspecO() const { return hspecO_; }
     HntrSpec hspecA() const { return make_hntrA(hspecO_); }
     double eq_rad() const { return eq_rad_; }
+    /** hcdefs() (GCMRegridder_ModelE.cpp:468-471): the local classes, then the base ice's; underice(ihc) (.hpp:157) */
+    std::vector<double> hcdefs() const {
+        std::vector<double> h(gcmO->hcdefs());
+        h.insert(h.end(), base_.hcdefs.begin(), base_.hcdefs.end());
+        return h;
+    }
+    int underice(int ihc) const { return ihc < (int)gcmO->nhc() ? UI_LOCALICE : UI_GLOBALICE; }
+
+    /** global_AvE (GCMRegridder_ModelE.cpp:579-628), composed the way the offline tools compose the library functions
+        (make_merged_topoo.cpp:232-238, make_topoa.cpp:131-135,191-196): the merge with the BASE hcdefs, then
+        _compute_AAmvEAm over every merged class.  emI_lands is accepted and, as in the reference, not used. */
+    std::unique_ptr<linear::Weighted_Eigen> global_AvE(std::vector<ArrayView<const double>> const &emI_lands,
+                                                       std::vector<ArrayView<const double>> const &emI_ices,
+                                                       ArrayView<const double> const &foceanAOp, ArrayView<const double> const &foceanAOm,
+                                                       bool scale, long &offsetE) const {
+        (void)emI_lands;
+        SparseSetT dimAOp;
+        EOpvAOpResult eo = compute_EOpvAOp_merged(dimAOp, base_, gcmO.get(), emI_ices, !base_.empty(), true, false);
+        offsetE = eo.offsetE;
+        return _compute_AAmvEAm(scale, eq_rad_, hspecO_, foceanAOp, foceanAOm, eo, dimAOp);
+    }
 
     /** make_agridA (GCMRegridder_ModelE.cpp:57-78): the realised atmosphere cells, first-seen in Hntr's stream order. */
     std::vector<long> agridA_dim(int sheet_index) const {

@@ -223,12 +223,13 @@ class GCMRegridder:
         check(lib().ibh_regridder_wA(self._sheets[sheet_name].h, int(native), float(fill), ptr(out)))
         return out
 
-    def to_modele(self, focean=None, hspecO=None, eq_rad=None):
+    def to_modele(self, focean=None, hspecO=None, eq_rad=None, global_ec=None):
         """Returns a new GCMRegridder object, suitable for use with ModelE (_icebin.pyx:128-147).  focean:
         (foceanAOp, foceanAOm), None = no ocean.  This regridder is on ModelE's ocean grid; its HntrSpec and the earth's
-        radius come from the regridder (HntrGCMRegridder) or from the keywords."""
+        radius come from the regridder (HntrGCMRegridder) or from the keywords.  global_ec = (hcdefs_base, (iE, iO, val), shape):
+        the base ice EOpvAOp that global_AvE merges in."""
         from .modele import to_modele
-        return to_modele(self, focean, hspecO, eq_rad)
+        return to_modele(self, focean, hspecO, eq_rad, global_ec)
 
     def regrid_matrices(self, sheet_name, elevmaskI, scale=True, correctA=True, sigma=(0, 0, 0), conserve=True):
         """_icebin.pyx:164-175.  `conserve` is accepted and, as in the reference's C++ shim

@@ -454,6 +454,52 @@ int ibh_modele_matrices_destroy(ibh_modele_matrices *mm);
  * *nA_dense is always set; to_sparse (may be NULL) receives that many indices (at most (imO/2)*(jmO/2)). */
 int ibh_modele_agridA(const ibh_regridder *rgO, int32_t imO, int32_t jmO, double offiO, double dlatO, int32_t *nA_dense,
                       int64_t *to_sparse);
+/* GCMRegridder_ModelE::global_AvE (modele/GCMRegridder_ModelE.cpp:579-628) in its library functions, composed the way the
+ * offline tools compose them (make_merged_topoo.cpp:232-238, make_topoa.cpp:131-135,186-196); DESIGN.md 16.
+ *
+ * ibh_modele_merge_EOpvAOp: compute_EOpvAOp_merged and, with squash_ecs, squash_ECs (modele/merge_topo.cpp:375-527).  rmOs:
+ * one regrid_matrices per ice sheet, in sheet order, all on the ocean grid of nO cells with the same nhc and indexingHC
+ * (their mask is that sheet's emI_ice; their scale / correctA are ignored: EvA is built with scale = false, correctA =
+ * false, sigma = 0 and fresh sets, :401-411).  One triplet stream in SPARSE indices: with use_local_ice every sheet's EvA
+ * visited by columns, rows ascending inside (:417-423); with use_global_ice the base matrix (base_iE + offsetE, base_iO,
+ * base_val) in the order of the arrays ([INFERRED]: the reference reads a ZArray generator, :441-446), offsetE = nO *
+ * nhc_local (:434; nhc_local = the sheets' nhc, 0 without sheets), else 0.  The stream numbers {dimEOp, dimAOp} first-seen
+ * ({ADD_DENSE, ADD_DENSE}) and is summed as setFromTriplets sums it (duplicates in stream order, the first assigned).  The
+ * result's wM / Mw are sum(M, dim, '+'): Mw is the wAOp that ibh_modele_AAmvEAm reads.  conservative = scaled = 0.
+ *   base_*            the base (global) ice EOpvAOp, UNSCALED, as host COO arrays in sparse indices over the shape (base_nE,
+ *                     base_nO), with the nhc_base elevations hcdefs_base and the strides of indexingHC_base; read only with
+ *                     use_global_ice, except the strides, which always give the order of the result's indexingHC
+ *   dimAOp            IN/OUT (NULL: owned by the result), appended to; dimEOp: OUT, a fresh set (NULL: owned by the result)
+ *   sparse extents    dimEOp offsetE + base_nE, dimAOp base_nO (:454-455); without global ice nO * nhc_local and nO (the
+ *                     reference leaves 0 there); after squash_ecs dimEOp has extent(dimAOp) * nhc_out (:520-521)
+ *   hcdefs_out, underice_out   [nhc_local + nhc_base] at most; *nhc_out entries are written: the local classes (UI_LOCALICE =
+ *                     1) then the base ones (UI_GLOBALICE = 2) (:426-449); after squash_ecs the sorted distinct elevations,
+ *                     all UI_GLOBALICE (:481-490), and a row key (iO, ihc0) of the merge has become (iO, to_new[ihc0]),
+ *                     computed in 64 bits (the reference uses int)
+ *   stride_*_out      indexingHC_base with its class extent replaced by *nhc_out (:364-372): (1, stride_HC) class-slowest, else
+ *                     (*nhc_out, 1)
+ * IBH_EINVAL, naming the offender: a sheet whose grid disagrees with nO or whose nhc / strides differ from sheet 0's, base_nO
+ * != nO, a base index outside its shape, a dimEOp that is not empty, sets whose extents disagree.  On any error *EOpvAOp is
+ * NULL and both sets are as they were. */
+int ibh_modele_merge_EOpvAOp(const ibh_regrid_matrices *const *rmOs, int nsheets, int64_t nO, int64_t base_nE, int64_t base_nO,
+                             int64_t base_nnz, const int64_t *base_iE, const int64_t *base_iO, const double *base_val,
+                             const double *hcdefs_base, int32_t nhc_base, int64_t base_stride_A, int64_t base_stride_HC, int use_global_ice,
+                             int use_local_ice, int squash_ecs, ibh_sparse_set *dimAOp, ibh_sparse_set *dimEOp, ibh_weighted **EOpvAOp,
+                             int64_t *offsetE, int32_t *nhc_out, double *hcdefs_out, int16_t *underice_out, int64_t *stride_A_out,
+                             int64_t *stride_HC_out);
+/* _compute_AAmvEAm_EIGEN (modele/topo.cpp:242-347): the atmosphere-grid matrix AAmvEAm of a GIVEN EOpvAOp (unscaled, dense over
+ * {dimEOp, dimAOp}, its Mw = wAOp = sum(EOpvAOp, 1, '+')) on the ocean grid O = HntrSpec(imO, jmO, offiO, dlatO) under A =
+ * make_hntrA(O).  nhc and the strides of indexingHCO (sA_O, sHC_O) and indexingHCA (sA_A, sHC_A) are explicit: raw_EOvEA
+ * (topo.cpp:147-161) looks for the classes [0, nhc) only.  With the canonical order of DESIGN.md 16:
+ *   M = diag(scale ? sAAmvAOm : wAAm .* sAAmvAOm) * AAmvAOm * diag(EOmvAOms) * AOmvEOm * diag(EAmvEOms) * EOmvEAm
+ *   wM = wAAm, Mw = wEAm, conservative = 0, scaled = scale
+ * dimAAm / dimEAm: IN/OUT (NULL: owned by the result), sparse extents nA_A and nA_A * nhc (-1 is taken as that).  IBH_EINVAL:
+ * odd imO or jmO, imO * jmO != nO, a cell of dimAOp outside [0, nO) or with foceanAOm neither 0 nor 1 (topo.cpp:70-71, names the
+ * cell), an Hntr overlap below 1e-8 (topo.cpp:138-139).  On any error *out is NULL and both sets are as they were. */
+int ibh_modele_AAmvEAm(const ibh_weighted *EOpvAOp, const ibh_sparse_set *dimEOp, const ibh_sparse_set *dimAOp, int32_t imO, int32_t jmO,
+                       double offiO, double dlatO, double eq_rad, int32_t nhc, int64_t sA_O, int64_t sHC_O, int64_t sA_A, int64_t sHC_A,
+                       const double *foceanAOp, const double *foceanAOm, int64_t nO, int scale, ibh_sparse_set *dimAAm,
+                       ibh_sparse_set *dimEAm, ibh_weighted **out);
 /* Diagnostic: the sparse product the ModelE matrices are composed with, alone.  C = L * R for two matrices in HBM (columns
  * ascending inside a row, L's columns = R's rows): C(r, c) sums L(r, k) * R(k, c) over k ascending, the first term assigned;
  * an entry exists wherever a term does.  Identity dims, wM = Mw = 0, flags of L.  Used by tests/test_gpu_modele.py. */
