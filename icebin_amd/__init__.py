@@ -9,4 +9,4 @@ from .regrid import GCMRegridder, RegridMatrices, from_synthetic  # noqa: F401
 from .hntr import Hntr, HntrSpec  # noqa: F401
 from .multivec import VectorMultivec, concatenate  # noqa: F401
 from .modele import (EOpvAOpResult, GCMRegridder_ModelE, RegridMatrices_ModelE, UI_GLOBALICE, UI_LOCALICE,  # noqa: F401
-                     compute_AAmvEAm, compute_EOpvAOp_merged, make_hntrA)
+                     compute_AAmvEAm, compute_EOpvAOp_merged, make_hntrA, make_topoA, merge_topoO)

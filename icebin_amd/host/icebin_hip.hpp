@@ -1159,7 +1159,7 @@ public:
 };
 
 // ---- modele/merge_topo.hpp, modele/topo.hpp: the library functions behind global_AvE ---------------
-enum { UI_LOCALICE = 1, UI_GLOBALICE = 2 };      // modele/grids.hpp:44-46
+enum { UI_UNUSED = 0, UI_LOCALICE = 1, UI_GLOBALICE = 2, UI_VGHOST = 3, UI_HGHOST = 4, UI_SEALAND = 5 };     // modele/grids.hpp:44-49
 
 /** The base (global) ice EOpvAOp of the global_ecO file, UNSCALED, as COO arrays in sparse indices over `shape` (the order of
     the arrays is the order the merge reads them in), its elevation classes and the strides of its indexingHC. */
@@ -1255,6 +1255,108 @@ inline std::unique_ptr<linear::Weighted_Eigen> _compute_AAmvEAm(bool scale, doub
                                   *eo.dimEOp, dimAOp);
 }
 
+
+// ---- modele/merge_topo.hpp, modele/topo.hpp: update_topo's field handling ------------------------------------
+namespace topo_detail {
+inline std::string cell(long c, int im) { return "(" + std::to_string(c % im + 1) + ", " + std::to_string(c / im + 1) + "): "; }
+inline std::string g(double v) { char b[64]; snprintf(b, sizeof b, "%g", v); return b; }
+/** sanity_check_land_fractions' strings (modele/topo.cpp:873-888) of the cells whose flag has `bit` set, j then i */
+inline void land_fraction_errors(std::vector<uint32_t> const &flags, uint32_t bit, const double *focean, const double *flake,
+                                 const double *fgrnd, const double *fgice, int im, std::vector<std::string> &errors) {
+    for (size_t c = 0; c < flags.size(); ++c) {
+        if (!(flags[c] & bit)) continue;
+        const double all_frac = focean[c] + fgrnd[c] + flake[c] + fgice[c];
+        errors.push_back(cell((long)c, im) + "FOCEAN(" + g(focean[c]) + ") + FGRND(" + g(fgrnd[c]) + ") + FLAKE(" + g(flake[c]) + ") + FGICE(" +
+                         g(fgice[c]) + ")  = " + g(all_frac));
+    }
+}
+}   // namespace topo_detail
+
+/** merge_topoO (modele/merge_topo.cpp:84-360; ibh_modele_merge_topoO) with the reference's argument order; the planes are plain
+    row-major arrays [jmO * imO] (iO = j * imO + i) where the reference has blitz arrays.  The nine leading planes are merged
+    into in place; zland_minO2, zland_maxO2 and mergemaskOm2 are written.  hspecO names the ocean grid (the reference reads it from
+    gcmO's grid spec).  paramsA is accepted and, as in the reference, only its sigma (which must be zero) matters: the builds
+    use (scale, correctA) = (true, false) and (false, true).  eq_rad is accepted and unused.  errors receives the sanity
+    checks' strings, check by check, then j, then i. */
+inline void merge_topoO(double *foceanOp2, double *fgiceOp2, double *zatmoOp2, double *foceanOm2, double *flakeOm2, double *fgrndOm2,
+                        double *fgiceOm2, double *zatmoOm2, double *zicetopO2, double *zland_minO2, double *zland_maxO2, int16_t *mergemaskOm2,
+                        GCMRegridder_Standard const *gcmO, HntrSpec const &hspecO, RegridParams const &paramsA,
+                        std::vector<ArrayView<const double>> const &emI_lands, std::vector<ArrayView<const double>> const &emI_ices,
+                        double const eq_rad, std::vector<std::string> &errors) {
+    if (emI_lands.size() != gcmO->nsheets() || emI_ices.size() != gcmO->nsheets())
+        throw Exception(IBH_EINVAL, "merge_topoO: " + std::to_string(emI_lands.size()) + " land masks and " + std::to_string(emI_ices.size()) +
+                                        " ice masks for " + std::to_string(gcmO->nsheets()) + " sheets");
+    std::vector<std::unique_ptr<RegridMatrices_Dynamic>> keep;
+    std::vector<const ibh_regrid_matrices *> lands, ices;
+    const RegridParams params(false, true, paramsA.sigma);
+    for (size_t k = 0; k < emI_ices.size(); ++k) {
+        keep.push_back(gcmO->regrid_matrices((int)k, emI_lands[k], params));
+        lands.push_back(keep.back()->handle());
+        keep.push_back(gcmO->regrid_matrices((int)k, emI_ices[k], params));
+        ices.push_back(keep.back()->handle());
+    }
+    double *planes[11] = {foceanOp2, fgiceOp2, zatmoOp2, foceanOm2, flakeOm2, fgrndOm2, fgiceOm2, zatmoOm2, zicetopO2, zland_minO2, zland_maxO2};
+    static const char *const labels[9] = {"foceanOp2", "fgiceOp2", "zatmoOp2", "foceanOm2", "flakeOm2", "fgrndOm2", "fgiceOm2", "zatmoOm2",
+                                          "zicetopO2"};
+    std::vector<uint32_t> flags((size_t)hspecO.size());
+    int64_t nerr = 0;
+    check(ibh_modele_merge_topoO(lands.data(), (int32_t)lands.size(), ices.data(), (int32_t)ices.size(), hspecO.im, hspecO.jm, eq_rad, planes,
+                                 mergemaskOm2, flags.data(), &nerr));
+    if (!nerr) return;
+    for (int bit = 0; bit < 18; ++bit)
+        for (size_t c = 0; c < flags.size(); ++c)
+            if (flags[c] >> bit & 1u)
+                errors.push_back(topo_detail::cell((long)c, hspecO.im) + labels[bit % 9] + (bit < 9 ? "-0" : "") + " is NaN");
+    topo_detail::land_fraction_errors(flags, 1u << 18, foceanOm2, flakeOm2, fgrndOm2, fgiceOm2, hspecO.im, errors);
+}
+
+/** make_topoA (modele/topo.cpp:581-855; ibh_modele_make_topoA) with the reference's argument order; planes are plain row-major
+    arrays ([jm * im]; fhc3, elevE3, underice3: [(nhc + 1) * jmA * imA]); indexingHCA: {stride_A, stride_HC}; AAmvEAm is read in
+    SPARSE indices through its two sets.  Returns the strings of sanity_check_land_fractions, then sanity_check_fhc. */
+inline std::vector<std::string> make_topoA(const double *foceanOm2, const double *flakeOm2, const double *fgrndOm2, const double *fgiceOm2,
+                                           const double *zatmoOm2, const double *zlakeOm2, const double *zicetopOm2, const double *zland_minOm2,
+                                           const double *zland_maxOm2, const int16_t *mergemaskOm2, HntrSpec const &hspecO,
+                                           HntrSpec const &hspecA, std::array<long, 2> indexingHCA, std::vector<double> const &hcdefs,
+                                           std::vector<int16_t> const &underice_hc, linear::Weighted_Eigen const &AAmvEAm, double *foceanA2,
+                                           double *flakeA2, double *fgrndA2, double *fgiceA2, double *zatmoA2, double *zlakeA2, double *zicetopA2,
+                                           double *zland_minA2, double *zland_maxA2, int16_t *mergemaskA2, double *fhc3, double *elevE3,
+                                           int16_t *underice3) {
+    if (hcdefs.size() != underice_hc.size()) throw Exception(IBH_EINVAL, "make_topoA: hcdefs and underice_hc differ in length");
+    const double *O[9] = {foceanOm2, flakeOm2, fgrndOm2, fgiceOm2, zatmoOm2, zlakeOm2, zicetopOm2, zland_minOm2, zland_maxOm2};
+    double *A[9] = {foceanA2, flakeA2, fgrndA2, fgiceA2, zatmoA2, zlakeA2, zicetopA2, zland_minA2, zland_maxA2};
+    const size_t nA = (size_t)hspecA.size(), nhc = hcdefs.size();
+    std::vector<uint32_t> flags(nA);
+    int64_t nerr = 0;
+    check(ibh_modele_make_topoA(O, mergemaskOm2, hspecO.im, hspecO.jm, hspecO.offi, hspecO.dlat, hspecA.im, hspecA.jm, hspecA.offi, hspecA.dlat,
+                                indexingHCA[0], indexingHCA[1], hcdefs.data(), underice_hc.data(), (int32_t)nhc, AAmvEAm.handle(), A, mergemaskA2,
+                                fhc3, elevE3, underice3, flags.data(), &nerr));
+    std::vector<std::string> errors;
+    if (!nerr) return errors;
+    topo_detail::land_fraction_errors(flags, 1u, foceanA2, flakeA2, fgrndA2, fgiceA2, hspecA.im, errors);
+    for (size_t c = 0; c < nA; ++c) {
+        if (!(flags[c] & 2u)) continue;
+        double all_fhc = 0;
+        for (size_t ihc = 0; ihc <= nhc; ++ihc) all_fhc += fhc3[ihc * nA + c];
+        all_fhc += 1.0;
+        errors.push_back(topo_detail::cell((long)c, hspecA.im) + "sum(FHC) = " + topo_detail::g(all_fhc - 1.0));
+    }
+    return errors;
+}
+
+/** What update_topo hands back: the TOPOA planes [jmA * imA] under TopoABundles' names, the elevation-class arrays
+    [(nhc + 1) * jmA * imA], wEAm_base (the entries of AAmvEAm's Mw whose sparse index is >= offsetE) and offsetE. */
+struct TopoA {
+    std::vector<double> focean, flake, fgrnd, fgice, zatmo, hlake, zicetop, zland_min, zland_max, fhc, elevE;
+    std::vector<int16_t> mergemask, underice;
+    std::vector<std::pair<long, double>> wEAm_base;
+    long offsetE = 0;
+};
+/** The TOPOO planes update_topo merges into, under topoo_bundle's names (modele/topo.cpp:384-474), each [jmO * imO]. */
+struct TopoO {
+    std::vector<double> FOCEANF, FGICEF, ZATMOF, FOCEAN, FLAKE, FGRND, FGICE, ZATMO, ZLAKE, ZICETOP, ZLAND_MIN, ZLAND_MAX;
+    std::vector<int16_t> mergemask;
+};
+
 /** GCMRegridder_ModelE (GCMRegridder_ModelE.hpp:102-200): gcmO regrids between (AOp, EOp, Ip) on ModelE's ocean grid; this
     class hands out the matrices between (AAm, EAm, Ip).  The reference reads the ocean HntrSpec and the earth's radius from
     gcmO's grid spec; here the caller names them.  The base ice of the global_ecO file comes in memory (EOpvAOpBase); the file
@@ -1305,6 +1407,55 @@ public:
         EOpvAOpResult eo = compute_EOpvAOp_merged(dimAOp, base_, gcmO.get(), emI_ices, !base_.empty(), true, false);
         offsetE = eo.offsetE;
         return _compute_AAmvEAm(scale, eq_rad_, hspecO_, foceanAOp, foceanAOm, eo, dimAOp);
+    }
+
+
+    /** GCMCoupler_ModelE::update_topo's body (modele/GCMCoupler_ModelE.cpp:1026-1082): merge_topoO with RegridParams(false, true,
+        0), global_AvE(scale = true), wEAm_base, make_topoA.  topoo holds the merged planes afterwards.  Throws with the
+        sanity-check strings when a check fails.  Reading the TOPOO file, packing into VectorMultivecs (:1099-1170) and
+        mergemaskA0 stay with the caller. */
+    TopoA update_topo(TopoO &topoo, std::vector<ArrayView<const double>> const &emI_lands,
+                      std::vector<ArrayView<const double>> const &emI_ices) const {
+        const size_t nO = (size_t)hspecO_.size();
+        for (std::vector<double> *p : {&topoo.FOCEANF, &topoo.FGICEF, &topoo.ZATMOF, &topoo.FOCEAN, &topoo.FLAKE, &topoo.FGRND, &topoo.FGICE,
+                                       &topoo.ZATMO, &topoo.ZLAKE, &topoo.ZICETOP})
+            if (p->size() != nO) throw Exception(IBH_EINVAL, "update_topo: a TOPOO plane has " + std::to_string(p->size()) + " cells, the ocean grid " +
+                                                                 std::to_string(nO));
+        topoo.ZLAND_MIN.resize(nO); topoo.ZLAND_MAX.resize(nO); topoo.mergemask.resize(nO);
+        auto halt = [](std::vector<std::string> const &errors) {
+            if (errors.empty()) return;
+            std::string msg = "Errors in TOPO merging or regridding; halting!";
+            for (std::string const &e : errors) msg += "\nERROR: " + e;
+            throw Exception(IBH_EINVAL, msg);
+        };
+        std::vector<std::string> errors;
+        merge_topoO(topoo.FOCEANF.data(), topoo.FGICEF.data(), topoo.ZATMOF.data(), topoo.FOCEAN.data(), topoo.FLAKE.data(), topoo.FGRND.data(),
+                    topoo.FGICE.data(), topoo.ZATMO.data(), topoo.ZICETOP.data(), topoo.ZLAND_MIN.data(), topoo.ZLAND_MAX.data(),
+                    topoo.mergemask.data(), gcmO.get(), hspecO_, RegridParams(false, true, {{0., 0., 0.}}), emI_lands, emI_ices, eq_rad_, errors);
+        halt(errors);
+        TopoA a;
+        auto AAmvEAm = global_AvE(emI_lands, emI_ices, ArrayView<const double>(topoo.FOCEANF), ArrayView<const double>(topoo.FOCEAN), true,
+                                  a.offsetE);
+        std::vector<long> iE = AAmvEAm->dim_to_sparse(1);
+        std::vector<double> const &Mw = AAmvEAm->Mw();
+        for (size_t d = 0; d < iE.size(); ++d)
+            if (iE[d] >= a.offsetE) a.wEAm_base.push_back(std::make_pair(iE[d], Mw[d]));
+        const std::vector<double> hc = hcdefs();
+        std::vector<int16_t> ui;
+        for (int ihc = 0; ihc < (int)hc.size(); ++ihc) ui.push_back((int16_t)underice(ihc));
+        const HntrSpec A = hspecA();
+        const size_t nA = (size_t)A.size(), n3 = nA * (hc.size() + 1);
+        const std::array<long, 2> sO = gcmO->indexingHC_strides();
+        const std::array<long, 2> sA = sO[1] >= sO[0] ? std::array<long, 2>{{1, (long)nA}} : std::array<long, 2>{{(long)hc.size(), 1}};
+        for (std::vector<double> *p : {&a.focean, &a.flake, &a.fgrnd, &a.fgice, &a.zatmo, &a.hlake, &a.zicetop, &a.zland_min, &a.zland_max})
+            p->resize(nA);
+        a.mergemask.resize(nA); a.fhc.resize(n3); a.elevE.resize(n3); a.underice.resize(n3);
+        halt(make_topoA(topoo.FOCEAN.data(), topoo.FLAKE.data(), topoo.FGRND.data(), topoo.FGICE.data(), topoo.ZATMO.data(), topoo.ZLAKE.data(),
+                        topoo.ZICETOP.data(), topoo.ZLAND_MIN.data(), topoo.ZLAND_MAX.data(), topoo.mergemask.data(), hspecO_, A, sA, hc, ui,
+                        *AAmvEAm, a.focean.data(), a.flake.data(), a.fgrnd.data(), a.fgice.data(), a.zatmo.data(), a.hlake.data(),
+                        a.zicetop.data(), a.zland_min.data(), a.zland_max.data(), a.mergemask.data(), a.fhc.data(), a.elevE.data(),
+                        a.underice.data()));
+        return a;
     }
 
     /** make_agridA (GCMRegridder_ModelE.cpp:57-78): the realised atmosphere cells, first-seen in Hntr's stream order. */

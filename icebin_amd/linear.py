@@ -265,6 +265,19 @@ class linear_Weighted:
                                                   C.c_void_p(s)))
         return outs
 
+    def row_stats_device(self, dx, want_sum=True, want_min=True, want_max=True, stream=None):
+        """(sum, min, max) per dense row over the STORED entries, in one pass over the CSR (ibh_weighted_row_stats_device):
+        sum[r] = sum of val * x[col], min / max of x[col] starting from DBL_MAX / DBL_MIN (the smallest positive normal number,
+        as merge_topoO's zland_max does).  dx: a contiguous torch.float64 CUDA tensor [ncol_d], which may hold NaN in columns
+        no entry names.  An output not wanted is None.  Only enqueues work on `stream` (default: torch's current stream)."""
+        import torch
+        assert dx.is_cuda and dx.dtype == torch.float64 and dx.is_contiguous() and dx.numel() == self.ncol_d
+        outs = [torch.empty(self.nrow_d, dtype=torch.float64, device=dx.device) if want else None for want in (want_sum, want_min, want_max)]
+        s = torch.cuda.current_stream(dx.device).cuda_stream if stream is None else stream
+        check(lib().ibh_weighted_row_stats_device(self._h, C.c_void_p(dx.data_ptr()), *[C.c_void_p(o.data_ptr()) if o is not None else None
+                                                                                     for o in outs], C.c_void_p(s)))
+        return tuple(outs)
+
     def reserve(self, nvar):
         """Size the handle's per-apply scratch for up to nvar variables (needed before capturing
         applies into a hipGraph: growing scratch allocates)."""

@@ -10,7 +10,14 @@ from ._capi import check, lib, ptr
 from .hntr import HntrSpec
 from .linear import SparseSet, linear_Weighted
 
-UI_LOCALICE, UI_GLOBALICE = 1, 2            # modele/grids.hpp:44-46
+UI_UNUSED, UI_LOCALICE, UI_GLOBALICE, UI_VGHOST, UI_HGHOST, UI_SEALAND = 0, 1, 2, 3, 4, 5      # modele/grids.hpp:44-49
+
+# topoo_bundle's names (modele/topo.cpp:384-474) in the order of merge_topoO's planes (merge_topo.cpp:89-101), the labels its
+# sanity checks print (:159-167), make_topoA's ocean planes (topo.cpp:584-592) and TopoABundles' names (:482-483)
+TOPOO_MERGE = ("FOCEANF", "FGICEF", "ZATMOF", "FOCEAN", "FLAKE", "FGRND", "FGICE", "ZATMO", "ZICETOP", "ZLAND_MIN", "ZLAND_MAX")
+MERGE_LABELS = ("foceanOp2", "fgiceOp2", "zatmoOp2", "foceanOm2", "flakeOm2", "fgrndOm2", "fgiceOm2", "zatmoOm2", "zicetopO2")
+TOPOO_MAKEA = ("FOCEAN", "FLAKE", "FGRND", "FGICE", "ZATMO", "ZLAKE", "ZICETOP", "ZLAND_MIN", "ZLAND_MAX")
+TOPOA_NAMES = ("focean", "flake", "fgrnd", "fgice", "zatmo", "hlake", "zicetop", "zland_min", "zland_max")
 
 
 def make_hntrA(hspecO):
@@ -130,6 +137,163 @@ def compute_AAmvEAm(EOpvAOp_result, hspecO, eq_rad, foceanAOp, foceanAOm, scale=
     return linear_Weighted(h, keep=(dims,))
 
 
+def _is_device(x):
+    return hasattr(x, "is_cuda")
+
+
+def _planes(arrays, n, what):
+    """The planes of one call as flat float64 arrays of n cells, all on the host (numpy, used in place when they can be) or
+    all in HBM (torch CUDA tensors, always in place) -> (planes, on_device)."""
+    dev = [_is_device(a) for a in arrays if a is not None]
+    if any(dev) and not all(dev):
+        raise ValueError("%s: host and device planes are mixed" % what)
+    on_device = bool(dev) and dev[0]
+    out = []
+    for a in arrays:
+        if a is None:
+            out.append(None)
+        elif on_device:
+            import torch
+            if not (a.is_cuda and a.dtype == torch.float64 and a.is_contiguous() and a.numel() == n):
+                raise ValueError("%s: a device plane must be a contiguous float64 CUDA tensor of %d cells" % (what, n))
+            out.append(a)
+        else:
+            b = np.ascontiguousarray(a, np.float64)
+            if b.size != n:
+                raise ValueError("%s: a plane has %d cells, the grid %d" % (what, b.size, n))
+            out.append(b)
+    return out, on_device
+
+
+def _pointer_list(planes):
+    return (C.c_void_p * len(planes))(*[p.data_ptr() if _is_device(p) else p.ctypes.data for p in planes])
+
+
+def _host(a):
+    return a.cpu().numpy() if _is_device(a) else np.asarray(a)
+
+
+def land_fraction_errors(bad, focean, flake, fgrnd, fgice, im):
+    """sanity_check_land_fractions' strings (modele/topo.cpp:873-888) for the flat cells `bad` (ascending: j, then i)."""
+    out = []
+    for c in bad:
+        fo, fl, fr, fi = float(focean[c]), float(flake[c]), float(fgrnd[c]), float(fgice[c])
+        out.append("(%d, %d): FOCEAN(%g) + FGRND(%g) + FLAKE(%g) + FGICE(%g)  = %g" % (c % im + 1, c // im + 1, fo, fr, fl, fi, fo + fr + fl + fi))
+    return out
+
+
+def merge_topoO(topoo, gcmO, emI_lands, emI_ices, hspecO, eq_rad=0.):
+    """merge_topoO (modele/merge_topo.cpp:84-360) -> (mergemaskOm, errors).  topoo: a dict of planes under topoo_bundle's
+    names; FOCEANF FGICEF ZATMOF FOCEAN FLAKE FGRND FGICE ZATMO ZICETOP are merged into (in place where the plane is a
+    contiguous float64 array; the dict holds the results either way, shaped (jmO, imO)), ZLAND_MIN / ZLAND_MAX are made.  Numpy
+    planes go through the host entry; torch CUDA planes (and masks) stay in HBM, on torch's current stream.  gcmO: the
+    GCMRegridder on the ocean grid, whose sheets (in the order they were added) emI_lands / emI_ices belong to.  errors: the
+    reference's sanity-check strings, check by check, then j, then i; the call itself succeeds when there are some."""
+    names = list(gcmO._sheets)
+    if len(emI_lands) != len(names) or len(emI_ices) != len(names):
+        raise ValueError("%d land masks and %d ice masks for %d sheets" % (len(emI_lands), len(emI_ices), len(names)))
+    lands = [gcmO.regrid_matrices(n, em, scale=False, correctA=True) for n, em in zip(names, emI_lands)]
+    ices = [gcmO.regrid_matrices(n, em, scale=False, correctA=True) for n, em in zip(names, emI_ices)]
+    return merge_topoO_rm(topoo, lands, ices, hspecO, eq_rad)
+
+
+def merge_topoO_rm(topoo, lands, ices, hspecO, eq_rad=0.):
+    """merge_topoO on the RegridMatrices of the masks (ibh_modele_merge_topoO[_device])."""
+    nO, im = hspecO.size, hspecO.im
+    planes, on_device = _planes([topoo[k] for k in TOPOO_MERGE[:9]], nO, "merge_topoO")
+    hl = (C.c_void_p * max(len(lands), 1))(*[rm._h for rm in lands])
+    hi = (C.c_void_p * max(len(ices), 1))(*[rm._h for rm in ices])
+    nerr = C.c_int64()
+    if on_device:
+        import torch
+        dev = planes[0].device
+        planes += [torch.empty(nO, dtype=torch.float64, device=dev) for _ in range(2)]
+        mask = torch.empty(nO, dtype=torch.int16, device=dev)
+        flags = torch.empty(nO, dtype=torch.int32, device=dev)
+        st = torch.cuda.current_stream(dev).cuda_stream
+        check(lib().ibh_modele_merge_topoO_device(hl, len(lands), hi, len(ices), hspecO.im, hspecO.jm, float(eq_rad), _pointer_list(planes),
+                                                 C.c_void_p(mask.data_ptr()), C.c_void_p(flags.data_ptr()), C.byref(nerr), C.c_void_p(st)))
+    else:
+        planes += [np.empty(nO), np.empty(nO)]
+        mask, flags = np.zeros(nO, np.int16), np.zeros(nO, np.uint32)
+        check(lib().ibh_modele_merge_topoO(hl, len(lands), hi, len(ices), hspecO.im, hspecO.jm, float(eq_rad), _pointer_list(planes), ptr(mask),
+                                          ptr(flags), C.byref(nerr)))
+    for k, p in zip(TOPOO_MERGE, planes):
+        topoo[k] = p.reshape(hspecO.jm, hspecO.im)
+    errors = []
+    if nerr.value:
+        f = _host(flags).astype(np.int64) & 0xFFFFFFFF
+        for bit in range(18):
+            label = MERGE_LABELS[bit % 9] + ("-0" if bit < 9 else "")
+            errors += ["(%d, %d): %s is NaN" % (c % im + 1, c // im + 1, label) for c in np.flatnonzero(f >> bit & 1)]
+        bad = np.flatnonzero(f >> 18 & 1)
+        if len(bad):
+            errors += land_fraction_errors(bad, _host(planes[3]), _host(planes[4]), _host(planes[5]), _host(planes[6]), im)
+        assert len(errors) == nerr.value
+    return mask.reshape(hspecO.jm, hspecO.im), errors
+
+
+def make_topoA(topoo, mergemaskOm, hspecO, hspecA, indexingHCA, hcdefs, underice_hc, AAmvEAm):
+    """make_topoA (modele/topo.cpp:581-855) -> (topoa, errors).  topoo: the planes FOCEAN FLAKE FGRND FGICE ZATMO ZLAKE ZICETOP
+    ZLAND_MIN ZLAND_MAX (numpy, or torch CUDA tensors with a torch int16 mergemaskOm: then everything stays in HBM);
+    indexingHCA: (stride_A, stride_HC); AAmvEAm: a linear_Weighted.  topoa: a dict of the planes under TopoABundles' names
+    (jmA, imA), mergemask (int16) and fhc, elevE (float64), underice (int16) of shape (nhc + 1, jmA, imA).  errors: the
+    strings of sanity_check_land_fractions, then sanity_check_fhc."""
+    nO, nA, im = hspecO.size, hspecA.size, hspecA.im
+    hc = np.ascontiguousarray(hcdefs, np.float64).reshape(-1)
+    ui = np.ascontiguousarray(underice_hc, np.int16).reshape(-1)
+    if len(hc) != len(ui):
+        raise ValueError("%d hcdefs for %d underice_hc" % (len(hc), len(ui)))
+    nhc = len(hc)
+    planesO, on_device = _planes([topoo[k] for k in TOPOO_MAKEA], nO, "make_topoA")
+    nerr = C.c_int64()
+    args = (hspecO.im, hspecO.jm, float(hspecO.offi), float(hspecO.dlat), hspecA.im, hspecA.jm, float(hspecA.offi), float(hspecA.dlat),
+            int(indexingHCA[0]), int(indexingHCA[1]), ptr(hc), ptr(ui), nhc, AAmvEAm._h)
+    if on_device:
+        import torch
+        dev = planesO[0].device
+        if not (_is_device(mergemaskOm) and mergemaskOm.dtype == torch.int16 and mergemaskOm.is_contiguous() and mergemaskOm.numel() == nO):
+            raise ValueError("make_topoA: mergemaskOm must be a contiguous int16 CUDA tensor of %d cells" % nO)
+        planesA = [torch.empty(nA, dtype=torch.float64, device=dev) for _ in range(9)]
+        maskA = torch.empty(nA, dtype=torch.int16, device=dev)
+        fhc, elevE = (torch.empty((nhc + 1) * nA, dtype=torch.float64, device=dev) for _ in range(2))
+        underice = torch.empty((nhc + 1) * nA, dtype=torch.int16, device=dev)
+        flags = torch.empty(nA, dtype=torch.int32, device=dev)
+        st = torch.cuda.current_stream(dev).cuda_stream
+        check(lib().ibh_modele_make_topoA_device(_pointer_list(planesO), C.c_void_p(mergemaskOm.data_ptr()), *args, _pointer_list(planesA),
+                                                *[C.c_void_p(t.data_ptr()) for t in (maskA, fhc, elevE, underice, flags)], C.byref(nerr),
+                                                C.c_void_p(st)))
+    else:
+        mO = np.ascontiguousarray(mergemaskOm, np.int16).reshape(-1)
+        if mO.size != nO:
+            raise ValueError("make_topoA: mergemaskOm has %d cells, the ocean grid %d" % (mO.size, nO))
+        planesA = [np.empty(nA) for _ in range(9)]
+        maskA, flags = np.zeros(nA, np.int16), np.zeros(nA, np.uint32)
+        fhc, elevE, underice = np.empty((nhc + 1) * nA), np.empty((nhc + 1) * nA), np.zeros((nhc + 1) * nA, np.int16)
+        check(lib().ibh_modele_make_topoA(_pointer_list(planesO), ptr(mO), *args, _pointer_list(planesA), ptr(maskA), ptr(fhc), ptr(elevE),
+                                         ptr(underice), ptr(flags), C.byref(nerr)))
+    shape2, shape3 = (hspecA.jm, hspecA.im), (nhc + 1, hspecA.jm, hspecA.im)
+    topoa = {k: p.reshape(shape2) for k, p in zip(TOPOA_NAMES, planesA)}
+    topoa.update(mergemask=maskA.reshape(shape2), fhc=fhc.reshape(shape3), elevE=elevE.reshape(shape3), underice=underice.reshape(shape3))
+    errors = []
+    if nerr.value:
+        f = _host(flags).astype(np.int64)
+        bad = np.flatnonzero(f & 1)
+        if len(bad):
+            errors += land_fraction_errors(bad, *[_host(planesA[k]) for k in (0, 1, 2, 3)], im)
+        bad = np.flatnonzero(f >> 1 & 1)
+        if len(bad):
+            fh = _host(fhc).reshape(nhc + 1, nA)
+            for c in bad:
+                all_fhc = 0.
+                for ihc in range(nhc + 1):
+                    all_fhc += float(fh[ihc, c])
+                all_fhc += 1.0
+                errors.append("(%d, %d): sum(FHC) = %g" % (c % im + 1, c // im + 1, all_fhc - 1.0))
+        assert len(errors) == nerr.value
+    return topoa, errors
+
+
 class GCMRegridder_ModelE:
     """GCMRegridder_WrapE (modele/GCMRegridder_ModelE.hpp): a GCMRegridder_ModelE over `gcmO` together with the two ocean
     fractions, so that regrid_matrices keeps the signature of GCMRegridder.regrid_matrices.  global_ec = (hcdefs_base, (iE, iO,
@@ -182,6 +346,35 @@ class GCMRegridder_ModelE:
         merged = compute_EOpvAOp_merged(rmOs, self.global_ec, use_global_ice=True, use_local_ice=True, squash_ecs=False,
                                         nO=self.gcmO.nA, indexingHC_base=self.gcmO._hc_strides)
         return compute_AAmvEAm(merged, self.hspecO, self.eq_rad, foceanAOp, foceanAOm, scale=scale), merged.offsetE
+
+    def update_topo(self, topoo, emI_lands, emI_ices, run_ice=True):
+        """GCMCoupler_ModelE::update_topo's body (modele/GCMCoupler_ModelE.cpp:1026-1082): merge_topoO with RegridParams(false,
+        true, 0), global_AvE(scale = true), wEAm_base, make_topoA.  topoo: a dict of the twelve planes under topoo_bundle's
+        names (ZLAND_MIN / ZLAND_MAX need not be there); it holds the merged planes afterwards.  Numpy planes and masks go
+        through the host entries; torch CUDA planes and masks stay in HBM between the calls (global_AvE alone reads the two
+        ocean fractions on the host).  Raises RuntimeError with the sanity-check strings when a check fails.  Returns a dict:
+        the TOPOA planes under TopoABundles' names, mergemask, fhc, elevE, underice, wEAm_base = (iE, weight) of the entries of
+        AAmvEAm's Mw whose sparse index is >= offsetE, and offsetE.  Not done here: reading the TOPOO file, packing into
+        VectorMultivecs (:1099-1170) and mergemaskA0."""
+        mergemaskOm, errors = merge_topoO(topoo, self.gcmO, emI_lands, emI_ices, self.hspecO, self.eq_rad)
+        self.foceanOp = np.ascontiguousarray(_host(topoo["FOCEANF"]), np.float64).reshape(-1).copy()
+        if not run_ice:
+            self.foceanOm = np.ascontiguousarray(_host(topoo["FOCEAN"]), np.float64).reshape(-1).copy()
+        if errors:
+            raise RuntimeError("Errors in TOPO merging or regridding; halting!\n" + "\n".join("ERROR: " + e for e in errors))
+        foceanOm = np.ascontiguousarray(_host(topoo["FOCEAN"]), np.float64).reshape(-1)
+        AAmvEAm, offsetE = self.global_AvE(emI_lands, emI_ices, self.foceanOp, foceanOm, scale=True)
+        iE, Mw = AAmvEAm.dim(1), AAmvEAm.Mw
+        keep = iE >= offsetE
+        nhc = len(self.hcdefs)
+        sO = self.gcmO._hc_strides
+        indexingHCA = (1, self.hspecA.size) if sO[1] >= sO[0] else (nhc, 1)
+        topoa, errors2 = make_topoA(topoo, mergemaskOm, self.hspecO, self.hspecA, indexingHCA, self.hcdefs,
+                                    [self.underice(k) for k in range(nhc)], AAmvEAm)
+        if errors2:
+            raise RuntimeError("Errors in TOPO merging or regridding; halting!\n" + "\n".join("ERROR: " + e for e in errors2))
+        topoa.update(wEAm_base=(iE[keep].copy(), Mw[keep].copy()), offsetE=offsetE)
+        return topoa
 
     def agridA(self, sheet_name):
         """make_agridA (GCMRegridder_ModelE.cpp:57-78): the realised atmosphere cells, first-seen (int64)."""

@@ -500,6 +500,55 @@ int ibh_modele_AAmvEAm(const ibh_weighted *EOpvAOp, const ibh_sparse_set *dimEOp
                        double offiO, double dlatO, double eq_rad, int32_t nhc, int64_t sA_O, int64_t sHC_O, int64_t sA_A, int64_t sHC_A,
                        const double *foceanAOp, const double *foceanAOm, int64_t nO, int scale, ibh_sparse_set *dimAAm,
                        ibh_sparse_set *dimEAm, ibh_weighted **out);
+/* GCMCoupler_ModelE::update_topo's field handling (modele/GCMCoupler_ModelE.cpp:972-1098): merge_topoO and make_topoA; DESIGN.md 17.
+ *
+ * ibh_weighted_row_stats_device: the statistics merge_topoO reads an OvI through, in ONE pass over the CSR.  Per dense row r:
+ * sum[r] = the sum of val * x[col], min[r] / max[r] = the smallest / largest x[col], over the STORED entries of the row alone
+ * (x may hold NaN in columns no entry names).  min starts at DBL_MAX and max at DBL_MIN, the smallest positive normal number,
+ * as the reference's zland_min / zland_max do (merge_topo.cpp:181-182): a row without entries gives (0, DBL_MAX, DBL_MIN) and a
+ * row whose x are all below DBL_MIN keeps DBL_MIN.  Any of d_sum / d_min / d_max may be NULL.  d_x [ncol_d], outputs
+ * [nrow_d], all device pointers.  The order of a row's sum depends on the row's length and the matrix's shape alone
+ * (repeatable; 1e-12 of the sequential sum).  A pure enqueue on `stream`. */
+int ibh_weighted_row_stats_device(const ibh_weighted *w, const double *d_x, double *d_sum, double *d_min, double *d_max, void *stream);
+/* merge_topoO (modele/merge_topo.cpp:84-360).  emI_lands / emI_ices: one regrid_matrices per ice sheet for the land mask and
+ * one for the ice mask (their elevmaskI is emI_lands[k] / emI_ices[k]; their scale / correctA are ignored), in sheet order, both
+ * of sheet k made from the same ice regridder, every sheet on one ocean grid of imO x jmO cells.  planes: eleven arrays
+ * [jmO*imO], iO = j*imO + i, in this order: the in/out planes foceanOp fgiceOp zatmoOp foceanOm flakeOm fgrndOm fgiceOm zatmoOm
+ * zicetopO, then the out-only zland_minO zland_maxO; mergemaskOm (int16) is out-only.  Per sheet the four AvI (scale = 1,
+ * correctA = 0 and scale = 0, correctA = 1 for either mask, fresh dimO, identity dimI) are built by ibh_regrid_matrices_matrix_batch's
+ * builder and accumulated in sheet order; then the per-cell update, the single-cell-ocean pass (one parallel pass from a
+ * snapshot of foceanOm: equal to the reference's sequential loop), the sanity checks and the NaN of the unset
+ * zland_*.  zland_maxO keeps DBL_MIN on a merged cell whose land lies entirely below that (the reference's quirk).
+ * flags [nO]: one word per cell; bit k < 9: plane k was NaN on entry ("<name>2-0"), bit 9 + k: plane k is NaN on return,
+ * bit 18: the land fractions do not sum to 1 within 1e-13.  *nerrors = the number of set bits.  The call succeeds when checks
+ * fail, as the reference's does.  eq_rad is accepted and unused.  IBH_EINVAL naming the offender, before anything is touched:
+ * mask counts that differ, imO * jmO != nA of a sheet, a sheet on another ocean grid, a non-zero sigma.
+ * _device: device pointers (planes: a host array of device pointers), enqueued on `stream`, which is synchronised before
+ * returning; the other form copies host arrays. */
+int ibh_modele_merge_topoO_device(const ibh_regrid_matrices *const *emI_lands, int32_t nlands, const ibh_regrid_matrices *const *emI_ices,
+                                  int32_t nices, int32_t imO, int32_t jmO, double eq_rad, double *const *d_planes /* [11] */,
+                                  int16_t *d_mergemaskOm, uint32_t *d_flags, int64_t *nerrors, void *stream);
+int ibh_modele_merge_topoO(const ibh_regrid_matrices *const *emI_lands, int32_t nlands, const ibh_regrid_matrices *const *emI_ices, int32_t nices,
+                           int32_t imO, int32_t jmO, double eq_rad, double *const *planes /* [11] */, int16_t *mergemaskOm, uint32_t *flags,
+                           int64_t *nerrors);
+/* make_topoA (modele/topo.cpp:581-855).  planesO: the nine ocean planes foceanOm flakeOm fgrndOm fgiceOm zatmoOm zlakeOm zicetopOm
+ * zland_minOm zland_maxOm [jmO*imO] and mergemaskOm (int16); the two HntrSpecs; (hc_stride_A, hc_stride_HC): the strides of
+ * indexingHCA; hcdefs / underice_hc [nhc] (host); AAmvEAm: read in SPARSE indices through its two sets.  planesA: the nine
+ * atmosphere planes in TopoABundles' order (focean flake fgrnd fgice zatmo hlake zicetop zland_min zland_max) [jmA*imA],
+ * mergemaskA (int16), fhc3 / elevE3 (double) and underice3 (int16) [nhc + 1, jmA, imA].  flags [nA]: bit 0: the land fractions
+ * do not sum to 1 within 1e-13, bit 1: sum(FHC) is neither 0 nor 1 within 1e-13; *nerrors = the number of set bits.
+ * IBH_EINVAL naming the entry: an entry of AAmvEAm whose iE splits into another A cell ("Matrix is non-local"), an ihc outside
+ * [0, nhc), an iA outside [0, nA); the outputs are then undefined (_device) or untouched (host form).  One host wait. */
+int ibh_modele_make_topoA_device(const double *const *d_planesO /* [9] */, const int16_t *d_mergemaskOm, int32_t imO, int32_t jmO,
+                                 double offiO, double dlatO, int32_t imA, int32_t jmA, double offiA, double dlatA, int64_t hc_stride_A,
+                                 int64_t hc_stride_HC, const double *hcdefs, const int16_t *underice_hc, int32_t nhc,
+                                 const ibh_weighted *AAmvEAm, double *const *d_planesA /* [9] */, int16_t *d_mergemaskA, double *d_fhc3,
+                                 double *d_elevE3, int16_t *d_underice3, uint32_t *d_flags, int64_t *nerrors, void *stream);
+int ibh_modele_make_topoA(const double *const *planesO /* [9] */, const int16_t *mergemaskOm, int32_t imO, int32_t jmO, double offiO,
+                          double dlatO, int32_t imA, int32_t jmA, double offiA, double dlatA, int64_t hc_stride_A, int64_t hc_stride_HC,
+                          const double *hcdefs, const int16_t *underice_hc, int32_t nhc, const ibh_weighted *AAmvEAm,
+                          double *const *planesA /* [9] */, int16_t *mergemaskA, double *fhc3, double *elevE3, int16_t *underice3,
+                          uint32_t *flags, int64_t *nerrors);
 /* Diagnostic: the sparse product the ModelE matrices are composed with, alone.  C = L * R for two matrices in HBM (columns
  * ascending inside a row, L's columns = R's rows): C(r, c) sums L(r, k) * R(k, c) over k ascending, the first term assigned;
  * an entry exists wherever a term does.  Identity dims, wM = Mw = 0, flags of L.  Used by tests/test_gpu_modele.py. */
