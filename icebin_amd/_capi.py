@@ -253,6 +253,8 @@ _SIGS = {
     "ibh_selftest_radix_sort": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "ibh_selftest_order": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                      C.POINTER(C.c_int)]),
+    "ibh_selftest_number_keys": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int,
+                                            C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_uint32)]),
 }
 
 _lib = None

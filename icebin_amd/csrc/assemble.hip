@@ -19,6 +19,7 @@
 #include "assemble.h"
 #include "csrops.h"
 #include "prims.h"
+#include "sparseset.h"
 #include "sweep_kernel.inl"
 #include <algorithm>
 #include <atomic>
@@ -208,125 +209,7 @@ __device__ __forceinline__ int list_entries(const XCell &c, long x, int list, in
 }
 
 // ---- dense numbering (spsparse::SparseSet::add_dense in emission order) ------------------------
-__global__ void k_fill_i32(int32_t *p, size_t n, int32_t v) {
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) p[i] = v;
-}
-__global__ void k_iota_i64(int64_t *p, size_t n) {
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) p[i] = (int64_t)i;
-}
-__global__ void k_scatter_existing(int32_t *tab, const int64_t *to_sparse, int n) {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) tab[to_sparse[i]] = i;
-}
-}  // namespace ibh
-
-// ibh_sparse_set (common.h)
-ibh_sparse_set::ibh_sparse_set(const ibh_sparse_set &o) : sparse_extent_(o.sparse_extent_), n_(o.n_), identity_(o.identity_) {
-    if (identity_ || !n_) return;
-    const int64_t *t = o.to_sparse_host();
-    host_.assign(t, t + n_);
-    host_n_ = n_;
-}
-void ibh_sparse_set::assign_host(int64_t sparse_extent, const int64_t *keys, int32_t n) {
-    std::vector<int64_t> sorted(keys, keys + n);
-    std::sort(sorted.begin(), sorted.end());
-    for (int32_t i = 0; i < n; ++i) {
-        IBH_CHECK(sorted[(size_t)i] >= 0 && (sparse_extent < 0 || sorted[(size_t)i] < sparse_extent),
-                  "sparse index %ld outside extent %ld", (long)sorted[(size_t)i], (long)sparse_extent);
-        IBH_CHECK(i == 0 || sorted[(size_t)i] != sorted[(size_t)i - 1], "duplicate sparse index %ld", (long)sorted[(size_t)i]);
-    }
-    *this = ibh_sparse_set(sparse_extent);
-    host_.assign(keys, keys + n);
-    n_ = host_n_ = n;
-}
-int32_t ibh_sparse_set::add_dense_host(int64_t key) {
-    IBH_CHECK(key >= 0 && (sparse_extent_ < 0 || key < sparse_extent_), "sparse index %ld outside extent %ld", (long)key, (long)sparse_extent_);
-    if (identity_ && key < n_) return (int32_t)key;
-    ensure_inverse();                       // materialises an identity prefix on the host
-    auto it = inv_.find(key);
-    if (it != inv_.end()) return it->second;
-    IBH_CHECK(n_ < 0x7fffffff, "dense extent overflows int32");
-    identity_ = false;
-    host_.push_back(key);
-    inv_[key] = n_;
-    host_n_ = inv_n_ = ++n_;                // the device copy (entries [0, dev_n_)) is completed by the next build
-    return n_ - 1;
-}
-int32_t ibh_sparse_set::to_dense(int64_t key) const {
-    if (identity_) return key >= 0 && key < n_ ? (int32_t)key : -1;
-    ensure_inverse();
-    auto it = inv_.find(key);
-    return it == inv_.end() ? -1 : it->second;
-}
-void ibh_sparse_set::ensure_host() const {
-    if (host_n_ >= n_) return;
-    host_.resize((size_t)n_);
-    if (identity_) {
-        for (int32_t i = host_n_; i < n_; ++i) host_[(size_t)i] = i;
-    } else {
-        if (dev_n_ < n_) ibh::fail(IBH_EINVAL, "internal: sparse set has no valid copy of entries [%d,%d)", host_n_, n_);
-        IBH_HIP(hipMemcpy(host_.data() + host_n_, dev_.p + host_n_, sizeof(int64_t) * (size_t)(n_ - host_n_), hipMemcpyDeviceToHost));
-    }
-    host_n_ = n_;
-}
-void ibh_sparse_set::check_entries_within(int64_t extent, const char *what) const {
-    IBH_CHECK(n_ <= extent, "%s holds %d entries, more than its extent of %lld", what, n_, (long long)extent);
-    if (identity_ || host_n_ < n_) return;          // (entries on the device only were checked when they were numbered)
-    for (int32_t i = 0; i < n_; ++i)
-        IBH_CHECK(host_[(size_t)i] >= 0 && host_[(size_t)i] < extent, "%s entry %lld outside [0, %lld)", what,
-                  (long long)host_[(size_t)i], (long long)extent);
-}
-void ibh_sparse_set::check_extent(int64_t extent, const char *what) const {
-    IBH_CHECK(sparse_extent_ == -1 || sparse_extent_ == extent, "%s has sparse extent %lld, the grid %lld cells", what,
-              (long long)sparse_extent_, (long long)extent);
-}
-void ibh_sparse_set::copy_to_sparse(int64_t *dst, int n, hipStream_t st) const {
-    if (n == 0) return;
-    if (identity_) {
-        hipLaunchKernelGGL(ibh::k_iota_i64, dim3(ibh::ceil_div(n, 256)), dim3(256), 0, st, dst, (size_t)n);
-    } else if (dev_n_ >= n) {
-        IBH_HIP(hipMemcpyAsync(dst, dev_.p, sizeof(int64_t) * (size_t)n, hipMemcpyDeviceToDevice, st));
-    } else {
-        ensure_host();
-        IBH_HIP(hipMemcpyAsync(dst, host_.data(), sizeof(int64_t) * (size_t)n, hipMemcpyHostToDevice, st));
-    }
-}
-const int64_t *ibh_sparse_set::device_to_sparse(int n, hipStream_t st) const {
-    if (n > 0 && on_device(n)) return dev_.p;
-    int64_t *t = ibh::arena().get<int64_t>((size_t)n);
-    copy_to_sparse(t, n, st);
-    return t;
-}
-const int32_t *ibh_sparse_set::device_to_dense(int64_t extent, hipStream_t st) {
-    if (tab_n_ == n_ && tab_extent_ == extent && tab_.p) return tab_.p;
-    const int T = 256;
-    tab_.alloc((size_t)extent);
-    if (dev_n_ < n_) {                      // complete the device copy of the dense -> sparse table first
-        ibh::DevBuf<int64_t> grown((size_t)n_);
-        copy_to_sparse(grown.p, n_, st);
-        IBH_HIP(hipStreamSynchronize(st));
-        dev_ = std::move(grown);
-        dev_n_ = n_;
-    }
-    hipLaunchKernelGGL(ibh::k_fill_i32, dim3(ibh::ceil_div(extent, T)), dim3(T), 0, st, tab_.p, (size_t)extent, -1);
-    hipLaunchKernelGGL(ibh::k_scatter_existing, dim3(ibh::ceil_div(n_, T)), dim3(T), 0, st, tab_.p, dev_.p, n_);
-    tab_n_ = n_; tab_extent_ = extent;
-    return tab_.p;
-}
-void ibh_sparse_set::adopt_device(ibh::DevBuf<int64_t> &&table, int32_t n, int64_t extent) noexcept {
-    set_sparse_extent(extent);
-    if (n <= n_) return;
-    // the host copy and the inverse map hold a prefix of the table and stay valid; the device inverse table does not
-    dev_ = std::move(table);
-    dev_n_ = n_ = n;
-    identity_ = false;
-    tab_n_ = -1;
-}
-
-namespace ibh {
-
+// The assembly's own, on purpose: TWO sets per exchange-cell visit, not the one key stream of sparseset.h (the set's members: there).
 // The generator passes handle BOTH sets of a matrix (rows and columns) per exchange-cell visit:
 //   pass 1 (k_first2)  first[key] = smallest emission position 2x+j naming the key (atomicMin)
 //   pass 2 (k_flag2)   pk[x] = which of the cell's entries are first occurrences + its number of
@@ -455,7 +338,6 @@ static Numbering number_set_prepare(const RgView &rg, ibh_sparse_set *set, int64
     nb.max_new = max_new;
     const int64_t cap = (int64_t)ds.n_old + max_new;
     ds.to_sparse = A.get<int64_t>((size_t)cap);
-    const int T = 256;
     SetArgs &a = nb.args;
     a.list = list; a.key = key; a.base = ds.n_old; a.to_sparse = ds.to_sparse; a.pkshift = pkshift;
     a.ident_n = -1; a.tab = nullptr;
@@ -464,8 +346,7 @@ static Numbering number_set_prepare(const RgView &rg, ibh_sparse_set *set, int64
         a.ident_n = ds.n_old;
     } else if (ds.n_old) {
         int32_t *tab = A.get<int32_t>((size_t)sparse_extent);
-        hipLaunchKernelGGL(k_fill_i32, dim3(ceil_div(sparse_extent, T)), dim3(T), 0, st, tab, (size_t)sparse_extent, -1);
-        hipLaunchKernelGGL(k_scatter_existing, dim3(ceil_div(ds.n_old, T)), dim3(T), 0, st, tab, ds.to_sparse, ds.n_old);
+        fill_to_dense_table(tab, sparse_extent, ds.to_sparse, ds.n_old, st);
         a.tab = tab;
     }
     ds.n = ds.n_old;
@@ -800,8 +681,8 @@ __global__ void k_col_sums_long(const uint32_t *__restrict__ colptr, const int32
 
 // ---- weights and scaling (RegridMatrices_Dynamic.cpp:100-146, 201-233, 290-329) ----------------
 __device__ __forceinline__ double ratio_of(const RgView &rg, int keykind, int64_t sparse) {
-    long iA = sparse;
-    if (keykind == KEY_E) iA = rg.sHC >= rg.sA ? (sparse % rg.sHC) / rg.sA : sparse / rg.sA;
+    int64_t iA = sparse, ihc;
+    if (keykind == KEY_E) HcIndexing{rg.sA, rg.sHC}.split(sparse, iA, ihc);
     return rg.ratioA[iA];
 }
 struct FinalizeArgs {
@@ -1061,8 +942,7 @@ static void build_csr_from_contributions(ibh_weighted *w, Triplets t, int nrow, 
 // classes pair up from the lowest (k, k+1), so the partner row of a band is always the same row.
 // A filtered copy of the CSR: no sorting, exact copies of M's values.
 __device__ __forceinline__ void e_decode(const RgView &rg, int64_t e, long &a, long &hc) {
-    if (rg.sHC >= rg.sA) { hc = e / rg.sHC; a = (e % rg.sHC) / rg.sA; }
-    else { a = e / rg.sA; hc = e % rg.sA; }
+    HcIndexing{rg.sA, rg.sHC}.split<true>(e, a, hc);      // (a regridder's strides are checked when it is made)
 }
 __global__ void k_band_roles(RgView rg, const int64_t *__restrict__ row_s, const uint32_t *__restrict__ colptr, int ncol,
                              const int32_t *__restrict__ lrow, const uint32_t *__restrict__ lidx,
@@ -2708,7 +2588,8 @@ void csr_from_device_triplets(ibh_weighted *w, int nrow, int ncol, int64_t n, co
 
 // setFromTriplets from triplets already on the device (dense ids, input order) and the plain weights wM / Mw = spsparse
 // sum(M, dim, '+') (columns visited ascending, rows ascending inside): the general-dims path of the Hntr matrices (hntr.hip).
-// Enqueued on `st`; reads nothing back but nnz.  The arena is not reset: the caller's triplets may live there.
+// Enqueued on `st`; reads nothing back but nnz.  The arena is not reset: the caller's triplets may live there.  n == 0: the
+// empty CSR over the given shape with zeroed wM / Mw.
 void weighted_from_device_triplets(ibh_weighted *w, int nrow, int ncol, int64_t n, const int32_t *drow, const int32_t *dcol,
                                    const double *dval, hipStream_t st) {
     csr_from_triplets(w, nrow, ncol, n, drow, dcol, dval, hipMemcpyDeviceToDevice, st);

@@ -4,10 +4,12 @@
 #include <map>
 #include <memory>
 #include <mutex>
+#include <type_traits>
 
 #include "assemble.h"
 #include "common.h"
 #include "prims.h"
+#include "sparseset.h"
 
 namespace ibh {
 
@@ -120,6 +122,51 @@ template <class T> static void selftest_download_guarded(T *host, const T *dev, 
     for (size_t i = 0; i < SELFTEST_GUARD * sizeof(T); ++i)
         IBH_CHECK(g[i] == 0xA5, "%s: written past its end (byte %zu after element %zu)", what, i, n);
     if (n) memcpy(host, tmp.data(), sizeof(T) * n);
+}
+// ibh_selftest_number_keys on keys of one width: number_stream where it serves the case, else the two host steps as a build uses them
+template <class K>
+static void selftest_number(ibh_sparse_set *set, int64_t extent, int transform, const K *hkey, int stride, long n, const uint8_t *hact,
+                            bool check_range, int32_t *dense_out, int64_t *table_out, int32_t *n_new_out, uint32_t *status_out) {
+    hipStream_t st = hipStreamPerThread;
+    Arena &A = arena();
+    A.reset();
+    const size_t nk = n ? (size_t)(n - 1) * (size_t)stride + 1 : 0;
+    K *key = A.get<K>(nk);
+    uint8_t *act = hact ? A.get<uint8_t>((size_t)n) : nullptr;
+    int32_t *dense = selftest_alloc_guarded<int32_t>(A, (size_t)n, st);
+    uint32_t *missing = A.get<uint32_t>(1);
+    if (n) IBH_HIP(hipMemcpyAsync(key, hkey, sizeof(K) * nk, hipMemcpyHostToDevice, st));
+    if (n && act) IBH_HIP(hipMemcpyAsync(act, hact, (size_t)n, hipMemcpyHostToDevice, st));
+    IBH_HIP(hipMemsetAsync(missing, 0, sizeof(uint32_t), st));
+    if (std::is_same<K, int64_t>::value && set && check_range && transform == IBH_ADD_DENSE && stride == 1 && !act) {
+        const int32_t n0 = set->n();        // number_stream's own case goes through number_stream, its failure path included
+        *status_out = 0;
+        try {
+            number_stream(*set, extent, reinterpret_cast<const int64_t *>(key), n, dense, "selftest", st);
+        } catch (const Error &e) {
+            if (!strstr(e.msg.c_str(), "an index outside")) throw;
+            *status_out = IBH_NUMBER_KEYS_OUT_OF_RANGE;
+        }
+        selftest_download_guarded(dense_out, dense, (size_t)n, st, "dense ids");
+        *n_new_out = set->n() - n0;
+        if (set->n()) std::copy(set->to_sparse_host(), set->to_sparse_host() + set->n(), table_out);
+        return;
+    }
+    const KeyNumberingRun nb = number_keys_prepare(set, extent, transform, key, stride, n, act, check_range, st);
+    number_keys_dense(nb, key, stride, n, dense, missing, st);
+    uint32_t h[2] = {0, 0}, hmiss = 0;
+    IBH_HIP(hipMemcpyAsync(h, nb.status, sizeof(h), hipMemcpyDeviceToHost, st));
+    IBH_HIP(hipMemcpyAsync(&hmiss, missing, sizeof(hmiss), hipMemcpyDeviceToHost, st));
+    selftest_download_guarded(dense_out, dense, (size_t)n, st, "dense ids");
+    const bool bad_range = check_range && h[1] != 0;
+    *status_out = (bad_range ? IBH_NUMBER_KEYS_OUT_OF_RANGE : 0u) | (hmiss ? IBH_NUMBER_KEYS_MISSING : 0u);
+    const uint32_t n_new = nb.adds() && !bad_range ? h[0] : 0;      // (a build fails on a key out of range: nothing is adopted)
+    *n_new_out = (int32_t)n_new;
+    if (!set) return;
+    DevBuf<int64_t> grown = number_keys_grow(nb, key, stride, n, n_new, st);
+    IBH_HIP(hipStreamSynchronize(st));
+    set->adopt_device(std::move(grown), (int32_t)(nb.s.n_old + n_new), extent);
+    if (set->n()) std::copy(set->to_sparse_host(), set->to_sparse_host() + set->n(), table_out);
 }
 }  // namespace ibh
 
@@ -828,6 +875,39 @@ int ibh_selftest_order(const uint64_t *keys, int64_t n, int lo_bits, int hi_bits
         const uint32_t f[6] = {h.flags, h.nchunks, h.maxlen, h.nsmall, h.nmid, h.nbig};
         memcpy(info_out, f, sizeof(f));
         *path_out = !(h.flags & ORD_FULL_DEC) ? 0 : h.maxlen <= (uint32_t)CS_BIG ? 1 : 2;
+    });
+}
+int ibh_selftest_number_keys(const void *keys, int key_bytes, int stride, int64_t n, const uint8_t *act, int64_t extent,
+                             const int64_t *to_sparse, int32_t n_old, int identity, int transform, int check_range,
+                             int32_t *dense_out, int64_t *table_out, int32_t *n_new_out, uint32_t *status_out) {
+    return guarded([&] {
+        IBH_CHECK(key_bytes == 4 || key_bytes == 8, "key_bytes = %d: keys are int32 (4) or int64 (8)", key_bytes);
+        IBH_CHECK(n >= 0 && n < (1ll << 31), "n = %lld out of range", (long long)n);
+        IBH_CHECK(stride >= 1 && (n == 0 || (n - 1) * (int64_t)stride < (1ll << 31)), "stride = %d out of range", stride);
+        IBH_CHECK(extent >= 0 && extent < (1ll << 31), "extent = %lld out of range", (long long)extent);
+        IBH_CHECK(transform == IBH_ADD_DENSE || transform == IBH_TO_DENSE || transform == IBH_TO_DENSE_IGNORE_MISSING, "unknown transform %d",
+                  transform);
+        IBH_CHECK(n_old >= -1 && n_old <= extent, "n_old = %d: -1 (no set) or 0 .. extent", n_old);
+        IBH_CHECK((identity == 0 || identity == 1) && (check_range == 0 || check_range == 1), "identity and check_range are 0 or 1");
+        IBH_CHECK((n == 0 || (keys && dense_out)) && n_new_out && status_out, "null argument");
+        IBH_CHECK(n_old <= 0 || identity || to_sparse, "null to_sparse");
+        IBH_CHECK(n_old < 0 || table_out, "null table_out");
+        if (!check_range)       // nothing on the device checks them then
+            for (int64_t p = 0; p < n; ++p) {
+                const int64_t k = key_bytes == 4 ? (int64_t)static_cast<const int32_t *>(keys)[p * stride] : static_cast<const int64_t *>(keys)[p * stride];
+                IBH_CHECK(k >= 0 && k < extent, "key %lld = %lld outside [0, %lld) and check_range = 0", (long long)p, (long long)k, (long long)extent);
+            }
+        ibh_sparse_set set(extent);
+        if (n_old >= 0 && identity) { set.make_identity(n_old); set.set_sparse_extent(extent); }
+        else if (n_old > 0) set.assign_host(extent, to_sparse, n_old);
+        require_device();
+        ibh_sparse_set *ps = n_old >= 0 ? &set : nullptr;
+        if (key_bytes == 4)
+            selftest_number(ps, extent, transform, static_cast<const int32_t *>(keys), stride, (long)n, act, check_range != 0, dense_out,
+                            table_out, n_new_out, status_out);
+        else
+            selftest_number(ps, extent, transform, static_cast<const int64_t *>(keys), stride, (long)n, act, check_range != 0, dense_out,
+                            table_out, n_new_out, status_out);
     });
 }
 int ibh_event_create(void **out) {

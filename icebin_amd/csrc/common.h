@@ -119,13 +119,30 @@ inline int bits_for(uint64_t n) {   // bits needed to represent values in [0, n)
     return b;
 }
 
+// indexingHC of an E index: iE = iA * sA + ihc * sHC, with (sA, sHC) = (1, nA) (the class slowest) or (nhc, 1) (the class
+// fastest).  The one definition of the tuple for every unit, on the host and on the device.
+struct HcIndexing {
+    int64_t sA, sHC;
+    // UNIT_CLASS_STRIDE: the caller has checked that the strides are one of the two pairs above, so the class stride of the
+    // class-fastest order is 1 and its division is left out (the assembly's kernels decode once per matrix entry: with the
+    // division the E-keyed builds measured 2 - 5 % slower)
+    template <bool UNIT_CLASS_STRIDE = false>
+    __host__ __device__ void split(int64_t iE, int64_t &iA, int64_t &ihc) const {
+        if (sHC >= sA) { ihc = iE / sHC; iA = (iE % sHC) / sA; }
+        else { iA = iE / sA; ihc = UNIT_CLASS_STRIDE ? iE % sA : (iE % sA) / sHC; }
+    }
+    __host__ __device__ int64_t index(int64_t iA, int64_t ihc) const { return iA * sA + ihc * sHC; }
+    // indexingHC_change_nhc (modele/merge_topo.cpp:364-372): the class-slowest order keeps (1, nA), the class-fastest one becomes (nhc, 1)
+    HcIndexing with_nhc(int64_t nhc) const { return sHC >= sA ? *this : HcIndexing{nhc, 1}; }
+};
+
 }  // namespace ibh
 
 // ---- handle layouts (opaque to the C-ABI user) ----------------------------------------------
 // A SparseSet (spsparse::SparseSet): the dense -> sparse table of a matrix dimension, in first-seen order.  A matrix build
 // appends on the DEVICE; the host copy is completed lazily (ensure_host) so that a 10^7-entry dims table never crosses PCIe
 // unless a caller actually reads it.  The copies and caches are changed by the members alone, so each decides in one place
-// which of them stay valid (the longer ones: assemble.hip, "dense numbering").
+// which of them stay valid (the longer ones: sparseset.hip).
 struct ibh_sparse_set {
   public:
     ibh_sparse_set() = default;

@@ -5,7 +5,7 @@
 // Where things live.  The merge keeps every index and value of every matrix in HBM: a sheet's EvA is visited by columns
 // through transpose_csr and an emit kernel that writes 64-bit SPARSE keys from the two device to_sparse tables, the base
 // matrix is uploaded once and shifted by offsetE there, and the first-seen numbering of the two key streams runs on the
-// device as well (number_stream: one atomicMin table over the sparse extent, a flag scan).  The composition behind it is
+// device as well (sparseset.h number_stream).  The composition behind it is
 // modele_parts.h's (the keys of the GCM-grid-sized sets on the host) followed by two sparse products with the
 // diagonal scalings between them, each operand rounded before it is used.
 #include <algorithm>
@@ -17,85 +17,12 @@
 #include "csrops.h"
 #include "modele_parts.h"
 #include "prims.h"
+#include "sparseset.h"
 
 namespace ibh {
 namespace {
 
 constexpr int16_t UI_LOCALICE = 1, UI_GLOBALICE = 2;        // modele/grids.hpp:44-46
-
-// ---- first-seen numbering of one key stream (spsparse::SparseSet::add_dense in stream order) --------------------------------
-// tab: the set's old sparse -> dense table (-1 missing), null for an empty set.  A key outside [0, extent) sets *bad and is
-// skipped by every pass (nothing is indexed with it); the build then fails before anything is read.
-__device__ __forceinline__ bool ga_known(const int32_t *__restrict__ tab, int64_t k) { return tab && tab[k] >= 0; }
-// pass 1: first[key] = smallest stream position that names a key the set lacks
-__global__ void k_ga_first(const int64_t *__restrict__ keys, long n, int64_t extent, const int32_t *__restrict__ tab,
-                           uint32_t *__restrict__ first, uint32_t *__restrict__ bad) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int64_t k = keys[i];
-    if (k < 0 || k >= extent) { *bad = 1u; return; }
-    if (!ga_known(tab, k)) atomicMin(&first[k], (uint32_t)i);
-}
-// pass 2: isnew[i] = position i is the first occurrence of a new key (a byte scan then ranks them)
-__global__ void k_ga_flag(const int64_t *__restrict__ keys, long n, int64_t extent, const int32_t *__restrict__ tab,
-                          const uint32_t *__restrict__ first, uint8_t *__restrict__ isnew) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int64_t k = keys[i];
-    isnew[i] = k >= 0 && k < extent && !ga_known(tab, k) && first[k] == (uint32_t)i ? 1 : 0;
-}
-// pass 3: dense id = the old one, or n0 + rank of the key's first occurrence; first occurrences record to_sparse
-__global__ void k_ga_number(const int64_t *__restrict__ keys, long n, int64_t extent, const int32_t *__restrict__ tab,
-                            const uint32_t *__restrict__ first, const uint8_t *__restrict__ isnew, const uint32_t *__restrict__ rank,
-                            int32_t n0, int32_t *__restrict__ dense, int64_t *__restrict__ table_new) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int64_t k = keys[i];
-    if (k < 0 || k >= extent) { dense[i] = 0; return; }
-    if (ga_known(tab, k)) { dense[i] = tab[k]; return; }
-    dense[i] = n0 + (int32_t)rank[first[k]];
-    if (isnew[i]) table_new[rank[i]] = k;
-}
-// dense[i] = add_dense(keys[i]) for i ascending; the set takes the new keys and `extent`.  Uses the arena (not reset: the
-// caller's arrays may live there); one host wait.
-void number_stream(ibh_sparse_set &set, int64_t extent, const int64_t *keys, long n, int32_t *dense, const char *what, hipStream_t st) {
-    IBH_CHECK(extent >= 0 && extent < (1ll << 31), "%s: a sparse extent of %lld cannot be numbered on the device", what, (long long)extent);
-    IBH_CHECK(n < (1ll << 31), "%s: %ld entries overflow int32", what, n);
-    if (n == 0 || extent == 0) {
-        IBH_CHECK(n == 0, "%s: entries in a set of extent 0", what);
-        set.set_sparse_extent(extent);
-        return;
-    }
-    const int T = 256;
-    const int32_t n0 = set.n();
-    const int32_t *tab = n0 ? set.device_to_dense(extent, st) : nullptr;
-    Arena &A = arena();
-    uint32_t *first = A.get<uint32_t>((size_t)extent), *rank = A.get<uint32_t>((size_t)n), *status = A.get<uint32_t>(2);
-    uint8_t *isnew = A.get<uint8_t>((size_t)n);
-    int64_t *table_new = A.get<int64_t>((size_t)n);
-    IBH_HIP(hipMemsetAsync(first, 0xFF, sizeof(uint32_t) * (size_t)extent, st));
-    IBH_HIP(hipMemsetAsync(status, 0, sizeof(uint32_t) * 2, st));
-    const dim3 grid(ceil_div(n, T));
-    hipLaunchKernelGGL(k_ga_first, grid, dim3(T), 0, st, keys, n, extent, tab, first, status + 1);
-    hipLaunchKernelGGL(k_ga_flag, grid, dim3(T), 0, st, keys, n, extent, tab, first, isnew);
-    exclusive_scan_u8(isnew, rank, (size_t)n, status, st);
-    hipLaunchKernelGGL(k_ga_number, grid, dim3(T), 0, st, keys, n, extent, tab, first, isnew, rank, n0, dense, table_new);
-    IBH_HIP(hipGetLastError());
-    uint32_t h[2] = {0, 0};
-    readback_sync(h, status, sizeof(h), st);                // the one host wait of a numbering
-    IBH_CHECK(h[1] == 0, "%s: an index outside [0, %lld)", what, (long long)extent);
-    const uint32_t n_new = h[0];
-    IBH_CHECK((int64_t)n0 + n_new < 0x7fffffffll, "dense extent overflows int32");
-    if (n_new) {
-        DevBuf<int64_t> grown((size_t)n0 + n_new);
-        set.copy_to_sparse(grown.p, n0, st);
-        IBH_HIP(hipMemcpyAsync(grown.p + n0, table_new, sizeof(int64_t) * n_new, hipMemcpyDeviceToDevice, st));
-        IBH_HIP(hipStreamSynchronize(st));
-        set.adopt_device(std::move(grown), (int32_t)(n0 + n_new), extent);
-    } else {
-        set.set_sparse_extent(extent);
-    }
-}
 
 // ---- the merge's streams ------------------------------------------------------------------------------------------------------
 // T = a sheet's EvA transposed: row c of T is column c of EvA with its rows ascending, so T's entries in storage order are
@@ -114,44 +41,29 @@ __global__ void k_ga_add_offset(int64_t *__restrict__ key, long n, int64_t offse
 // squash_ECs (:507-519): T = EOpvAOp0 transposed (the column-major visit).  A row key splits through the strides of
 // indexingHC0 into (iO, ihc0) and becomes indexingHC1(iO, to_new[ihc0]); the column stays dense.  64-bit throughout (the
 // reference computes these in int).  An ihc0 outside [0, nhc0) gives key -1, which number_stream refuses.
-struct HcStrides { int64_t sA, sHC; };
-__global__ void k_ga_squash(Csr T, const int64_t *__restrict__ tsE0, HcStrides s0, int32_t nhc0, const int32_t *__restrict__ to_new,
-                            HcStrides s1, int64_t *__restrict__ keyE, int32_t *__restrict__ col, double *__restrict__ val) {
+__global__ void k_ga_squash(Csr T, const int64_t *__restrict__ tsE0, HcIndexing s0, int32_t nhc0, const int32_t *__restrict__ to_new,
+                            HcIndexing s1, int64_t *__restrict__ keyE, int32_t *__restrict__ col, double *__restrict__ val) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= T.nrow) return;
     for (int e = T.rowptr[c]; e < T.rowptr[c + 1]; ++e) {
         const int64_t k = tsE0[T.colind[e]];
         int64_t iO, ihc;
-        if (s0.sHC >= s0.sA) { ihc = k / s0.sHC; iO = (k % s0.sHC) / s0.sA; }
-        else { iO = k / s0.sA; ihc = (k % s0.sA) / s0.sHC; }
-        keyE[e] = ihc >= 0 && ihc < nhc0 ? iO * s1.sA + (int64_t)to_new[ihc] * s1.sHC : -1;
+        s0.split(k, iO, ihc);
+        keyE[e] = ihc >= 0 && ihc < nhc0 ? s1.index(iO, to_new[ihc]) : -1;
         col[e] = c; val[e] = T.val[e];
     }
 }
 
-// setFromTriplets with the weights; a stream without entries gives the empty matrix over the sets as they are
-void triplets_to_weighted(ibh_weighted *w, int nrow, int ncol, int64_t n, const int32_t *drow, const int32_t *dcol, const double *dval,
-                          hipStream_t st) {
-    if (n) { weighted_from_device_triplets(w, nrow, ncol, n, drow, dcol, dval, st); return; }
-    w->nrow = nrow; w->ncol = ncol; w->nnz = 0;
-    w->rowptr.alloc((size_t)nrow + 1); w->rowptr.zero(st);
-    w->colind.alloc(0); w->val.alloc(0);
-    w->wM.alloc((size_t)nrow); w->wM.zero(st);
-    w->Mw.alloc((size_t)ncol); w->Mw.zero(st);
-}
-
 struct MergeOut {
-    int64_t offsetE = 0, sA = 1, sHC = 0;
+    int64_t offsetE = 0;
+    HcIndexing hc{1, 0};
     std::vector<double> hcdefs;
     std::vector<int16_t> underice;
 };
 
-// indexingHC_change_nhc (:364-372) on strides: the class-slowest order keeps (1, nO), the class-fastest one becomes (nhc, 1)
-HcStrides change_nhc(HcStrides s, int32_t nhc) { return s.sHC >= s.sA ? s : HcStrides{nhc, 1}; }
-
 void merge_EOpvAOp(const ibh_regrid_matrices *const *rmOs, int nsheets, int64_t nO, int64_t base_nE, int64_t base_nO, int64_t base_nnz,
                    const int64_t *base_iE, const int64_t *base_iO, const double *base_val, const double *hcdefs_base, int32_t nhc_base,
-                   HcStrides sbase, bool use_global, bool use_local, bool squash, ibh_sparse_set *dimAOp, ibh_sparse_set *dimEOp,
+                   HcIndexing sbase, bool use_global, bool use_local, bool squash, ibh_sparse_set *dimAOp, ibh_sparse_set *dimEOp,
                    ibh_weighted **out, MergeOut &mo) {
     hipStream_t st = hipStreamPerThread;
     const int T = 256;
@@ -197,7 +109,7 @@ void merge_EOpvAOp(const ibh_regrid_matrices *const *rmOs, int nsheets, int64_t 
         mo.underice.insert(mo.underice.end(), (size_t)nhc_base, UI_GLOBALICE);
     }
     const int32_t nhc0 = (int32_t)mo.hcdefs.size();
-    const HcStrides s0 = change_nhc(sbase, nhc0);
+    const HcIndexing s0 = sbase.with_nhc(nhc0);
     if (dimAOp) { dimAOp->check_extent(extentA, "merge_EOpvAOp: dimAOp"); dimAOp->check_entries_within(extentA, "dimAOp"); }
     // squash_ECs (:481-495): the sorted distinct elevations and the old class -> new class map
     std::vector<double> hc1(mo.hcdefs);
@@ -244,7 +156,8 @@ void merge_EOpvAOp(const ibh_regrid_matrices *const *rmOs, int nsheets, int64_t 
     }
     sheets.clear();
 
-    // {ADD_DENSE, ADD_DENSE} over {dimEOp (fresh), dimAOp (the caller's)}, then setFromTriplets with the weights
+    // {ADD_DENSE, ADD_DENSE} over {dimEOp (fresh), dimAOp (the caller's)}, then setFromTriplets with the weights (a stream
+    // without entries gives the empty matrix over the sets as they are)
     WorkingSet wA(dimAOp), wE(dimEOp);
     ibh_sparse_set dimEOp0;                 // the unsquashed rows, when squash_ECs follows
     ibh_sparse_set &setE0 = squash ? dimEOp0 : *wE;
@@ -252,11 +165,11 @@ void merge_EOpvAOp(const ibh_regrid_matrices *const *rmOs, int nsheets, int64_t 
     number_stream(setE0, extentE, keyE.p, (long)total, drow.p, "merge_EOpvAOp: rows", st);
     number_stream(*wA, extentA, keyA.p, (long)total, dcol.p, "merge_EOpvAOp: columns", st);
     auto w = new_weighted();
-    triplets_to_weighted(w.get(), setE0.n(), wA->n(), total, drow.p, dcol.p, val.p, st);
-    mo.sA = s0.sA; mo.sHC = s0.sHC;
+    weighted_from_device_triplets(w.get(), setE0.n(), wA->n(), total, drow.p, dcol.p, val.p, st);
+    mo.hc = s0;
     if (squash) {
         // squash_ECs (:497-523)
-        const HcStrides s1 = change_nhc(s0, nhc1);
+        const HcIndexing s1 = s0.with_nhc(nhc1);
         const int64_t nnz0 = w->nnz;
         DevBuf<int32_t> d_to_new;
         d_to_new.upload(to_new.data(), to_new.size(), st);
@@ -272,11 +185,11 @@ void merge_EOpvAOp(const ibh_regrid_matrices *const *rmOs, int nsheets, int64_t 
         }
         arena().reset();
         number_stream(*wE, extentA * nhc1, keyE.p, (long)nnz0, drow.p, "squash_ECs: rows", st);
-        triplets_to_weighted(w1.get(), wE->n(), wA->n(), nnz0, drow.p, dcol.p, val.p, st);
+        weighted_from_device_triplets(w1.get(), wE->n(), wA->n(), nnz0, drow.p, dcol.p, val.p, st);
         w = std::move(w1);
         mo.hcdefs = hc1;
         mo.underice.assign((size_t)nhc1, UI_GLOBALICE);
-        mo.sA = s1.sA; mo.sHC = s1.sHC;
+        mo.hc = s1;
     }
     w->conservative = 0; w->scaled = 0;
     IBH_HIP(hipStreamSynchronize(st));      // the caller's base arrays are free
@@ -357,7 +270,7 @@ void compute_AAmvEAm(const ibh_weighted *EOpvAOp, const ibh_sparse_set *dimEOp, 
     const int nEOm = dimEOm.n();
 
     // EOmvEAm numbers dimEAm (:309-315); wEAm (:320-323)
-    auto EOmvEAm = raw_EOvEA(hntr.get(), eq_rad, includeO, dimEOm, wEOm, wEOm_h, nhc, sA_O, sHC_O, sA_A, sHC_A, *work[1], st);
+    auto EOmvEAm = raw_EOvEA(hntr.get(), eq_rad, includeO, dimEOm, wEOm, wEOm_h, nhc, HcIndexing{sA_O, sHC_O}, HcIndexing{sA_A, sHC_A}, *work[1], st);
     const int nEAm = work[1]->n();
     IBH_CHECK(EOmvEAm->nrow == nEOm && EOmvEAm->ncol == nEAm && EOmvAOm.nrow == nEOm && EOmvAOm.ncol == nAOm,
               "internal: AAmvEAm matrix shapes disagree");
@@ -412,10 +325,10 @@ int ibh_modele_merge_EOpvAOp(const ibh_regrid_matrices *const *rmOs, int nsheets
         IBH_CHECK(EOpvAOp && offsetE && nhc_out && stride_A_out && stride_HC_out, "null argument");
         MergeOut mo;
         merge_EOpvAOp(rmOs, nsheets, nO, base_nE, base_nO, base_nnz, base_iE, base_iO, base_val, hcdefs_base, nhc_base,
-                      HcStrides{base_stride_A, base_stride_HC}, use_global_ice != 0, use_local_ice != 0, squash_ecs != 0, dimAOp, dimEOp,
+                      HcIndexing{base_stride_A, base_stride_HC}, use_global_ice != 0, use_local_ice != 0, squash_ecs != 0, dimAOp, dimEOp,
                       EOpvAOp, mo);
         *offsetE = mo.offsetE; *nhc_out = (int32_t)mo.hcdefs.size();
-        *stride_A_out = mo.sA; *stride_HC_out = mo.sHC;
+        *stride_A_out = mo.hc.sA; *stride_HC_out = mo.hc.sHC;
         if (hcdefs_out) std::copy(mo.hcdefs.begin(), mo.hcdefs.end(), hcdefs_out);
         if (underice_out) std::copy(mo.underice.begin(), mo.underice.end(), underice_out);
     });

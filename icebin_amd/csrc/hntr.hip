@@ -27,6 +27,7 @@
 
 #include "assemble.h"
 #include "common.h"
+#include "sparseset.h"
 
 namespace ibh {
 
@@ -599,76 +600,38 @@ __global__ void k_hm_colsum(HmArgs a, double *__restrict__ Mw) {
     Mw[col] = s;
 }
 
-// ---- first-seen numbering of one set (spsparse::SparseSet::add_dense in stream order), and the to-dense transforms ----
+// ---- the to-dense transforms of the triplets (the numbering itself: sparseset.h) ----------------------------------------------
 // An entry's indices are transformed in order, B then A, and the entry stops at the first index that
 // TO_DENSE_IGNORE_MISSING drops: its A index is then neither numbered (ADD_DENSE) nor looked up (TO_DENSE).  So B is
 // numbered over every entry and A over the entries whose B index survived (`act`).
-struct HmSet {
-    long ident_n;               // >= 0: the old part is the identity on [0, ident_n)
-    const int32_t *tab;         // otherwise: old sparse -> dense (-1 missing), [extent]
-    int n_old, transform;
-    uint32_t *first;            // ADD_DENSE: [extent] smallest stream position naming a missing key
-    uint32_t *rank;             // ADD_DENSE: [n] exclusive scan of the new-key flags
-    const uint8_t *act;         // entries this set sees (nullptr: all)
-};
-__device__ __forceinline__ int hm_old(const HmSet &s, long key) {
-    if (s.ident_n >= 0) return key < s.ident_n ? (int)key : -1;
-    return s.tab[key];
-}
-// the key of stream position p is key[p * stride]: stride 1 for the triplets' own index arrays, 2 for the ice index (.y) of
-// global_ec's exchange indices
-__global__ void k_hm_first(HmSet s, const int32_t *__restrict__ key, int stride, long n) {
-    const long p = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= n || (s.act && !s.act[p])) return;
-    const int32_t k = key[p * stride];
-    if (hm_old(s, k) < 0) atomicMin(&s.first[k], (uint32_t)p);
-}
-__global__ void k_hm_newflag(HmSet s, const int32_t *__restrict__ key, int stride, long n, uint32_t *__restrict__ flag) {
-    const long p = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= n) return;
-    const int32_t k = key[p * stride];
-    flag[p] = (!s.act || s.act[p]) && hm_old(s, k) < 0 && s.first[k] == (uint32_t)p ? 1u : 0u;
-}
-__device__ __forceinline__ int hm_dense(const HmSet &s, long key) {
-    const int d = hm_old(s, key);
-    if (d >= 0 || s.transform != IBH_ADD_DENSE) return d;
-    return s.n_old + (int)s.rank[s.first[key]];
-}
 // act[p]: the B index has a dense id; keep[p]: so has the A index of an active entry.  A key missing under TO_DENSE
 // raises *bad.
-__global__ void k_hm_gate(HmSet sb, const int32_t *__restrict__ iB, long n, uint8_t *__restrict__ act, uint32_t *__restrict__ bad) {
+__global__ void k_hm_gate(KeyNumbering sb, const int32_t *__restrict__ iB, long n, uint8_t *__restrict__ act, uint32_t *__restrict__ bad) {
     const long p = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= n) return;
-    const int db = hm_dense(sb, iB[p]);
+    const int db = dense_of(sb, iB[p]);
     if (db < 0 && sb.transform == IBH_TO_DENSE) atomicOr(bad, 1u);
     act[p] = db >= 0;
 }
-__global__ void k_hm_keep(HmSet sa, const int32_t *__restrict__ iA, long n, uint32_t *__restrict__ keep, uint32_t *__restrict__ bad) {
+__global__ void k_hm_keep(KeyNumbering sa, const int32_t *__restrict__ iA, long n, uint32_t *__restrict__ keep, uint32_t *__restrict__ bad) {
     const long p = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= n) return;
     if (!sa.act[p]) { keep[p] = 0; return; }
-    const int da = hm_dense(sa, iA[p]);
+    const int da = dense_of(sa, iA[p]);
     if (da < 0 && sa.transform == IBH_TO_DENSE) atomicOr(bad, 1u);
     keep[p] = da >= 0 ? 1u : 0u;
 }
-__global__ void k_hm_compact(HmSet sb, HmSet sa, const int32_t *__restrict__ iB, const int32_t *__restrict__ iA,
+__global__ void k_hm_compact(KeyNumbering sb, KeyNumbering sa, const int32_t *__restrict__ iB, const int32_t *__restrict__ iA,
                              const double *__restrict__ v, long n, const uint32_t *__restrict__ kpos, int transpose,
                              int32_t *__restrict__ row, int32_t *__restrict__ col, double *__restrict__ val) {
     const long p = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= n || kpos[p + 1] == kpos[p]) return;
-    const int db = hm_dense(sb, iB[p]), da = hm_dense(sa, iA[p]);
+    const int db = dense_of(sb, iB[p]), da = dense_of(sa, iA[p]);
     const uint32_t q = kpos[p];
     row[q] = transpose ? da : db;
     col[q] = transpose ? db : da;
     val[q] = v[p];
 }
-// new keys in first-seen order
-__global__ void k_hm_newkeys(const int32_t *__restrict__ key, int stride, long n, const uint32_t *__restrict__ rank,
-                             int64_t *__restrict__ out) {
-    const long p = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p < n && rank[p + 1] != rank[p]) out[rank[p]] = key[p * stride];
-}
-
 static int hm_tpr(int64_t nnz, int64_t nrow) {
     const int64_t avg = nrow ? nnz / nrow : 0;
     int tpr = 4;
@@ -746,50 +709,6 @@ static bool hm_full_identity(const ibh_sparse_set *set, int64_t extent) {
     return !set || (set->identity() && set->n() == extent);
 }
 
-struct HmNumber {
-    HmSet s{};
-    ibh_sparse_set *set = nullptr;
-    uint32_t *flag = nullptr;       // [n+1]: new-key flags, then their exclusive scan (rank)
-};
-static HmNumber hm_number_prepare(ibh_sparse_set *set, int64_t extent, int transform, const int32_t *key, int stride, long n,
-                                  const uint8_t *act, hipStream_t st) {
-    Arena &A = arena();
-    HmNumber nb;
-    nb.set = set;
-    HmSet &s = nb.s;
-    s.transform = transform;
-    s.act = act;
-    s.n_old = set ? set->n() : (int)extent;
-    s.ident_n = -1;
-    if (!set || set->identity() || s.n_old == 0) s.ident_n = s.n_old;      // an empty set: the identity on [0, 0)
-    else s.tab = set->device_to_dense(extent, st);
-    if (transform == IBH_ADD_DENSE) {
-        s.first = A.get<uint32_t>((size_t)extent);
-        IBH_HIP(hipMemsetAsync(s.first, 0xFF, sizeof(uint32_t) * (size_t)extent, st));
-        nb.flag = A.get<uint32_t>((size_t)n + 1);
-        if (n) {
-            hipLaunchKernelGGL(k_hm_first, dim3(ceil_div(n, 256)), dim3(256), 0, st, s, key, stride, n);
-            hipLaunchKernelGGL(k_hm_newflag, dim3(ceil_div(n, 256)), dim3(256), 0, st, s, key, stride, n, nb.flag);
-        }
-        exclusive_scan_u32(nb.flag, nb.flag, (size_t)n, nb.flag + n, st);
-        s.rank = nb.flag;
-    }
-    IBH_HIP(hipGetLastError());
-    return nb;
-}
-// the set's grown dense -> sparse table (old entries, then the new keys first-seen); empty when it gains nothing.  The set takes
-// it (adopt_device) only once everything else has succeeded.
-static DevBuf<int64_t> hm_number_grow(HmNumber &nb, const int32_t *key, int stride, long n, uint32_t n_new, hipStream_t st) {
-    DevBuf<int64_t> grown;
-    if (!nb.set || nb.s.transform != IBH_ADD_DENSE || n_new == 0) return grown;
-    const int n_old = nb.s.n_old;
-    grown.alloc((size_t)n_old + n_new);
-    nb.set->copy_to_sparse(grown.p, n_old, st);
-    hipLaunchKernelGGL(k_hm_newkeys, dim3(ceil_div(n, 256)), dim3(256), 0, st, key, stride, n, nb.flag, grown.p + n_old);
-    IBH_HIP(hipGetLastError());
-    return grown;
-}
-
 static void hntr_matrix(const ibh_hntr *h, int kind, double eq_rad, const uint8_t *includeB, ibh_sparse_set *dimB, int tB,
                         ibh_sparse_set *dimA, int tA, int transpose, ibh_weighted **out) {
     IBH_CHECK(out != nullptr, "null argument");
@@ -810,7 +729,7 @@ static void hntr_matrix(const ibh_hntr *h, int kind, double eq_rad, const uint8_
     auto w = new_weighted();
     w->conservative = 1;
     w->scaled = kind == IBH_HNTR_SCALED;
-    HmNumber nbB, nbA;          // the fast path numbers nothing: the sets only take their sparse extent
+    KeyNumberingRun nbB, nbA;   // the fast path numbers nothing: the sets only take their sparse extent
     DevBuf<int64_t> grownB, grownA;
     if (fast) {
         w->nrow = (int32_t)nB; w->ncol = (int32_t)nA; w->nnz = n;
@@ -834,16 +753,16 @@ static void hntr_matrix(const ibh_hntr *h, int kind, double eq_rad, const uint8_
         uint32_t *keep = A.get<uint32_t>((size_t)n + 1), *bad = A.get<uint32_t>(1);
         uint8_t *act = A.get<uint8_t>((size_t)n);
         IBH_HIP(hipMemsetAsync(bad, 0, sizeof(uint32_t), st));
-        nbB = hm_number_prepare(dimB, nB, tB, iB, 1, (long)n, nullptr, st);
+        nbB = number_keys_prepare(dimB, nB, tB, iB, 1, (long)n, nullptr, false, st);
         if (n) hipLaunchKernelGGL(k_hm_gate, dim3(ceil_div(n, 256)), dim3(256), 0, st, nbB.s, iB, (long)n, act, bad);
-        nbA = hm_number_prepare(dimA, nA, tA, iA, 1, (long)n, act, st);
+        nbA = number_keys_prepare(dimA, nA, tA, iA, 1, (long)n, act, false, st);
         if (n) hipLaunchKernelGGL(k_hm_keep, dim3(ceil_div(n, 256)), dim3(256), 0, st, nbA.s, iA, (long)n, keep, bad);
         exclusive_scan_u32(keep, keep, (size_t)n, keep + n, st);
         struct { uint32_t kept, bad, newB, newA; } rb{0, 0, 0, 0};
         readback_sync(&rb.kept, keep + n, sizeof(uint32_t), st);
         readback_sync(&rb.bad, bad, sizeof(uint32_t), st);
-        if (nbB.flag) readback_sync(&rb.newB, nbB.flag + n, sizeof(uint32_t), st);
-        if (nbA.flag) readback_sync(&rb.newA, nbA.flag + n, sizeof(uint32_t), st);
+        if (nbB.adds()) readback_sync(&rb.newB, nbB.status, sizeof(uint32_t), st);
+        if (nbA.adds()) readback_sync(&rb.newA, nbA.status, sizeof(uint32_t), st);
         IBH_CHECK(!rb.bad, "Hntr matrix_d: a key is missing from a TO_DENSE set");
         const int nrowB = (nbB.set ? nbB.s.n_old : (int)nB) + (int)rb.newB;
         const int ncolA = (nbA.set ? nbA.s.n_old : (int)nA) + (int)rb.newA;
@@ -854,8 +773,8 @@ static void hntr_matrix(const ibh_hntr *h, int kind, double eq_rad, const uint8_
         IBH_HIP(hipGetLastError());
         weighted_from_device_triplets(w.get(), transpose ? ncolA : nrowB, transpose ? nrowB : ncolA, rb.kept, row, col, val, st);
         // both grown tables exist before either set changes: an error up to here leaves both sets as they were
-        grownB = hm_number_grow(nbB, iB, 1, (long)n, rb.newB, st);
-        grownA = hm_number_grow(nbA, iA, 1, (long)n, rb.newA, st);
+        grownB = number_keys_grow(nbB, iB, 1, (long)n, rb.newB, st);
+        grownA = number_keys_grow(nbA, iA, 1, (long)n, rb.newA, st);
         IBH_HIP(hipStreamSynchronize(st));
     }
     // the fresh identities first (they allocate), then the caller's sets take their tables: that cannot fail
@@ -904,7 +823,7 @@ static void hntr_triplets(const ibh_hntr *h, int kind, double eq_rad, const uint
 //   count     TPR lanes per B cell (grid-stride): the cell's kept terms (mask reads only), cnt[r]; a 64-bit grand total
 //   scan      prims' exclusive scan of cnt (only once the total is known to fit in int32)
 //   fill      TPR lanes per B cell: the terms in stream order, TPR at a time; a ballot over the team ranks the kept ones
-//   dims      dimA = the cells with cnt > 0 (a flag scan); dimI = ice cells first-seen in stream order (as k_hm_first)
+//   dims      dimA = the cells with cnt > 0 (a flag scan); dimI = ice cells first-seen in stream order (sparseset.h)
 constexpr int HX_T = 256;
 __global__ __launch_bounds__(HX_T) void k_hx_count(HmArgs a, const double *__restrict__ mask, int TPR, uint32_t *__restrict__ cnt,
                                                    unsigned long long *__restrict__ total) {
@@ -1131,9 +1050,9 @@ static void regridder_create_hntr(const ibh_hntr_regridder_desc *d, ibh_sparse_s
     uint32_t nId = 0;
     if (dimI_out) {
         const int32_t *iI = reinterpret_cast<const int32_t *>(idx) + 1;
-        HmNumber nb = hm_number_prepare(dimI_out, nI, IBH_ADD_DENSE, iI, 2, (long)nX, nullptr, st);
-        readback_sync(&nId, nb.flag + nX, sizeof(nId), st);
-        dI = hm_number_grow(nb, iI, 2, (long)nX, nId, st);
+        const KeyNumberingRun nb = number_keys_prepare(dimI_out, nI, IBH_ADD_DENSE, iI, 2, (long)nX, nullptr, false, st);
+        readback_sync(&nId, nb.status, sizeof(nId), st);
+        dI = number_keys_grow(nb, iI, 2, (long)nX, nId, st);
     }
     IBH_HIP(hipGetLastError());
     // agridA on the host: make_abbr_grid's areas (GridGen_LonLat.cpp:234-275) from make_grid_spec(hspecA, false)

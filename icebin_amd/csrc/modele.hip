@@ -5,7 +5,8 @@
 // the vector scalings are csrops.hip's, ModelE's two weight vectors kernels below.  The bookkeeping of the GCM-grid-sized SETS (dimAOp -> dimAOm, dimEOm, dimEAm: at
 // most nO * nhc keys) runs on the host, where ibh_sparse_set keeps its keys: it reads the sets' keys, the INDICES of EOpvAOp
 // (one entry per elevation class of an ice-bearing O cell) and, for raw_EOvEA's "weight != 0" test, the vector wEOm.  No
-// entry of an ice-sized matrix travels to the host.
+// entry of an ice-sized matrix travels to the host.  (So the add_dense_host loops below stay host loops, not sparseset.h's
+// device numbering: moving them is a performance change of its own.)
 #include <algorithm>
 #include <cmath>
 #include <memory>
@@ -160,17 +161,16 @@ void compute_EOmvAOm_unscaled(const ibh_weighted &EOpvAOp, const ibh_sparse_set 
 
 std::unique_ptr<ibh_weighted> raw_EOvEA(const ibh_hntr *hntr, double eq_rad, const std::vector<uint8_t> &includeO,
                                         const ibh_sparse_set &dimEOm, const DevBuf<double> &wEOm, const std::vector<double> &wEOm_h,
-                                        int32_t nhc, int64_t sA_O, int64_t sHC_O, int64_t sA_A, int64_t sHC_A, ibh_sparse_set &dimEAm,
-                                        hipStream_t st) {
+                                        int32_t nhc, HcIndexing hcO, HcIndexing hcA, ibh_sparse_set &dimEAm, hipStream_t st) {
     const HostTriplets s = hntr_overlap_triplets(hntr, eq_rad, includeO.data());
     std::vector<int32_t> trow, tcol;
     for (size_t p = 0; p < s.v.size(); ++p) {
         if (std::abs(s.v[p]) < 1e-8) fail(IBH_EINVAL, "Found a stray overlap; what should we do about it?");
         for (int ihc = 0; ihc < nhc; ++ihc) {
-            const int dEO = dimEOm.to_dense(s.iB[p] * sA_O + ihc * sHC_O);
+            const int dEO = dimEOm.to_dense(hcO.index(s.iB[p], ihc));
             if (dEO < 0 || wEOm_h[(size_t)dEO] == 0) continue;
             trow.push_back(dEO);
-            tcol.push_back(dimEAm.add_dense_host(s.iA[p] * sA_A + ihc * sHC_A));
+            tcol.push_back(dimEAm.add_dense_host(hcA.index(s.iA[p], ihc)));
         }
     }
     const long ne = (long)trow.size();
@@ -219,8 +219,8 @@ void modele_matrix(const ibh_modele_matrices *mm, char gridX, char gridG, bool X
             compute_EOmvAOm_unscaled(*EOpvAOp, dimEOp2, dimAOp2, dimAOm, wAOm, nO * mm->nhc, dimEOm, nullptr, nullptr, wEOm, wEOm_h, st);
         }
         wXOm = wEOm.p;
-        XOmvXAm = raw_EOvEA(mm->hntr, mm->eq_rad, includeO, dimEOm, wEOm, wEOm_h, mm->nhc, mm->sA_O, mm->sHC_O, mm->sA_A, mm->sHC_A,
-                            dimXAm, st);
+        XOmvXAm = raw_EOvEA(mm->hntr, mm->eq_rad, includeO, dimEOm, wEOm, wEOm_h, mm->nhc, HcIndexing{mm->sA_O, mm->sHC_O},
+                            HcIndexing{mm->sA_A, mm->sHC_A}, dimXAm, st);
     } else {
         XOpvIp = o_matrix(mm, nameXvG, &dimAOp, &dimGp, 0);
         IBH_HIP(hipStreamSynchronize(st));

@@ -1,7 +1,7 @@
 // modele_parts.h -- the topo.cpp helpers (slib/icebin/modele/topo.cpp:50-240) that both ModelE matrix makers compose: the
 // per-sheet matrices of modele.hip (GCMRegridder_ModelE::regrid_matrices) and the global AvE of globalave.hip
 // (_compute_AAmvEAm_EIGEN).  Defined in modele.hip.  Each takes what it works on as arguments: the weights and the sets of
-// a given EOpvAOp, the elevation-class count and the strides of the two indexingHC.  Where the work lives is DESIGN.md 15:
+// a given EOpvAOp, the elevation-class count and the two indexingHC.  Where the work lives is DESIGN.md 15:
 // the keys of the GCM-grid-sized sets on the host, every matrix entry and weight on the device.
 #pragma once
 #include <memory>
@@ -33,12 +33,11 @@ void compute_EOmvAOm_unscaled(const ibh_weighted &EOpvAOp, const ibh_sparse_set 
                               hipStream_t st);
 
 // raw_EOvEA (topo.cpp:112-204), by its columns: Hntr's O -> A overlap clipped by includeO (DimClip(dimAOm)), every entry
-// expanded over nhc elevation classes through the strides of indexingHCO / indexingHCA; numbers dimEAm.  IBH_EINVAL for an
+// expanded over nhc elevation classes through indexingHCO / indexingHCA; numbers dimEAm.  IBH_EINVAL for an
 // overlap below 1e-8 in magnitude.  Synchronises st.
 std::unique_ptr<ibh_weighted> raw_EOvEA(const ibh_hntr *hntr, double eq_rad, const std::vector<uint8_t> &includeO,
                                         const ibh_sparse_set &dimEOm, const DevBuf<double> &wEOm, const std::vector<double> &wEOm_h,
-                                        int32_t nhc, int64_t sA_O, int64_t sHC_O, int64_t sA_A, int64_t sHC_A, ibh_sparse_set &dimEAm,
-                                        hipStream_t st);
+                                        int32_t nhc, HcIndexing hcO, HcIndexing hcA, ibh_sparse_set &dimEAm, hipStream_t st);
 
 // y = (M * diag(d)) * w: y[r] = sum over the row's columns k ascending, from 0, of (M(r, k) * d[k]) * w[k]
 void scaled_matvec(const ibh_weighted &M, const double *d, const double *w, double *y, hipStream_t st);

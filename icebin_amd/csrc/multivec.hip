@@ -242,6 +242,7 @@ struct Grouped {
 // prefix: n0 keys on the device (a set's dense -> sparse table) sorted in front of the multivec's; limit: the multivec's indices
 // must lie in [0, limit).  Synchronises `st` once (the range check and the key width of the sort come from one read-back).
 // report_missing / isnew: see k_mv_heads.
+// (Sort-based, not sparseset.h's table numbering, on purpose: a multivec's set may have an unbounded sparse extent.)
 static Grouped group_entries(const ibh_multivec *mv, const int64_t *prefix, uint32_t n0, int64_t limit, const char *what,
                              int report_missing, uint8_t *isnew, hipStream_t st) {
     Arena &A = arena();

@@ -352,8 +352,7 @@ __global__ void k_topoa_init3(double *__restrict__ fhc, double *__restrict__ ele
 
 // Segment 0 (:706-731): one thread per row of AAmvEAm (an A cell: at most nhc entries).  An entry of the matrix is unique,
 // so its cell of fhc receives one add onto 0.  A bad entry is not written anywhere; the smallest bad entry is reported.
-struct HcStrides { int64_t sA, sHC; };
-__global__ void k_topoa_classes(Csr M, const int64_t *__restrict__ tsA, const int64_t *__restrict__ tsE, HcStrides s, int32_t nhc, int64_t nA,
+__global__ void k_topoa_classes(Csr M, const int64_t *__restrict__ tsA, const int64_t *__restrict__ tsE, HcIndexing s, int32_t nhc, int64_t nA,
                                 const int16_t *__restrict__ underice_hc, double *__restrict__ fhc, int16_t *__restrict__ underice,
                                 uint32_t *__restrict__ bad) {
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
@@ -362,8 +361,7 @@ __global__ void k_topoa_classes(Csr M, const int64_t *__restrict__ tsA, const in
     for (int e = M.rowptr[r]; e < M.rowptr[r + 1]; ++e) {
         const int64_t iE = tsE[M.colind[e]];
         int64_t iA2, ihc;
-        if (s.sHC >= s.sA) { ihc = iE / s.sHC; iA2 = (iE % s.sHC) / s.sA; }
-        else { iA2 = iE / s.sA; ihc = (iE % s.sA) / s.sHC; }
+        s.split(iE, iA2, ihc);
         if (iA2 != iA || ihc < 0 || ihc >= nhc || iA < 0 || iA >= nA) { atomicMin(bad, (uint32_t)e); continue; }
         fhc[ihc * nA + iA] += M.val[e];
         underice[ihc * nA + iA] = underice_hc[ihc];
@@ -428,7 +426,7 @@ __global__ void k_topoa_levels(PlanesA P, const double *__restrict__ hcdefs, int
 struct TopoAArgs {
     int32_t imO, jmO, imA, jmA, nhc;
     double offiO, dlatO, offiA, dlatA;
-    int64_t sA, sHC;
+    HcIndexing hc;          // indexingHCA
     const double *hcdefs;
     const int16_t *underice_hc;
     const ibh_weighted *AAmvEAm;
@@ -437,7 +435,7 @@ struct TopoAArgs {
 void check_topoA_args(const TopoAArgs &t) {
     IBH_CHECK(t.imO > 0 && t.jmO > 0 && t.imA > 0 && t.jmA > 0, "make_topoA: the grids are %d x %d and %d x %d", t.imO, t.jmO, t.imA, t.jmA);
     IBH_CHECK(t.nhc >= 0 && (t.nhc == 0 || (t.hcdefs && t.underice_hc)), "make_topoA: nhc=%d or null hcdefs / underice_hc", t.nhc);
-    IBH_CHECK(t.sA > 0 && t.sHC > 0, "make_topoA: indexingHCA strides (%lld,%lld) must be positive", (long long)t.sA, (long long)t.sHC);
+    IBH_CHECK(t.hc.sA > 0 && t.hc.sHC > 0, "make_topoA: indexingHCA strides (%lld,%lld) must be positive", (long long)t.hc.sA, (long long)t.hc.sHC);
     IBH_CHECK(t.AAmvEAm != nullptr, "make_topoA: null AAmvEAm");
     check_current_device(t.AAmvEAm->device, "AAmvEAm");
     IBH_CHECK((int64_t)(t.nhc + 1) * t.imA * t.jmA < (1ll << 31), "make_topoA: %d classes of %d x %d cells overflow int32", t.nhc + 1, t.imA, t.jmA);
@@ -458,8 +456,7 @@ void check_topoA_args(const TopoAArgs &t) {
     while (r + 1 < M.nrow && (uint32_t)rp[(size_t)r + 1] <= e) ++r;
     const int64_t iA = M.dims[0]->to_sparse_host()[r], iE = M.dims[1]->to_sparse_host()[col];
     int64_t iA2, ihc;
-    if (t.sHC >= t.sA) { ihc = iE / t.sHC; iA2 = (iE % t.sHC) / t.sA; }
-    else { iA2 = iE / t.sA; ihc = (iE % t.sA) / t.sHC; }
+    t.hc.split(iE, iA2, ihc);
     const int64_t nA = (int64_t)t.imA * t.jmA;
     if (iA2 != iA) fail(IBH_EINVAL, "make_topoA: Matrix is non-local: iA=%ld, iE=%ld, iA2=%ld", (long)iA, (long)iE, (long)iA2);
     if (ihc < 0 || ihc >= t.nhc) fail(IBH_EINVAL, "make_topoA: ihc out of range [0,%d): %ld (iA=%ld, iE=%ld)", t.nhc, (long)ihc, (long)iA, (long)iE);
@@ -512,7 +509,7 @@ int64_t make_topoA(const TopoAArgs &t, const double *const *O, const int16_t *me
     IBH_HIP(hipGetLastError());
     if (M.nrow && M.nnz) {
         const int64_t *tsA = M.dims[0]->device_to_sparse(M.nrow, st), *tsE = M.dims[1]->device_to_sparse(M.ncol, st);
-        hipLaunchKernelGGL(k_topoa_classes, dim3((unsigned)ceil_div(M.nrow, T)), dim3(T), 0, st, view(M), tsA, tsE, HcStrides{t.sA, t.sHC}, nhc,
+        hipLaunchKernelGGL(k_topoa_classes, dim3((unsigned)ceil_div(M.nrow, T)), dim3(T), 0, st, view(M), tsA, tsE, t.hc, nhc,
                            (int64_t)nA, dui.p, fhc, underice, status);
         IBH_HIP(hipGetLastError());
     }
@@ -599,7 +596,7 @@ int ibh_modele_make_topoA_device(const double *const *d_planesO, const int16_t *
                                  double *const *d_planesA, int16_t *d_mergemaskA, double *d_fhc3, double *d_elevE3, int16_t *d_underice3,
                                  uint32_t *d_flags, int64_t *nerrors, void *stream) {
     return guarded([&] {
-        const TopoAArgs t{imO, jmO, imA, jmA, nhc, offiO, dlatO, offiA, dlatA, hc_stride_A, hc_stride_HC, hcdefs, underice_hc, AAmvEAm};
+        const TopoAArgs t{imO, jmO, imA, jmA, nhc, offiO, dlatO, offiA, dlatA, HcIndexing{hc_stride_A, hc_stride_HC}, hcdefs, underice_hc, AAmvEAm};
         check_topoA_args(t);
         check_planes(reinterpret_cast<const void *const *>(d_planesO), NP_A, "make_topoA: O");
         check_planes(reinterpret_cast<const void *const *>(d_planesA), NP_A, "make_topoA: A");
@@ -617,7 +614,7 @@ int ibh_modele_make_topoA(const double *const *planesO, const int16_t *mergemask
                           const int16_t *underice_hc, int32_t nhc, const ibh_weighted *AAmvEAm, double *const *planesA, int16_t *mergemaskA,
                           double *fhc3, double *elevE3, int16_t *underice3, uint32_t *flags, int64_t *nerrors) {
     return guarded([&] {
-        const TopoAArgs t{imO, jmO, imA, jmA, nhc, offiO, dlatO, offiA, dlatA, hc_stride_A, hc_stride_HC, hcdefs, underice_hc, AAmvEAm};
+        const TopoAArgs t{imO, jmO, imA, jmA, nhc, offiO, dlatO, offiA, dlatA, HcIndexing{hc_stride_A, hc_stride_HC}, hcdefs, underice_hc, AAmvEAm};
         check_topoA_args(t);
         check_planes(reinterpret_cast<const void *const *>(planesO), NP_A, "make_topoA: O");
         check_planes(reinterpret_cast<const void *const *>(planesA), NP_A, "make_topoA: A");

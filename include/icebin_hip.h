@@ -901,6 +901,21 @@ int ibh_selftest_radix_sort(const uint64_t *keys, int64_t n, const int32_t *fiel
  * the flags-only analysis followed by the radix sort it plans (the low field is skipped when it never decreases). */
 int ibh_selftest_order(const uint64_t *keys, int64_t n, int lo_bits, int hi_bits, int try_pieces, uint32_t *perm_out,
                        uint32_t *info_out, int *path_out);
+/* Diagnostic of the first-seen numbering of a key stream (sparseset.hip), as the Hntr matrices, global_ec and the global AvE
+ * use it; host buffers in and out.  Used by tests/test_gpu_numbering.py.  The key of stream position p is keys[p * stride],
+ * key_bytes 4 (int32) or 8 (int64); act (may be NULL): one byte per position, 0 = the numbering does not see it.  The old
+ * set over [0, extent): n_old = -1 no set (the identity over the whole extent, which nothing can grow), else n_old entries,
+ * the identity prefix (identity = 1) or to_sparse[n_old].  transform: IBH_ADD_DENSE, IBH_TO_DENSE or
+ * IBH_TO_DENSE_IGNORE_MISSING.  check_range = 1: keys outside [0, extent) are skipped on the device and reported;
+ * 0: such a key is IBH_EINVAL.  dense_out[n]: the dense id of every position, -1 where it is not seen, missing or out of
+ * range; table_out (a set is given: room for n_old + min(n, extent) entries): the set's dense -> sparse table afterwards,
+ * n_old + *n_new_out entries; *status_out: the IBH_NUMBER_KEYS_* bits (with OUT_OF_RANGE nothing is added, as a build
+ * fails there). */
+#define IBH_NUMBER_KEYS_OUT_OF_RANGE  1u    /* check_range: a key outside [0, extent) */
+#define IBH_NUMBER_KEYS_MISSING       2u    /* IBH_TO_DENSE: a key the set lacks */
+int ibh_selftest_number_keys(const void *keys, int key_bytes, int stride, int64_t n, const uint8_t *act, int64_t extent,
+                             const int64_t *to_sparse, int32_t n_old, int identity, int transform, int check_range,
+                             int32_t *dense_out, int64_t *table_out, int32_t *n_new_out, uint32_t *status_out);
 /* Return the build workspaces of ALL host threads (the caller's and the library's worker threads') and
  * all cached device blocks to the driver (the library keeps freed device memory for reuse: a coupler
  * rebuilds the same matrices every step).  Call it while no build is in flight. */

@@ -250,6 +250,28 @@ def test_selftest_order_rejects_bad_arguments(lib):
     assert lib.ibh_selftest_order(k.ctypes.data, 2, 20, 12, 2, perm.ctypes.data, info.ctypes.data, C.byref(path)) == _capi.IBH_EINVAL
 
 
+def test_selftest_number_keys_rejects_bad_arguments(lib):
+    import ctypes as C
+    import numpy as np
+    keys, ts = np.asarray([1, 2, 3, 0], np.int64), np.asarray([2, 0], np.int64)
+    dense, table, n_new, status = np.zeros(4, np.int32), np.zeros(16, np.int64), C.c_int32(0), C.c_uint32(0)
+
+    def call(key_bytes=8, stride=1, n=4, extent=8, to_sparse=ts.ctypes.data, n_old=2, identity=0, transform=0, check_range=0,
+             k=keys.ctypes.data, d=dense.ctypes.data, t=table.ctypes.data, nn=C.byref(n_new), s=C.byref(status)):
+        return lib.ibh_selftest_number_keys(k, key_bytes, stride, n, None, extent, to_sparse, n_old, identity, transform, check_range, d, t, nn, s)
+
+    for bad in (dict(key_bytes=2), dict(key_bytes=16), dict(stride=0), dict(stride=-1), dict(n=-1), dict(n=1 << 31), dict(extent=-1),
+                dict(extent=1 << 31), dict(transform=3), dict(transform=-1), dict(n_old=-2), dict(n_old=9), dict(identity=2),
+                dict(check_range=2), dict(k=None), dict(d=None), dict(t=None), dict(nn=None), dict(s=None), dict(to_sparse=None),
+                dict(extent=3),                     # key 3 outside [0, 3) without the range check (the old set's entries lie inside)
+                dict(extent=2)):                    # ... and the old set's entry 2 outside its extent
+        assert call(**bad) == _capi.IBH_EINVAL, bad
+    dup = np.asarray([2, 2], np.int64)
+    assert call(to_sparse=dup.ctypes.data) == _capi.IBH_EINVAL
+    neg = np.asarray([1, -1, 3, 0], np.int64)
+    assert call(k=neg.ctypes.data) == _capi.IBH_EINVAL
+
+
 def assembly_kernel_name(mangled):
     """"_ZN3ibh9k_sa_emitILb1ELb0EjLi4EEEv..." -> "k_sa_emit<true, false, unsigned int, 4>": prims_kernel_name's spelling, with bool
     template arguments as well."""
