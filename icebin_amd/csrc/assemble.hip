@@ -17,6 +17,7 @@
 // no FMA contraction (this file is compiled with -ffp-contract=off), so the
 // CSR structure, dims, wM, Mw and M are bit-identical to the oracle.
 #include "assemble.h"
+#include "asm_plan.h"
 #include "csrops.h"
 #include "prims.h"
 #include "sparseset.h"
@@ -33,9 +34,7 @@
 
 namespace ibh {
 
-enum { LIST_AP = 0, LIST_I = 1, LIST_EP = 2 };
-enum { KEY_A = 0, KEY_I = 1, KEY_E = 2, KEY_X = 3 };
-enum { FAM_AEVI = 0, FAM_IVAE = 1, FAM_EVA = 2 };
+// (LIST_*, KEY_*, FAM_*: asm_plan.h)
 // contribution formulas: t = fl(fl(lhs * sinv) * rhs)
 enum { TERM_PLAIN_A = 0,   // a                       (AvX, XvA)
        TERM_PLAIN_E,       // vE                      (EvX, XvE)
@@ -2229,9 +2228,63 @@ RowGroups build_groups_from_csr(const ibh_weighted *w, hipStream_t st) {
 #include "fastasm.inl"
 #include "streamasm.inl"
 
+// ---- the sorted-grid builds: facts -> plan_build (asm_plan.h) -> the plan's candidate paths in order ----------------------------
+// The only place that reads the handles for a decision.  (The sheet's static plan is made here, by the first build that wants it.)
+static BuildFacts facts_of_build(const ibh_regrid_matrices *rm, const MatSpec *sp, ibh_sparse_set *const dims[2], bool smooth, bool bands_wanted,
+                                 ibh_comm *comm, hipStream_t st) {
+    const ibh_regridder *gr = rm->rg;
+    BuildFacts f;
+    f.family = sp->family; f.row_key = sp->row_key; f.col_key = sp->col_key; f.row_list = sp->row_list; f.col_list = sp->col_list;
+    f.nX = gr->nX; f.nI = gr->nI; f.nhc = gr->nhc;
+    for (int k = 0; k < 2; ++k) {
+        const ibh_sparse_set *s = dims[k];
+        f.set[k].extent = key_extent(gr, k == 0 ? sp->row_key : sp->col_key);
+        if (s) { f.set[k].n = s->n(); f.set[k].identity = s->identity(); }
+    }
+    f.same_set = dims[0] == dims[1];
+    f.smooth = smooth; f.bands_wanted = bands_wanted;
+    f.shared = comm != nullptr; f.world = comm ? comm_world(comm) : 1;
+    f.plan_ok = fast_path_wanted(f) && ensure_plan(gr, st);
+    if (f.plan_ok) {
+        const ibh_plan &P = gr->plan;
+        f.nAr = P.nAr; f.nmulti = P.nmulti; f.nmulti3 = P.nmulti3; f.npair = P.npair; f.maxrange = P.maxrange;
+        f.tiny = P.tiny; f.icnt_pos = P.icnt_pos.p != nullptr; f.icnt_nz = P.icnt_nz.p != nullptr;
+    }
+    return f;
+}
+// Batch builds (assemble_batch): everything a concurrent fast build would otherwise create lazily in shared objects --
+// the sheet's plan, the inverse table of a pre-populated column set -- is created up front on the calling thread.
+static void fast_prewarm(const ibh_regrid_matrices *rm, const MatSpec *sp, ibh_sparse_set *dims[2], hipStream_t st) {
+    const BuildPlan bp = plan_build(facts_of_build(rm, sp, dims, false, false, nullptr, st));
+    if (!bp.prepop_table) return;
+    (void)dims[1]->device_to_dense(bp.roles.gext, st);
+    IBH_HIP(hipStreamSynchronize(st));
+}
+// returns the path that built the matrix; PATH_GENERAL: none did (nothing has been touched: the caller runs the general pipeline)
+static BuildPath fast_build(const ibh_regrid_matrices *rm, const MatSpec *sp, const BuildPlan &bp, ibh_sparse_set *dims[2], int scale, int correctA,
+                            const RgView &rg, ibh_weighted *w, hipStream_t st, ibh_comm *comm) {
+    const Roles &role = bp.roles;
+    const FaSets sets{dims[role.g_is_row ? 0 : 1], dims[role.g_is_row ? 1 : 0]};
+    for (int k = 0; k < bp.npath; ++k) {
+        const BuildPath path = bp.path[k];
+        bool built = false;
+        if (path == PATH_EVA) built = fast_build_eva(rm, sp, bp.range, dims, scale, correctA, rg, w, st);
+        else if (path == PATH_STREAM_SHARED || path == PATH_STREAM) {
+            const StreamPlan &s = path == PATH_STREAM ? bp.stream : bp.stream_shared;
+            ibh_comm *c = path == PATH_STREAM ? nullptr : comm;
+            built = role.EP ? stream_build<true>(rm, sp, role, sets, s, scale, correctA, rg, w, st, c)
+                            : stream_build<false>(rm, sp, role, sets, s, scale, correctA, rg, w, st, c);
+        } else if (path == PATH_RANGE)
+            built = role.EP ? fast_build_gp<true>(rm, sp, role, sets, bp.range, scale, correctA, rg, w, st)
+                            : fast_build_gp<false>(rm, sp, role, sets, bp.range, scale, correctA, rg, w, st);
+        if (built) return path;
+    }
+    return PATH_GENERAL;
+}
+
 bool elevmask_classes(const ibh_regrid_matrices *rm, hipStream_t stream, const double *d_src) {
     const ibh_regridder *gr = rm->rg;
-    if (gr->nhc > 64 || !get_tuning("assemble_stream", gr->nX >= (1l << 20) ? 1 : 0)) return false;      // (not a grid of the streamed build: the first build that wants the bytes makes them)
+    if (gr->nhc > 64 || !stream_default(gr->nX)) return false;      // (not a grid of the streamed build: the first build that wants the bytes makes them)
     elevmask_classes_impl(rm, stream, d_src);
     return true;
 }
@@ -2272,18 +2325,20 @@ bool assemble_matrix(const ibh_regrid_matrices *rm, const char *spec_name, ibh_s
     }
     w->conservative = 1;              // :63, :167 (no smoothing), :258
     w->scaled = scale;                // :421
-    if (sp->row_key == KEY_E && (sp->col_key == KEY_I || sp->col_key == KEY_X)) {       // EvI, EvX: bands may be built later (ensure_bands)
+    if (band_eligible(sp->row_key, sp->col_key)) {       // EvI, EvX: bands may be built later (ensure_bands)
         w->band_eligible = 1; w->band_sA = g->hc_stride_A; w->band_sHC = g->hc_stride_HC;
     }
 
     // sorted exchange grid + dims shapes it covers: the plan-based fast path (fastasm.inl); smoothing and the
     // band structure work on intermediates of the general pipeline
-    const bool bands_wanted = sp->row_key == KEY_E && (sp->col_key == KEY_I || sp->col_key == KEY_X) && get_tuning("assemble_bands", 0);
+    const bool bands_wanted = bands_at_build(sp->row_key, sp->col_key);
     // A SHARED smoothed build (comm): the unsmoothed matrix from the shared build -- the same bits as the general pipeline's --
     // then the smoothing, shared as well, over the row cells of its own row set
     if (smooth && comm) smooth_check(rm, sigma);
-    if ((!smooth || comm) && !bands_wanted && fast_build(rm, sp, dims, scale, correctA, rg, w.get(), st, comm)) {
-        if (!w->built_fast) w->built_fast = 1;          // (2: the streamed build, set by stream_build)
+    const BuildPath built = fast_build(rm, sp, plan_build(facts_of_build(rm, sp, dims, smooth, bands_wanted, comm, st)), dims, scale, correctA, rg,
+                                       w.get(), st, comm);
+    if (built != PATH_GENERAL) {
+        w->built_fast = built == PATH_EVA ? (int)PATH_RANGE : (int)built;
         if (smooth) {
             w->built_fast = 1;                          // (3 again when the smoothing is shared as well)
             smooth_matrix(w.get(), rm, dims[0]->device_to_sparse(w->nrow, st), sigma, st, comm);
@@ -2381,11 +2436,8 @@ bool assemble_matrix(const ibh_regrid_matrices *rm, const char *spec_name, ibh_s
     IBH_HIP(hipGetLastError());
     if (smooth) smooth_matrix(w.get(), rm, rset.to_sparse, sigma, st, comm);
     // E-row matrices over ice / exchange columns: band structure for the apply (after the scaling: exact
-    // copies of M).  Opt-in (ibh_set_tuning("assemble_bands", 1)): it costs +25-35 % of the build and
-    // buys -16 % on a 1 km apply, nothing at 5 km -- right for a matrix that is applied to many field
-    // batches, wrong for the coupler's one build : one apply per step.
-    const bool want_bands = sp->row_key == KEY_E && (sp->col_key == KEY_I || sp->col_key == KEY_X) && colptr != nullptr &&
-                            ncol < (1 << 28) && get_tuning("assemble_bands", 0);
+    // copies of M), when asked for (bands_at_build)
+    const bool want_bands = bands_wanted && colptr != nullptr && ncol < (1 << 28);
     uint32_t nband_entries = 0;
     if (want_bands) {
         uint32_t *d_nb = A.get<uint32_t>(1);

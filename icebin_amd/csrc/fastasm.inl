@@ -14,7 +14,7 @@
 // segment sums + column slots (~45 launches):
 //   numbering  first-occurrence flags (written by k_fa_count) -> scan       (ice / exchange keys; skipped for identity dims)
 //              k_fa_count (one workgroup per range; one-class matrices of large grids: k_fa_count_stream, a thread per
-//              cell) -> k_fa_rscan / fa_rscan_many                          (A / E keys, entry counts)
+//              cell) -> k_fa_rscan / fa_scan_ranges                         (A / E keys, entry counts)
 //   A/E rows   k_fa_range<EMIT>: every entry is written straight to its CSR slot -- inside a row the
 //              columns first seen in this range ascend in x order (rank = a per-class running count),
 //              only the ice cells that straddle in from an earlier range (a few %) are ranked in LDS --
@@ -32,11 +32,9 @@
 // (fa_publish); independent work rides in extra workgroups of launches that exist anyway (the straddlers' column sums in
 // k_fa_range's, the static row lengths of the identity ice set in k_fa_count's) -- a G-row build is k_fa_count -> k_fa_range.
 
-constexpr int FA_NC = 64;           // elevation classes per range (nhc <= 64)
 constexpr int FA_ILMAX = 8;         // exchange cells per ice cell
 constexpr int FA_DUPMAX = 4;        // consecutive cells with the same (iA, iI)
 constexpr int FA_OLDMAX = 512;      // straddling entries of one range ranked in LDS
-constexpr int FA_T = 256;          // threads per workgroup of the per-element kernels (the per-range kernels: fa_range_shape)
 enum { FA_ERR_OLDOVER = 1, FA_ERR_MISSING = 2 };
 
 struct PlanView {
@@ -410,7 +408,6 @@ __device__ __forceinline__ uint32_t fa_block_excl_scan(uint32_t v, uint32_t *s_w
     __syncthreads();
     return wbase + inc - v;
 }
-constexpr int FA_CH_NP = 21, FA_CH_NE = 22, FA_CH_NC = 15;
 // Exclusive prefix of `mine` (<= 58 bits, fields that cannot overflow) over the workgroups before r; every thread of the workgroup
 // calls it and gets the same value.  One round looks at T predecessors at once -- at 5 km every range sees all the others in one.
 template <int T>
@@ -867,18 +864,6 @@ __global__ __launch_bounds__(1024) void k_fa_rscan_apply(const uint32_t *__restr
         if (i < nAr) out[i] = ex;
         if (i == nAr - 1) out[nAr] = (ch == 2 ? tot_a : tot + ch)[0];
     }
-}
-// launches the three; false when there are too many ranges for one workgroup of tile sums (the caller scans channel by channel)
-static bool fa_rscan_many(const FaG &g, int nAr, uint32_t *abase, uint32_t *tot, uint32_t *tot_a, hipStream_t st) {
-    const int nb = ceil_div(nAr, 1024);
-    if (nb > 1024) return false;
-    const int nch = abase ? 3 : 2;
-    uint32_t *sums = arena().get<uint32_t>((size_t)nch * nb);
-    hipLaunchKernelGGL(k_fa_rscan_tiles, dim3(nb), dim3(1024), 0, st, g.r_ncls, g.r_nent, nAr, nch, sums);
-    hipLaunchKernelGGL(k_fa_rscan_sums, dim3(1), dim3(1024), 0, st, sums, nb, nch, tot, tot_a);
-    hipLaunchKernelGGL(k_fa_rscan_apply, dim3(nb), dim3(1024), 0, st, g.r_ncls, g.r_nent, nAr, nch, (const uint32_t *)sums, (const uint32_t *)tot,
-                       (const uint32_t *)tot_a, g.gbase, g.ebase, abase);
-    return true;
 }
 __device__ __forceinline__ int fa_gdense(const FaG &g, int r, int cls, long gkey) {
     if (g.tab) return g.tab[gkey];
@@ -1425,64 +1410,49 @@ __global__ void k_fa_zero_identity(double *__restrict__ w, long n) {
 }
 
 // ---- host side --------------------------------------------------------------------------------------
-// Which dims shapes the fast path serves: a G set (A / E) that is fresh or -- E columns only -- pre-populated
-// (the coupler's shared dimE); a P set (I / X) that is fresh or the identity over the whole extent.
-static int fa_pset_mode(const ibh_sparse_set *set, int64_t extent) {       // 1 fresh, 0 identity-complete, -1 unsupported
-    if (set->n() == 0) return 1;
-    if (set->identity() && set->n() == extent) return 0;
-    return -1;
+// Which dims shapes the fast path serves (plan_build, asm_plan.h): a G set (A / E) that is fresh or -- E columns only --
+// pre-populated (the coupler's shared dimE); a P set (I / X) that is fresh or the identity over the whole extent.
+struct FaSets { ibh_sparse_set *g, *p; };      // the two sets of a G/P build, by role (Roles)
+static PlanView plan_view(const ibh_plan &P, bool static_count) {
+    return PlanView{P.arng.p, P.aidx.p, P.ilptr.p, P.ilist.p, P.ifirst.p, P.isdup.p, P.mlist.p, P.nAr, P.nmulti,
+                    static_count ? P.icnt_pos.p : nullptr, P.icnt_nz.p, P.exI.p};
 }
-
-// The two sides of a matrix of the G/P builds (every family but EvA): G = the A / E side, counted and numbered by the ranges;
-// P = the I / X side, an element of which sees at most a few exchange cells
-struct FaRoles {
-    bool g_is_row;                  // AvI, EvI, AvX, EvX: G is the row side
-    ibh_sparse_set *gset, *pset;
-    int gkey, glist, pkey, plist;
-    int64_t gext, pext;             // the sparse extents of the two keys
-    int pmode;                      // fa_pset_mode of the P set
-    bool g_fresh;                   // the G set is numbered by this build; else pre-populated (E columns)
-    int merge;                      // 1: neither side is X, entries of the same (G, P) pair merge
-};
 __global__ void k_fa_init(uint32_t *cnt) {
     if (threadIdx.x < 8) cnt[threadIdx.x] = threadIdx.x == 0 ? 0xffffffffu : 0u;
 }
 
-// Workgroup shape of the two per-range kernels, by the size of the ranges.  One workgroup owns one range; what bounds it is
-// latency (staged load rounds, ranking barriers, the sequential sums of one wave per class), so the chip wants many small
-// workgroups when there are many small ranges and few large ones otherwise.  Measured (ms per build, AvI / EvI):
-//   Antarctica 1 km x 1/2 deg (49 771 ranges of ~780 cells): 256 x 4 cells 1.53 / 2.10, 256 x 2 1.40 / 1.92, 128 x 2 1.26 / 1.74,
-//                                                            128 x 4 1.33 / 1.87, 64 x 4 1.32 / 2.12, 64 x 2 1.38 / 2.22
-//   1 km (553 ranges of ~7 900 cells):                       128 x 2 0.30 / 0.44, 256 x 4 0.24 / 0.32, 1024 x 4 0.34 / 0.37
-//   5 km (122 ranges of ~1 500: fewer workgroups than CUs):  128 x 2 0.096 / 0.142, 256 x 4 0.082 / 0.109, 1024 x 4 0.076 / 0.089
-// Round 5, the synthetic 5 km grid of the tests (252 ranges of ~720 cells; us per build AvI / EvI / IvE / XvE): 256 x 4 64.8 / 94.3 /
-// 115.0 / 89.8, 1024 x 4 58.6 / 75.8 / 97.9 / 74.2, 1024 x 1 54.6 / 68.8 / 92.6 / 69.5; 20 km (60 ranges of ~240): 256 x 4 46.0 / 68.2 /
-// 84.1 / 63.4, 1024 x 4 54.5 / 69.5 / 88.0 / 68.0, 1024 x 1 46.2 / 62.5 / 80.3 / 60.1 -- with fewer workgroups than the chip holds, one
-// cell per thread: the per-thread loops over the cells of a pass are what a range's workgroup spends its time in.
-// shape 0: 128 threads x 2 cells, 1: 256 x 4, 2: 1024 x 4, 3: 1024 x 1 (tuning "assemble_range_shape" overrides; scratch/asm_shapes.py)
-static int fa_range_shape(long nX, int nAr) {
-    const int forced = get_tuning("assemble_range_shape", -1);
-    if (forced >= 0 && forced <= 3) return forced;
-    const long mean = nX / (nAr > 0 ? nAr : 1);
-    if (mean <= 1024 && nAr <= 512) return 3;           // every workgroup resident at once (two of 1024 threads per CU): a cell per thread
-    if (mean <= 1024 && nAr >= 2048) return 0;
-    if (mean > 1024 && nAr <= 256) return 2;            // at most one workgroup per CU: make it a big one
-    return 1;
+// ---- one launcher per templated kernel family: the plan's field picks the instantiation -------------------------
+template <bool EP>
+static void fa_launch_count(const RangePlan &rp, int nAr, hipStream_t st, const RgView &rg, const PlanView &pl, const MatSpec &s, const FaG &g,
+                            const FaP &p, int g_is_row, int merge, uint32_t *err_x, uint32_t *flags, int eva_check, const FaChain &ch) {
+    const dim3 grid(nAr + rp.count_extra);
+    switch (rp.shape) {
+    case 0: hipLaunchKernelGGL((k_fa_count<EP, 128, 2>), grid, dim3(128), 0, st, rg, pl, s, g, p, g_is_row, merge, err_x, flags, eva_check, ch); break;
+    case 2: hipLaunchKernelGGL((k_fa_count<EP, 1024, 4>), grid, dim3(1024), 0, st, rg, pl, s, g, p, g_is_row, merge, err_x, flags, eva_check, ch); break;
+    case 3: hipLaunchKernelGGL((k_fa_count<EP, 1024, 1>), grid, dim3(1024), 0, st, rg, pl, s, g, p, g_is_row, merge, err_x, flags, eva_check, ch); break;
+    default: hipLaunchKernelGGL((k_fa_count<EP, 256, 4>), grid, dim3(256), 0, st, rg, pl, s, g, p, g_is_row, merge, err_x, flags, eva_check, ch);
+    }
 }
-#define FA_LAUNCH_COUNT(EP, ...)                                                                                        \
-    do {                                                                                                                \
-        if (fa_shape == 0) hipLaunchKernelGGL((k_fa_count<EP, 128, 2>), dim3(nAr + count_extra), dim3(128), 0, st, __VA_ARGS__);      \
-        else if (fa_shape == 2) hipLaunchKernelGGL((k_fa_count<EP, 1024, 4>), dim3(nAr + count_extra), dim3(1024), 0, st, __VA_ARGS__); \
-        else if (fa_shape == 3) hipLaunchKernelGGL((k_fa_count<EP, 1024, 1>), dim3(nAr + count_extra), dim3(1024), 0, st, __VA_ARGS__); \
-        else hipLaunchKernelGGL((k_fa_count<EP, 256, 4>), dim3(nAr + count_extra), dim3(256), 0, st, __VA_ARGS__);                    \
-    } while (0)
-#define FA_LAUNCH_RANGE(EP, EM, ...)                                                                                    \
-    do {                                                                                                                \
-        if (fa_shape == 0) hipLaunchKernelGGL((k_fa_range<EP, EM, 128, 2>), dim3(nAr + range_extra), dim3(128), 0, st, __VA_ARGS__);  \
-        else if (fa_shape == 2) hipLaunchKernelGGL((k_fa_range<EP, EM, 1024, 4>), dim3(nAr + range_extra), dim3(1024), 0, st, __VA_ARGS__); \
-        else if (fa_shape == 3) hipLaunchKernelGGL((k_fa_range<EP, EM, 1024, 1>), dim3(nAr + range_extra), dim3(1024), 0, st, __VA_ARGS__); \
-        else hipLaunchKernelGGL((k_fa_range<EP, EM, 256, 4>), dim3(nAr + range_extra), dim3(256), 0, st, __VA_ARGS__);                \
-    } while (0)
+template <bool EP, bool EMIT>
+static void fa_launch_range(const RangePlan &rp, int nAr, hipStream_t st, const RgView &rg, const PlanView &pl, const MatSpec &s, const FaG &g,
+                            const FaP &p, int merge, const FaOut &o, uint32_t *flags) {
+    const dim3 grid(nAr + rp.range_extra);
+    switch (rp.shape) {
+    case 0: hipLaunchKernelGGL((k_fa_range<EP, EMIT, 128, 2>), grid, dim3(128), 0, st, rg, pl, s, g, p, merge, o, flags); break;
+    case 2: hipLaunchKernelGGL((k_fa_range<EP, EMIT, 1024, 4>), grid, dim3(1024), 0, st, rg, pl, s, g, p, merge, o, flags); break;
+    case 3: hipLaunchKernelGGL((k_fa_range<EP, EMIT, 1024, 1>), grid, dim3(1024), 0, st, rg, pl, s, g, p, merge, o, flags); break;
+    default: hipLaunchKernelGGL((k_fa_range<EP, EMIT, 256, 4>), grid, dim3(256), 0, st, rg, pl, s, g, p, merge, o, flags);
+    }
+}
+// the rows of np P elements (only_multi: of the list pl.mlist).  A pre-populated G set may list the columns in another order: the
+// variant with the per-row selection branch
+template <bool EP>
+static void fa_launch_pemit(bool g_fresh, long np, hipStream_t st, const RgView &rg, const PlanView &pl, const MatSpec &s, const FaG &g, const FaP &p,
+                            int merge, const FaOut &o, uint32_t *rowlen, uint32_t *flags, int only_multi) {
+    const dim3 grid(ceil_div(np, FA_T));
+    if (!g_fresh) hipLaunchKernelGGL((k_fa_pelem<EP, FA_PEMIT, true>), grid, dim3(FA_T), 0, st, rg, pl, s, g, p, merge, np, o, rowlen, flags, only_multi);
+    else hipLaunchKernelGGL((k_fa_pelem<EP, FA_PEMIT, false>), grid, dim3(FA_T), 0, st, rg, pl, s, g, p, merge, np, o, rowlen, flags, only_multi);
+}
 
 // ---- EvA / AvE (compute_EvA, RegridMatrices_Dynamic.cpp:254-332) -----------------------------------------------
 // EpvAp = EpvG * diag(1 / rowsum(GvAp)) * GvAp is a product over the exchange cells: entry (e, a) is the sum over the
@@ -1543,19 +1513,44 @@ __global__ void k_eva_final(RgView rg, PlanView pl, FaG g, const uint32_t *__res
     else { o.rs[a] = sum; o.rowptr[a] = (int32_t)eb; }
 }
 
-static bool fast_build_eva(const ibh_regrid_matrices *rm, const MatSpec *sp, ibh_sparse_set *dims[2], int scale, int correctA,
+// The scans of the ranges' class and entry counts when they did not ride in the counting launch (range_scan_form): gbase / ebase,
+// the totals to tot[0] / tot[1]; abase (EvA): also of "the range has entries", its total to tot_a
+static void fa_scan_ranges(ScanForm form, const FaG &g, int nAr, uint32_t *abase, uint32_t *tot, uint32_t *tot_a, hipStream_t st) {
+    if (form == SCAN_ONE_WORKGROUP) {                           // few: one workgroup, one launch
+        hipLaunchKernelGGL(k_fa_rscan, dim3(1), dim3(1024), 0, st, g.r_ncls, g.r_nent, nAr, g.gbase, g.ebase, tot);
+        if (abase) hipLaunchKernelGGL(k_eva_ascan, dim3(1), dim3(1024), 0, st, g.r_nent, nAr, abase, tot_a);
+    } else if (form == SCAN_MANY) {                             // many: three short launches for all channels
+        const int nb = ceil_div(nAr, 1024), nch = abase ? 3 : 2;
+        uint32_t *sums = arena().get<uint32_t>((size_t)nch * nb);
+        hipLaunchKernelGGL(k_fa_rscan_tiles, dim3(nb), dim3(1024), 0, st, g.r_ncls, g.r_nent, nAr, nch, sums);
+        hipLaunchKernelGGL(k_fa_rscan_sums, dim3(1), dim3(1024), 0, st, sums, nb, nch, tot, tot_a);
+        hipLaunchKernelGGL(k_fa_rscan_apply, dim3(nb), dim3(1024), 0, st, g.r_ncls, g.r_nent, nAr, nch, (const uint32_t *)sums, (const uint32_t *)tot,
+                           (const uint32_t *)tot_a, g.gbase, g.ebase, abase);
+    } else if (form == SCAN_DEVICE_WIDE) {                      // very many: the device-wide scan, channel by channel
+        exclusive_scan_u32(g.r_ncls, g.gbase, (size_t)nAr, g.gbase + nAr, st);
+        exclusive_scan_u32(g.r_nent, g.ebase, (size_t)nAr, g.ebase + nAr, st);
+        if (abase) {
+            uint32_t *has = arena().get<uint32_t>((size_t)nAr);
+            hipLaunchKernelGGL(k_eva_hasa, dim3(ceil_div(nAr, FA_T)), dim3(FA_T), 0, st, g.r_nent, nAr, has);
+            exclusive_scan_u32(has, abase, (size_t)nAr, abase + nAr, st);
+        }
+        IBH_HIP(hipMemcpyAsync(tot, g.gbase + nAr, sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+        IBH_HIP(hipMemcpyAsync(tot + 1, g.ebase + nAr, sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+        if (abase) IBH_HIP(hipMemcpyAsync(tot_a, abase + nAr, sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+    }
+}
+
+// (both sets are fresh: plan_build)
+static bool fast_build_eva(const ibh_regrid_matrices *rm, const MatSpec *sp, const RangePlan &rp, ibh_sparse_set *dims[2], int scale, int correctA,
                            const RgView &rg, ibh_weighted *w, hipStream_t st) {
     const ibh_regridder *gr = rm->rg;
     const bool e_is_row = sp->row_key == KEY_E;
     ibh_sparse_set *eset = dims[e_is_row ? 0 : 1], *aset = dims[e_is_row ? 1 : 0];
-    if (eset->n() != 0 || aset->n() != 0 || eset == aset) return false;
     const int64_t extE = key_extent(gr, KEY_E), extA = key_extent(gr, KEY_A);
     Arena &A = arena();
     A.reset();
     const ibh_plan &P = gr->plan;
-    PlanView pl{P.arng.p, P.aidx.p, P.ilptr.p, P.ilist.p, P.ifirst.p, P.isdup.p, P.mlist.p, P.nAr, P.nmulti,
-                get_tuning("assemble_static_count", 1) ? P.icnt_pos.p : nullptr, P.icnt_nz.p, P.exI.p};
-    const long nX = gr->nX;
+    const PlanView pl = plan_view(P, rp.static_count);
     const int T = FA_T, nAr = P.nAr;
     FaG g{};
     g.key = KEY_E; g.list = LIST_EP; g.NC = gr->nhc;
@@ -1569,24 +1564,8 @@ static bool fast_build_eva(const ibh_regrid_matrices *rm, const MatSpec *sp, ibh
     // counters: [0] first out-of-range cell, [1] fallback flags, [3] classes, [4] terms, [5] atmosphere cells
     uint32_t *d_cnt = A.get<uint32_t>(8);
     hipLaunchKernelGGL(k_fa_init, dim3(1), dim3(64), 0, st, d_cnt);
-    const int fa_shape = fa_range_shape(nX, nAr);
-    const int count_extra = 0;
-    FA_LAUNCH_COUNT(true, rg, pl, *sp, g, p, e_is_row ? 1 : 0, 0, d_cnt, d_cnt + 1, 1, FaChain{});
-    if (nAr > 4096 && fa_rscan_many(g, nAr, abase, d_cnt + 3, d_cnt + 5, st)) {
-        // (three short launches for the three channels)
-    } else if (nAr > 4096) {
-        exclusive_scan_u32(g.r_ncls, g.gbase, (size_t)nAr, g.gbase + nAr, st);
-        exclusive_scan_u32(g.r_nent, g.ebase, (size_t)nAr, g.ebase + nAr, st);
-        uint32_t *has = A.get<uint32_t>((size_t)nAr);
-        hipLaunchKernelGGL(k_eva_hasa, dim3(ceil_div(nAr, T)), dim3(T), 0, st, g.r_nent, nAr, has);
-        exclusive_scan_u32(has, abase, (size_t)nAr, abase + nAr, st);
-        IBH_HIP(hipMemcpyAsync(d_cnt + 3, g.gbase + nAr, sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
-        IBH_HIP(hipMemcpyAsync(d_cnt + 4, g.ebase + nAr, sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
-        IBH_HIP(hipMemcpyAsync(d_cnt + 5, abase + nAr, sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
-    } else {
-        hipLaunchKernelGGL(k_fa_rscan, dim3(1), dim3(1024), 0, st, g.r_ncls, g.r_nent, nAr, g.gbase, g.ebase, d_cnt + 3);
-        hipLaunchKernelGGL(k_eva_ascan, dim3(1), dim3(1024), 0, st, g.r_nent, nAr, abase, d_cnt + 5);
-    }
+    fa_launch_count<true>(rp, nAr, st, rg, pl, *sp, g, p, e_is_row ? 1 : 0, 0, d_cnt, d_cnt + 1, 1, FaChain{});
+    fa_scan_ranges(rp.scan, g, nAr, abase, d_cnt + 3, d_cnt + 5, st);
     IBH_HIP(hipGetLastError());
     uint32_t h[8];
     auto check_counters = [&]() -> bool {
@@ -1615,8 +1594,7 @@ static bool fast_build_eva(const ibh_regrid_matrices *rm, const MatSpec *sp, ibh
     if (nE) {
         // T[e]: the terms go to their (class, x-order) slot of a scratch array, one wave per class adds them up in sequence
         FaOut os{nullptr, nullptr, A.get<double>(nterm), nullptr, S, sp->family, 0, 0, e_is_row ? 1 : 0};
-        const int range_extra = 0;
-        FA_LAUNCH_RANGE(true, false, rg, pl, *sp, g, p, 0, os, flags);
+        fa_launch_range<true, false>(rp, nAr, st, rg, pl, *sp, g, p, 0, os, flags);
         EvaOut eo{w->rowptr.p, w->colind.p, row, w->val.p, rs, cs, atable.p};
         hipLaunchKernelGGL(k_eva_final, dim3(ceil_div(nAr, T)), dim3(T), 0, st, rg, pl, g, abase, S, e_is_row ? 1 : 0, eo, flags);
         IBH_HIP(hipGetLastError());
@@ -1636,19 +1614,9 @@ static bool fast_build_eva(const ibh_regrid_matrices *rm, const MatSpec *sp, ibh
     return true;
 }
 
-// Batch builds (assemble_batch): everything a concurrent fast build would otherwise create lazily in shared objects --
-// the sheet's plan, the inverse table of a pre-populated column set -- is created up front on the calling thread.
-static void fast_prewarm(const ibh_regrid_matrices *rm, const MatSpec *sp, ibh_sparse_set *dims[2], hipStream_t st) {
-    const ibh_regridder *gr = rm->rg;
-    if (!get_tuning("assemble_fast", 1) || !ensure_plan(gr, st)) return;
-    if (sp->family != FAM_IVAE || !dims[1] || dims[1]->n() == 0 || dims[1]->identity() || sp->col_key != KEY_E) return;
-    (void)dims[1]->device_to_dense(key_extent(gr, KEY_E), st);
-    IBH_HIP(hipStreamSynchronize(st));
-}
-
 template <bool EP>
-static bool stream_build(const ibh_regrid_matrices *rm, const MatSpec *sp, const FaRoles &role, int scale, int correctA,
-                         const RgView &rg, ibh_weighted *w, hipStream_t st, ibh_comm *comm);          // streamasm.inl
+static bool stream_build(const ibh_regrid_matrices *rm, const MatSpec *sp, const Roles &role, const FaSets &sets, const StreamPlan &plan, int scale,
+                         int correctA, const RgView &rg, ibh_weighted *w, hipStream_t st, ibh_comm *comm);          // streamasm.inl
 // Per host thread (a thread's builds run one after the other on its stream): the status words of the chained scans and a ring of
 // counter slots {0xffffffff, 0, ...}.  The words carry a 4-bit epoch, so they are cleared every 15 builds; the ring is
 // initialised again when it has gone round (both stream-ordered, both amortised to nothing).
@@ -1718,117 +1686,77 @@ static const std::vector<int32_t> &plan_arng_host(const ibh_regridder *g) {
     }
     return P.arng_h;
 }
-// EP: the matrix has elevation-class entries (LIST_EP on one side)
+// The per-range build of a G/P matrix, as plan_range decided it.  EP: the matrix has elevation-class entries (LIST_EP on one side)
 template <bool EP>
-static bool fast_build_gp(const ibh_regrid_matrices *rm, const MatSpec *sp, const FaRoles &role, int scale, int correctA,
-                          const RgView &rg, ibh_weighted *w, hipStream_t st, ibh_comm *comm) {
+static bool fast_build_gp(const ibh_regrid_matrices *rm, const MatSpec *sp, const Roles &role, const FaSets &sets, const RangePlan &rp, int scale,
+                          int correctA, const RgView &rg, ibh_weighted *w, hipStream_t st) {
     const ibh_regridder *gr = rm->rg;
-    // the sharded build; when it does not apply (the same on every rank: static conditions, exchanged flags) the ranks go on
-    // to build the matrix redundantly
-    if (comm && comm_world(comm) > 1 && stream_build<EP>(rm, sp, role, scale, correctA, rg, w, st, comm)) return true;
-    if (stream_build<EP>(rm, sp, role, scale, correctA, rg, w, st, nullptr)) return true;       // large grids: the streamed build
     const bool g_is_row = role.g_is_row, g_fresh = role.g_fresh;
     const int merge = role.merge;
 
     Arena &A = arena();
     A.reset();
     const ibh_plan &P = gr->plan;
-    PlanView pl{P.arng.p, P.aidx.p, P.ilptr.p, P.ilist.p, P.ifirst.p, P.isdup.p, P.mlist.p, P.nAr, P.nmulti,
-                get_tuning("assemble_static_count", 1) ? P.icnt_pos.p : nullptr, P.icnt_nz.p, P.exI.p};
+    const PlanView pl = plan_view(P, rp.static_count);
     const long nX = gr->nX;
     const int T = FA_T, nAr = P.nAr;
     FaG g{};
-    g.key = role.gkey; g.list = role.glist; g.NC = role.gkey == KEY_E ? gr->nhc : 1;
-    const size_t nrc = (size_t)nAr * g.NC;
+    g.key = role.gkey; g.list = role.glist; g.NC = rp.NC;
+    const size_t nrc = (size_t)rp.nrc;
     g.erank = A.get<int8_t>(nrc); g.ecntn = A.get<uint32_t>(nrc); g.ecnto = A.get<uint32_t>(nrc);
     g.r_ncls = A.get<uint32_t>((size_t)nAr); g.r_nent = A.get<uint32_t>((size_t)nAr);
     g.gbase = A.get<uint32_t>((size_t)nAr + 1); g.ebase = A.get<uint32_t>((size_t)nAr + 1);
-    if (!g_fresh) g.tab = role.gset->device_to_dense(role.gext, st);
+    if (!g_fresh) g.tab = sets.g->device_to_dense(role.gext, st);
     FaP p{};
     p.key = role.pkey; p.list = role.plist; p.fresh = role.pmode;
     // counters read back with one sync: [0] first out-of-range cell, [1] fallback flags, [2] new P keys, [3] G classes, [4] entries
-    const bool stream_count = !EP && g.NC == 1 && !g.tab && get_tuning("assemble_stream_count", nX >= (1l << 20) ? 1 : 0);
-    // small grids: the scans ride in the counting kernel (FaChain) and the counters come initialised from a ring of slots --
-    // three launches fewer in a chain of seven to nine that is all a 5 km build costs
-    const bool optimistic = nX <= (1l << 20);
-    const bool chained = optimistic && !stream_count && nrc < (1ul << FA_CH_NC);
     FaChain chain{};
     uint32_t *d_cnt;
     uint32_t *rowlen_early = nullptr;
-    const int fa_shape = fa_range_shape(nX, nAr);
-    int count_extra = 0;                                        // workgroups of k_fa_count that count row lengths (FaChain::pc_*)
-    if (chained) {
+    if (rp.chained) {
         FaChainState &cs = fa_chain_state();
         d_cnt = cs.counters(st);
-        // (row lengths of an I-row build on the identity ice set: counted and scanned by extra workgroups of the counting launch)
-        const bool pc = !g_is_row && role.pkey == KEY_I && !p.fresh && pl.icnt_pos;
-        const long pc_rows = pc ? (long)role.pext : 0;
-        const int tshape_c = fa_shape == 0 ? 128 : fa_shape == 1 ? 256 : 1024;
-        count_extra = pc ? ceil_div(pc_rows, tshape_c) : 0;
-        const bool ir = !g_is_row && role.pkey == KEY_I && p.fresh && pl.icnt_pos;
-        chain = FaChain{cs.words((size_t)nAr + (size_t)count_extra + (ir ? (size_t)nAr : 0), st), cs.epoch, d_cnt + 2, nullptr, 0u, nullptr, 0u, nullptr, 0u,
+        chain = FaChain{cs.words((size_t)rp.nstatus, st), cs.epoch, d_cnt + 2, nullptr, 0u, nullptr, 0u, nullptr, 0u,
                         nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0l, 0, 0};
-        if (ir) {                                               // (I rows on an ice set numbered by this build: the row pointer from the counting launch)
-            const size_t np_ub0 = (size_t)std::min<int64_t>(role.pext, nX);
-            w->rowptr.alloc(np_ub0 + 1);
-            chain.ir_rowptr = reinterpret_cast<uint32_t *>(w->rowptr.p);
+        if (rp.rowptr_rows) w->rowptr.alloc((size_t)rp.rowptr_rows + 1);      // (the row pointer is written by the counting launch)
+        uint32_t *rowptr = reinterpret_cast<uint32_t *>(w->rowptr.p);
+        if (rp.rowptr == ROWPTR_COUNT_LAUNCH_FRESH_I) {
+            chain.ir_rowptr = rowptr;
             chain.ir_tmp = A.get<uint32_t>((size_t)nX);
-            chain.ir_status0 = nAr + count_extra;
+            chain.ir_status0 = nAr + rp.count_extra;
+        } else if (rp.rowptr == ROWPTR_RANGES_X) chain.xr_rowptr = rowptr;
+        else if (rp.rowptr == ROWPTR_COUNT_LAUNCH_IDENTITY_I) {
+            chain.pc_rowptr = rowptr; chain.pc_n = rp.rowptr_rows; chain.pc_first = nAr; chain.pc_status0 = nAr;
         }
-        if (!g_is_row && role.pkey == KEY_X && !p.fresh && merge == 0) {
-            // (X rows on the identity exchange-cell set: the row pointer falls out of the ranges' own look-back)
-            w->rowptr.alloc((size_t)nX + 1);
-            chain.xr_rowptr = reinterpret_cast<uint32_t *>(w->rowptr.p);
+        if (rp.nclear_mw_g) {
+            w->Mw.alloc((size_t)role.g_n);
+            chain.zero2 = reinterpret_cast<uint32_t *>(w->Mw.p); chain.nzero2 = (unsigned)rp.nclear_mw_g;
         }
-        if (pc) {
-            w->rowptr.alloc((size_t)pc_rows + 1);
-            chain.pc_rowptr = reinterpret_cast<uint32_t *>(w->rowptr.p); chain.pc_n = pc_rows; chain.pc_first = nAr; chain.pc_status0 = nAr;
-        }
-        if (!g_is_row && !g_fresh && role.gset->n() > 0) {           // (what k_fa_zero_identity did in a launch of its own)
-            w->Mw.alloc((size_t)role.gset->n());
-            chain.zero2 = reinterpret_cast<uint32_t *>(w->Mw.p); chain.nzero2 = 2u * (unsigned)role.gset->n();
-        }
-        // a fresh E set: the step's later builds (IvE, XvE on the dimE this EvI numbers: IceCoupler.cpp:361-377) look keys up in the
-        // sparse -> dense table -- written here as the set is numbered instead of by two launches and a synchronisation later
-        if (g_fresh && role.gkey == KEY_E && role.gext < (1l << 22)) {
-            g.tab_out = role.gset->device_to_dense_for_write(role.gext);
-            chain.fill_m1 = g.tab_out; chain.nfill = (unsigned)role.gext;
+        if (rp.nfill) {
+            g.tab_out = sets.g->device_to_dense_for_write(role.gext);
+            chain.fill_m1 = g.tab_out; chain.nfill = (unsigned)rp.nfill;
         }
         // what the later kernels want cleared, by the upper bounds the outputs are allocated with below
-        const size_t np_ub = p.fresh ? (size_t)std::min<int64_t>(role.pext, nX) : (size_t)role.pext;
-        if (g_is_row && !p.fresh && np_ub) {                    // Mw of an identity P set: members without entries stay 0
-            w->Mw.alloc(np_ub);
-            chain.zero = reinterpret_cast<uint32_t *>(w->Mw.p); chain.nzero = (unsigned)(2 * np_ub);
-        } else if (!g_is_row && p.fresh) {                      // row lengths beyond the real number of rows
-            rowlen_early = A.get<uint32_t>(np_ub + 1);
-            chain.zero = rowlen_early; chain.nzero = (unsigned)(np_ub + 1);
+        if (rp.clears == CLEAR_MW_P) {
+            w->Mw.alloc((size_t)rp.np_ub);
+            chain.zero = reinterpret_cast<uint32_t *>(w->Mw.p); chain.nzero = (unsigned)rp.nclear;
+        } else if (rp.clears == CLEAR_ROWLEN) {
+            rowlen_early = A.get<uint32_t>((size_t)rp.nclear);
+            chain.zero = rowlen_early; chain.nzero = (unsigned)rp.nclear;
         }
     } else {
         d_cnt = A.get<uint32_t>(8);
         hipLaunchKernelGGL(k_fa_init, dim3(1), dim3(64), 0, st, d_cnt);
     }
     if (p.fresh) { p.pflag = A.get<uint8_t>((size_t)nX); p.poff = A.get<uint32_t>((size_t)nX); }
-    const bool pcount_done = count_extra > 0 || chain.xr_rowptr != nullptr || chain.ir_rowptr != nullptr;      // (the row pointer is written by the counting launch)
-    if (stream_count) {
-        // one-class matrices of large grids: cells streamed, counts by integer atomics (three launches, all short)
+    if (rp.stream_count) {
         hipLaunchKernelGGL(k_fa_zero_counts, dim3(ceil_div(nAr, 256)), dim3(256), 0, st, g.r_ncls, g.ecntn, g.ecnto, nAr);
         hipLaunchKernelGGL(k_fa_count_stream<4>, dim3(ceil_div(nX, 1024)), dim3(256), 0, st, rg, pl, *sp, g, p, g_is_row ? 1 : 0, merge);
         hipLaunchKernelGGL(k_fa_count_fin, dim3(ceil_div(nAr, 256)), dim3(256), 0, st, g, nAr, d_cnt + 1);
-    } else FA_LAUNCH_COUNT(EP, rg, pl, *sp, g, p, g_is_row ? 1 : 0, merge, d_cnt, d_cnt + 1, 0, chain);
-    if (chained) {
-        // (poff, gbase / ebase and the three totals were written by k_fa_count)
-    } else if (p.fresh) exclusive_scan_u8(p.pflag, p.poff, (size_t)nX, d_cnt + 2, st);
-    if (chained) {
-    } else if (nAr > 4096 && fa_rscan_many(g, nAr, nullptr, d_cnt + 3, nullptr, st)) {
-        // (many ranges: three short launches for both channels)
-    } else if (nAr > 4096) {                                    // very many: the device-wide scan; few: one workgroup, one launch
-        exclusive_scan_u32(g.r_ncls, g.gbase, (size_t)nAr, g.gbase + nAr, st);
-        exclusive_scan_u32(g.r_nent, g.ebase, (size_t)nAr, g.ebase + nAr, st);
-        IBH_HIP(hipMemcpyAsync(d_cnt + 3, g.gbase + nAr, sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
-        IBH_HIP(hipMemcpyAsync(d_cnt + 4, g.ebase + nAr, sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
-    } else {
-        hipLaunchKernelGGL(k_fa_rscan, dim3(1), dim3(1024), 0, st, g.r_ncls, g.r_nent, nAr, g.gbase, g.ebase, d_cnt + 3);
-    }
+    } else fa_launch_count<EP>(rp, nAr, st, rg, pl, *sp, g, p, g_is_row ? 1 : 0, merge, d_cnt, d_cnt + 1, 0, chain);
+    // (chained: poff, gbase / ebase and the three totals were written by k_fa_count)
+    if (!rp.chained && p.fresh) exclusive_scan_u8(p.pflag, p.poff, (size_t)nX, d_cnt + 2, st);
+    fa_scan_ranges(rp.scan, g, nAr, nullptr, d_cnt + 3, nullptr, st);
     IBH_HIP(hipGetLastError());
     uint32_t h[8];
     bool published = false;
@@ -1842,15 +1770,12 @@ static bool fast_build_gp(const ibh_regrid_matrices *rm, const MatSpec *sp, cons
         IBH_CHECK(h[4] < (1u << 31) && h[2] < (1u << 31), "matrix too large for int32 indices");
         return true;
     };
-    // Small grids are bound by launches and synchronisations, not by bytes: their outputs are allocated by upper bounds
-    // (<= 2 entries per exchange cell, <= NC rows per range) so that the counters are read back ONCE, with the final
-    // synchronisation; large grids read them here and allocate exactly.
-    if (!optimistic && !check_counters()) return false;
-    const uint32_t n_pnew = optimistic ? (uint32_t)std::min<int64_t>(role.pext, nX) : h[2];
-    const uint32_t n_g = optimistic ? (uint32_t)nrc : h[3];
-    const uint32_t nnz = optimistic ? (uint32_t)((EP ? 2 : 1) * nX) : h[4];
-    int np_d = p.fresh ? (int)n_pnew : (int)role.pext;
-    int ng_d = g_fresh ? (int)n_g : role.gset->n();
+    // optimistic builds allocate by the plan's upper bounds and read the counters back once, at the end; the others read them
+    // here and allocate exactly
+    if (!rp.optimistic && !check_counters()) return false;
+    const uint32_t nnz = rp.optimistic ? (uint32_t)rp.nnz_ub : h[4];
+    int np_d = !p.fresh ? (int)role.pext : rp.optimistic ? (int)rp.np_ub : (int)h[2];
+    int ng_d = !g_fresh ? (int)role.g_n : rp.optimistic ? (int)rp.ng_ub : (int)h[3];
     // dims tables of the sets numbered by this build are written straight into the sets' device buffers
     DevBuf<int64_t> ptable, gtable;
     if (p.fresh) { ptable.alloc((size_t)np_d); p.to_sparse = ptable.p; }
@@ -1861,53 +1786,39 @@ static bool fast_build_gp(const ibh_regrid_matrices *rm, const MatSpec *sp, cons
     w->wM.alloc((size_t)nrow); w->Mw.alloc((size_t)ncol);
     FaOut o{w->rowptr.p, w->colind.p, w->val.p, w->wM.p, w->Mw.p, sp->family, scale, correctA, 0};
     uint32_t *flags = d_cnt + 1;
-    int range_extra = 0;                                        // workgroups of k_fa_range that do k_fa_psums8's work
     const long np_s = p.key == KEY_I ? gr->nI : nX;             // P elements by sparse index
-    const dim3 gp(ceil_div(np_s, T));
     if (g_is_row) {
         // rows = G: CSR + wM + (most of) Mw from the ranges; members of the P set without entries keep Mw = 0
         // (a set numbered by this build: every member's Mw is written by k_fa_range / k_fa_pelem<SUMS>; an identity set has
         // non-members -- masked cells -- whose Mw stays 0)
-        if (ncol && !p.fresh && !chain.zero) IBH_HIP(hipMemsetAsync(w->Mw.p, 0, sizeof(double) * (size_t)ncol, st));
-        bool sums_after = p.key == KEY_I && P.nmulti;
+        if (ncol && !p.fresh && rp.clears != CLEAR_MW_P) IBH_HIP(hipMemsetAsync(w->Mw.p, 0, sizeof(double) * (size_t)ncol, st));
         FaOut ol = o;                                         // (the build's last kernel publishes the counters)
-        // (chained => optimistic: the counters are read once, at the end)
-        if (chained) { fa_chain_state().publish_into(ol, d_cnt, st); published = true; }
-        if (sums_after && chained && P.nmulti <= (1l << 20)) {
-            // small grids: the straddlers' Mw in extra workgroups of the range kernel's own launch
-            const int tshape = fa_shape == 0 ? 128 : fa_shape == 1 ? 256 : 1024;
-            range_extra = ceil_div(8 * (long)P.nmulti, tshape);
-            ol.psums_first = nAr; ol.psums_n = (long)P.nmulti;
-            sums_after = false;
-        }
-        FA_LAUNCH_RANGE(EP, true, rg, pl, *sp, g, p, merge, (sums_after ? o : ol), flags);
-        range_extra = 0;
-        if (sums_after) {                                     // Mw of the ice cells that straddle ranges (a few %)
-            const dim3 gm(ceil_div(P.nmulti, T));
-            if (P.nmulti <= (1l << 20)) {                      // few of them: eight lanes per ice cell
-                const dim3 g8(ceil_div(8 * (long)P.nmulti, T));
-                hipLaunchKernelGGL((k_fa_psums8<EP>), g8, dim3(T), 0, st, rg, pl, *sp, g, p, merge, (long)P.nmulti, ol);
-            } else hipLaunchKernelGGL((k_fa_pelem<EP, FA_PSUMS, false>), gm, dim3(T), 0, st, rg, pl, *sp, g, p, merge, (long)P.nmulti, ol, (uint32_t *)nullptr, flags, 0);
-        }
+        if (rp.published) { fa_chain_state().publish_into(ol, d_cnt, st); published = true; }
+        const long nmulti = (long)P.nmulti;
+        if (rp.sums == SUMS_IN_RANGE_LAUNCH) { ol.psums_first = nAr; ol.psums_n = nmulti; }
+        const bool sums_after = rp.sums == SUMS_PSUMS8 || rp.sums == SUMS_PELEM;
+        fa_launch_range<EP, true>(rp, nAr, st, rg, pl, *sp, g, p, merge, (sums_after ? o : ol), flags);
+        if (rp.sums == SUMS_PSUMS8)
+            hipLaunchKernelGGL((k_fa_psums8<EP>), dim3(ceil_div(8 * nmulti, T)), dim3(T), 0, st, rg, pl, *sp, g, p, merge, nmulti, ol);
+        else if (rp.sums == SUMS_PELEM)
+            hipLaunchKernelGGL((k_fa_pelem<EP, FA_PSUMS, false>), dim3(ceil_div(nmulti, T)), dim3(T), 0, st, rg, pl, *sp, g, p, merge, nmulti, ol, (uint32_t *)nullptr, flags, 0);
     } else {
         // rows = P: count -> scan -> emit per element; Mw (G columns) from the ranges through a scratch copy of the terms
         uint32_t *rowlen = rowlen_early ? rowlen_early : A.get<uint32_t>((size_t)nrow + 1);
-        if (optimistic && p.fresh && !rowlen_early) IBH_HIP(hipMemsetAsync(rowlen, 0, sizeof(uint32_t) * ((size_t)nrow + 1), st));   // rows beyond the real count
-        if (pcount_done) {
-            // (the row lengths were counted by extra workgroups of k_fa_count's launch)
-        } else hipLaunchKernelGGL((k_fa_pelem<EP, FA_PCOUNT, false>), gp, dim3(T), 0, st, rg, pl, *sp, g, p, merge, np_s, o, rowlen, flags, 0);
-        if (!pcount_done) exclusive_scan_u32(rowlen, reinterpret_cast<uint32_t *>(w->rowptr.p), (size_t)nrow, reinterpret_cast<uint32_t *>(w->rowptr.p) + nrow, st);
-        // (a pre-populated G set may list the columns in another order: the variant with the per-row selection branch)
-        if (!g_fresh) hipLaunchKernelGGL((k_fa_pelem<EP, FA_PEMIT, true>), gp, dim3(T), 0, st, rg, pl, *sp, g, p, merge, np_s, o, rowlen, flags, 0);
-        else hipLaunchKernelGGL((k_fa_pelem<EP, FA_PEMIT, false>), gp, dim3(T), 0, st, rg, pl, *sp, g, p, merge, np_s, o, rowlen, flags, 0);
+        if (rp.optimistic && p.fresh && !rowlen_early) IBH_HIP(hipMemsetAsync(rowlen, 0, sizeof(uint32_t) * ((size_t)nrow + 1), st));   // rows beyond the real count
+        if (rp.rowptr == ROWPTR_PELEM_COUNT) {
+            hipLaunchKernelGGL((k_fa_pelem<EP, FA_PCOUNT, false>), dim3(ceil_div(np_s, T)), dim3(T), 0, st, rg, pl, *sp, g, p, merge, np_s, o, rowlen, flags, 0);
+            exclusive_scan_u32(rowlen, reinterpret_cast<uint32_t *>(w->rowptr.p), (size_t)nrow, reinterpret_cast<uint32_t *>(w->rowptr.p) + nrow, st);
+        }
+        fa_launch_pemit<EP>(g_fresh, np_s, st, rg, pl, *sp, g, p, merge, o, rowlen, flags, 0);
         FaOut os = o;
         os.val = A.get<double>(nnz);
-        if (chained) { fa_chain_state().publish_into(os, d_cnt, st); published = true; }
-        if (!g_fresh && ncol && !chain.zero2) hipLaunchKernelGGL(k_fa_zero_identity, dim3(ceil_div(ncol, T)), dim3(T), 0, st, w->Mw.p, (long)ncol);   // columns of the shared set this mask does not touch
-        FA_LAUNCH_RANGE(EP, false, rg, pl, *sp, g, p, merge, os, flags);
+        if (rp.published) { fa_chain_state().publish_into(os, d_cnt, st); published = true; }
+        if (!g_fresh && ncol && !rp.nclear_mw_g) hipLaunchKernelGGL(k_fa_zero_identity, dim3(ceil_div(ncol, T)), dim3(T), 0, st, w->Mw.p, (long)ncol);   // columns of the shared set this mask does not touch
+        fa_launch_range<EP, false>(rp, nAr, st, rg, pl, *sp, g, p, merge, os, flags);
     }
     IBH_HIP(hipGetLastError());
-    if (optimistic) {                                           // the one read-back of a small build: flags and the real sizes
+    if (rp.optimistic) {                                        // the one read-back of a small build: flags and the real sizes
         if (!check_counters()) return false;
         if (p.fresh) np_d = (int)h[2];
         if (g_fresh) ng_d = (int)h[3];
@@ -1916,30 +1827,9 @@ static bool fast_build_gp(const ibh_regrid_matrices *rm, const MatSpec *sp, cons
         w->wM.n = (size_t)w->nrow; w->Mw.n = (size_t)w->ncol;
         ptable.n = p.fresh ? (size_t)np_d : 0; gtable.n = g_fresh ? (size_t)ng_d : 0;
     }
-    role.pset->adopt_device(std::move(ptable), np_d, role.pext);
-    role.gset->adopt_device(std::move(gtable), ng_d, role.gext);
-    if (g.tab_out) role.gset->mark_device_to_dense_written(role.gext);
+    sets.p->adopt_device(std::move(ptable), np_d, role.pext);
+    sets.g->adopt_device(std::move(gtable), ng_d, role.gext);
+    if (g.tab_out) sets.g->mark_device_to_dense_written(role.gext);
     IBH_HIP(hipStreamSynchronize(st));
     return true;
-}
-// returns false when the fast path does not apply (nothing has been touched: the caller runs the general pipeline)
-static bool fast_build(const ibh_regrid_matrices *rm, const MatSpec *sp, ibh_sparse_set *dims[2], int scale, int correctA,
-                       const RgView &rg, ibh_weighted *w, hipStream_t st, ibh_comm *comm = nullptr) {
-    const ibh_regridder *gr = rm->rg;
-    if (!get_tuning("assemble_fast", 1)) return false;
-    if (!ensure_plan(gr, st)) return false;
-    if (sp->family == FAM_EVA) return get_tuning("assemble_fast_eva", 1) && fast_build_eva(rm, sp, dims, scale, correctA, rg, w, st);
-    FaRoles role;
-    role.g_is_row = sp->family == FAM_AEVI;
-    role.gset = dims[role.g_is_row ? 0 : 1]; role.pset = dims[role.g_is_row ? 1 : 0];
-    role.gkey = role.g_is_row ? sp->row_key : sp->col_key; role.glist = role.g_is_row ? sp->row_list : sp->col_list;
-    role.pkey = role.g_is_row ? sp->col_key : sp->row_key; role.plist = role.g_is_row ? sp->col_list : sp->row_list;
-    role.gext = key_extent(gr, role.gkey); role.pext = key_extent(gr, role.pkey);
-    role.pmode = fa_pset_mode(role.pset, role.pext);
-    if (role.pmode < 0) return false;
-    role.g_fresh = role.gset->n() == 0;
-    if (!role.g_fresh && (role.gset->identity() || role.gkey != KEY_E || role.g_is_row)) return false;      // pre-populated: E columns only
-    role.merge = (sp->row_key != KEY_X && sp->col_key != KEY_X) ? 1 : 0;
-    const bool uses_ep = sp->row_list == LIST_EP || sp->col_list == LIST_EP;
-    return uses_ep ? fast_build_gp<true>(rm, sp, role, scale, correctA, rg, w, st, comm) : fast_build_gp<false>(rm, sp, role, scale, correctA, rg, w, st, comm);
 }

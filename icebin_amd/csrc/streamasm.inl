@@ -25,14 +25,10 @@
 // Not served here (fastasm.inl's kernels take them): plans with underflowing areas (the elevation-class builds count by the sign
 // of the area), EvA / AvE (fast_build_eva).
 
-constexpr int SA_T = 256, SA_CPT = 4, SA_TILE = SA_T * SA_CPT;
 // code byte: a P key is first seen here | this cell heads a group with entries | those entries straddle in from an earlier range |
 // unmasked | static plan bits the emit pass needs (so that it does not read the plan's byte again): the only exchange cell of its
 // ice cell, the first-seen cell of its ice cell, a duplicate follows, the first cell of its range
 enum { SA_P = 1, SA_ENT = 2, SA_OLD = 4, SA_UNM = 8, SA_ONE = 16, SA_FIRST = 32, SA_DUPNEXT = 64, SA_RHEAD = 128 };
-// straddling entries of one (range, class) segment sorted in LDS by k_sa_rows: tables of 128 (many short ranges: four waves of a
-// workgroup hold 12 KB, the CU stays full) or 512 (long ranges: few segments, occupancy does not matter); more -> fastasm.inl
-constexpr int SA_OLDSEG_S = 128, SA_OLDSEG_L = 512;
 
 struct SaBuf {
     uint8_t *code;          // [nW * 64]
@@ -1325,8 +1321,45 @@ __global__ void k_sa_unpack_mw(const int32_t *__restrict__ cidx, const double *_
     Mw[cidx[k]] = cval[k];
 }
 
-// false: not served here (nothing has been touched: fast_build's own kernels run next).  role: the two sides, already past
-// fast_build's gates (the P set fresh or the identity, the G set fresh or pre-populated E columns).
+// ---- one launcher per templated kernel family: the plan's field picks the instantiation -------------------------
+// the class counts of nr ranges: wpr waves per range, positions of 16 or 32 bits
+template <typename RT>
+static void sa_launch_ranges_rt(const StreamPlan &plan, int nr, hipStream_t st, const RgView &rg, const PlanView &pl, const SaBuf &sb, const FaG &g, uint32_t *flags) {
+    if (plan.wpr == 1) hipLaunchKernelGGL((k_sa_ranges<true, RT, 1>), dim3(ceil_div(nr, 4)), dim3(256), 0, st, rg, pl, sb, g, flags, plan.oldseg);
+    else if (plan.wpr == 4) hipLaunchKernelGGL((k_sa_ranges<true, RT, 4>), dim3(nr), dim3(256), 0, st, rg, pl, sb, g, flags, plan.oldseg);
+    else hipLaunchKernelGGL((k_sa_ranges<true, RT, 16>), dim3(nr), dim3(1024), 0, st, rg, pl, sb, g, flags, plan.oldseg);
+}
+static void sa_launch_ranges(const StreamPlan &plan, int nr, hipStream_t st, const RgView &rg, const PlanView &pl, const SaBuf &sb, const FaG &g, uint32_t *flags) {
+    if (plan.rel32) sa_launch_ranges_rt<uint32_t>(plan, nr, st, rg, pl, sb, g, flags);
+    else sa_launch_ranges_rt<uint16_t>(plan, nr, st, rg, pl, sb, g, flags);
+}
+// the emit pass over ncell cells (GR: the G side is the row side)
+template <bool EP, bool GR>
+static void sa_launch_emit(const StreamPlan &plan, long ncell, hipStream_t st, const RgView &rg, const PlanView &pl, const MatSpec &s, const FaG &g,
+                           const FaP &p, const SaBuf &sb, int merge, const FaOut &o, double *sval, int32_t *sdid) {
+    const dim3 grid(stream_emit_grid(plan, ncell));
+    if (plan.rel32) hipLaunchKernelGGL((k_sa_emit<EP, GR, uint32_t, 4>), grid, dim3(SA_T), 0, st, rg, pl, s, g, p, sb, merge, o, sval, sdid);
+    else hipLaunchKernelGGL((k_sa_emit<EP, GR, uint16_t, 1>), grid, dim3(SA_T), 0, st, rg, pl, s, g, p, sb, merge, o, sval, sdid);
+}
+// the sums of the (range, class) segments of ranges [sr0, sr1) -- EMIT: the rows of an A/E-row matrix in place, else the column sums
+// over the scratch copy (sdid: its dense ids) -- by the lane-parallel kernel behind a sort of the straddlers (sort_idx / sort_val:
+// the entries it sorts), four segments per wave, or one
+template <bool EMIT>
+static void sa_launch_rows(const StreamPlan &plan, const StreamRowsPlan &rows, hipStream_t st, const RgView &rg, const PlanView &pl, const FaG &g,
+                           const FaOut &o, int32_t *sort_idx, double *sort_val, int32_t *sdid, int sr0, int sr1) {
+    const dim3 g4(rows.grid_rows4[0], rows.grid_rows4[1]), g1(rows.grid_rows1[0], rows.grid_rows1[1]);
+    const bool small = plan.oldseg == SA_OLDSEG_S;
+    if (plan.rowsl) {
+        if (small) hipLaunchKernelGGL((k_sa_oldsort<SA_OLDSEG_S>), dim3(ceil_div(sr1 - sr0, 4)), dim3(256), 0, st, g, sort_idx, sort_val, sr0, sr1);
+        else hipLaunchKernelGGL((k_sa_oldsort<SA_OLDSEG_L>), dim3(ceil_div(sr1 - sr0, 4)), dim3(256), 0, st, g, sort_idx, sort_val, sr0, sr1);
+        hipLaunchKernelGGL((k_sa_rowsL<EMIT>), dim3(rows.grid_rowsl), dim3(256), 0, st, rg, pl, g, o, sr0, sr1, rows.rows_R);
+    } else if (plan.rows4) hipLaunchKernelGGL((k_sa_rows<EMIT, SA_OLDSEG_S, 4>), g4, dim3(256), 0, st, rg, pl, g, o, sdid, sr0, sr1);
+    else if (small) hipLaunchKernelGGL((k_sa_rows1<EMIT, SA_OLDSEG_S>), g1, dim3(256), 0, st, rg, pl, g, o, sdid, sr0, sr1);
+    else hipLaunchKernelGGL((k_sa_rows1<EMIT, SA_OLDSEG_L>), g1, dim3(256), 0, st, rg, pl, g, o, sdid, sr0, sr1);
+}
+
+// The streamed build as plan_stream decided it (plan.ok).  false: a limit was hit at run time (nothing has been touched: fast_build's
+// next candidate runs).  role / sets: the two sides.
 // comm != nullptr: the SHARDED build of ibh_regrid_matrices_matrix_d_sharded -- every rank of the communicator calls this with the
 // same arguments; rank k runs the passes over its share of the ranges (contiguous, balanced by exchange cells: the grid is sorted
 // by atmosphere cell, AbbrGrid.cpp:10-21, so a block of ranges is a block of rows of an A/E-row matrix), three exchanges make
@@ -1337,43 +1370,31 @@ __global__ void k_sa_unpack_mw(const int32_t *__restrict__ cidx, const double *_
 //      of the rank that numbered its ice cell), the class ranks and row offsets of every range   (~1 byte per exchange cell)
 //   3. the pieces of the result: CSR, wM, Mw, the dims tables
 template <bool EP>
-static bool stream_build(const ibh_regrid_matrices *rm, const MatSpec *sp, const FaRoles &role, int scale, int correctA,
-                         const RgView &rg, ibh_weighted *w, hipStream_t st, ibh_comm *comm) {
+static bool stream_build(const ibh_regrid_matrices *rm, const MatSpec *sp, const Roles &role, const FaSets &sets, const StreamPlan &plan, int scale,
+                         int correctA, const RgView &rg, ibh_weighted *w, hipStream_t st, ibh_comm *comm) {
     const ibh_regridder *gr = rm->rg;
     const ibh_plan &P = gr->plan;
     const long nX = gr->nX;
-    const int world = comm ? comm_world(comm) : 1, rank = comm ? comm_rank(comm) : 0;
-    if (!comm && !get_tuning("assemble_stream", nX >= (1l << 20) ? 1 : 0)) return false;
+    const int world = plan.world, rank = comm ? comm_rank(comm) : 0;
+    IBH_CHECK(plan.ok && world == (comm ? comm_world(comm) : 1), "internal: the streamed build's plan is not for this call");
     const bool g_is_row = role.g_is_row, g_fresh = role.g_fresh;
     const int pmode = role.pmode, merge = role.merge;
-    if (EP && (P.tiny || !P.icnt_nz.p)) return false;             // classes are counted by the sign of the area here
-    if (!P.icnt_pos.p) return false;
-    // an I-row matrix on an identity ice set (the coupler's IvE, IceCoupler.cpp:462): its rows lie in ice-cell order, not in
-    // first-seen order -- row lengths are scattered by ice cell and scanned over the ice cells
-    const bool by_ice = !g_is_row && role.pkey == KEY_I && pmode == 0;
-    // sharded: the pieces of a rank must be contiguous in every result array -- sets numbered by this build; at most 8 ranks (one
-    // 256-byte read-back carries all counters).  An A/E-row matrix on an IDENTITY P set (the coupler's EvI / AvI over the identity
-    // dimI, IceCoupler.cpp:366-377) is served too: its CSR pieces are contiguous as they are (an entry's column is its sparse
-    // index), only Mw is scattered -- the sums travel as {position, value} pairs at their first-seen ranks (k_sa_pack_mw).
+    // The pieces of the shared build (plan_stream).  An A/E-row matrix on an IDENTITY P set (the coupler's EvI / AvI over the identity
+    // dimI, IceCoupler.cpp:366-377): its CSR pieces are contiguous as they are (an entry's column is its sparse index), only Mw is
+    // scattered -- the sums travel as {position, value} pairs at their first-seen ranks (k_sa_pack_mw).
     // An X-row matrix on the identity dimX (the coupler's XvE, :467) has its rows in exchange-cell order: a block of cells is a block
     // of rows.  A pre-populated G set (its dimE1, numbered by EvI) is looked up in the table every rank has; the column sums sit
     // at the caller's dense ids and travel as pairs too, at the ranks a fresh numbering would give the classes (k_sa_pack_mw_g).
     // I rows on the identity dimI (its IvE, :462; by_ice): rows in ice-cell order -- the row lengths are merged before the row pointer
     // is scanned, the rows travel in first-seen order and are copied to their places (k_sa_pack_keys / k_sa_pack_rows).
-    const bool ident_p = world > 1 && pmode == 0 && g_is_row;
-    const bool ident_x_rows = world > 1 && pmode == 0 && !g_is_row && role.pkey == KEY_X;
-    const bool ident_i_rows = world > 1 && by_ice;
-    const bool prepop_g = world > 1 && !g_fresh;                 // (an E column set: fast_build checks)
-    if (world > 1 && ((pmode != 1 && !ident_p && !ident_x_rows && !ident_i_rows) || world > 8 || P.nAr < world)) return false;
-    const bool pscan = pmode == 1 || ident_p || ident_i_rows;    // the P keys are numbered (first-seen ranks)
-    const int S = EP ? 2 : 1;
-    if (gr->nhc > 64) return false;
+    const bool by_ice = plan.by_ice, ident_p = plan.ident_p, ident_x_rows = plan.ident_x_rows, ident_i_rows = plan.ident_i_rows, prepop_g = plan.prepop_g;
+    const bool pscan = plan.pscan, rel32 = plan.rel32;
+    const int S = EP ? 2 : 1, oldseg = plan.oldseg;
     const uint8_t *emc = elevmask_classes_impl(rm, st);          // (made when the object was created, or here by the first build)
-    const bool rel32 = (int64_t)S * P.maxrange > 65535;
 
     Arena &A = arena();
     A.reset();
-    PlanView pl{P.arng.p, P.aidx.p, P.ilptr.p, P.ilist.p, P.ifirst.p, P.isdup.p, P.mlist.p, P.nAr, P.nmulti, P.icnt_pos.p, P.icnt_nz.p, P.exI.p};
+    PlanView pl = plan_view(P, true);
     pl.riA = P.riA.p;
     const int T = FA_T, nAr = P.nAr;
     const long nW = ceil_div(nX, 64l);
@@ -1400,12 +1421,12 @@ static bool stream_build(const ibh_regrid_matrices *rm, const MatSpec *sp, const
     PlanView pl3 = pl;                                           // (k_fa_pelem walks pl.mlist: here the ice cells that are no clean pairs)
     pl3.mlist = P.mlist3.p; pl3.nmulti = P.nmulti3;
     FaG g{};
-    g.key = role.gkey; g.list = role.glist; g.NC = role.gkey == KEY_E ? gr->nhc : 1;
+    g.key = role.gkey; g.list = role.glist; g.NC = plan.NC;
     const size_t nrc = (size_t)nAr * g.NC;
     g.erank = A.get<int8_t>(nrc); g.ecntn = A.get<uint32_t>(nrc); g.ecnto = A.get<uint32_t>(nrc);
     g.r_ncls = A.get<uint32_t>((size_t)nAr); g.r_nent = A.get<uint32_t>((size_t)nAr);
     g.gbase = A.get<uint32_t>((size_t)nAr + 1); g.ebase = A.get<uint32_t>((size_t)nAr + 1);
-    if (!g_fresh) g.tab = role.gset->device_to_dense(role.gext, st);
+    if (!g_fresh) g.tab = sets.g->device_to_dense(role.gext, st);
     FaP p{};
     p.key = role.pkey; p.list = role.plist; p.fresh = pmode;
     sb.code = A.get<uint8_t>((size_t)nW * 64);
@@ -1441,25 +1462,9 @@ static bool stream_build(const ibh_regrid_matrices *rm, const MatSpec *sp, const
         IBH_HIP(hipMemsetAsync(sb.cntE + gW1, 0, 1, st));
         IBH_HIP(hipMemsetAsync(sb.cntO + gW1, 0, 1, st));
     }
-    const dim3 gs(ceil_div(sb.gx1 - sb.gx0, (long)SA_TILE)), gr4(ceil_div(nr, 4));
+    const dim3 gs(ceil_div(sb.gx1 - sb.gx0, (long)SA_TILE));
     hipLaunchKernelGGL((k_sa_flags<EP>), gs, dim3(SA_T), 0, st, rg, pl, sb, role.pkey == KEY_X ? 1 : 0, p.fresh, role.plist, g_is_row ? 0 : 1, d_cnt, emc);
-    const long mean = nX / std::max(nAr, 1);
-    // (straddlers of a range ~ its perimeter: a range of ~10^3 cells has a few dozen, one of 10^4 a few hundred)
-    const int forced_os = get_tuning("assemble_stream_oldseg", -1);
-    const int oldseg = (forced_os == SA_OLDSEG_S || forced_os == SA_OLDSEG_L) ? forced_os : mean <= 2048 ? SA_OLDSEG_S : SA_OLDSEG_L;
-    if (EP) {
-        // waves per range by the size of the ranges: one wave walks ~10^3 cells in a few round trips; longer ranges are cut
-        const int forced = get_tuning("assemble_stream_wpr", -1);
-        const int wpr = (forced == 1 || forced == 4 || forced == 16) ? forced : mean <= 1024 ? 1 : mean <= 4096 ? 4 : 16;
-#define SA_LAUNCH_RANGES(RT)                                                                                                    \
-        do {                                                                                                                \
-            if (wpr == 1) hipLaunchKernelGGL((k_sa_ranges<true, RT, 1>), gr4, dim3(256), 0, st, rg, pl, sb, g, d_cnt + 1, oldseg);    \
-            else if (wpr == 4) hipLaunchKernelGGL((k_sa_ranges<true, RT, 4>), dim3(nr), dim3(256), 0, st, rg, pl, sb, g, d_cnt + 1, oldseg); \
-            else hipLaunchKernelGGL((k_sa_ranges<true, RT, 16>), dim3(nr), dim3(1024), 0, st, rg, pl, sb, g, d_cnt + 1, oldseg);     \
-        } while (0)
-        if (rel32) SA_LAUNCH_RANGES(uint32_t); else SA_LAUNCH_RANGES(uint16_t);
-#undef SA_LAUNCH_RANGES
-    }
+    if (EP) sa_launch_ranges(plan, nr, st, rg, pl, sb, g, d_cnt + 1);
     // scans over the slice (numberings local to it until the offsets of the ranks are known), two launches per set of channels.
     // (world > 1: one more wave than the slice has -- the zero count behind the last one makes the scan yield the totals in place)
     {
@@ -1500,7 +1505,7 @@ static bool stream_build(const ibh_regrid_matrices *rm, const MatSpec *sp, const
     const uint32_t *hme = hh + 8 * rank;
     const uint32_t nnz = (uint32_t)E0[world];
     const int np_d = p.fresh ? (int)P0[world] : (int)role.pext;
-    const int ng_d = g_fresh ? (int)G0[world] : role.gset->n();
+    const int ng_d = g_fresh ? (int)G0[world] : (int)role.g_n;
     // local -> global numbering of this rank's slice
     if (world > 1) hipLaunchKernelGGL(k_sa_shift, dim3(ceil_div(std::max<long>(nwl + 1, nr + 1), 256l)), dim3(256), 0, st, pscan ? sb.Pw : nullptr, g_is_row ? nullptr : sb.Lw,
                        gW0, nwl + 1, (uint32_t)(P0[rank] - hme[6]), (uint32_t)(L0[rank] - hme[7]), g.gbase, g.ebase, sb.sr0, nr, (uint32_t)G0[rank], (uint32_t)E0[rank]);
@@ -1525,47 +1530,10 @@ static bool stream_build(const ibh_regrid_matrices *rm, const MatSpec *sp, const
     w->wM.alloc((size_t)nrow); w->Mw.alloc((size_t)ncol);
     FaOut o{w->rowptr.p, w->colind.p, w->val.p, w->wM.p, w->Mw.p, sp->family, scale, correctA, 0};
     uint32_t *flags = d_cnt + 1;
-    // row kernel: a 16-lane row of a wave per segment.  One-class matrices: four consecutive ranges per wave; elevation classes: a
-    // wave per range and group of four classes, y = the groups a range has on average, + 1 (the others loop)
-    const int forced_r4 = get_tuning("assemble_stream_rows4", -1);
-    // (measured on the Antarctic sheet, same box, four segments per wave against one: the column sums of the I/X-row matrices win
-    // -- IvA 0.902 / 0.939 ms, IvE 1.53 / 1.55, XvE 1.14 / 1.20; the rows of AvI are even, 0.684 / 0.686, but with 128 values of a
-    // segment in registers -- more cost occupancy: 146 VGPRs at 256 -- the scaling re-reads the rest: 264 against 176 MB fetched; EvI
-    // loses, 1.33 / 1.25: a range has two or three classes there, a quarter to half of the rows idle.  So: column sums only.)
-    const bool rows4 = oldseg == SA_OLDSEG_S && (forced_r4 >= 0 ? forced_r4 != 0 : !g_is_row);
-    const int rows_wpb = 4;
-    const int rows_waves = g.NC == 1 ? ceil_div(nr, 4) : nr;
-    const int rows_y = g.NC == 1 ? 1 : std::max(1, std::min((std::min(g.NC, 16) + 3) / 4, ((int)(hme[3] / (uint32_t)std::max(nr, 1)) + 2 + 3) / 4));
-    const dim3 grq(ceil_div(rows_waves, rows_wpb), rows_y);
-    // (long ranges: one wave per (range, class), y = the classes a range has on average, rounded up, + 1)
-    const dim3 grq1(ceil_div(nr, 4), g.NC == 1 ? 1 : std::max(1, std::min(std::min(g.NC, 16), (int)(hme[3] / (uint32_t)std::max(nr, 1)) + 2)));
-    // the lane-parallel row kernel (k_sa_oldsort + k_sa_rowsL), R ranges per wave.  Measured on the Antarctic sheet, same box, against
-    // the kernels above: the column sums of IvE 42 + 149 us against 231 (IvE 1.55 -> 1.43 ms, IvA 0.937 -> 0.910), the rows of AvI 25 +
-    // 143 against 138, of EvI 42 + 340 against 270 -- a wave with sixteen chains waits for its memory round trips with two waves per
-    // SIMD (66 KB of LDS per workgroup), and R = 4 beats 16: more waves matter more than full lanes.  1 km Greenland (1 143 long
-    // ranges) loses by 2 x.  So: column sums of grids with many ranges only.
-    const int forced_rl = get_tuning("assemble_stream_rowsl", -1);
-    const bool rowsl = forced_rl >= 0 ? forced_rl != 0 : (!g_is_row && nAr >= 16384);       // (by the whole grid's ranges: every rank of a shared build takes the same kernel)
-    const int avg_cls = g.NC == 1 ? 1 : std::max(1, (int)((G0[world] + (uint64_t)std::max(nAr, 1) - 1) / (uint64_t)std::max(nAr, 1)));     // (the whole grid's, as rowsl)
-    const int rows_R = std::max(1, std::min(16, get_tuning("assemble_stream_rowsl_r", std::min(4, 16 / avg_cls))));
-    const dim3 grl(ceil_div(nr, 4 * rows_R));
+    const StreamRowsPlan rows = plan_stream_rows(plan, nr, hme[3], G0[world]);
     double *sval = nullptr;
     int32_t *sdid = nullptr;
-    // the emit pass: one cell per thread (four with 32-bit offsets), at most EMIT_BLOCKS workgroups.  The pass is bound by instruction
-    // issue and latency, not by bandwidth (ablation on the Antarctic AvI: 129 us with every load of cell data, every term and every
-    // store removed; stores +95, the first-seen lookup of the straddlers +45 after the bitmask change, +115 before): a workgroup that
-    // walks several tiles has the code bytes of its next tile in flight while it works.  Measured (cells per thread x workgroups), a1h
-    // AvI / IvA / EvI / IvE ms, same box: 2 x full grid 0.645 /
-    // 0.915 / 1.216 / 1.604; 1 x full 0.704 / 0.919 / 1.228 / 1.555; 1 x 8192 0.636 / 0.878 / 1.135 / 1.470; 2 x 8192 0.642 / 0.926 /
-    // 1.183 / 1.574; 4 x full 0.709 / 1.063 / 1.274 / 1.711
-    constexpr long EMIT_BLOCKS = 8192;
     const long ncell = sb.gx1 - sb.gx0;
-    auto egrid = [&](int cpt) { const long full = ceil_div(ncell, (long)SA_T * cpt); return dim3((unsigned)std::min(full, EMIT_BLOCKS)); };
-#define SA_LAUNCH_EMIT(GR)                                                                                                      \
-    do {                                                                                                                        \
-        if (rel32) hipLaunchKernelGGL((k_sa_emit<EP, GR, uint32_t, 4>), egrid(4), dim3(SA_T), 0, st, rg, pl, *sp, g, p, sb, merge, o, sval, sdid); \
-        else hipLaunchKernelGGL((k_sa_emit<EP, GR, uint16_t, 1>), egrid(1), dim3(SA_T), 0, st, rg, pl, *sp, g, p, sb, merge, o, sval, sdid);       \
-    } while (0)
     sb.end_row = nrow; sb.end_nnz = nnz;
     int32_t *kidx = nullptr;                                     // shared build, identity ice rows: the ice cell / row length of every P key, in first-seen order
     uint8_t *klen = nullptr;
@@ -1588,7 +1556,7 @@ static bool stream_build(const ibh_regrid_matrices *rm, const MatSpec *sp, const
     }
     if (g_is_row) {
         if (ncol && !p.fresh) IBH_HIP(hipMemsetAsync(w->Mw.p, 0, sizeof(double) * (size_t)ncol, st));
-        SA_LAUNCH_EMIT(true);
+        sa_launch_emit<EP, true>(plan, ncell, st, rg, pl, *sp, g, p, sb, merge, o, sval, sdid);
         if (p.key == KEY_I && P.npair) {                      // Mw of the ice cells across one GCM-cell edge
             const dim3 gp2(ceil_div(P.npair, 256));
             hipLaunchKernelGGL((k_sa_pairs<EP, true>), gp2, dim3(256), 0, st, rg, pl, *sp, g, p, sb, P.px1.p, P.px2.p, P.piI.p, P.pa1.p, P.pa2.p, P.npair, o);
@@ -1597,37 +1565,22 @@ static bool stream_build(const ibh_regrid_matrices *rm, const MatSpec *sp, const
             const dim3 gm(ceil_div(P.nmulti3, T));
             hipLaunchKernelGGL((k_fa_pelem<EP, FA_PSUMS, false>), gm, dim3(T), 0, st, rg, pl3, *sp, g, p, merge, (long)P.nmulti3, o, (uint32_t *)nullptr, flags, 1);
         }
-        if (rowsl) {
-            if (oldseg == SA_OLDSEG_S) hipLaunchKernelGGL((k_sa_oldsort<SA_OLDSEG_S>), gr4, dim3(256), 0, st, g, o.colind, o.val, sb.sr0, sb.sr1);
-            else hipLaunchKernelGGL((k_sa_oldsort<SA_OLDSEG_L>), gr4, dim3(256), 0, st, g, o.colind, o.val, sb.sr0, sb.sr1);
-            hipLaunchKernelGGL((k_sa_rowsL<true>), grl, dim3(256), 0, st, rg, pl, g, o, sb.sr0, sb.sr1, rows_R);
-        } else if (rows4) hipLaunchKernelGGL((k_sa_rows<true, SA_OLDSEG_S, 4>), grq, dim3(256), 0, st, rg, pl, g, o, (int32_t *)nullptr, sb.sr0, sb.sr1);
-        else if (oldseg == SA_OLDSEG_S) hipLaunchKernelGGL((k_sa_rows1<true, SA_OLDSEG_S>), grq1, dim3(256), 0, st, rg, pl, g, o, (int32_t *)nullptr, sb.sr0, sb.sr1);
-        else hipLaunchKernelGGL((k_sa_rows1<true, SA_OLDSEG_L>), grq1, dim3(256), 0, st, rg, pl, g, o, (int32_t *)nullptr, sb.sr0, sb.sr1);
+        sa_launch_rows<true>(plan, rows, st, rg, pl, g, o, o.colind, o.val, nullptr, sb.sr0, sb.sr1);
     } else {
         sval = A.get<double>(nnz); sdid = A.get<int32_t>(nnz);
-        SA_LAUNCH_EMIT(false);
+        sa_launch_emit<EP, false>(plan, ncell, st, rg, pl, *sp, g, p, sb, merge, o, sval, sdid);
         if (p.key == KEY_I && P.npair) {                      // the rows of the ice cells across one GCM-cell edge
             const dim3 gp2(ceil_div(P.npair, 256));
             hipLaunchKernelGGL((k_sa_pairs<EP, false>), gp2, dim3(256), 0, st, rg, pl, *sp, g, p, sb, P.px1.p, P.px2.p, P.piI.p, P.pa1.p, P.pa2.p, P.npair, o);
         }
         if (p.key == KEY_I && P.nmulti3) {                    // ... and of the rest of the ice cells with several exchange cells
-            const dim3 gm(ceil_div(P.nmulti3, T));
-            if (!g_fresh) hipLaunchKernelGGL((k_fa_pelem<EP, FA_PEMIT, true>), gm, dim3(T), 0, st, rg, pl3, *sp, g, p, merge, (long)P.nmulti3, o, (uint32_t *)nullptr, flags, 1);
-            else hipLaunchKernelGGL((k_fa_pelem<EP, FA_PEMIT, false>), gm, dim3(T), 0, st, rg, pl3, *sp, g, p, merge, (long)P.nmulti3, o, (uint32_t *)nullptr, flags, 1);
+            fa_launch_pemit<EP>(g_fresh, (long)P.nmulti3, st, rg, pl3, *sp, g, p, merge, o, nullptr, flags, 1);
         }
         if (!g_fresh && ncol) hipLaunchKernelGGL(k_fa_zero_identity, dim3(ceil_div(ncol, T)), dim3(T), 0, st, w->Mw.p, (long)ncol);
         FaOut os = o;
         os.val = sval;
-        if (rowsl) {
-            if (oldseg == SA_OLDSEG_S) hipLaunchKernelGGL((k_sa_oldsort<SA_OLDSEG_S>), gr4, dim3(256), 0, st, g, sdid, sval, sb.sr0, sb.sr1);
-            else hipLaunchKernelGGL((k_sa_oldsort<SA_OLDSEG_L>), gr4, dim3(256), 0, st, g, sdid, sval, sb.sr0, sb.sr1);
-            hipLaunchKernelGGL((k_sa_rowsL<false>), grl, dim3(256), 0, st, rg, pl, g, os, sb.sr0, sb.sr1, rows_R);
-        } else if (rows4) hipLaunchKernelGGL((k_sa_rows<false, SA_OLDSEG_S, 4>), grq, dim3(256), 0, st, rg, pl, g, os, sdid, sb.sr0, sb.sr1);
-        else if (oldseg == SA_OLDSEG_S) hipLaunchKernelGGL((k_sa_rows1<false, SA_OLDSEG_S>), grq1, dim3(256), 0, st, rg, pl, g, os, sdid, sb.sr0, sb.sr1);
-        else hipLaunchKernelGGL((k_sa_rows1<false, SA_OLDSEG_L>), grq1, dim3(256), 0, st, rg, pl, g, os, sdid, sb.sr0, sb.sr1);
+        sa_launch_rows<false>(plan, rows, st, rg, pl, g, os, sdid, sval, sdid, sb.sr0, sb.sr1);
     }
-#undef SA_LAUNCH_EMIT
     IBH_HIP(hipGetLastError());
     if (world > 1) {                                             // exchange 3: the pieces of the result
         // A/E-row matrix: CSR by entries of the ranges, rows by classes; I/X-row matrix: CSR by row entries, rows by P keys (an
@@ -1684,10 +1637,9 @@ static bool stream_build(const ibh_regrid_matrices *rm, const MatSpec *sp, const
                                (long)P0[rank + 1], nkeys, w->rowptr.p, w->colind.p, w->val.p, w->wM.p);
         if (pairs && npk) hipLaunchKernelGGL(k_sa_unpack_mw, dim3((unsigned)ceil_div(npk, 256l)), dim3(256), 0, st, cidx, cval, (long)Cl[rank], (long)Cl[rank + 1], npk, w->Mw.p);
     }
-    role.pset->adopt_device(std::move(ptable), np_d, role.pext);
-    role.gset->adopt_device(std::move(gtable), ng_d, role.gext);
+    sets.p->adopt_device(std::move(ptable), np_d, role.pext);
+    sets.g->adopt_device(std::move(gtable), ng_d, role.gext);
     IBH_HIP(hipStreamSynchronize(st));
-    w->built_fast = world > 1 ? 3 : 2;
     // (flags raised by the later kernels -- a straddler list that overflowed -- cannot differ from the count pass's; checked there)
     return true;
 }

@@ -5,6 +5,7 @@ bench.py's cpu_baseline leg.  The product package (icebin_amd/) never imports
 this module.  See icebin_oracle.h for scope and parity status.
 """
 import ctypes as C
+import fcntl
 import os
 import subprocess
 
@@ -18,10 +19,24 @@ def build(force=False):
     so = os.path.join(_HERE, "liboracle.so")
     src = os.path.join(_HERE, "icebin_oracle.c")
     hdr = os.path.join(_HERE, "icebin_oracle.h")
-    stale = (not os.path.exists(so)) or any(
-        os.path.getmtime(f) > os.path.getmtime(so) for f in (src, hdr))
-    if force or stale:
-        subprocess.check_call(["make", "-C", _HERE, "-s", "-B", "liboracle.so"])
+    def stale():
+        return (not os.path.exists(so)) or any(os.path.getmtime(f) > os.path.getmtime(so) for f in (src, hdr))
+    if force or stale():
+        # Several processes may find the library stale at once (the spawned ranks of a distributed test): one of them builds it,
+        # under a lock on this directory, into a file of its own that then replaces the library whole -- nobody loads half a file.
+        fd = os.open(_HERE, os.O_RDONLY)
+        try:
+            fcntl.flock(fd, fcntl.LOCK_EX)
+            if force or stale():
+                tmp = "liboracle.so.%d.tmp" % os.getpid()
+                try:
+                    subprocess.check_call(["make", "-C", _HERE, "-s", "-B", "liboracle.so", "OUT=" + tmp])
+                    os.replace(os.path.join(_HERE, tmp), so)
+                finally:
+                    if os.path.exists(os.path.join(_HERE, tmp)):
+                        os.remove(os.path.join(_HERE, tmp))
+        finally:
+            os.close(fd)
     return so
 
 

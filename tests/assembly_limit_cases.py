@@ -8,7 +8,8 @@ property its case claims; tests/test_gpu_assembly_limits.py runs every case on t
 and compares it with the oracle bit for bit; tests/test_capi_symbols.py checks that KERNELS names exactly the k_plan_* / k_fa_* /
 k_sa_* kernels of the code object.
 
-THRESHOLDS  one row per condition: where it sits, what is measured, and the value on each side ("in" / "over": any value on that side);
+THRESHOLDS  one row per condition: where it sits (host-decided rows: the rule function of icebin_amd/csrc/asm_plan.h, checked on both
+            sides by tests/cpp/test_asm_plan.cpp; limits the kernels detect: file and line), what is measured, and the value on each side ("in" / "over": any value on that side);
             INSIDE holds the predicate "inside the limit" of every row.
 CASES       one dict per case:
   grid      the description build_grid takes;
@@ -28,34 +29,34 @@ TINY = 1e-290                          # k_plan_ifirst: a nonzero |area| below t
 
 # name -> (where, what is measured, value inside the limit, value beyond it; "in" / "over": any value on that side)
 THRESHOLDS = {
-    "sorted": ("fastasm.inl:76 k_plan_flags", "adjacent (iA, iI) pairs out of order", 0, 1),
-    "nhc": ("fastasm.inl:171 ensure_plan", "elevation classes (nhc <= FA_NC = 64)", 64, 65),
-    "ilmax": ("fastasm.inl:100 k_plan_ifirst", "exchange cells of one ice cell (<= FA_ILMAX = 8)", 8, 9),
-    "dupmax": ("fastasm.inl:83 k_plan_ranges", "longest run of one (iA, iI) pair (<= FA_DUPMAX = 4)", 4, 5),
-    "tiny": ("fastasm.inl:110 k_plan_ifirst", "smallest nonzero |area| (>= 1e-290 keeps the static counts)", TINY, np.nextafter(TINY, 0.0)),
-    "rel32_ep": ("streamasm.inl:1372 stream_build", "2 * longest range (elevation-class builds; <= 65535: 16-bit positions)", 65534, 65536),
-    "rel32": ("streamasm.inl:1372 stream_build", "longest range (builds without classes; <= 65535: 16-bit positions)", 65535, 65536),
-    "emit_blocks": ("streamasm.inl:1561 EMIT_BLOCKS", "exchange cells of a 32-bit-position grid (<= 8192 workgroups x 1024 cells)", "in", "over"),
-    "oldseg_s": ("streamasm.inl:358 k_sa_ranges / :262 k_sa_rangecounts", "straddlers of one (range, class) segment, small table (<= 128)", 128, 129),
-    "oldseg_l": ("streamasm.inl:358 k_sa_ranges / :262 k_sa_rangecounts", "straddlers of one (range, class) segment, large table (<= 512)", 512, 513),
-    "default_oldseg": ("streamasm.inl:1449 stream_build", "mean range length (<= 2048: the small straddler table)", "in", "over"),
-    "default_wpr4": ("streamasm.inl:1453 stream_build", "mean range length (<= 1024: one wave per range)", "in", "over"),
-    "default_wpr16": ("streamasm.inl:1453 stream_build", "mean range length (<= 4096: four waves per range)", "in", "over"),
-    "default_rowsl": ("streamasm.inl:1548 stream_build", "ranges (< 16384: no lane-parallel row kernel)", "in", "over"),
-    "fa_oldmax": ("fastasm.inl:647 k_fa_count / :1178 k_fa_range", "straddling entries of one range (<= FA_OLDMAX = 512)", 512, 513),
-    "lcap_s0": ("fastasm.inl:995 k_fa_range<128, 2>", "entries of one range (<= LCAP = 1024: values in LDS)", 1024, 1025),
-    "lcap_s1": ("fastasm.inl:995 k_fa_range<256, 4>", "entries of one range (<= LCAP = 2048)", 2048, 2049),
-    "lcap_s2": ("fastasm.inl:995 k_fa_range<1024, 4>", "entries of one range (<= LCAP = 4096)", 4096, 4097),
-    "lcap_s3": ("fastasm.inl:995 k_fa_range<1024, 1>", "entries of one range (<= LCAP = 4096)", 4096, 4097),
-    "pass_s0": ("fastasm.inl:1505 shape 0 (128 x 2)", "range length against one pass of 256 cells", 256, 257),
-    "pass_s1": ("fastasm.inl:1505 shape 1 (256 x 4)", "range length against one pass of 1024 cells", 1024, 1025),
-    "pass_s2": ("fastasm.inl:1505 shape 2 (1024 x 4)", "range length against one pass of 4096 cells", 4096, 4097),
-    "pass_s3": ("fastasm.inl:1505 shape 3 (1024 x 1)", "range length against one pass of 1024 cells", 1024, 1025),
-    "stream_default": ("streamasm.inl:1346 stream_build", "exchange cells (< 2^20: no streamed build by default)", (1 << 20) - 1, 1 << 20),
-    "optimistic": ("fastasm.inl:1785 fast_build_gp", "exchange cells (<= 2^20: outputs by upper bounds, one read-back)", 1 << 20, (1 << 20) + 1),
-    "chained": ("fastasm.inl:1786 fast_build_gp", "ranges (x 1 class) of a one-class build (< 2^15: scans chained in k_fa_count)", 32767, 32768),
-    "rscan_many": ("fastasm.inl:1856 fast_build_gp", "ranges of an unchained build (<= 4096: k_fa_rscan in one workgroup)", 4096, 4097),
-    "psums": ("fastasm.inl:1921 fast_build_gp", "ice cells with several exchange cells (<= 2^20: k_fa_psums8)", "in", "over"),
+    "sorted": ("fastasm.inl:65 k_plan_flags", "adjacent (iA, iI) pairs out of order", 0, 1),
+    "nhc": ("fastasm.inl:169 ensure_plan (the streamed build: asm_plan.h plan_stream)", "elevation classes (nhc <= FA_NC = 64)", 64, 65),
+    "ilmax": ("fastasm.inl:98 k_plan_ifirst", "exchange cells of one ice cell (<= FA_ILMAX = 8)", 8, 9),
+    "dupmax": ("fastasm.inl:81 k_plan_ranges", "longest run of one (iA, iI) pair (<= FA_DUPMAX = 4)", 4, 5),
+    "tiny": ("fastasm.inl:108 k_plan_ifirst", "smallest nonzero |area| (>= 1e-290 keeps the static counts)", TINY, np.nextafter(TINY, 0.0)),
+    "rel32_ep": ("asm_plan.h stream_rel32", "2 * longest range (elevation-class builds; <= 65535: 16-bit positions)", 65534, 65536),
+    "rel32": ("asm_plan.h stream_rel32", "longest range (builds without classes; <= 65535: 16-bit positions)", 65535, 65536),
+    "emit_blocks": ("asm_plan.h stream_emit_grid (EMIT_BLOCKS)", "exchange cells of a 32-bit-position grid (<= 8192 workgroups x 1024 cells)", "in", "over"),
+    "oldseg_s": ("streamasm.inl:354 k_sa_ranges / :258 k_sa_rangecounts", "straddlers of one (range, class) segment, small table (<= 128)", 128, 129),
+    "oldseg_l": ("streamasm.inl:354 k_sa_ranges / :258 k_sa_rangecounts", "straddlers of one (range, class) segment, large table (<= 512)", 512, 513),
+    "default_oldseg": ("asm_plan.h stream_oldseg", "mean range length (<= 2048: the small straddler table)", "in", "over"),
+    "default_wpr4": ("asm_plan.h stream_wpr", "mean range length (<= 1024: one wave per range)", "in", "over"),
+    "default_wpr16": ("asm_plan.h stream_wpr", "mean range length (<= 4096: four waves per range)", "in", "over"),
+    "default_rowsl": ("asm_plan.h stream_rowsl", "ranges (< 16384: no lane-parallel row kernel)", "in", "over"),
+    "fa_oldmax": ("fastasm.inl:644 k_fa_count / :1163 k_fa_range", "straddling entries of one range (<= FA_OLDMAX = 512)", 512, 513),
+    "lcap_s0": ("fastasm.inl:980 k_fa_range<128, 2>", "entries of one range (<= LCAP = 1024: values in LDS)", 1024, 1025),
+    "lcap_s1": ("fastasm.inl:980 k_fa_range<256, 4>", "entries of one range (<= LCAP = 2048)", 2048, 2049),
+    "lcap_s2": ("fastasm.inl:980 k_fa_range<1024, 4>", "entries of one range (<= LCAP = 4096)", 4096, 4097),
+    "lcap_s3": ("fastasm.inl:980 k_fa_range<1024, 1>", "entries of one range (<= LCAP = 4096)", 4096, 4097),
+    "pass_s0": ("asm_plan.h FA_SHAPE_T x FA_SHAPE_CPT, shape 0 (128 x 2)", "range length against one pass of 256 cells", 256, 257),
+    "pass_s1": ("asm_plan.h FA_SHAPE_T x FA_SHAPE_CPT, shape 1 (256 x 4)", "range length against one pass of 1024 cells", 1024, 1025),
+    "pass_s2": ("asm_plan.h FA_SHAPE_T x FA_SHAPE_CPT, shape 2 (1024 x 4)", "range length against one pass of 4096 cells", 4096, 4097),
+    "pass_s3": ("asm_plan.h FA_SHAPE_T x FA_SHAPE_CPT, shape 3 (1024 x 1)", "range length against one pass of 1024 cells", 1024, 1025),
+    "stream_default": ("asm_plan.h stream_default", "exchange cells (< 2^20: no streamed build by default)", (1 << 20) - 1, 1 << 20),
+    "optimistic": ("asm_plan.h range_optimistic", "exchange cells (<= 2^20: outputs by upper bounds, one read-back)", 1 << 20, (1 << 20) + 1),
+    "chained": ("asm_plan.h range_chained", "ranges (x 1 class) of a one-class build (< 2^15: scans chained in k_fa_count)", 32767, 32768),
+    "rscan_many": ("asm_plan.h range_scan_form", "ranges of an unchained build (<= 4096: k_fa_rscan in one workgroup)", 4096, 4097),
+    "psums": ("asm_plan.h range_sums_form", "ice cells with several exchange cells (<= 2^20: k_fa_psums8)", "in", "over"),
 }
 # the predicate "inside the limit" of each row, on the measured value
 INSIDE = {
@@ -332,6 +333,6 @@ KERNELS.update({
 # instantiated but unreachable: kernel -> why no build launches it (test_capi_symbols.py accepts these and no others)
 UNREACHABLE = {
     # a pre-populated column set is an E set (fast_build), and every matrix with E keys is an elevation-class build (EP = true):
-    # the EP = false instantiation of the per-row selection branch (fastasm.inl fast_build_gp, streamasm.inl stream_build) is dead
+    # the EP = false instantiation of the per-row selection branch (fastasm.inl fa_launch_pemit) is dead
     "k_fa_pelem<false, 2, true>": "pre-populated G sets are E sets, and E-key builds are always elevation-class (EP) builds",
 }
