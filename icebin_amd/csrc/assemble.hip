@@ -18,6 +18,7 @@
 // CSR structure, dims, wM, Mw and M are bit-identical to the oracle.
 #include "assemble.h"
 #include "asm_plan.h"
+#include "smooth_plan.h"
 #include "csrops.h"
 #include "prims.h"
 #include "sparseset.h"
@@ -1141,7 +1142,7 @@ __global__ void k_smooth_prod_emit(const uint64_t *__restrict__ skeys, const uin
 // order instead of ascending j: entries agree with the triplet pipeline to rounding (the smoothing test's tolerance: the
 // reference's RTree order is not reproducible either); the structure is identical.  Rows with more than SMD_MAXCOL columns
 // send the build to the triplet pipeline.
-constexpr int SMD_HASH = 256, SMD_MAXCOL = 128, SMD_HITS = 1024, SMD_WAVES = 4;
+// (SMD_HASH, SMD_MAXCOL, SMD_HITS, SMD_WAVES: smooth_plan.h)
 __device__ __forceinline__ double smd_wave_sum(double v) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
@@ -1292,8 +1293,7 @@ __global__ __launch_bounds__(SMD_WAVES * 64) void k_smooth_direct(SmoothView v, 
 // oracle's ascending-j order to rounding (the test's 1e-12).
 // More than SMT_KMAX columns around a bin, or a member row of M with more than SMT_ROWMAX entries: the triplet pipeline serves
 // the build.
-constexpr int SMT_KMAX = 128, SMT_ROWMAX = 8, SMT_HASH = 1024;
-struct SmtCand { double x, y, z, area; };
+// (SMT_KMAX, SMT_ROWMAX, SMT_HASH, SmtCand: smooth_plan.h)
 // compact records in member (bin) order: position / elevation / area, and the member's row of M entry-major
 // (mcol[e * nmem + q], mval[...]): the tile kernel stages them with coalesced, independent loads
 // (the member positions [q0, q1): a rank of a shared build packs the candidates of its own bins only)
@@ -1369,13 +1369,15 @@ __global__ __launch_bounds__(64) void k_smt_tile(SmoothView v, const uint32_t *_
                                                  const int32_t *__restrict__ bincols, const int32_t *__restrict__ binK,
                                                  const uint32_t *__restrict__ wstart, const int32_t *__restrict__ wavebin, int w0, int kstride,
                                                  double *__restrict__ scratch, unsigned long long *__restrict__ pres, uint32_t *__restrict__ rowlen) {
-    extern __shared__ double smt_lds[];
-    double *acc = smt_lds;                                       // [K][64]
-    SmtCand *s_c = reinterpret_cast<SmtCand *>(smt_lds + (size_t)kstride * 64);      // [64]
-    double *s_val = reinterpret_cast<double *>(s_c + 64);        // [64][SMT_ROWMAX]
-    int *s_cols = reinterpret_cast<int *>(s_val + 64 * SMT_ROWMAX);                  // [SMT_KMAX]
-    unsigned char *s_slot = reinterpret_cast<unsigned char *>(s_cols + SMT_KMAX);    // [64][SMT_ROWMAX]
-    unsigned char *s_ne = s_slot + 64 * SMT_ROWMAX;             // [64]
+    extern __shared__ double smt_mem[];
+    const SmtLds at = smt_lds(kstride);                          // (the layout and its size: smooth_plan.h)
+    unsigned char *const lds = reinterpret_cast<unsigned char *>(smt_mem);
+    double *acc = reinterpret_cast<double *>(lds + at.acc);      // [K][64]
+    SmtCand *s_c = reinterpret_cast<SmtCand *>(lds + at.s_c);    // [64]
+    double *s_val = reinterpret_cast<double *>(lds + at.s_val);  // [64][SMT_ROWMAX]
+    int *s_cols = reinterpret_cast<int *>(lds + at.s_cols);      // [SMT_KMAX]
+    unsigned char *s_slot = lds + at.s_slot;                     // [64][SMT_ROWMAX]
+    unsigned char *s_ne = lds + at.s_ne;                         // [64]
     const int w = w0 + (int)blockIdx.x, lane = threadIdx.x;       // (w0: the first wave of a rank's bins in a shared build)
     const int b = wavebin[w], bx = b % v.nbx, by = b / v.nbx;
     const int K = binK[b];
@@ -1519,249 +1521,268 @@ static void smooth_check(const ibh_regrid_matrices *rm, const double sigma[3]) {
     IBH_CHECK(rm->rg->has_centroid, "smoothing (sigma != 0) needs the ice grid's centroid_xy (ibh_regridder_desc.I_centroid_xy)");
     IBH_CHECK(sigma[0] > 0 && sigma[1] > 0 && sigma[2] > 0, "smoothing needs three positive sigmas, got (%g, %g, %g)", sigma[0], sigma[1], sigma[2]);
 }
-// comm (world > 1): every rank of the communicator calls this with the same matrix; the tile form is shared (w->built_fast = 3),
-// the direct form and the triplet pipeline run on every rank.  The result is the same bits on every rank and for every world.
-static void smooth_matrix(ibh_weighted *w, const ibh_regrid_matrices *rm, const int64_t *row_s, const double sigma[3],
-                          hipStream_t st, ibh_comm *comm = nullptr) {
+// ---- the smoothed build on the host: smooth_matrix (below) takes the plan (smooth_plan.h), bins the rows and tries the plan's forms in
+// order; a form builds a new CSR beside the one it reads and returns false, with nothing touched, when its tables overflow
+constexpr int SMOOTH_NO_BAD = 0x7fffffff;
+struct SmoothBins {
+    SmoothView v;
+    size_t nbins;
+    const uint32_t *binstart;   // [nbins + 1]: the bins' first member positions
+    const int32_t *members;     // [binstart[nbins]] unmasked rows, bin by bin, ascending in a bin
+    uint32_t *d_cnt;            // four words a form reads back at once: three of its own, and the smallest dense row whose area is zero
+    const int64_t *row_s;       // (SMOOTH_NO_BAD: none)
+};
+struct SmoothedCsr {
+    DevBuf<int32_t> rowptr, colind;
+    DevBuf<double> val;
+    int64_t nnz = 0;
+    bool shared = false;        // the ranks of a communicator built it together
+};
+// "Area of cell %ld must be non-zero", smoother.cpp:89-90: d = the fourth counter word, as a form's first read-back brought it
+static void fail_zero_area(const int64_t *row_s, int d) {
+    if (d == SMOOTH_NO_BAD) return;
+    int64_t sc = 0;
+    IBH_HIP(hipMemcpy(&sc, row_s + d, sizeof(int64_t), hipMemcpyDeviceToHost));
+    fail(IBH_EINVAL, "Area of cell %ld must be non-zero", (long)sc);
+}
+// bin count -> scan -> keys -> sort
+static SmoothBins smooth_bins(const ibh_weighted *w, const ibh_regrid_matrices *rm, const int64_t *row_s, const SmoothGrid &sg,
+                              const double sigma[3], hipStream_t st) {
     const ibh_regridder *g = rm->rg;
-    smooth_check(rm, sigma);
-    if (w->nrow == 0) return;
-    const int world = comm ? comm_world(comm) : 1, rank = comm ? comm_rank(comm) : 0;
     Arena &A = arena();
     const int T = 256, n = w->nrow;
-    SmoothView v{row_s, rm->elevmaskI.p, g->I_centroid.p, w->wM.p, n, sigma[0], sigma[1], sigma[2],
-                 g->cmin[0], g->cmin[1], 2.0 * sigma[0], 2.0 * sigma[1], 1, 1};
-    v.nbx = (int)std::min(4096.0, std::floor((g->cmax[0] - g->cmin[0]) / v.bw) + 1.0);
-    v.nby = (int)std::min(4096.0, std::floor((g->cmax[1] - g->cmin[1]) / v.bh) + 1.0);
-    if (v.nbx == 4096) v.bw = (g->cmax[0] - g->cmin[0]) / 4096.0 * (1 + 1e-12);     // never finer than 4096 bins: bins only grow
-    if (v.nby == 4096) v.bh = (g->cmax[1] - g->cmin[1]) / 4096.0 * (1 + 1e-12);
-    const size_t nbins = (size_t)v.nbx * v.nby;
+    SmoothBins B{};
+    B.v = SmoothView{row_s, rm->elevmaskI.p, g->I_centroid.p, w->wM.p, n, sigma[0], sigma[1], sigma[2], sg.x0, sg.y0, sg.bw, sg.bh, sg.nbx, sg.nby};
+    B.nbins = sg.nbins();
+    B.row_s = row_s;
+    const size_t nbins = B.nbins;
     uint32_t *binstart = A.get<uint32_t>(nbins + 1);
     uint64_t *bkeys = A.get<uint64_t>((size_t)n), *bkeys2 = A.get<uint64_t>((size_t)n);
     uint32_t *brows = A.get<uint32_t>((size_t)n), *brows2 = A.get<uint32_t>((size_t)n);
-    uint32_t *d_cnt = A.get<uint32_t>(4);
-    int *d_bad = reinterpret_cast<int *>(d_cnt + 3);
-    const int big = 0x7fffffff;
+    B.d_cnt = A.get<uint32_t>(4);
+    int *d_bad = reinterpret_cast<int *>(B.d_cnt + 3);
+    const int big = SMOOTH_NO_BAD;
     IBH_HIP(hipMemsetAsync(binstart, 0, sizeof(uint32_t) * (nbins + 1), st));
     IBH_HIP(hipMemcpyAsync(d_bad, &big, sizeof(int), hipMemcpyHostToDevice, st));
     const dim3 grid(ceil_div(n, T));
-    hipLaunchKernelGGL(k_smooth_bin_count, grid, dim3(T), 0, st, v, binstart, d_bad);
+    hipLaunchKernelGGL(k_smooth_bin_count, grid, dim3(T), 0, st, B.v, binstart, d_bad);
     exclusive_scan_u32(binstart, binstart, nbins + 1, nullptr, st);
-    hipLaunchKernelGGL(k_smooth_bin_keys, grid, dim3(T), 0, st, v, (uint32_t)nbins, bkeys, brows);
+    hipLaunchKernelGGL(k_smooth_bin_keys, grid, dim3(T), 0, st, B.v, (uint32_t)nbins, bkeys, brows);
     const KeyField bf{0, bits_for((uint64_t)nbins + 1)};
     if (bf.nbits > 0 && radix_sort_pairs(bkeys, bkeys2, brows, brows2, (size_t)n, &bf, 1, st)) std::swap(brows, brows2);
-    const int32_t *members = reinterpret_cast<const int32_t *>(brows);      // [binstart[nbins]] unmasked rows, bin by bin
-    // (measured: 2 x faster than the triplet pipeline at 20 km -- 0.50 against 1.08 ms, that one is launch-bound there --
-    // but slower at 5 km, 13 against 12 ms: three passes of ~3600 candidate evaluations per row, each five gathers; the
-    // direct form is therefore taken for small problems only.  `smooth_direct`: 1 always, 0 never, -1 by size.)
-    const int direct = get_tuning("smooth_direct", -1);
-    const bool take_direct = direct > 0 || (direct < 0 && n <= get_tuning("smooth_direct_max_rows", 16384));
-    const int tile = get_tuning("smooth_tile", -1);
-    if (tile > 0 || (tile < 0 && !take_direct)) {
-        // tiles (k_smt_*): column tables per bin -> one wave per 64 rows of a bin -> compaction; two read-backs
-        const int nb = (int)nbins;
-        uint32_t h4[4];
-        IBH_HIP(hipMemsetAsync(d_cnt, 0, 3 * sizeof(uint32_t), st));
-        int32_t *bincols = A.get<int32_t>(nbins * SMT_KMAX), *binK = A.get<int32_t>(nbins);
-        uint32_t *binwaves = A.get<uint32_t>(nbins + 1), *wstart = A.get<uint32_t>(nbins + 1);
-        // members of all bins = the unmasked rows: binstart[nbins]
-        hipLaunchKernelGGL(k_smt_bincols, dim3(nb), dim3(256), 0, st, v, binstart, members, w->rowptr.p, w->colind.p, bincols, binK, binwaves, d_cnt + 1);
-        exclusive_scan_u32(binwaves, wstart, nbins, d_cnt, st);
-        IBH_HIP(hipMemcpyAsync(d_cnt + 2, binstart + nbins, sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
-        readback_sync(h4, d_cnt, sizeof(h4), st);
-        if ((int)h4[3] != big) {
-            int64_t sc = 0;
-            IBH_HIP(hipMemcpy(&sc, row_s + (int)h4[3], sizeof(int64_t), hipMemcpyDeviceToHost));
-            fail(IBH_EINVAL, "Area of cell %ld must be non-zero", (long)sc);
-        }
-        if (world > 1) {                // the overflow flag is taken by all ranks together (it is a whole-grid quantity: equal anyway)
-            double *d_fl = A.get<double>((size_t)world);
-            const double mine = (double)h4[1];
-            IBH_HIP(hipMemcpyAsync(d_fl + rank, &mine, sizeof(double), hipMemcpyHostToDevice, st));
-            comm_exchange_blocks(comm, d_fl, 1, 1, st);
-            std::vector<double> fl((size_t)world);
-            readback_sync(fl.data(), d_fl, sizeof(double) * (size_t)world, st);
-            for (double f : fl) h4[1] |= (uint32_t)f;
-        }
-        if (h4[1] == 0) {
-            const int nwaves = (int)h4[0], nmem = (int)h4[2];
-            std::vector<int32_t> hK(nbins);
-            IBH_HIP(hipMemcpy(hK.data(), binK, sizeof(int32_t) * nbins, hipMemcpyDeviceToHost));
-            int kmax = 1;
-            for (size_t q = 0; q < nbins; ++q) kmax = std::max(kmax, hK[q]);
-            uint32_t *rowlen = A.get<uint32_t>((size_t)n + 1);
-            IBH_HIP(hipMemsetAsync(rowlen, 0, sizeof(uint32_t) * ((size_t)n + 1), st));
-            SmtCand *cand = A.get<SmtCand>((size_t)std::max(nmem, 1));
-            int32_t *wavebin = A.get<int32_t>((size_t)std::max(nwaves, 1)), *memberbin = A.get<int32_t>((size_t)std::max(nmem, 1));
-            double *scratch = A.get<double>((size_t)std::max(nwaves, 1) * kmax * 64);
-            unsigned long long *pres = A.get<unsigned long long>(2 * (size_t)std::max(nmem, 1));
-            unsigned char *mne = A.get<unsigned char>((size_t)std::max(nmem, 1));
-            int32_t *mcol = A.get<int32_t>((size_t)std::max(nmem, 1) * SMT_ROWMAX);
-            double *mval = A.get<double>((size_t)std::max(nmem, 1) * SMT_ROWMAX);
-            DevBuf<int32_t> nrowptr((size_t)n + 1);
-            // this rank's share: bins [b0, b1), their member positions [m0, m1) and waves [w0, w1); the candidates [c0, c1) it packs
-            int b0 = 0, b1 = nb, m0 = 0, m1 = nmem, w0 = 0, w1 = nwaves, c0 = 0, c1 = nmem;
-            std::vector<uint32_t> hb;
-            std::vector<int> bs;
-            if (world > 1) {
-                // contiguous bin ranges balanced by work: a bin costs its members times the candidates of its 3 x 3 neighbourhood
-                hb.resize(nbins + 1);
-                IBH_HIP(hipMemcpy(hb.data(), binstart, sizeof(uint32_t) * (nbins + 1), hipMemcpyDeviceToHost));
-                std::vector<double> cw(nbins + 1, 0.0);
-                for (int b = 0; b < nb; ++b) {
-                    const int bx = b % v.nbx, by = b / v.nbx;
-                    const int x0 = std::max(bx - 1, 0), x1 = std::min(bx + 1, v.nbx - 1);
-                    double ncand = 0;
-                    for (int yy = std::max(by - 1, 0); yy <= std::min(by + 1, v.nby - 1); ++yy)
-                        ncand += (double)(hb[(size_t)yy * v.nbx + x1 + 1] - hb[(size_t)yy * v.nbx + x0]);
-                    cw[(size_t)b + 1] = cw[(size_t)b] + (double)(hb[(size_t)b + 1] - hb[(size_t)b]) * ncand;
-                }
-                bs.assign((size_t)world + 1, nb);
-                bs[0] = 0;
-                for (int r = 1; r < world; ++r)
-                    bs[(size_t)r] = std::max(bs[(size_t)r - 1],
-                                             (int)(std::lower_bound(cw.begin(), cw.end(), cw[nbins] * r / world) - cw.begin()));
-                auto waves_before = [&](int bb) {
-                    uint32_t s = 0;
-                    for (int b = 0; b < bb; ++b) s += (hb[(size_t)b + 1] - hb[(size_t)b] + 63) / 64;
-                    return (int)s;
-                };
-                b0 = bs[(size_t)rank]; b1 = bs[(size_t)rank + 1];
-                m0 = (int)hb[(size_t)b0]; m1 = (int)hb[(size_t)b1];
-                w0 = waves_before(b0); w1 = waves_before(b1);
-                c0 = (int)hb[(size_t)std::max(b0 - v.nbx - 1, 0)]; c1 = (int)hb[(size_t)std::min(b1 + v.nbx + 1, nb)];
-            }
-            if (nmem) {
-                if (c1 > c0)
-                    hipLaunchKernelGGL(k_smt_pack, dim3(ceil_div(c1 - c0, T)), dim3(T), 0, st, v, members, c0, c1, nmem, w->rowptr.p, w->colind.p, w->val.p,
-                                       cand, mne, mcol, mval);
-                hipLaunchKernelGGL(k_smt_wavebin, dim3(ceil_div(nb, T)), dim3(T), 0, st, wstart, binwaves, nb, wavebin);
-                hipLaunchKernelGGL(k_smt_memberbin, dim3(nb), dim3(64), 0, st, binstart, nb, memberbin);
-                const size_t lds = (size_t)kmax * 64 * 8 + 64 * sizeof(SmtCand) + 64 * SMT_ROWMAX * 8 + SMT_KMAX * 4 + 64 * SMT_ROWMAX + 64;
-                static std::mutex mu;
-                static bool raised[64] = {};
-                if (lds > 64 * 1024) {
-                    std::lock_guard<std::mutex> lk(mu);
-                    if (!raised[w->device & 63]) {
-                        IBH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_smt_tile), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                        raised[w->device & 63] = true;
-                    }
-                }
-                if (w1 > w0)
-                    hipLaunchKernelGGL(k_smt_tile, dim3(w1 - w0), dim3(64), lds, st, v, binstart, members, cand, mne, mcol, mval, nmem, bincols, binK,
-                                       wstart, wavebin, w0, kmax, scratch, pres, rowlen);
-            }
-            DevBuf<int32_t> ncol;
-            DevBuf<double> nval;
-            uint32_t nnz2 = 0;
-            if (world == 1) {
-                exclusive_scan_u32(rowlen, reinterpret_cast<uint32_t *>(nrowptr.p), (size_t)n, d_cnt, st);
-                readback_sync(h4, d_cnt, sizeof(h4), st);
-                nnz2 = h4[0];
-                IBH_CHECK(nnz2 < (1u << 31), "smoothed matrix too large (%u entries)", nnz2);
-                IBH_HIP(hipMemcpyAsync(nrowptr.p + n, d_cnt, sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
-                ncol.alloc((size_t)nnz2); nval.alloc((size_t)nnz2);
-                if (nmem) hipLaunchKernelGGL(k_smt_emit, dim3(ceil_div(nmem, T)), dim3(T), 0, st, binstart, members, 0, nmem, wstart, memberbin, bincols, kmax, scratch,
-                                             pres, nrowptr.p, (const uint32_t *)nullptr, ncol.p, nval.p);
-            } else {
-                // every rank's rows reach every rank: the row lengths in member order (gatherv) -> the row pointer and the
-                // member-order offsets (scans) -> the rows packed in member order (gatherv) -> placed into the CSR
-                uint32_t *mlen = A.get<uint32_t>((size_t)nmem + 1), *mptr = A.get<uint32_t>((size_t)nmem + 1);
-                if (m1 > m0) hipLaunchKernelGGL(k_smt_mlen, dim3(ceil_div(m1 - m0, T)), dim3(T), 0, st, members, m0, m1, rowlen, mlen);
-                std::vector<int64_t> ol((size_t)world + 1), oc((size_t)world + 1), ov((size_t)world + 1);
-                for (int r = 0; r <= world; ++r) ol[(size_t)r] = 4 * (int64_t)hb[(size_t)bs[(size_t)r]];
-                {
-                    void *bases[1] = {mlen};
-                    const int64_t *offs[1] = {ol.data()};
-                    comm_gatherv(comm, 1, bases, offs, st);
-                }
-                if (nmem) hipLaunchKernelGGL(k_smt_rowlen, dim3(ceil_div(nmem, T)), dim3(T), 0, st, members, nmem, mlen, rowlen);
-                exclusive_scan_u32(rowlen, reinterpret_cast<uint32_t *>(nrowptr.p), (size_t)n, d_cnt, st);
-                exclusive_scan_u32(mlen, mptr, (size_t)nmem, mptr + nmem, st);
-                IBH_HIP(hipMemcpyAsync(nrowptr.p + n, d_cnt, sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
-                std::vector<uint32_t> hp((size_t)world + 1);
-                for (int r = 0; r <= world; ++r)
-                    IBH_HIP(hipMemcpyAsync(&hp[(size_t)r], mptr + hb[(size_t)bs[(size_t)r]], sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-                IBH_HIP(hipStreamSynchronize(st));
-                nnz2 = hp[(size_t)world];
-                IBH_CHECK(nnz2 < (1u << 31), "smoothed matrix too large (%u entries)", nnz2);
-                for (int r = 0; r <= world; ++r) { oc[(size_t)r] = 4 * (int64_t)hp[(size_t)r]; ov[(size_t)r] = 8 * (int64_t)hp[(size_t)r]; }
-                DevBuf<int32_t> pcol((size_t)nnz2);
-                DevBuf<double> pval((size_t)nnz2);
-                if (m1 > m0) hipLaunchKernelGGL(k_smt_emit, dim3(ceil_div(m1 - m0, T)), dim3(T), 0, st, binstart, members, m0, m1, wstart, memberbin, bincols, kmax,
-                                                scratch, pres, (const int32_t *)nullptr, mptr, pcol.p, pval.p);
-                {
-                    void *bases[2] = {pcol.p, pval.p};
-                    const int64_t *offs[2] = {oc.data(), ov.data()};
-                    comm_gatherv(comm, 2, bases, offs, st);
-                }
-                ncol.alloc((size_t)nnz2); nval.alloc((size_t)nnz2);
-                if (nmem) hipLaunchKernelGGL(k_smt_place, dim3(ceil_div(nmem, T)), dim3(T), 0, st, members, nmem, mlen, mptr, nrowptr.p, pcol.p, pval.p,
-                                             ncol.p, nval.p);
-                IBH_HIP(hipGetLastError());
-                IBH_HIP(hipStreamSynchronize(st));          // (pcol / pval are freed on leaving this scope)
-                w->built_fast = 3;
-            }
-            IBH_HIP(hipGetLastError());
-            IBH_HIP(hipStreamSynchronize(st));
-            w->rowptr = std::move(nrowptr); w->colind = std::move(ncol); w->val = std::move(nval);
-            w->nnz = nnz2;
-            w->conservative = 0;            // conservative = !smooth, RegridMatrices_Dynamic.cpp:167
-            return;
-        }
-        // more than SMT_KMAX columns around a bin, or a member row longer than SMT_ROWMAX: the pipelines below serve the build
+    B.binstart = binstart;
+    B.members = reinterpret_cast<const int32_t *>(brows);
+    return B;
+}
+
+// ---- the tile form (k_smt_*): column tables per bin -> one wave per 64 rows of a bin -> compaction ------------------------------------
+struct SmtBuild {               // what the steps of the tile form share
+    int32_t *bincols, *binK;
+    uint32_t *binwaves, *wstart;
+    int nwaves, nmem, kmax;     // waves and members of all bins (the members = the unmasked rows), the widest column table
+    uint32_t *rowlen;
+    SmtCand *cand;
+    int32_t *wavebin, *memberbin;
+    double *scratch;
+    unsigned long long *pres;
+    unsigned char *mne;
+    int32_t *mcol;
+    double *mval;
+};
+// the column tables, the waves per bin and the overflow flags; the first read-back.  world > 1: the flag is taken by all ranks
+// together (it is a whole-grid quantity: equal anyway).  false: more than SMT_KMAX columns around a bin, or a member row longer than
+// SMT_ROWMAX
+static bool smt_tables(const SmoothBins &B, const ibh_weighted *w, ibh_comm *comm, hipStream_t st, SmtBuild *t) {
+    Arena &A = arena();
+    const size_t nbins = B.nbins;
+    uint32_t h4[4];
+    IBH_HIP(hipMemsetAsync(B.d_cnt, 0, 3 * sizeof(uint32_t), st));
+    t->bincols = A.get<int32_t>(nbins * SMT_KMAX); t->binK = A.get<int32_t>(nbins);
+    t->binwaves = A.get<uint32_t>(nbins + 1); t->wstart = A.get<uint32_t>(nbins + 1);
+    hipLaunchKernelGGL(k_smt_bincols, dim3((int)nbins), dim3(256), 0, st, B.v, B.binstart, B.members, w->rowptr.p, w->colind.p, t->bincols, t->binK,
+                       t->binwaves, B.d_cnt + 1);
+    exclusive_scan_u32(t->binwaves, t->wstart, nbins, B.d_cnt, st);
+    IBH_HIP(hipMemcpyAsync(B.d_cnt + 2, B.binstart + nbins, sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+    readback_sync(h4, B.d_cnt, sizeof(h4), st);
+    fail_zero_area(B.row_s, (int)h4[3]);
+    if (comm && comm_world(comm) > 1) {
+        const int world = comm_world(comm);
+        double *d_fl = A.get<double>((size_t)world);
+        const double mine = (double)h4[1];
+        IBH_HIP(hipMemcpyAsync(d_fl + comm_rank(comm), &mine, sizeof(double), hipMemcpyHostToDevice, st));
+        comm_exchange_blocks(comm, d_fl, 1, 1, st);
+        std::vector<double> fl((size_t)world);
+        readback_sync(fl.data(), d_fl, sizeof(double) * (size_t)world, st);
+        for (double f : fl) h4[1] |= (uint32_t)f;
     }
-    if (take_direct) {
-        // direct rows (k_smooth_direct): count -> scan -> emit; one read-back (error word, overflow flag, nnz)
-        uint32_t *rowlen = A.get<uint32_t>((size_t)n + 1);
-        IBH_HIP(hipMemsetAsync(d_cnt, 0, 3 * sizeof(uint32_t), st));
-        const dim3 gd(ceil_div(n, SMD_WAVES));
-        hipLaunchKernelGGL(k_smooth_direct<false>, gd, dim3(SMD_WAVES * 64), 0, st, v, binstart, members, w->rowptr.p, w->colind.p, w->val.p, rowlen,
-                           (const int32_t *)nullptr, (int32_t *)nullptr, (double *)nullptr, d_cnt + 1);
-        DevBuf<int32_t> nrowptr((size_t)n + 1);
-        exclusive_scan_u32(rowlen, reinterpret_cast<uint32_t *>(nrowptr.p), (size_t)n, d_cnt, st);
-        uint32_t hd[4];
-        readback_sync(hd, d_cnt, sizeof(hd), st);
-        if ((int)hd[3] != big) {
-            int64_t sc = 0;
-            IBH_HIP(hipMemcpy(&sc, row_s + (int)hd[3], sizeof(int64_t), hipMemcpyDeviceToHost));
-            fail(IBH_EINVAL, "Area of cell %ld must be non-zero", (long)sc);
-        }
-        if (hd[1] == 0) {
-            const uint32_t nnz2 = hd[0];
-            IBH_CHECK(nnz2 < (1u << 31), "smoothed matrix too large (%u entries)", nnz2);
-            IBH_HIP(hipMemcpyAsync(nrowptr.p + n, d_cnt, sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
-            DevBuf<int32_t> ncol((size_t)nnz2);
-            DevBuf<double> nval((size_t)nnz2);
-            hipLaunchKernelGGL(k_smooth_direct<true>, gd, dim3(SMD_WAVES * 64), 0, st, v, binstart, members, w->rowptr.p, w->colind.p, w->val.p,
-                               (uint32_t *)nullptr, nrowptr.p, ncol.p, nval.p, d_cnt + 1);
-            IBH_HIP(hipGetLastError());
-            IBH_HIP(hipStreamSynchronize(st));          // the old CSR was read until here
-            w->rowptr = std::move(nrowptr); w->colind = std::move(ncol); w->val = std::move(nval);
-            w->nnz = nnz2;
-            w->conservative = 0;            // conservative = !smooth, RegridMatrices_Dynamic.cpp:167
-            return;
-        }
-        // a row with more than SMD_MAXCOL columns: the triplet pipeline below serves the build
+    if (h4[1] != 0) return false;
+    t->nwaves = (int)h4[0]; t->nmem = (int)h4[2];
+    std::vector<int32_t> hK(nbins);
+    IBH_HIP(hipMemcpy(hK.data(), t->binK, sizeof(int32_t) * nbins, hipMemcpyDeviceToHost));
+    t->kmax = 1;
+    for (size_t q = 0; q < nbins; ++q) t->kmax = std::max(t->kmax, hK[q]);
+    return true;
+}
+// the kernel's dynamic-LDS limit is raised once per device, when a build first needs more than the default
+static void smt_raise_lds_limit(int device, size_t lds) {
+    static std::mutex mu;
+    static bool raised[64] = {};
+    if (lds <= 64 * 1024) return;
+    std::lock_guard<std::mutex> lk(mu);
+    if (raised[device & 63]) return;
+    IBH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_smt_tile), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SMT_LDS_RAISED));
+    raised[device & 63] = true;
+}
+// pack the candidates of a share and run its waves
+static void smt_run_share(const SmoothBins &B, const ibh_weighted *w, const SmtBuild &t, const SmtShare &s, hipStream_t st) {
+    if (!t.nmem) return;
+    const int T = 256, nb = (int)B.nbins;
+    if (s.c1 > s.c0)
+        hipLaunchKernelGGL(k_smt_pack, dim3(ceil_div(s.c1 - s.c0, T)), dim3(T), 0, st, B.v, B.members, s.c0, s.c1, t.nmem, w->rowptr.p, w->colind.p, w->val.p,
+                           t.cand, t.mne, t.mcol, t.mval);
+    hipLaunchKernelGGL(k_smt_wavebin, dim3(ceil_div(nb, T)), dim3(T), 0, st, t.wstart, t.binwaves, nb, t.wavebin);
+    hipLaunchKernelGGL(k_smt_memberbin, dim3(nb), dim3(64), 0, st, B.binstart, nb, t.memberbin);
+    const size_t lds = smt_lds(t.kmax).total;
+    smt_raise_lds_limit(w->device, lds);
+    if (s.w1 > s.w0)
+        hipLaunchKernelGGL(k_smt_tile, dim3(s.w1 - s.w0), dim3(64), lds, st, B.v, B.binstart, B.members, t.cand, t.mne, t.mcol, t.mval, t.nmem, t.bincols,
+                           t.binK, t.wstart, t.wavebin, s.w0, t.kmax, t.scratch, t.pres, t.rowlen);
+}
+// one rank: row lengths -> row pointer (the second read-back: nnz) -> the rows
+static void smt_collect(const SmoothBins &B, const SmtBuild &t, hipStream_t st, SmoothedCsr *out) {
+    const int T = 256, n = B.v.n;
+    uint32_t h4[4];
+    exclusive_scan_u32(t.rowlen, reinterpret_cast<uint32_t *>(out->rowptr.p), (size_t)n, B.d_cnt, st);
+    readback_sync(h4, B.d_cnt, sizeof(h4), st);
+    const uint32_t nnz2 = h4[0];
+    IBH_CHECK(nnz2 < (1u << 31), "smoothed matrix too large (%u entries)", nnz2);
+    IBH_HIP(hipMemcpyAsync(out->rowptr.p + n, B.d_cnt, sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+    out->colind.alloc((size_t)nnz2); out->val.alloc((size_t)nnz2);
+    if (t.nmem) hipLaunchKernelGGL(k_smt_emit, dim3(ceil_div(t.nmem, T)), dim3(T), 0, st, B.binstart, B.members, 0, t.nmem, t.wstart, t.memberbin, t.bincols, t.kmax,
+                                   t.scratch, t.pres, out->rowptr.p, (const uint32_t *)nullptr, out->colind.p, out->val.p);
+    out->nnz = nnz2;
+}
+// several ranks: every rank's rows reach every rank -- the row lengths in member order (gatherv) -> the row pointer and the
+// member-order offsets (scans) -> the rows packed in member order (gatherv) -> placed into the CSR.  ms: smt_member_starts
+static void smt_collect_ranks(const SmoothBins &B, const SmtBuild &t, const SmtShare &s, const std::vector<uint32_t> &ms, ibh_comm *comm, hipStream_t st,
+                              SmoothedCsr *out) {
+    Arena &A = arena();
+    const int T = 256, n = B.v.n, nmem = t.nmem;
+    const size_t nr = ms.size();        // world + 1
+    uint32_t *mlen = A.get<uint32_t>((size_t)nmem + 1), *mptr = A.get<uint32_t>((size_t)nmem + 1);
+    if (s.m1 > s.m0) hipLaunchKernelGGL(k_smt_mlen, dim3(ceil_div(s.m1 - s.m0, T)), dim3(T), 0, st, B.members, s.m0, s.m1, t.rowlen, mlen);
+    {
+        const std::vector<int64_t> ol = smt_gather_offsets(ms, 4);
+        void *bases[1] = {mlen};
+        const int64_t *offs[1] = {ol.data()};
+        comm_gatherv(comm, 1, bases, offs, st);
     }
-    uint32_t *ncnt = A.get<uint32_t>((size_t)n);
-    hipLaunchKernelGGL(k_smooth_neighbours<0>, grid, dim3(T), 0, st, v, binstart, members, ncnt, (const uint32_t *)nullptr,
-                       (uint64_t *)nullptr, (uint32_t *)nullptr, (double *)nullptr);
-    exclusive_scan_u32(ncnt, ncnt, (size_t)n, d_cnt, st);
-    uint32_t h[4];
-    IBH_HIP(hipMemcpyAsync(h, d_cnt, sizeof(h), hipMemcpyDeviceToHost, st));
+    if (nmem) hipLaunchKernelGGL(k_smt_rowlen, dim3(ceil_div(nmem, T)), dim3(T), 0, st, B.members, nmem, mlen, t.rowlen);
+    exclusive_scan_u32(t.rowlen, reinterpret_cast<uint32_t *>(out->rowptr.p), (size_t)n, B.d_cnt, st);
+    exclusive_scan_u32(mlen, mptr, (size_t)nmem, mptr + nmem, st);
+    IBH_HIP(hipMemcpyAsync(out->rowptr.p + n, B.d_cnt, sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+    std::vector<uint32_t> hp(nr);       // the packed rows of rank r start at hp[r]; hp[world] = nnz
+    for (size_t r = 0; r < nr; ++r) IBH_HIP(hipMemcpyAsync(&hp[r], mptr + ms[r], sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     IBH_HIP(hipStreamSynchronize(st));
-    if ((int)h[3] != big) {
-        int64_t s = 0;
-        IBH_HIP(hipMemcpy(&s, row_s + (int)h[3], sizeof(int64_t), hipMemcpyDeviceToHost));
-        fail(IBH_EINVAL, "Area of cell %ld must be non-zero", (long)s);
+    const uint32_t nnz2 = hp[nr - 1];
+    IBH_CHECK(nnz2 < (1u << 31), "smoothed matrix too large (%u entries)", nnz2);
+    DevBuf<int32_t> pcol((size_t)nnz2);
+    DevBuf<double> pval((size_t)nnz2);
+    if (s.m1 > s.m0) hipLaunchKernelGGL(k_smt_emit, dim3(ceil_div(s.m1 - s.m0, T)), dim3(T), 0, st, B.binstart, B.members, s.m0, s.m1, t.wstart, t.memberbin, t.bincols,
+                                        t.kmax, t.scratch, t.pres, (const int32_t *)nullptr, mptr, pcol.p, pval.p);
+    {
+        const std::vector<int64_t> oc = smt_gather_offsets(hp, 4), ov = smt_gather_offsets(hp, 8);
+        void *bases[2] = {pcol.p, pval.p};
+        const int64_t *offs[2] = {oc.data(), ov.data()};
+        comm_gatherv(comm, 2, bases, offs, st);
     }
+    out->colind.alloc((size_t)nnz2); out->val.alloc((size_t)nnz2);
+    if (nmem) hipLaunchKernelGGL(k_smt_place, dim3(ceil_div(nmem, T)), dim3(T), 0, st, B.members, nmem, mlen, mptr, out->rowptr.p, pcol.p, pval.p,
+                                 out->colind.p, out->val.p);
+    IBH_HIP(hipGetLastError());
+    IBH_HIP(hipStreamSynchronize(st));          // (pcol / pval are freed on leaving this scope)
+    out->nnz = nnz2;
+    out->shared = true;
+}
+static bool smooth_by_tiles(const SmoothBins &B, const ibh_weighted *w, ibh_comm *comm, hipStream_t st, SmoothedCsr *out) {
+    Arena &A = arena();
+    const int n = w->nrow, nb = (int)B.nbins;
+    const int world = comm ? comm_world(comm) : 1;
+    SmtBuild t{};
+    if (!smt_tables(B, w, comm, st, &t)) return false;
+    const size_t nmem1 = (size_t)std::max(t.nmem, 1), nwaves1 = (size_t)std::max(t.nwaves, 1);
+    t.rowlen = A.get<uint32_t>((size_t)n + 1);
+    IBH_HIP(hipMemsetAsync(t.rowlen, 0, sizeof(uint32_t) * ((size_t)n + 1), st));
+    t.cand = A.get<SmtCand>(nmem1);
+    t.wavebin = A.get<int32_t>(nwaves1); t.memberbin = A.get<int32_t>(nmem1);
+    t.scratch = A.get<double>(nwaves1 * t.kmax * 64);
+    t.pres = A.get<unsigned long long>(2 * nmem1);
+    t.mne = A.get<unsigned char>(nmem1);
+    t.mcol = A.get<int32_t>(nmem1 * SMT_ROWMAX);
+    t.mval = A.get<double>(nmem1 * SMT_ROWMAX);
+    SmoothedCsr r;
+    r.rowptr.alloc((size_t)n + 1);
+    if (world == 1) {
+        smt_run_share(B, w, t, smt_whole(nb, t.nmem, t.nwaves), st);
+        smt_collect(B, t, st, &r);
+    } else {
+        std::vector<uint32_t> hb(B.nbins + 1);
+        IBH_HIP(hipMemcpy(hb.data(), B.binstart, sizeof(uint32_t) * (B.nbins + 1), hipMemcpyDeviceToHost));
+        const std::vector<int> bs = smt_split(hb, B.v.nbx, B.v.nby, world);
+        const SmtShare s = smt_share(hb, bs, comm_rank(comm), B.v.nbx);
+        smt_run_share(B, w, t, s, st);
+        smt_collect_ranks(B, t, s, smt_member_starts(hb, bs), comm, st, &r);
+    }
+    *out = std::move(r);
+    return true;
+}
+// ---- the direct form (k_smooth_direct): count -> scan -> emit; one read-back (error word, overflow flag, nnz).  false: a row with more
+// than SMD_MAXCOL columns
+static bool smooth_by_rows(const SmoothBins &B, const ibh_weighted *w, hipStream_t st, SmoothedCsr *out) {
+    Arena &A = arena();
+    const int n = w->nrow;
+    uint32_t *rowlen = A.get<uint32_t>((size_t)n + 1);
+    IBH_HIP(hipMemsetAsync(B.d_cnt, 0, 3 * sizeof(uint32_t), st));
+    const dim3 gd(ceil_div(n, SMD_WAVES));
+    hipLaunchKernelGGL(k_smooth_direct<false>, gd, dim3(SMD_WAVES * 64), 0, st, B.v, B.binstart, B.members, w->rowptr.p, w->colind.p, w->val.p, rowlen,
+                       (const int32_t *)nullptr, (int32_t *)nullptr, (double *)nullptr, B.d_cnt + 1);
+    SmoothedCsr r;
+    r.rowptr.alloc((size_t)n + 1);
+    exclusive_scan_u32(rowlen, reinterpret_cast<uint32_t *>(r.rowptr.p), (size_t)n, B.d_cnt, st);
+    uint32_t hd[4];
+    readback_sync(hd, B.d_cnt, sizeof(hd), st);
+    fail_zero_area(B.row_s, (int)hd[3]);
+    if (hd[1] != 0) return false;
+    const uint32_t nnz2 = hd[0];
+    IBH_CHECK(nnz2 < (1u << 31), "smoothed matrix too large (%u entries)", nnz2);
+    IBH_HIP(hipMemcpyAsync(r.rowptr.p + n, B.d_cnt, sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+    r.colind.alloc((size_t)nnz2); r.val.alloc((size_t)nnz2);
+    hipLaunchKernelGGL(k_smooth_direct<true>, gd, dim3(SMD_WAVES * 64), 0, st, B.v, B.binstart, B.members, w->rowptr.p, w->colind.p, w->val.p,
+                       (uint32_t *)nullptr, r.rowptr.p, r.colind.p, r.val.p, B.d_cnt + 1);
+    r.nnz = nnz2;
+    *out = std::move(r);
+    return true;
+}
+// ---- the triplet pipeline: neighbour triplets -> sort by (i, j) -> row denominators -> products with the rows of M as contributions ->
+// build_csr_from_contributions.  No limit of its own: never false
+static bool smooth_by_triplets(const SmoothBins &B, const ibh_weighted *w, hipStream_t st, SmoothedCsr *out) {
+    Arena &A = arena();
+    const int T = 256, n = w->nrow;
+    const dim3 grid(ceil_div(n, T));
+    uint32_t *ncnt = A.get<uint32_t>((size_t)n);
+    hipLaunchKernelGGL(k_smooth_neighbours<0>, grid, dim3(T), 0, st, B.v, B.binstart, B.members, ncnt, (const uint32_t *)nullptr,
+                       (uint64_t *)nullptr, (uint32_t *)nullptr, (double *)nullptr);
+    exclusive_scan_u32(ncnt, ncnt, (size_t)n, B.d_cnt, st);
+    uint32_t h[4];
+    IBH_HIP(hipMemcpyAsync(h, B.d_cnt, sizeof(h), hipMemcpyDeviceToHost, st));
+    IBH_HIP(hipStreamSynchronize(st));
+    fail_zero_area(B.row_s, (int)h[3]);
     const size_t ns = h[0];
     IBH_CHECK(ns < (1ul << 31), "smoothing matrix too large (%zu entries)", ns);
     uint64_t *sk = A.get<uint64_t>(ns), *sk2 = A.get<uint64_t>(ns);
     uint32_t *si = A.get<uint32_t>(ns), *si2 = A.get<uint32_t>(ns);
     double *wraw = A.get<double>(ns);
-    hipLaunchKernelGGL(k_smooth_neighbours<1>, grid, dim3(T), 0, st, v, binstart, members, (uint32_t *)nullptr, ncnt, sk, si, wraw);
+    hipLaunchKernelGGL(k_smooth_neighbours<1>, grid, dim3(T), 0, st, B.v, B.binstart, B.members, (uint32_t *)nullptr, ncnt, sk, si, wraw);
     // order the triplets by (i, j): rows become contiguous with ascending columns
     KeyField sf[2] = {{0, bits_for((uint64_t)n)}, {32, bits_for((uint64_t)n)}};
     if (ns && sf[0].nbits > 0 && radix_sort_pairs(sk, sk2, si, si2, ns, sf, 2, st)) { std::swap(sk, sk2); std::swap(si, si2); }
@@ -1772,22 +1793,46 @@ static void smooth_matrix(ibh_weighted *w, const ibh_regrid_matrices *rm, const 
     // smoothI * M as contributions in (i, j ascending) order
     uint32_t *pcnt = A.get<uint32_t>(ns ? ns : 1);
     if (ns) hipLaunchKernelGGL(k_smooth_prod_count, dim3(ceil_div(ns, T)), dim3(T), 0, st, sk, ns, w->rowptr.p, pcnt);
-    exclusive_scan_u32(pcnt, pcnt, ns, d_cnt + 1, st);
-    IBH_HIP(hipMemcpyAsync(h, d_cnt, sizeof(h), hipMemcpyDeviceToHost, st));
+    exclusive_scan_u32(pcnt, pcnt, ns, B.d_cnt + 1, st);
+    IBH_HIP(hipMemcpyAsync(h, B.d_cnt, sizeof(h), hipMemcpyDeviceToHost, st));
     IBH_HIP(hipStreamSynchronize(st));
     IBH_CHECK(h[1] < (1ul << 31), "smoothed matrix too large (%zu products)", (size_t)h[1]);
     Triplets t = triplets_in_arena(h[1]);
     if (ns) hipLaunchKernelGGL(k_smooth_prod_emit, dim3(ceil_div(ns, T)), dim3(T), 0, st, sk, si, wraw, denom, ns, w->rowptr.p,
                                w->colind.p, w->val.p, pcnt, t.keys, t.idx, t.term);
     IBH_HIP(hipGetLastError());
-    // the products read w's CSR while the new one is being built: build into fresh buffers, then swap
     ibh_weighted tmp;
     int32_t *row = nullptr;
     build_csr_from_contributions(&tmp, t, w->nrow, w->ncol, &row, st);
-    IBH_HIP(hipStreamSynchronize(st));
-    w->rowptr = std::move(tmp.rowptr); w->colind = std::move(tmp.colind); w->val = std::move(tmp.val);
-    w->nnz = tmp.nnz;
+    out->rowptr = std::move(tmp.rowptr); out->colind = std::move(tmp.colind); out->val = std::move(tmp.val);
+    out->nnz = tmp.nnz;
+    return true;
+}
+// Every form reads w's CSR while it builds the new one into fresh buffers: wait for it, then swap.
+static void commit_smoothed(ibh_weighted *w, SmoothedCsr *out, SmoothForm form, hipStream_t st) {
+    IBH_HIP(hipGetLastError());
+    IBH_HIP(hipStreamSynchronize(st));          // the old CSR was read until here
+    w->rowptr = std::move(out->rowptr); w->colind = std::move(out->colind); w->val = std::move(out->val);
+    w->nnz = out->nnz;
     w->conservative = 0;            // conservative = !smooth, RegridMatrices_Dynamic.cpp:167
+    w->smoothed_by = (int)form;
+    if (out->shared) w->built_fast = 3;
+}
+// comm (world > 1): every rank of the communicator calls this with the same matrix; the tile form is shared (w->built_fast = 3),
+// the direct form and the triplet pipeline run on every rank.  The result is the same bits on every rank and for every world.
+static void smooth_matrix(ibh_weighted *w, const ibh_regrid_matrices *rm, const int64_t *row_s, const double sigma[3],
+                          hipStream_t st, ibh_comm *comm = nullptr) {
+    smooth_check(rm, sigma);
+    if (w->nrow == 0) return;
+    const SmoothPlan plan = plan_smooth(w->nrow, rm->rg->cmin, rm->rg->cmax, sigma);
+    const SmoothBins B = smooth_bins(w, rm, row_s, plan.grid, sigma, st);
+    SmoothedCsr out;
+    for (int k = 0; k < plan.nform; ++k) {
+        const SmoothForm form = plan.form[k];
+        const bool built = form == SMOOTH_TILE ? smooth_by_tiles(B, w, comm, st, &out)
+                         : form == SMOOTH_DIRECT ? smooth_by_rows(B, w, st, &out) : smooth_by_triplets(B, w, st, &out);
+        if (built) return commit_smoothed(w, &out, form, st);
+    }
 }
 
 // The same structure for a matrix that already exists (either assembly path; spmm.hip calls this when an E-row matrix is

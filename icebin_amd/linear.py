@@ -420,6 +420,13 @@ class linear_Weighted:
         check(lib().ibh_weighted_built_fast(self._h, C.byref(v)))
         return v.value == 3
 
+    def smoothed_by(self):
+        """The device form that smoothed this matrix (sigma != 0): 0 none, 1 the triplet pipeline, 2 the direct form, 3 the spatial
+        tiles (ibh_weighted_smoothed_by)."""
+        v = C.c_int()
+        check(lib().ibh_weighted_smoothed_by(self._h, C.byref(v)))
+        return v.value
+
     def last_kernel(self):
         buf = C.create_string_buffer(32)
         check(lib().ibh_weighted_last_kernel(self._h, buf, 32))

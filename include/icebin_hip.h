@@ -861,6 +861,11 @@ int ibh_weighted_set_option(ibh_weighted *w, const char *key, int value);
  * variant did (streamasm.inl: grids of 2^20 exchange cells and more; ibh_set_tuning("assemble_stream", 0 | 1) overrides),
  * 0 when the general pipeline built it (ibh_set_tuning("assemble_fast", 0) forces the latter).  Results are bit-identical. */
 int ibh_weighted_built_fast(const ibh_weighted *w, int *out);
+/* Which device form smoothed the matrix (sigma != 0, IvA / IvE): 0 not smoothed, 1 the triplet pipeline, 2 the direct form (one wave
+ * per row), 3 the spatial tiles.  The forms are tried in the order tiles, direct, triplets as ibh_set_tuning "smooth_tile",
+ * "smooth_direct" (1 always, 0 never, -1 by size: "smooth_direct_max_rows") admit them; a form whose tables overflow leaves the build
+ * to the next one.  Same structure from every form, entries to rounding.  Introspection only. */
+int ibh_weighted_smoothed_by(const ibh_weighted *w, int *out);
 /* PROCESS-WIDE launch-heuristic overrides for measurements and tests -- experiments only; a product caller that needs a knob sets it
  * on the handle (ibh_weighted_set_option).  (README.md lists the keys: assemble_fast, assemble_fast_eva,
  * assemble_range_shape, assemble_stream_count, assemble_static_count, rowgroup_*, rowone*, rowblock_*, shortrow_*, sweep_*,

@@ -1,6 +1,6 @@
-"""Compares two rocprofv3 kernel traces of scratch/asm_plan_launches.py (dev tool): per build, the ordered list of (kernel, grid,
-workgroup, LDS bytes) -- for the batched call, whose builds run on several host threads, the sorted list.
-usage: compare_launches.py parent_kernel_trace.csv new_kernel_trace.csv labels.txt > profiles/asm_plan_launches.txt"""
+"""Compares two rocprofv3 kernel traces of scratch/asm_plan_launches.py or scratch/smooth_plan_bits.py (dev tool): per build, the
+ordered list of (kernel, grid, workgroup, LDS bytes) -- for the batched call, whose builds run on several host threads, the sorted list.
+usage: compare_launches.py parent_kernel_trace.csv new_kernel_trace.csv labels.txt [what was traced] > profiles/asm_plan_launches.txt"""
 import csv
 import sys
 
@@ -23,7 +23,8 @@ def segments(path):
 
 a, b = segments(sys.argv[1]), segments(sys.argv[2])
 labels = [l.rstrip("\n") for l in open(sys.argv[3])]
-print("# Kernel launches of the sorted-grid builds, parent commit against the plan walkers: scratch/asm_plan_launches.py under")
+what = sys.argv[4] if len(sys.argv) > 4 else "the sorted-grid builds, parent commit against the plan walkers: scratch/asm_plan_launches.py"
+print("# Kernel launches of %s under" % what)
 print("# rocprofv3 --kernel-trace, one run per library build on one MI355X.  Per build: the ordered list of (kernel name, grid,")
 print("# workgroup size, LDS bytes); the batched call's builds run on several host threads: compared as a sorted list.")
 print("# segments: parent %d, new %d, labels %d" % (len(a), len(b), len(labels)))

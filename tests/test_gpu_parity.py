@@ -7,9 +7,18 @@ import math
 import numpy as np
 import pytest
 
+import os
+import sys
+
 import icebin_amd
 from icebin_amd import synthetic as syn
 from oracle import oracle as orc
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+try:
+    import smoothing_cases as smc
+finally:
+    sys.path.pop(0)
 
 pytestmark = pytest.mark.gpu
 
@@ -1344,7 +1353,15 @@ def test_smoothing_sigma_nonzero(name):
     from icebin_amd.linear import set_tuning
     g, em, mm, rg = setup("g20")
     sigma = (60e3, 60e3, 250.0)
-    for (scale, correctA), direct, tile in (((True, True), 1, 0), ((False, False), 0, 0), ((True, True), 0, 0), ((True, True), 0, 1), ((False, True), 0, 1)):
+    # The form that builds each leg, from the CPU (tests/smoothing_cases.py).  IvA: 18 columns around the widest bin, the tile legs run
+    # the tiles.  IvE at 20 km: 146 columns around the widest bin, more than SMT_KMAX = 128 -- the column tables overflow and the
+    # smooth_tile = 1 legs are served by the triplet pipeline (the tiles are checked against the oracle at 50 km, where IvE has 127:
+    # test_smoothing_forms_and_their_fallthroughs).
+    _, _, widest, longest, longest_smoothed = smc.oracle_case("g20", name, sigma)
+    tile_form = {"IvA": smc.TILE, "IvE": smc.TRIPLET}[name]
+    for (scale, correctA), direct, tile, form in (((True, True), 1, 0, smc.DIRECT), ((False, False), 0, 0, smc.TRIPLET), ((True, True), 0, 0, smc.TRIPLET),
+                                                  ((True, True), 0, 1, tile_form), ((False, True), 0, 1, tile_form)):
+        smc.assert_input_side(form, tile > 0, direct > 0, widest, longest, longest_smoothed)
         set_tuning("smooth_direct", direct)
         set_tuning("smooth_tile", tile)           # 1: the spatial-tile form (taken by itself for grids beyond the direct form's size)
         try:
@@ -1352,6 +1369,7 @@ def test_smoothing_sigma_nonzero(name):
         finally:
             set_tuning("smooth_direct", -1)
             set_tuning("smooth_tile", -1)
+        assert w.smoothed_by() == form
         o = rg.matrix_d(name, em, scale=scale, correctA=correctA, sigma=sigma)
         plain = rg.matrix_d(name, em, scale=scale, correctA=correctA)
         assert not w.conservative and not o.conservative and w.scaled == scale
@@ -1373,8 +1391,84 @@ def test_smoothing_sigma_nonzero(name):
             assert _conservation(w, x[k], y[k]) < 1e-13
     # matrices whose build never smooths ignore sigma (compute_AEvI, compute_EvA)
     a = mm.regrid_matrices("greenland", em, sigma=sigma).matrix("AvI")
-    assert a.conservative
+    assert a.conservative and a.smoothed_by() == smc.NONE
     assert_same_weighted(a, rg.matrix_d("AvI", em, scale=True, correctA=True), "AvI with sigma")
+
+
+def _smoothed_build(mm, em, name, sigma, knobs):
+    from icebin_amd.linear import set_tuning
+    set_tuning("smooth_direct", knobs[0])
+    set_tuning("smooth_tile", knobs[1])
+    try:
+        return mm.regrid_matrices("greenland", em, scale=True, correctA=True, sigma=sigma).matrix(name)
+    finally:
+        set_tuning("smooth_direct", -1)
+        set_tuning("smooth_tile", -1)
+
+
+def _same_bits(a, b):
+    if (a.nrow_d, a.ncol_d, a.nnz, a.conservative) != (b.nrow_d, b.ncol_d, b.nnz, b.conservative):
+        return False
+    return all(np.array_equal(x.view(np.uint64) if x.dtype == np.float64 else x, y.view(np.uint64) if y.dtype == np.float64 else y)
+               for x, y in zip(a.csr_dense() + (a.wM, a.Mw), b.csr_dense() + (b.wM, b.Mw)))
+
+
+def check_smoothing_leg(mm, sigma, name, knobs, form, same_as, assert_form=True):
+    """One leg of smc.G50_LEGS: the input lies on the intended side of the forms' limits (decided on the CPU), the form that built the
+    matrix is the intended one, the matrix is the oracle's (structure exact, entries to 1e-12) and, where another knob setting must
+    give the same form, bitwise that build.  assert_form=False: a library without smoothed_by (a parent build, measured by hand)."""
+    g, em = smc.grids("g50")
+    plain, o, widest, longest, longest_smoothed = smc.oracle_case("g50", name, sigma)
+    smc.assert_input_side(form, knobs[1] > 0, knobs[0] > 0, widest, longest, longest_smoothed)
+    w = _smoothed_build(mm, em, name, sigma, knobs)
+    if assert_form:
+        assert w.smoothed_by() == form
+    assert not w.conservative and not o.conservative
+    assert (w.nrow_d, w.ncol_d, w.nnz) == (o.nrow, o.ncol, o.nnz)
+    np.testing.assert_array_equal(w.dim(0), o.dims[0])
+    np.testing.assert_array_equal(w.dim(1), o.dims[1])
+    row, col, val = w.coo_dense()
+    np.testing.assert_array_equal(row, o.row)
+    np.testing.assert_array_equal(col, o.col)
+    np.testing.assert_allclose(val, o.val, rtol=1e-12, atol=0)
+    np.testing.assert_array_equal(w.wM.view(np.uint64), plain.wM.view(np.uint64))
+    np.testing.assert_array_equal(w.Mw.view(np.uint64), plain.Mw.view(np.uint64))
+    if same_as is not None:
+        other = _smoothed_build(mm, em, name, sigma, same_as)
+        if assert_form:
+            assert other.smoothed_by() == form
+        assert _same_bits(w, other)
+
+
+@pytest.mark.parametrize("leg", range(len(smc.G50_LEGS)), ids=["%s-%dkm-%d%d" % (l[1], l[0][0] / 1e3, l[2][0], l[2][1]) for l in smc.G50_LEGS])
+def test_smoothing_forms_and_their_fallthroughs(leg):
+    # 50 km (793 rows): the tile form at the edge of its column table (IvE, 127 of SMT_KMAX = 128 columns: the raised-LDS launch), the
+    # tiles overflowing into the direct form, both overflowing into the triplet pipeline, and the tiles serving IvA at a sigma where
+    # they cannot serve IvE -- each against the oracle; a fall-through is bitwise the build that asks for the serving form alone
+    g, em = smc.grids("g50")
+    check_smoothing_leg(icebin_amd.from_synthetic(g), *smc.G50_LEGS[leg])
+
+
+def test_smoothing_refusals_are_decided_before_any_smoothing_work():
+    # smooth_check: "three positive sigmas" and the centroids, IBH_EINVAL both, after the unsmoothed build and before the first bin
+    g, em = smc.grids("g50")
+    mm = icebin_amd.from_synthetic(g)
+    # (RegridParams::smooth() is sigma.x != 0: a zero x component asks for no smoothing at all)
+    plain = mm.regrid_matrices("greenland", em, sigma=(0.0, 60e3, 250.0)).matrix("IvA")
+    assert plain.conservative and plain.smoothed_by() == smc.NONE
+    for sigma in ((60e3, 60e3, 0.0), (60e3, -1.0, 250.0), (-60e3, 60e3, 250.0)):
+        for name in ("IvA", "IvE"):
+            with pytest.raises(icebin_amd.IcebinHipError, match="three positive sigmas") as ei:
+                mm.regrid_matrices("greenland", em, sigma=sigma).matrix(name)
+            assert ei.value.code == icebin_amd._capi.IBH_EINVAL
+    bare = dict(g)
+    bare["I_centroid_xy"] = None
+    mb = icebin_amd.from_synthetic(bare)
+    assert mb.regrid_matrices("greenland", em).matrix("IvA").nnz > 0              # unsmoothed builds do not need them
+    for name in ("IvA", "IvE"):
+        with pytest.raises(icebin_amd.IcebinHipError, match="centroid_xy") as ei:
+            mb.regrid_matrices("greenland", em, sigma=(60e3, 60e3, 250.0)).matrix(name)
+        assert ei.value.code == icebin_amd._capi.IBH_EINVAL
 
 
 def test_apply_is_graph_capturable():

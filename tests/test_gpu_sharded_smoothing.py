@@ -19,6 +19,7 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 SIGMA = (50e3, 50e3, 100.0)
+TRIPLET, DIRECT, TILE = 1, 2, 3                 # linear_Weighted.smoothed_by()
 PAIRS = ((True, True), (True, False), (False, True), (False, False))
 
 
@@ -131,12 +132,14 @@ FORMS = {                                       # (smooth_direct, smooth_tile) a
 }
 
 
-def _job_build(comm, world, rank, cases, sigma=SIGMA):
+def _job_build(comm, world, rank, cases):
+    """cases: (config, knobs of FORMS, sigma, {matrix: (built_fast code, smoothed_by form)}) -- per matrix: at one sigma the tiles may
+    serve IvA (shared) and overflow for IvE (every rank steps down to a redundant build)"""
     import icebin_amd
     from icebin_amd import synthetic as syn
     from icebin_amd.linear import set_tuning
     ok, notes = True, []
-    for config, form, expect in cases:
+    for config, form, sigma, expects in cases:
         g = syn.make_grids(config)
         em = syn.dome_elevmask(g)
         mm = icebin_amd.from_synthetic(g)
@@ -149,9 +152,11 @@ def _job_build(comm, world, rank, cases, sigma=SIGMA):
             for name, scale, correctA in jobs:
                 ws = rm.matrix_d_sharded(comm, name, scale=scale, correctA=correctA, sigma=sigma)
                 w1 = rm.matrix_d(name, scale=scale, correctA=correctA, sigma=sigma)
-                good = _same_matrix(ws, w1) and not ws.conservative and _built_code(ws) == expect
+                good = _same_matrix(ws, w1) and not ws.conservative and (_built_code(ws), ws.smoothed_by()) == expects[name] and \
+                    w1.smoothed_by() == expects[name][1]
                 if not good:
-                    notes.append("%s %s %s scale=%d correctA=%d: built %d" % (config, form, name, scale, correctA, _built_code(ws)))
+                    notes.append("%s %s %s scale=%d correctA=%d: built %d by form %d (one rank: form %d)" %
+                                 (config, form, name, scale, correctA, _built_code(ws), ws.smoothed_by(), w1.smoothed_by()))
                 ok = ok and good
             # the coupler's call (IceCoupler.cpp:461-467): IvE on the identity dimI and the dimE an earlier EvI numbered
             nE = g["nA"] * len(g["hcdefs"])
@@ -161,9 +166,10 @@ def _job_build(comm, world, rank, cases, sigma=SIGMA):
                 build = (lambda n, d, **kw: rm.matrix_d_sharded(comm, n, d, **kw)) if sharded else (lambda n, d, **kw: rm.matrix_d(n, d, **kw))
                 build("EvI", (dimE, dimI), scale=False, correctA=False)
                 got.append(build("IvE", (dimI, dimE), scale=True, correctA=True, sigma=sigma))
-            good = _same_matrix(got[0], got[1]) and _built_code(got[0]) == expect
+            good = _same_matrix(got[0], got[1]) and (_built_code(got[0]), got[0].smoothed_by()) == expects["IvE"] and \
+                got[1].smoothed_by() == expects["IvE"][1]
             if not good:
-                notes.append("%s %s coupler IvE: built %d" % (config, form, _built_code(got[0])))
+                notes.append("%s %s coupler IvE: built %d by form %d" % (config, form, _built_code(got[0]), got[0].smoothed_by()))
             ok = ok and good
         finally:
             set_tuning("smooth_direct", -1)
@@ -310,7 +316,7 @@ def test_shared_smoothed_build_is_the_single_rank_build_bitwise(world):
     """5 km, sigma = (50 km, 50 km, 100 m): the spatial-tile form by size, shared by the ranks (built_fast 3) -- IvA and IvE with
     all four (scale, correctA) pairs and the coupler's IvE on the identity dimI and a dimE numbered by an EvI: every rank's matrix
     is bitwise matrix_d(..., sigma) on one rank (dims, CSR, val bits, wM, Mw, conservative = 0); the rows travelled (gatherv)."""
-    got = _spawn(world, "build", ([("g5", "size", 3)],))
+    got = _spawn(world, "build", ([("g5", "size", SIGMA, {"IvA": (3, TILE), "IvE": (3, TILE)})],))
     assert all(ok for _, ok, _, _ in got), got
     assert all(c["gatherv"] > 0 for _, _, _, c in got), got
 
@@ -318,8 +324,25 @@ def test_shared_smoothed_build_is_the_single_rank_build_bitwise(world):
 @pytest.mark.gpu
 def test_smoothed_build_forms_on_two_ranks():
     """20 km: the direct form by size and the triplet pipeline (smooth_tile = smooth_direct = 0) run on every rank (built_fast 1),
-    the tile form forced (smooth_tile = 1) is shared (3); every result bitwise the single-rank build."""
-    got = _spawn(2, "build", ([("g20", "size", 1), ("g20", "triplet", 1), ("g20", "tile", 3)],))
+    the tile form forced (smooth_tile = 1) is shared (3); every result bitwise the single-rank build.  50 km, sigma = (120 km,
+    120 km, 400 m), smooth_tile = 1: the tiles serve IvA (45 columns around the widest bin) shared, while IvE (347 > SMT_KMAX) makes
+    both ranks step down together to the redundant triplet build (built_fast 1).  Which side of the limits each input lies on is
+    asserted here, on the CPU, before any rank starts."""
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    try:
+        import smoothing_cases as smc
+    finally:
+        sys.path.pop(0)
+    sigma_wide = (120e3, 120e3, 400.0)
+    cases = [("g20", "size", SIGMA, {"IvA": (1, DIRECT), "IvE": (1, DIRECT)}), ("g20", "triplet", SIGMA, {"IvA": (1, TRIPLET), "IvE": (1, TRIPLET)}),
+             ("g20", "tile", SIGMA, {"IvA": (3, TILE), "IvE": (3, TILE)}), ("g50", "tile", sigma_wide, {"IvA": (3, TILE), "IvE": (1, TRIPLET)})]
+    for config, form, sigma, expects in cases:
+        direct, tile = FORMS[form]
+        for name, (_, by) in expects.items():
+            _, _, widest, longest, longest_smoothed = smc.oracle_case(config, name, sigma)
+            # ("size": 20 km lies below smooth_direct_max_rows, the direct form is tried and the tiles are not)
+            smc.assert_input_side(by, tile > 0, direct > 0 or form == "size", widest, longest, longest_smoothed)
+    got = _spawn(2, "build", (cases,))
     assert all(ok for _, ok, _, _ in got), got
 
 
