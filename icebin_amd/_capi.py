@@ -66,6 +66,11 @@ class MultivecDeviceView(C.Structure):
     _fields_ = [("n", C.c_int64), ("nvar", C.c_int32), ("index", C.c_void_p), ("weights", C.c_void_p), ("vals", C.c_void_p)]
 
 
+class PlanePack(C.Structure):
+    _fields_ = [("mv", C.c_void_p), ("planes", C.c_void_p), ("plane_type", C.c_void_p), ("nvar", C.c_int32), ("nclass", C.c_int32),
+                ("plane_class_stride", C.c_int64), ("index_stride_cell", C.c_int64), ("index_stride_class", C.c_int64)]
+
+
 _SIGS = {
     "ibh_version": (C.c_int, []),
     "ibh_device_count": (C.c_int, [C.POINTER(C.c_int)]),
@@ -195,6 +200,14 @@ _SIGS = {
     "ibh_multivec_get": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ibh_multivec_device_view_get": (C.c_int, [C.c_void_p, C.POINTER(MultivecDeviceView)]),
     "ibh_multivec_append_weighted_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p]),
+    "ibh_multivec_append_planes_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int64, C.c_void_p,
+                                                   C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.c_void_p]),
+    "ibh_multivec_append_planes_many_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64),
+                                                        C.c_void_p]),
+    "ibh_multivec_append_planes_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int64, C.c_void_p,
+                                                 C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_int64)]),
+    "ibh_multivec_append_planes_many_host": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]),
+    "ibh_multivec_affine_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ibh_multivec_append": (C.c_int, [C.c_void_p, C.c_void_p]),
     "ibh_multivec_concatenate": (C.c_int, [C.c_int32, C.c_void_p, C.POINTER(C.c_void_p)]),
     "ibh_multivec_to_dense_scale": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),

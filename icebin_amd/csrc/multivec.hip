@@ -63,6 +63,132 @@ __global__ __launch_bounds__(AP_THREADS) void k_mv_append(const double *__restri
     }
 }
 
+// ---- append_planes: the masked, ordered pack of field planes (modele/GCMCoupler_ModelE.cpp:1099-1164) -------------------------
+// A cell c is KEPT when mask[c] != 0 || mask0[c] != 0.  The kept cells are listed in ascending order ONCE per call -- list[rank]
+// = cell -- and every pack of the call, and every class of a pack, reads that list: entry n0 + ihc * nkept + rank.
+//
+// The list is made by tiles of PK_TILE cells, PK_I passes of one cell per thread: a pass's kept flags are one ballot per wave,
+// a cell's rank inside its tile is the kept cells of the (pass, wave) pairs before its own plus the set bits below its lane,
+// and the kept cells of the tiles before come from k_mv_pack_count's per-tile counts -- summed by the tile's own block up to
+// PK_SELF_TILES tiles (two launches; 2 M cells, every atmosphere grid there is), scanned by prims.h's scan beyond (three).  No
+// atomics, and no block waits for another.
+constexpr int PK_T = 256, PK_I = 8, PK_TILE = PK_T * PK_I, PK_SELF_TILES = 1024;
+__device__ __forceinline__ bool pk_kept(const int16_t *__restrict__ mask, const int16_t *__restrict__ mask0, long c, long ncell) {
+    return c < ncell && (mask[c] != 0 || (mask0 && mask0[c] != 0));
+}
+__global__ __launch_bounds__(PK_T) void k_mv_pack_count(const int16_t *__restrict__ mask, const int16_t *__restrict__ mask0, long ncell,
+                                                       uint32_t *__restrict__ cnt) {
+    __shared__ uint32_t s_wave[PK_T / 64];
+    const long base = (long)blockIdx.x * PK_TILE;
+    uint32_t n = 0;
+#pragma unroll
+    for (int i = 0; i < PK_I; ++i) n += (uint32_t)__popcll(__ballot(pk_kept(mask, mask0, base + i * PK_T + threadIdx.x, ncell)));
+    if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = n;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t tot = 0;
+#pragma unroll
+        for (int w = 0; w < PK_T / 64; ++w) tot += s_wave[w];
+        cnt[blockIdx.x] = tot;
+    }
+}
+// PRESCANNED: cnt[b] is already the kept cells before tile b; else the count of tile b alone.  *total: the kept cells in all.
+template <bool PRESCANNED>
+__global__ __launch_bounds__(PK_T) void k_mv_pack_rank(const int16_t *__restrict__ mask, const int16_t *__restrict__ mask0, long ncell,
+                                                      const uint32_t *__restrict__ cnt, uint32_t *__restrict__ list,
+                                                      uint32_t *__restrict__ total) {
+    __shared__ uint32_t s_cnt[PK_I][PK_T / 64];
+    __shared__ uint32_t s_before[PK_T / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long base = (long)blockIdx.x * PK_TILE;
+    unsigned long long kept[PK_I];              // (wave-uniform; the loops over it are unrolled)
+#pragma unroll
+    for (int i = 0; i < PK_I; ++i) {
+        kept[i] = __ballot(pk_kept(mask, mask0, base + i * PK_T + threadIdx.x, ncell));
+        if (lane == 0) s_cnt[i][wave] = (uint32_t)__popcll(kept[i]);
+    }
+    if (!PRESCANNED) {
+        uint32_t s = 0;
+        for (uint32_t b = threadIdx.x; b < blockIdx.x; b += PK_T) s += cnt[b];
+        for (int d = 32; d; d >>= 1) s += __shfl_xor(s, d, 64);
+        if (lane == 0) s_before[wave] = s;
+    }
+    __syncthreads();
+    uint32_t run = 0;
+    if (PRESCANNED) run = cnt[blockIdx.x];
+    else {
+#pragma unroll
+        for (int w = 0; w < PK_T / 64; ++w) run += s_before[w];
+    }
+    const unsigned long long below = (1ull << lane) - 1ull;
+#pragma unroll
+    for (int i = 0; i < PK_I; ++i) {
+        uint32_t mine = 0;
+#pragma unroll
+        for (int w = 0; w < PK_T / 64; ++w) {
+            if (w == wave) mine = run;
+            run += s_cnt[i][w];
+        }
+        if (kept[i] >> lane & 1ull) list[mine + (uint32_t)__popcll(kept[i] & below)] = (uint32_t)(base + i * PK_T + threadIdx.x);
+    }
+    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) *total = run;
+}
+// One unit = AP_ROWS kept cells of one class, staged like k_mv_append's tile: a wave gathers 64 kept cells of one variable
+// (adjacent in the plane wherever the mask is dense), then consecutive lanes write consecutive (entry, variable) pairs.  A double
+// plane is copied as 64-bit words, an int16 plane converted: no other floating-point operation.  Blocks stride over the units.
+__global__ __launch_bounds__(AP_THREADS) void k_mv_pack(const void *const *__restrict__ planes, const int32_t *__restrict__ types, int nvar,
+                                                       long class_stride, const uint32_t *__restrict__ list, uint32_t nkept, long nunit,
+                                                       long stride_cell, long stride_class, int64_t *__restrict__ index,
+                                                       double *__restrict__ weights, unsigned long long *__restrict__ vals) {
+    __shared__ unsigned long long tile[AP_VC * AP_LD];
+    const int t = threadIdx.x;
+    const int lr = t & (AP_ROWS - 1), lv = t / AP_ROWS;
+    const long ntile = (nkept + AP_ROWS - 1) / AP_ROWS;
+    for (long u = blockIdx.x; u < nunit; u += gridDim.x) {
+        const long ihc = u / ntile;
+        const long row0 = (u - ihc * ntile) * AP_ROWS;
+        const int nr = (int)min((long)AP_ROWS, (long)nkept - row0);
+        const long pos0 = ihc * (long)nkept + row0;
+        const long cell = lr < nr ? (long)list[row0 + lr] : 0;
+        if (t < nr) {
+            index[pos0 + t] = cell * stride_cell + ihc * stride_class;
+            weights[pos0 + t] = 1.0;
+        }
+        const long src = ihc * class_stride + cell;
+        for (int v0 = 0; v0 < nvar; v0 += AP_VC) {
+            const int nc = min(AP_VC, nvar - v0);
+            if (lr < nr)
+                for (int v = lv; v < nc; v += AP_THREADS / AP_ROWS) {
+                    const void *p = planes[v0 + v];
+                    tile[v * AP_LD + lr] = types[v0 + v]
+                                               ? (unsigned long long)__double_as_longlong((double)static_cast<const int16_t *>(p)[src])
+                                               : static_cast<const unsigned long long *>(p)[src];
+                }
+            __syncthreads();
+            for (int o = t; o < nr * nc; o += AP_THREADS) {
+                const int r = o / nc, v = o - r * nc;
+                vals[(pos0 + r) * nvar + v0 + v] = tile[v * AP_LD + r];
+            }
+            __syncthreads();
+        }
+    }
+}
+
+// ---- affine: couple()'s unit conversion (GCMCoupler_ModelE.cpp:1216-1228) ------------------------------------------------------
+// vals[ix * nvar + k] = vals[ix * nvar + k] * mm[k] + bb[k] for AFF_VC variables from v0 on; the coefficients ride in the kernel
+// arguments, so the call is a pure enqueue.  One product, then one add (-ffp-contract=off).
+constexpr int AFF_VC = 16;
+struct AffineArgs { double mm[AFF_VC], bb[AFF_VC]; };
+__global__ __launch_bounds__(256) void k_mv_affine(double *__restrict__ vals, long n, int nvar, int v0, int nc, AffineArgs P) {
+    const long total = n * nc;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const long ix = i / nc;
+        const int k = (int)(i - ix * nc);
+        double *p = vals + ix * nvar + v0 + k;
+        *p = *p * P.mm[k] + P.bb[k];
+    }
+}
+
 // ---- grouping ---------------------------------------------------------------------------------------------------------------
 // What the host reads back: badinv = 0xFFFFFFFF - (the first offending entry), 0: none (entries are < 2^31); maxkey = largest key
 struct MvStatus { uint32_t badinv, pad; unsigned long long maxkey; };
@@ -326,6 +452,91 @@ static void mv_check_dense_args(const ibh_multivec *mv, const void *a, const voi
     IBH_CHECK(ld >= nE, "%s: ld=%lld is shorter than nE=%lld", what, (long long)ld, (long long)nE);
 }
 
+// ---- append_planes, host side ------------------------------------------------------------------------------------------------
+// Everything that can be refused without the count, before anything is launched or touched.  `what` names the entry.
+static void check_packs(const ibh_plane_pack *packs, int32_t npack, int64_t ncell, const int16_t *mask, const char *what) {
+    IBH_CHECK(npack >= 1 && packs != nullptr, "%s: at least one pack is needed", what);
+    IBH_CHECK(ncell >= 0 && ncell < (1ll << 31), "%s: ncell=%lld (0 .. 2^31 - 1 supported)", what, (long long)ncell);
+    IBH_CHECK(ncell == 0 || mask != nullptr, "%s: null mask", what);
+    for (int p = 0; p < npack; ++p) {
+        const ibh_plane_pack &k = packs[p];
+        IBH_CHECK(k.mv != nullptr, "%s: pack %d: null VectorMultivec handle", what, p);
+        check_mv(k.mv);
+        for (int q = 0; q < p; ++q) IBH_CHECK(packs[q].mv != k.mv, "%s: packs %d and %d name the same VectorMultivec", what, q, p);
+        IBH_CHECK(k.nvar == k.mv->nvar, "%s: pack %d: Inconsistant nvar: %d vs %d", what, p, k.mv->nvar, k.nvar);
+        IBH_CHECK(k.nclass >= 0, "%s: pack %d: nclass=%d is negative", what, p, k.nclass);
+        IBH_CHECK(k.plane_class_stride >= 0, "%s: pack %d: plane_class_stride=%lld is negative", what, p, (long long)k.plane_class_stride);
+        IBH_CHECK(k.nclass <= 1 || k.plane_class_stride <= (INT64_MAX / 16 - ncell) / (k.nclass - 1),
+                  "%s: pack %d: %d classes of stride %lld overflow", what, p, k.nclass, (long long)k.plane_class_stride);
+        for (int v = 0; v < k.nvar; ++v)
+            IBH_CHECK(!k.plane_type || k.plane_type[v] == 0 || k.plane_type[v] == 1, "%s: pack %d: plane %d has type %d (0: double, 1: int16)",
+                      what, p, v, k.plane_type[v]);
+        if (ncell == 0 || k.nclass == 0) continue;              // nothing is read
+        IBH_CHECK(k.planes != nullptr, "%s: pack %d: null plane array", what, p);
+        for (int v = 0; v < k.nvar; ++v) IBH_CHECK(k.planes[v] != nullptr, "%s: pack %d: plane %d is null", what, p, v);
+    }
+}
+
+// The kept cells of (mask, mask0), ascending, in the arena; their number comes back in the call's one host wait.
+static const uint32_t *list_kept(const int16_t *d_mask, const int16_t *d_mask0, int64_t ncell, uint32_t *nkept, hipStream_t st) {
+    Arena &A = arena();
+    const uint32_t nb = (uint32_t)ceil_div(ncell, (int64_t)PK_TILE);
+    uint32_t *list = A.get<uint32_t>((size_t)ncell), *cnt = A.get<uint32_t>(nb), *total = A.get<uint32_t>(1);
+    hipLaunchKernelGGL(k_mv_pack_count, dim3(nb), dim3(PK_T), 0, st, d_mask, d_mask0, (long)ncell, cnt);
+    if (nb <= (uint32_t)PK_SELF_TILES) {
+        hipLaunchKernelGGL(k_mv_pack_rank<false>, dim3(nb), dim3(PK_T), 0, st, d_mask, d_mask0, (long)ncell, cnt, list, total);
+    } else {
+        exclusive_scan_u32(cnt, cnt, nb, nullptr, st);
+        hipLaunchKernelGGL(k_mv_pack_rank<true>, dim3(nb), dim3(PK_T), 0, st, d_mask, d_mask0, (long)ncell, cnt, list, total);
+    }
+    IBH_HIP(hipGetLastError());
+    readback_sync(nkept, total, sizeof(uint32_t), st);
+    return list;
+}
+
+static void append_planes_many(const ibh_plane_pack *packs, int32_t npack, int64_t ncell, const int16_t *d_mask, const int16_t *d_mask0,
+                               int64_t *nkept_out, hipStream_t st) {
+    const char *what = "append_planes";
+    check_packs(packs, npack, ncell, d_mask, what);
+    if (nkept_out) *nkept_out = 0;
+    if (ncell == 0) return;
+    Arena &A = arena();
+    A.reset();
+    // the plane tables go up in front of the mask pass: its host wait covers them
+    std::vector<const void **> d_planes((size_t)npack, nullptr);
+    std::vector<int32_t *> d_types((size_t)npack, nullptr);
+    for (int p = 0; p < npack; ++p) {
+        const ibh_plane_pack &k = packs[p];
+        if (k.nclass == 0) continue;
+        d_planes[(size_t)p] = A.get<const void *>((size_t)k.nvar);
+        d_types[(size_t)p] = A.get<int32_t>((size_t)k.nvar);
+        IBH_HIP(hipMemcpyAsync(d_planes[(size_t)p], k.planes, sizeof(void *) * (size_t)k.nvar, hipMemcpyHostToDevice, st));
+        if (k.plane_type) IBH_HIP(hipMemcpyAsync(d_types[(size_t)p], k.plane_type, sizeof(int32_t) * (size_t)k.nvar, hipMemcpyHostToDevice, st));
+        else IBH_HIP(hipMemsetAsync(d_types[(size_t)p], 0, sizeof(int32_t) * (size_t)k.nvar, st));
+    }
+    uint32_t nkept = 0;
+    const uint32_t *list = list_kept(d_mask, d_mask0, ncell, &nkept, st);
+    for (int p = 0; p < npack; ++p) {
+        const long long total = (long long)packs[p].mv->n + (long long)packs[p].nclass * (long long)nkept;
+        IBH_CHECK(total < (1ll << 31), "%s: pack %d: %lld entries (fewer than 2^31 supported)", what, p, total);
+    }
+    if (nkept_out) *nkept_out = nkept;
+    for (int p = 0; p < npack && nkept; ++p) {
+        const ibh_plane_pack &k = packs[p];
+        if (k.nclass == 0) continue;
+        ibh_multivec *mv = k.mv;
+        const int64_t added = (int64_t)k.nclass * nkept;
+        mv_reserve(mv, mv->n + added, st);
+        const long nunit = (long)ceil_div((int64_t)nkept, (int64_t)AP_ROWS) * k.nclass;
+        hipLaunchKernelGGL(k_mv_pack, dim3((unsigned)std::min<long>(nunit, 1l << 20)), dim3(AP_THREADS), 0, st, d_planes[(size_t)p],
+                           d_types[(size_t)p], (int)k.nvar, (long)k.plane_class_stride, list, nkept, nunit, (long)k.index_stride_cell,
+                           (long)k.index_stride_class, mv->index.p + mv->n, mv->weights.p + mv->n,
+                           reinterpret_cast<unsigned long long *>(mv->vals.p + (size_t)mv->n * (size_t)k.nvar));
+        IBH_HIP(hipGetLastError());
+        mv_grew(mv, added);
+    }
+}
+
 }  // namespace ibh
 
 using namespace ibh;
@@ -413,6 +624,66 @@ int ibh_multivec_append_weighted_device(ibh_multivec *mv, const ibh_weighted *w,
                            w->wM.p, mv->index.p + mv->n, mv->weights.p + mv->n, mv->vals.p + (size_t)mv->n * (size_t)nvar);
         IBH_HIP(hipGetLastError());
         mv_grew(mv, nrow);
+    });
+}
+
+int ibh_multivec_append_planes_many_device(const ibh_plane_pack *packs, int32_t npack, int64_t ncell, const int16_t *d_mask,
+                                           const int16_t *d_mask0, int64_t *nkept, void *stream) {
+    return guarded([&] { append_planes_many(packs, npack, ncell, d_mask, d_mask0, nkept, (hipStream_t)stream); });
+}
+int ibh_multivec_append_planes_device(ibh_multivec *mv, const void *const *d_planes, const int32_t *plane_type, int32_t nvar, int64_t ncell,
+                                      int32_t nclass, int64_t plane_class_stride, const int16_t *d_mask, const int16_t *d_mask0,
+                                      int64_t index_stride_cell, int64_t index_stride_class, int64_t *nkept, void *stream) {
+    const ibh_plane_pack pack = {mv, d_planes, plane_type, nvar, nclass, plane_class_stride, index_stride_cell, index_stride_class};
+    return ibh_multivec_append_planes_many_device(&pack, 1, ncell, d_mask, d_mask0, nkept, stream);
+}
+int ibh_multivec_append_planes_many_host(const ibh_plane_pack *packs, int32_t npack, int64_t ncell, const int16_t *mask, const int16_t *mask0,
+                                         int64_t *nkept) {
+    return guarded([&] {
+        check_packs(packs, npack, ncell, mask, "append_planes");
+        require_device();
+        DevBuf<int16_t> dm((size_t)ncell), dm0(mask0 ? (size_t)ncell : 0);
+        dm.upload(mask, (size_t)ncell);
+        if (mask0) dm0.upload(mask0, (size_t)ncell);
+        std::vector<DevBuf<char>> bufs;
+        std::vector<std::vector<const void *>> tables((size_t)npack);
+        std::vector<ibh_plane_pack> dpacks(packs, packs + npack);
+        for (int p = 0; p < npack; ++p) {
+            const ibh_plane_pack &k = packs[p];
+            if (ncell == 0 || k.nclass == 0) continue;
+            const size_t count = (size_t)(k.nclass - 1) * (size_t)k.plane_class_stride + (size_t)ncell;
+            for (int v = 0; v < k.nvar; ++v) {
+                const size_t bytes = count * (k.plane_type && k.plane_type[v] ? sizeof(int16_t) : sizeof(double));
+                bufs.emplace_back(bytes);
+                bufs.back().upload(static_cast<const char *>(k.planes[v]), bytes);
+                tables[(size_t)p].push_back(bufs.back().p);
+            }
+            dpacks[(size_t)p].planes = tables[(size_t)p].data();
+        }
+        rethrow(ibh_multivec_append_planes_many_device(dpacks.data(), npack, ncell, dm.p, mask0 ? dm0.p : nullptr, nkept, nullptr));
+        IBH_HIP(hipStreamSynchronize(nullptr));       // the host arrays are borrowed for the call only, the copies go away
+    });
+}
+int ibh_multivec_append_planes_host(ibh_multivec *mv, const void *const *planes, const int32_t *plane_type, int32_t nvar, int64_t ncell,
+                                    int32_t nclass, int64_t plane_class_stride, const int16_t *mask, const int16_t *mask0,
+                                    int64_t index_stride_cell, int64_t index_stride_class, int64_t *nkept) {
+    const ibh_plane_pack pack = {mv, planes, plane_type, nvar, nclass, plane_class_stride, index_stride_cell, index_stride_class};
+    return ibh_multivec_append_planes_many_host(&pack, 1, ncell, mask, mask0, nkept);
+}
+int ibh_multivec_affine_device(ibh_multivec *mv, const double *mm, const double *bb, void *stream) {
+    return guarded([&] {
+        check_mv(mv);
+        IBH_CHECK(mm && bb, "affine: null coefficient array");
+        if (mv->n == 0) return;
+        for (int v0 = 0; v0 < mv->nvar; v0 += AFF_VC) {
+            const int nc = std::min(AFF_VC, mv->nvar - v0);
+            AffineArgs P{};
+            for (int k = 0; k < nc; ++k) { P.mm[k] = mm[v0 + k]; P.bb[k] = bb[v0 + k]; }
+            const long blocks = std::min<long>(((long)mv->n * nc + 255) / 256, 1l << 20);
+            hipLaunchKernelGGL(k_mv_affine, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, mv->vals.p, (long)mv->n, (int)mv->nvar, v0,
+                               nc, P);
+        }
+        IBH_HIP(hipGetLastError());
     });
 }
 

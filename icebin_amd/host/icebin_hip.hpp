@@ -437,6 +437,41 @@ public:
         check(ibh_multivec_append_weighted_device(h_, M.handle(), dB_b, nvar_, ldb, stream));
     }
     void append(VectorMultivec const &other) { check(ibh_multivec_append(h_, other.h_)); }
+    /** update_topo's packing (modele/GCMCoupler_ModelE.cpp:1099-1164; ibh_multivec_append_planes_host): for ihc < nclass (outer)
+        and every cell c ascending with mask[c] != 0 || (mask0 && mask0[c] != 0) one entry (c * index_stride_cell + ihc *
+        index_stride_class, planes[k][ihc * plane_class_stride + c] for every k, weight 1.0).  planes: nvar() host arrays; types:
+        0 double / 1 int16 per plane, empty: all double.  Returns the kept cells.  The _device form takes device planes and masks. */
+    long append_planes(std::vector<const void *> const &planes, std::vector<int32_t> const &types, long ncell, int nclass,
+                       long plane_class_stride, const int16_t *mask, const int16_t *mask0, long index_stride_cell, long index_stride_class) {
+        int64_t nkept = 0;
+        check(ibh_multivec_append_planes_host(h_, planes.data(), plane_types(planes, types), (int32_t)planes.size(), ncell, nclass,
+                                              plane_class_stride, mask, mask0, index_stride_cell, index_stride_class, &nkept));
+        return (long)nkept;
+    }
+    long append_planes_device(std::vector<const void *> const &d_planes, std::vector<int32_t> const &types, long ncell, int nclass,
+                              long plane_class_stride, const int16_t *d_mask, const int16_t *d_mask0, long index_stride_cell,
+                              long index_stride_class, void *stream) {
+        int64_t nkept = 0;
+        check(ibh_multivec_append_planes_device(h_, d_planes.data(), plane_types(d_planes, types), (int32_t)d_planes.size(), ncell, nclass,
+                                                plane_class_stride, d_mask, d_mask0, index_stride_cell, index_stride_class, &nkept, stream));
+        return (long)nkept;
+    }
+    /** couple()'s unit conversion (modele/GCMCoupler_ModelE.cpp:1216-1228) over every entry: val = val * mm[ivar] + bb[ivar], a
+        product then an add.  Enqueued on `stream`. */
+    void affine(std::vector<double> const &mm, std::vector<double> const &bb, void *stream = nullptr) {
+        if ((int)mm.size() != nvar() || (int)bb.size() != nvar())
+            throw Exception(IBH_EINVAL, "affine: " + std::to_string(mm.size()) + " mm and " + std::to_string(bb.size()) + " bb for nvar=" +
+                                            std::to_string(nvar()));
+        check(ibh_multivec_affine_device(h_, mm.data(), bb.data(), stream));
+    }
+private:
+    static const int32_t *plane_types(std::vector<const void *> const &planes, std::vector<int32_t> const &types) {
+        if (types.empty()) return nullptr;
+        if (types.size() != planes.size())
+            throw Exception(IBH_EINVAL, "append_planes: " + std::to_string(types.size()) + " types for " + std::to_string(planes.size()) + " planes");
+        return types.data();
+    }
+public:
 
     /** to_dense_scale(scaleE) (multivec.cpp:35-50): scaleE's length is nE. */
     void to_dense_scale(std::vector<double> &scaleE) const { check(ibh_multivec_to_dense_scale_host(h_, (int64_t)scaleE.size(), scaleE.data())); }
@@ -1357,6 +1392,81 @@ struct TopoO {
     std::vector<int16_t> mergemask;
 };
 
+/** The end of GCMCoupler_ModelE::update_topo (modele/GCMCoupler_ModelE.cpp:1090-1167) and couple()'s unit conversion
+    (:1216-1228): the TOPOA planes packed into gcm_ivalss_s[ATOPO] and [ETOPO] on the device, from one pass over the masks
+    (ibh_multivec_append_planes_many_host).  varsA: the ATOPO contract's variables, names of TopoABundles' 2-D planes; varsE: the
+    ETOPO contract's, out of fhc elevE underice_d (the int16 plane, converted while it is packed); an unknown name throws
+    IBH_ENOKEY, as the reference's .at(name) throws (:1114, :1147).  index_strides_E: indexingE as {stride of the cell j * im + i,
+    stride of the class}.  mm / bb: the contract's scale and offset per variable (one empty: ones / zeros; both empty: no
+    conversion).  The object owns mergemaskA0, the previous step's mask (:1017, :1167). */
+class TopoPacker {
+    std::vector<std::string> varsA_, varsE_;
+    std::array<long, 2> stridesE_;
+    std::vector<double> mmA_, bbA_, mmE_, bbE_;
+    std::vector<int16_t> mergemaskA0_;
+    bool have0_ = false;
+
+    static void units(std::vector<double> &mm, std::vector<double> &bb, size_t nvar) {
+        if (mm.empty() && bb.empty()) return;
+        if (mm.empty()) mm.assign(nvar, 1.);
+        if (bb.empty()) bb.assign(nvar, 0.);
+        if (mm.size() != nvar || bb.size() != nvar)
+            throw Exception(IBH_EINVAL, "TopoPacker: " + std::to_string(mm.size()) + " mm and " + std::to_string(bb.size()) + " bb for " +
+                                            std::to_string(nvar) + " variables");
+    }
+    static const void *planeA(TopoA const &a, std::string const &name) {
+        const char *names[9] = {"focean", "flake", "fgrnd", "fgice", "zatmo", "hlake", "zicetop", "zland_min", "zland_max"};
+        std::vector<double> const *planes[9] = {&a.focean, &a.flake, &a.fgrnd, &a.fgice, &a.zatmo, &a.hlake, &a.zicetop, &a.zland_min, &a.zland_max};
+        for (int k = 0; k < 9; ++k)
+            if (name == names[k]) return planes[k]->data();
+        throw Exception(IBH_ENOKEY, "TopoPacker: no TOPOA plane named '" + name + "'");
+    }
+    static const void *planeE(TopoA const &a, std::string const &name, int32_t &type) {
+        type = name == "underice_d";
+        if (name == "fhc") return a.fhc.data();
+        if (name == "elevE") return a.elevE.data();
+        if (name == "underice_d") return a.underice.data();
+        throw Exception(IBH_ENOKEY, "TopoPacker: no TOPOE array named '" + name + "'");
+    }
+public:
+    TopoPacker(std::vector<std::string> varsA, std::vector<std::string> varsE, std::array<long, 2> index_strides_E, std::vector<double> mmA = {},
+               std::vector<double> bbA = {}, std::vector<double> mmE = {}, std::vector<double> bbE = {})
+        : varsA_(std::move(varsA)), varsE_(std::move(varsE)), stridesE_(index_strides_E), mmA_(std::move(mmA)), bbA_(std::move(bbA)),
+          mmE_(std::move(mmE)), bbE_(std::move(bbE)) {
+        TopoA none;
+        int32_t type;
+        for (std::string const &n : varsA_) planeA(none, n);
+        for (std::string const &n : varsE_) planeE(none, n, type);
+        units(mmA_, bbA_, varsA_.size());
+        units(mmE_, bbE_, varsE_.size());
+    }
+    std::vector<int16_t> const &mergemaskA0() const { return mergemaskA0_; }
+
+    /** a: update_topo's / make_topoA's planes; nhc: the classes to pack (a.fhc, a.elevE and a.underice carry nhc + 1: the
+        sea-land class is not packed, as in the reference).  run_ice = false (initialisation): the previous mask is this step's
+        (:1017); afterwards this step's mask is kept (:1167).  The entries go behind those outA / outE hold; the conversion runs
+        over ALL entries of each vector, as :1216-1228 does. */
+    void pack(TopoA const &a, int nhc, bool run_ice, VectorMultivec &outA, VectorMultivec &outE) {
+        const long ncell = (long)a.mergemask.size();
+        if (run_ice && !have0_) throw Exception(IBH_EINVAL, "TopoPacker::pack: run_ice without a mask of an earlier step");
+        if (run_ice && (long)mergemaskA0_.size() != ncell)
+            throw Exception(IBH_EINVAL, "TopoPacker::pack: the previous mask has " + std::to_string(mergemaskA0_.size()) + " cells, this one " +
+                                            std::to_string(ncell));
+        std::vector<const void *> pA, pE;
+        std::vector<int32_t> tE(varsE_.size(), 0);
+        for (std::string const &n : varsA_) pA.push_back(planeA(a, n));
+        for (size_t k = 0; k < varsE_.size(); ++k) pE.push_back(planeE(a, varsE_[k], tE[k]));
+        const ibh_plane_pack packs[2] = {{outA.handle(), pA.data(), nullptr, (int32_t)pA.size(), 1, ncell, 1, ncell},
+                                         {outE.handle(), pE.data(), tE.data(), (int32_t)pE.size(), nhc, ncell, stridesE_[0], stridesE_[1]}};
+        check(ibh_multivec_append_planes_many_host(packs, 2, ncell, a.mergemask.data(), run_ice ? mergemaskA0_.data() : a.mergemask.data(),
+                                                   nullptr));
+        mergemaskA0_ = a.mergemask;
+        have0_ = true;
+        if (!mmA_.empty()) outA.affine(mmA_, bbA_);
+        if (!mmE_.empty()) outE.affine(mmE_, bbE_);
+    }
+};
+
 /** GCMRegridder_ModelE (GCMRegridder_ModelE.hpp:102-200): gcmO regrids between (AOp, EOp, Ip) on ModelE's ocean grid; this
     class hands out the matrices between (AAm, EAm, Ip).  The reference reads the ocean HntrSpec and the earth's radius from
     gcmO's grid spec; here the caller names them.  The base ice of the global_ecO file comes in memory (EOpvAOpBase); the file
@@ -1412,8 +1522,8 @@ public:
 
     /** GCMCoupler_ModelE::update_topo's body (modele/GCMCoupler_ModelE.cpp:1026-1082): merge_topoO with RegridParams(false, true,
         0), global_AvE(scale = true), wEAm_base, make_topoA.  topoo holds the merged planes afterwards.  Throws with the
-        sanity-check strings when a check fails.  Reading the TOPOO file, packing into VectorMultivecs (:1099-1170) and
-        mergemaskA0 stay with the caller. */
+        sanity-check strings when a check fails.  Reading the TOPOO file stays with the caller; the packing into VectorMultivecs
+        (:1099-1167) is the overload below. */
     TopoA update_topo(TopoO &topoo, std::vector<ArrayView<const double>> const &emI_lands,
                       std::vector<ArrayView<const double>> const &emI_ices) const {
         const size_t nO = (size_t)hspecO_.size();
@@ -1455,6 +1565,16 @@ public:
                         *AAmvEAm, a.focean.data(), a.flake.data(), a.fgrnd.data(), a.fgice.data(), a.zatmo.data(), a.hlake.data(),
                         a.zicetop.data(), a.zland_min.data(), a.zland_max.data(), a.mergemask.data(), a.fhc.data(), a.elevE.data(),
                         a.underice.data()));
+        return a;
+    }
+
+    /** update_topo to its end (:1026-1167) with couple()'s unit conversion (:1216-1228): the planes as above, then packed by
+        `packer` (which holds mergemaskA0 from step to step) behind the entries of gcm_ivalsA / gcm_ivalsE, every class of hcdefs(). */
+    TopoA update_topo(TopoO &topoo, std::vector<ArrayView<const double>> const &emI_lands,
+                      std::vector<ArrayView<const double>> const &emI_ices, bool run_ice, TopoPacker &packer, VectorMultivec &gcm_ivalsA,
+                      VectorMultivec &gcm_ivalsE) const {
+        TopoA a = update_topo(topoo, emI_lands, emI_ices);
+        packer.pack(a, (int)hcdefs().size(), run_ice, gcm_ivalsA, gcm_ivalsE);
         return a;
     }
 

@@ -294,6 +294,74 @@ def make_topoA(topoo, mergemaskOm, hspecO, hspecA, indexingHCA, hcdefs, underice
     return topoa, errors
 
 
+TOPOE_NAMES = ("fhc", "elevE", "underice_d")       # topoa.a3's arrays once underice_d is added (GCMCoupler_ModelE.cpp:1090-1097)
+
+
+class TopoPacker:
+    """The end of GCMCoupler_ModelE::update_topo (modele/GCMCoupler_ModelE.cpp:1090-1167) and couple()'s unit conversion
+    (:1216-1228): the TOPOA planes packed into the two VectorMultivecs ModelE scatters, gcm_ivalss_s[ATOPO] and [ETOPO].
+
+    varsA: the contract's ATOPO variables, names of TopoABundles' 2-D planes; varsE: the ETOPO variables, names out of fhc,
+    elevE, underice_d; an unknown name raises KeyError (the reference's .at(name), :1114, :1147).  index_strides_E: indexingE
+    as (stride of the cell j * im + i, stride of the class).  mm / bb: the contract's scale and offset per variable; without
+    either no conversion runs.  The object owns mergemaskA0, the previous step's mask (:1017, :1167): on the device when the
+    planes are, else numpy."""
+
+    def __init__(self, varsA, varsE, index_strides_E, mmA=None, bbA=None, mmE=None, bbE=None):
+        self.varsA, self.varsE = tuple(varsA), tuple(varsE)
+        for name in self.varsA:
+            if name not in TOPOA_NAMES:
+                raise KeyError(name)
+        for name in self.varsE:
+            if name not in TOPOE_NAMES:
+                raise KeyError(name)
+        self.index_strides_E = (int(index_strides_E[0]), int(index_strides_E[1]))
+        self.affineA = self._affine(mmA, bbA, len(self.varsA))
+        self.affineE = self._affine(mmE, bbE, len(self.varsE))
+        self.mergemaskA0 = None
+
+    @staticmethod
+    def _affine(mm, bb, nvar):
+        if mm is None and bb is None:
+            return None
+        mm = np.ones(nvar) if mm is None else np.asarray(mm, np.float64).reshape(-1)
+        bb = np.zeros(nvar) if bb is None else np.asarray(bb, np.float64).reshape(-1)
+        if len(mm) != nvar or len(bb) != nvar:
+            raise ValueError("%d mm and %d bb for %d variables" % (len(mm), len(bb), nvar))
+        return mm, bb
+
+    def pack(self, topoa, nhc, run_ice, outA=None, outE=None):
+        """topoa: make_topoA's / update_topo's dict; nhc: the classes to pack (fhc, elevE and underice carry nhc + 1: the
+        sea-land class is not packed, as in the reference).  run_ice = False (initialisation): the previous mask is this
+        step's (:1017).  Afterwards this step's mask is kept -- the array itself, as the reference keeps a reference (:1167).
+        outA / outE: vectors to append to (default: fresh ones).  The conversion runs over ALL entries of each vector, as
+        :1216-1228 does: append what else belongs in them first.  -> (gcm_ivalsA, gcm_ivalsE)."""
+        from .multivec import VectorMultivec, append_planes_many
+        mask = topoa["mergemask"]
+        on_device = _is_device(mask)
+        ncell = mask.numel() if on_device else np.asarray(mask).size
+        if not run_ice:
+            mask0 = mask
+        else:
+            mask0 = self.mergemaskA0
+            if mask0 is None:
+                raise RuntimeError("TopoPacker.pack: run_ice without a mask of an earlier step (initialise with run_ice=False)")
+            if _is_device(mask0) != on_device:      # the planes moved between the host and the device since the last step
+                import torch
+                mask0 = torch.from_numpy(np.ascontiguousarray(mask0)).to(mask.device) if on_device else mask0.cpu().numpy()
+        source = {"fhc": "fhc", "elevE": "elevE", "underice_d": "underice"}
+        outA = VectorMultivec(len(self.varsA)) if outA is None else outA
+        outE = VectorMultivec(len(self.varsE)) if outE is None else outE
+        append_planes_many([dict(vec=outA, planes=[topoa[k] for k in self.varsA], nclass=1, index_strides=(1, ncell)),
+                            dict(vec=outE, planes=[topoa[source[k]] for k in self.varsE], nclass=int(nhc), plane_class_stride=ncell,
+                                 index_strides=self.index_strides_E)], mask, mask0)
+        self.mergemaskA0 = mask
+        for vec, aff in ((outA, self.affineA), (outE, self.affineE)):
+            if aff is not None:
+                vec.affine(*aff)
+        return outA, outE
+
+
 class GCMRegridder_ModelE:
     """GCMRegridder_WrapE (modele/GCMRegridder_ModelE.hpp): a GCMRegridder_ModelE over `gcmO` together with the two ocean
     fractions, so that regrid_matrices keeps the signature of GCMRegridder.regrid_matrices.  global_ec = (hcdefs_base, (iE, iO,
@@ -347,15 +415,16 @@ class GCMRegridder_ModelE:
                                         nO=self.gcmO.nA, indexingHC_base=self.gcmO._hc_strides)
         return compute_AAmvEAm(merged, self.hspecO, self.eq_rad, foceanAOp, foceanAOm, scale=scale), merged.offsetE
 
-    def update_topo(self, topoo, emI_lands, emI_ices, run_ice=True):
-        """GCMCoupler_ModelE::update_topo's body (modele/GCMCoupler_ModelE.cpp:1026-1082): merge_topoO with RegridParams(false,
-        true, 0), global_AvE(scale = true), wEAm_base, make_topoA.  topoo: a dict of the twelve planes under topoo_bundle's
+    def update_topo(self, topoo, emI_lands, emI_ices, run_ice=True, packer=None):
+        """GCMCoupler_ModelE::update_topo's body (modele/GCMCoupler_ModelE.cpp:1026-1167): merge_topoO with RegridParams(false,
+        true, 0), global_AvE(scale = true), wEAm_base, make_topoA and, with a TopoPacker, the packing.  topoo: a dict of the twelve planes under topoo_bundle's
         names (ZLAND_MIN / ZLAND_MAX need not be there); it holds the merged planes afterwards.  Numpy planes and masks go
         through the host entries; torch CUDA planes and masks stay in HBM between the calls (global_AvE alone reads the two
         ocean fractions on the host).  Raises RuntimeError with the sanity-check strings when a check fails.  Returns a dict:
         the TOPOA planes under TopoABundles' names, mergemask, fhc, elevE, underice, wEAm_base = (iE, weight) of the entries of
-        AAmvEAm's Mw whose sparse index is >= offsetE, and offsetE.  Not done here: reading the TOPOO file, packing into
-        VectorMultivecs (:1099-1170) and mergemaskA0."""
+        AAmvEAm's Mw whose sparse index is >= offsetE, and offsetE.  packer: a TopoPacker, which holds mergemaskA0 from step
+        to step; the dict then also has gcm_ivalsA and gcm_ivalsE, the VectorMultivecs of :1099-1164 after couple()'s unit
+        conversion (:1216-1228), packed on the device without a host copy of any plane.  Not done here: reading the TOPOO file."""
         mergemaskOm, errors = merge_topoO(topoo, self.gcmO, emI_lands, emI_ices, self.hspecO, self.eq_rad)
         self.foceanOp = np.ascontiguousarray(_host(topoo["FOCEANF"]), np.float64).reshape(-1).copy()
         if not run_ice:
@@ -374,6 +443,8 @@ class GCMRegridder_ModelE:
         if errors2:
             raise RuntimeError("Errors in TOPO merging or regridding; halting!\n" + "\n".join("ERROR: " + e for e in errors2))
         topoa.update(wEAm_base=(iE[keep].copy(), Mw[keep].copy()), offsetE=offsetE)
+        if packer is not None:
+            topoa["gcm_ivalsA"], topoa["gcm_ivalsE"] = packer.pack(topoa, nhc, run_ice)
         return topoa
 
     def agridA(self, sheet_name):

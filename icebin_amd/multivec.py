@@ -125,6 +125,24 @@ class VectorMultivec:
     def append(self, other):
         check(lib().ibh_multivec_append(self._h, other._h))
 
+    def append_planes(self, planes, mask, mask0=None, nclass=1, plane_class_stride=None, index_strides=None, types=None):
+        """update_topo's packing (modele/GCMCoupler_ModelE.cpp:1099-1164): for ihc < nclass (outer) and every cell c ascending
+        with mask[c] != 0 or mask0[c] != 0, one entry (c * index_strides[0] + ihc * index_strides[1], planes[k][ihc *
+        plane_class_stride + c] for every k, weight 1.0) -> the number of kept cells.  planes: nvar float64 or int16 arrays
+        (types: 0 / 1 per plane, default: by dtype); mask, mask0: int16, ncell = mask's size.  All numpy arrays, or all torch
+        CUDA tensors (used in place, on torch's current stream).  Defaults: plane_class_stride = ncell, index_strides = (1, ncell)."""
+        return append_planes_many([dict(vec=self, planes=planes, nclass=nclass, plane_class_stride=plane_class_stride,
+                                        index_strides=index_strides, types=types)], mask, mask0)
+
+    def affine(self, mm, bb):
+        """couple()'s unit conversion (modele/GCMCoupler_ModelE.cpp:1216-1228): vals[:, k] = vals[:, k] * mm[k] + bb[k] over every
+        entry, one product then one add.  Enqueued on torch's current stream; the grouping of the merge calls stays valid."""
+        import torch
+        mm, bb = np.ascontiguousarray(mm, np.float64).reshape(-1), np.ascontiguousarray(bb, np.float64).reshape(-1)
+        if len(mm) != self.nvar or len(bb) != self.nvar:
+            raise ValueError("affine: %d mm and %d bb for nvar=%d" % (len(mm), len(bb), self.nvar))
+        check(lib().ibh_multivec_affine_device(self._h, ptr(mm), ptr(bb), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+
     def to_dense_scale(self, nE, out=None):
         """1 / (sum of weights per cell) over [0, nE), +inf where no entry falls (multivec.cpp:35-50).  Returns a CUDA tensor
         (or fills `out`)."""
@@ -167,6 +185,68 @@ class VectorMultivec:
         assert _is_cuda(out) and out.dtype == torch.float64 and out.shape == (self.nvar, nd) and out.stride(1) == 1
         check(lib().ibh_multivec_densify_device(self._h, sparse_set._h, C.c_void_p(out.data_ptr()), max(out.stride(0), nd), _stream(out)))
         return out
+
+
+def append_planes_many(packs, mask, mask0=None):
+    """VectorMultivec.append_planes for several vectors from ONE pass over the masks (ibh_multivec_append_planes_many_*): packs
+    is a list of dict(vec, planes, nclass=1, plane_class_stride=None, index_strides=None, types=None) -> the number of kept
+    cells.  The masks and every plane are numpy arrays, or all are torch CUDA tensors."""
+    arrays = [mask] + ([] if mask0 is None else [mask0]) + [p for k in packs for p in k["planes"]]
+    dev = [_is_cuda(a) for a in arrays]
+    if any(dev) and not all(dev):
+        raise ValueError("append_planes: host and device arrays are mixed")
+    on_device = dev[0]
+    if on_device:
+        import torch
+
+    def flat(a, int16_only=False):
+        if on_device:
+            if a.dtype not in ((torch.int16,) if int16_only else (torch.int16, torch.float64)) or not a.is_contiguous():
+                raise ValueError("append_planes: a device array must be a contiguous %s CUDA tensor" % ("int16" if int16_only else "float64 or int16"))
+            return a.reshape(-1)
+        a = np.asarray(a)
+        return np.ascontiguousarray(a, np.int16 if int16_only or a.dtype == np.int16 else np.float64).reshape(-1)
+
+    def address(a):
+        return a.data_ptr() if on_device else a.ctypes.data
+
+    def size(a):
+        return a.numel() if on_device else a.size
+
+    m = flat(mask, True)
+    m0 = None if mask0 is None else flat(mask0, True)
+    ncell = size(m)
+    if m0 is not None and size(m0) != ncell:
+        raise ValueError("append_planes: mask0 has %d cells, mask %d" % (size(m0), ncell))
+    keep, structs = [m, m0], (_capi.PlanePack * len(packs))()
+    for s, k in zip(structs, packs):
+        vec, nclass = k["vec"], int(k.get("nclass", 1))
+        stride = k.get("plane_class_stride")
+        stride = ncell if stride is None else int(stride)
+        strides = k.get("index_strides") or (1, ncell)
+        planes = [flat(p) for p in k["planes"]]
+        by_dtype = [int(p.dtype == (torch.int16 if on_device else np.int16)) for p in planes]
+        types = np.ascontiguousarray(by_dtype if k.get("types") is None else k["types"], np.int32).reshape(-1)
+        if len(types) != len(planes) or any(t in (0, 1) and t != d for t, d in zip(types, by_dtype)):
+            raise ValueError("append_planes: types %s for planes of types %s" % (types.tolist(), by_dtype))
+        need = (max(nclass, 1) - 1) * stride + ncell
+        for p in planes:
+            if nclass > 0 and size(p) < need:
+                raise ValueError("append_planes: a plane has %d elements, %d classes of stride %d over %d cells need %d"
+                                 % (size(p), nclass, stride, ncell, need))
+        table = (C.c_void_p * max(len(planes), 1))(*[address(p) for p in planes])
+        keep += [planes, types, table]
+        s.mv, s.planes, s.plane_type = vec._h.value, C.cast(table, C.c_void_p).value, types.ctypes.data
+        s.nvar, s.nclass, s.plane_class_stride = len(planes), nclass, stride
+        s.index_stride_cell, s.index_stride_class = int(strides[0]), int(strides[1])
+    nkept = C.c_int64()
+    if on_device:
+        check(lib().ibh_multivec_append_planes_many_device(C.cast(structs, C.c_void_p), len(packs), ncell, C.c_void_p(address(m)),
+                                                          None if m0 is None else C.c_void_p(address(m0)), C.byref(nkept), _stream(m)))
+    else:
+        check(lib().ibh_multivec_append_planes_many_host(C.cast(structs, C.c_void_p), len(packs), ncell, C.c_void_p(address(m)),
+                                                        None if m0 is None else C.c_void_p(address(m0)), C.byref(nkept)))
+    return nkept.value
 
 
 def concatenate(vecs):

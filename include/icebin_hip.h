@@ -811,6 +811,43 @@ int ibh_multivec_device_view_get(const ibh_multivec *mv, ibh_multivec_device_vie
  * nvar != the vector's is IBH_EINVAL.  A pure enqueue on `stream` when the capacity suffices. */
 int ibh_multivec_append_weighted_device(ibh_multivec *mv, const ibh_weighted *w, const double *dB_b, int32_t nvar, int64_t ldb,
                                         void *stream);
+/* update_topo's packing of the TOPO planes (modele/GCMCoupler_ModelE.cpp:1099-1164).  Appends, for ihc = 0..nclass-1 (outer)
+ * and every cell c = 0..ncell-1 ascending with d_mask[c] != 0 || (d_mask0 && d_mask0[c] != 0) -- :1122, :1156; d_mask0 is the
+ * previous step's mask (:1017, :1167), NULL: none -- one entry:
+ *   index = c * index_stride_cell + ihc * index_stride_class (indexingA / indexingE's tuple_to_index), weight = 1.0,
+ *   vals[k] = plane k at [ihc * plane_class_stride + c]   (type 0: double, copied bit for bit; type 1: int16, converted: the
+ *             underice_d of :1090-1097 without the double plane)
+ * d_planes: HOST array of nvar device pointers; plane_type: [nvar] on the host, NULL = all double.  *nkept = the kept cells
+ * (may be NULL).  The nclass * nkept entries go behind the existing ones; no floating-point arithmetic but the conversion.
+ * ONE host wait on `stream` (the count, which sizes the buffers).  ncell == 0 or nclass == 0 appends nothing.
+ * IBH_EINVAL, naming the offender and before the vector is touched: a null handle, mask or plane (where one would be read),
+ * nvar != the vector's, a plane type other than 0 or 1, ncell < 0, nclass < 0, a negative class stride, 2^31 cells or more, a
+ * total of 2^31 entries or more.
+ * The _many form packs several vectors from ONE pass over the masks (the A and the E vector of an update_topo share the list
+ * of kept cells); a vector may be named by one pack only. */
+typedef struct ibh_plane_pack {
+    ibh_multivec *mv;
+    const void *const *planes;      /* HOST array of nvar plane pointers: device planes for _device, host planes for _host */
+    const int32_t *plane_type;      /* [nvar] on the host, NULL: all double */
+    int32_t nvar, nclass;
+    int64_t plane_class_stride, index_stride_cell, index_stride_class;
+} ibh_plane_pack;
+int ibh_multivec_append_planes_device(ibh_multivec *mv, const void *const *d_planes, const int32_t *plane_type, int32_t nvar, int64_t ncell,
+                                      int32_t nclass, int64_t plane_class_stride, const int16_t *d_mask, const int16_t *d_mask0,
+                                      int64_t index_stride_cell, int64_t index_stride_class, int64_t *nkept, void *stream);
+int ibh_multivec_append_planes_many_device(const ibh_plane_pack *packs, int32_t npack, int64_t ncell, const int16_t *d_mask,
+                                           const int16_t *d_mask0, int64_t *nkept, void *stream);
+/* The same from host arrays (plane k holds (nclass - 1) * plane_class_stride + ncell elements): copied in, the device call
+ * runs on the default stream. */
+int ibh_multivec_append_planes_host(ibh_multivec *mv, const void *const *planes, const int32_t *plane_type, int32_t nvar, int64_t ncell,
+                                    int32_t nclass, int64_t plane_class_stride, const int16_t *mask, const int16_t *mask0,
+                                    int64_t index_stride_cell, int64_t index_stride_class, int64_t *nkept);
+int ibh_multivec_append_planes_many_host(const ibh_plane_pack *packs, int32_t npack, int64_t ncell, const int16_t *mask, const int16_t *mask0,
+                                         int64_t *nkept);
+/* couple()'s unit conversion (modele/GCMCoupler_ModelE.cpp:1216-1228) over ALL entries: vals[ix * nvar + k] = vals[ix * nvar + k]
+ * * mm[k] + bb[k], one product then one add, no contraction.  mm, bb: [nvar] on the host, read during the call.  A pure enqueue;
+ * no index changes, so the grouping of the merge calls stays valid. */
+int ibh_multivec_affine_device(ibh_multivec *mv, const double *mm, const double *bb, void *stream);
 /* concatenate() (multivec.cpp:15-33): the entries of `other` behind mv's / of mvs[0..k) in order into a new vector.
  * k == 0 or differing nvar is IBH_EINVAL (:19-20, :29-30).  Device copies on the default stream. */
 int ibh_multivec_append(ibh_multivec *mv, const ibh_multivec *other);
