@@ -237,6 +237,12 @@ _SIGS = {
                                         C.c_int64, C.c_int, C.c_double, C.c_double, C.c_void_p]),
     "ibh_hntr_regrid_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p,
                                       C.c_int64, C.c_int, C.c_double, C.c_double]),
+    "ibh_hntr_regrid_typed_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_double, C.c_void_p, C.c_int, C.c_int32,
+                                              C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_double, C.c_double, C.c_void_p]),
+    "ibh_hntr_regrid_typed_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_double, C.c_void_p, C.c_int, C.c_int32,
+                                            C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_double, C.c_double]),
+    "ibh_hntr_regrid_shape": (C.c_int, [C.c_void_p, C.c_int32, C.c_int, C.c_int, C.c_int64, C.c_int, C.POINTER(C.c_int32),
+                                       C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     "ibh_hntr_partition": (C.c_int, [C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_double, C.c_double]
                            + [C.c_void_p] * 10),
     "ibh_hntr_dxyp": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p]),

@@ -21,6 +21,18 @@
 // leave fewer than 16 columns); the LDS a workgroup asks for is what its tile needs, so small tiles leave room for more
 // workgroups per CU.  A lane holds at most HNTR_STAGE staged doubles, which keeps the kernel within 141 VGPRs (no
 // spills to AGPRs or scratch).
+//
+// Typed planes and a constant weight (the reference's template regrid<WeightT, SrcT, DestT>, hntr.hpp:385-391, as its TOPO
+// tools instantiate it: int16 planes, const_array(shape, c) as the weight).  The kernel is a template over the weight form
+// (double, float, int16_t planes or HntrConstW) and the source element type (double, float, int16_t); B stays double.  An
+// element is converted to double, exactly, as it is loaded, and staged into LDS as a double: the LDS layout, the odd row
+// stride S = K | 1 in doubles and the chains are those of the double kernel, so the bits are those of the double kernel on
+// the widened planes.  K depends on the number of staged planes P alone, not on the element size: P = 1 + NV with a weight
+// plane, P = NV under a constant weight, where no weight plane is loaded or staged and wta = wtm*c + wtb is computed per term
+// in the same place (the bits of a plane filled with c); there the larger LDS budget is 32 KiB, not 40 (hntr_shape).  Loads are one element per lane (2, 4 or 8 bytes), consecutive lanes
+// on consecutive columns: no load is wider than an element, so a plane base aligned to its element only (an odd lda of int16
+// planes, a pointer at an odd element offset), a window that starts at any column or wraps the date line, and an odd imA need
+// no special case, and no load touches an element outside [0, imA*jmA) of its plane.
 #include <algorithm>
 #include <cmath>
 #include <memory>
@@ -33,6 +45,7 @@ namespace ibh {
 
 constexpr int HNTR_LDS = 5056;      // most doubles of LDS per workgroup: with the row windows, 40 KiB (four workgroups per CU)
 constexpr int HNTR_LDS_SMALL = 2496;    // the same for 20 KiB (eight workgroups per CU)
+constexpr int HNTR_LDS_CONST = 4032;    // under a constant weight, in place of HNTR_LDS: 32 KiB (five workgroups per CU)
 constexpr int HNTR_STAGE = 32;      // doubles a lane holds between its global loads and its LDS writes
 
 // ---- partition (hntr.cpp:63-168), host side ----------------------------------------------------
@@ -142,10 +155,11 @@ static void hntr_partition(int imA, int jmA, double offiA, double dlatA, int imB
 struct HntrArgs {
     const double *SINA, *FMIN, *FMAX, *GMIN, *GMAX;
     const int32_t *IMIN, *IMAX, *JMIN, *JMAX;
-    const double *WTA;
-    int64_t wta_ld;         // 0: one WTA plane shared by all fields
-    const double *A;
-    int64_t lda;
+    const void *WTA;        // planes of the kernel's weight type; unused under a constant weight
+    int64_t wta_ld;         // 0: one WTA plane shared by all fields; in elements of the weight type
+    double wconst;          // the constant weight (HntrConstW)
+    const void *A;          // planes of the kernel's source type
+    int64_t lda;            // in elements of the source type
     double *B;
     int64_t ldb;
     int imA, imB, jmB, nvar;
@@ -153,12 +167,18 @@ struct HntrArgs {
     double wtm, wtb, datmis;
 };
 
+struct HntrConstW {};       // the weight type of a constant weight: no plane is loaded or staged
+
 // One wave per workgroup: column IB = blockIdx.x % imB, rows jb0 .. jb0+L-1, fields NV*blockIdx.y .. (at most NV).
 // A shared weight feeds the NV VALUE chains from one wt / WEIGHT chain; per-field weights run with NV = 1.
-template <int NV>
+// WT: double, float, int16_t or HntrConstW; ST: double, float or int16_t.  An element becomes a double as it is loaded.
+template <int NV, class WT, class ST>
 __global__ __launch_bounds__(64) void hntr_regrid_kernel(HntrArgs a) {
-    constexpr int P = 1 + NV;                       // staged planes: WTA, then the fields
-    constexpr int U = HNTR_STAGE / P > 1 ? HNTR_STAGE / P : 1;    // staged items per lane in flight
+    constexpr bool CW = std::is_same<WT, HntrConstW>::value;
+    constexpr int PW = CW ? 0 : 1;                  // staged weight planes
+    constexpr int P = PW + NV;                      // staged planes: WTA (if any), then the fields
+    constexpr int U = HNTR_STAGE / (1 + NV) > 1 ? HNTR_STAGE / (1 + NV) : 1;   // staged items per lane in flight (a constant weight: as with a plane)
+    using WE = typename std::conditional<CW, double, WT>::type;
     extern __shared__ double lds[];                 // [P][L][S], L*S*P <= HNTR_LDS
     __shared__ int sj0[64], sj1[64];
 
@@ -167,8 +187,8 @@ __global__ __launch_bounds__(64) void hntr_regrid_kernel(HntrArgs a) {
     const int jb0 = (blockIdx.x / a.imB) * a.L;
     const int f0 = blockIdx.y * NV;
     const int nv = min(NV, a.nvar - f0);
-    const double *__restrict__ W = a.wta_ld ? a.WTA + (int64_t)f0 * a.wta_ld : a.WTA;
-    const double *__restrict__ Af = a.A + (int64_t)f0 * a.lda;
+    const WE *__restrict__ W = static_cast<const WE *>(a.WTA) + (a.wta_ld ? (int64_t)f0 * a.wta_ld : 0);
+    const ST *__restrict__ Af = static_cast<const ST *>(a.A) + (int64_t)f0 * a.lda;
     const int L = a.L, S = a.S, K = a.K, imA = a.imA;
     const int64_t plane = (int64_t)L * S;
 
@@ -226,10 +246,10 @@ __global__ __launch_bounds__(64) void hntr_regrid_kernel(HntrArgs a) {
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
                     if (off[u] >= 0) {
-                        v[u][0] = W[off[u]];
+                        if (!CW) v[u][0] = (double)W[off[u]];
 #pragma unroll
                         for (int f = 0; f < NV; ++f)
-                            if (f < nv) v[u][1 + f] = Af[(int64_t)f * a.lda + off[u]];
+                            if (f < nv) v[u][PW + f] = (double)Af[(int64_t)f * a.lda + off[u]];
                     }
                 }
 #pragma unroll
@@ -237,7 +257,7 @@ __global__ __launch_bounds__(64) void hntr_regrid_kernel(HntrArgs a) {
                     if (off[u] >= 0) {
 #pragma unroll
                         for (int p = 0; p < P; ++p)
-                            if (p <= nv) lds[p * plane + dst[u]] = v[u][p];
+                            if (p < PW + nv) lds[p * plane + dst[u]] = v[u][p];
                     }
                 }
             }
@@ -251,12 +271,12 @@ __global__ __launch_bounds__(64) void hntr_regrid_kernel(HntrArgs a) {
                     if (IAREV == imn) F -= fmn;
                     if (IAREV == imx) F -= fmx;
                     const double FG = F * G;
-                    const double wta = a.wtm * row[kk] + a.wtb;
+                    const double wta = a.wtm * (CW ? a.wconst : row[kk]) + a.wtb;
                     const double wt = FG * wta;
                     WEIGHT += wt;
 #pragma unroll
                     for (int f = 0; f < NV; ++f)
-                        if (f < nv) VALUE[f] += wt * row[(1 + f) * plane + kk];
+                        if (f < nv) VALUE[f] += wt * row[(PW + f) * plane + kk];
                 }
             }
         }
@@ -309,10 +329,19 @@ struct ibh_hntr {
 
 namespace ibh {
 
-template <int NV>
-static void hntr_launch_nv(const ibh_hntr *h, HntrArgs a, hipStream_t s) {
-    const int P = 1 + NV;
-    const int ngroups = (a.nvar + NV - 1) / NV;
+// The shape of one launch, decided from the handle, nvar and the weight form alone: the planes are staged as doubles, so the
+// element types play no part.
+struct HntrShape {
+    int NV, L, K, S;        // fields per group, chain lanes per wave, columns per chunk, LDS row stride in doubles (odd, >= K)
+    int ngroups;
+    size_t lds_bytes;       // dynamic LDS of a workgroup: the staged planes, 8 * P * L * S
+};
+
+static HntrShape hntr_shape(const ibh_hntr *h, int nvar, bool const_weight, bool per_field) {
+    // fields per group: per-field weights run one field per group; a shared or constant weight serves up to 8
+    const int NV = per_field || nvar <= 1 ? 1 : nvar == 2 ? 2 : nvar <= 4 ? 4 : 8;
+    const int P = (const_weight ? 0 : 1) + NV;      // staged planes
+    const int ngroups = (nvar + NV - 1) / NV;
     // lanes per wave: all 64 when there are B cells enough for four waves per CU, fewer (more workgroups, so more
     // CUs streaming at once) for small B grids
     int L = 64;
@@ -320,29 +349,58 @@ static void hntr_launch_nv(const ibh_hntr *h, HntrArgs a, hipStream_t s) {
     if (L > h->jmB) { L = 1; while (L < h->jmB) L <<= 1; }
     // LDS per workgroup: 20 KiB (eight one-wave workgroups per CU) while that still leaves chunks of 16 columns, else up
     // to 40 KiB.  Measured from a 1' field: one field 1.38 ms at 20 KiB against 1.79 ms at 40 KiB (1/2 deg); eight fields,
-    // whose chunks would shrink to 3 columns at 20 KiB, 9.2 ms at 40 KiB against 15.3 ms.
+    // whose chunks would shrink to 3 columns at 20 KiB, 9.2 ms at 40 KiB against 15.3 ms.  Under a constant weight the large
+    // budget is 32 KiB: eight double fields onto 1 deg ran 18.5 ms with 9 columns in 36.5 KiB (four workgroups per CU) and
+    // 12.6 ms with 7 columns in 28.5 KiB (five).
     int smax = HNTR_LDS_SMALL / (L * P);
-    if (smax < std::min(h->wmax, 16)) smax = HNTR_LDS / (L * P);
+    if (smax < std::min(h->wmax, 16)) smax = (const_weight ? HNTR_LDS_CONST : HNTR_LDS) / (L * P);
     if (!(smax & 1)) --smax;
     const int K = std::min(h->wmax, smax);
-    a.L = L; a.K = K; a.S = K | 1;
-    dim3 grid((unsigned)(ceil_div(h->jmB, L) * h->imB), (unsigned)ngroups);
-    hipLaunchKernelGGL(hntr_regrid_kernel<NV>, grid, dim3(64), (size_t)L * a.S * P * sizeof(double), s, a);
-    IBH_HIP(hipGetLastError());
+    const int S = K | 1;
+    return HntrShape{NV, L, K, S, ngroups, (size_t)L * S * P * sizeof(double)};
 }
 
-static void hntr_regrid(const ibh_hntr *h, const double *dWTA, int64_t wta_ld, const double *dA, int32_t nvar, int64_t lda,
-                        double *dB, int64_t ldb, int mean_polar, double wtm, double wtb, hipStream_t s) {
+template <int NV, class WT, class ST>
+static void hntr_launch_nv(const ibh_hntr *h, HntrShape const &sh, HntrArgs a, hipStream_t s) {
+    a.L = sh.L; a.K = sh.K; a.S = sh.S;
+    dim3 grid((unsigned)(ceil_div(h->jmB, sh.L) * h->imB), (unsigned)sh.ngroups);
+    hipLaunchKernelGGL((hntr_regrid_kernel<NV, WT, ST>), grid, dim3(64), sh.lds_bytes, s, a);
+    IBH_HIP(hipGetLastError());
+}
+template <class WT, class ST>
+static void hntr_launch_types(const ibh_hntr *h, HntrShape const &sh, HntrArgs const &a, hipStream_t s) {
+    if (sh.NV == 1) hntr_launch_nv<1, WT, ST>(h, sh, a, s);
+    else if (sh.NV == 2) hntr_launch_nv<2, WT, ST>(h, sh, a, s);
+    else if (sh.NV == 4) hntr_launch_nv<4, WT, ST>(h, sh, a, s);
+    else hntr_launch_nv<8, WT, ST>(h, sh, a, s);
+}
+template <class WT>
+static void hntr_launch_weight(const ibh_hntr *h, HntrShape const &sh, HntrArgs const &a, int a_type, hipStream_t s) {
+    if (a_type == IBH_HNTR_F64) hntr_launch_types<WT, double>(h, sh, a, s);
+    else if (a_type == IBH_HNTR_F32) hntr_launch_types<WT, float>(h, sh, a, s);
+    else hntr_launch_types<WT, int16_t>(h, sh, a, s);
+}
+
+static size_t hntr_elem_size(int type) { return type == IBH_HNTR_F64 ? 8 : type == IBH_HNTR_F32 ? 4 : 2; }
+static void check_elem_type(int type, const char *which) {
+    IBH_CHECK(type == IBH_HNTR_F64 || type == IBH_HNTR_I16 || type == IBH_HNTR_F32,
+              "Hntr regrid: type code %d of %s is not IBH_HNTR_F64 (0), IBH_HNTR_I16 (1) or IBH_HNTR_F32 (2)", type, which);
+}
+
+// dWTA == nullptr: the constant weight wta_const (wta_type and wta_ld are not read)
+static void hntr_regrid(const ibh_hntr *h, const void *dWTA, int wta_type, int64_t wta_ld, double wta_const, const void *dA, int a_type,
+                        int32_t nvar, int64_t lda, double *dB, int64_t ldb, int mean_polar, double wtm, double wtb, hipStream_t s) {
     HntrArgs a{};
     a.SINA = h->SINA.p; a.FMIN = h->FMIN.p; a.FMAX = h->FMAX.p; a.GMIN = h->GMIN.p; a.GMAX = h->GMAX.p;
     a.IMIN = h->IMIN.p; a.IMAX = h->IMAX.p; a.JMIN = h->JMIN.p; a.JMAX = h->JMAX.p;
-    a.WTA = dWTA; a.wta_ld = wta_ld; a.A = dA; a.lda = lda; a.B = dB; a.ldb = ldb;
+    a.WTA = dWTA; a.wta_ld = dWTA ? wta_ld : 0; a.wconst = wta_const; a.A = dA; a.lda = lda; a.B = dB; a.ldb = ldb;
     a.imA = h->imA; a.imB = h->imB; a.jmB = h->jmB; a.nvar = nvar;
     a.wtm = wtm; a.wtb = wtb; a.datmis = h->datmis;
-    if (wta_ld != 0 || nvar == 1) hntr_launch_nv<1>(h, a, s);
-    else if (nvar == 2) hntr_launch_nv<2>(h, a, s);
-    else if (nvar <= 4) hntr_launch_nv<4>(h, a, s);
-    else hntr_launch_nv<8>(h, a, s);
+    const HntrShape sh = hntr_shape(h, nvar, dWTA == nullptr, a.wta_ld != 0);
+    if (!dWTA) hntr_launch_weight<HntrConstW>(h, sh, a, a_type, s);
+    else if (wta_type == IBH_HNTR_F64) hntr_launch_weight<double>(h, sh, a, a_type, s);
+    else if (wta_type == IBH_HNTR_F32) hntr_launch_weight<float>(h, sh, a, a_type, s);
+    else hntr_launch_weight<int16_t>(h, sh, a, a_type, s);
     if (mean_polar) {
         hipLaunchKernelGGL(hntr_mean_polar_kernel, dim3((unsigned)ceil_div(2 * (int64_t)nvar, 64)), dim3(64), 0, s,
                            dB, ldb, nvar, h->imB, h->jmB, h->datmis);
@@ -350,17 +408,24 @@ static void hntr_regrid(const ibh_hntr *h, const double *dWTA, int64_t wta_ld, c
     }
 }
 
+// const_weight: the typed entries' WTA == nullptr, where no weight plane is read and wta_ld is ignored
 static void check_regrid_args(const ibh_hntr *h, const void *WTA, int64_t wta_ld, const void *A, int32_t nvar, int64_t lda,
-                              const void *B, int64_t ldb, int mean_polar) {
+                              const void *B, int64_t ldb, int mean_polar, bool const_weight = false) {
     IBH_CHECK(h != nullptr, "null Hntr handle");
     check_current_device(h->device, "Hntr handle");
     const int64_t nA = (int64_t)h->imA * h->jmA, nB = (int64_t)h->imB * h->jmB;
-    IBH_CHECK(nvar >= 0 && (nvar == 0 || (WTA && A && B)), "Hntr regrid: bad arguments (nvar=%d or a null array)", nvar);
+    IBH_CHECK(nvar >= 0 && (nvar == 0 || ((WTA || const_weight) && A && B)), "Hntr regrid: bad arguments (nvar=%d or a null array)", nvar);
     IBH_CHECK(lda >= nA && ldb >= nB, "Hntr regrid: leading dimensions too small (lda=%lld < %lld or ldb=%lld < %lld)",
               (long long)lda, (long long)nA, (long long)ldb, (long long)nB);
-    IBH_CHECK(wta_ld == 0 || wta_ld >= nA, "Hntr regrid: wta_ld=%lld must be 0 (shared weight) or >= %lld", (long long)wta_ld,
-              (long long)nA);
+    IBH_CHECK(const_weight || wta_ld == 0 || wta_ld >= nA, "Hntr regrid: wta_ld=%lld must be 0 (shared weight) or >= %lld",
+              (long long)wta_ld, (long long)nA);
     IBH_CHECK(!mean_polar || h->jmB >= 2, "Hntr regrid: mean_polar needs jmB >= 2 (the reference loops forever on jmB=1)");
+}
+static void check_typed_args(const ibh_hntr *h, const void *WTA, int wta_type, int64_t wta_ld, const void *A, int a_type, int32_t nvar,
+                             int64_t lda, const void *B, int64_t ldb, int mean_polar) {
+    check_elem_type(a_type, "A");
+    if (WTA) check_elem_type(wta_type, "WTA");
+    check_regrid_args(h, WTA, wta_ld, A, nvar, lda, B, ldb, mean_polar, WTA == nullptr);
 }
 
 // ---- matrix forms (hntr.hpp:205-338 Hntr::matrix, OverlapMatAccum, ScaledRegridMatAccum; hntr.cpp:33-52 make_dxyp) ----
@@ -1171,7 +1236,60 @@ int ibh_hntr_regrid_device(const ibh_hntr *h, const double *dWTA, int64_t wta_ld
     return guarded([&] {
         check_regrid_args(h, dWTA, wta_ld, dA, nvar, lda, dB, ldb, mean_polar);
         if (nvar == 0) return;
-        hntr_regrid(h, dWTA, wta_ld, dA, nvar, lda, dB, ldb, mean_polar, wtm, wtb, static_cast<hipStream_t>(stream));
+        hntr_regrid(h, dWTA, IBH_HNTR_F64, wta_ld, 0., dA, IBH_HNTR_F64, nvar, lda, dB, ldb, mean_polar, wtm, wtb,
+                    static_cast<hipStream_t>(stream));
+    });
+}
+
+int ibh_hntr_regrid_typed_device(const ibh_hntr *h, const void *dWTA, int wta_type, int64_t wta_ld, double wta_const, const void *dA,
+                                 int a_type, int32_t nvar, int64_t lda, double *dB, int64_t ldb, int mean_polar, double wtm, double wtb,
+                                 void *stream) {
+    return guarded([&] {
+        check_typed_args(h, dWTA, wta_type, wta_ld, dA, a_type, nvar, lda, dB, ldb, mean_polar);
+        if (nvar == 0) return;
+        hntr_regrid(h, dWTA, wta_type, wta_ld, wta_const, dA, a_type, nvar, lda, dB, ldb, mean_polar, wtm, wtb,
+                    static_cast<hipStream_t>(stream));
+    });
+}
+
+int ibh_hntr_regrid_shape(const ibh_hntr *h, int32_t nvar, int wta_is_const, int wta_type, int64_t wta_ld, int a_type, int32_t *NV,
+                          int32_t *L, int32_t *K, int64_t *lds_bytes) {
+    return guarded([&] {
+        IBH_CHECK(h != nullptr, "null Hntr handle");
+        check_elem_type(a_type, "A");
+        if (!wta_is_const) check_elem_type(wta_type, "WTA");
+        IBH_CHECK(nvar >= 1, "Hntr regrid shape: nvar=%d (must be >= 1)", nvar);
+        IBH_CHECK(NV && L && K && lds_bytes, "Hntr regrid shape: null output");
+        const HntrShape sh = hntr_shape(h, nvar, wta_is_const != 0, !wta_is_const && wta_ld != 0);
+        *NV = sh.NV; *L = sh.L; *K = sh.K; *lds_bytes = (int64_t)sh.lds_bytes;
+    });
+}
+
+// The host forms, after their checks: every plane is copied in its own width and packed on the device, regridded there, and B
+// copied back.  WTA == nullptr: the constant weight.
+static void hntr_regrid_from_host(const ibh_hntr *h, const void *WTA, int wta_type, int64_t wta_ld, double wta_const, const void *A,
+                                  int a_type, int32_t nvar, int64_t lda, double *B, int64_t ldb, int mean_polar, double wtm, double wtb) {
+    if (nvar == 0) return;
+    const size_t nA = (size_t)h->imA * h->jmA, nB = (size_t)h->imB * h->jmB;
+    const size_t sS = hntr_elem_size(a_type), sW = WTA ? hntr_elem_size(wta_type) : 0;
+    const size_t nw = !WTA ? 0 : wta_ld ? (size_t)nvar : 1;
+    DevBuf<uint8_t> dW(sW * nw * nA), dA(sS * (size_t)nvar * nA);
+    DevBuf<double> dB((size_t)nvar * nB);
+    if (WTA)
+        IBH_HIP(hipMemcpy2DAsync(dW.p, sW * nA, WTA, sW * (size_t)(wta_ld ? wta_ld : (int64_t)nA), sW * nA, nw, hipMemcpyHostToDevice, nullptr));
+    IBH_HIP(hipMemcpy2DAsync(dA.p, sS * nA, A, sS * (size_t)lda, sS * nA, (size_t)nvar, hipMemcpyHostToDevice, nullptr));
+    hntr_regrid(h, WTA ? dW.p : nullptr, wta_type, wta_ld ? (int64_t)nA : 0, wta_const, dA.p, a_type, nvar, (int64_t)nA, dB.p, (int64_t)nB,
+                mean_polar, wtm, wtb, nullptr);
+    IBH_HIP(hipMemcpy2DAsync(B, sizeof(double) * (size_t)ldb, dB.p, sizeof(double) * nB, sizeof(double) * nB, (size_t)nvar,
+                             hipMemcpyDeviceToHost, nullptr));
+    IBH_HIP(hipStreamSynchronize(nullptr));
+}
+
+int ibh_hntr_regrid_typed_host(const ibh_hntr *h, const void *WTA, int wta_type, int64_t wta_ld, double wta_const, const void *A,
+                               int a_type, int32_t nvar, int64_t lda, double *B, int64_t ldb, int mean_polar, double wtm, double wtb) {
+    return guarded([&] {
+        check_typed_args(h, WTA, wta_type, wta_ld, A, a_type, nvar, lda, B, ldb, mean_polar);
+        hntr_regrid_from_host(h, WTA, wta_type, WTA ? wta_ld : 0, wta_const, A, a_type, nvar, lda, B, ldb, mean_polar, wtm, wtb);
     });
 }
 
@@ -1179,18 +1297,7 @@ int ibh_hntr_regrid_host(const ibh_hntr *h, const double *WTA, int64_t wta_ld, c
                          double *B, int64_t ldb, int mean_polar, double wtm, double wtb) {
     return guarded([&] {
         check_regrid_args(h, WTA, wta_ld, A, nvar, lda, B, ldb, mean_polar);
-        if (nvar == 0) return;
-        const size_t nA = (size_t)h->imA * h->jmA, nB = (size_t)h->imB * h->jmB;
-        const size_t nw = wta_ld ? (size_t)nvar : 1;
-        DevBuf<double> dW(nw * nA), dA((size_t)nvar * nA), dB((size_t)nvar * nB);
-        IBH_HIP(hipMemcpy2DAsync(dW.p, sizeof(double) * nA, WTA, sizeof(double) * (size_t)(wta_ld ? wta_ld : (int64_t)nA),
-                                 sizeof(double) * nA, nw, hipMemcpyHostToDevice, nullptr));
-        IBH_HIP(hipMemcpy2DAsync(dA.p, sizeof(double) * nA, A, sizeof(double) * (size_t)lda, sizeof(double) * nA, (size_t)nvar,
-                                 hipMemcpyHostToDevice, nullptr));
-        hntr_regrid(h, dW.p, wta_ld ? (int64_t)nA : 0, dA.p, nvar, (int64_t)nA, dB.p, (int64_t)nB, mean_polar, wtm, wtb, nullptr);
-        IBH_HIP(hipMemcpy2DAsync(B, sizeof(double) * (size_t)ldb, dB.p, sizeof(double) * nB, sizeof(double) * nB, (size_t)nvar,
-                                 hipMemcpyDeviceToHost, nullptr));
-        IBH_HIP(hipStreamSynchronize(nullptr));
+        hntr_regrid_from_host(h, WTA, IBH_HNTR_F64, wta_ld, 0., A, IBH_HNTR_F64, nvar, lda, B, ldb, mean_polar, wtm, wtb);
     });
 }
 

@@ -297,6 +297,8 @@ int64_t merge_topoO(const ibh_regrid_matrices *const *lands, const ibh_regrid_ma
 enum { A_focean, A_flake, A_fgrnd, A_fgice, A_zatmo, A_zlake, A_zicetop, A_zland_min, A_zland_max, NP_A };
 struct PlanesA { double *p[NP_A]; int16_t *mergemask; };
 
+// Fills a plane with one value.  make_topoA no longer launches it (its weight-1 regrids take Hntr's constant weight); it stays
+// because tests/test_topo_kernels.py holds the kernel inventory of this unit.
 __global__ void k_topo_fill(double *__restrict__ p, long n, double v) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) p[i] = v;
@@ -485,7 +487,7 @@ int64_t make_topoA(const TopoAArgs &t, const double *const *O, const int16_t *me
     while (nhc_local < nhc && t.underice_hc[nhc_local] == UI_LOCALICE) ++nhc_local;
 
     DevBuf<int32_t> dwin;
-    DevBuf<double> ones((size_t)nO), dhc;
+    DevBuf<double> dhc;
     DevBuf<int16_t> dui;
     DevBuf<unsigned long long> stat(2);                     // [0] failing checks, [1] (its low word) the smallest bad entry
     unsigned long long *nerr = stat.p;
@@ -495,11 +497,10 @@ int64_t make_topoA(const TopoAArgs &t, const double *const *O, const int16_t *me
     dui.upload(t.underice_hc, (size_t)nhc, st);
     IBH_HIP(hipMemsetAsync(nerr, 0, sizeof(unsigned long long), st));
     IBH_HIP(hipMemsetAsync(status, 0xFF, sizeof(unsigned long long), st));
-    hipLaunchKernelGGL(k_topo_fill, dim3((unsigned)ceil_div(nO, T)), dim3(T), 0, st, ones.p, nO, 1.0);
-    IBH_HIP(hipGetLastError());
-    // (:623-630): six regrids under the weight 1, zicetop under fgiceOm
+    // (:623-630): six regrids under the constant weight 1 (const_array(shape, 1.0)), zicetop under fgiceOm
     for (int k = 0; k <= A_zicetop; ++k)
-        rethrow(ibh_hntr_regrid_device(hntr.get(), k == A_zicetop ? O[A_fgice] : ones.p, 0, O[k], 1, nO, P.p[k], nA, 0, 1., 0., st));
+        rethrow(ibh_hntr_regrid_typed_device(hntr.get(), k == A_zicetop ? O[A_fgice] : nullptr, IBH_HNTR_F64, 0, 1., O[k], IBH_HNTR_F64, 1,
+                                             nO, P.p[k], nA, 0, 1., 0., st));
     Windows w{dwin.p, dwin.p + t.imA, dwin.p + 2 * t.imA, dwin.p + 2 * t.imA + t.jmA, t.imO, t.jmO, t.imA, t.jmA};
     hipLaunchKernelGGL(k_topoa_window, dim3((unsigned)ceil_div(nA, T)), dim3(T), 0, st, w, O[A_zland_min], O[A_zland_max], mergemaskO,
                        P.p[A_zland_min], P.p[A_zland_max], P.mergemask);

@@ -54,6 +54,28 @@ def make_dxyp(spec):
     return out
 
 
+# element codes of the typed regrid (IBH_HNTR_F64 / _I16 / _F32); 0 and 1 are ibh_multivec_append_planes_*'s plane types
+F64, I16, F32 = 0, 1, 2
+_CODES = {"float64": F64, "int16": I16, "float32": F32}
+
+
+def _code(dtype):
+    """The element code of a numpy or torch dtype; KeyError for any other (a numpy dtype that is not in native byte order
+    included: the library reads the memory as it is)."""
+    name = str(dtype).replace("torch.", "")
+    if name not in _CODES:
+        try:
+            d = np.dtype(dtype)
+        except TypeError:       # a torch dtype without a numpy counterpart
+            raise KeyError(name) from None
+        name = d.name if d.isnative else str(d)
+    return _CODES[name]
+
+
+def _is_scalar(x):
+    return isinstance(x, (int, float, np.integer, np.floating)) or (isinstance(x, np.ndarray) and x.ndim == 0)
+
+
 def _kind(kind):
     k = {"overlap": OVERLAP, "scaled": SCALED}.get(kind, kind)
     return int(k)
@@ -78,7 +100,11 @@ class Hntr:
         self._h = None
 
     def _planes(self, X, what):
-        X = np.asarray(X, np.float64)
+        X = np.asarray(X)
+        # int16, float32 and float64 planes in native byte order travel as they are; anything else (a byte-swapped array from
+        # a netCDF-3 or Fortran file included) becomes native float64, as np.asarray(X, np.float64) always did
+        if not (X.dtype.isnative and X.dtype.name in _CODES):
+            X = X.astype(np.float64)
         nA = self.Agrid.size
         if X.ndim == 1 or (X.ndim == 2 and X.shape == (self.Agrid.jm, self.Agrid.im)):
             if X.size != nA:
@@ -92,17 +118,25 @@ class Hntr:
     def regrid(self, WTA, A, mean_polar=False, wtm=1., wtb=0.):
         """Hntr::regrid(WTA, A, B, mean_polar, wtm, wtb) (hntr.hpp:341-435): returns B.  A is one field ((size,) or
         (jm, im)) or several ((nvar, size) or (nvar, jm, im)); WTA is one weight plane for all of them or one per
-        field.  One field comes back shaped like A on grid B, several as (nvar, Bgrid.size)."""
+        field, or a scalar: the constant weight (the reference's const_array(shape, c)).  int16, float32 and float64 arrays
+        are copied to the device in their own dtype (regrid<WeightT, SrcT, double>, hntr.hpp:385-391) and may differ between
+        WTA and A; any other dtype is converted to float64 first.  One field comes back shaped like A on grid B, several as
+        (nvar, Bgrid.size); B is float64."""
         A2, single = self._planes(A, "A")
-        W2, _ = self._planes(WTA, "WTA")
         nvar = A2.shape[0]
-        if W2.shape[0] not in (1, nvar):
-            raise ValueError("WTA has %d planes for %d fields" % (W2.shape[0], nvar))
+        const = _is_scalar(WTA)
+        if const:
+            W2, wcode, wta_ld, wconst = None, F64, 0, float(WTA)
+        else:
+            W2, _ = self._planes(WTA, "WTA")
+            if W2.shape[0] not in (1, nvar):
+                raise ValueError("WTA has %d planes for %d fields" % (W2.shape[0], nvar))
+            wcode, wta_ld, wconst = _code(W2.dtype), 0 if W2.shape[0] == 1 else W2.shape[1], 0.
         nB = self.Bgrid.size
         B = np.empty((nvar, nB))
         if nvar:
-            check(lib().ibh_hntr_regrid_host(self._h, ptr(W2), 0 if W2.shape[0] == 1 else W2.shape[1], ptr(A2), nvar, A2.shape[1],
-                                             ptr(B), nB, int(bool(mean_polar)), float(wtm), float(wtb)))
+            check(lib().ibh_hntr_regrid_typed_host(self._h, None if const else ptr(W2), wcode, wta_ld, wconst, ptr(A2), _code(A2.dtype),
+                                                   nvar, A2.shape[1], ptr(B), nB, int(bool(mean_polar)), float(wtm), float(wtb)))
         if single:
             return B[0].reshape(self.Bgrid.jm, self.Bgrid.im) if np.ndim(A) == 2 else B[0]
         return B
@@ -150,25 +184,41 @@ class Hntr:
         return linear_Weighted(h, keep=(self, dims))
 
     def regrid_device(self, WTA, A, out=None, mean_polar=False, wtm=1., wtb=0., stream=None):
-        """The same on fields resident in HBM: torch.float64 CUDA tensors, A [nvar, Agrid.size] (row stride >= size),
-        WTA [Agrid.size] or [1, size] (shared) or [nvar, size]; only enqueues work on `stream` (default: torch's
-        current stream).  Returns out [nvar, Bgrid.size]."""
+        """The same on fields resident in HBM: torch.float64, float32 or int16 CUDA tensors (A and WTA may differ), A [nvar,
+        Agrid.size] (row stride >= size), WTA [Agrid.size] or [1, size] (shared) or [nvar, size], or a scalar: the constant
+        weight; only enqueues work on `stream` (default: torch's current stream).  Returns out [nvar, Bgrid.size], float64."""
         import torch
         nA, nB = self.Agrid.size, self.Bgrid.size
-        assert A.is_cuda and A.dtype == torch.float64 and A.dim() == 2 and A.stride(1) == 1 and A.shape[1] == nA
+        types = (torch.float64, torch.float32, torch.int16)
+        assert A.is_cuda and A.dtype in types and A.dim() == 2 and A.stride(1) == 1 and A.shape[1] == nA
         nvar = A.shape[0]
-        W = WTA if WTA.dim() == 2 else WTA.reshape(1, -1)
-        assert W.is_cuda and W.dtype == torch.float64 and W.dim() == 2 and W.stride(1) == 1 and W.shape[1] == nA
-        assert W.shape[0] in (1, nvar)
+        const = _is_scalar(WTA)
+        if not const:
+            W = WTA if WTA.dim() == 2 else WTA.reshape(1, -1)
+            assert W.is_cuda and W.dtype in types and W.dim() == 2 and W.stride(1) == 1 and W.shape[1] == nA
+            assert W.shape[0] in (1, nvar)
         if out is None:
             out = torch.empty((nvar, (nB + 63) // 64 * 64), dtype=torch.float64, device=A.device)[:, :nB]
         assert out.is_cuda and out.dtype == torch.float64 and out.dim() == 2 and out.shape == (nvar, nB) and out.stride(1) == 1
-        wta_ld, lda, ldb = device_strides(nvar, nA, nB, W.shape[0], W.stride(0), A.stride(0), out.stride(0))
+        wta_ld, lda, ldb = device_strides(nvar, nA, nB, 1 if const else W.shape[0], 0 if const else W.stride(0), A.stride(0),
+                                          out.stride(0))
         s = torch.cuda.current_stream(A.device).cuda_stream if stream is None else stream
-        check(lib().ibh_hntr_regrid_device(self._h, C.c_void_p(W.data_ptr()), wta_ld, C.c_void_p(A.data_ptr()), nvar, lda,
-                                           C.c_void_p(out.data_ptr()), ldb, int(bool(mean_polar)), float(wtm), float(wtb),
-                                           C.c_void_p(s)))
+        check(lib().ibh_hntr_regrid_typed_device(self._h, None if const else C.c_void_p(W.data_ptr()), F64 if const else _code(W.dtype),
+                                                 wta_ld, float(WTA) if const else 0., C.c_void_p(A.data_ptr()), _code(A.dtype), nvar,
+                                                 lda, C.c_void_p(out.data_ptr()), ldb, int(bool(mean_polar)), float(wtm), float(wtb),
+                                                 C.c_void_p(s)))
         return out
+
+    def regrid_shape(self, nvar, WTA_dtype, A_dtype, per_field=False):
+        """What regrid of nvar fields would launch (ibh_hntr_regrid_shape; launches nothing): dict(NV, L, K, lds_bytes) = fields
+        per group, chain lanes per wave, columns per chunk, LDS bytes per workgroup.  WTA_dtype None: the constant weight;
+        per_field: one weight plane per field."""
+        NV, L, K, lds = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64()
+        const = WTA_dtype is None
+        check(lib().ibh_hntr_regrid_shape(self._h, int(nvar), int(const), F64 if const else _code(WTA_dtype),
+                                          1 if per_field and not const else 0, _code(A_dtype), C.byref(NV), C.byref(L), C.byref(K),
+                                          C.byref(lds)))
+        return dict(NV=NV.value, L=L.value, K=K.value, lds_bytes=lds.value)
 
 
 def device_strides(nvar, nA, nB, wta_planes, wta_stride, a_stride, out_stride):

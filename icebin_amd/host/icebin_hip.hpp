@@ -998,10 +998,27 @@ enum class DenseTransform { ADD_DENSE = IBH_ADD_DENSE, TO_DENSE = IBH_TO_DENSE, 
 /** Which accumulator of Hntr::matrix: OverlapMatAccum (overlap) or ScaledRegridMatAccum (scaled_regrid_matrix). */
 enum class HntrMatrix { OVERLAP = IBH_HNTR_OVERLAP, SCALED = IBH_HNTR_SCALED };
 
+/** The element types of the typed regrid and their IBH_HNTR_* codes; any other type has no code and does not compile. */
+template <class T> struct HntrElem;
+template <> struct HntrElem<double> { static constexpr int code = IBH_HNTR_F64; };
+template <> struct HntrElem<float> { static constexpr int code = IBH_HNTR_F32; };
+template <> struct HntrElem<int16_t> { static constexpr int code = IBH_HNTR_I16; };
+/** A constant weight in place of WTA: the reference's const_array(shape, c), a stride-0 array that holds one number. */
+struct ConstWeight {
+    double c;
+};
+
 /** Hntr (hntr.hpp:63-135): the partition is computed and uploaded to the current HIP device by the constructor; regrid
     runs on that device.  Owns a device handle: movable, not copyable. */
 class Hntr {
     ibh_hntr *h_;
+    /** The reference's dimension check (hntr.hpp:361-369). */
+    void check_dims(long nW, long nA, long nB) const {
+        if (nW != Agrid.spec.size() || nA != Agrid.spec.size() || nB != Bgrid.spec.size())
+            throw Exception(IBH_EINVAL, "Error in dimensions: (" + std::to_string(nW) + ", " + std::to_string(nA) + ", " +
+                                        std::to_string(nB) + ") vs. (" + std::to_string(Agrid.spec.size()) + ", " +
+                                        std::to_string(Bgrid.spec.size()) + ")");
+    }
 public:
     HntrGrid const Agrid;
     HntrGrid const Bgrid;
@@ -1021,10 +1038,7 @@ public:
         dimension check (:361-369) included. */
     void regrid(ArrayView<const double> const &WTA, ArrayView<const double> const &A, ArrayView<double> const &B,
                 bool mean_polar = false, double wtm = 1.0, double wtb = 0.0) const {
-        if (WTA.size() != Agrid.spec.size() || A.size() != Agrid.spec.size() || B.size() != Bgrid.spec.size())
-            throw Exception(IBH_EINVAL, "Error in dimensions: (" + std::to_string(WTA.size()) + ", " + std::to_string(A.size()) + ", " +
-                                        std::to_string(B.size()) + ") vs. (" + std::to_string(Agrid.spec.size()) + ", " +
-                                        std::to_string(Bgrid.spec.size()) + ")");
+        check_dims(WTA.size(), A.size(), B.size());
         check(ibh_hntr_regrid_host(h_, WTA.data, 0, A.data, 1, Agrid.spec.size(), B.data, Bgrid.spec.size(), mean_polar ? 1 : 0, wtm, wtb));
     }
     /** regrid(WTA, A, mean_polar) (hntr.hpp:214-218): allocates and returns B. */
@@ -1032,6 +1046,39 @@ public:
         std::vector<double> B((size_t)Bgrid.spec.size());
         regrid(WTA, A, ArrayView<double>(B.data(), (long)B.size()), mean_polar);
         return B;
+    }
+    /** regrid<WeightT, SrcT>(WTA, A, B, mean_polar, wtm, wtb): the reference's template (hntr.hpp:385-391) with DestT = double,
+        for WeightT and SrcT in double, float, int16_t (e.g. regrid<double, int16_t, double> from the 1' ETOPO1 planes,
+        etopo1_ice.cpp:22-26).  The planes are copied to the device in their own width; bitwise the double overload on the
+        widened arrays.  Any other element type does not compile. */
+    template <class WeightT, class SrcT>
+    void regrid(ArrayView<const WeightT> const &WTA, ArrayView<const SrcT> const &A, ArrayView<double> const &B,
+                bool mean_polar = false, double wtm = 1.0, double wtb = 0.0) const {
+        check_dims(WTA.size(), A.size(), B.size());
+        check(ibh_hntr_regrid_typed_host(h_, WTA.data, HntrElem<WeightT>::code, 0, 0.0, A.data, HntrElem<SrcT>::code, 1, Agrid.spec.size(),
+                                         B.data, Bgrid.spec.size(), mean_polar ? 1 : 0, wtm, wtb));
+    }
+    /** The same under a constant weight, the reference's const_array(shape, c) as WTA: regrid(ConstWeight{1.0}, A, B, ...). */
+    template <class SrcT>
+    void regrid(ConstWeight const &WTA, ArrayView<const SrcT> const &A, ArrayView<double> const &B, bool mean_polar = false,
+                double wtm = 1.0, double wtb = 0.0) const {
+        check_dims(Agrid.spec.size(), A.size(), B.size());
+        check(ibh_hntr_regrid_typed_host(h_, nullptr, IBH_HNTR_F64, 0, WTA.c, A.data, HntrElem<SrcT>::code, 1, Agrid.spec.size(), B.data,
+                                         Bgrid.spec.size(), mean_polar ? 1 : 0, wtm, wtb));
+    }
+    /** Device overloads with typed pointers: as the double one below; wta_ld and lda count elements of the plane's own type.
+        A pure enqueue on `stream` (ibh_hntr_regrid_typed_device). */
+    template <class WeightT, class SrcT>
+    void regrid(const WeightT *dWTA, long wta_ld, const SrcT *dA, int nvar, long lda, double *dB, long ldb, bool mean_polar = false,
+                double wtm = 1.0, double wtb = 0.0, void *stream = nullptr) const {
+        check(ibh_hntr_regrid_typed_device(h_, dWTA, HntrElem<WeightT>::code, wta_ld, 0.0, dA, HntrElem<SrcT>::code, nvar, lda, dB, ldb,
+                                           mean_polar ? 1 : 0, wtm, wtb, stream));
+    }
+    template <class SrcT>
+    void regrid(ConstWeight const &WTA, const SrcT *dA, int nvar, long lda, double *dB, long ldb, bool mean_polar = false,
+                double wtm = 1.0, double wtb = 0.0, void *stream = nullptr) const {
+        check(ibh_hntr_regrid_typed_device(h_, nullptr, IBH_HNTR_F64, 0, WTA.c, dA, HntrElem<SrcT>::code, nvar, lda, dB, ldb,
+                                           mean_polar ? 1 : 0, wtm, wtb, stream));
     }
     /** Device overload: nvar fields resident in HBM, B[k*ldb + IJB] from A[k*lda + IJA]; the weight is one plane for all
         fields (wta_ld = 0) or one per field.  A pure enqueue on `stream` (ibh_hntr_regrid_device). */

@@ -156,6 +156,31 @@ int ibh_hntr_regrid_device(const ibh_hntr *h, const double *dWTA, int64_t wta_ld
                            double *dB, int64_t ldb, int mean_polar, double wtm, double wtb, void *stream);
 int ibh_hntr_regrid_host(const ibh_hntr *h, const double *WTA, int64_t wta_ld, const double *A, int32_t nvar, int64_t lda,
                          double *B, int64_t ldb, int mean_polar, double wtm, double wtb);
+/* The same with typed planes and a constant weight, the instantiations of the reference's template
+ * regrid<WeightT, SrcT, DestT> (hntr.hpp:385-391) that its callers use: regrid<double, int16_t, double> from the 1' ETOPO1
+ * planes (etopo1_ice.cpp:22-26, topo_base.cpp:390-399, :646-663) and const_array(shape, c) as the weight.  Element codes;
+ * 0 and 1 are the plane_type codes of ibh_multivec_append_planes_*: */
+#define IBH_HNTR_F64 0      /* double */
+#define IBH_HNTR_I16 1      /* int16_t */
+#define IBH_HNTR_F32 2      /* float */
+/* WTA holds elements of wta_type and A of a_type (all fields of a call share one type); wta_ld and lda count elements of the
+ * plane's own type, so a plane base is aligned to its element only.  WTA == NULL selects the constant weight wta_const, a
+ * plane that holds one number: wta_type and wta_ld are then ignored and no weight plane is read.  Every element becomes a
+ * double (exactly) before it enters the chain wta = wtm*WTA + wtb; wt = FG*wta; WEIGHT += wt; VALUE += wt*A, so the result is
+ * bitwise that of ibh_hntr_regrid_* on the widened planes, or on a plane filled with wta_const.  B stays double.  The checks of
+ * ibh_hntr_regrid_* hold; a type code other than the three above is IBH_EINVAL and the message names it.
+ * _device: a pure enqueue on `stream`.  _host: copies every plane over PCIe in its own width (never widened on the host),
+ * synchronous. */
+int ibh_hntr_regrid_typed_device(const ibh_hntr *h, const void *dWTA, int wta_type, int64_t wta_ld, double wta_const, const void *dA,
+                                 int a_type, int32_t nvar, int64_t lda, double *dB, int64_t ldb, int mean_polar, double wtm, double wtb,
+                                 void *stream);
+int ibh_hntr_regrid_typed_host(const ibh_hntr *h, const void *WTA, int wta_type, int64_t wta_ld, double wta_const, const void *A,
+                               int a_type, int32_t nvar, int64_t lda, double *B, int64_t ldb, int mean_polar, double wtm, double wtb);
+/* What a regrid of nvar fields would launch, without launching anything: NV = fields per group (1 with per-field weights,
+ * wta_ld != 0), L = chain lanes per wave, K = columns per chunk, lds_bytes = dynamic LDS of a workgroup.  wta_is_const != 0:
+ * the constant weight (wta_type and wta_ld ignored).  nvar >= 1. */
+int ibh_hntr_regrid_shape(const ibh_hntr *h, int32_t nvar, int wta_is_const, int wta_type, int64_t wta_ld, int a_type, int32_t *NV,
+                          int32_t *L, int32_t *K, int64_t *lds_bytes);
 /* The partition alone, host only (no device needed): SINA[jmA+1], SINB[jmB+1]; IMIN, IMAX, FMIN, FMAX [imB]
  * (IMAX(imB) already += imA, as hntr.cpp:116 leaves it); JMIN, JMAX, GMIN, GMAX [jmB].  Indices are the reference's,
  * 1-based; entry i of a per-column or per-row array belongs to IB or JB = i+1. */

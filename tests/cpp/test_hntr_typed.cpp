@@ -1,0 +1,124 @@
+// C++ test of the typed regrid of icebin::modele::Hntr in icebin_amd/host/icebin_hip.hpp: the reference's template
+// regrid<WeightT, SrcT, DestT> (hntr.hpp:385-391) the way its TOPO tools call it.  store_h (etopo1_ice.cpp:17-29) regrids an int16
+// plane under const_array(shape, 1.0) with mean_polar = true; topo_base.cpp:646-663 regrids an int16 plane under an int16 weight.
+// An int16 converts to double exactly, so both must be bitwise the double overloads on the widened arrays, which
+// tests/cpp/test_hntr.cpp holds against the reference's loop.
+// Exit code 0 = pass, 3 = no GPU (the no-fallback error path was verified instead).
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../icebin_amd/host/icebin_hip.hpp"
+
+using namespace icebin;
+using icebin::modele::ConstWeight;
+using icebin::modele::Hntr;
+using icebin::modele::HntrSpec;
+
+#define REQUIRE(cond)                                                        \
+    do {                                                                     \
+        if (!(cond)) { std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); return 1; } \
+    } while (0)
+
+static bool same_bits(std::vector<double> const &a, std::vector<double> const &b) {
+    return a.size() == b.size() && std::memcmp(a.data(), b.data(), a.size() * sizeof(double)) == 0;
+}
+
+template <class T>
+static std::vector<double> widened(std::vector<T> const &v) {
+    return std::vector<double>(v.begin(), v.end());
+}
+
+int main() {
+    // a 1-degree plane onto ModelE's 72 x 46 grid with half-height polar cells: ("72x46", "360x180")
+    const HntrSpec gA(360, 180, 0., 60.), gB(72, 46, 0., 240.);
+    const double DATMIS = -1e30;
+    const size_t nA = (size_t)gA.size(), nB = (size_t)gB.size();
+    std::vector<int16_t> val((size_t)nA), focean((size_t)nA);
+    std::vector<float> valf((size_t)nA);
+    uint32_t lcg = 12345u;
+    for (int j = 0; j < gA.jm; ++j)
+        for (int i = 0; i < gA.im; ++i) {
+            const size_t ij = (size_t)i + (size_t)gA.im * j;
+            lcg = lcg * 1664525u + 1013904223u;
+            val[ij] = (int16_t)((int)((lcg >> 8) % 19851u) - 11000);       // elevations in [-11000, 8850]
+            valf[ij] = (float)val[ij] * 0.37f;
+            focean[ij] = (i >= 100 && i < 140 && j >= 20 && j < 160) || j == 0 ? 0 : (int16_t)((lcg >> 4) % 3u);
+        }
+    const std::vector<double> vald = widened(val), valfd = widened(valf), foceand = widened(focean), ones(nA, 1.0);
+    try {
+        Hntr hntr(17.17, gB, gA, DATMIS);
+        std::vector<double> B(nB, 0.0), Bd(nB, 0.0);
+        const ArrayView<double> vB(B.data(), (long)nB), vBd(Bd.data(), (long)nB);
+        // store_h: hntr.regrid<double, int16_t, double>(const_array(shape, 1.0), val1m, valh, true)
+        hntr.regrid(ConstWeight{1.0}, ArrayView<const int16_t>(val), vB, true);
+        hntr.regrid(ArrayView<const double>(ones), ArrayView<const double>(vald), vBd, true);
+        REQUIRE(same_bits(B, Bd));
+        REQUIRE(B[0] == B[gB.im - 1] && B[nB - 1] == B[nB - gB.im] && B[0] != DATMIS);     // the polar rows hold their means
+        // a double weight plane over an int16 source, as the template's name says
+        hntr.regrid(ArrayView<const double>(foceand), ArrayView<const int16_t>(val), vB, false);
+        hntr.regrid(ArrayView<const double>(foceand), ArrayView<const double>(vald), vBd, false);
+        REQUIRE(same_bits(B, Bd));
+        // regrid(FOCEAN1m, ZSOLG1m, ...): int16 weight and int16 source; and 1 - FOCEAN (wtm = -1, wtb = 1)
+        hntr.regrid(ArrayView<const int16_t>(focean), ArrayView<const int16_t>(val), vB, false);
+        REQUIRE(same_bits(B, Bd));
+        int ndatmis = 0;
+        for (double b : B) ndatmis += b == DATMIS;
+        REQUIRE(ndatmis > 0 && ndatmis < (int)nB);
+        hntr.regrid(ArrayView<const int16_t>(focean), ArrayView<const int16_t>(val), vB, true, -1.0, 1.0);
+        hntr.regrid(ArrayView<const double>(foceand), ArrayView<const double>(vald), vBd, true, -1.0, 1.0);
+        REQUIRE(same_bits(B, Bd));
+        // float planes
+        hntr.regrid(ArrayView<const int16_t>(focean), ArrayView<const float>(valf), vB, false);
+        hntr.regrid(ArrayView<const double>(foceand), ArrayView<const double>(valfd), vBd, false);
+        REQUIRE(same_bits(B, Bd));
+        hntr.regrid(ConstWeight{0.37}, ArrayView<const float>(valf), vB, false, -1.0, 1.0);
+        hntr.regrid(ArrayView<const double>(std::vector<double>(nA, 0.37)), ArrayView<const double>(valfd), vBd, false, -1.0, 1.0);
+        REQUIRE(same_bits(B, Bd));
+        // the reference's dimension check holds for the typed forms
+        bool threw = false;
+        try {
+            hntr.regrid(ConstWeight{1.0}, ArrayView<const int16_t>(val.data(), 10), vB);
+        } catch (Exception const &e) {
+            threw = e.code == IBH_EINVAL && std::string(e.what()).find("Error in dimensions") != std::string::npos;
+        }
+        REQUIRE(threw);
+        threw = false;
+        try {
+            hntr.regrid(ArrayView<const int16_t>(focean.data(), 10), ArrayView<const int16_t>(val), vB);
+        } catch (Exception const &e) {
+            threw = e.code == IBH_EINVAL && std::string(e.what()).find("Error in dimensions") != std::string::npos;
+        }
+        REQUIRE(threw);
+        // The device overloads with typed pointers.  This program allocates nothing on the device, so they run with nvar = 0, which
+        // checks every argument and launches nothing; each leading dimension is then refused where it stands in the argument list.
+        const int16_t *d16 = nullptr;
+        const float *d32 = nullptr;
+        double *dB = nullptr;
+        const long lA = (long)nA, lB = (long)nB;
+        hntr.regrid(d16, 0L, d16, 0, lA, dB, lB);
+        hntr.regrid(d32, lA, d16, 0, lA, dB, lB, true, -1.0, 1.0, nullptr);
+        hntr.regrid(ConstWeight{1.0}, d16, 0, lA, dB, lB);
+        hntr.regrid(ConstWeight{0.37}, d32, 0, lA, dB, lB, true, -1.0, 1.0, nullptr);
+        int refused = 0;
+        // (a null weight pointer selects the constant weight, which ignores wta_ld: this one takes a non-null pointer, never read)
+        try { hntr.regrid(focean.data(), 5L, d16, 0, lA, dB, lB); } catch (Exception const &e) { refused += e.code == IBH_EINVAL && std::string(e.what()).find("wta_ld=5") != std::string::npos; }
+        try { hntr.regrid(d16, 0L, d32, 0, lA - 1, dB, lB); } catch (Exception const &e) { refused += e.code == IBH_EINVAL && std::string(e.what()).find("lda=") != std::string::npos; }
+        try { hntr.regrid(d16, 0L, d32, 0, lA, dB, lB - 1); } catch (Exception const &e) { refused += e.code == IBH_EINVAL && std::string(e.what()).find("ldb=") != std::string::npos; }
+        try { hntr.regrid(ConstWeight{1.0}, d16, 0, lA - 1, dB, lB); } catch (Exception const &e) { refused += e.code == IBH_EINVAL; }
+        try { hntr.regrid(ConstWeight{1.0}, d16, 0, lA, dB, lB - 1); } catch (Exception const &e) { refused += e.code == IBH_EINVAL; }
+        try { hntr.regrid(ConstWeight{1.0}, d16, -1, lA, dB, lB); } catch (Exception const &e) { refused += e.code == IBH_EINVAL && std::string(e.what()).find("nvar=-1") != std::string::npos; }
+        REQUIRE(refused == 6);
+    } catch (Exception const &e) {
+        if (e.code == IBH_ENODEVICE) {
+            std::printf("%s\n", e.what());
+            return 3;
+        }
+        std::printf("FAILED: %s\n", e.what());
+        return 1;
+    }
+    std::printf("all checks passed\n");
+    return 0;
+}
