@@ -6,6 +6,14 @@
 #include "prims.h"
 
 namespace ibh {
+// The forms one triplets -> CSR build took (build_csr_from_contributions), as ibh_selftest_triplets reports them; introspection only
+enum { ORDER_IN_ORDER = 0, ORDER_PIECES = 1, ORDER_RADIX = 2 };     // the contributions were in order / pieces sorted in LDS / radix
+enum { SRB_NOT_TRIED = 0, SRB_TAKEN = 1, SRB_DECLINED = 2 };        // per-row slots (a row over SRB_MAX declines, then the sort)
+enum { OPT_NOT_TRIED = 0, OPT_HELD = 1, OPT_FAILED = 2 };           // the optimistic row-only sort and its check
+enum { SEG_NONE = 0, SEG_THREAD = 1, SEG_WAVE = 2 };                // seg_sums: no launch / a thread / a wave per segment
+enum { PTR_NONE = 0, PTR_SEARCH = 1, PTR_HEADS_FILL = 2 };          // rowptr_from_rows: every row searches / heads + fill
+struct CsrBuildTrace { int order = ORDER_IN_ORDER, short_rows = SRB_NOT_TRIED, optimistic = OPT_NOT_TRIED, seg_form = SEG_NONE,
+                       rowptr_form = PTR_NONE; };
 // RegridMatrices_Dynamic::matrix_d (RegridMatrices_Dynamic.cpp:412-423) on device.
 // comm: the sharded build (streamasm.inl) -- every rank of the communicator makes this call with the same arguments and gets the
 // whole matrix; the ranks share the work when the build is one the streamed path serves, and build redundantly otherwise

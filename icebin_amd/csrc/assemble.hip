@@ -508,14 +508,16 @@ __global__ void k_rowptr_search(const int32_t *__restrict__ row, long nnz, int n
     }
     rowptr[q] = (int32_t)lo;
 }
-static void rowptr_from_rows(const int32_t *row, long nnz, int nrow, int32_t *rowptr, hipStream_t st) {
+// returns the form taken (CsrBuildTrace: PTR_*)
+static int rowptr_from_rows(const int32_t *row, long nnz, int nrow, int32_t *rowptr, hipStream_t st) {
     if (nrow < (1 << 16)) {                      // few rows: one launch, every row searches (the small builds are launch-bound)
         hipLaunchKernelGGL(k_rowptr_search, dim3(ceil_div(nrow + 1, 256)), dim3(256), 0, st, row, nnz, nrow, rowptr);
-        return;
+        return PTR_SEARCH;
     }
     IBH_HIP(hipMemsetAsync(rowptr, 0xFF, sizeof(int32_t) * ((size_t)nrow + 1), st));
     if (nnz) hipLaunchKernelGGL(k_rowptr_heads, dim3(ceil_div(nnz, 256)), dim3(256), 0, st, row, nnz, rowptr);
     hipLaunchKernelGGL(k_rowptr_fill, dim3(ceil_div(nrow + 1, 256)), dim3(256), 0, st, row, nnz, nrow, rowptr);
+    return PTR_HEADS_FILL;
 }
 // spsparse sum(M,dim,'+'): one sequential chain per segment (a CSR row in ascending column order,
 // or a column in ascending row order through the stable by-column permutation `idx`), exactly
@@ -563,14 +565,17 @@ __global__ void k_seg_sums_wave(const int32_t *__restrict__ ptr, const uint32_t 
     }
     if (lane == 0) out[r] = s;
 }
+// returns the form taken (CsrBuildTrace: SEG_*)
 template <bool FROM_ZERO>
-static void seg_sums(const int32_t *ptr, const uint32_t *idx, const double *val, int nseg, long nnz, double *out,
-                     hipStream_t st) {
-    if (nseg == 0) return;
-    if (nnz >= 8l * nseg)
+static int seg_sums(const int32_t *ptr, const uint32_t *idx, const double *val, int nseg, long nnz, double *out,
+                    hipStream_t st) {
+    if (nseg == 0) return SEG_NONE;
+    if (nnz >= 8l * nseg) {
         hipLaunchKernelGGL(k_seg_sums_wave<FROM_ZERO>, dim3(ceil_div((long)nseg * 64, 256)), dim3(256), 0, st, ptr, idx, val, nseg, out);
-    else
-        hipLaunchKernelGGL(k_seg_sums_thread<FROM_ZERO>, dim3(ceil_div(nseg, 256)), dim3(256), 0, st, ptr, idx, val, nseg, out);
+        return SEG_WAVE;
+    }
+    hipLaunchKernelGGL(k_seg_sums_thread<FROM_ZERO>, dim3(ceil_div(nseg, 256)), dim3(256), 0, st, ptr, idx, val, nseg, out);
+    return SEG_THREAD;
 }
 __global__ void k_col_keys(const int32_t *__restrict__ col, long nnz, uint64_t *__restrict__ keys, uint32_t *__restrict__ idx) {
     const long u = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -582,8 +587,10 @@ __global__ void k_keys_to_i32(const uint64_t *__restrict__ keys, long n, int32_t
 }
 // cs[c] = spsparse sum(M, 1, '+') of column c of w's CSR: the entries ordered by column (a stable radix sort keeps the rows of a
 // column ascending), then summed per column.  Enqueued on st.
-static void col_sums_by_sort(const ibh_weighted *w, int ncol, double *cs, hipStream_t st) {
+// forms (may be null): {the seg_sums form, the rowptr_from_rows form} it took
+static void col_sums_by_sort(const ibh_weighted *w, int ncol, double *cs, hipStream_t st, int *forms = nullptr) {
     const long nnz = w->nnz;
+    if (forms) forms[0] = SEG_NONE, forms[1] = PTR_NONE;
     if (!nnz) {
         if (ncol) IBH_HIP(hipMemsetAsync(cs, 0, sizeof(double) * (size_t)ncol, st));
         return;
@@ -597,8 +604,9 @@ static void col_sums_by_sort(const ibh_weighted *w, int ncol, double *cs, hipStr
     if (f.nbits > 0 && radix_sort_pairs(ck, ck2, ci, ci2, (size_t)nnz, &f, 1, st)) { std::swap(ck, ck2); std::swap(ci, ci2); }
     int32_t *scol = A.get<int32_t>((size_t)nnz), *colptr = A.get<int32_t>((size_t)ncol + 1);
     hipLaunchKernelGGL(k_keys_to_i32, dim3(ceil_div(nnz, T)), dim3(T), 0, st, ck, nnz, scol);
-    rowptr_from_rows(scol, nnz, ncol, colptr, st);
-    seg_sums<true>(colptr, ci, w->val.p, ncol, nnz, cs, st);
+    const int pf = rowptr_from_rows(scol, nnz, ncol, colptr, st);
+    const int sf = seg_sums<true>(colptr, ci, w->val.p, ncol, nnz, cs, st);
+    if (forms) forms[0] = sf, forms[1] = pf;
 }
 
 // ---- column sums for matrices with short columns (AvI, EvI, AvX, EvX, AvE: <= a few rows per column) ----
@@ -677,6 +685,30 @@ __global__ void k_col_sums_long(const uint32_t *__restrict__ colptr, const int32
         }
         if (lane == 0) cs[c] = s;
     }
+}
+// the matrices whose column sums go through the slots (col_sums_by_slots) instead of the sort (col_sums_by_sort)
+inline bool short_columns(long nnz, int ncol) { return nnz && nnz <= 4l * ncol; }
+// cs = the column sums of w's CSR through per-column slots (`row`: the row of every entry), for short_columns().  The slots are
+// handed back for build_bands, with the device count of the columns that went to k_col_sums_long.  Enqueued on st.
+struct ColSlots { uint32_t *colptr = nullptr, *lidx = nullptr; int32_t *lrow = nullptr; uint32_t *nlong = nullptr; };
+static ColSlots col_sums_by_slots(const ibh_weighted *w, const int32_t *row, int ncol, double *cs, hipStream_t st) {
+    Arena &A = arena();
+    const int T = 256;
+    const long nnz = w->nnz;
+    ColSlots s;
+    s.colptr = A.get<uint32_t>((size_t)ncol + 1);
+    uint32_t *cntc = A.get<uint32_t>(2 * (size_t)ncol + 1), *fillc = cntc + ncol;    // zeroed together
+    s.nlong = fillc + ncol;
+    s.lrow = A.get<int32_t>((size_t)nnz);
+    int32_t *longcols = A.get<int32_t>((size_t)ncol);
+    s.lidx = A.get<uint32_t>((size_t)nnz);
+    IBH_HIP(hipMemsetAsync(cntc, 0, sizeof(uint32_t) * (2 * (size_t)ncol + 1), st));
+    hipLaunchKernelGGL(k_col_count, dim3(ceil_div(nnz, T)), dim3(T), 0, st, w->colind.p, nnz, cntc);
+    exclusive_scan_u32(cntc, s.colptr, (size_t)ncol, s.colptr + ncol, st);
+    hipLaunchKernelGGL(k_col_scatter, dim3(ceil_div(nnz, T)), dim3(T), 0, st, row, w->colind.p, nnz, s.colptr, fillc, s.lrow, s.lidx);
+    hipLaunchKernelGGL(k_col_sums, dim3(ceil_div(ncol, T)), dim3(T), 0, st, s.colptr, ncol, s.lrow, s.lidx, w->val.p, cs, s.nlong, longcols);
+    hipLaunchKernelGGL(k_col_sums_long, dim3(256), dim3(T), 0, st, s.colptr, s.lrow, s.lidx, w->val.p, cs, s.nlong, longcols);
+    return s;
 }
 
 // ---- weights and scaling (RegridMatrices_Dynamic.cpp:100-146, 201-233, 290-329) ----------------
@@ -858,10 +890,14 @@ static bool build_csr_short_rows(ibh_weighted *w, const Triplets &t, int nrow, i
     return true;
 }
 
+// trace (may be null): the forms this build took
 static void build_csr_from_contributions(ibh_weighted *w, Triplets t, int nrow, int ncol, int32_t **row_out,
-                                         hipStream_t st, bool expect_local = true) {
+                                         hipStream_t st, bool expect_local = true, CsrBuildTrace *trace = nullptr) {
     Arena &A = arena();
     const int T = 256;
+    CsrBuildTrace unread;
+    CsrBuildTrace &tr = trace ? *trace : unread;
+    tr = CsrBuildTrace{};
     w->nrow = nrow; w->ncol = ncol;
     w->rowptr.alloc((size_t)nrow + 1);
     if (t.n == 0) {
@@ -874,9 +910,11 @@ static void build_csr_from_contributions(ibh_weighted *w, Triplets t, int nrow, 
     // ice / exchange rows with a handful of contributions each: per-row slots, no ordering of the list
     // (measured: always for ~1 contribution per row; with 2+ per row -- IvE -- only while the build is
     // launch-bound, at 35 M contributions the radix passes are cheaper than the per-row selection)
-    if (!expect_local && nrow > 0 && t.n <= 8 * (size_t)nrow && (2 * t.n <= 3 * (size_t)nrow || t.n < (4u << 20)) &&
-        build_csr_short_rows(w, t, nrow, ncol, row_out, st))
-        return;
+    if (!expect_local && nrow > 0 && t.n <= 8 * (size_t)nrow && (2 * t.n <= 3 * (size_t)nrow || t.n < (4u << 20))) {
+        const bool taken = build_csr_short_rows(w, t, nrow, ncol, row_out, st);
+        tr.short_rows = taken ? SRB_TAKEN : SRB_DECLINED;
+        if (taken) return;
+    }
     // Order analysis + piece sort, then (speculatively, on the data as it stands) the duplicate
     // flags and their scan: ONE host synchronisation returns both the analysis and nnz.  Only when a
     // piece was too long for LDS (nothing was touched) does the radix sort run and the tail repeat.
@@ -903,21 +941,27 @@ static void build_csr_from_contributions(ibh_weighted *w, Triplets t, int nrow, 
         const bool optimistic = !expect_local && (rb.info.flags & ORD_LO_DEC) && hi_bits > 0;
         OrderInfo plan = rb.info;
         if (optimistic) plan.flags &= ~(uint32_t)ORD_LO_DEC;
+        tr.order = ORDER_RADIX;
+        if (optimistic) tr.optimistic = OPT_HELD;
         if (radix_after_analysis(plan, t.keys, t.keys_alt, t.idx, t.idx_alt, t.n, lo_bits, hi_bits, st)) {
             std::swap(t.keys, t.keys_alt); std::swap(t.idx, t.idx_alt);
         }
         flags_and_count(optimistic);
         readback_sync(&rb.total, d_total, 2 * sizeof(uint32_t), st);
         if (optimistic && rb.unsorted) {
+            tr.optimistic = OPT_FAILED;
             if (radix_after_analysis(rb.info, t.keys, t.keys_alt, t.idx, t.idx_alt, t.n, lo_bits, hi_bits, st)) {
                 std::swap(t.keys, t.keys_alt); std::swap(t.idx, t.idx_alt);
             }
             flags_and_count(false);
             readback_sync(&rb.total, d_total, sizeof(uint32_t), st);
         }
-    } else if (!expect_local) {
-        flags_and_count(false);
-        readback_sync(&rb.total, d_total, sizeof(uint32_t), st);
+    } else {
+        tr.order = t.n >= 2 && (rb.info.flags & ORD_FULL_DEC) ? ORDER_PIECES : ORDER_IN_ORDER;
+        if (!expect_local) {
+            flags_and_count(false);
+            readback_sync(&rb.total, d_total, sizeof(uint32_t), st);
+        }
     }
     const uint32_t nnz = rb.total;
     IBH_CHECK(nnz < (1u << 31), "nnz overflows int32");
@@ -926,8 +970,8 @@ static void build_csr_from_contributions(ibh_weighted *w, Triplets t, int nrow, 
     int32_t *row = A.get<int32_t>(nnz);
     int32_t *segptr = A.get<int32_t>((size_t)nnz + 1);
     hipLaunchKernelGGL(k_segment_heads, dim3(ceil_div(t.n, T)), dim3(T), 0, st, t.keys, t.n, head, nnz, segptr, row, w->colind.p);
-    seg_sums<false>(segptr, t.idx, t.term, (int)nnz, (long)t.n, w->val.p, st);
-    rowptr_from_rows(row, (long)nnz, nrow, w->rowptr.p, st);
+    tr.seg_form = seg_sums<false>(segptr, t.idx, t.term, (int)nnz, (long)t.n, w->val.p, st);
+    tr.rowptr_form = rowptr_from_rows(row, (long)nnz, nrow, w->rowptr.p, st);
     IBH_HIP(hipGetLastError());
     *row_out = row;
 }
@@ -2453,19 +2497,10 @@ bool assemble_matrix(const ibh_regrid_matrices *rm, const char *spec_name, ibh_s
     seg_sums<true>(w->rowptr.p, nullptr, w->val.p, nrow, nnz, rs, st);
     uint32_t *colptr = nullptr, *lidx = nullptr;       // per-column slots (short-column path), reused by build_bands
     int32_t *lrow = nullptr;
-    if (nnz && nnz <= 4l * ncol) {
+    if (short_columns(nnz, ncol)) {
         // short columns: per-column slots + one thread per column (see k_col_sums)
-        colptr = A.get<uint32_t>((size_t)ncol + 1);
-        uint32_t *cntc = A.get<uint32_t>(2 * (size_t)ncol + 1), *fillc = cntc + ncol, *nlong = fillc + ncol;    // zeroed together
-        lrow = A.get<int32_t>((size_t)nnz);
-        int32_t *longcols = A.get<int32_t>((size_t)ncol);
-        lidx = A.get<uint32_t>((size_t)nnz);
-        IBH_HIP(hipMemsetAsync(cntc, 0, sizeof(uint32_t) * (2 * (size_t)ncol + 1), st));
-        hipLaunchKernelGGL(k_col_count, dim3(ceil_div(nnz, T)), dim3(T), 0, st, w->colind.p, nnz, cntc);
-        exclusive_scan_u32(cntc, colptr, (size_t)ncol, colptr + ncol, st);
-        hipLaunchKernelGGL(k_col_scatter, dim3(ceil_div(nnz, T)), dim3(T), 0, st, row, w->colind.p, nnz, colptr, fillc, lrow, lidx);
-        hipLaunchKernelGGL(k_col_sums, dim3(ceil_div(ncol, T)), dim3(T), 0, st, colptr, ncol, lrow, lidx, w->val.p, cs, nlong, longcols);
-        hipLaunchKernelGGL(k_col_sums_long, dim3(256), dim3(T), 0, st, colptr, lrow, lidx, w->val.p, cs, nlong, longcols);
+        const ColSlots s = col_sums_by_slots(w.get(), row, ncol, cs, st);
+        colptr = s.colptr; lrow = s.lrow; lidx = s.lidx;
     } else {
         col_sums_by_sort(w.get(), ncol, cs, st);
     }
@@ -2931,4 +2966,65 @@ void i2vx_compute(const ibh_weighted *IvI2, const ibh_weighted *IvX, ibh_weighte
     out->scaled = 0;
 }
 
+// ibh_selftest_triplets: the shared triplets -> CSR build on host triplets, with the weights as a matrix build takes them
+static void selftest_triplets(int nrow, int ncol, int64_t n, const int32_t *row, const int32_t *col, const double *val, bool expect_local,
+                              ibh_weighted *w, int32_t *info) {
+    hipStream_t st = hipStreamPerThread;
+    Arena &A = arena();
+    A.reset();
+    int32_t *drow = A.get<int32_t>((size_t)n), *dcol = A.get<int32_t>((size_t)n);
+    Triplets t = triplets_in_arena((size_t)n);
+    if (n) {
+        IBH_HIP(hipMemcpyAsync(drow, row, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, st));
+        IBH_HIP(hipMemcpyAsync(dcol, col, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, st));
+        IBH_HIP(hipMemcpyAsync(t.term, val, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_coo_keys, dim3(ceil_div(n, 256)), dim3(256), 0, st, drow, dcol, t.n, t.keys, t.idx);
+    }
+    CsrBuildTrace tr;
+    int32_t *erow = nullptr;
+    build_csr_from_contributions(w, t, nrow, ncol, &erow, st, expect_local, &tr);
+    const long nnz = w->nnz;
+    w->wM.alloc((size_t)nrow); w->Mw.alloc((size_t)ncol);
+    const int wM_form = seg_sums<true>(w->rowptr.p, nullptr, w->val.p, nrow, nnz, w->wM.p, st);
+    int Mw_forms[2] = {SEG_NONE, PTR_NONE};
+    uint32_t nlong = 0;
+    const bool slots = short_columns(nnz, ncol);
+    if (slots) {
+        const ColSlots s = col_sums_by_slots(w, erow, ncol, w->Mw.p, st);
+        readback_sync(&nlong, s.nlong, sizeof(nlong), st);
+    } else {
+        col_sums_by_sort(w, ncol, w->Mw.p, st, Mw_forms);
+    }
+    IBH_HIP(hipGetLastError());
+    IBH_HIP(hipStreamSynchronize(st));
+    const int32_t out[IBH_TRIPLETS_INFO] = {tr.order, tr.short_rows, tr.optimistic, tr.seg_form, tr.rowptr_form, wM_form,
+                                            slots ? 1 : nnz ? 2 : 0, (int32_t)nlong, Mw_forms[0], Mw_forms[1]};
+    std::copy(out, out + IBH_TRIPLETS_INFO, info);
+}
+
 }  // namespace ibh
+
+using namespace ibh;
+extern "C" {
+
+int ibh_selftest_triplets(int32_t nrow, int32_t ncol, int64_t n, const int32_t *row, const int32_t *col, const double *val, int mode,
+                          ibh_weighted **out, int32_t *info_out) {
+    if (out) *out = nullptr;
+    return guarded([&] {
+        IBH_CHECK(out && info_out, "null argument");
+        IBH_CHECK(nrow >= 0 && ncol >= 0 && n >= 0 && n < (1ll << 31), "bad sizes %d x %d, %lld triplets", nrow, ncol, (long long)n);
+        IBH_CHECK(n == 0 || (row && col && val), "null triplets");
+        IBH_CHECK(mode == 0 || mode == 1, "mode %d is neither 0 (expect_local) nor 1", mode);
+        for (int64_t k = 0; k < n; ++k)
+            IBH_CHECK(row[k] >= 0 && row[k] < nrow && col[k] >= 0 && col[k] < ncol, "triplet %lld (%d, %d) outside %d x %d", (long long)k,
+                      row[k], col[k], nrow, ncol);
+        require_device();
+        auto w = new_weighted();
+        selftest_triplets(nrow, ncol, n, row, col, val, mode == 0, w.get(), info_out);
+        w->conservative = 1; w->scaled = 0;
+        w->dims[0] = DimRef::owned_identity(nrow); w->dims[1] = DimRef::owned_identity(ncol);
+        *out = w.release();
+    });
+}
+
+}  // extern "C"

@@ -245,4 +245,111 @@ int ibh_selftest_csr_product(const ibh_weighted *L, const ibh_weighted *R, ibh_w
     });
 }
 
+int ibh_selftest_csr_op(int op, const ibh_weighted *in, const int32_t *idx, int64_t nidx, const double *a, int64_t na, const double *b,
+                        int64_t nb, int64_t nout, ibh_weighted **mat_out, void *vec_out) {
+    if (mat_out) *mat_out = nullptr;
+    return guarded([&] {
+        const bool matrix_op = op >= IBH_CSROP_TRANSPOSE && op <= IBH_CSROP_SCALE_ROWS_RECIP;
+        IBH_CHECK(op >= IBH_CSROP_TRANSPOSE && op <= IBH_CSROP_EXPAND_ROWS, "unknown op %d", op);
+        IBH_CHECK(nidx >= 0 && na >= 0 && nb >= 0 && nout >= 0 && std::max({nidx, na, nb, nout}) < (1ll << 31), "bad lengths");
+        IBH_CHECK((nidx == 0 || idx) && (na == 0 || a) && (nb == 0 || b), "a length without its array");
+        IBH_CHECK(!(nidx == 0 && idx) && !(na == 0 && a) && !(nb == 0 && b), "an array without its length");
+        IBH_CHECK(matrix_op ? mat_out != nullptr : (vec_out != nullptr || nout == 0 || op == IBH_CSROP_EXPAND_ROWS), "no output");
+        IBH_CHECK((matrix_op || op == IBH_CSROP_EXPAND_ROWS) == (in != nullptr), "op %d %s a matrix", op, in ? "takes no" : "needs");
+        if (op == IBH_CSROP_EXPAND_ROWS) IBH_CHECK(vec_out || in->nnz == 0, "no output");
+        const auto all_within = [&](int64_t lo, int64_t hi) {
+            for (int64_t k = 0; k < nidx; ++k)
+                if (idx[k] < lo || idx[k] >= hi) return false;
+            return true;
+        };
+        switch (op) {
+        case IBH_CSROP_TRANSPOSE: case IBH_CSROP_EXPAND_ROWS:
+            IBH_CHECK(!nidx && !na && !nb, "op %d takes the matrix alone", op);
+            break;
+        case IBH_CSROP_CROP_ROWS:
+            IBH_CHECK(nidx == nout && (na == 0 || na == in->nrow) && !nb, "crop_rows: src[nout], rs[nrow] or none");
+            IBH_CHECK(all_within(-1, in->nrow), "crop_rows: a source row outside [-1, %d)", in->nrow);
+            break;
+        case IBH_CSROP_CROP_COLS: {
+            IBH_CHECK(nidx == in->ncol && (na == 0 || na == in->nrow) && (nb == 0 || nb == nout), "crop_cols: map[ncol], rs[nrow], cs[nout]");
+            IBH_CHECK(all_within(-1, nout), "crop_cols: a target column outside [-1, %lld)", (long long)nout);
+            std::vector<char> hit((size_t)nout, 0);
+            for (int64_t k = 0; k < nidx; ++k)
+                if (idx[k] >= 0) { IBH_CHECK(!hit[(size_t)idx[k]], "crop_cols: the map is not one-to-one"); hit[(size_t)idx[k]] = 1; }
+            break;
+        }
+        case IBH_CSROP_SCALE_ROWS: case IBH_CSROP_SCALE_ROWS_RECIP:
+            IBH_CHECK(!nidx && na == in->nrow && !nb, "a row scaling takes a[nrow]");
+            break;
+        case IBH_CSROP_SCALE_COLS:
+            IBH_CHECK(!nidx && na == in->ncol && !nb, "scale_cols takes a[ncol]");
+            break;
+        case IBH_CSROP_RECIP:
+            IBH_CHECK(!nidx && na == nout && !nb, "recip takes a[nout]");
+            break;
+        case IBH_CSROP_MUL:
+            IBH_CHECK(!nidx && na == nout && nb == nout, "mul takes a[nout], b[nout]");
+            break;
+        case IBH_CSROP_GATHER:
+            IBH_CHECK(nidx == nout && !nb && all_within(0, na), "gather takes idx[nout] into a[na]");
+            break;
+        }
+        require_device();
+        if (in) check_current_device(in->device, "the matrix");
+        hipStream_t st = hipStreamPerThread;
+        Arena &A = arena();
+        A.reset();
+        // (the operands live outside the arena: csr_product and transpose_csr reset it)
+        DevBuf<int32_t> d_idx; DevBuf<double> d_a, d_b, d_out;
+        if (nidx) d_idx.upload(idx, (size_t)nidx, st);
+        if (na) d_a.upload(a, (size_t)na, st);
+        if (nb) d_b.upload(b, (size_t)nb, st);
+        if (matrix_op) {
+            auto w = new_weighted();
+            if (op == IBH_CSROP_TRANSPOSE) {
+                transpose_csr(*in, w.get(), st);
+            } else if (op == IBH_CSROP_CROP_ROWS) {
+                crop_rows(*in, d_idx.p, (int)nout, na ? d_a.p : nullptr, w.get(), st);
+            } else if (op == IBH_CSROP_CROP_COLS) {
+                crop_cols(*in, d_idx.p, (int)nout, na ? d_a.p : nullptr, nb ? d_b.p : nullptr, w.get(), st);
+            } else {                                        // the scalings work in place: on a copy of the CSR
+                w->nrow = in->nrow; w->ncol = in->ncol; w->nnz = in->nnz;
+                w->rowptr.alloc((size_t)in->nrow + 1); w->colind.alloc((size_t)in->nnz); w->val.alloc((size_t)in->nnz);
+                IBH_HIP(hipMemcpyAsync(w->rowptr.p, in->rowptr.p, sizeof(int32_t) * ((size_t)in->nrow + 1), hipMemcpyDeviceToDevice, st));
+                if (in->nnz) {
+                    IBH_HIP(hipMemcpyAsync(w->colind.p, in->colind.p, sizeof(int32_t) * (size_t)in->nnz, hipMemcpyDeviceToDevice, st));
+                    IBH_HIP(hipMemcpyAsync(w->val.p, in->val.p, sizeof(double) * (size_t)in->nnz, hipMemcpyDeviceToDevice, st));
+                }
+                if (op == IBH_CSROP_SCALE_ROWS) scale_rows(w->rowptr.p, w->nrow, d_a.p, w->val.p, st);
+                else if (op == IBH_CSROP_SCALE_COLS) scale_cols(w->colind.p, w->nnz, d_a.p, w->val.p, st);
+                else scale_rows_recip(w->rowptr.p, w->nrow, d_a.p, w->val.p, st);
+            }
+            IBH_HIP(hipGetLastError());
+            w->wM.alloc((size_t)w->nrow); w->wM.zero(st);
+            w->Mw.alloc((size_t)w->ncol); w->Mw.zero(st);
+            IBH_HIP(hipStreamSynchronize(st));
+            w->conservative = in->conservative; w->scaled = in->scaled;
+            w->dims[0] = DimRef::owned_identity(w->nrow); w->dims[1] = DimRef::owned_identity(w->ncol);
+            *mat_out = w.release();
+            return;
+        }
+        if (op == IBH_CSROP_EXPAND_ROWS) {
+            DevBuf<int32_t> d_row((size_t)in->nnz);
+            expand_rows(in->rowptr.p, in->nrow, d_row.p, st);
+            IBH_HIP(hipGetLastError());
+            d_row.download(static_cast<int32_t *>(vec_out), (size_t)in->nnz, st);
+            return;
+        }
+        if (op == IBH_CSROP_RECIP) {
+            recip(d_a.p, (int)nout, d_out, st);
+        } else {
+            d_out.alloc((size_t)nout);
+            if (op == IBH_CSROP_MUL) mul(d_a.p, d_b.p, (int)nout, d_out.p, st);
+            else gather(d_a.p, d_idx.p, (long)nout, d_out.p, st);
+        }
+        IBH_HIP(hipGetLastError());
+        d_out.download(static_cast<double *>(vec_out), (size_t)nout, st);
+    });
+}
+
 }  // extern "C"

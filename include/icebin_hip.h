@@ -578,6 +578,31 @@ int ibh_modele_make_topoA(const double *const *planesO /* [9] */, const int16_t 
  * ascending inside a row, L's columns = R's rows): C(r, c) sums L(r, k) * R(k, c) over k ascending, the first term assigned;
  * an entry exists wherever a term does.  Identity dims, wM = Mw = 0, flags of L.  Used by tests/test_gpu_modele.py. */
 int ibh_selftest_csr_product(const ibh_weighted *L, const ibh_weighted *R, ibh_weighted **out);
+/* Diagnostic: the shared triplets -> CSR build (Eigen setFromTriplets: duplicates summed in input order, the first term
+ * assigned) on n host triplets with dense ids, and the plain weights as a matrix build takes them.  mode 0: local disorder
+ * is expected, as ibh_weighted_from_coo; mode 1: it is not (the ice-row builds: per-row slots, the optimistic row-only sort).
+ * *out: identity dims, wM = sum(M, 0, '+') (columns ascending, from 0), Mw = sum(M, 1, '+') (rows ascending, from 0) through
+ * per-column slots when nnz <= 4 * ncol, else through the stable sort by column.  info_out[IBH_TRIPLETS_INFO]: the forms that ran,
+ *   [0] order: 0 in order, 1 pieces sorted in LDS, 2 radix sort       [1] per-row slots: 0 not tried, 1 taken, 2 declined
+ *   [2] optimistic row-only sort: 0 not tried, 1 held, 2 failed        [3] sums of the values: 0 none, 1 thread, 2 wave per entry
+ *   [4] row pointer: 0 none, 1 every row searches, 2 heads + fill      [5] wM: as [3], per row
+ *   [6] Mw: 0 no entries, 1 slots, 2 sort                              [7] slots: columns of more than 64 entries
+ *   [8], [9] sort: as [3] per column, as [4] for the column pointer.
+ * Every argument is checked before a device is touched.  Used by tests/test_gpu_csr_build.py. */
+#define IBH_TRIPLETS_INFO 10
+int ibh_selftest_triplets(int32_t nrow, int32_t ncol, int64_t n, const int32_t *row, const int32_t *col, const double *val, int mode,
+                          ibh_weighted **out, int32_t *info_out);
+/* Diagnostic: one piece of the CSR algebra alone (csrops.h).  Host arrays: idx[nidx], a[na], b[nb]; an unused one is NULL with
+ * length 0.  The matrix ops take `in` and return *mat_out (identity dims, wM = Mw = 0, flags of `in`):
+ *   TRANSPOSE;  CROP_ROWS idx = src[nout] (-1: an empty row), a = rs[nrow] or none;  CROP_COLS idx = map[ncol] into [0, nout)
+ *   (-1: dropped; one-to-one), a = rs[nrow] or none, b = cs[nout] or none;  SCALE_ROWS a[nrow] * v;  SCALE_COLS v * a[ncol];
+ *   SCALE_ROWS_RECIP v * (1 / a[nrow]), rows without entries skipped.
+ * The vector ops take in = NULL and fill vec_out (double[nout]): RECIP 1 / a;  MUL a * b;  GATHER a[idx[k]].  EXPAND_ROWS takes
+ * `in` and fills vec_out (int32[nnz]) with the row of every entry.  Every argument is checked before a device is touched. */
+enum { IBH_CSROP_TRANSPOSE = 0, IBH_CSROP_CROP_ROWS, IBH_CSROP_CROP_COLS, IBH_CSROP_SCALE_ROWS, IBH_CSROP_SCALE_COLS,
+       IBH_CSROP_SCALE_ROWS_RECIP, IBH_CSROP_RECIP, IBH_CSROP_MUL, IBH_CSROP_GATHER, IBH_CSROP_EXPAND_ROWS };
+int ibh_selftest_csr_op(int op, const ibh_weighted *in, const int32_t *idx, int64_t nidx, const double *a, int64_t na, const double *b,
+                        int64_t nb, int64_t nout, ibh_weighted **mat_out, void *vec_out);
 
 /* Public members of Weighted_Eigen, read back to host. */
 int ibh_weighted_shape(const ibh_weighted *w, int32_t *nrow_d, int32_t *ncol_d, int64_t *nnz);

@@ -323,3 +323,87 @@ def test_every_sorted_grid_assembly_kernel_has_a_case(lib, tmp_path):
         if "[" in func:
             case = func[func.index("[") + 1:-1]
             assert module == "test_gpu_assembly_limits.py" and case in {c["name"] for c in alc.CASES}, (kernel, test)
+
+
+def csr_build_cases_module():
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    try:
+        import csr_build_cases as cbc
+    finally:
+        sys.path.pop(0)
+    return cbc
+
+
+def assert_named_tests_exist(table):
+    modules = {}
+    for kernel, test in table.items():
+        module, func = test.split("::")
+        if module not in modules:
+            modules[module] = open(os.path.join(ROOT, "tests", module)).read()
+        assert re.search(r"^def %s\(" % func, modules[module], re.M), (kernel, test)
+
+
+def test_every_csrops_kernel_and_every_triplet_build_kernel_has_a_case(lib, tmp_path):
+    # tests/csr_build_cases.py names, for every kernel of csrops.o and for the kernels of the triplets -> CSR layer in assemble.o
+    # (listed there by a pattern of names), the test of tests/test_gpu_csr_build.py that runs it against the exact restatement: a
+    # kernel built without a case, or a case for a kernel no longer built, fails here; so does a test named there that does not exist
+    cbc = csr_build_cases_module()
+    mangled = re.findall(r"^    \.name:\s+(\S+)", code_object_notes(tmp_path, "csrops"), re.M)
+    built = {assembly_kernel_name(m.replace("12_GLOBAL__N_1", "", 1)) for m in mangled}
+    assert None not in built and len(built) == len(mangled) >= 14, (sorted(mangled), sorted(map(str, built)))
+    assert built == set(cbc.CSROPS_KERNELS), ("built without a case", sorted(built - set(cbc.CSROPS_KERNELS)), "case without a kernel",
+                                              sorted(set(cbc.CSROPS_KERNELS) - built))
+    mangled = re.findall(r"^    \.name:\s+(\S+)", code_object_notes(tmp_path, "assemble"), re.M)
+    names = {assembly_kernel_name(m) for m in mangled if re.match(r"_ZN3ibh\d+k_", m)}
+    layer = {n for n in names if n and re.match(cbc.LAYER_KERNEL_PATTERN, n.split("<")[0])}
+    assert len(layer) >= 20
+    assert layer == set(cbc.LAYER_KERNELS), ("built without a case", sorted(layer - set(cbc.LAYER_KERNELS)), "case without a kernel",
+                                            sorted(set(cbc.LAYER_KERNELS) - layer))
+    assert_named_tests_exist(cbc.CSROPS_KERNELS)
+    assert_named_tests_exist(cbc.LAYER_KERNELS)
+
+
+def test_selftest_triplets_rejects_bad_arguments(lib):
+    import ctypes as C
+    import numpy as np
+    cbc = csr_build_cases_module()
+    row, col, val = np.asarray([0, 1], np.int32), np.asarray([2, 0], np.int32), np.asarray([1., 2.])
+    info, h = np.zeros(len(cbc.INFO), np.int32), C.c_void_p()
+
+    def call(nrow=2, ncol=3, n=2, r=row, c=col, v=val, mode=0, out=C.byref(h), inf=info):
+        p = lambda a: None if a is None else a.ctypes.data
+        return lib.ibh_selftest_triplets(nrow, ncol, n, p(r), p(c), p(v), mode, out, p(inf))
+
+    for bad in (dict(nrow=-1), dict(ncol=-1), dict(n=-1), dict(n=1 << 31), dict(mode=2), dict(mode=-1), dict(r=None), dict(c=None),
+                dict(v=None), dict(out=None), dict(inf=None), dict(nrow=1), dict(ncol=2), dict(r=np.asarray([0, -1], np.int32)),
+                dict(c=np.asarray([3, 0], np.int32)), dict(nrow=0, ncol=0)):
+        assert call(**bad) == _capi.IBH_EINVAL, bad
+        assert not h.value
+
+
+def test_selftest_csr_op_rejects_bad_arguments(lib):
+    import ctypes as C
+    import numpy as np
+    cbc = csr_build_cases_module()
+    op = cbc.OPS
+    i32, f64 = (lambda *x: np.asarray(x, np.int32)), (lambda *x: np.asarray(x, np.float64))
+    h, vec = C.c_void_p(), np.zeros(8)
+    # a handle is only looked at once the other arguments hold: without a GPU no matrix can be made, so the checks that need one
+    # (lengths against its shape) are left to the GPU tests; here, everything that is wrong whatever the matrix
+
+    def call(code, m=None, idx=None, a=None, b=None, nout=0, nidx=None, na=None, nb=None, out=C.byref(h), v=vec.ctypes.data):
+        p = lambda x: None if x is None else x.ctypes.data
+        n = lambda x, k: (0 if x is None else len(x)) if k is None else k
+        return lib.ibh_selftest_csr_op(code, m, p(idx), n(idx, nidx), p(a), n(a, na), p(b), n(b, nb), nout, out, v)
+
+    for bad in (dict(code=-1), dict(code=10), dict(code=op["recip"], a=f64(1, 2), nout=2, na=-1), dict(code=op["recip"], a=f64(1, 2), nout=3),
+                dict(code=op["recip"], a=f64(1, 2), nout=2, v=None), dict(code=op["recip"], nout=2, na=2),
+                dict(code=op["recip"], a=f64(1, 2), nout=2, idx=i32(0)), dict(code=op["mul"], a=f64(1, 2), b=f64(1), nout=2),
+                dict(code=op["mul"], a=f64(1, 2), nout=2), dict(code=op["gather"], a=f64(1, 2), idx=i32(0, 2), nout=2),
+                dict(code=op["gather"], a=f64(1, 2), idx=i32(0, -1), nout=2), dict(code=op["gather"], a=f64(1, 2), idx=i32(0), nout=2),
+                dict(code=op["gather"], a=f64(1, 2), idx=i32(0, 1), nout=2, nidx=1 << 31), dict(code=op["transpose"]),
+                dict(code=op["crop_rows"]), dict(code=op["crop_cols"]), dict(code=op["scale_rows"], a=f64(1)), dict(code=op["scale_cols"]),
+                dict(code=op["scale_rows_recip"]), dict(code=op["expand_rows"]), dict(code=op["transpose"], out=None)):
+        assert call(**bad) == _capi.IBH_EINVAL, bad
+        assert not h.value
