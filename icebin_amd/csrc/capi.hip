@@ -8,6 +8,8 @@
 
 #include "assemble.h"
 #include "common.h"
+#include "csrbuild.h"
+#include "csrops.h"
 #include "prims.h"
 #include "sparseset.h"
 
@@ -864,7 +866,7 @@ int ibh_selftest_order(const uint64_t *keys, int64_t n, int lo_bits, int hi_bits
         bool alt = false;
         if (try_pieces) {
             alt = adaptive_sort_pairs(k, k2, v, v2, m, lo_bits, hi_bits, info, st);
-        } else {                // the flags-only analysis, then the radix sort it plans (assemble.hip, expect_local = false)
+        } else {                // the flags-only analysis, then the radix sort it plans (csrbuild.hip, expect_local = false)
             order_and_chunk_sort(k, v, m, info, st, false);
             OrderInfo h;
             readback_sync(&h, info, sizeof(h), st);

@@ -514,4 +514,10 @@ size_t weight_dot_scratch(int n, int nvar);
 void set_launch_events(hipEvent_t start, hipEvent_t stop);
 int get_tuning(const char *key, int dflt);
 void set_tuning(const char *key, int value);
+// gridgen.hip
+// make_exchange_grid (gridgen/GridGen_Exchange.cpp:175-284) for a rectilinear XY ice grid
+void exgrid_generate(const ibh_exgrid_desc *d, ibh_exgrid *out);
+// the same from polygons already in HBM (d_*: device arrays, ascending iA; edges on the host), through the streamed clip
+void exgrid_generate_polys(int nx, int ny, const double *xedges, const double *yedges, int x_fastest, int npoly, const int32_t *d_polyptr,
+                           const double *d_vx, const double *d_vy, const int64_t *d_iA, ibh_exgrid *out, hipStream_t st);
 }  // namespace ibh

@@ -1,7 +1,8 @@
 // csrops.h -- small algebra on CSR matrices that are already in HBM (csrops.hip): the sparse product, re-numbered copies, the
 // transpose, and row / vector scalings.  Each piece exists once; the matrix builds outside the exchange-grid assembly (modele.hip,
-// l1.hip, hntr.hip, E1vE0 and I2vX in assemble.hip) compose them.  Everything is enqueued on the caller's stream and uses the
-// calling thread's arena; what waits for the device says so.
+// l1.hip, hntr.hip, globalave.hip, topo.hip) compose them, and so do the two builds at the end of this header, E1vE0 and I2vX,
+// which are keyed sums over matrices already in HBM.  Everything is enqueued on the caller's stream and uses the calling
+// thread's arena; what waits for the device says so.
 #pragma once
 #include "common.h"
 
@@ -33,6 +34,10 @@ void scale_cols(const int32_t *colind, int64_t nnz, const double *d, double *val
 // diag(1 / sum) * M in place: one reciprocal per row, val = val * (1 / sum[row]); rows without entries are skipped (their
 // sum may be 0)
 void scale_rows_recip(const int32_t *rowptr, int nrow, const double *sum, double *val, hipStream_t st);
+// compute_E1vE0c (e1ve0.cpp:55-106) on device; `out` comes with identity dims over nE.
+void e1ve0_compute(int nsheets, const ibh_weighted *const *XuE1s, const ibh_weighted *const *XuE0s, int64_t nE, ibh_weighted *out);
+// make_I2vX's products (global_ec.cpp:345-376): IvI2 = I2vI by columns (rows dense I); fills out's CSR, wM, Mw and flags
+void i2vx_compute(const ibh_weighted *IvI2, const ibh_weighted *IvX, ibh_weighted *out);
 
 #ifdef __HIPCC__
 // Adds this thread's count into a per-launch total: wave shuffle, one partial per wave in LDS, one atomic per block.  Every

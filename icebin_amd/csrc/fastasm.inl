@@ -191,7 +191,7 @@ static bool ensure_plan(const ibh_regridder *g, hipStream_t st) {
     KeyField f{0, bits_for((uint64_t)nI)};
     if (f.nbits > 0 && radix_sort_pairs(k, k2, v, v2, (size_t)nX, &f, 1, st)) { std::swap(k, k2); std::swap(v, v2); }
     int32_t *srow = A.get<int32_t>((size_t)nX);
-    hipLaunchKernelGGL(k_keys_to_i32, dim3(ceil_div(nX, T)), dim3(T), 0, st, k, nX, srow);
+    keys_to_i32(k, nX, srow, st);
     P.ilptr.alloc((size_t)nI + 1); P.ilist.alloc((size_t)nX); P.ifirst.alloc((size_t)nI);
     rowptr_from_rows(srow, nX, (int)nI, P.ilptr.p, st);
     hipLaunchKernelGGL(k_u32_to_i32, dim3(ceil_div(nX, T)), dim3(T), 0, st, v, nX, P.ilist.p);

@@ -14,6 +14,7 @@
 
 #include "assemble.h"
 #include "common.h"
+#include "csrbuild.h"
 #include "csrops.h"
 #include "modele_parts.h"
 #include "prims.h"

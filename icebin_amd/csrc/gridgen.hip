@@ -14,7 +14,6 @@
 // contraction (the CGAL result is exact rationals rounded to double: areas agree to rounding).
 #include <algorithm>
 
-#include "assemble.h"
 #include "prims.h"
 
 namespace ibh {

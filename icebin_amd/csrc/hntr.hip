@@ -37,8 +37,10 @@
 #include <cmath>
 #include <memory>
 
-#include "assemble.h"
 #include "common.h"
+#include "csrbuild.h"
+#include "csrops.h"
+#include "prims.h"
 #include "sparseset.h"
 
 namespace ibh {
@@ -443,7 +445,7 @@ static void check_typed_args(const ibh_hntr *h, const void *WTA, int wta_type, i
 //   Mw        one thread per A column: the B cells whose windows hold it, rows ascending, from 0
 // All values are recomputed with the same expressions wherever they are needed, so fill, wM and Mw agree bit for bit.
 // Other dims (ADD_DENSE onto a partial set, TO_DENSE through a pre-populated or permuted one, transpose) take the triplets
-// through a first-seen numbering on the device and the assembly's setFromTriplets (weighted_from_device_triplets).
+// through a first-seen numbering on the device and the triplets -> CSR layer's setFromTriplets (weighted_from_device_triplets).
 static void hntr_dxyp(int im, int jm, double *dxyp) {
     const double dLON = (2. * M_PI) / im;
     const double dLAT = M_PI / jm;
@@ -1150,7 +1152,7 @@ static void regridder_create_hntr(const ibh_hntr_regridder_desc *d, ibh_sparse_s
 }
 
 // make_I2vX (modele/global_ec.cpp:345-376): I2vI from the Hntr overlap (as I2vI's columns: no transpose), then the products
-// on the device (assemble.hip i2vx_compute).  dimI2 is numbered on a copy that replaces it only once everything succeeded.
+// on the device (csrops.hip i2vx_compute).  dimI2 is numbered on a copy that replaces it only once everything succeeded.
 static void make_i2vx(const ibh_weighted *IvX, const ibh_hntr *h, double eq_rad, const uint8_t *includeI, int64_t nincl,
                       ibh_sparse_set *dimI2, ibh_weighted **out) {
     IBH_CHECK(out != nullptr && IvX != nullptr, "null argument");

@@ -16,9 +16,9 @@
 //    three corners, which is exact for a linear integrand.  Plain + - * / in a fixed order (the unit is compiled without
 //    contraction): tests/l1_restatement.py states the same arithmetic in numpy, bit for bit.
 //  * the matrix: compute_AvI (element_l1.py:96-148).  Three triplets per exchange cell stay on the device and go through the
-//    assembly's setFromTriplets (weighted_from_device_triplets): duplicates summed in stream order with the first term assigned,
+//    triplets -> CSR layer's setFromTriplets (weighted_from_device_triplets): duplicates summed in stream order with the first term assigned,
 //    wM / Mw in the canonical order.
-#include "assemble.h"
+#include "csrbuild.h"
 #include "csrops.h"
 #include "prims.h"
 

@@ -28,7 +28,6 @@
 #include <memory>
 #include <string>
 
-#include "assemble.h"
 #include "prims.h"
 
 struct ibh_lonlat_cells {

@@ -1,11 +1,11 @@
-"""The triplets -> CSR builder (assemble.hip build_csr_from_contributions and its helpers) and the CSR algebra (csrops.hip) at
+"""The triplets -> CSR builder (csrbuild.hip build_csr_from_contributions and its helpers) and the CSR algebra (csrops.hip) at
 their form edges: the table of selectors, the cases, and an exact restatement in plain Python / numpy float64.
 
 A plain module (no test in it): tests/test_csr_build_cases.py checks on the CPU that every case lies where it claims, that the
 restatement is the oracle, and that the values can tell a wrong kernel from a right one; tests/test_gpu_csr_build.py runs the
 cases on the device, asserts the form that ran (ibh_selftest_triplets' info_out) and then the bits.
 
-The restatement follows csrops.h and the comments of assemble.hip: triplets are ordered stably by (row, col); the terms of one
+The restatement follows csrops.h and the comments of csrbuild.hip: triplets are ordered stably by (row, col); the terms of one
 key are summed by an explicit sequential loop with the first term ASSIGNED (Eigen's setFromTriplets: a signed zero survives);
 row sums run from 0.0 over ascending columns, column sums from 0.0 over ascending rows (spsparse sum); the product emits its
 terms by row of L, k ascending, then the row of R; every product of a crop or scaling is rounded on its own."""
@@ -731,8 +731,12 @@ def wide_matrix(rng=None):
     return random_matrix(rng, 3, 70000, [2000, 0, 1500])
 
 
-# ---- kernel -> the test that runs it (tests/test_capi_symbols.py checks both tables against the code objects) ---------------------------
+# ---- kernel -> the test that runs it (tests/test_capi_symbols.py checks both tables against the code objects: every kernel of
+# csrops.o is a key of CSROPS_KERNELS, every kernel of csrbuild.o a key of LAYER_KERNELS, and the other way round) ------------------
 G = "test_gpu_csr_build.py::"
+# E1vE0 and I2vX against the oracle, bit for bit (E1vE0's two-sheet, own-X-dims cases reach k_csr_to_contrib and k_scatter_rowmap)
+E1VE0 = "test_gpu_parity.py::test_e1ve0_bit_exact_against_oracle"
+I2VX = "test_gpu_global_ec.py::test_make_I2vX_bitwise"
 CSROPS_KERNELS = {
     "k_prod_count": G + "test_product", "k_prod_emit<64>": G + "test_product", "k_prod_emit<1>": G + "test_product",
     "k_crop_rows_count": G + "test_crop_rows", "k_crop_rows_fill": G + "test_crop_rows",
@@ -740,6 +744,9 @@ CSROPS_KERNELS = {
     "k_recip": G + "test_vector_ops", "k_mul": G + "test_vector_ops", "k_gather": G + "test_vector_ops",
     "k_scale_rows": G + "test_scalings", "k_scale_cols": G + "test_scalings", "k_scale_rows_recip": G + "test_scale_rows_recip_skips_empty_rows",
     "k_expand_rows": G + "test_transpose_and_expand_rows",
+    "k_e1ve0<0>": E1VE0, "k_e1ve0<1>": E1VE0, "k_scatter_rowmap": E1VE0, "k_add_by_sparse": E1VE0, "k_csr_to_contrib": E1VE0,
+    "k_fill_f64": E1VE0,
+    "k_i2vx_count": I2VX, "k_i2vx_terms": I2VX, "k_i2vx_wM": I2VX,
 }
 LAYER_KERNELS = {
     "k_head_flags": G + "test_run_lengths", "k_segment_heads": G + "test_run_lengths",
@@ -751,4 +758,3 @@ LAYER_KERNELS = {
     "k_srb_count": G + "test_short_rows", "k_srb_scatter": G + "test_short_rows", "k_srb_unique": G + "test_short_rows",
     "k_srb_emit": G + "test_short_rows", "k_coo_keys": G + "test_run_lengths",
 }
-LAYER_KERNEL_PATTERN = r"k_(head_flags|segment_heads|rowptr_\w+|seg_sums_\w+|col_\w+|keys_to_i32|srb_\w+|coo_keys)$"

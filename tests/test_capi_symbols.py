@@ -345,19 +345,18 @@ def assert_named_tests_exist(table):
 
 
 def test_every_csrops_kernel_and_every_triplet_build_kernel_has_a_case(lib, tmp_path):
-    # tests/csr_build_cases.py names, for every kernel of csrops.o and for the kernels of the triplets -> CSR layer in assemble.o
-    # (listed there by a pattern of names), the test of tests/test_gpu_csr_build.py that runs it against the exact restatement: a
-    # kernel built without a case, or a case for a kernel no longer built, fails here; so does a test named there that does not exist
+    # tests/csr_build_cases.py names, for every kernel of csrops.o and every kernel of the triplets -> CSR layer, csrbuild.o, the
+    # test that runs it against an exact reference: a kernel built without a case, or a case for a kernel no longer built, fails
+    # here; so does a test named there that does not exist
     cbc = csr_build_cases_module()
     mangled = re.findall(r"^    \.name:\s+(\S+)", code_object_notes(tmp_path, "csrops"), re.M)
     built = {assembly_kernel_name(m.replace("12_GLOBAL__N_1", "", 1)) for m in mangled}
     assert None not in built and len(built) == len(mangled) >= 14, (sorted(mangled), sorted(map(str, built)))
     assert built == set(cbc.CSROPS_KERNELS), ("built without a case", sorted(built - set(cbc.CSROPS_KERNELS)), "case without a kernel",
                                               sorted(set(cbc.CSROPS_KERNELS) - built))
-    mangled = re.findall(r"^    \.name:\s+(\S+)", code_object_notes(tmp_path, "assemble"), re.M)
-    names = {assembly_kernel_name(m) for m in mangled if re.match(r"_ZN3ibh\d+k_", m)}
-    layer = {n for n in names if n and re.match(cbc.LAYER_KERNEL_PATTERN, n.split("<")[0])}
-    assert len(layer) >= 20
+    mangled = re.findall(r"^    \.name:\s+(\S+)", code_object_notes(tmp_path, "csrbuild"), re.M)
+    layer = {assembly_kernel_name(m) for m in mangled}
+    assert None not in layer and len(layer) == len(mangled) >= 20, (sorted(mangled), sorted(map(str, layer)))
     assert layer == set(cbc.LAYER_KERNELS), ("built without a case", sorted(layer - set(cbc.LAYER_KERNELS)), "case without a kernel",
                                             sorted(set(cbc.LAYER_KERNELS) - layer))
     assert_named_tests_exist(cbc.CSROPS_KERNELS)

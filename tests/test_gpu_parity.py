@@ -1761,7 +1761,7 @@ def test_shortrow_shared_columns_are_bitwise_the_gather_form(pattern):
 
 def test_column_sums_with_long_columns():
     """Mw (column sums in ascending row order) when a few ice cells are overlapped by MANY atmosphere
-    cells: the short-column path (assemble.hip k_col_sums) takes its selection branch (3..64 entries)
+    cells: the short-column path (csrbuild.hip k_col_sums) takes its selection branch (3..64 entries)
     and its one-wave-per-column branch (> 64), still bit-exact against the oracle."""
     g = syn.make_grids("g20")
     em = syn.dome_elevmask(g)
