@@ -114,6 +114,19 @@ _SIGS = {
     "ibh_e1ve0_compute": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_void_p)]),
     "ibh_weighted_make_I2vX": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_int64, C.c_void_p,
                                         C.POINTER(C.c_void_p)]),
+    "ibh_global_ec_scan_create": (C.c_int, [C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_double, C.c_double,
+                                           C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "ibh_global_ec_scan_destroy": (C.c_int, [C.c_void_p]),
+    "ibh_global_ec_scan_get": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ibh_global_ec_scan_copy_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ibh_global_ec_ec_range": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p]),
+    "ibh_global_ec_chunk_plan": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]),
+    "ibh_global_ec_chunk_plan_counts": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p,
+                                                 C.c_void_p, C.POINTER(C.c_int32)]),
+    "ibh_global_ec_chunk_mask": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
+    "ibh_global_ec_chunk_mask_host": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64]),
+    "ibh_global_ec_combine_chunks": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.POINTER(C.c_void_p)]),
     "ibh_modele_matrices_create": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_void_p,
                                             C.c_void_p, C.c_int64, C.POINTER(C.c_void_p)]),
     "ibh_modele_matrices_matrix_d": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),

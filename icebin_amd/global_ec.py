@@ -223,3 +223,238 @@ def write_matrices(gcm, elevmaskI, hspecI2, fname, names=MATRIX_NAMES, correctA=
         ds.variables[vn].attrs["description"] = desc[k]
     ds.write(fname)
     return out
+
+
+# ---- global_ec in chunks: main() below "Check that I grid fits neatly into O grid" (global_ec.cpp:752-893) and
+# combine_global_ec.cpp's combine_chunks (:94-262) ----------------------------------------------------------------------------
+CHUNK_SIZE = 12000000           # global_ec.cpp:100
+
+
+def _einval(msg):
+    return _capi.IcebinHipError(_capi.IBH_EINVAL, msg)
+
+
+def chunk_plan(imO, jmO, mult_i, mult_j, counts, chunk_size=CHUNK_SIZE):
+    """The chunk walk of global_ec.cpp:863-893 over host counts c[k] = fgiceO[k] != 0 ? nice[k] : 0, k = jO*imO + iO (no GPU
+    needed): [((chunkno, jO0, iO0, jO1, iO1), nice), ...].  See IceScan.chunks."""
+    c = np.ascontiguousarray(np.asarray(counts).reshape(-1), np.int32)
+    if len(c) != int(imO) * int(jmO):
+        raise _einval("counts: %d cells, the ocean grid has %d" % (len(c), int(imO) * int(jmO)))
+    n = C.c_int32()
+    args = (int(imO), int(jmO), int(mult_i), int(mult_j), ptr(c), int(chunk_size))
+    check(lib().ibh_global_ec_chunk_plan_counts(*args, 0, None, None, C.byref(n)))
+    ch, nice = np.zeros((n.value, 5), np.int32), np.zeros(n.value, np.int64)
+    check(lib().ibh_global_ec_chunk_plan_counts(*args, n.value, ptr(ch), ptr(nice), C.byref(n)))
+    return [(tuple(int(x) for x in ch[i]), int(nice[i])) for i in range(n.value)]
+
+
+class IceScan:
+    """The global ice of global_ec's main() (global_ec.cpp:752-816) on the device: fgiceI / elevI are the int16 planes
+    [jmI, imI] (FGICE1m / ZICETOP1m), host numpy arrays (uploaded once in their own width and kept) or torch.int16 CUDA
+    tensors (kept as they are).  hspecI must nest in hspecO.  One pass over both planes gives .nice and .elevI_range;
+    .fgiceO is Hntr(17.17, hspecO, hspecI).regrid(1.0, fgiceI).  fgiceO and nice are torch CUDA tensors [jmO, imO]."""
+
+    def __init__(self, hspecO, hspecI, fgiceI, elevI):
+        self.hspecO, self.hspecI = hspecO, hspecI
+        self._h = None
+        planes, dev = [], [hasattr(p, "is_cuda") and p.is_cuda for p in (fgiceI, elevI)]
+        if dev[0] != dev[1]:
+            raise _einval("fgiceI / elevI: one plane is on the host and one on the device")
+        for name, p in (("fgiceI", fgiceI), ("elevI", elevI)):
+            if dev[0]:
+                if str(p.dtype) != "torch.int16":
+                    raise _einval("%s: dtype %s, the ice planes are int16" % (name, p.dtype))
+                p = p.reshape(-1).contiguous()
+                n = p.numel()
+            else:
+                p = np.asarray(p)
+                if p.dtype != np.int16:
+                    raise _einval("%s: dtype %s, the ice planes are int16" % (name, p.dtype))
+                p = np.ascontiguousarray(p.reshape(-1))
+                n = p.size
+            if n != hspecI.size:
+                raise _einval("%s: the plane holds %d cells, hspecI has %d" % (name, n, hspecI.size))
+            planes.append(p)
+        stream = None
+        if dev[0]:
+            import torch
+            stream = torch.cuda.current_stream(planes[0].device).cuda_stream
+            pp = [C.c_void_p(p.data_ptr()) for p in planes]
+        else:
+            pp = [ptr(p) for p in planes]
+        h = C.c_void_p()
+        from .hntr import I16
+        check(lib().ibh_global_ec_scan_create(hspecO.im, hspecO.jm, hspecO.offi, hspecO.dlat, hspecI.im, hspecI.jm, hspecI.offi, hspecI.dlat,
+                                              pp[0], pp[1], hspecI.size, I16, int(dev[0]), C.c_void_p(stream), C.byref(h)))
+        self._h = h
+        self._planes = planes if dev[0] else None       # device planes are read in place: they live as long as the scan
+        self.mult_i, self.mult_j = hspecI.im // hspecO.im, hspecI.jm // hspecO.jm
+        r = np.zeros(2, np.int16)
+        check(lib().ibh_global_ec_scan_get(h, None, None, ptr(r), None, None))
+        self.elevI_range = (int(r[0]), int(r[1]))
+        self._fgiceO = self._nice = None
+
+    def __del__(self):
+        try:
+            _capi.destroy("ibh_global_ec_scan_destroy", getattr(self, "_h", None))
+        except Exception:      # interpreter shutdown
+            pass
+        self._h = None
+
+    def _copies(self):
+        """fgiceO and nice as torch tensors: device-to-device copies of the scan's arrays, made once."""
+        if self._fgiceO is None:
+            import torch
+            shape = (self.hspecO.jm, self.hspecO.im)
+            f = torch.empty(shape, dtype=torch.float64, device="cuda")
+            n = torch.empty(shape, dtype=torch.int32, device="cuda")
+            s = torch.cuda.current_stream(f.device).cuda_stream
+            check(lib().ibh_global_ec_scan_copy_device(self._h, C.c_void_p(f.data_ptr()), C.c_void_p(n.data_ptr()), C.c_void_p(s)))
+            self._fgiceO, self._nice = f, n
+        return self._fgiceO, self._nice
+
+    @property
+    def fgiceO(self):
+        """[jmO, imO] float64 on the device: Hntr(17.17, hspecO, hspecI).regrid(1.0, fgiceI)."""
+        return self._copies()[0]
+
+    @property
+    def nice(self):
+        """[jmO, imO] int32 on the device: the ice cells (fgiceI != 0) of every ocean cell's tile."""
+        return self._copies()[1]
+
+    def ec_range(self, ec_skip):
+        """(ec_skip*floor(min/ec_skip), ec_skip*ceil(max/ec_skip)) (global_ec.cpp:815-816): global, so every chunk gets the
+        same classes hcdefs(lo, hi, ec_skip)."""
+        r, out = np.asarray(self.elevI_range, np.int16), np.zeros(2)
+        check(lib().ibh_global_ec_ec_range(ptr(r), float(ec_skip), ptr(out)))
+        return float(out[0]), float(out[1])
+
+    def chunks(self, chunk_size=CHUNK_SIZE):
+        """The chunk plan (global_ec.cpp:863-893): [((chunkno, jO0, iO0, jO1, iO1), nice), ...], the last bound (jmO, 0).
+        A chunk ends, exclusive, at the first ocean cell at which its running ice count reaches chunk_size; that cell is the
+        next chunk's first, and its ice is in the reported nice of both.  chunk_size must exceed mult_i*mult_j."""
+        n = C.c_int32()
+        check(lib().ibh_global_ec_chunk_plan(self._h, int(chunk_size), 0, None, None, C.byref(n)))
+        ch, nice = np.zeros((n.value, 5), np.int32), np.zeros(n.value, np.int64)
+        check(lib().ibh_global_ec_chunk_plan(self._h, int(chunk_size), n.value, ptr(ch), ptr(nice), C.byref(n)))
+        return [(tuple(int(x) for x in ch[i]), int(nice[i])) for i in range(n.value)]
+
+    def chunk_mask(self, chunk, out=None):
+        """elevmaskI of one chunk (global_ec.cpp:818-855) as a torch.float64 CUDA tensor [nI]: elevI where the cell has ice and
+        its ocean cell lies in the chunk and has fgiceO != 0, else NaN.  chunk: (chunkno, jO0, iO0, jO1, iO1), or a pair
+        (chunk, nice) as .chunks() returns them."""
+        import torch
+        if len(chunk) == 2:
+            chunk = chunk[0]
+        if len(chunk) != 5:
+            raise _einval("chunk: expected (chunkno, jO0, iO0, jO1, iO1)")
+        if out is None:
+            out = torch.empty(self.hspecI.size, dtype=torch.float64, device="cuda")
+        if not (hasattr(out, "is_cuda") and out.is_cuda and out.dtype == torch.float64 and out.is_contiguous()):
+            raise _einval("out: the mask is written to a contiguous torch.float64 CUDA tensor of %d cells" % self.hspecI.size)
+        s = torch.cuda.current_stream(out.device).cuda_stream
+        check(lib().ibh_global_ec_chunk_mask(self._h, *[int(x) for x in chunk[1:]], C.c_void_p(out.data_ptr()), out.numel(), C.c_void_p(s)))
+        return out
+
+
+def run_chunk(scan, chunk, hspecA, hspecI2, ec_skip, ofname=None, names=MATRIX_NAMES, correctA=True, sigma=(0., 0., 0.), Achar=None,
+              eq_rad=6371000.):
+    """One chunk of global_ec (--runchunk, global_ec.cpp:818-861): the chunk's mask, new_gcmA_standard on hspecA with the
+    classes of the WHOLE globe's ice (scan.ec_range), and global_ec_section through write_matrices into "%s-%02d" % (ofname,
+    chunkno) (:529; ofname None: nothing is kept).  Achar defaults to "O" when hspecA is the scan's ocean grid (the `ocean`
+    option), else "A".  Returns write_matrices' {variable name: linear_Weighted}."""
+    import os
+    if len(chunk) == 2:
+        chunk = chunk[0]
+    mask = scan.chunk_mask(chunk)
+    lo, hi = scan.ec_range(ec_skip)
+    gcm = gcm_from_hntr(hspecA, scan.hspecI, mask, hcdefs(lo, hi, ec_skip), correctA, eq_rad)
+    if Achar is None:
+        O = scan.hspecO
+        Achar = "O" if (hspecA.im, hspecA.jm, hspecA.offi, hspecA.dlat) == (O.im, O.jm, O.offi, O.dlat) else "A"
+    # write_matrices always writes its file (it is global_ec_section); without a name the image goes to the null device
+    fname = os.devnull if ofname is None else "%s-%02d" % (ofname, int(chunk[0]))
+    return write_matrices(gcm, mask, hspecI2, fname, names, correctA, sigma, Achar)
+
+
+class CombinedWeighted(linear_Weighted):
+    """What combine_chunks returns: the combined matrix over {dimB_out, dimA_out} with the weights wM_out / Mw_out, and the
+    triplet stream it was summed from."""
+
+    def coo_sparse(self):
+        """(iB, iA, val): the reference's stream (combine_global_ec.cpp:217-227) in sparse indices, chunks in order, each chunk's
+        entries in stored row-major order; duplicates across chunks are NOT summed.  With shape, the base of
+        compute_EOpvAOp_merged."""
+        return self._stream
+
+
+def _combine(mats, scale, host=None):
+    """mats: the chunks' matrices in order; host: None (the handles' own sets) or [(dimB, dimA, extB, extA), ...]."""
+    n = len(mats)
+    if n == 0:
+        raise _einval("chunk_results: combine_chunks needs at least one chunk")
+    hs = (C.c_void_p * n)(*[m._h.value for m in mats])
+    nnz = sum(m.nnz for m in mats)
+    iB, iA, val = np.zeros(nnz, np.int64), np.zeros(nnz, np.int64), np.zeros(nnz)
+    dp = ext = keep = None
+    if host is not None:
+        keep = [np.ascontiguousarray(d, np.int64) for h_ in host for d in h_[:2]]
+        dp = (C.c_void_p * (2 * n))(*[ptr(d).value if len(d) else None for d in keep])
+        ext = np.asarray([e for h_ in host for e in h_[2:]], np.int64)
+    h = C.c_void_p()
+    check(lib().ibh_global_ec_combine_chunks(n, hs, dp, ptr(ext), int(bool(scale)), ptr(iB), ptr(iA), ptr(val), C.byref(h)))
+    w = CombinedWeighted(h)
+    w._stream = (iB, iA, val)
+    return w
+
+
+def _chunk_matrix(result, c, name):
+    for vn in (name, name.replace("A", "O")):
+        if vn in result:
+            return result[vn]
+    raise _einval("name: chunk %d holds no matrix %r (it has %s)" % (c, name, ", ".join(sorted(result))))
+
+
+def combine_chunks(chunk_results, name, scale=False):
+    """combine_chunks (combine_global_ec.cpp:94-262) for the matrix `name` ("EvA", ...; found under A -> O in the results of an
+    ocean run, :124-127).  chunk_results: run_chunk's results in chunk order.  The chunks' matrices, sets and weights are read
+    where they are, in HBM.  Returns a CombinedWeighted: dims = the first-seen numbering of the chunks' sets, wM / Mw = the
+    chunks' weights summed in chunk order, M = setFromTriplets of the stream (scale: values times 1/wM of their row), and
+    .coo_sparse() the stream itself."""
+    chunk_results = list(chunk_results)
+    return _combine([_chunk_matrix(r, c, name) for c, r in enumerate(chunk_results)], scale)
+
+
+def combine_chunk_files(ifnames, ofname, names=MATRIX_NAMES, scale=False):
+    """combine_global_ec's main loop: every matrix of `names` read from the chunk files `ifnames` (ncio), combined, and
+    written in the Eigen format under BvA, with A -> O when the files are an ocean run's (:124-127).  Returns {variable
+    name: CombinedWeighted}."""
+    from . import ncio
+    dss = [ncio.Dataset.read(f) for f in ifnames]
+    if not dss:
+        raise _einval("ifnames: combine_chunk_files needs at least one chunk file")
+    out, ds, written = {}, ncio.Dataset(), {}
+
+    def dim_name(letter, vname, to_sparse):
+        """dimB, shared by the matrices whose combined set is the same table; a matrix whose numbering differs gets its own."""
+        base = "dim" + letter
+        if not np.array_equal(written.setdefault(base, to_sparse), to_sparse):
+            base += "_" + vname
+            written[base] = to_sparse
+        return base
+
+    for name in names:
+        vname = name if name + ".info" in dss[0].variables else name.replace("A", "O")
+        mats, host = [], []
+        for c, d in enumerate(dss):
+            if vname + ".info" not in d.variables:
+                raise _einval("names: chunk file %s holds no matrix %r" % (ifnames[c], name))
+            w = linear_Weighted.nc_read(d, vname)
+            mats.append(w)
+            host.append((w._dims[0], w._dims[1], w._sparse_extents[0], w._sparse_extents[1]))
+        w = _combine(mats, scale, host)
+        w.ncio(ds, vname, (dim_name(vname[0], vname, w.dim(0)), dim_name(vname[2], vname, w.dim(1))))
+        out[vname] = w
+    ds.write(ofname)
+    return out

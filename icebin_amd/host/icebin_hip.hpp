@@ -1203,6 +1203,118 @@ inline void check_negative(linear::Weighted_Eigen const &mat, std::string const 
     if (neg) throw Exception(IBH_EINVAL, "Negative values found in matrix or weights for " + name);
 }
 
+// ---- global_ec in chunks: main() of modele/global_ec.cpp (:752-893) and combine_global_ec.cpp's combine_chunks (:94-262) ----
+namespace global_ec {
+
+/** {chunkno, jO0, iO0, jO1, iO1} (global_ec.cpp:892): the ocean cells [jO0 * imO + iO0, jO1 * imO + iO1) in row-major order. */
+typedef std::array<int, 5> Chunk;
+struct ChunkPlan {
+    std::vector<Chunk> chunks;
+    std::vector<long> nice;         // the count the reference prints (:891): the chunk's ice plus the cell that ended it
+};
+
+/** The global ice of main() (:762-816) on the device (ibh_global_ec_scan_create): the int16 planes FGICE1m / ZICETOP1m
+    [jmI, imI] on the host (uploaded once in their own width) or, with on_device, in HBM (read on `stream`; they outlive the
+    scan).  hspecI must nest in hspecO. */
+class IceScan {
+    ibh_global_ec_scan *h_ = nullptr;
+public:
+    HntrSpec const hspecO, hspecI;
+    IceScan(HntrSpec const &_hspecO, HntrSpec const &_hspecI, ArrayView<const int16_t> const &fgiceI, ArrayView<const int16_t> const &elevI,
+            bool on_device = false, void *stream = nullptr)
+        : hspecO(_hspecO), hspecI(_hspecI) {
+        if (fgiceI.size() != elevI.size()) throw Exception(IBH_EINVAL, "fgiceI / elevI: the planes differ in size");
+        check(ibh_global_ec_scan_create(hspecO.im, hspecO.jm, hspecO.offi, hspecO.dlat, hspecI.im, hspecI.jm, hspecI.offi, hspecI.dlat,
+                                        fgiceI.data, elevI.data, fgiceI.size(), IBH_HNTR_I16, on_device ? 1 : 0, stream, &h_));
+    }
+    IceScan(IceScan const &) = delete;
+    IceScan &operator=(IceScan const &) = delete;
+    ~IceScan() { if (h_) ibh_global_ec_scan_destroy(h_); }
+    ibh_global_ec_scan *handle() const { return h_; }
+    int mult_i() const { return hspecI.im / hspecO.im; }
+    int mult_j() const { return hspecI.jm / hspecO.jm; }
+    /** Hntr(17.17, hspecO, hspecI).regrid(const 1.0, fgiceI) (:778-780), [jmO * imO] */
+    std::vector<double> fgiceO() const {
+        std::vector<double> f((size_t)hspecO.size());
+        check(ibh_global_ec_scan_get(h_, nullptr, nullptr, nullptr, f.data(), nullptr));
+        return f;
+    }
+    /** the cells with fgiceI != 0 of every ocean cell's tile, [jmO * imO] */
+    std::vector<int> nice() const {
+        std::vector<int32_t> n((size_t)hspecO.size());
+        check(ibh_global_ec_scan_get(h_, nullptr, nullptr, nullptr, nullptr, n.data()));
+        return std::vector<int>(n.begin(), n.end());
+    }
+    /** the two arrays where they are, in HBM */
+    const double *fgiceO_device() const { const double *p; check(ibh_global_ec_scan_get(h_, &p, nullptr, nullptr, nullptr, nullptr)); return p; }
+    const int32_t *nice_device() const { const int32_t *p; check(ibh_global_ec_scan_get(h_, nullptr, &p, nullptr, nullptr, nullptr)); return p; }
+    /** elevI_range (:805-813) */
+    std::array<int16_t, 2> elevI_range() const {
+        std::array<int16_t, 2> r;
+        check(ibh_global_ec_scan_get(h_, nullptr, nullptr, r.data(), nullptr, nullptr));
+        return r;
+    }
+    /** args.ec_range (:815-816): the same for every chunk */
+    std::array<double, 2> ec_range(double ec_skip) const {
+        std::array<double, 2> out;
+        check(ibh_global_ec_ec_range(elevI_range().data(), ec_skip, out.data()));
+        return out;
+    }
+};
+
+/** The chunk plan (:863-893; ibh_global_ec_chunk_plan): chunk_size must exceed mult_i * mult_j. */
+inline ChunkPlan chunk_plan(IceScan const &scan, long chunk_size = 12000000) {
+    int32_t n = 0;
+    check(ibh_global_ec_chunk_plan(scan.handle(), chunk_size, 0, nullptr, nullptr, &n));
+    std::vector<int32_t> ch(5 * (size_t)n);
+    std::vector<int64_t> nice((size_t)n);
+    check(ibh_global_ec_chunk_plan(scan.handle(), chunk_size, n, ch.data(), nice.data(), &n));
+    ChunkPlan plan;
+    for (size_t c = 0; c < (size_t)n; ++c) plan.chunks.push_back({{ch[5 * c], ch[5 * c + 1], ch[5 * c + 2], ch[5 * c + 3], ch[5 * c + 4]}});
+    plan.nice.assign(nice.begin(), nice.end());
+    return plan;
+}
+
+/** A chunk's elevmaskI (:818-855) into a device array of hspecI.size() doubles, one launch on `stream`. */
+inline void chunk_mask(IceScan const &scan, Chunk const &chunk, double *d_elevmaskI, void *stream = nullptr) {
+    check(ibh_global_ec_chunk_mask(scan.handle(), chunk[1], chunk[2], chunk[3], chunk[4], d_elevmaskI, scan.hspecI.size(), stream));
+}
+/** The same, brought to the host (for new_gcmA_standard's host mask). */
+inline std::vector<double> chunk_mask(IceScan const &scan, Chunk const &chunk) {
+    std::vector<double> em((size_t)scan.hspecI.size());
+    check(ibh_global_ec_chunk_mask_host(scan.handle(), chunk[1], chunk[2], chunk[3], chunk[4], em.data(), (int64_t)em.size()));
+    return em;
+}
+
+/** What combine_chunks gives: the combined matrix over the first-seen numbering of the chunks' sets, with the chunks' weights
+    summed in chunk order, and the triplet stream it was summed from, in sparse indices (the reference's contract and
+    EOpvAOpBase's form). */
+struct CombinedChunks {
+    std::unique_ptr<linear::Weighted_Eigen> M;
+    std::vector<int64_t> iB, iA;
+    std::vector<double> val;
+};
+/** combine_chunks (combine_global_ec.cpp:94-262) for one matrix: the chunks' UNSCALED matrices in chunk order, read where they
+    are, in HBM (ibh_global_ec_combine_chunks). */
+inline CombinedChunks combine_chunks(std::vector<linear::Weighted const *> const &mats, bool scale = false) {
+    std::vector<const ibh_weighted *> hs;
+    size_t nnz = 0;
+    for (linear::Weighted const *m : mats) {
+        if (!m) throw Exception(IBH_EINVAL, "mats: null chunk matrix");
+        hs.push_back(m->handle());
+        nnz += (size_t)m->nnz();
+    }
+    CombinedChunks out;
+    out.iB.resize(nnz); out.iA.resize(nnz); out.val.resize(nnz);
+    ibh_weighted *w = nullptr;
+    check(ibh_global_ec_combine_chunks((int32_t)hs.size(), hs.data(), nullptr, nullptr, scale ? 1 : 0, out.iB.data(), out.iA.data(),
+                                       out.val.data(), &w));
+    out.M.reset(new linear::Weighted_Eigen(w));
+    return out;
+}
+
+}   // namespace global_ec
+
 // ---- modele/GCMRegridder_ModelE.hpp ------------------------------------------------------------------
 /** make_hntrA (modele/hntr.cpp:232-241): the atmosphere grid is exactly twice as coarse as the ocean grid. */
 inline HntrSpec make_hntrA(HntrSpec const &hntrO) {

@@ -450,6 +450,73 @@ int ibh_weighted_make_I2vX(const ibh_weighted *IvX, const ibh_hntr *hIvI2, doubl
                            ibh_sparse_set *dimI2, ibh_weighted **out);
 
 /* ------------------------------------------------------------------------- */
+/* global_ec in chunks: main() of modele/global_ec.cpp below "Check that I grid fits neatly into O grid" (:752-893) and
+ * combine_chunks of modele/combine_global_ec.cpp (:94-262).  The ocean grid O and the ice grid I nest: imI % imO == 0 and
+ * jmI % jmO == 0, else IBH_EINVAL "Hntr grid (%dx%d) must be an even multiple of (%dx%d)" (:752-760); mult_i = imI / imO,
+ * mult_j = jmI / jmO, O cell k = jO * imO + iO owns the ice cells jI in [jO * mult_j, (jO + 1) * mult_j), iI in
+ * [iO * mult_i, (iO + 1) * mult_i).  Every entry validates its arguments before it touches a device. */
+typedef struct ibh_global_ec_scan ibh_global_ec_scan;
+/* The ice scan (:762-813).  fgiceI / elevI: the int16 planes FGICE1m / ZICETOP1m [jmI, imI] (plane_type must be
+ * IBH_HNTR_I16, nplane = imI * jmI), on the host (on_device = 0: uploaded once in their own width and kept by the scan) or
+ * on the device (on_device = 1: read on `stream`, and they outlive the scan).  Left on the device:
+ *   fgiceO[nO]  = Hntr(17.17, hspecO, hspecI).regrid(const 1.0, fgiceI) (:778-780), bitwise ibh_hntr_regrid_typed_device
+ *   nice[nO]    = the number of cells with fgiceI != 0 in the O cell's tile (the count of :881-884)
+ *   elevI_range = {min, max} of elevI over the cells with fgiceI != 0, from {10000, -10000} (:805-813)
+ * nice and the range come from one pass over both planes with integer atomics, so they are exact.  Waits for the device. */
+int ibh_global_ec_scan_create(int32_t imO, int32_t jmO, double offiO, double dlatO, int32_t imI, int32_t jmI, double offiI, double dlatI,
+                              const void *fgiceI, const void *elevI, int64_t nplane, int plane_type, int on_device, void *stream,
+                              ibh_global_ec_scan **out);
+/* Frees what the scan holds of :763-803: the regridded fgiceO, the counts, and the copies of host planes (never the caller's). */
+int ibh_global_ec_scan_destroy(ibh_global_ec_scan *s);
+/* What the scan holds of :762-816; every output may be NULL.  d_fgiceO / d_nice: the device arrays fgiceO (:778-780) and the tile
+ * counts (:881-884), valid as long as the scan; elevI_range[2] (:805-813); fgiceO / nice: host copies [nO]. */
+int ibh_global_ec_scan_get(const ibh_global_ec_scan *s, const double **d_fgiceO, const int32_t **d_nice, int16_t *elevI_range, double *fgiceO,
+                           int32_t *nice);
+/* fgiceO (:778-780) and the tile counts (:881-884) copied device to device into the caller's arrays [nO] (either may be NULL), on
+ * `stream`; only enqueues. */
+int ibh_global_ec_scan_copy_device(const ibh_global_ec_scan *s, double *d_fgiceO, int32_t *d_nice, void *stream);
+/* ec_range = {ec_skip * floor(min / ec_skip), ec_skip * ceil(max / ec_skip)} in double (:815-816).  Host only. */
+int ibh_global_ec_ec_range(const int16_t *elevI_range, double ec_skip, double *ec_range /* [2] */);
+/* The chunk plan (:863-893) over c[k] = fgiceO[k] != 0 ? nice[k] : 0, k row-major.  Chunk n starts where chunk n - 1 ended and
+ * ends, exclusive, at the first k >= start whose running sum of c from start, that cell included, is >= chunk_size (the cell
+ * itself goes to the next chunk -- goto endscan2 does not advance iO -- while its ice is in this chunk's reported nice), or at
+ * nO.  chunks[5 * n] = {chunkno, jO0, iO0, jO1, iO1}, the last bound (jmO, 0); nice[n] the reported count; *nchunks the number
+ * of chunks there are, of which the first min(cap, *nchunks) are written (chunks / nice may be NULL).  No ice: one chunk with
+ * nice = 0.  chunk_size must exceed mult_i * mult_j, else IBH_EINVAL: a full O cell would reach a smaller chunk_size on its
+ * own, the chunk would end where it starts, and the reference loops forever.  The masking and the scan run on the device and
+ * the nO + 1 sums are read back once per scan; the walk is host code. */
+int ibh_global_ec_chunk_plan(ibh_global_ec_scan *s, int64_t chunk_size, int32_t cap, int32_t *chunks, int64_t *nice, int32_t *nchunks);
+/* The walk of :863-893 over host counts c[nO] (each in [0, mult_i * mult_j]; c[k] stands for the count of :881-884 where
+ * fgiceO(jO, iO) != 0, :878, and is 0 elsewhere), with the same rules and outputs.  Host only, no device needed. */
+int ibh_global_ec_chunk_plan_counts(int32_t imO, int32_t jmO, int32_t mult_i, int32_t mult_j, const int32_t *counts, int64_t chunk_size,
+                                    int32_t cap, int32_t *chunks, int64_t *nice, int32_t *nchunks);
+/* A chunk's mask (:818-855) into the device array d_elevmaskI [nI]: (double)elevI where the cell's O cell k lies in
+ * [jO0 * imO + iO0, jO1 * imO + iO1), fgiceO[k] != 0 and fgiceI != 0, else NaN.  One launch on `stream`; only enqueues. */
+int ibh_global_ec_chunk_mask(const ibh_global_ec_scan *s, int32_t jO0, int32_t iO0, int32_t jO1, int32_t iO1, double *d_elevmaskI,
+                             int64_t nmask, void *stream);
+/* elevmaskI of :818-855 for the same chunk into the HOST array elevmaskI [nI] (a device array of the call's own, one download).
+ * Waits for the device. */
+int ibh_global_ec_chunk_mask_host(const ibh_global_ec_scan *s, int32_t jO0, int32_t iO0, int32_t jO1, int32_t iO1, double *elevmaskI,
+                                  int64_t nmask);
+/* combine_chunks (combine_global_ec.cpp:94-262) for one matrix BvA: mats[c] is chunk c's UNSCALED matrix (a scaled one is
+ * IBH_EINVAL) with its weights wM_c / Mw_c; its sets dimB_c / dimA_c are the first nrow / ncol entries of the handle's own
+ * dims, or -- with dims_host -- the host arrays dims_host[2 * c], dims_host[2 * c + 1] over the sparse extents
+ * extents[2 * c], extents[2 * c + 1] (matrices read back from files); such an array that names a sparse index twice is
+ * IBH_EINVAL, as a set cannot.  Chunks whose sparse extents disagree are IBH_EINVAL.
+ *   dimB_out = the first-seen numbering of the stream dimB_c[i], c ascending then i < len(wM_c) ascending; dimA_out alike
+ *   wM_out[d] = the sum from 0.0, in chunk order, of the wM_c[i] that name d (:197-200); Mw_out alike (:247-249)
+ *   sM_s      = 1 / the same sum (:152-174)
+ *   stream    = (dimB_c[row], dimA_c[col], scale ? v * sM_s[dimB_c[row]] : v), chunks in order, a chunk's entries in stored
+ *               row-major order (:217-227); written to the host arrays stream_iB / stream_iA / stream_val [sum of nnz_c]
+ *               (all three or none), the reference's contract and the base of ibh_modele_merge_EOpvAOp
+ *   *out      = setFromTriplets of that stream over {dimB_out, dimA_out} (duplicates across chunks summed in stream order),
+ *               with wM_out / Mw_out as its weights, scaled = scale, conservative = the AND of the chunks' flags; it owns
+ *               its two sets.
+ * The iE % 12960 locality check (:229-245) is tied to one grid and is not made.  Waits for the device. */
+int ibh_global_ec_combine_chunks(int32_t nchunks, const ibh_weighted *const *mats, const int64_t *const *dims_host, const int64_t *extents,
+                                 int scale, int64_t *stream_iB, int64_t *stream_iA, double *stream_val, ibh_weighted **out);
+
+/* ------------------------------------------------------------------------- */
 /* ModelE's regridder: GCMRegridder_ModelE::regrid_matrices (slib/icebin/modele/GCMRegridder_ModelE.cpp:487-571).  rmO holds
  * the matrices on ModelE's OCEAN grid O = HntrSpec(imO, jmO, offiO, dlatO); the atmosphere grid A is make_hntrA(O) =
  * HntrSpec(imO/2, jmO/2, offiO/2, 2*dlatO) (modele/hntr.cpp:232-241).  foceanAOp / foceanAOm [nO], sparse O indexing: the
