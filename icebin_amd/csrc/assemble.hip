@@ -610,7 +610,7 @@ static Bands build_bands(const ibh_weighted *w, const RgView &rg, const int64_t 
 // ---- smoothing (sigma != 0): M <- smoothI * M  (smoother.cpp:8-99, RegridMatrices_Dynamic.cpp:237-248) ------
 // smoothI[i,j] = exp(-.5 d2(i,j)) * area_j / sum_j(...) over the unmasked ice cells j of dimI with
 // d2 = sum_k ((c_j[k]-c_i[k])/sigma[k])^2 < 4, c = (x, y, elevation), area = wM.  The reference finds
-// neighbours with an RTree; here: uniform bins of 2*sigma_x x 2*sigma_y, 3x3 bins searched per cell.
+// neighbours with an RTree; here: uniform bins a margin wider than 2*sigma_x x 2*sigma_y (smooth_plan.h), 3x3 bins searched per cell.
 // Everything downstream reuses the assembly machinery: neighbour triplets -> sort by (i,j) -> row
 // denominators (sequential) -> products with the rows of M as contributions -> sort by (i,a) ->
 // sequential sums.  exp() is the device library's: entries agree with the oracle to rounding, not bitwise.
@@ -634,12 +634,17 @@ __device__ __forceinline__ int smooth_bin(const SmoothView &v, const double c[3]
     by = by < 0 ? 0 : by >= v.nby ? v.nby - 1 : by;
     return by * v.nbx + bx;
 }
-__global__ void k_smooth_bin_count(SmoothView v, uint32_t *__restrict__ bincnt, int *__restrict__ bad) {
+// bad: SMOOTH_NO_BAD unless an unmasked row has no area; bad_cell: the smallest SPARSE index of such a row -- the reference walks the
+// cells in ascending index and names the first (smoother.cpp:83-90); dense rows are numbered first-seen, in another order
+__global__ void k_smooth_bin_count(SmoothView v, uint32_t *__restrict__ bincnt, int *__restrict__ bad, unsigned long long *__restrict__ bad_cell) {
     const int d = blockIdx.x * blockDim.x + threadIdx.x;
     if (d >= v.n) return;
     double c[3];
     if (!smooth_tuple(v, d, c)) return;
-    if (v.area[d] == 0.0) atomicMin(bad, d);          // "Area of cell %ld must be non-zero", smoother.cpp:89-90
+    if (v.area[d] == 0.0) {                           // "Area of cell %ld must be non-zero", smoother.cpp:89-90
+        atomicMin(bad, d);
+        atomicMin(bad_cell, (unsigned long long)v.row_s[d]);
+    }
     atomicAdd(&bincnt[smooth_bin(v, c)], 1u);
 }
 // the members of every bin in ascending dense row: key = bin (nbins: masked, sorted past the last bin), value = row, ordered by
@@ -1117,7 +1122,8 @@ struct SmoothBins {
     const uint32_t *binstart;   // [nbins + 1]: the bins' first member positions
     const int32_t *members;     // [binstart[nbins]] unmasked rows, bin by bin, ascending in a bin
     uint32_t *d_cnt;            // four words a form reads back at once: three of its own, and the smallest dense row whose area is zero
-    const int64_t *row_s;       // (SMOOTH_NO_BAD: none)
+                                // (SMOOTH_NO_BAD: none); behind them, read only on that failure:
+    const unsigned long long *bad_cell;     // the smallest sparse index of a row whose area is zero
 };
 struct SmoothedCsr {
     DevBuf<int32_t> rowptr, colind;
@@ -1125,11 +1131,12 @@ struct SmoothedCsr {
     int64_t nnz = 0;
     bool shared = false;        // the ranks of a communicator built it together
 };
-// "Area of cell %ld must be non-zero", smoother.cpp:89-90: d = the fourth counter word, as a form's first read-back brought it
-static void fail_zero_area(const int64_t *row_s, int d) {
+// "Area of cell %ld must be non-zero", smoother.cpp:89-90: d = the fourth counter word, as a form's first read-back brought it; the
+// cell named is the reference's, the one with the smallest index
+static void fail_zero_area(const SmoothBins &B, int d) {
     if (d == SMOOTH_NO_BAD) return;
-    int64_t sc = 0;
-    IBH_HIP(hipMemcpy(&sc, row_s + d, sizeof(int64_t), hipMemcpyDeviceToHost));
+    unsigned long long sc = 0;
+    IBH_HIP(hipMemcpy(&sc, B.bad_cell, sizeof(sc), hipMemcpyDeviceToHost));
     fail(IBH_EINVAL, "Area of cell %ld must be non-zero", (long)sc);
 }
 // bin count -> scan -> keys -> sort
@@ -1141,18 +1148,20 @@ static SmoothBins smooth_bins(const ibh_weighted *w, const ibh_regrid_matrices *
     SmoothBins B{};
     B.v = SmoothView{row_s, rm->elevmaskI.p, g->I_centroid.p, w->wM.p, n, sigma[0], sigma[1], sigma[2], sg.x0, sg.y0, sg.bw, sg.bh, sg.nbx, sg.nby};
     B.nbins = sg.nbins();
-    B.row_s = row_s;
     const size_t nbins = B.nbins;
     uint32_t *binstart = A.get<uint32_t>(nbins + 1);
     uint64_t *bkeys = A.get<uint64_t>((size_t)n), *bkeys2 = A.get<uint64_t>((size_t)n);
     uint32_t *brows = A.get<uint32_t>((size_t)n), *brows2 = A.get<uint32_t>((size_t)n);
-    B.d_cnt = A.get<uint32_t>(4);
+    B.d_cnt = A.get<uint32_t>(6);                   // (the arena aligns to 256 bytes: words 4, 5 hold a 64-bit value)
     int *d_bad = reinterpret_cast<int *>(B.d_cnt + 3);
+    unsigned long long *d_bad_cell = reinterpret_cast<unsigned long long *>(B.d_cnt + 4);
+    B.bad_cell = d_bad_cell;
     const int big = SMOOTH_NO_BAD;
     IBH_HIP(hipMemsetAsync(binstart, 0, sizeof(uint32_t) * (nbins + 1), st));
     IBH_HIP(hipMemcpyAsync(d_bad, &big, sizeof(int), hipMemcpyHostToDevice, st));
+    IBH_HIP(hipMemsetAsync(d_bad_cell, 0xff, sizeof(unsigned long long), st));
     const dim3 grid(ceil_div(n, T));
-    hipLaunchKernelGGL(k_smooth_bin_count, grid, dim3(T), 0, st, B.v, binstart, d_bad);
+    hipLaunchKernelGGL(k_smooth_bin_count, grid, dim3(T), 0, st, B.v, binstart, d_bad, d_bad_cell);
     exclusive_scan_u32(binstart, binstart, nbins + 1, nullptr, st);
     hipLaunchKernelGGL(k_smooth_bin_keys, grid, dim3(T), 0, st, B.v, (uint32_t)nbins, bkeys, brows);
     const KeyField bf{0, bits_for((uint64_t)nbins + 1)};
@@ -1191,7 +1200,7 @@ static bool smt_tables(const SmoothBins &B, const ibh_weighted *w, ibh_comm *com
     exclusive_scan_u32(t->binwaves, t->wstart, nbins, B.d_cnt, st);
     IBH_HIP(hipMemcpyAsync(B.d_cnt + 2, B.binstart + nbins, sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
     readback_sync(h4, B.d_cnt, sizeof(h4), st);
-    fail_zero_area(B.row_s, (int)h4[3]);
+    fail_zero_area(B, (int)h4[3]);
     if (comm && comm_world(comm) > 1) {
         const int world = comm_world(comm);
         double *d_fl = A.get<double>((size_t)world);
@@ -1338,7 +1347,7 @@ static bool smooth_by_rows(const SmoothBins &B, const ibh_weighted *w, hipStream
     exclusive_scan_u32(rowlen, reinterpret_cast<uint32_t *>(r.rowptr.p), (size_t)n, B.d_cnt, st);
     uint32_t hd[4];
     readback_sync(hd, B.d_cnt, sizeof(hd), st);
-    fail_zero_area(B.row_s, (int)hd[3]);
+    fail_zero_area(B, (int)hd[3]);
     if (hd[1] != 0) return false;
     const uint32_t nnz2 = hd[0];
     IBH_CHECK(nnz2 < (1u << 31), "smoothed matrix too large (%u entries)", nnz2);
@@ -1363,7 +1372,7 @@ static bool smooth_by_triplets(const SmoothBins &B, const ibh_weighted *w, hipSt
     uint32_t h[4];
     IBH_HIP(hipMemcpyAsync(h, B.d_cnt, sizeof(h), hipMemcpyDeviceToHost, st));
     IBH_HIP(hipStreamSynchronize(st));
-    fail_zero_area(B.row_s, (int)h[3]);
+    fail_zero_area(B, (int)h[3]);
     const size_t ns = h[0];
     IBH_CHECK(ns < (1ul << 31), "smoothing matrix too large (%zu entries)", ns);
     uint64_t *sk = A.get<uint64_t>(ns), *sk2 = A.get<uint64_t>(ns);
@@ -1410,7 +1419,10 @@ static void commit_smoothed(ibh_weighted *w, SmoothedCsr *out, SmoothForm form, 
 static void smooth_matrix(ibh_weighted *w, const ibh_regrid_matrices *rm, const int64_t *row_s, const double sigma[3],
                           hipStream_t st, ibh_comm *comm = nullptr) {
     smooth_check(rm, sigma);
-    if (w->nrow == 0) return;
+    if (w->nrow == 0) {             // nothing to smooth, no form runs; still conservative = !smooth (RegridMatrices_Dynamic.cpp:167)
+        w->conservative = 0;
+        return;
+    }
     const SmoothPlan plan = plan_smooth(w->nrow, rm->rg->cmin, rm->rg->cmax, sigma);
     const SmoothBins B = smooth_bins(w, rm, row_s, plan.grid, sigma, st);
     SmoothedCsr out;

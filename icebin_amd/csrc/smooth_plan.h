@@ -20,19 +20,30 @@ constexpr int SMT_KMAX = 128, SMT_ROWMAX = 8, SMT_HASH = 1024;
 constexpr int SMOOTH_MAX_BINS = 4096;       // per axis
 struct SmtCand { double x, y, z, area; };   // a candidate as the tile kernel stages it
 
-// ---- the bins: 2 sigma_x x 2 sigma_y over the centroids' bounding box, never finer than SMOOTH_MAX_BINS per axis ---------------
+// ---- the bins: a margin wider than 2 sigma_x x 2 sigma_y over the centroids' bounding box, never finer than SMOOTH_MAX_BINS per
+// axis.  Every form searches the 3 x 3 bins around a row, so two coordinates a, b that the smoother takes for neighbours must fall at
+// most one bin apart.  Neighbours have fl((b - a) / sigma) < 2, hence b - a < 2 sigma exactly (2 sigma is a double and rounding is
+// monotone).  A bin is t(c) = fl(fl(c - x0) / bw), truncated: both roundings are relative to their result, and the result is at most
+// the number of bins, so |t(c) - (c - x0) / bw| <= 2.01 * 2^-53 * SMOOTH_MAX_BINS = 9.2e-13, however far the grid lies from the plane's
+// origin.  With bw = 2 sigma (1 + m):  t(b) - t(a) < 1 / (1 + m) + 1.9e-12, which is below 1 -- truncation then separates the two by
+// at most one bin -- once m > 1.9e-12.  With bins of exactly two sigmas (m = 0) it is not: a pair 2 sigma (1 - 4e-16) apart, astride
+// a bin edge, was seen two bins apart and dropped.  m = 1e-9 leaves a factor of 500 and costs nothing; the width of the capped
+// branch takes the same margin, so bins only grow on every branch (and the far corner, at SMOOTH_MAX_BINS / (1 + m), stays inside).
+constexpr double SMOOTH_BIN_MARGIN = 1e-9;
 struct SmoothGrid {
     double x0 = 0, y0 = 0, bw = 1, bh = 1;
     int nbx = 1, nby = 1;
     size_t nbins() const { return (size_t)nbx * nby; }
 };
+inline double smooth_bin_width(double extent, double sigma) {
+    return std::max(2.0 * sigma, extent / (double)SMOOTH_MAX_BINS) * (1.0 + SMOOTH_BIN_MARGIN);
+}
 inline SmoothGrid smooth_grid(const double cmin[2], const double cmax[2], const double sigma[3]) {
     SmoothGrid g;
-    g.x0 = cmin[0]; g.y0 = cmin[1]; g.bw = 2.0 * sigma[0]; g.bh = 2.0 * sigma[1];
+    g.x0 = cmin[0]; g.y0 = cmin[1];
+    g.bw = smooth_bin_width(cmax[0] - cmin[0], sigma[0]); g.bh = smooth_bin_width(cmax[1] - cmin[1], sigma[1]);
     g.nbx = (int)std::min((double)SMOOTH_MAX_BINS, std::floor((cmax[0] - cmin[0]) / g.bw) + 1.0);
     g.nby = (int)std::min((double)SMOOTH_MAX_BINS, std::floor((cmax[1] - cmin[1]) / g.bh) + 1.0);
-    if (g.nbx == SMOOTH_MAX_BINS) g.bw = (cmax[0] - cmin[0]) / (double)SMOOTH_MAX_BINS * (1 + 1e-12);    // bins only grow
-    if (g.nby == SMOOTH_MAX_BINS) g.bh = (cmax[1] - cmin[1]) / (double)SMOOTH_MAX_BINS * (1 + 1e-12);
     return g;
 }
 

@@ -1,8 +1,9 @@
 // The decisions of a smoothed build (icebin_amd/csrc/smooth_plan.h): the bin geometry with its cap, the order of the device forms for
 // every knob setting on both sides of the row threshold, the LDS layout of the tile kernel, and the split of a shared tile build among
-// the ranks -- which otherwise runs only inside multi-process GPU tests at worlds 2 and 3.  Expected values are written out here from
-// smooth_matrix as it stood before the plan existed (the *_before functions are that code's arithmetic, line by line); the properties
-// are what the kernels rely on.  Host code only: its own get_tuning, no HIP.
+// the ranks -- which otherwise runs only inside multi-process GPU tests at worlds 2 and 3.  Expected values are written out here: the
+// bin geometry from its definition (grid_expected), the rest from smooth_matrix as it stood before the plan existed (the *_before
+// functions are that code's arithmetic, line by line); the properties are what the kernels rely on.  Host code only: its own
+// get_tuning, no HIP.
 #include "../../icebin_amd/csrc/smooth_plan.h"
 
 #include <cstdio>
@@ -23,13 +24,16 @@ static int g_failed = 0;
 #define CHECK(c) do { if (!(c)) { if (g_failed < 50) printf("FAILED line %d: %s\n", __LINE__, #c); ++g_failed; } } while (0)
 
 // ---- the bins ----------------------------------------------------------------------------------------------------------------------
-struct GridBefore { double x0, y0, bw, bh; int nbx, nby; };
-static GridBefore grid_before(const double cmin[2], const double cmax[2], const double sigma[3]) {
-    GridBefore v{cmin[0], cmin[1], 2.0 * sigma[0], 2.0 * sigma[1], 1, 1};
-    v.nbx = (int)std::min(4096.0, std::floor((cmax[0] - cmin[0]) / v.bw) + 1.0);
-    v.nby = (int)std::min(4096.0, std::floor((cmax[1] - cmin[1]) / v.bh) + 1.0);
-    if (v.nbx == 4096) v.bw = (cmax[0] - cmin[0]) / 4096.0 * (1 + 1e-12);
-    if (v.nby == 4096) v.bh = (cmax[1] - cmin[1]) / 4096.0 * (1 + 1e-12);
+// The expected geometry, written out: bins two sigmas wide over the bounding box, regrown to extent / 4096 where that is wider (the
+// cap), and on either branch wider by the margin that keeps neighbours within one bin of each other (smooth_plan.h states the argument).
+// Before the margin the widths were exactly 2 sigma, or extent / 4096 * (1 + 1e-12) when the uncapped count reached 4096 -- which on
+// the cap's edge, an extent of [4095, 4096) bin widths, was up to 1/4096 NARROWER than two sigmas.
+struct GridExpected { double x0, y0, bw, bh; int nbx, nby; };
+static GridExpected grid_expected(const double cmin[2], const double cmax[2], const double sigma[3]) {
+    const double ex = cmax[0] - cmin[0], ey = cmax[1] - cmin[1];
+    GridExpected v{cmin[0], cmin[1], std::max(2.0 * sigma[0], ex / 4096.0) * (1.0 + 1e-9), std::max(2.0 * sigma[1], ey / 4096.0) * (1.0 + 1e-9), 1, 1};
+    v.nbx = (int)std::min(4096.0, std::floor(ex / v.bw) + 1.0);
+    v.nby = (int)std::min(4096.0, std::floor(ey / v.bh) + 1.0);
     return v;
 }
 // the unclamped bin of a coordinate, as smooth_bin forms it on the device
@@ -37,14 +41,12 @@ static int bin_of(double c, double c0, double width) { return (int)((c - c0) / w
 static void check_grid(double x0, double y0, double ex, double ey, double sx, double sy, int want_nbx = 0, int want_nby = 0) {
     const double cmin[2] = {x0, y0}, cmax[2] = {x0 + ex, y0 + ey}, sigma[3] = {sx, sy, 100.0};
     const SmoothGrid g = smooth_grid(cmin, cmax, sigma);
-    const GridBefore b = grid_before(cmin, cmax, sigma);
+    const GridExpected b = grid_expected(cmin, cmax, sigma);
     CHECK(g.x0 == b.x0 && g.y0 == b.y0 && g.bw == b.bw && g.bh == b.bh && g.nbx == b.nbx && g.nby == b.nby);
     CHECK(g.nbx >= 1 && g.nbx <= 4096 && g.nby >= 1 && g.nby <= 4096 && g.nbins() == (size_t)g.nbx * g.nby);
-    // bins only grow, so that 3 x 3 bins hold everything within two sigmas -- except on the cap's edge: an extent of [4095, 4096) bin
-    // widths gives 4096 bins uncapped, and the capped width, extent / 4096, is then up to 1/4096 narrower than two sigmas.  That is the
-    // arithmetic as it was before the plan (a finding, kept: this header changes no result)
-    if (g.nbx < 4096 || ex / (2.0 * sx) >= 4096.0) CHECK(g.bw >= 2.0 * sx);
-    if (g.nby < 4096 || ey / (2.0 * sy) >= 4096.0) CHECK(g.bh >= 2.0 * sy);
+    // bins only grow, on every branch, so that 3 x 3 bins hold everything within two sigmas; and by no more than the margin or the cap
+    CHECK(g.bw > 2.0 * sx && g.bh > 2.0 * sy);
+    CHECK(g.bw <= std::max(2.0 * sx, (cmax[0] - cmin[0]) / 4096.0) * (1 + 2e-9) && g.bh <= std::max(2.0 * sy, (cmax[1] - cmin[1]) / 4096.0) * (1 + 2e-9));
     CHECK(bin_of(cmin[0], g.x0, g.bw) == 0 && bin_of(cmin[1], g.y0, g.bh) == 0);
     // the far corner falls inside the grid before clamping -- by construction where the cap is not active, by the (1 + 1e-12) where it is
     CHECK(bin_of(cmax[0], g.x0, g.bw) < g.nbx && bin_of(cmax[1], g.y0, g.bh) < g.nby);
@@ -56,9 +58,11 @@ static void check_grid(double x0, double y0, double ex, double ey, double sx, do
 static void test_grid() {
     check_grid(0, 0, 0, 0, 50e3, 50e3, 1, 1);                       // zero extent
     check_grid(-3e5, 2e5, 99e3, 1e3, 50e3, 50e3, 1, 1);             // smaller than one bin
-    check_grid(0, 0, 100e3, 300e3, 50e3, 50e3, 2, 4);               // exact multiples of the bin width: the far edge opens a bin
+    check_grid(0, 0, 100e3, 300e3, 50e3, 50e3, 1, 3);               // exact multiples of two sigmas: the margin keeps the far edge in the last bin
+    check_grid(0, 0, 100e3 + 1.0, 300e3 + 1.0, 50e3, 50e3, 2, 4);   // just beyond: it opens one
     check_grid(25e3, 25e3, 1450e3, 2750e3, 60e3, 60e3, 13, 23);     // the 50 km test grid
-    check_grid(0, 0, 4095 * 100e3, 4094 * 100e3, 50e3, 50e3, 4096, 4095);      // the last sizes below the cap
+    check_grid(0, 0, 4095 * 100e3, 4094 * 100e3, 50e3, 50e3, 4095, 4094);      // the last sizes below the cap
+    check_grid(0, 0, 4095.5 * 100e3, 4096 * 100e3, 50e3, 50e3, 4096, 4096);    // 4096 bins uncapped (two sigmas wide), and the cap's first size
     check_grid(0, 0, 4096 * 100e3, 10e3, 50e3, 50e3, 4096, 1);      // the cap in x only
     check_grid(0, 0, 10e3, 1e9, 50e3, 50e3, 1, 4096);               // in y only
     check_grid(-1e9, -1e9, 3e9, 5e9, 10.0, 20.0, 4096, 4096);       // in both
@@ -71,6 +75,39 @@ static void test_grid() {
         check_grid((u(rng) - .5) * 1e7, (u(rng) - .5) * 1e7, ex, ey, sx, sy);
         check_grid(0, 0, std::floor(ex / (2 * sx)) * 2 * sx, std::floor(ey / (2 * sy)) * 2 * sy, sx, sy);      // multiples of the width
     }
+}
+
+// two coordinates the smoother takes for neighbours -- fl((b - a) / sigma) < 2 -- fall at most one bin apart: the pair that bins of exactly
+// two sigmas put two apart, and pairs just under two sigmas apart a few ulps around every kind of bin edge, on grids far from the origin
+static void test_neighbours_one_bin_apart() {
+    {
+        const double cmin[2] = {-1234500.0, 0}, cmax[2] = {215500.0, 1e5}, sigma[3] = {50e3, 50e3, 1e6};
+        const double a = -234500.0000000001, b = -134500.00000000012;
+        CHECK((b - a) / sigma[0] < 2.0);
+        CHECK(bin_of(b, cmin[0], 2.0 * sigma[0]) - bin_of(a, cmin[0], 2.0 * sigma[0]) == 2);      // (the bins before the margin)
+        const SmoothGrid g = smooth_grid(cmin, cmax, sigma);
+        CHECK(bin_of(b, g.x0, g.bw) - bin_of(a, g.x0, g.bw) <= 1);
+    }
+    std::mt19937_64 rng(23);
+    std::uniform_real_distribution<double> u(0.0, 1.0);
+    long tried = 0;
+    for (int k = 0; k < 4000; ++k) {
+        const double sx = std::pow(10.0, 1.0 + 4.0 * u(rng)), ext = sx * std::pow(10.0, 4.6 * u(rng));
+        const double x0 = (u(rng) - .5) * std::pow(10.0, 3.0 + 7.0 * u(rng));
+        const double cmin[2] = {x0, 0}, cmax[2] = {x0 + ext, 1.0}, sigma[3] = {sx, 1.0, 1.0};
+        const SmoothGrid g = smooth_grid(cmin, cmax, sigma);
+        for (int t = 0; t < 32; ++t) {
+            const int e = 1 + (int)(rng() % (uint64_t)std::max(g.nbx, 2));
+            double a = x0 + e * (rng() % 2 ? 2.0 * sx : g.bw);       // an edge of the old bins, or of the new ones
+            for (int s = (int)(rng() % 5); s > 0; --s) a = std::nextafter(a, rng() % 2 ? -1e300 : 1e300);
+            double b = a + std::nextafter(2.0 * sx, 0.0);
+            for (int s = (int)(rng() % 3); s > 0; --s) b = std::nextafter(b, -1e300);
+            if (a < x0 || b > x0 + ext || !((b - a) / sx < 2.0)) continue;
+            ++tried;
+            CHECK(bin_of(b, g.x0, g.bw) - bin_of(a, g.x0, g.bw) <= 1);
+        }
+    }
+    CHECK(tried > 10000);
 }
 
 // ---- the forms ---------------------------------------------------------------------------------------------------------------------
@@ -271,6 +308,7 @@ static void test_shares() {
 
 int main() {
     test_grid();
+    test_neighbours_one_bin_apart();
     test_plan();
     test_lds();
     test_shares();

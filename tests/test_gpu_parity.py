@@ -1354,8 +1354,8 @@ def test_smoothing_sigma_nonzero(name):
     g, em, mm, rg = setup("g20")
     sigma = (60e3, 60e3, 250.0)
     # The form that builds each leg, from the CPU (tests/smoothing_cases.py).  IvA: 18 columns around the widest bin, the tile legs run
-    # the tiles.  IvE at 20 km: 146 columns around the widest bin, more than SMT_KMAX = 128 -- the column tables overflow and the
-    # smooth_tile = 1 legs are served by the triplet pipeline (the tiles are checked against the oracle at 50 km, where IvE has 127:
+    # the tiles.  IvE at 20 km: 145 columns around the widest bin, more than SMT_KMAX = 128 -- the column tables overflow and the
+    # smooth_tile = 1 legs are served by the triplet pipeline (the tiles are checked against the oracle at 50 km, where IvE has 125:
     # test_smoothing_forms_and_their_fallthroughs).
     _, _, widest, longest, longest_smoothed = smc.oracle_case("g20", name, sigma)
     tile_form = {"IvA": smc.TILE, "IvE": smc.TRIPLET}[name]
@@ -1442,7 +1442,7 @@ def check_smoothing_leg(mm, sigma, name, knobs, form, same_as, assert_form=True)
 
 @pytest.mark.parametrize("leg", range(len(smc.G50_LEGS)), ids=["%s-%dkm-%d%d" % (l[1], l[0][0] / 1e3, l[2][0], l[2][1]) for l in smc.G50_LEGS])
 def test_smoothing_forms_and_their_fallthroughs(leg):
-    # 50 km (793 rows): the tile form at the edge of its column table (IvE, 127 of SMT_KMAX = 128 columns: the raised-LDS launch), the
+    # 50 km (793 rows): the tile form at the edge of its column table (IvE, 125 of SMT_KMAX = 128 columns: the raised-LDS launch), the
     # tiles overflowing into the direct form, both overflowing into the triplet pipeline, and the tiles serving IvA at a sigma where
     # they cannot serve IvE -- each against the oracle; a fall-through is bitwise the build that asks for the serving form alone
     g, em = smc.grids("g50")

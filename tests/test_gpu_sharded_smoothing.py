@@ -325,7 +325,7 @@ def test_shared_smoothed_build_is_the_single_rank_build_bitwise(world):
 def test_smoothed_build_forms_on_two_ranks():
     """20 km: the direct form by size and the triplet pipeline (smooth_tile = smooth_direct = 0) run on every rank (built_fast 1),
     the tile form forced (smooth_tile = 1) is shared (3); every result bitwise the single-rank build.  50 km, sigma = (120 km,
-    120 km, 400 m), smooth_tile = 1: the tiles serve IvA (45 columns around the widest bin) shared, while IvE (347 > SMT_KMAX) makes
+    120 km, 400 m), smooth_tile = 1: the tiles serve IvA (45 columns around the widest bin) shared, while IvE (365 > SMT_KMAX) makes
     both ranks step down together to the redundant triplet build (built_fast 1).  Which side of the limits each input lies on is
     asserted here, on the CPU, before any rank starts."""
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
