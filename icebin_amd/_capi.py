@@ -130,6 +130,8 @@ _SIGS = {
     "ibh_modele_matrices_create": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_void_p,
                                             C.c_void_p, C.c_int64, C.POINTER(C.c_void_p)]),
     "ibh_modele_matrices_matrix_d": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
+    "ibh_modele_matrices_matrix_d_sigma": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                                    C.POINTER(C.c_void_p)]),
     "ibh_modele_matrices_destroy": (C.c_int, [C.c_void_p]),
     "ibh_modele_agridA": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_double, C.POINTER(C.c_int32), C.c_void_p]),
     "ibh_modele_merge_EOpvAOp": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
@@ -152,6 +154,8 @@ _SIGS = {
                                        C.c_double, C.c_double, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]),
     "ibh_selftest_csr_product": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "ibh_selftest_compose_cols": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                           C.POINTER(C.c_void_p)]),
     "ibh_selftest_triplets": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                         C.POINTER(C.c_void_p), C.c_void_p]),
     "ibh_selftest_csr_op": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64,
@@ -243,6 +247,7 @@ _SIGS = {
     "ibh_set_launch_events": (C.c_int, [C.c_void_p, C.c_void_p]),
     "ibh_weighted_built_fast": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "ibh_weighted_smoothed_by": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    "ibh_weighted_composed_by": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "ibh_weighted_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
     "ibh_weighted_last_launch": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
     "ibh_set_tuning": (C.c_int, [C.c_char_p, C.c_int]),

@@ -745,6 +745,9 @@ int ibh_weighted_built_fast(const ibh_weighted *w, int *out) {
 int ibh_weighted_smoothed_by(const ibh_weighted *w, int *out) {
     return guarded([&] { IBH_CHECK(w && out, "null argument"); *out = w->smoothed_by; });
 }
+int ibh_weighted_composed_by(const ibh_weighted *w, int *out) {
+    return guarded([&] { IBH_CHECK(w && out, "null argument"); *out = w->composed_by; });
+}
 int ibh_selftest_sort(const uint64_t *keys, int64_t n, int lo_bits, int hi_bits, uint32_t *perm_out, int *path_out) {
     return guarded([&] {
         IBH_CHECK(n >= 0 && n < (1ll << 31) && (n == 0 || (keys && perm_out)) && path_out, "bad arguments");

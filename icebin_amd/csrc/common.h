@@ -450,7 +450,8 @@ struct ibh_weighted {
     int conservative = 1, scaled = 1;
     int built_fast = 0;                 // assembled by the plan-based fast path (fastasm.inl); introspection only
     int smoothed_by = 0;                // the SmoothForm (smooth_plan.h) that smoothed it, 0: not smoothed; introspection only
-    ibh::ApplyKernel kernel_override = ibh::KERNEL_AUTO;     // SpMM dispatch (ibh_weighted_set_kernel)
+    int composed_by = 0;                // the ComposeForm (csrops.h) a to_modele matrix was composed by, 0: not composed; introspection only
+    ibh::ApplyKernel kernel_override = ibh::KERNEL_AUTO;    // SpMM dispatch (ibh_weighted_set_kernel)
     // E-row matrices over ice / exchange columns can get row groups, a column sweep or bands from their CSR (spmm.hip
     // build_structures): set by the matrix build, with how the row keys decode into (GCM cell, class)
     int band_eligible = 0;

@@ -19,6 +19,30 @@ void csr_product(const ibh_weighted &L, const ibh_weighted &R, ibh_weighted *out
 void crop_rows(const ibh_weighted &in, const int32_t *d_src, int nout, const double *d_rs, ibh_weighted *out, hipStream_t st);
 void crop_cols(const ibh_weighted &in, const int32_t *d_map, int ncol_out, const double *d_rs, const double *d_cs, ibh_weighted *out,
                hipStream_t st);
+// ---- crop_cols(L) * R where every row of R holds at most one entry (csrcompose.hip) ------------------------------
+// The I-row matrices of to_modele: R = XOmvXAm sends an O cell (or one of its elevation classes) to ONE atmosphere column, so the
+// product relabels the columns of each row of L and merges equal ones -- a row-local operation, no triplet stream, no global sort.
+// Per entry (i, p, v) of L: k = d_map[p] (dropped when k < 0 or row k of R is empty), c = R.colind[R.rowptr[k]],
+// t = ((d_rs ? d_rs[i] * v : v) * d_cs[k]) * R.val[R.rowptr[k]] (d_cs may be null as well), every product rounded.  Row i of the
+// result: columns c ascending, C(i, c) = its terms summed in ascending k, the first assigned -- the bits of crop_cols + csr_product.
+enum ComposeForm { COMPOSED_NONE = 0, COMPOSED_PRODUCT = 1, COMPOSED_ROWLOCAL = 2 };     // as ibh_weighted_composed_by reports them
+// Lanes that serve one row: a smoothed ice row holds 19-24 entries on average (8 unsmoothed), so half a wave takes a typical row
+// in one pass where a whole wave would idle two lanes in three.
+constexpr int COMPOSE_LANES = 32;
+// Entries of one row kept in LDS: the longest smoothed row measured is 44, so 128 leaves a factor of three, and the eight rows of
+// a workgroup then take 28 KiB -- five workgroups share a CU's 160 KiB.
+constexpr int COMPOSE_ROWCAP = 128;
+// "modele_rowlocal": 1 whenever the row-local form can serve, 0 never, -1 (default) for smoothed builds only -- unsmoothed rows hold
+// a few entries and stay where they were measured
+inline bool compose_rowlocal_wanted(bool smoothed) {
+    const int v = get_tuning("modele_rowlocal", -1);
+    return v > 0 || (v < 0 && smoothed);
+}
+// out's CSR by the row-local form when `rowlocal` and it can serve -- no row keeps more than COMPOSE_ROWCAP entries and no row of R
+// holds two, both found in its counting pass -- else by crop_cols + csr_product; returns the form that built it.  d_map: L.ncol
+// entries in [-1, R.nrow), one-to-one.  Resets the arena; two host waits (row-local) or those of the two pieces.
+ComposeForm compose_cols(const ibh_weighted &L, const int32_t *d_map, const double *d_rs, const double *d_cs, const ibh_weighted &R,
+                         bool rowlocal, ibh_weighted *out, hipStream_t st);
 // out's CSR = the transpose of in's (rows few and short: a matrix over the GCM grids); resets the arena
 void transpose_csr(const ibh_weighted &in, ibh_weighted *out, hipStream_t st);
 // row[e] = the row of entry e, one thread per row (short rows)

@@ -60,10 +60,12 @@ T *to_arena(const std::vector<T> &h, hipStream_t st) {
 template <class T>
 void upload(DevBuf<T> &b, const std::vector<T> &h, hipStream_t st) { b.alloc(h.size()); b.upload(h.data(), h.size(), st); }
 
-std::unique_ptr<ibh_weighted> o_matrix(const ibh_modele_matrices *mm, const char *name, ibh_sparse_set *d0, ibh_sparse_set *d1, int correctA) {
+// sigma: only compute_GpvXAm's IpvXOp takes the caller's (RegridMatrices_Dynamic.cpp:404-409); every other build is unsmoothed
+std::unique_ptr<ibh_weighted> o_matrix(const ibh_modele_matrices *mm, const char *name, ibh_sparse_set *d0, ibh_sparse_set *d1, int correctA,
+                                       const double *sigma = nullptr) {
     const double zero[3] = {0, 0, 0};
     ibh_weighted *w = nullptr;
-    assemble_matrix(mm->rmO, name, d0, d1, 0, correctA, zero, &w);
+    assemble_matrix(mm->rmO, name, d0, d1, 0, correctA, sigma ? sigma : zero, &w);
     return std::unique_ptr<ibh_weighted>(w);
 }
 }  // namespace
@@ -187,7 +189,8 @@ std::unique_ptr<ibh_weighted> raw_EOvEA(const ibh_hntr *hntr, double eq_rad, con
 
 namespace {
 // dimXAm, dimGp: the caller's sets (copies: the caller's own change only when the matrix is built).  XvG: true = XAmvGp.
-void modele_matrix(const ibh_modele_matrices *mm, char gridX, char gridG, bool XvG, int scale, ibh_sparse_set &dimXAm,
+// sigma (null: none): GpvXAm's smoothing, which goes to the one O-grid build of IpvXOp and to nothing else.
+void modele_matrix(const ibh_modele_matrices *mm, char gridX, char gridG, bool XvG, int scale, const double *sigma, ibh_sparse_set &dimXAm,
                    ibh_sparse_set &dimGp, ibh_weighted *ret) {
     hipStream_t st = hipStreamPerThread;
     const char nameAvG[4] = {'A', 'v', gridG, 0}, nameXvG[4] = {gridX, 'v', gridG, 0}, nameGvX[4] = {gridG, 'v', gridX, 0};
@@ -254,11 +257,11 @@ void modele_matrix(const ibh_modele_matrices *mm, char gridX, char gridG, bool X
         }
     }
     DevBuf<int32_t> d_map;
-    ibh_weighted cropped;
     const int nG = dimGp.n();
     if (XvG) {
         // M = diag(scale ? sXAm : wXAm * sXAm) * XAmvXOm * crop_mvp(dimXOm, dimXOp, 0, diag(1 / XOpvIp.wM) * XOpvIp.M)   (:346-365)
         DevBuf<double> sXOpvIp;
+        ibh_weighted cropped;
         recip(XOpvIp->wM.p, nXOp, sXOpvIp, st);
         upload(d_map, om2op, st);
         arena().reset();
@@ -272,19 +275,23 @@ void modele_matrix(const ibh_modele_matrices *mm, char gridX, char gridG, bool X
         scale_rows(XAmvXOm.rowptr.p, nXAm, ls, XAmvXOm.val.p, st);
         IBH_HIP(hipGetLastError());
         csr_product(XAmvXOm, cropped, ret, st);
+        ret->composed_by = COMPOSED_PRODUCT;
         ret->wM = std::move(wXAm);
         ret->Mw.alloc((size_t)nG);
         if (nG) IBH_HIP(hipMemcpyAsync(ret->Mw.p, XOpvIp->Mw.p, sizeof(double) * (size_t)nG, hipMemcpyDeviceToDevice, st));
     } else {
         // M = crop_mvp(dimXOm, dimXOp, 1, [diag(1 / IpvXOp.wM) *] IpvXOp.M) * diag(XAmvXOms) * XOmvXAm   (:402-430)
-        auto IpvXOp = o_matrix(mm, nameGvX, &dimGp, dimXOp, 0);
+        // (a smoothed IpvXOp keeps the rows and columns of the unsmoothed one: the smoother mixes rows of the same matrix)
+        auto IpvXOp = o_matrix(mm, nameGvX, &dimGp, dimXOp, 0, sigma);
         IBH_CHECK(IpvXOp->ncol == nXOp && IpvXOp->nrow == nG, "internal: %s added cells to a set the O-grid builds had numbered", nameGvX);
         DevBuf<double> sIpvXOp;
         if (scale) recip(IpvXOp->wM.p, nG, sIpvXOp, st);
         upload(d_map, op2om, st);
-        arena().reset();
-        crop_cols(*IpvXOp, d_map.p, nXOm, scale ? sIpvXOp.p : nullptr, XAmvXOms.p, &cropped, st);
-        csr_product(cropped, *XOmvXAm, ret, st);
+        // every row of XOmvXAm holds at most one entry (an O cell lies in one A cell; raw_EOvEA emits one pair per class), so
+        // the product is row-local; smoothed rows, tens of entries each, take that form (csrops.h)
+        ret->composed_by = compose_cols(*IpvXOp, d_map.p, scale ? sIpvXOp.p : nullptr, XAmvXOms.p, *XOmvXAm,
+                                        compose_rowlocal_wanted(sigma != nullptr), ret, st);
+        ret->smoothed_by = IpvXOp->smoothed_by;
         ret->wM.alloc((size_t)nG);
         if (nG) IBH_HIP(hipMemcpyAsync(ret->wM.p, XOpvIp->Mw.p, sizeof(double) * (size_t)nG, hipMemcpyDeviceToDevice, st));
         ret->Mw = std::move(wXAm);
@@ -314,8 +321,10 @@ void check_extent(const ibh_sparse_set *s, int64_t extent, const char *which) {
 }
 
 void modele_matrix_d(const ibh_modele_matrices *mm, const char *spec, ibh_sparse_set *dim0, ibh_sparse_set *dim1, int scale,
-                     ibh_weighted **out) {
+                     const double *sigma, ibh_weighted **out) {
     const Parsed p = parse_spec(spec);
+    // only compute_GpvXAm hands sigma on (RegridMatrices_Dynamic.cpp:404-409); compute_XAmvGp and compute_AOmvAAm never read it
+    if (!(sigma && sigma[0] != 0 && p.kind == 1)) sigma = nullptr;
     const ibh_regridder *rg = mm->rmO->rg;
     check_current_device(rg->device, "regridder");
     IBH_CHECK(dim0 == nullptr || dim0 != dim1, "dims[0] and dims[1] must be distinct sets");
@@ -340,7 +349,7 @@ void modele_matrix_d(const ibh_modele_matrices *mm, const char *spec, ibh_sparse
         w.reset(h);
     } else {
         w = new_weighted();
-        modele_matrix(mm, p.gridX, p.gridG, p.kind == 0, scale, *work[iX], *work[iG], w.get());
+        modele_matrix(mm, p.gridX, p.gridG, p.kind == 0, scale, sigma, *work[iX], *work[iG], w.get());
     }
     // built: the caller's sets take the numbering, the result names them (or owns the fresh ones).  AAmvAOm is hntr's
     // transpose, stored {dimAAm, dimAOm}: its sets go to the other slot each.
@@ -405,13 +414,17 @@ int ibh_modele_matrices_create(const ibh_regrid_matrices *rmO, int32_t imO, int3
     if (out) *out = nullptr;
     return guarded([&] { modele_create(rmO, imO, jmO, offiO, dlatO, eq_rad, foceanAOp, foceanAOm, nO, out); });
 }
-int ibh_modele_matrices_matrix_d(const ibh_modele_matrices *mm, const char *spec, ibh_sparse_set *dim0, ibh_sparse_set *dim1, int scale,
-                                 ibh_weighted **out) {
+int ibh_modele_matrices_matrix_d_sigma(const ibh_modele_matrices *mm, const char *spec, ibh_sparse_set *dim0, ibh_sparse_set *dim1, int scale,
+                                       const double sigma[3], ibh_weighted **out) {
     if (out) *out = nullptr;
     return guarded([&] {
         IBH_CHECK(mm && spec && out, "null argument");
-        modele_matrix_d(mm, spec, dim0, dim1, scale, out);
+        modele_matrix_d(mm, spec, dim0, dim1, scale, sigma, out);
     });
+}
+int ibh_modele_matrices_matrix_d(const ibh_modele_matrices *mm, const char *spec, ibh_sparse_set *dim0, ibh_sparse_set *dim1, int scale,
+                                 ibh_weighted **out) {
+    return ibh_modele_matrices_matrix_d_sigma(mm, spec, dim0, dim1, scale, nullptr, out);
 }
 int ibh_modele_matrices_destroy(ibh_modele_matrices *mm) { delete mm; return IBH_OK; }
 int ibh_modele_agridA(const ibh_regridder *rgO, int32_t imO, int32_t jmO, double offiO, double dlatO, int32_t *nA_dense,

@@ -407,6 +407,7 @@ cdef class GCMRegridder_ModelE:
         raise NotImplementedError("wA on the ModelE regridder is not supported")
 
     def regrid_matrices(self, str sheet_name, elevmaskI, bool scale=True, bool correctA=True, sigma=(0, 0, 0), conserve=True):
+        """sigma: kept by the result, whose matrix(name) smooths IvA / IvE with it (RegridMatrices_Dynamic.cpp:425-437)."""
         cdef double[::1] em = np.ascontiguousarray(np.asarray(elevmaskI, np.float64).reshape(-1))
         cdef cicebin.RegridMatrices *crm = cicebin.new_regrid_matrices_modele(
             self.cself, sheet_name.encode(), &em[0] if em.shape[0] else NULL, em.shape[0], scale, correctA,

@@ -1337,14 +1337,14 @@ public:
     RegridMatrices_ModelE(RegridMatrices_ModelE const &) = delete;
     RegridMatrices_ModelE &operator=(RegridMatrices_ModelE const &) = delete;
 
-    /** matrix_d(spec_name, dims, params): params.correctA is ignored, as compute_XAmvGp / compute_GpvXAm ignore it; dims may
-        be pre-populated, are appended to and must outlive the result. */
+    /** matrix_d(spec_name, dims, params): params.correctA is ignored, as compute_XAmvGp / compute_GpvXAm ignore it; params.sigma
+        smooths IvA / IvE (the coupler's IvE, IceCoupler.cpp:461-463), is ignored by AvI EvI AvX EvX and refused for XvA / XvE
+        (ibh_modele_matrices_matrix_d_sigma); dims may be pre-populated, are appended to and must outlive the result. */
     std::unique_ptr<linear::Weighted_Eigen> matrix_d(std::string const &spec_name, std::array<SparseSetT *, 2> dims,
                                                      RegridParams const &params) const {
-        if (params.smooth()) throw Exception(IBH_ENOTIMPL, "smoothing through the ModelE regridder is not supported");
         ibh_weighted *w = nullptr;
-        check(ibh_modele_matrices_matrix_d(h_, spec_name.c_str(), dims[0] ? dims[0]->handle() : nullptr,
-                                           dims[1] ? dims[1]->handle() : nullptr, params.scale, &w));
+        check(ibh_modele_matrices_matrix_d_sigma(h_, spec_name.c_str(), dims[0] ? dims[0]->handle() : nullptr,
+                                                 dims[1] ? dims[1]->handle() : nullptr, params.scale, params.sigma.data(), &w));
         return std::unique_ptr<linear::Weighted_Eigen>(new linear::Weighted_Eigen(w));
     }
     std::unique_ptr<linear::Weighted> matrix(std::string const &spec_name) const override {
@@ -1746,13 +1746,14 @@ public:
     }
 
     /** regrid_matrices(sheet_index, foceanAOp, foceanAOm, elevmaskI, params) (GCMRegridder_ModelE.hpp:180-186): the arrays are
-        copied. */
+        copied.  The O-grid matrices are made with a zero sigma; params.sigma stays with the result, whose matrix(name) passes it
+        per call (RegridMatrices_Dynamic.cpp:425-437). */
     std::unique_ptr<RegridMatrices_ModelE> regrid_matrices(int sheet_index, ArrayView<const double> const &foceanAOp,
                                                            ArrayView<const double> const &foceanAOm,
                                                            ArrayView<const double> const &elevmaskI,
                                                            RegridParams const &params = RegridParams()) const {
         if (foceanAOp.size() != foceanAOm.size()) throw Exception(IBH_EINVAL, "foceanAOp and foceanAOm differ in length");
-        auto rmO = gcmO->regrid_matrices(sheet_index, elevmaskI, params);
+        auto rmO = gcmO->regrid_matrices(sheet_index, elevmaskI, RegridParams(params.scale, params.correctA, {{0., 0., 0.}}));
         ibh_modele_matrices *h = nullptr;
         check(ibh_modele_matrices_create(rmO->handle(), hspecO_.im, hspecO_.jm, hspecO_.offi, hspecO_.dlat, eq_rad_, foceanAOp.data,
                                          foceanAOm.data, foceanAOp.size(), &h));

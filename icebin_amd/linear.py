@@ -427,6 +427,13 @@ class linear_Weighted:
         check(lib().ibh_weighted_smoothed_by(self._h, C.byref(v)))
         return v.value
 
+    def composed_by(self):
+        """How a to_modele matrix was composed: 0 not composed, 1 the generic sparse product, 2 the row-local form
+        (ibh_weighted_composed_by)."""
+        v = C.c_int()
+        check(lib().ibh_weighted_composed_by(self._h, C.byref(v)))
+        return v.value
+
     def last_kernel(self):
         buf = C.create_string_buffer(32)
         check(lib().ibh_weighted_last_kernel(self._h, buf, 32))

@@ -31,10 +31,11 @@ class RegridMatrices_ModelE:
     """The RegridMatrices_Dynamic that GCMRegridder_ModelE::regrid_matrices returns: matrix() / matrix_d() over
     AvI EvI AvX EvX IvA IvE XvA XvE, the aliases EAmvIp AAmvIp IpvEAm IpvAAm and the test matrices AOmvAAm / AAmvAOm."""
 
-    def __init__(self, handle, keep, scale):
+    def __init__(self, handle, keep, scale, sigma=(0., 0., 0.)):
         self._h = handle
         self._keep = keep
         self._scale = bool(scale)
+        self._sigma = tuple(float(s) for s in sigma)
 
     def __del__(self):
         try:
@@ -44,18 +45,21 @@ class RegridMatrices_ModelE:
         self._h = None
 
     def matrix(self, spec_name):
-        """Own dims, the scale the object was made with (_icebin.pyx:56-75)."""
-        return self.matrix_d(spec_name, scale=self._scale)
+        """Own dims, the scale and the sigma the object was made with (_icebin.pyx:56-75; RegridMatrices_Dynamic.cpp:425-437)."""
+        return self.matrix_d(spec_name, scale=self._scale, sigma=self._sigma)
 
     def matrix_d(self, spec_name, dims=(None, None), scale=True, correctA=False, sigma=(0., 0., 0.)):
         """matrix_d(spec, dims, RegridParams(scale, correctA, sigma)): correctA is ignored, as compute_XAmvGp and
-        compute_GpvXAm ignore it; sigma must be zero."""
-        if np.any(np.asarray(sigma, np.float64) != 0):
-            raise NotImplementedError("smoothing through to_modele is not supported")
+        compute_GpvXAm ignore it.  sigma smooths IvA / IvE (IpvAAm / IpvEAm) -- it goes to the O-grid build of IpvXOp alone, as
+        in compute_GpvXAm --, is ignored by AvI EvI AvX EvX and the test matrices, and is refused for XvA / XvE
+        (ibh_modele_matrices_matrix_d_sigma)."""
+        sg = np.ascontiguousarray(sigma, np.float64).reshape(-1)
+        if len(sg) != 3:
+            raise ValueError("sigma has %d values, not 3" % len(sg))
         h = C.c_void_p()
         d0 = dims[0]._h if dims[0] is not None else None
         d1 = dims[1]._h if dims[1] is not None else None
-        check(lib().ibh_modele_matrices_matrix_d(self._h, spec_name.encode(), d0, d1, int(scale), C.byref(h)))
+        check(lib().ibh_modele_matrices_matrix_d_sigma(self._h, spec_name.encode(), d0, d1, int(scale), ptr(sg), C.byref(h)))
         return linear_Weighted(h, keep=(self, dims))
 
 
@@ -459,15 +463,15 @@ class GCMRegridder_ModelE:
         raise NotImplementedError("wA on the ModelE regridder is not supported")
 
     def regrid_matrices(self, sheet_name, elevmaskI, scale=True, correctA=True, sigma=(0, 0, 0), conserve=True):
-        """_icebin.pyx:164-175 on the ModelE regridder."""
-        if np.any(np.asarray(sigma, np.float64) != 0):
-            raise NotImplementedError("smoothing through to_modele is not supported")
-        rmO = self.gcmO.regrid_matrices(sheet_name, elevmaskI, scale=scale, correctA=correctA, sigma=sigma, conserve=conserve)
+        """_icebin.pyx:164-175 on the ModelE regridder.  The O-grid matrices are made with a zero sigma; the caller's is kept,
+        and matrix() passes it per call, as the reference's matrix(name) uses the params the object was made with
+        (RegridMatrices_Dynamic.cpp:425-437)."""
+        rmO = self.gcmO.regrid_matrices(sheet_name, elevmaskI, scale=scale, correctA=correctA, sigma=(0, 0, 0), conserve=conserve)
         o = self.hspecO
         h = C.c_void_p()
         check(lib().ibh_modele_matrices_create(rmO._h, o.im, o.jm, float(o.offi), float(o.dlat), self.eq_rad, ptr(self.foceanOp),
                                               ptr(self.foceanOm), len(self.foceanOp), C.byref(h)))
-        return RegridMatrices_ModelE(h, keep=(rmO, self), scale=scale)
+        return RegridMatrices_ModelE(h, keep=(rmO, self), scale=scale, sigma=sigma)
 
 
 def to_modele(gcmO, focean=None, hspecO=None, eq_rad=None, global_ec=None):

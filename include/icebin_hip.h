@@ -541,6 +541,20 @@ int ibh_modele_matrices_create(const ibh_regrid_matrices *rmO, int32_t imO, int3
  * overlap below 1e-8 in magnitude is IBH_EINVAL (topo.cpp:138-139).  On any error *out is NULL and both sets are as they were. */
 int ibh_modele_matrices_matrix_d(const ibh_modele_matrices *mm, const char *spec, ibh_sparse_set *dim0, ibh_sparse_set *dim1,
                                  int scale, ibh_weighted **out);
+/* matrix_d with RegridParams(scale, correctA, sigma): the coupler's smoothed IvE (IceCoupler.cpp:461-463).  sigma == NULL or
+ * sigma[0] == 0 is exactly ibh_modele_matrices_matrix_d, which is this entry with a zero sigma.  As in the reference, where of
+ * the builders behind matrix_d only compute_IvAE reads sigma (RegridMatrices_Dynamic.cpp:237-248) and compute_GpvXAm hands the
+ * caller's params to one O-grid build (:404-409): for IvA IvE IpvAAm IpvEAm sigma goes to the build of IpvXOp (scale = false,
+ * correctA = false) and to nothing else -- wM = XOpvIp.Mw and Mw = wXAm are those of sigma = 0, conservative stays 0; AvI EvI AvX
+ * EvX AOmvAAm AAmvAOm ignore it; XvA / XvE with a non-zero sigma are IBH_ENOTIMPL, the O-grid's own refusal (the smoother needs
+ * ice-grid centroids).  The smoother's checks come through unchanged: three positive sigmas and the ice grid's centroids, else
+ * IBH_EINVAL.  dim0 / dim1 as above, pre-populated sets and the identity dimI included; on any error both are as they were.
+ * The composition crop_mvp(IpvXOp) * diag * XOmvXAm of a smoothed build is row-local (every row of XOmvXAm holds at most one
+ * entry; ibh_set_tuning "modele_rowlocal": 1 whenever it can serve, also for sigma = 0; 0 never; -1 the default, smoothed builds
+ * only).  It declines a row of more than 128 kept entries to the generic product; the bits are the same either way.
+ * ibh_weighted_smoothed_by of the result reports the form that smoothed IpvXOp, ibh_weighted_composed_by the composition. */
+int ibh_modele_matrices_matrix_d_sigma(const ibh_modele_matrices *mm, const char *spec, ibh_sparse_set *dim0, ibh_sparse_set *dim1,
+                                       int scale, const double sigma[3], ibh_weighted **out);
 int ibh_modele_matrices_destroy(ibh_modele_matrices *mm);
 /* make_agridA (:57-78): the cells of A under the realised cells of rgO's grid, first-seen in Hntr's stream order.
  * *nA_dense is always set; to_sparse (may be NULL) receives that many indices (at most (imO/2)*(jmO/2)). */
@@ -645,6 +659,15 @@ int ibh_modele_make_topoA(const double *const *planesO /* [9] */, const int16_t 
  * ascending inside a row, L's columns = R's rows): C(r, c) sums L(r, k) * R(k, c) over k ascending, the first term assigned;
  * an entry exists wherever a term does.  Identity dims, wM = Mw = 0, flags of L.  Used by tests/test_gpu_modele.py. */
 int ibh_selftest_csr_product(const ibh_weighted *L, const ibh_weighted *R, ibh_weighted **out);
+/* Diagnostic: the composition of the I-row ModelE matrices alone, crop_cols(L) * R, by one named form: 1 crop_cols + the product
+ * above, 2 the row-local kernel.  Host arrays: map[nmap = L's columns] into [-1, R's rows), one-to-one (-1: the entry is dropped);
+ * rs[L's rows] and cs[R's rows], either may be NULL.  Per entry (i, p, v) of L with k = map[p] >= 0 and a non-empty row k of R:
+ * the term ((rs ? rs[i] * v : v) [* cs[k]]) * R(k, c) for each entry c of that row, every product rounded; C(i, c) sums its
+ * terms in ascending k, the first assigned.  Form 2 serves an R whose rows hold at most one entry and rows of at most 128 kept
+ * entries; otherwise it leaves the build to form 1, and ibh_weighted_composed_by of *out tells which form built it.  Identity dims,
+ * wM = Mw = 0, flags of L.  Every argument is checked before a device is touched.  Used by tests/test_gpu_compose_cols.py. */
+int ibh_selftest_compose_cols(const ibh_weighted *L, const int32_t *map, int64_t nmap, const double *rs, const double *cs,
+                              const ibh_weighted *R, int form, ibh_weighted **out);
 /* Diagnostic: the shared triplets -> CSR build (Eigen setFromTriplets: duplicates summed in input order, the first term
  * assigned) on n host triplets with dense ids, and the plain weights as a matrix build takes them.  mode 0: local disorder
  * is expected, as ibh_weighted_from_coo; mode 1: it is not (the ice-row builds: per-row slots, the optimistic row-only sort).
@@ -1020,9 +1043,13 @@ int ibh_weighted_built_fast(const ibh_weighted *w, int *out);
  * "smooth_direct" (1 always, 0 never, -1 by size: "smooth_direct_max_rows") admit them; a form whose tables overflow leaves the build
  * to the next one.  Same structure from every form, entries to rounding.  Introspection only. */
 int ibh_weighted_smoothed_by(const ibh_weighted *w, int *out);
+/* How a matrix of ibh_modele_matrices_matrix_d[_sigma] was composed: 0 not composed (any other matrix, AOmvAAm / AAmvAOm), 1 the
+ * generic sparse product, 2 the row-local form (IvA IvE XvA XvE of a smoothed build, or under ibh_set_tuning("modele_rowlocal", 1)).
+ * Same bits from both.  Introspection only. */
+int ibh_weighted_composed_by(const ibh_weighted *w, int *out);
 /* PROCESS-WIDE launch-heuristic overrides for measurements and tests -- experiments only; a product caller that needs a knob sets it
  * on the handle (ibh_weighted_set_option).  (README.md lists the keys: assemble_fast, assemble_fast_eva,
- * assemble_range_shape, assemble_stream_count, assemble_static_count, rowgroup_*, rowone*, rowblock_*, shortrow_*, sweep_*,
+ * assemble_range_shape, assemble_stream_count, assemble_static_count, modele_rowlocal, rowgroup_*, rowone*, rowblock_*, shortrow_*, sweep_*,
  * lazy_structures ...).  No key changes a result beyond the documented tolerance of the kernel it selects; the assembly keys
  * change no bit.  value INT32_MIN: back to the built-in default. */
 int ibh_set_tuning(const char *key, int value);
