@@ -1315,6 +1315,67 @@ inline CombinedChunks combine_chunks(std::vector<linear::Weighted const *> const
 
 }   // namespace global_ec
 
+// ---- modele/etopo1_ice.cpp:45-247 --------------------------------------------------------------------
+/** The grids of one etopo1_ice (ibh_etopo1_ice_create): the row areas of hspecI and hspecC and, with hspecH, the regridder of
+    store_h (:22), on the current HIP device.  hspecI must nest in hspecC, a coarse cell holding at most IBH_ETOPO1_MAX_TILE
+    fine cells.  Owns a device handle: not copyable. */
+class Etopo1IceGrids {
+    ibh_etopo1_ice *h_ = nullptr;
+public:
+    HntrSpec const hspecI, hspecC, hspecH;      // hspecH.im == 0: no h planes
+    Etopo1IceGrids(HntrSpec const &_hspecI, HntrSpec const &_hspecC, HntrSpec const *_hspecH = nullptr)
+        : hspecI(_hspecI), hspecC(_hspecC), hspecH(_hspecH ? *_hspecH : HntrSpec(0, 0, 0., 0.)) {
+        check(ibh_etopo1_ice_create(&h_, hspecI.im, hspecI.jm, hspecI.offi, hspecI.dlat, hspecC.im, hspecC.jm, hspecH.im, hspecH.jm,
+                                    hspecH.offi, hspecH.dlat));
+    }
+    Etopo1IceGrids(Etopo1IceGrids const &) = delete;
+    Etopo1IceGrids &operator=(Etopo1IceGrids const &) = delete;
+    ~Etopo1IceGrids() { if (h_) ibh_etopo1_ice_destroy(h_); }
+    ibh_etopo1_ice *handle() const { return h_; }
+    bool has_h() const { return hspecH.im != 0; }
+    /** The planes where they are, in HBM: a pure enqueue on `stream` (ibh_etopo1_ice_device).  d_planes_h: the four h planes
+        FOCEANh, FGICEh, ZICETOPh, ZSOLGh, ldh doubles apart, or nullptr. */
+    void run_device(const int16_t *d_focean, const int16_t *d_zictop, const int16_t *d_zsolid, const double *d_fgiceC, bool include_greenland,
+                    int16_t *d_FOCEAN1m, int16_t *d_FGICE1m, int16_t *d_ZICETOP1m, int16_t *d_ZSOLG1m, double *d_planes_h = nullptr, long ldh = 0,
+                    void *stream = nullptr) const {
+        check(ibh_etopo1_ice_device(h_, d_focean, d_zictop, d_zsolid, d_fgiceC, include_greenland ? 1 : 0, d_FOCEAN1m, d_FGICE1m, d_ZICETOP1m,
+                                    d_ZSOLG1m, d_planes_h, ldh, stream));
+    }
+};
+
+/** What etopo1_ice writes to <root>1m.nc and <root>h.nc, as arrays: the int16 planes [jmI * imI] and the double h planes
+    [jmH * imH] (empty without hspecH). */
+struct Etopo1Ice {
+    std::vector<int16_t> FOCEAN1m, FGICE1m, ZICETOP1m, ZSOLG1m;
+    std::vector<double> FOCEANh, FGICEh, ZICETOPh, ZSOLGh;
+};
+
+/** etopo1_ice(files, include_greenland, ofname_root) (etopo1_ice.cpp:45-247) from host arrays instead of files
+    (ibh_etopo1_ice_host): focean / zictop / zsolid are the file's FOCEAN / ZICTOP / ZSOLID [jmI * imI], fgiceC its FGICE1
+    [jmC * imC]; every plane crosses PCIe once in its own width.  hspecH: the grid of the h planes, nullptr for none. */
+inline Etopo1Ice etopo1_ice(HntrSpec const &hspecI, HntrSpec const &hspecC, ArrayView<const int16_t> const &focean,
+                            ArrayView<const int16_t> const &zictop, ArrayView<const int16_t> const &zsolid, ArrayView<const double> const &fgiceC,
+                            bool include_greenland = false, HntrSpec const *hspecH = nullptr) {
+    if (focean.size() != hspecI.size() || zictop.size() != hspecI.size() || zsolid.size() != hspecI.size())
+        throw Exception(IBH_EINVAL, "focean / zictop / zsolid: a plane does not hold the " + std::to_string(hspecI.size()) + " cells of hspecI");
+    if (fgiceC.size() != hspecC.size())
+        throw Exception(IBH_EINVAL, "fgiceC: the plane does not hold the " + std::to_string(hspecC.size()) + " cells of hspecC");
+    Etopo1IceGrids grids(hspecI, hspecC, hspecH);
+    Etopo1Ice out;
+    const size_t nI = (size_t)hspecI.size(), nH = hspecH ? (size_t)hspecH->size() : 0;
+    out.FOCEAN1m.resize(nI); out.FGICE1m.resize(nI); out.ZICETOP1m.resize(nI); out.ZSOLG1m.resize(nI);
+    std::vector<double> planes_h(4 * nH);
+    check(ibh_etopo1_ice_host(grids.handle(), focean.data, zictop.data, zsolid.data, fgiceC.data, include_greenland ? 1 : 0, out.FOCEAN1m.data(),
+                              out.FGICE1m.data(), out.ZICETOP1m.data(), out.ZSOLG1m.data(), nH ? planes_h.data() : nullptr, (int64_t)nH));
+    if (nH) {
+        out.FOCEANh.assign(planes_h.begin(), planes_h.begin() + (long)nH);
+        out.FGICEh.assign(planes_h.begin() + (long)nH, planes_h.begin() + 2 * (long)nH);
+        out.ZICETOPh.assign(planes_h.begin() + 2 * (long)nH, planes_h.begin() + 3 * (long)nH);
+        out.ZSOLGh.assign(planes_h.begin() + 3 * (long)nH, planes_h.end());
+    }
+    return out;
+}
+
 // ---- modele/GCMRegridder_ModelE.hpp ------------------------------------------------------------------
 /** make_hntrA (modele/hntr.cpp:232-241): the atmosphere grid is exactly twice as coarse as the ocean grid. */
 inline HntrSpec make_hntrA(HntrSpec const &hntrO) {

@@ -517,6 +517,49 @@ int ibh_global_ec_combine_chunks(int32_t nchunks, const ibh_weighted *const *mat
                                  int scale, int64_t *stream_iB, int64_t *stream_iA, double *stream_val, ibh_weighted **out);
 
 /* ------------------------------------------------------------------------- */
+/* etopo1_ice: etopo1_ice(files, include_greenland, ofname_root) of modele/etopo1_ice.cpp (:45-247) from arrays instead of
+ * files.  The fine grid I (the reference's g1mx1m) and the coarse grid C of the ice fractions (g1x1) nest: imI % imC == 0 and
+ * jmI % jmC == 0, mult_i = imI / imC, mult_j = jmI / jmC, coarse cell (j1, i1) owns the fine rows [j1 * mult_j, (j1 + 1) * mult_j)
+ * and columns [i1 * mult_i, (i1 + 1) * mult_i).  Planes are int16 [jmI, imI], i fastest.  In the reference's order, with C int
+ * arithmetic:
+ *   FGICE1m = 0 (:51-52); rows j >= (jmI * 14) / 15: FOCEAN == 0 -> 1 (:84-93); rows j < jmI / 2: FOCEAN == 0 and
+ *   ZICTOP - ZSOLID >= 50 -> 1 (:109-117); rows j >= jmI / 2, FOCEAN == 2 (Greenland): with include_greenland
+ *   ZICTOP - ZSOLID >= 50 -> 1, without it ZICETOP1m = ZSOLG1m = -300 (:121-140); elsewhere ZICETOP1m / ZSOLG1m are the inputs.
+ *   For j1 in [jmC / 2, jmC) and every i1 with fgiceC[j1, i1] != 0 (:166-209): the tile's cells with FOCEAN == 0 (the Greenland
+ *   clause of :179, `(include_greenland && focean) == 2`, is never true), ascending by (-ZICTOP, j, i) with the negation taken
+ *   in int (the reference's tuple narrows it to int16, undefined at -32768); remain = fgiceC * dxypC[j1]; along the sorted
+ *   cells, area = dxypI[j]: area <= remain -> remain -= area, FGICE1m = 1; else FGICE1m = 1 if remain >= area * .5, and stop.
+ *   The subtractions are one fp64 chain in that order.  NaN, negative and > 1 fractions take what these comparisons give.
+ *   Rows j >= jmI / 2, FOCEAN == 2 (:212-224): FOCEAN1m = include_greenland ? 0 : 1 (elsewhere the input), and the
+ *   TRANSPOSED cell (i, j) loses its ice (FGICE1m = 0) where the ocean mask the loop is rewriting reads 1 there: the new value
+ *   where FOCEAN[i, j] == 2, i >= jmI / 2 and i <= j (the loop has been there), the input elsewhere.  Where i >= jmI or
+ *   j >= imI the reference indexes outside its array; nothing is read or written there.
+ *   The h planes (store_h, :17-29): Hntr(17.17, hspecH, hspecI), constant weight 1.0, mean_polar, bitwise
+ *   ibh_hntr_regrid_typed_device of each output plane.
+ * A tile holds at most IBH_ETOPO1_MAX_TILE fine cells (its sort keys live in LDS), else IBH_EINVAL. */
+#define IBH_ETOPO1_MAX_TILE 8192
+typedef struct ibh_etopo1_ice ibh_etopo1_ice;
+/* The grids of one etopo1_ice (:22, :166-167): the row areas make_dxyp(hspecI) / make_dxyp(hspecC) and, with imH != 0, the
+ * regridder of store_h (:22) are made once and uploaded.  imH == jmH == 0: no h planes.  Shapes, nesting and the tile limit are
+ * checked before a device is looked for; the messages name both shapes.  Waits for the device. */
+int ibh_etopo1_ice_create(ibh_etopo1_ice **out, int32_t imI, int32_t jmI, double offiI, double dlatI, int32_t imC, int32_t jmC, int32_t imH,
+                          int32_t jmH, double offiH, double dlatH);
+/* Frees the tables of :22 and :166-167 (never a caller's plane). */
+int ibh_etopo1_ice_destroy(ibh_etopo1_ice *h);
+/* etopo1_ice (:45-247) on planes in HBM: inputs FOCEAN / ZICTOP / ZSOLID int16 [jmI * imI] and FGICE1 double [jmC * imC], never
+ * written; outputs four int16 planes [jmI * imI] and, with d_planes_h != NULL, the four h planes FOCEANh, FGICEh, ZICETOPh,
+ * ZSOLGh as doubles at d_planes_h + k * ldh (ldh >= imH * jmH).  A NULL plane, a misaligned one, an output that overlaps an
+ * input or another output, or h planes from a handle made without hspecH are IBH_EINVAL before a device is touched.  A pure
+ * enqueue on `stream`. */
+int ibh_etopo1_ice_device(const ibh_etopo1_ice *h, const int16_t *d_focean, const int16_t *d_zictop, const int16_t *d_zsolid, const double *d_fgiceC,
+                          int include_greenland, int16_t *d_FOCEAN1m, int16_t *d_FGICE1m, int16_t *d_ZICETOP1m, int16_t *d_ZSOLG1m, double *d_planes_h,
+                          int64_t ldh, void *stream);
+/* etopo1_ice (:45-247) on host arrays of the same shapes: every plane crosses PCIe once in its own width.  Waits for the device. */
+int ibh_etopo1_ice_host(const ibh_etopo1_ice *h, const int16_t *focean, const int16_t *zictop, const int16_t *zsolid, const double *fgiceC,
+                        int include_greenland, int16_t *FOCEAN1m, int16_t *FGICE1m, int16_t *ZICETOP1m, int16_t *ZSOLG1m, double *planes_h,
+                        int64_t ldh);
+
+/* ------------------------------------------------------------------------- */
 /* ModelE's regridder: GCMRegridder_ModelE::regrid_matrices (slib/icebin/modele/GCMRegridder_ModelE.cpp:487-571).  rmO holds
  * the matrices on ModelE's OCEAN grid O = HntrSpec(imO, jmO, offiO, dlatO); the atmosphere grid A is make_hntrA(O) =
  * HntrSpec(imO/2, jmO/2, offiO/2, 2*dlatO) (modele/hntr.cpp:232-241).  foceanAOp / foceanAOm [nO], sparse O indexing: the
