@@ -29,6 +29,7 @@
 #include <hip/hip_ext.h>
 #include <mutex>
 #include <set>
+#include <type_traits>
 
 namespace ibh {
 
@@ -149,6 +150,45 @@ __device__ __forceinline__ double xload(__amdgpu_buffer_rsrc_t rs, int byte_off)
     return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rs, byte_off, 0, 0));
 }
 
+// The tail batch of a row kernel: the last NU <= UNROLL slots of a wave's share of a staged segment, k = k0 + u * STEP < n
+// (k0 holds the lane).  Every lane issues its NU * FPW gathers before the first FMA; the weights are read from LDS when the
+// gathered values are consumed.  Slots below NU - 1 are full in every lane; in the last one the lanes past the end re-read the
+// last entry and are masked at the FMA (never multiplied by 0: 0*NaN must not leak into a row).
+template <int FPW, int NU, int STEP>
+__device__ __forceinline__ void tail_slots(const int *s_col, const double *s_val, const __amdgpu_buffer_rsrc_t (&rs)[FPW], int k0, int n,
+                                           double (&acc)[FPW]) {
+    double x[FPW][NU];
+#pragma unroll
+    for (int u = 0; u < NU; ++u) {
+        const int k = k0 + u * STEP;
+        const int off = s_col[u < NU - 1 || k < n ? k : n - 1] << 3;
+#pragma unroll
+        for (int j = 0; j < FPW; ++j) x[j][u] = xload(rs[j], off);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int u = 0; u < NU; ++u) {
+        const int k = k0 + u * STEP;
+        const bool ok = u < NU - 1 || k < n;
+        const double v = s_val[ok ? k : n - 1];
+#pragma unroll
+        for (int j = 0; j < FPW; ++j) acc[j] = ok ? fma(v, x[j][u], acc[j]) : acc[j];
+    }
+}
+// f(integral_constant<nu>) for a wave-uniform nu in 1..N.  A row issues only the slots that hold entries of it (the 5 km rows
+// need 11.0 of 14 on average, a one-entry row 1; the others re-read the last entry for nothing), and each count is its own
+// straight-line body: the wait in front of FMA u is then the constant NU - 1 - u, as it is in a full batch.  (Skipping slots
+// inside ONE unrolled body makes the first FMA wait for every load: leave the body early and the number of loads behind a slot
+// is no constant any more; enter it late -- the last nu slots, which keeps that number -- and the compiler, as built, still
+// waits vmcnt(0) per slot and spills the gathered values: 92 bytes of scratch in rowblock<1, 1, 14, 8>.)
+template <int N, class F>
+__device__ __forceinline__ void with_slot_count(int nu, F &&f) {
+    if constexpr (N > 1) {
+        if (nu < N) { with_slot_count<N - 1>(nu, f); return; }
+    }
+    f(std::integral_constant<int, N>{});
+}
+
 // Field batches of one launch (ibh_weighted_apply_many_device): batch q reads x[q] and writes y[q],
 // all with the same nvar / leading dimensions.  Passed by value in the kernarg segment, so a launch
 // needs no device-side pointer table and stays stream-ordered and graph-capturable.
@@ -166,6 +206,11 @@ struct BatchPtrs {
 // A 40 MB apply is a latency-sized problem on this chip (launch + rowptr -> segment -> X are
 // ~4 us of an 11 us launch); in one launch over several batches the workgroups of batch q+1 start
 // while those of batch q still stream, so the prologue and the drain are paid once per LAUNCH.
+// (Tried and dropped: renumbering the workgroups so that the batch groups of one (row, chunk) follow each other on one XCD and
+// the row's CSR segment comes from the fabric once per launch instead of once per group.  With a buffer of its own for every
+// batch of the launch it is SLOWER, 6.89 -> 7.83 us per apply at the headline shape: sixteen different X streams at once per
+// XCD instead of one cost more than the 0.1 x of re-read CSR the Infinity Cache serves.  It looks faster, 6.8 -> 5.2 us, only
+// where a launch holds the same X several times, because the repeats then meet in L2.  DESIGN.md section 3.)
 //
 // DUAL (EvI, EvX; WK == 1): the "row" is a BAND -- the ice cells of one GCM cell whose elevation lies
 // between two neighbouring classes.  Such a cell is a column of two rows of M (weights 1-r and r on
@@ -275,26 +320,11 @@ __global__ __launch_bounds__(NW * 64, (FPW == 1 && !DUAL) ? 8 : 1) void spmm_row
                         for (int j = 0; j < FPW; ++j) acc[j] = fma(v, x[j][u], acc[j]);
                     }
                 }
-                // Tail batch: lanes past the end re-read the last entry and are masked at the FMA (never
-                // multiplied by 0: 0*NaN must not leak into a row).
+                // Tail batch (every row of the 5 km matrices is nothing else): the slots that hold entries of this wave.
                 if (kb + wk * 64 < n) {
-                    double x[FPW][UNROLL];
-#pragma unroll
-                    for (int u = 0; u < UNROLL; ++u) {
-                        const int k = kb + wk * 64 + lane + u * STEP;
-                        const int off = s_col[k < n ? k : n - 1] << 3;
-#pragma unroll
-                        for (int j = 0; j < FPW; ++j) x[j][u] = xload(rs[j], off);
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int u = 0; u < UNROLL; ++u) {
-                        const int k = kb + wk * 64 + lane + u * STEP;
-                        const bool ok = k < n;
-                        const double v = s_val[ok ? k : n - 1];
-#pragma unroll
-                        for (int j = 0; j < FPW; ++j) acc[j] = ok ? fma(v, x[j][u], acc[j]) : acc[j];
-                    }
+                    const int k0 = kb + wk * 64;
+                    const int nu = __builtin_amdgcn_readfirstlane(min(UNROLL, (n - k0 + STEP - 1) / STEP));
+                    with_slot_count<UNROLL>(nu, [&](auto c) { tail_slots<FPW, decltype(c)::value, STEP>(s_col, s_val, rs, k0 + lane, n, acc); });
                 }
             } else {
             for (; kb < nfull; kb += BATCH) {
@@ -416,8 +446,8 @@ __global__ __launch_bounds__(NW * 64, 8) void spmm_rowone_kernel(
     const int fw = fc * NW + wave;
     const int f = fw < nf ? fw : nf - 1;            // clamp: tail fields read valid memory, never stored
     const int beg = rowptr[r], end = rowptr[r + 1];
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *)(X + (long)f * ldx), 0, ncol * 8, 0x00020000);
-    double acc = 0.0;
+    const __amdgpu_buffer_rsrc_t rs[1] = {__builtin_amdgcn_make_buffer_rsrc((void *)(X + (long)f * ldx), 0, ncol * 8, 0x00020000)};
+    double acc[1] = {0.0};
     for (int seg = beg; seg < end; seg += SEG) {
         const int n = min(SEG, end - seg);
         int cc[ST];
@@ -435,23 +465,12 @@ __global__ __launch_bounds__(NW * 64, 8) void spmm_rowone_kernel(
             if (k < n) { s_col[k] = cc[i]; s_val[k] = vv[i]; }
         }
         __syncthreads();
-        double x[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int k = lane + 64 * u;
-            x[u] = xload(rs, s_col[k < n ? k : n - 1] << 3);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int u = 0; u < U; ++u) {               // lanes past the end are masked, never multiplied by 0 (0*NaN)
-            const int k = lane + 64 * u;
-            const bool ok = k < n;
-            const double v = s_val[ok ? k : n - 1];
-            acc = ok ? fma(v, x[u], acc) : acc;
-        }
+        // the ceil(n / 64) slots that hold entries, and no others (tail_slots: the tail batch of rowblock)
+        const int nu = __builtin_amdgcn_readfirstlane(min(U, (n + 63) >> 6));
+        with_slot_count<U>(nu, [&](auto c) { tail_slots<1, decltype(c)::value, 64>(s_col, s_val, rs, lane, n, acc); });
     }
-    acc = wave_sum(acc);
-    if (lane == 0 && fw < nf) Y[(long)fw * ldy + r] = wM[r] == 0.0 ? fill : acc;      // mask_result, IceCoupler.cpp:186-201
+    const double sum = wave_sum(acc[0]);
+    if (lane == 0 && fw < nf) Y[(long)fw * ldy + r] = wM[r] == 0.0 ? fill : sum;      // mask_result, IceCoupler.cpp:186-201
 }
 // Tried on top of this and dropped (measured on MI355X, 5 km AvI, 64 fields): RUN HINTS -- the first-seen numbering makes a
 // row's columns a contiguous run behind ~18 scattered ones, so the gathers of the run were issued with arithmetic addresses
