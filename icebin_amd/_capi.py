@@ -134,6 +134,15 @@ _SIGS = {
                                        C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "ibh_etopo1_ice_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.c_int64]),
+    "ibh_make_topoo_create": (C.c_int, [C.POINTER(C.c_void_p)] + [C.c_int32, C.c_int32, C.c_double, C.c_double] * 3
+                              + [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "ibh_make_topoo_destroy": (C.c_int, [C.c_void_p]),
+    "ibh_make_topoo_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                       C.c_void_p]),
+    "ibh_make_topoo_status": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ibh_make_topoo_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                     C.c_void_p]),
+    "ibh_selftest_pow03": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "ibh_modele_matrices_create": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_void_p,
                                             C.c_void_p, C.c_int64, C.POINTER(C.c_void_p)]),
     "ibh_modele_matrices_matrix_d": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),

@@ -69,6 +69,16 @@ class Etopo1Ice:
         from .global_ec import IceScan
         return IceScan(hspecO, self.hspecI, self.FGICE1m, self.ZICETOP1m)
 
+    def make_topoO(self, hspecO, hspecS, FLAKES, set_to_land=(), set_to_ocean=(), resets=()):
+        """topoo.make_topoO on the resident planes (topo_base.cpp:263-809): no 1' plane leaves the device.  FLAKES: a torch CUDA
+        tensor, or a host array (uploaded)."""
+        from .topoo import make_topoO
+        if not (hasattr(FLAKES, "is_cuda") and FLAKES.is_cuda):
+            import torch
+            FLAKES = torch.from_numpy(np.ascontiguousarray(FLAKES, np.float64).copy()).to(self.FGICE1m.device)
+        return make_topoO(self.hspecI, hspecO, self.FGICE1m, self.ZICETOP1m, self.ZSOLG1m, self.FOCEAN1m, hspecS, FLAKES, set_to_land,
+                          set_to_ocean, resets)
+
     def write(self, ofname_root):
         """<root>1m.nc (:143-157, :229-243) and, with h planes, <root>h.nc (store_h, :27-28) through ncio, CDF-5: `short` /
         `double` variables under the reference's names over (jm1m, im1m) / (jmh, imh), with the units, description and source

@@ -1376,6 +1376,120 @@ inline Etopo1Ice etopo1_ice(HntrSpec const &hspecI, HntrSpec const &hspecC, Arra
     return out;
 }
 
+// ---- modele/topo_base.cpp:20-221, :263-809 -----------------------------------------------------------
+/** The hand-set cells of _make_topoO, 1-based (i, j) on the ocean grid: SET_TO = TO_LAND (:416-446) and TO_OCEAN (:449-494, set
+    after the land cells), and the resets (:231-248) with their elevations.  Empty by default; the reference's own lists for g1qx1
+    are the settings fixture tests/golden/make_topoo_g1qx1_cells.json. */
+struct TopoOCells {
+    std::vector<std::pair<int, int>> set_to_land, set_to_ocean;
+    struct Reset { int i, j; double elev; };
+    std::vector<Reset> resets;
+};
+
+/** What ibh_make_topoo_status reports: the reference's stderr warnings as counts. */
+struct TopoOCounts {
+    long FGICE_low = 0, FGICE_high = 0, FLAKE_reduced = 0, FGRND_range = 0, dZOCEN_nonpositive = 0, FLAKE_one = 0;
+};
+
+/** The grids, tables and scratch of one make_topoO (ibh_make_topoo_create) on the current HIP device: hspecI (the reference's
+    g1mx1m) must nest in hspecO (g1qx1), whose sizes must be even; hspecS (g10mx10m) is the grid of FLAKES.  Owns a device
+    handle: not copyable. */
+class MakeTopoOGrids {
+    ibh_make_topoo *h_ = nullptr;
+public:
+    HntrSpec const hspecI, hspecO, hspecS;
+    MakeTopoOGrids(HntrSpec const &_hspecI, HntrSpec const &_hspecO, HntrSpec const &_hspecS, TopoOCells const &cells = TopoOCells())
+        : hspecI(_hspecI), hspecO(_hspecO), hspecS(_hspecS) {
+        std::vector<int32_t> land, ocean, rij;
+        std::vector<double> relev;
+        for (auto const &c : cells.set_to_land) { land.push_back(c.first); land.push_back(c.second); }
+        for (auto const &c : cells.set_to_ocean) { ocean.push_back(c.first); ocean.push_back(c.second); }
+        for (auto const &r : cells.resets) { rij.push_back(r.i); rij.push_back(r.j); relev.push_back(r.elev); }
+        check(ibh_make_topoo_create(&h_, hspecI.im, hspecI.jm, hspecI.offi, hspecI.dlat, hspecO.im, hspecO.jm, hspecO.offi, hspecO.dlat, hspecS.im,
+                                    hspecS.jm, hspecS.offi, hspecS.dlat, (int32_t)cells.set_to_land.size(), land.data(),
+                                    (int32_t)cells.set_to_ocean.size(), ocean.data(), (int32_t)cells.resets.size(), rij.data(), relev.data()));
+    }
+    MakeTopoOGrids(MakeTopoOGrids const &) = delete;
+    MakeTopoOGrids &operator=(MakeTopoOGrids const &) = delete;
+    ~MakeTopoOGrids() { if (h_) ibh_make_topoo_destroy(h_); }
+    ibh_make_topoo *handle() const { return h_; }
+    /** The planes where they are, in HBM: a pure enqueue on `stream` (ibh_make_topoo_device); plane k of the
+        IBH_MAKE_TOPOO_NPLANE outputs goes to d_planes + k * ld. */
+    void run_device(const int16_t *d_FGICE1m, const int16_t *d_ZICETOP1m, const int16_t *d_ZSOLG1m, const int16_t *d_FOCEAN1m,
+                    const double *d_FLAKES, double *d_planes, long ld, void *stream = nullptr) const {
+        check(ibh_make_topoo_device(h_, d_FGICE1m, d_ZICETOP1m, d_ZSOLG1m, d_FOCEAN1m, d_FLAKES, d_planes, ld, stream));
+    }
+    /** Waits for `stream`; throws as make_topoO does for the first fatal cell, else returns the warning counts. */
+    TopoOCounts status(void *stream = nullptr) const {
+        int64_t s[IBH_MAKE_TOPOO_NSTATUS];
+        check(ibh_make_topoo_status(h_, stream, s));
+        return counts(s);
+    }
+    /** the status words as counts, or the reference's error (:85-89, :146-148) for the first cell in its order */
+    TopoOCounts counts(const int64_t *s) const {
+        const int64_t first = s[1] >= 0 && (s[3] < 0 || s[1] < s[3]) ? s[1] : s[3];
+        if (first >= 0) {
+            const bool ocean = first == s[1];
+            const int J = (int)(first / hspecO.im) + 1, I = (int)(first % hspecO.im) + 1;
+            const bool pole = J == 1 || J == hspecO.jm;
+            const int J11 = (J - 1) * hspecI.jm / hspecO.jm + 1, J1M = J * hspecI.jm / hspecO.jm;
+            const int I11 = (I - 1) * hspecI.im / hspecO.im + 1, I1M = pole ? hspecI.im : I * hspecI.im / hspecO.im;
+            char buf[256];
+            if (ocean)
+                std::snprintf(buf, sizeof buf, "Ocean cell FOCEAN(%d,%d)=%g has no ocean area on 2-minute grid; I11,I1M,J11,J1M = %d,%d,%d,%d", I, J,
+                              1., I11, I1M, J11, J1M);
+            else
+                std::snprintf(buf, sizeof buf, "Continental cell (%d,%d) has no continental area on 2-minute grid. (%d-%d, %d-%d)", I, J, I11, I1M,
+                              J11, J1M);
+            throw Exception(IBH_EINVAL, buf);
+        }
+        TopoOCounts c;
+        c.FGICE_low = (long)s[4]; c.FGICE_high = (long)s[5]; c.FLAKE_reduced = (long)s[6]; c.FGRND_range = (long)s[7];
+        c.dZOCEN_nonpositive = (long)s[8]; c.FLAKE_one = (long)s[9];
+        return c;
+    }
+};
+
+/** What _make_topoO returns (its ArrayBundle, :274-380), as arrays [jmO * imO] under the reference's names in its order. */
+struct BaseTopoO {
+    static const char *const *names() {
+        static const char *const n[IBH_MAKE_TOPOO_NPLANE] = {"FOCEAN", "FLAKE", "FGRND", "FGICE", "FGICE_greenland", "ZATMO", "dZOCEN", "dZLAKE",
+                                                             "dZGICE", "ZSOLDG", "ZICETOP", "ZLAND_MIN", "ZLAND_MAX", "ZSGLO", "ZLAKE", "ZGRND",
+                                                             "ZSGHI", "FOCEANF", "FGICEF", "ZATMOF"};
+        return n;
+    }
+    std::vector<std::vector<double>> planes;    // [IBH_MAKE_TOPOO_NPLANE][jmO * imO]
+    TopoOCounts counts;
+    std::vector<double> const &at(std::string const &name) const {
+        for (int k = 0; k < IBH_MAKE_TOPOO_NPLANE; ++k)
+            if (name == names()[k]) return planes[(size_t)k];
+        throw Exception(IBH_EINVAL, "BaseTopoO: no plane named " + name);
+    }
+};
+
+/** _make_topoO(FGICE1m, ZICETOP1m, ZSOLG1m, FOCEAN1m, FLAKES) (topo_base.cpp:263-809) from host arrays, with the grids as
+    arguments (ibh_make_topoo_host): every plane crosses PCIe once in its own width.  Throws the reference's error for the first
+    ocean cell without ocean area (:85) or continental cell without land (:146). */
+inline BaseTopoO make_topoO(HntrSpec const &hspecI, HntrSpec const &hspecO, ArrayView<const int16_t> const &FGICE1m,
+                        ArrayView<const int16_t> const &ZICETOP1m, ArrayView<const int16_t> const &ZSOLG1m,
+                        ArrayView<const int16_t> const &FOCEAN1m, HntrSpec const &hspecS, ArrayView<const double> const &FLAKES,
+                        TopoOCells const &cells = TopoOCells()) {
+    if (FGICE1m.size() != hspecI.size() || ZICETOP1m.size() != hspecI.size() || ZSOLG1m.size() != hspecI.size() || FOCEAN1m.size() != hspecI.size())
+        throw Exception(IBH_EINVAL, "FGICE1m / ZICETOP1m / ZSOLG1m / FOCEAN1m: a plane does not hold the " + std::to_string(hspecI.size()) +
+                                        " cells of hspecI");
+    if (FLAKES.size() != hspecS.size())
+        throw Exception(IBH_EINVAL, "FLAKES: the plane does not hold the " + std::to_string(hspecS.size()) + " cells of hspecS");
+    MakeTopoOGrids grids(hspecI, hspecO, hspecS, cells);
+    const size_t nO = (size_t)hspecO.size();
+    std::vector<double> flat((size_t)IBH_MAKE_TOPOO_NPLANE * nO);
+    int64_t s[IBH_MAKE_TOPOO_NSTATUS];
+    check(ibh_make_topoo_host(grids.handle(), FGICE1m.data, ZICETOP1m.data, ZSOLG1m.data, FOCEAN1m.data, FLAKES.data, flat.data(), (int64_t)nO, s));
+    BaseTopoO out;
+    out.counts = grids.counts(s);
+    for (int k = 0; k < IBH_MAKE_TOPOO_NPLANE; ++k) out.planes.emplace_back(flat.begin() + (long)((size_t)k * nO), flat.begin() + (long)((size_t)(k + 1) * nO));
+    return out;
+}
+
 // ---- modele/GCMRegridder_ModelE.hpp ------------------------------------------------------------------
 /** make_hntrA (modele/hntr.cpp:232-241): the atmosphere grid is exactly twice as coarse as the ocean grid. */
 inline HntrSpec make_hntrA(HntrSpec const &hntrO) {
@@ -1611,6 +1725,14 @@ struct TopoO {
     std::vector<double> FOCEANF, FGICEF, ZATMOF, FOCEAN, FLAKE, FGRND, FGICE, ZATMO, ZLAKE, ZICETOP, ZLAND_MIN, ZLAND_MAX;
     std::vector<int16_t> mergemask;
 };
+/** The planes of make_topoO that update_topo starts from. */
+inline TopoO topoo(BaseTopoO const &b) {
+    TopoO t;
+    t.FOCEANF = b.at("FOCEANF"); t.FGICEF = b.at("FGICEF"); t.ZATMOF = b.at("ZATMOF"); t.FOCEAN = b.at("FOCEAN"); t.FLAKE = b.at("FLAKE");
+    t.FGRND = b.at("FGRND"); t.FGICE = b.at("FGICE"); t.ZATMO = b.at("ZATMO"); t.ZLAKE = b.at("ZLAKE"); t.ZICETOP = b.at("ZICETOP");
+    t.ZLAND_MIN = b.at("ZLAND_MIN"); t.ZLAND_MAX = b.at("ZLAND_MAX");
+    return t;
+}
 
 /** The end of GCMCoupler_ModelE::update_topo (modele/GCMCoupler_ModelE.cpp:1090-1167) and couple()'s unit conversion
     (:1216-1228): the TOPOA planes packed into gcm_ivalss_s[ATOPO] and [ETOPO] on the device, from one pass over the masks

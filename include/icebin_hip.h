@@ -560,6 +560,64 @@ int ibh_etopo1_ice_host(const ibh_etopo1_ice *h, const int16_t *focean, const in
                         int64_t ldh);
 
 /* ------------------------------------------------------------------------- */
+/* make_topoO: _make_topoO of modele/topo_base.cpp (:263-809) with its callZ (:20-221), from arrays and with the grids as
+ * arguments in place of g1mx1m / g1qx1 / g10mx10m.  The fine grid I of the four int16 planes nests in the ocean grid O of the
+ * outputs (imI % imO == 0, jmI % jmO == 0; ocean cell (J, I) owns the fine rows [(J-1) * mult_j, J * mult_j) and columns
+ * [(I-1) * mult_i, I * mult_i)); imO and jmO are even (the 2 x 2 block pass, :774-795); the grid S of FLAKES need not nest.
+ * The outputs are IBH_MAKE_TOPOO_NPLANE double planes [jmO * imO], i fastest, in the reference's order of out.add (:275-377):
+ *   FOCEAN FLAKE FGRND FGICE FGICE_greenland ZATMO dZOCEN dZLAKE dZGICE ZSOLDG ZICETOP ZLAND_MIN ZLAND_MAX ZSGLO ZLAKE ZGRND
+ *   ZSGHI FOCEANF FGICEF ZATMOF
+ * Steps, in the reference's order, every band bound in C int (and double where written), all arithmetic fp64 without contraction:
+ *   the six regrids (:392, :399, :575, :646, :661, :663), mean_polar, bitwise ibh_hntr_regrid_typed_device of the same planes;
+ *   the south-pole row (:498-502) and the rounding under SET_TO (:506-531); FLAKE's bands and wedge (:578-586), apportioning and
+ *   std::round to 1/256 (:589-600), the clamp for J > JM/6 (:608-623); FGRND with its 1e-14 snap (:633-641); dZOCEN (:646-655);
+ *   dZGICE (:671-711): the sums over I in order per row, SUMDFR / SUMDF over J in order, CONSTK, the fill -- the cells filled
+ *   through pow (:708) carry the device pow's error, every other cell is bitwise; ZSOLDG = -dZOCEN, ZICETOP = 0 (:723-724);
+ *   callZ (:61-220) for every ocean cell, one tile of imI x mult_j fine cells on rows 1 and JM (IMAX = 1), replicated along the row
+ *   for the eight planes of :211-218: the sums of :92-108 / :124-142 are sequential chains in traversal order (J1m outer, I1m
+ *   inner) with area = make_dxyp(hspecI)[J1m - 1]; the continental cells are sorted ascending by (ZICETOP1m, traversal position)
+ *   -- std::sort on the depth alone (:117-118, :144) leaves ties in any order, this is one of them -- and the walks of :159-205 are
+ *   sequential chains in that order; the resets (:747-758) in list order; the 2 x 2 lake -> ground pass (:774-795).
+ * Planes the reference never writes are 0: ZLAND_MIN, ZLAND_MAX, FGICE_greenland, and ZATMOF at I >= 2 of rows 1 and JM.
+ * The debug outputs (int.nc, the printf tables) are not made.  The two fatal conditions -- an ocean cell without an ocean fine
+ * cell (:85), a continental cell without land (:146) -- and the stderr warnings are counted on the device (ibh_make_topoo_status);
+ * after a fatal condition the planes' contents are unspecified.
+ * A tile of at most IBH_MAKE_TOPOO_MAX_TILE fine cells is sorted in LDS; larger tiles (at 1' on 1/4 x 1 degree: the two pole
+ * tiles) take a path with scratch in global memory sized at create, with the same order and the same chains. */
+#define IBH_MAKE_TOPOO_MAX_TILE 8192
+#define IBH_MAKE_TOPOO_NPLANE 20
+#define IBH_MAKE_TOPOO_NSTATUS 10
+typedef struct ibh_make_topoo ibh_make_topoo;
+/* The grids and the hand-set cells of one make_topoO: make_dxyp(hspecI) and make_dxyp(hspecO) (:98, :672), Hntr(17.17, hspecO,
+ * hspecI) (:391) and Hntr(17.17, hspecO, hspecS) (:574), SET_TO (:403-494: land_ij then ocean_ij, a later entry wins) and the
+ * resets (:231-248), each list as 1-based (i, j) pairs [2 * n] (reset_elev[n]: the elevations), and the long path's scratch.
+ * IBH_EINVAL before a device is looked for: a size <= 0, grids that do not nest, odd imO or jmO, 2^31 or more fine cells, a list
+ * entry outside [1, imO] x [1, jmO]; the messages name the shapes.  Waits for the device. */
+int ibh_make_topoo_create(ibh_make_topoo **out, int32_t imI, int32_t jmI, double offiI, double dlatI, int32_t imO, int32_t jmO, double offiO,
+                          double dlatO, int32_t imS, int32_t jmS, double offiS, double dlatS, int32_t nland, const int32_t *land_ij, int32_t nocean,
+                          const int32_t *ocean_ij, int32_t nreset, const int32_t *reset_ij, const double *reset_elev);
+/* Frees the tables and the scratch (never a caller's plane). */
+int ibh_make_topoo_destroy(ibh_make_topoo *h);
+/* _make_topoO (:263-809) on planes in HBM: four int16 planes [jmI * imI] and FLAKES double [jmS * imS], never written; plane k
+ * of the outputs at d_planes + k * ld (ld >= imO * jmO; the gaps are left untouched).  A NULL or misaligned plane, a short ld or
+ * outputs that overlap an input are IBH_EINVAL before a device is touched.  A pure enqueue on `stream`; the handle's work planes,
+ * scratch and status serve one call at a time. */
+int ibh_make_topoo_device(ibh_make_topoo *h, const int16_t *d_FGICE1m, const int16_t *d_ZICETOP1m, const int16_t *d_ZSOLG1m,
+                          const int16_t *d_FOCEAN1m, const double *d_FLAKES, double *d_planes, int64_t ld, void *stream);
+/* What the last call on `stream` found, after waiting for it; status[IBH_MAKE_TOPOO_NSTATUS]:
+ *   [0] ocean cells without an ocean fine cell (:85), [1] the first of them, (J-1) * imO + (I-1), -1: none;
+ *   [2] continental cells without land (:146), [3] the first of them, -1: none;
+ *   the warnings, as counts: [4] FGICE < 0 (:610), [5] FGICE > 1 (:614), [6] FLAKE reduced (:618), [7] FGRND outside [0, 1]
+ *   (:637), [8] dZOCEN <= 0 on an ocean cell (:652), [9] FLAKE == 1 (:763). */
+int ibh_make_topoo_status(const ibh_make_topoo *h, void *stream, int64_t *status);
+/* _make_topoO (:263-809) on host arrays of the same shapes: every plane crosses PCIe once in its own width.  status (may be
+ * NULL) as above.  Waits for the device. */
+int ibh_make_topoo_host(ibh_make_topoo *h, const int16_t *FGICE1m, const int16_t *ZICETOP1m, const int16_t *ZSOLG1m, const int16_t *FOCEAN1m,
+                        const double *FLAKES, double *planes, int64_t ld, int64_t *status);
+/* out[k] = pow(x[k], .3) as the kernels of make_topoO evaluate it (:690, :708), for measuring its error.  A pure enqueue. */
+int ibh_selftest_pow03(const double *d_x, int64_t n, double *d_out, void *stream);
+
+/* ------------------------------------------------------------------------- */
 /* ModelE's regridder: GCMRegridder_ModelE::regrid_matrices (slib/icebin/modele/GCMRegridder_ModelE.cpp:487-571).  rmO holds
  * the matrices on ModelE's OCEAN grid O = HntrSpec(imO, jmO, offiO, dlatO); the atmosphere grid A is make_hntrA(O) =
  * HntrSpec(imO/2, jmO/2, offiO/2, 2*dlatO) (modele/hntr.cpp:232-241).  foceanAOp / foceanAOm [nO], sparse O indexing: the
