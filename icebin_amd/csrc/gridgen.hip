@@ -1,4 +1,5 @@
-// gridgen.hip -- exchange-grid generation for a rectilinear XY ice grid under convex (projected) GCM cells.
+// gridgen.hip -- exchange-grid generation for a rectilinear XY ice grid under (projected) GCM cells: convex ones of up to 16
+// vertices through k_gg_clip's per-lane arrays, anything else through the streamed clip (exgrid_generate decides per call).
 //
 // Replaces make_exchange_grid (slib/icebin/gridgen/GridGen_Exchange.cpp:175-284) for the case the
 // regrid path is quoted on: ice cells are axis-aligned rectangles in the projected plane
@@ -264,21 +265,53 @@ void check_ice_edges(int nx, int ny, const double *xedges, const double *yedges)
     for (int k = 0; k < ny; ++k) IBH_CHECK(yedges[k + 1] > yedges[k], "y edges must be ascending");
 }
 
+// Convex, as k_gg_clip's arrays need it: clip_axis adds one vertex per run of outside vertices, a convex n-gon has at most one
+// such run per half-plane (n + 4 <= GG_CLIPV), a non-convex one can have n / 2.  The test: no two turn cross products of
+// opposite strict sign, and the edge directions wind once -- at most two strict sign changes of the edges' x components and
+// of their y components round the cycle (a {16/7} star turns the same way everywhere and winds seven times).  The count of
+// runs follows from the sign changes alone, and the sign of a rounded difference is exact.  Zero tolerance, and a cross product
+// that is not finite is "no": a wrong "no" only picks the streamed kernel.  Either orientation passes.
+static bool gg_convex(const double *x, const double *y, int n) {
+    bool pos = false, neg = false;
+    int chg[2] = {0, 0}, first[2] = {0, 0}, last[2] = {0, 0};      // per axis: sign changes, first and latest non-zero sign
+    for (int k = 0; k < n; ++k) {
+        const int k1 = k + 1 == n ? 0 : k + 1, k2 = k1 + 1 == n ? 0 : k1 + 1;
+        const double e[2] = {x[k1] - x[k], y[k1] - y[k]}, f[2] = {x[k2] - x[k1], y[k2] - y[k1]};
+        const double c = e[0] * f[1] - e[1] * f[0];
+        if (!(c - c == 0)) return false;
+        pos |= c > 0; neg |= c < 0;
+        for (int a = 0; a < 2; ++a) {
+            const int s = e[a] > 0 ? 1 : e[a] < 0 ? -1 : 0;
+            if (!s) continue;
+            if (last[a] && s != last[a]) ++chg[a];
+            if (!first[a]) first[a] = s;
+            last[a] = s;
+        }
+    }
+    for (int a = 0; a < 2; ++a)
+        if (first[a] && last[a] != first[a]) ++chg[a];             // the cycle closes
+    return !(pos && neg) && chg[0] <= 2 && chg[1] <= 2;
+}
+
 void exgrid_generate(const ibh_exgrid_desc *d, ibh_exgrid *out) {
     check_ice_edges(d->nx, d->ny, d->xedges, d->yedges);
     IBH_CHECK(d->npoly >= 0 && (d->npoly == 0 || (d->polyptr && d->vx && d->vy && d->iA)), "null polygon arrays");
-    int maxv = 0;
+    int maxv = 0, first_nonconvex = -1;
     for (int p = 0; p < d->npoly; ++p) {
         const int n = d->polyptr[p + 1] - d->polyptr[p];
         IBH_CHECK(n >= 3, "polygon %d has %d vertices (3 or more needed)", p, n);
         maxv = std::max(maxv, n);
         IBH_CHECK(d->iA[p] >= 0 && d->iA[p] < (1ll << 31), "polygon %d: iA out of range", p);
         IBH_CHECK(p == 0 || d->iA[p] > d->iA[p - 1], "polygons must come in ascending iA order (cells.sorted(), AbbrGrid.cpp:15)");
+        if (first_nonconvex < 0 && n <= GG_MAXV && !gg_convex(d->vx + d->polyptr[p], d->vy + d->polyptr[p], n)) first_nonconvex = p;
     }
-    // the array kernel for every call it can take (<= GG_MAXV vertices), the streamed one beyond; gridgen_stream_clip forces one
+    // the array kernel for every call it can take (convex polygons of <= GG_MAXV vertices), the streamed one for the rest;
+    // gridgen_stream_clip forces one
     const int forced = get_tuning("gridgen_stream_clip", -1);
     IBH_CHECK(forced != 0 || maxv <= GG_MAXV, "gridgen_stream_clip=0: a polygon has %d vertices, the array kernel takes 3..%d", maxv, GG_MAXV);
-    const bool stream_clip = forced >= 0 ? forced != 0 : maxv > GG_MAXV;
+    IBH_CHECK(forced != 0 || first_nonconvex < 0, "gridgen_stream_clip=0: polygon %d is not convex, the array kernel takes convex polygons only",
+              first_nonconvex);
+    const bool stream_clip = forced >= 0 ? forced != 0 : maxv > GG_MAXV || first_nonconvex >= 0;
     hipStream_t st = nullptr;
     Arena &A = arena();
     A.reset();

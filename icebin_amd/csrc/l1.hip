@@ -289,6 +289,49 @@ static void l1_finish(ibh_l1_exgrid *ex, uint32_t n, uint64_t nq, uint64_t *keys
     IBH_HIP(hipStreamSynchronize(st));
 }
 
+// k_l1_clip intersects the triangle with the half-plane of every polygon edge, which is the polygon only when the polygon is
+// convex and counter-clockwise: a reflex vertex loses area and a clockwise polygon yields nothing, both silently.  So such a
+// polygon is refused here.  A refusal must not trip on a side that carries computed collinear points (a projected lon/lat box
+// with points_in_side > 1), so a turn counts as reflex only when it is more negative than rounding can make a straight one.
+// The bound is derived, not measured.  With M the polygon's largest |coordinate|, u = ulp(M) <= eps M (eps = 2^-52), e = e_k,
+// f = e_{k+1} and S = |e|_1 + |f|_1:
+//   * moving every vertex by up to d in each coordinate moves each edge component by up to 2 d and
+//     cross(e, f) = e_x f_y - e_y f_x by up to 2 d S + 8 d^2;  d = u (the stored coordinate is the exact one rounded at M's
+//     binade) gives 2 u S + 8 u^2;
+//   * evaluating the cross product in doubles (two differences, a product and the final difference, half an ulp each) is off by
+//     up to 2 eps (|e_x f_y| + |e_y f_x|) <= 2 eps |e|_1 |f|_1 <= 4 eps M S, since an edge component is at most 2 M.
+// Together 6 eps M S + 8 (eps M)^2.  The factor used is 16: it also covers a point computed as a + t (b - a), which carries
+// three roundings (d up to 2.5 u: 5 + 4 = 9).  A turn more reflex than that is a property of the input.
+// The edge directions must wind once as well (a star polygon turns left everywhere): at most two sign changes of the
+// edges' x components and of their y components round the cycle, a component within 2 eps M of zero (both ends moved by u)
+// counting as zero.
+constexpr double L1_TURN_FACTOR = 16.0;
+static void l1_check_convex_ccw(int p, const double *x, const double *y, int n) {
+    const double eps = 2.220446049250313e-16;
+    double M = 0;
+    for (int k = 0; k < n; ++k) M = std::max(M, std::max(std::fabs(x[k]), std::fabs(y[k])));
+    const double eM = eps * M;
+    int chg[2] = {0, 0}, last[2] = {0, 0};      // per axis: sign changes so far, latest non-zero sign
+    for (int k = 0; k < n; ++k) {
+        const int k1 = k + 1 == n ? 0 : k + 1, k2 = k1 + 1 == n ? 0 : k1 + 1;
+        const double e[2] = {x[k1] - x[k], y[k1] - y[k]}, f[2] = {x[k2] - x[k1], y[k2] - y[k1]};
+        const double c = e[0] * f[1] - e[1] * f[0];
+        const double S = (std::fabs(e[0]) + std::fabs(e[1])) + (std::fabs(f[0]) + std::fabs(f[1]));
+        const double tol = L1_TURN_FACTOR * eM * (S + eM);
+        IBH_CHECK(c >= -tol, "polygon %d is not counter-clockwise convex: the turn at vertex %d is reflex (cross product %.3e, rounding allows %.3e)",
+                  p, k1, c, -tol);
+        for (int a = 0; a < 2; ++a) {
+            const int s = e[a] > 2 * eM ? 1 : e[a] < -2 * eM ? -1 : 0;
+            if (!s) continue;
+            if (last[a] && s != last[a]) ++chg[a];
+            last[a] = s;
+            // changes round the cycle come in pairs: a third one along the walk is the fourth of the cycle
+            IBH_CHECK(chg[a] <= 2, "polygon %d is not convex: its edges wind more than once (the %c direction turns back a third time at vertex %d)",
+                      p, a ? 'y' : 'x', k);
+        }
+    }
+}
+
 static void l1_exgrid_generate(const ibh_l1_mesh *m, int32_t npoly, const int32_t *polyptr, const double *px, const double *py,
                                const int64_t *iA, ibh_l1_exgrid **out) {
     IBH_CHECK(m && out, "null argument");
@@ -304,6 +347,7 @@ static void l1_exgrid_generate(const ibh_l1_mesh *m, int32_t npoly, const int32_
             g.x0 = std::min(g.x0, px[k]); g.x1 = std::max(g.x1, px[k]);
             g.y0 = std::min(g.y0, py[k]); g.y1 = std::max(g.y1, py[k]);
         }
+        l1_check_convex_ccw(p, px + polyptr[p], py + polyptr[p], n);
     }
     require_device();
     std::unique_ptr<ibh_l1_exgrid> ex(new ibh_l1_exgrid);

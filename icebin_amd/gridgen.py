@@ -1,6 +1,7 @@
 """Exchange-grid generation (slib/icebin/gridgen/GridGen_Exchange.cpp:175-284) over the C-ABI: a rectilinear
-ice grid in the projected plane under convex GCM-cell polygons.  Inputs only -- the overlap arithmetic runs
-in gridgen.hip."""
+ice grid in the projected plane under GCM-cell polygons (convex ones of up to 16 vertices through the array
+clip, anything else -- more vertices, concave -- through the streamed one).  Inputs only -- the overlap arithmetic
+runs in gridgen.hip."""
 import ctypes as C
 
 import numpy as np
@@ -11,7 +12,8 @@ from ._capi import check, lib, ptr
 
 def make_exchange_grid(xedges, yedges, polys, iA, x_fastest=False):
     """xedges [nx+1], yedges [ny+1]: ice-cell edges (ascending); polys: list of [nv, 2] vertex arrays
-    (counter-clockwise, projected XY) of the realised GCM cells; iA: their sparse indices (ascending).
+    (simple, counter-clockwise, projected XY; concave ones are served, by the streamed clip) of the realised GCM
+    cells; iA: their sparse indices (ascending).
     Returns dict(indices=int32[nX, 2] (iA, iI), overlaps=f64[nX]) sorted by (iA, iI)."""
     xe, ye = np.ascontiguousarray(xedges, np.float64), np.ascontiguousarray(yedges, np.float64)
     iA = np.ascontiguousarray(iA, np.int64)

@@ -851,7 +851,8 @@ inline std::unique_ptr<linear::Weighted_Eigen> compute_E1vE0c(std::vector<linear
 }   // namespace e1ve0
 
 // ---- gridgen/GridGen_Exchange.cpp:175-284 ----------------------------------------------------------
-/** make_exchange_grid for a rectilinear XY ice grid under convex projected GCM-cell polygons (ibh_exgrid_generate). */
+/** make_exchange_grid for a rectilinear XY ice grid under projected GCM-cell polygons (ibh_exgrid_generate): simple and
+ *  counter-clockwise; a call with a non-convex polygon, or one of more than 16 vertices, runs the streamed clip. */
 inline ExchangeGrid make_exchange_grid(std::vector<double> const &xedges, std::vector<double> const &yedges, bool x_fastest,
                                        std::vector<int> const &polyptr, std::vector<double> const &vx, std::vector<double> const &vy,
                                        std::vector<long> const &iA) {

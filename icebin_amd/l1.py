@@ -82,7 +82,9 @@ def _ragged(polys):
 def make_exchange_grid(mesh, polys, iA):
     """make_exchange_grid (slib/icebin/gridgen/GridGen_Exchange.cpp:175-284) for a triangle mesh.  polys: list of [nv, 2]
     vertex arrays (convex, counter-clockwise, projected XY, at most 16 vertices) of the realised GCM cells; iA: their
-    sparse indices (ascending).  Returns an ExchangeGrid: indices, areas and polygons."""
+    sparse indices (ascending).  A polygon that is clockwise, has a reflex vertex (beyond rounding: sides with computed
+    collinear points pass) or winds more than once raises IcebinHipError(IBH_EINVAL) naming polygon and vertex.
+    Returns an ExchangeGrid: indices, areas and polygons."""
     iA = np.ascontiguousarray(iA, np.int64)
     if len(polys) != len(iA):
         raise ValueError("%d polygons, %d indices" % (len(polys), len(iA)))

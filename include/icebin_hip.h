@@ -70,10 +70,13 @@ int ibh_sparse_set_add_dense(ibh_sparse_set *s, int64_t sparse, int32_t *dense);
 
 /* ------------------------------------------------------------------------- */
 /* Exchange-grid generation: make_exchange_grid (slib/icebin/gridgen/GridGen_Exchange.cpp:175-284) for a
- * rectilinear ice grid in the projected plane (gridgen/searise_grid.cpp) under convex GCM-cell polygons
- * whose vertices the caller has projected to that plane (OGrid, GridGen_Exchange.cpp:120-166; counter-
- * clockwise, 3 or more vertices, ascending iA; up to 16 vertices run the array clip, more the streamed one, and
- * ibh_set_tuning("gridgen_stream_clip", 0 | 1) forces one).  Every non-empty overlap becomes one exchange cell
+ * rectilinear ice grid in the projected plane (gridgen/searise_grid.cpp) under GCM-cell polygons
+ * whose vertices the caller has projected to that plane (OGrid, GridGen_Exchange.cpp:120-166; simple, counter-
+ * clockwise, 3 or more vertices, ascending iA).  A call whose polygons are all convex and of up to 16 vertices runs
+ * the array clip; one polygon with more vertices or not convex (the host tests every polygon: turns of one sign,
+ * edge directions winding once) sends the call to the streamed clip, which takes concave polygons.
+ * ibh_set_tuning("gridgen_stream_clip", 0 | 1) forces one; forcing the array clip on a call it cannot take is
+ * IBH_EINVAL naming the vertex count or the first polygon that is not convex.  Every non-empty overlap becomes one exchange cell
  * (iA, iI, area) with area = Cell::proj_area of the overlap polygon (Grid.cpp:42-70); cells come out
  * sorted by (iA, iI) like ExchangeGrid's constructor leaves them (AbbrGrid.cpp:10-21).  The result
  * stays in HBM; ibh_exgrid_get copies it out (the layout ibh_regridder_desc takes). */
@@ -105,7 +108,10 @@ int ibh_l1_mesh_destroy(ibh_l1_mesh *mesh);
 /* The exchange grid of a mesh: one cell per (GCM cell, element) overlap of positive area, holding (iA, iTri), the area and
  * the overlap polygon (counter-clockwise, 3..19 vertices, mesh coordinates), sorted by (iA, iTri).  Generated here
  * (make_exchange_grid, slib/icebin/gridgen/GridGen_Exchange.cpp:175-284, for triangles: polygons as in ibh_exgrid_desc --
- * convex, counter-clockwise, projected, 3..16 vertices, ascending iA; more vertices is IBH_EINVAL) or taken from the
+ * convex, counter-clockwise, projected, 3..16 vertices, ascending iA.  The clip intersects half-planes, so more vertices,
+ * a clockwise polygon, a reflex vertex or edges that wind more than once are IBH_EINVAL naming polygon and vertex; a turn
+ * counts as reflex only beyond what rounding of the stored coordinates can do, 16 eps M (|e_k|_1 + |e_k+1|_1) with M the
+ * polygon's largest |coordinate|, so sides with computed collinear points pass) or taken from the
  * caller as the reference's exgrid.cells carry it (element_l1.py:96-148 reads cellX.vertices, .i, .j): any order, sorted
  * here by (iA, iTri), ties in input order.  The area is Cell::proj_area (Grid.cpp:42-70) of the stored polygon, summed
  * with the polygon's vertex 0 as the origin.  Two calls on the same input give the same bytes. */

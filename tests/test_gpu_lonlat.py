@@ -157,9 +157,14 @@ def test_stream_clip_bitwise_on_cells_and_invariant(n, stream_clip):
 
 
 def test_old_path_untouched(stream_clip):
-    """<= 16 vertices (test_gpu_parity.py's general convex polygons, and the CPU test's grid pair near the origin): the default
-    call and the forced array kernel give the same bytes; the streamed kernel gives the same indices, and areas within the
-    CPU test's bound for it plus the array kernel's own rounding (absolute coordinates), relative to the ice cell's area."""
+    """Convex, <= 16 vertices (test_gpu_parity.py's general convex polygons, and the CPU test's grid pair near the origin): the
+    default call and the forced array kernel give the same bytes; the streamed kernel gives the same indices, and areas within
+    the CPU test's bound for it plus the array kernel's own rounding (absolute coordinates), relative to the ice cell's area.
+    The grid pair's octagon has a concave side: the array kernel is not for it (its arrays hold n + 4 vertices, a convex
+    polygon's count), so with it the default call is the streamed kernel's and forcing the array kernel is refused."""
+    def turns(p):
+        e = np.roll(p, -1, 0) - p
+        return e[:, 0] * np.roll(e[:, 1], -1) - e[:, 1] * np.roll(e[:, 0], -1)
     rng = np.random.default_rng(11)
     xe, ye = np.cumsum(rng.uniform(0.5, 1.5, 41)), np.cumsum(rng.uniform(0.5, 1.5, 31))
     polys = []
@@ -168,7 +173,20 @@ def test_old_path_untouched(stream_clip):
         ang = np.sort(rng.uniform(0, 2 * np.pi, rng.integers(3, 9)))
         polys.append(c + rng.uniform(2.0, 5.0) * np.stack([np.cos(ang), np.sin(ang)], axis=1))
     xe2, ye2, polys2 = cpu.clip_pair()
-    for xe, ye, polys in ((xe, ye, polys), (xe2, ye2, [p for p in polys2 if len(p) <= 16])):
+    small = [p for p in polys2 if len(p) <= 16]
+    concave = [k for k, p in enumerate(small) if np.any(turns(p) < 0)]
+    assert len(small) == 7 and concave == [6]
+    iA = np.arange(len(small)) * 3 + 100
+    stream_clip(0)
+    with pytest.raises(_capi.IcebinHipError, match="gridgen_stream_clip=0: polygon 6 is not convex"):
+        gg.make_exchange_grid(xe2, ye2, small, iA)
+    stream_clip(-1)
+    dflt = gg.make_exchange_grid(xe2, ye2, small, iA)
+    stream_clip(1)
+    st = gg.make_exchange_grid(xe2, ye2, small, iA)
+    assert np.array_equal(dflt["indices"], st["indices"]) and np.array_equal(u64(dflt["overlaps"]), u64(st["overlaps"]))
+    for xe, ye, polys in ((xe, ye, polys), (xe2, ye2, small[:6])):
+        assert all(np.all(turns(p) > 0) for p in polys)
         iA = np.arange(len(polys)) * 3 + 100
         stream_clip(-1)
         dflt = gg.make_exchange_grid(xe, ye, polys, iA)
