@@ -9,12 +9,13 @@
 //                 bitonic sort, the fill chain walked by one wave in lockstep, the taken cells' flags stored
 //   k_et_unice    the transposed zeroing of :222, after the tiles
 // then the typed Hntr regrid once per output plane.  The row areas (make_dxyp, libm sin) are host tables uploaded by the
-// handle, so a call only enqueues.
+// handle, so a call only enqueues.  The 16-byte split of a plane, the eight-cell loads and stores, the LDS sort and the argument
+// checks are planetile.h's, shared with globalec.hip and topoo.hip.
 #include <algorithm>
 #include <memory>
 #include <vector>
 
-#include "common.h"
+#include "planetile.h"
 
 struct ibh_etopo1_ice {
     int device = 0;
@@ -33,9 +34,6 @@ constexpr int ET_T = 256;
 constexpr int16_t ET_GREENLAND = 2;         // GREENLAND_VAL (:14)
 constexpr int ET_MIN_THK = 50;              // MIN_LANDICE_THK (:15)
 constexpr int16_t ET_NO_GREENLAND = -300;   // :136-137
-typedef short short8 __attribute__((ext_vector_type(8)));
-
-inline long cdiv(long a, long b) { return (a + b - 1) / b; }
 
 struct EtCell {
     int16_t fo, fg, zt, zs;
@@ -64,35 +62,22 @@ struct EtPlanes {
     int16_t *ofo, *ofg, *ozt, *ozs;     // FOCEAN1m, FGICE1m, ZICETOP1m, ZSOLG1m
 };
 
-__device__ __forceinline__ short8 et_load8(const int16_t *p, bool vec) {
-    if (vec) return *reinterpret_cast<const short8 *>(p);
-    short8 v;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) v[k] = p[k];
-    return v;
-}
-__device__ __forceinline__ void et_store8(int16_t *p, short8 v, bool vec) {
-    if (vec) { *reinterpret_cast<short8 *>(p) = v; return; }
-#pragma unroll
-    for (int k = 0; k < 8; ++k) p[k] = v[k];
-}
-
-// The flat plane in 16-byte pieces (8 cells) between a head and a tail of fewer than 8 cells each, which go one cell a thread.
-// The head is where FOCEAN becomes 16-byte aligned; avec bit p says that plane p (ZICTOP, ZSOLID, then the four outputs) is
-// aligned there too, else its eight cells go one by one.  A piece may straddle rows: the row is carried along its cells.
-__global__ __launch_bounds__(ET_T) void k_et_planes(EtPlanes P, unsigned nI, unsigned imI, int jband, int jhalf, int incl, unsigned head,
-                                                    unsigned npiece, unsigned avec) {
+// The flat plane in 16-byte pieces (8 cells) between a head and a tail of fewer than 8 cells each, which go one cell a thread
+// (S: FOCEAN's PlaneSplit).  The head is where FOCEAN becomes 16-byte aligned; avec bit p says that plane p (ZICTOP, ZSOLID, then
+// the four outputs) is aligned there too, else its eight cells go one by one.  A piece may straddle rows: the row is carried
+// along its cells.
+__global__ __launch_bounds__(ET_T) void k_et_planes(EtPlanes P, unsigned nI, unsigned imI, int jband, int jhalf, int incl, PlaneSplit S,
+                                                    unsigned avec) {
     const unsigned g = blockIdx.x * (unsigned)ET_T + threadIdx.x;
-    const unsigned tail0 = head + npiece * 8u;
-    if (g < head + (nI - tail0)) {
-        const unsigned x = g < head ? g : tail0 + (g - head);
+    if (g < S.nloose(nI)) {
+        const unsigned x = S.cell(g);
         const EtCell o = et_cell(P.fo[x], P.zt[x], P.zs[x], (int)(x / imI), jband, jhalf, incl);
         P.ofo[x] = o.fo; P.ofg[x] = o.fg; P.ozt[x] = o.zt; P.ozs[x] = o.zs;
     }
-    if (g >= npiece) return;
-    const unsigned x0 = head + g * 8u;
-    const short8 fo = *reinterpret_cast<const short8 *>(P.fo + x0);
-    const short8 zt = et_load8(P.zt + x0, avec & 1u), zs = et_load8(P.zs + x0, avec & 2u);
+    if (g >= S.npiece) return;
+    const unsigned x0 = S.piece(g);
+    const short8 fo = load8(P.fo + x0, true);
+    const short8 zt = load8(P.zt + x0, avec & 1u), zs = load8(P.zs + x0, avec & 2u);
     unsigned j = x0 / imI, rem = x0 - j * imI;
     short8 ofo, ofg, ozt, ozs;
 #pragma unroll
@@ -101,42 +86,16 @@ __global__ __launch_bounds__(ET_T) void k_et_planes(EtPlanes P, unsigned nI, uns
         ofo[k] = o.fo; ofg[k] = o.fg; ozt[k] = o.zt; ozs[k] = o.zs;
         if (++rem == imI) { rem = 0; ++j; }
     }
-    et_store8(P.ofo + x0, ofo, avec & 4u); et_store8(P.ofg + x0, ofg, avec & 8u);
-    et_store8(P.ozt + x0, ozt, avec & 16u); et_store8(P.ozs + x0, ozs, avec & 32u);
-}
-
-// R compare-exchange steps of the bitonic stage k (distances j, j / 2, ..., jl = j >> (R - 1)) on 2^R keys held in registers: the
-// keys whose indices differ in those R bits only.  One trip through LDS and one barrier in place of R.
-template <int R>
-__device__ __forceinline__ void et_bitonic_pass(uint32_t *s, int n2, int k, int j, int tid) {
-    constexpr int E = 1 << R;
-    const int jl = j >> (R - 1);
-    for (int t = tid; t < (n2 >> R); t += ET_T) {
-        const int base = ((t & ~(jl - 1)) << R) | (t & (jl - 1));       // t with R zero bits put in at jl
-        const bool asc = (base & k) == 0;       // (k > j: the direction bit is none of the R)
-        uint32_t e[E];
-#pragma unroll
-        for (int m = 0; m < E; ++m) e[m] = s[base + m * jl];
-#pragma unroll
-        for (int d = E >> 1; d > 0; d >>= 1) {
-#pragma unroll
-            for (int m = 0; m < E; ++m) {
-                if (m & d) continue;
-                const uint32_t a = e[m], b = e[m | d];
-                if ((a > b) == asc) { e[m] = b; e[m | d] = a; }
-            }
-        }
-#pragma unroll
-        for (int m = 0; m < E; ++m) s[base + m * jl] = e[m];
-    }
+    store8(P.ofo + x0, ofo, avec & 4u); store8(P.ofg + x0, ofg, avec & 8u);
+    store8(P.ozt + x0, ozt, avec & 16u); store8(P.ozs + x0, ozs, avec & 32u);
 }
 
 // ---- the downscaled ice fraction (:166-209) ----------------------------------------------------------------------------------------
 // Workgroup b owns coarse cell (j1, i1) = (jC0 + b / imC, b % imC) and leaves at once when its fraction is 0 (:172).  A land
 // cell (FOCEAN == 0; the Greenland clause of :179 is never true) becomes the key (32767 - ZICTOP) << 16 | local index, local =
 // (j - j0) * mult_i + (i - i0): ascending keys are the reference's (-elev, j1m, i1m) order, the negation taken in int.  The keys
-// are appended in any order (an LDS counter), padded with ~0 to a power of two -- no key is ~0, a tile has fewer than 65536
-// cells -- and sorted by a bitonic network, three of its steps to a trip through LDS.  Wave 0 then walks the chain of :190-207 in lockstep: 64 areas a step are fetched
+// are appended in any order (an LDS counter) and sorted by planetile.h's lds_sort_keys -- no key is ~0, its padding: a tile has
+// fewer than 65536 cells.  Wave 0 then walks the chain of :190-207 in lockstep: 64 areas a step are fetched
 // one a lane, broadcast lane by lane, and every lane carries the same `remain`, so the subtractions are the reference's, in its
 // order; a cell is a compare and two selects, without a branch (the chain is the critical path: :190-207 once per tile).  The cells taken are the first ntake of the sorted keys; the workgroup stores their flags.
 __global__ __launch_bounds__(ET_T) void k_et_tiles(const int16_t *__restrict__ fo, const int16_t *__restrict__ zt, const double *__restrict__ fgiceC,
@@ -160,18 +119,7 @@ __global__ __launch_bounds__(ET_T) void k_et_tiles(const int16_t *__restrict__ f
     __syncthreads();
     const int n = s_n;
     if (n == 0) return;             // :185
-    int n2 = 1;
-    while (n2 < n) n2 <<= 1;
-    for (int c = n + tid; c < n2; c += ET_T) s_key[c] = 0xFFFFFFFFu;
-    __syncthreads();
-    for (int k = 2; k <= n2; k <<= 1) {
-        for (int j = k >> 1; j > 0;) {
-            if (j >= 4) { et_bitonic_pass<3>(s_key, n2, k, j, tid); j >>= 3; }
-            else if (j == 2) { et_bitonic_pass<2>(s_key, n2, k, j, tid); j = 0; }
-            else { et_bitonic_pass<1>(s_key, n2, k, j, tid); j = 0; }
-            __syncthreads();
-        }
-    }
+    lds_sort_keys<ET_T>(s_key, n, tid);
     if (tid < 64) {
         double remain = snow1 * dxypC[j1];      // :188
         const size_t jrow0 = (size_t)j1 * mult_j;
@@ -191,12 +139,11 @@ __global__ __launch_bounds__(ET_T) void k_et_tiles(const int16_t *__restrict__ f
         for (int b0 = 0; b0 < n; b0 += 64) {
             const double mine = next;
             next = area_of(b0 + 64);
-            const int lo = __double2loint(mine), hi = __double2hiint(mine);
             if (n - b0 >= 64) {
 #pragma unroll
-                for (int t = 0; t < 64; ++t) step(__hiloint2double(__builtin_amdgcn_readlane(hi, t), __builtin_amdgcn_readlane(lo, t)));
+                for (int t = 0; t < 64; ++t) step(lane_bcast(mine, t));
             } else {
-                for (int t = 0; t < n - b0; ++t) step(__hiloint2double(__builtin_amdgcn_readlane(hi, t), __builtin_amdgcn_readlane(lo, t)));
+                for (int t = 0; t < n - b0; ++t) step(lane_bcast(mine, t));
             }
             if (!__builtin_amdgcn_readfirstlane((int)alive)) break;
         }
@@ -226,35 +173,22 @@ __device__ __forceinline__ void et_unice_cell(const int16_t *__restrict__ fo, un
     if (v == ET_GREENLAND && i >= jhalf && i <= j) v = incl ? 0 : 1;
     if (v == 1) ofg[t] = 0;
 }
-// The north half [x0, nI) of the flat ocean mask in 16-byte pieces between a head and a tail of fewer than 8 cells, as k_et_planes
-// reads it; few pieces hold a Greenland cell.
+// The north half [x0, nI) of the flat ocean mask in 16-byte pieces between a head and a tail of fewer than 8 cells (S: the
+// PlaneSplit of the nI - x0 cells from fo + x0), as k_et_planes reads it; few pieces hold a Greenland cell.
 __global__ __launch_bounds__(ET_T) void k_et_unice(const int16_t *__restrict__ fo, unsigned nI, int imI, int jmI, int jhalf, int incl, unsigned x0,
-                                                   unsigned head, unsigned npiece, int16_t *__restrict__ ofg) {
+                                                   PlaneSplit S, int16_t *__restrict__ ofg) {
     const unsigned g = blockIdx.x * (unsigned)ET_T + threadIdx.x;
-    const unsigned tail0 = x0 + head + npiece * 8u;
-    if (g < head + (nI - tail0)) {
-        const unsigned x = g < head ? x0 + g : tail0 + (g - head);
+    if (g < S.nloose(nI - x0)) {
+        const unsigned x = x0 + S.cell(g);
         if (fo[x] == ET_GREENLAND) et_unice_cell(fo, x, imI, jmI, jhalf, incl, ofg);
     }
-    if (g >= npiece) return;
-    const unsigned xp = x0 + head + g * 8u;
-    const short8 v = *reinterpret_cast<const short8 *>(fo + xp);
+    if (g >= S.npiece) return;
+    const unsigned xp = x0 + S.piece(g);
+    const short8 v = load8(fo + xp, true);
 #pragma unroll
     for (int k = 0; k < 8; ++k)
         if (v[k] == ET_GREENLAND) et_unice_cell(fo, xp + (unsigned)k, imI, jmI, jhalf, incl, ofg);
 }
-
-bool overlap(const void *a, size_t na, const void *b, size_t nb) {
-    const uintptr_t A = (uintptr_t)a, B = (uintptr_t)b;
-    return A < B + nb && B < A + na;
-}
-
-struct EtArg {
-    const void *p;
-    size_t bytes;
-    const char *name;
-    bool out;
-};
 
 // NULL planes, alignment, an output over an input or another output: all before a device is touched
 void check_planes(const ibh_etopo1_ice *h, const void *focean, const void *zictop, const void *zsolid, const void *fgiceC, const void *oFO,
@@ -263,21 +197,12 @@ void check_planes(const ibh_etopo1_ice *h, const void *focean, const void *zicto
     const size_t pb = sizeof(int16_t) * (size_t)h->nI();
     IBH_CHECK(planes_h == nullptr || h->hntrH, "etopo1_ice: h planes asked for, the handle was made without hspecH");
     IBH_CHECK(planes_h == nullptr || ldh >= h->nH(), "etopo1_ice: ldh=%lld < %lld cells of hspecH", (long long)ldh, (long long)h->nH());
-    const EtArg a[] = {{focean, pb, "focean", false}, {zictop, pb, "zictop", false}, {zsolid, pb, "zsolid", false},
-                       {fgiceC, sizeof(double) * (size_t)h->imC * h->jmC, "fgiceC", false},
-                       {oFO, pb, "FOCEAN1m", true}, {oFG, pb, "FGICE1m", true}, {oZT, pb, "ZICETOP1m", true}, {oZS, pb, "ZSOLG1m", true},
-                       {planes_h, planes_h ? sizeof(double) * (size_t)(3 * ldh + h->nH()) : 0, "the h planes", true}};
-    const int na = (int)(sizeof(a) / sizeof(a[0]));
-    for (int k = 0; k < na - 1; ++k) IBH_CHECK(a[k].p, "etopo1_ice: %s is null", a[k].name);
-    for (int k = 0; k < na; ++k) {
-        const bool f64 = k == 3 || k == na - 1;
-        IBH_CHECK(((uintptr_t)a[k].p & (f64 ? 7 : 1)) == 0, "etopo1_ice: %s is not aligned to %s", a[k].name, f64 ? "double" : "int16");
-    }
-    for (int o = 0; o < na; ++o) {
-        if (!a[o].out || !a[o].p) continue;
-        for (int k = 0; k < o; ++k)
-            IBH_CHECK(!a[k].p || !overlap(a[o].p, a[o].bytes, a[k].p, a[k].bytes), "etopo1_ice: the output %s overlaps %s", a[o].name, a[k].name);
-    }
+    const PlaneArg a[] = {{focean, pb, "focean", 2, false, false}, {zictop, pb, "zictop", 2, false, false}, {zsolid, pb, "zsolid", 2, false, false},
+                          {fgiceC, sizeof(double) * (size_t)h->imC * h->jmC, "fgiceC", 8, false, false},
+                          {oFO, pb, "FOCEAN1m", 2, true, false}, {oFG, pb, "FGICE1m", 2, true, false}, {oZT, pb, "ZICETOP1m", 2, true, false},
+                          {oZS, pb, "ZSOLG1m", 2, true, false},
+                          {planes_h, planes_h ? sizeof(double) * (size_t)(3 * ldh + h->nH()) : 0, "the h planes", 8, true, true}};
+    check_plane_args("etopo1_ice", a, (int)(sizeof(a) / sizeof(a[0])));
 }
 
 // the enqueue proper; every pointer is a device pointer
@@ -286,30 +211,27 @@ void run_device(const ibh_etopo1_ice *h, const int16_t *fo, const int16_t *zt, c
     const unsigned nI = (unsigned)h->nI();
     const int jband = (int)(((int64_t)h->jmI * 14) / 15), jhalf = h->jmI / 2;
     {
-        const unsigned head = std::min<unsigned>((unsigned)(((16 - ((uintptr_t)fo & 15)) & 15) >> 1), nI);
-        const unsigned npiece = (nI - head) >> 3;
+        const PlaneSplit S = plane_split(fo, nI);
         const void *others[6] = {zt, zs, oFO, oFG, oZT, oZS};
         unsigned avec = 0;
         for (int k = 0; k < 6; ++k)
-            if ((((uintptr_t)others[k] + 2 * (uintptr_t)head) & 15) == 0) avec |= 1u << k;
-        const long nthread = std::max<long>(npiece, head + (nI - head - npiece * 8));
+            if ((((uintptr_t)others[k] + 2 * (uintptr_t)S.head) & 15) == 0) avec |= 1u << k;
+        const long nthread = std::max<long>(S.npiece, S.nloose(nI));
         const EtPlanes P{fo, zt, zs, oFO, oFG, oZT, oZS};
         hipLaunchKernelGGL(k_et_planes, dim3((unsigned)cdiv(nthread, ET_T)), dim3(ET_T), 0, st, P, nI,
-                           (unsigned)h->imI, jband, jhalf, incl, head, npiece, avec);
+                           (unsigned)h->imI, jband, jhalf, incl, S, avec);
     }
     const int jC0 = h->jmC / 2;
     if (h->jmC > jC0) {
-        int n2 = 1;
-        while (n2 < h->mult_i * h->mult_j) n2 <<= 1;
+        const int n2 = pow2_ceil(h->mult_i * h->mult_j);
         hipLaunchKernelGGL(k_et_tiles, dim3((unsigned)(h->jmC - jC0) * (unsigned)h->imC), dim3(ET_T), sizeof(uint32_t) * (size_t)n2, st, fo, zt, fgiceC,
                            h->dxypI.p, h->dxypC.p, h->imI, h->imC, h->mult_i, h->mult_j, jC0, oFG);
     }
     if (h->jmI > jhalf) {
         const unsigned x0 = (unsigned)jhalf * (unsigned)h->imI, nN = nI - x0;
-        const unsigned head = std::min<unsigned>((unsigned)(((16 - ((uintptr_t)(fo + x0) & 15)) & 15) >> 1), nN);
-        const unsigned npiece = (nN - head) >> 3;
-        const long nthread = std::max<long>(npiece, head + (nN - head - npiece * 8));
-        hipLaunchKernelGGL(k_et_unice, dim3((unsigned)cdiv(nthread, ET_T)), dim3(ET_T), 0, st, fo, nI, h->imI, h->jmI, jhalf, incl, x0, head, npiece, oFG);
+        const PlaneSplit S = plane_split(fo + x0, nN);
+        const long nthread = std::max<long>(S.npiece, S.nloose(nN));
+        hipLaunchKernelGGL(k_et_unice, dim3((unsigned)cdiv(nthread, ET_T)), dim3(ET_T), 0, st, fo, nI, h->imI, h->jmI, jhalf, incl, x0, S, oFG);
     }
     IBH_HIP(hipGetLastError());
     if (planes_h) {     // store_h (:17-29), in the reference's plane order of this library's outputs
@@ -342,9 +264,7 @@ int ibh_etopo1_ice_create(ibh_etopo1_ice **out, int32_t imI, int32_t jmI, double
         IBH_CHECK(imH == 0 || jmH >= 2, "hspecH: jm=%d; store_h's mean_polar needs at least two rows", jmH);
         std::unique_ptr<ibh_etopo1_ice> h(new ibh_etopo1_ice);
         h->imI = imI; h->jmI = jmI; h->imC = imC; h->jmC = jmC; h->mult_i = imI / imC; h->mult_j = jmI / jmC; h->imH = imH; h->jmH = jmH;
-        std::vector<double> dI((size_t)jmI), dC((size_t)jmC);
-        rethrow(ibh_hntr_dxyp(imI, jmI, dI.data()));
-        rethrow(ibh_hntr_dxyp(imC, jmC, dC.data()));
+        const std::vector<double> dI = dxyp_rows(imI, jmI), dC = dxyp_rows(imC, jmC);
         // the regridder of store_h checks its grids on the host before it looks for a device
         if (imH) rethrow(ibh_hntr_create(&h->hntrH, imI, jmI, offiI, dlatI, imH, jmH, offiH, dlatH, 0.));
         require_device();

@@ -7,7 +7,8 @@
 // scans them (prims.h) and reads the nO + 1 sums back once; the walk over them is host code.  A chunk's mask is one launch
 // (k_gec_mask).  combine_chunks numbers the chunks' row and column keys first-seen (sparseset.h number_stream), adds the
 // weights chunk by chunk with plain read-modify-write -- a key occurs once per chunk, so each launch touches a cell once and
-// the launches are stream-ordered -- and hands the triplet stream to the triplets -> CSR layer (csrbuild.h).
+// the launches are stream-ordered -- and hands the triplet stream to the triplets -> CSR layer (csrbuild.h).  The scan's 16-byte
+// split of a row and its eight-cell loads are planetile.h's, shared with etopo1.hip and topoo.hip.
 #include <algorithm>
 #include <cmath>
 #include <memory>
@@ -15,6 +16,7 @@
 #include "common.h"
 #include "csrbuild.h"
 #include "csrops.h"
+#include "planetile.h"
 #include "prims.h"
 #include "sparseset.h"
 
@@ -38,15 +40,12 @@ namespace {
 
 constexpr int GEC_T = 256;
 constexpr int GEC_MAXCELLS = 2048;      // O cells of one workgroup's longitude slice (their counts live in LDS)
-typedef short short8 __attribute__((ext_vector_type(8)));
-
-inline long cdiv(long a, long b) { return (a + b - 1) / b; }
 
 // ---- the ice scan (:805-813 and the tile counts of :876-886) ---------------------------------------------------------------------
 // Workgroup (jO, slice) owns the O cells [o0, o0 + nc) of ocean row jO: mult_j ice rows, columns [o0 * mult_i, (o0 + nc) * mult_i).
-// A row is read in 16-byte pieces (8 cells) between a head and a tail of fewer than 8 cells each, which go one cell a thread;
-// a piece may straddle O cells, so its cells are walked with the tile index carried along.  The elevation piece is read only
-// where the piece holds ice.  Counts and the range are integers: LDS atomics give the same result in any order.
+// A row is read in 16-byte pieces (8 cells) between a head and a tail of fewer than 8 cells each, which go one cell a thread (the
+// FGICE1m row's PlaneSplit); a piece may straddle O cells, so its cells are walked with the tile index carried along.  The elevation
+// piece is read only where the piece holds ice.  Counts and the range are integers: LDS atomics give the same result in any order.
 __global__ __launch_bounds__(GEC_T) void k_gec_scan(const int16_t *__restrict__ fg, const int16_t *__restrict__ el, int imI, int imO, int mult_i,
                                                     int mult_j, int cps, int nslice, int32_t *__restrict__ nice, int32_t *__restrict__ part) {
     __shared__ int s_cnt[GEC_MAXCELLS];
@@ -62,11 +61,11 @@ __global__ __launch_bounds__(GEC_T) void k_gec_scan(const int16_t *__restrict__ 
     for (int r = 0; r < mult_j; ++r) {
         const size_t base = ((size_t)jO * mult_j + r) * (size_t)imI + (size_t)o0 * mult_i;
         const int16_t *f = fg + base, *e = el + base;
-        const int head = min((int)(((16 - ((uintptr_t)f & 15)) & 15) >> 1), len);
-        const int npiece = (len - head) >> 3, tail0 = head + npiece * 8;
-        const bool evec = (((uintptr_t)(e + head)) & 15) == 0;
-        if (tid < head + (len - tail0)) {
-            const int x = tid < head ? tid : tail0 + (tid - head);
+        const PlaneSplit S = plane_split(f, (unsigned)len);
+        const int npiece = (int)S.npiece;
+        const bool evec = (((uintptr_t)(e + S.head)) & 15) == 0;
+        if (tid < (int)S.nloose((unsigned)len)) {
+            const int x = (int)S.cell((unsigned)tid);
             if (f[x] != 0) {
                 atomicAdd(&s_cnt[x / mult_i], 1);
                 const int v = e[x];
@@ -74,19 +73,13 @@ __global__ __launch_bounds__(GEC_T) void k_gec_scan(const int16_t *__restrict__ 
             }
         }
         for (int p = tid; p < npiece; p += GEC_T) {
-            const int x0 = head + p * 8;
-            const short8 fv = *reinterpret_cast<const short8 *>(f + x0);
+            const int x0 = (int)S.piece((unsigned)p);
+            const short8 fv = load8(f + x0, true);
             bool any = false;
 #pragma unroll
             for (int k = 0; k < 8; ++k) any |= fv[k] != 0;
             if (!any) continue;
-            short8 ev;
-            if (evec) {
-                ev = *reinterpret_cast<const short8 *>(e + x0);
-            } else {
-#pragma unroll
-                for (int k = 0; k < 8; ++k) ev[k] = e[x0 + k];
-            }
+            const short8 ev = load8(e + x0, evec);
             int o = x0 / mult_i, rem = x0 - o * mult_i, run = 0;
 #pragma unroll
             for (int k = 0; k < 8; ++k) {

@@ -12,13 +12,14 @@
 //                bitonic sort, and every chain of :92-205 walked by one wave in lockstep
 //   k_to_tiles<LONG>  the same for tiles above IBH_MAKE_TOPOO_MAX_TILE cells, with a counting sort in global scratch
 //   k_to_resets, k_to_blocks   :747-758 and :761-795
-// The row areas (make_dxyp, libm sin) are host tables uploaded by the handle, so a call only enqueues.
+// The row areas (make_dxyp, libm sin) are host tables uploaded by the handle, so a call only enqueues.  The 16-byte split of a tile's
+// row, the eight-cell loads, the LDS sort and the argument checks are planetile.h's, shared with globalec.hip and etopo1.hip.
 #include <algorithm>
 #include <climits>
 #include <memory>
 #include <vector>
 
-#include "common.h"
+#include "planetile.h"
 
 namespace ibh {
 namespace {
@@ -59,9 +60,6 @@ struct ibh_make_topoo {
 
 namespace ibh {
 namespace {
-typedef short short8 __attribute__((ext_vector_type(8)));
-
-inline long cdiv(long a, long b) { return (a + b - 1) / b; }
 
 // ---- :498-655, :681-692, :723: everything a cell takes from its own values ------------------------------------------------------
 __global__ __launch_bounds__(TO_T) void k_to_cells(double *__restrict__ planes, long ld, const double *__restrict__ zictop,
@@ -161,44 +159,9 @@ __global__ __launch_bounds__(TO_T) void k_to_gice(double *__restrict__ planes, l
 }
 
 // ---- callZ (:20-221) ---------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ short8 to_load8(const int16_t *p) {
-    if (((uintptr_t)p & 15) == 0) return *reinterpret_cast<const short8 *>(p);
-    short8 v;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) v[k] = p[k];
-    return v;
-}
 // a fine cell as the chains want it: the biased elevation in the high half, bit 1: FGICE1m != 0, bit 0: FOCEAN1m == 1
 __device__ __forceinline__ uint32_t to_pack(int zt, int fg, int fo) {
     return (uint32_t)(zt + 32768) << 16 | (fg != 0 ? 2u : 0u) | (fo == 1 ? 1u : 0u);
-}
-__device__ __forceinline__ double to_bcast(double v, int t) {
-    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), t), __builtin_amdgcn_readlane(__double2loint(v), t));
-}
-
-// R compare-exchange steps of the bitonic stage k on 2^R keys held in registers (etopo1.hip's pass)
-template <int R>
-__device__ __forceinline__ void to_bitonic_pass(uint32_t *s, int n2, int k, int j, int tid) {
-    constexpr int E = 1 << R;
-    const int jl = j >> (R - 1);
-    for (int t = tid; t < (n2 >> R); t += TO_T) {
-        const int base = ((t & ~(jl - 1)) << R) | (t & (jl - 1));
-        const bool asc = (base & k) == 0;
-        uint32_t e[E];
-#pragma unroll
-        for (int m = 0; m < E; ++m) e[m] = s[base + m * jl];
-#pragma unroll
-        for (int d = E >> 1; d > 0; d >>= 1) {
-#pragma unroll
-            for (int m = 0; m < E; ++m) {
-                if (m & d) continue;
-                const uint32_t a = e[m], b = e[m | d];
-                if ((a > b) == asc) { e[m] = b; e[m | d] = a; }
-            }
-        }
-#pragma unroll
-        for (int m = 0; m < E; ++m) s[base + m * jl] = e[m];
-    }
 }
 
 struct ToTiles {
@@ -216,7 +179,7 @@ struct ToTiles {
 // Workgroup b owns one ocean cell and its tile of w x mult_j fine cells, traversal position c = (J1m - J11) * w + (I1m - I11).
 // Short path: the tile is staged in LDS (elevation and two flag bits a cell, read in 16-byte pieces between a row's unaligned head
 // and tail); a land cell becomes the key (ZICETOP1m + 32768) << 16 | c, so ascending keys are (depth, traversal position); the keys
-// are appended in any order, padded with ~0 to a power of two and sorted by the bitonic network.  Long path: nothing is staged; the
+// are appended in any order and sorted by planetile.h's lds_sort_keys.  Long path: nothing is staged; the
 // land cells are counted per depth in global scratch, the counts scanned, and the cells placed 256 at a time in traversal order --
 // a cell goes to its depth's cursor plus the number of equal depths before it in its chunk -- which gives the same order.
 // Wave 0 then walks every chain in lockstep: 64 cells a step are fetched one a lane and broadcast lane by lane, and every lane
@@ -234,8 +197,7 @@ __global__ __launch_bounds__(TO_T) void k_to_tiles(ToTiles A) {
     const size_t jrow0 = (size_t)jO * h;
     const size_t base = jrow0 * (size_t)A.imI + (size_t)iO * w;
     const bool ocean = A.planes[P_FOCEAN * A.ld + xO] != 0;     // :69
-    int n2 = 1;
-    while (n2 < ncell) n2 <<= 1;
+    const int n2 = pow2_ceil(ncell);
     uint16_t *s_z = reinterpret_cast<uint16_t *>(s_key + (LONG ? 0 : n2));
     uint8_t *s_f = reinterpret_cast<uint8_t *>(s_z + (LONG ? 0 : ncell));
     uint32_t *cnt = LONG ? A.scratch + (size_t)blockIdx.x * ((size_t)TO_BINS + ncell) : nullptr, *ord = LONG ? cnt + TO_BINS : nullptr;
@@ -251,27 +213,27 @@ __global__ __launch_bounds__(TO_T) void k_to_tiles(ToTiles A) {
     };
 
     if (!LONG) {
-        // a row is a head of fewer than 8 cells up to FOCEAN1m's 16-byte boundary, whole pieces, and a tail of fewer than 8
+        // a row is FOCEAN1m's PlaneSplit: work items [0, P8) of a row are its pieces, the 16 after them its loose cells
         const int P8 = w >> 3, per = P8 + 16;
         for (int it = tid; it < h * per; it += TO_T) {
             const int r = it / per, k = it - r * per;
             const size_t x0 = base + (size_t)r * A.imI;
-            const int head = min(w, (int)(((16 - ((uintptr_t)(A.fo + x0) & 15)) & 15) >> 1));
-            const int np = (w - head) >> 3;
+            const PlaneSplit S = plane_split(A.fo + x0, (unsigned)w);
             if (k < P8) {
-                if (k >= np) continue;
-                const int c0 = head + 8 * k;
-                const short8 fo = *reinterpret_cast<const short8 *>(A.fo + x0 + c0);
-                const short8 zt = to_load8(A.zt + x0 + c0), fg = to_load8(A.fg + x0 + c0);
+                if (k >= (int)S.npiece) continue;
+                const int c0 = (int)S.piece((unsigned)k);
+                const int16_t *pzt = A.zt + x0 + c0, *pfg = A.fg + x0 + c0;
+                const short8 fo = load8(A.fo + x0 + c0, true);
+                const short8 zt = load8(pzt, ((uintptr_t)pzt & 15) == 0), fg = load8(pfg, ((uintptr_t)pfg & 15) == 0);
 #pragma unroll
                 for (int m = 0; m < 8; ++m) {
                     const uint32_t p = to_pack(zt[m], fg[m], fo[m]);
                     s_z[r * w + c0 + m] = (uint16_t)(p >> 16); s_f[r * w + c0 + m] = (uint8_t)(p & 3u);
                 }
             } else {
-                const int s = k - P8, tail = w - head - 8 * np;
-                if (s >= head + tail) continue;
-                const int c = s < head ? s : head + 8 * np + (s - head);
+                const int s = k - P8;
+                if (s >= (int)S.nloose((unsigned)w)) continue;
+                const int c = (int)S.cell((unsigned)s);
                 const uint32_t p = to_pack(A.zt[x0 + c], A.fg[x0 + c], A.fo[x0 + c]);
                 s_z[r * w + c] = (uint16_t)(p >> 16); s_f[r * w + c] = (uint8_t)(p & 3u);
             }
@@ -294,19 +256,7 @@ __global__ __launch_bounds__(TO_T) void k_to_tiles(ToTiles A) {
             if (!(p & 1u)) s_key[atomicAdd(&s_n, 1)] = (p & 0xFFFF0000u) | (uint32_t)c;
         }
         __syncthreads();
-        const int n = s_n;
-        int m2 = 1;
-        while (m2 < n) m2 <<= 1;
-        for (int c = n + tid; c < m2; c += TO_T) s_key[c] = 0xFFFFFFFFu;
-        __syncthreads();
-        for (int k = 2; k <= m2; k <<= 1) {
-            for (int j = k >> 1; j > 0;) {
-                if (j >= 4) { to_bitonic_pass<3>(s_key, m2, k, j, tid); j >>= 3; }
-                else if (j == 2) { to_bitonic_pass<2>(s_key, m2, k, j, tid); j = 0; }
-                else { to_bitonic_pass<1>(s_key, m2, k, j, tid); j = 0; }
-                __syncthreads();
-            }
-        }
+        lds_sort_keys<TO_T>(s_key, s_n, tid);
     } else {
         for (int c = tid; c < ncell; c += TO_T) {
             const uint32_t p = cell(c);
@@ -373,7 +323,7 @@ __global__ __launch_bounds__(TO_T) void k_to_tiles(ToTiles A) {
             const int cnt64 = min(64, ncell - b0);
             for (int t = 0; t < cnt64; ++t) {
                 const uint32_t p = (uint32_t)__builtin_amdgcn_readlane((int)pm, t);
-                const double area = to_bcast(am, t);
+                const double area = lane_bcast(am, t);
                 const double z = (double)((int)(p >> 16) - 32768);
                 if (ocean) SAREA += area;
                 if (p & 1u) continue;
@@ -431,7 +381,7 @@ __global__ __launch_bounds__(TO_T) void k_to_tiles(ToTiles A) {
             const int cnt64 = min(64, n - b0);
             for (int t = 0; t < cnt64; ++t) {
                 const double depth = (double)__builtin_amdgcn_readlane(dm, t);
-                const double area = to_bcast(am, t);
+                const double area = lane_bcast(am, t);
                 const int k = b0 + t;
                 if (k == 0) ZSGLO = depth;
                 dlast = depth;
@@ -520,39 +470,20 @@ __global__ __launch_bounds__(TO_T) void k_to_pow03(const double *__restrict__ x,
     if (g < n) out[g] = pow(x[g], .3);
 }
 
-bool overlap(const void *a, size_t na, const void *b, size_t nb) {
-    const uintptr_t A = (uintptr_t)a, B = (uintptr_t)b;
-    return A < B + nb && B < A + na;
-}
-
-struct ToArg {
-    const void *p;
-    size_t bytes;
-    const char *name;
-    int align;
-};
-
 // NULL planes, alignment, ld, the outputs over an input: all before a device is touched
 void check_planes(const ibh_make_topoo *h, const void *fgice, const void *zicetop, const void *zsolg, const void *focean, const void *flakes,
                   const void *planes, int64_t ld) {
     IBH_CHECK(h, "make_topoo: null handle");
     IBH_CHECK(ld >= h->nO(), "make_topoo: ld=%lld < %lld cells of hspecO", (long long)ld, (long long)h->nO());
     const size_t pb = sizeof(int16_t) * (size_t)h->nI();
-    const ToArg a[] = {{fgice, pb, "FGICE1m", 2}, {zicetop, pb, "ZICETOP1m", 2}, {zsolg, pb, "ZSOLG1m", 2}, {focean, pb, "FOCEAN1m", 2},
-                       {flakes, sizeof(double) * (size_t)h->nS(), "FLAKES", 8},
-                       {planes, sizeof(double) * ((size_t)(P_N - 1) * (size_t)ld + (size_t)h->nO()), "the output planes", 8}};
-    for (const ToArg &x : a) {
-        IBH_CHECK(x.p, "make_topoo: %s is null", x.name);
-        IBH_CHECK(((uintptr_t)x.p & (uintptr_t)(x.align - 1)) == 0, "make_topoo: %s is not aligned to %s", x.name, x.align == 8 ? "double" : "int16");
-    }
-    for (int k = 0; k < 5; ++k)
-        IBH_CHECK(!overlap(a[5].p, a[5].bytes, a[k].p, a[k].bytes), "make_topoo: the output planes overlap %s", a[k].name);
+    const PlaneArg a[] = {{fgice, pb, "FGICE1m", 2, false, false}, {zicetop, pb, "ZICETOP1m", 2, false, false}, {zsolg, pb, "ZSOLG1m", 2, false, false},
+                          {focean, pb, "FOCEAN1m", 2, false, false}, {flakes, sizeof(double) * (size_t)h->nS(), "FLAKES", 8, false, false},
+                          {planes, sizeof(double) * ((size_t)(P_N - 1) * (size_t)ld + (size_t)h->nO()), "the output planes", 8, true, false}};
+    check_plane_args("make_topoo", a, (int)(sizeof(a) / sizeof(a[0])), "%s: %s overlap %s");
 }
 
 size_t tiles_lds(int ncell) {
-    int n2 = 1;
-    while (n2 < ncell) n2 <<= 1;
-    return sizeof(uint32_t) * (size_t)n2 + sizeof(uint16_t) * (size_t)ncell + (size_t)ncell + 16;
+    return sizeof(uint32_t) * (size_t)pow2_ceil(ncell) + sizeof(uint16_t) * (size_t)ncell + (size_t)ncell + 16;
 }
 
 // the enqueue proper; every pointer is a device pointer
@@ -641,9 +572,7 @@ int ibh_make_topoo_create(ibh_make_topoo **out, int32_t imI, int32_t jmI, double
         for (int k = 0; k < nocean; ++k) set_to[(size_t)(ocean_ij[2 * k + 1] - 1) * imO + (ocean_ij[2 * k] - 1)] = 1;   // :449-494, after
         std::vector<int32_t> rx((size_t)nreset);
         for (int k = 0; k < nreset; ++k) rx[(size_t)k] = (reset_ij[2 * k + 1] - 1) * imO + (reset_ij[2 * k] - 1);
-        std::vector<double> dI((size_t)jmI), dO((size_t)jmO);
-        rethrow(ibh_hntr_dxyp(imI, jmI, dI.data()));
-        rethrow(ibh_hntr_dxyp(imO, jmO, dO.data()));
+        const std::vector<double> dI = dxyp_rows(imI, jmI), dO = dxyp_rows(imO, jmO);
         // the regridders check their grids on the host before they look for a device
         rethrow(ibh_hntr_create(&h->hntrI, imI, jmI, offiI, dlatI, imO, jmO, offiO, dlatO, 0.));
         rethrow(ibh_hntr_create(&h->hntrS, imS, jmS, offiS, dlatS, imO, jmO, offiO, dlatO, 0.));
