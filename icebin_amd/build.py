@@ -8,8 +8,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libicebin_hip.so")
-SOURCES = ["capi.hip", "spmm.hip", "prims.hip", "assemble.hip", "csrbuild.hip", "gridgen.hip", "comm.hip", "hntr.hip", "l1.hip", "lonlat.hip", "multivec.hip", "modele.hip", "csrops.hip", "csrcompose.hip", "globalave.hip", "globalec.hip", "etopo1.hip", "topoo.hip", "topo.hip", "sparseset.hip"]
-HEADERS = ["common.h", "apply_plan.h", "asm_plan.h", "smooth_plan.h", "plane_split.h", "planetile.h", "prims.h", "assemble.h", "csrbuild.h", "csrops.h", "modele_parts.h", "sparseset.h", "fastasm.inl", "streamasm.inl", "sweep_kernel.inl", os.path.join("..", "..", "include", "icebin_hip.h")]
+SOURCES = ["capi.hip", "spmm.hip", "prims.hip", "assemble.hip", "smooth.hip", "applystruct.hip", "csrbuild.hip", "gridgen.hip", "comm.hip", "hntr.hip", "l1.hip", "lonlat.hip", "multivec.hip", "modele.hip", "csrops.hip", "csrcompose.hip", "globalave.hip", "globalec.hip", "etopo1.hip", "topoo.hip", "topo.hip", "sparseset.hip"]
+HEADERS = ["common.h", "apply_plan.h", "asm_plan.h", "smooth_plan.h", "plane_split.h", "planetile.h", "prims.h", "assemble.h", "smooth.h", "applystruct.h", "csrbuild.h", "csrops.h", "modele_parts.h", "sparseset.h", "fastasm.inl", "streamasm.inl", "sweep_kernel.inl", os.path.join("..", "..", "include", "icebin_hip.h")]
 # -ffp-contract=off: the bookkeeping kernels must round every multiply and add separately
 # (bit-exact weights); the SpMM kernels ask for FMA explicitly with fma().
 # -amdgpu-kernarg-preload-count=16: the first 16 dwords of the kernel arguments arrive in SGPRs with the wave instead of

@@ -286,11 +286,11 @@ inline uint64_t next_weighted_uid() {
 }
 
 // ---- apply structures: optional copies of a matrix's entries in the order one apply kernel family wants them ------------------
-// Each is a value that owns its buffers: a builder (assemble.hip) fills a local one and returns it, `x = {}` empties it,
+// Each is a value that owns its buffers: a builder (applystruct.hip) fills a local one and returns it, `x = {}` empties it,
 // built() says whether it exists.
 
 // rowdual (EvI, EvX): the CSR filtered to one entry per (GCM cell, ice cell) carrying the weights of BOTH elevation classes
-// the cell lies between (assemble.hip build_bands); band r = row r
+// the cell lies between (applystruct.hip build_bands); band r = row r
 struct Bands {
     int64_t n = 0;                          // band entries, 0: not built
     int32_t nrow = 0;                       // bands = rows of the matrix
@@ -304,7 +304,7 @@ struct Bands {
 };
 
 // colsweep (EvI, EvX, and AvI, AvX in batched launches; sweep_kernel.inl): the entries in column order, paired per column into
-// items, 64 items a block, tb blocks a task with its local row table (assemble.hip build_sweep_from_csr)
+// items, 64 items a block, tb blocks a task with its local row table (applystruct.hip build_sweep_from_csr)
 struct Sweep {
     int32_t ntask = 0, nblk = 0, nprow = 0, nslot = 0;      // ntask == 0: not built
     int32_t tb = 0, nitems = 0, ident = 0;                  // blocks per task, items, column == item index
@@ -335,7 +335,7 @@ struct Pair {
 // rowgroup (EvI, EvX; spmm.hip): the rows of one GCM cell (its elevation classes) form a GROUP; the group's entries are
 // listed once per distinct column, ascending, as ITEMS {col, meta = slot0 | slot1 << 8 | has-bits, v0, v1} -- the column set
 // of a group is the AvI row of its GCM cell, so X is gathered once per (GCM cell, ice cell) instead of once per class; slot s
-// of group g is row slotrow[g * IBH_GSLOTS + s] (assemble.hip build_groups_from_csr).
+// of group g is row slotrow[g * IBH_GSLOTS + s] (applystruct.hip build_groups_from_csr).
 struct RowGroups {
     int32_t n = 0, nslot = 0, nitems = 0;           // groups (0: not built), most rows in a group, items
     DevBuf<int32_t> ptr, ns, slotrow, col;          // [n+1] items of a group; [n] rows of a group; [n*IBH_GSLOTS]; [nitems]
@@ -500,11 +500,6 @@ void spmm_launch_pair(const ibh_weighted *first, const ibh_weighted *second, con
                       int64_t ldb1, double *dB2, int64_t ldb2, double fill, hipStream_t stream);
 void spmm_launch_chain(const ibh_weighted *first, const ibh_weighted *second, const ibh_weighted *third, const double *dA, int nvar, int64_t lda,
                        double *dB1, int64_t ldb1, double *dB2, int64_t ldb2, double *dB3, int64_t ldb3, double fill, hipStream_t stream);
-// assemble.hip: the apply structures of a matrix from its CSR; an unbuilt value: the matrix is not eligible or the structure not
-// representable.  The handle is only read: the caller keeps what it gets.
-Bands build_bands_from_csr(const ibh_weighted *w, hipStream_t st);      // (same result as building them with the matrix)
-Sweep build_sweep_from_csr(const ibh_weighted *w, hipStream_t st);
-RowGroups build_groups_from_csr(const ibh_weighted *w, hipStream_t st); // (with their tiles, where those fit)
 void matvec_legacy_launch(const ibh_weighted *w, const double *dx, int nvar, int64_t ldx, double *dy, int64_t ldy,
                           int ignore_nan, hipStream_t stream);
 void spmm_transformed_launch(const ibh_weighted *w, const double *dA, int nvar_in, int64_t lda, const double *T,

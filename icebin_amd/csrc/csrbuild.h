@@ -1,7 +1,7 @@
 // csrbuild.h -- the triplets -> CSR layer (csrbuild.hip): contributions (key = (row, col), emission index, term) -> unique CSR
 // entries summed in emission order with the first term assigned, the row pointer, the row and column sums in spsparse's order, and
-// the COO entry points on top of them.  Every matrix builder of the library ends here: the exchange-grid assembly and the smoother
-// (assemble.hip), the CSR algebra (csrops.hip) and, through the COO entry points, hntr / l1 / modele / globalave.  Everything is
+// the COO entry points on top of them.  Every matrix builder of the library ends here: the exchange-grid assembly (assemble.hip), the smoother
+// (smooth.hip), the CSR algebra (csrops.hip) and, through the COO entry points, hntr / l1 / modele / globalave.  Everything is
 // enqueued on the caller's stream and uses the calling thread's arena; what waits for the device says so.
 #pragma once
 #include "common.h"
@@ -44,7 +44,7 @@ inline bool short_columns(long nnz, int ncol) { return nnz && nnz <= 4l * ncol; 
 // (col_sums_by_slots counts there the columns that went to k_col_sums_long).  Arena; enqueued on st.
 struct ColSlots { uint32_t *colptr = nullptr, *lidx = nullptr; int32_t *lrow = nullptr; uint32_t *nlong = nullptr; };
 ColSlots col_slots(const int32_t *colind, const int32_t *row, long nnz, int ncol, hipStream_t st);
-// cs = the column sums of w's CSR through per-column slots, for short_columns().  The slots are handed back for build_bands.
+// cs = the column sums of w's CSR through per-column slots, for short_columns().  The slots are handed back for build_bands (applystruct.h).
 // Enqueued on st.
 ColSlots col_sums_by_slots(const ibh_weighted *w, const int32_t *row, int ncol, double *cs, hipStream_t st);
 

@@ -2,6 +2,7 @@
 // stable LSD radix sort of (u64 key, u32 payload) pairs, hand-written for wave64.
 #pragma once
 #include "common.h"
+#include <utility>
 
 namespace ibh {
 
@@ -48,6 +49,11 @@ void exclusive_scan3(const uint32_t *pk, size_t n, uint32_t *o0, uint32_t *o1, u
 struct KeyField { int shift, nbits; };
 bool radix_sort_pairs(uint64_t *keys, uint64_t *keys_alt, uint32_t *vals, uint32_t *vals_alt, size_t n,
                       const KeyField *fields, int nfields, hipStream_t stream);
+// "sort, result in front": the same sort; afterwards (keys, vals) name the sorted pairs and (keys_alt, vals_alt) the other half
+inline void radix_sort_pairs_front(uint64_t *&keys, uint64_t *&keys_alt, uint32_t *&vals, uint32_t *&vals_alt, size_t n,
+                                   const KeyField *fields, int nfields, hipStream_t stream) {
+    if (radix_sort_pairs(keys, keys_alt, vals, vals_alt, n, fields, nfields, stream)) { std::swap(keys, keys_alt); std::swap(vals, vals_alt); }
+}
 
 // Same result as radix_sort_pairs on key = (hi field at bit 32, lo field at bit 0), but first tries
 // to finish in one analysis pass + LDS sorts of the independent pieces the sequence splits into

@@ -1,6 +1,6 @@
 // smooth_plan.h -- how a smoothed build (sigma != 0, DESIGN K5) runs, decided once, as plain values: the bin geometry, the device
 // forms in the order they are tried, the LDS layout of the tile kernel and the split of a shared tile build among the ranks
-// (assemble.hip's smooth_matrix walks them).  Host arithmetic over the centroids' bounding box, the sigmas, the tuning map and a bin
+// (smooth.hip's smooth_matrix walks them).  Host arithmetic over the centroids' bounding box, the sigmas, the tuning map and a bin
 // histogram: no HIP (tests/cpp/test_smooth_plan.cpp).
 #pragma once
 #include <algorithm>

@@ -25,6 +25,7 @@
 //    Y stores -- is fully coalesced (512 B per wave-store, non-temporal); the
 //    small X (nf x nA_d) is served from L2.
 #include "common.h"
+#include "applystruct.h"
 #include "sweep_kernel.inl"
 #include <hip/hip_ext.h>
 #include <mutex>
@@ -219,7 +220,7 @@ struct BatchPtrs {
 // of these matrices is fetched twice (measured: 2.0 GB for 1.03 GB algorithmic at 1 km).  The kernel
 // then stores the two partial sums of the band (Y = lower-class sums, Y2 = upper-class sums, no
 // fill); dual_combine_kernel adds, for every row, its own lower sum and the upper sum of the band
-// below it.  The band arrays are a filtered copy of the CSR (assemble.hip build_bands).
+// below it.  The band arrays are a filtered copy of the CSR (applystruct.hip build_bands).
 template <int FPW, int WK, int UNROLL, int NW, bool DUAL = false>
 __global__ __launch_bounds__(NW * 64, (FPW == 1 && !DUAL) ? 8 : 1) void spmm_rowblock_kernel(
     const int *__restrict__ rowptr, const int *__restrict__ colind, const double *__restrict__ vals,
@@ -488,7 +489,7 @@ __global__ __launch_bounds__(NW * 64, 8) void spmm_rowone_kernel(
 // every X element is gathered twice, and each of the ~10 class rows of a GCM cell touches ~15 % of the cell's footprint: most
 // of every line it fetches belongs to other classes (5 km EvI: ~100 MB effective for a 42 MB apply).  Here the rows of one GCM
 // cell form a GROUP whose entries are listed once per distinct column, ascending, as items {col, slot0, slot1, v0, v1}
-// (assemble.hip build_groups_from_csr): the column set of a group is the AvI row of its GCM cell -- a contiguous run behind a
+// (applystruct.hip build_groups_from_csr): the column set of a group is the AvI row of its GCM cell -- a contiguous run behind a
 // few cells shared with earlier GCM cells -- so the gathers are those of the A-row kernel: every X element once, whole lines.
 // Lane = column, wave = field (as rowone): lane L multiplies its column's value into the sums of the column's two classes,
 // kept in a per-wave LDS table acc[slot][lane] (bank = lane: conflict-free whatever the slots); at the end one wave_sum per
@@ -662,7 +663,7 @@ __global__ __launch_bounds__(NW * 64) void spmm_rowgroup_kernel(const GroupView 
 // ---- grouptile: the row groups with X staged through LDS and register sums (round 5) ---------------------------------------------
 // What bounded the row-group kernel above was the LDS pipe: wave = field, lane = column, so every wave re-read each item's
 // {col, meta, v0, v1} and issued two ds_add_f64 per item (~56 B through LDS per item and field).  Here the roles are turned:
-// the columns of a group are cut into TILES of SEG = 256 or 128 items (assemble.hip build_group_tiles); a workgroup serves (group, F
+// the columns of a group are cut into TILES of SEG = 256 or 128 items (applystruct.hip build_group_tiles); a workgroup serves (group, F
 // fields, F = 16 or 32) and for every tile
 //   1. gathers X[f, col[k]] for the tile's items -- lane = item, one field per load, exactly the gathers of the kernel above:
 //      every X element once per GCM cell, whole lines -- into an LDS tile s_x[f][k];

@@ -3,7 +3,7 @@
 //
 // Row by row an E-row matrix reads every X element once per class row it feeds (measured at 1 km: 2.0 GB fetched for
 // 1.03 GB algorithmic); the band structure (rowdual) still wastes 64-byte lines (1.39 x).  Here ALL columns are swept
-// ONCE, in ascending order.  The structure (assemble.hip build_sweep_from_csr): entries ordered by column and paired
+// ONCE, in ascending order.  The structure (applystruct.hip build_sweep_from_csr): entries ordered by column and paired
 // into ITEMS (a column + <= 2 of its entries), 64 items a block, tb blocks a task; a task's local row table = the distinct
 // rows its columns touch ("slots").  Per block:
 //   load     the four waves of a workgroup bring the block's X tile (64 planes x 64 columns) in with plain loads, lane =

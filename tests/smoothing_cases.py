@@ -1,5 +1,5 @@
 """Which device form a smoothed build must take, decided on the CPU from the oracle's matrices: a numpy transcription of the bin
-arithmetic (icebin_amd/csrc/smooth_plan.h smooth_grid, assemble.hip smooth_bin / k_smt_bincols) gives the quantities the forms' limits
+arithmetic (icebin_amd/csrc/smooth_plan.h smooth_grid, smooth.hip smooth_bin / k_smt_bincols) gives the quantities the forms' limits
 are about, so that a test first asserts that its input lies on the intended side of a limit and only then which form ran
 (linear_Weighted.smoothed_by): an input that drifts fails loudly instead of testing another form.
 

@@ -325,6 +325,26 @@ def test_every_sorted_grid_assembly_kernel_has_a_case(lib, tmp_path):
             assert module == "test_gpu_assembly_limits.py" and case in {c["name"] for c in alc.CASES}, (kernel, test)
 
 
+def test_smoother_and_apply_structure_kernels_live_in_their_own_units(lib, tmp_path):
+    # the unit boundary, by kernel name: smooth.o holds the smoother's kernels and nothing else, applystruct.o the kernels of the
+    # apply-structure builders (bands, sweep, row groups, tiles, the row expansions and the run heads the builders share; it
+    # includes sweep_kernel.inl for the item meta bits only and instantiates no kernel of it), and assemble.o holds none of either
+    smoother = r"k_smooth_|k_smt_"
+    builders = r"k_band_|k_sw_|k_rg_|k_gt_|k_expand_|k_key_heads$"
+
+    def names(unit):
+        mangled = re.findall(r"^    \.name:\s+(\S+)", code_object_notes(tmp_path, unit), re.M)
+        heads = [re.match(r"_ZN3ibh(\d+)", m) for m in mangled]
+        assert all(heads), sorted(mangled)              # every kernel is named directly in namespace ibh
+        return sorted(m[h.end():h.end() + int(h.group(1))] for m, h in zip(mangled, heads))
+
+    in_smooth, in_builders, in_assembly = names("smooth"), names("applystruct"), names("assemble")
+    assert len(in_smooth) >= 18 and all(re.match(smoother, n) for n in in_smooth), in_smooth
+    assert len(in_builders) >= 20 and all(re.match(builders, n) for n in in_builders), in_builders
+    strays = [n for n in in_assembly if re.match(smoother + "|" + builders, n)]
+    assert not strays, strays
+
+
 def csr_build_cases_module():
     import sys
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))

@@ -1,4 +1,4 @@
-"""The smoother's three device forms (assemble.hip: the triplet pipeline, the wave-per-row direct form, the spatial tiles) at their bin,
+"""The smoother's three device forms (smooth.hip: the triplet pipeline, the wave-per-row direct form, the spatial tiles) at their bin,
 wave and table edges, each against the oracle and, where the scene is small, against the long-double definition within the derived
 entry bound (tests/smoothing_cases.py; tests/test_smoothing_cases.py asserts on the CPU that every scene lies where its leg needs it).
 Every leg first asserts its input's side of the limits, then which form built the matrix, then the matrix."""
