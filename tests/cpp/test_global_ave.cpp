@@ -10,36 +10,15 @@
 #include <string>
 #include <vector>
 
-#include "../../icebin_amd/host/icebin_hip.hpp"
+#include "host_test.h"
 
 using namespace icebin;
 using icebin::modele::HntrSpec;
 
-#define REQUIRE(cond)                                                        \
-    do {                                                                     \
-        if (!(cond)) { std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); return 1; } \
-    } while (0)
-
-template <class T>
-static bool dump(std::string const &path, std::vector<T> const &v) {
-    FILE *f = std::fopen(path.c_str(), "wb");
-    if (!f) return false;
-    const int64_t n = (int64_t)v.size();
-    bool ok = std::fwrite(&n, sizeof(n), 1, f) == 1 && std::fwrite(v.data(), sizeof(T), v.size(), f) == v.size();
-    return std::fclose(f) == 0 && ok;
-}
-
-// a matrix as <name>.row/.col (int32), .val/.wM/.Mw (f64), .dim0/.dim1 (int64), .extent (int64[2])
-static bool dump_matrix(std::string const &out, std::string const &name, linear::Weighted const &w) {
-    std::vector<int> r, c;
-    std::vector<double> v;
-    w.M_coo(r, c, v);
-    std::vector<int64_t> d0, d1, ext = {w.shape()[0], w.shape()[1]};
-    for (long x : w.dim_to_sparse(0)) d0.push_back(x);
-    for (long x : w.dim_to_sparse(1)) d1.push_back(x);
-    return dump(out + "/" + name + ".row", r) && dump(out + "/" + name + ".col", c) && dump(out + "/" + name + ".val", v) &&
-           dump(out + "/" + name + ".wM", w.wM()) && dump(out + "/" + name + ".Mw", w.Mw()) && dump(out + "/" + name + ".dim0", d0) &&
-           dump(out + "/" + name + ".dim1", d1) && dump(out + "/" + name + ".extent", ext);
+// dump_matrix's files and .extent (int64[2])
+static bool dump_matrix_extent(std::string const &out, std::string const &name, linear::Weighted const &w) {
+    std::vector<int64_t> ext = {w.shape()[0], w.shape()[1]};
+    return dump_matrix(out, name, w) && dump(out + "/" + name + ".extent", ext);
 }
 
 static bool dump_classes(std::string const &out, std::string const &name, modele::EOpvAOpResult const &eo) {
@@ -92,21 +71,21 @@ int main(int argc, char **argv) {
         modele::EOpvAOpResult eo = modele::compute_EOpvAOp_merged(dimAOp, base, gcmO.get(), emIs, true, true, false);
         REQUIRE(eo.offsetE == 3 * nO && eo.hcdefs.size() == 5 && eo.underice_hc[2] == modele::UI_LOCALICE && eo.underice_hc[3] == modele::UI_GLOBALICE);
         REQUIRE(eo.dimEOp->sparse_extent() == 5 * nO && dimAOp.sparse_extent() == nO && !eo.EOpvAOp->scaled);
-        REQUIRE(dump_matrix(out, "EOpvAOp", *eo.EOpvAOp) && dump_classes(out, "EOpvAOp", eo));
+        REQUIRE(dump_matrix_extent(out, "EOpvAOp", *eo.EOpvAOp) && dump_classes(out, "EOpvAOp", eo));
         SparseSetT dimAOp2;
         modele::EOpvAOpResult sq = modele::compute_EOpvAOp_merged(dimAOp2, base, gcmO.get(), emIs, true, true, true);
         REQUIRE(sq.hcdefs.size() == 4 && sq.dimEOp->sparse_extent() == 4 * nO);
-        REQUIRE(dump_matrix(out, "EOpvAOp_sq", *sq.EOpvAOp) && dump_classes(out, "EOpvAOp_sq", sq));
+        REQUIRE(dump_matrix_extent(out, "EOpvAOp_sq", *sq.EOpvAOp) && dump_classes(out, "EOpvAOp_sq", sq));
 
         auto AvE_s = modele::_compute_AAmvEAm(true, eq_rad, hspecO, ArrayView<const double>(foceanOp), ArrayView<const double>(foceanOm), eo, dimAOp);
         REQUIRE(!AvE_s->conservative && AvE_s->scaled && AvE_s->shape()[0] == 12 && AvE_s->shape()[1] == 60);
-        REQUIRE(dump_matrix(out, "AvE_s", *AvE_s));
+        REQUIRE(dump_matrix_extent(out, "AvE_s", *AvE_s));
         SparseSetT dimAAm, dimEAm;
         auto AvE_sq = modele::_compute_AAmvEAm_EIGEN({{&dimAAm, &dimEAm}}, false, eq_rad, hspecO, sq.indexingHC_strides, {{1, 12}}, 4,
                                                     ArrayView<const double>(foceanOp), ArrayView<const double>(foceanOm), *sq.EOpvAOp,
                                                     *sq.dimEOp, dimAOp2);
         REQUIRE(dimAAm.dense_extent() == AvE_sq->shape_d()[0] && dimEAm.sparse_extent() == 48 && !AvE_sq->scaled);
-        REQUIRE(dump_matrix(out, "AvE_sq", *AvE_sq));
+        REQUIRE(dump_matrix_extent(out, "AvE_sq", *AvE_sq));
 
         modele::GCMRegridder_ModelE gcmA(base, gcmO, hspecO, eq_rad);
         REQUIRE(gcmA.hcdefs().size() == 5 && gcmA.hcdefs()[3] == 1500. && gcmA.underice(2) == modele::UI_LOCALICE &&
@@ -114,7 +93,7 @@ int main(int argc, char **argv) {
         long offsetE = -1;
         auto AvE_u = gcmA.global_AvE({}, emIs, ArrayView<const double>(foceanOp), ArrayView<const double>(foceanOm), false, offsetE);
         REQUIRE(offsetE == 3 * nO && !AvE_u->scaled);
-        REQUIRE(dump_matrix(out, "AvE_u", *AvE_u));
+        REQUIRE(dump_matrix_extent(out, "AvE_u", *AvE_u));
 
         // a base index outside its shape; a ModelE ocean that is neither 0 nor 1 on a cell with ice
         modele::EOpvAOpBase bad = base;
@@ -134,10 +113,7 @@ int main(int argc, char **argv) {
             REQUIRE(e.code == IBH_EINVAL && std::string(e.what()).find("fcont_m[7]") != std::string::npos);
         }
     } catch (Exception const &e) {
-        if (e.code == IBH_ENODEVICE) {
-            std::printf("no GPU: %s (no CPU fallback)\n", e.what());
-            return 3;
-        }
+        if (no_gpu(e)) return 3;
         std::printf("FAILED: exception %d: %s\n", e.code, e.what());
         return 1;
     }

@@ -9,16 +9,11 @@
 #include <string>
 #include <vector>
 
-#include "../../icebin_amd/host/icebin_hip.hpp"
+#include "host_test.h"
 
 using namespace icebin;
 using icebin::modele::Hntr;
 using icebin::modele::HntrSpec;
-
-#define REQUIRE(cond)                                                        \
-    do {                                                                     \
-        if (!(cond)) { std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); return 1; } \
-    } while (0)
 
 static std::vector<double> serial_regrid(HntrSpec const &B, HntrSpec const &A, double DATMIS, std::vector<double> const &WTA,
                                          std::vector<double> const &Av, bool mean_polar, double wtm, double wtb) {

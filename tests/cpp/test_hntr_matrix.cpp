@@ -8,7 +8,7 @@
 #include <string>
 #include <vector>
 
-#include "../../icebin_amd/host/icebin_hip.hpp"
+#include "host_test.h"
 
 using namespace icebin;
 using icebin::modele::DenseTransform;
@@ -17,11 +17,6 @@ using icebin::modele::Hntr;
 using icebin::modele::HntrMatrix;
 using icebin::modele::HntrSpec;
 
-#define REQUIRE(cond)                                                        \
-    do {                                                                     \
-        if (!(cond)) { std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); return 1; } \
-    } while (0)
-
 // a user accumulator in the reference's shape: add({iB, iA}, value)
 struct Collect {
     std::vector<int> iB, iA;
@@ -29,6 +24,7 @@ struct Collect {
     void add(std::array<int, 2> const &ix, double v) { iB.push_back(ix[0]); iA.push_back(ix[1]); val.push_back(v); }
 };
 
+// its own format, three arrays under one count: <long n><n int><n int><n double>
 static bool dump(std::string const &path, std::vector<int> const &a, std::vector<int> const &b, std::vector<double> const &v) {
     FILE *f = std::fopen(path.c_str(), "wb");
     if (!f) return false;
@@ -84,10 +80,7 @@ int main(int argc, char **argv) {
         REQUIRE(S->shape_d()[0] == B.size() && S->shape_d()[1] == A.size() && S->scaled);
         REQUIRE(S->dim_to_sparse(0).size() == (size_t)B.size());
     } catch (Exception const &e) {
-        if (e.code == IBH_ENODEVICE) {
-            std::printf("no GPU: %s (no CPU fallback)\n", e.what());
-            return 3;
-        }
+        if (no_gpu(e)) return 3;
         std::printf("FAILED: exception %d: %s\n", e.code, e.what());
         return 1;
     }

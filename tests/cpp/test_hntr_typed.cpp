@@ -10,17 +10,12 @@
 #include <string>
 #include <vector>
 
-#include "../../icebin_amd/host/icebin_hip.hpp"
+#include "host_test.h"
 
 using namespace icebin;
 using icebin::modele::ConstWeight;
 using icebin::modele::Hntr;
 using icebin::modele::HntrSpec;
-
-#define REQUIRE(cond)                                                        \
-    do {                                                                     \
-        if (!(cond)) { std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); return 1; } \
-    } while (0)
 
 static bool same_bits(std::vector<double> const &a, std::vector<double> const &b) {
     return a.size() == b.size() && std::memcmp(a.data(), b.data(), a.size() * sizeof(double)) == 0;

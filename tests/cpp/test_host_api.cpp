@@ -8,15 +8,10 @@
 #include <string>
 #include <vector>
 
-#include "../../icebin_amd/host/icebin_hip.hpp"
+#include "host_test.h"
 
 using namespace icebin;
 static const double NaN = std::nan("");
-
-#define REQUIRE(cond)                                                        \
-    do {                                                                     \
-        if (!(cond)) { std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); return 1; } \
-    } while (0)
 
 int main(int argc, char **argv) {
     // ---- a 12 x 10 ice grid (cell 1 x 1) under a 3 x 2 atmosphere block (cell 4.5 x 5.5), nA = 8 x 4

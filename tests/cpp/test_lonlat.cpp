@@ -7,14 +7,9 @@
 #include <string>
 #include <vector>
 
-#include "../../icebin_amd/host/icebin_hip.hpp"
+#include "host_test.h"
 
 using namespace icebin;
-
-#define REQUIRE(cond)                                                        \
-    do {                                                                     \
-        if (!(cond)) { std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); return 1; } \
-    } while (0)
 
 int main() {
     const std::string sproj = "+proj=stere +lon_0=-39 +lat_0=90 +lat_ts=71.0 +ellps=WGS84";

@@ -7,23 +7,10 @@
 #include <string>
 #include <vector>
 
-#include "../../icebin_amd/host/icebin_hip.hpp"
+#include "host_test.h"
 
 using namespace icebin;
 using icebin::modele::HntrSpec;
-
-#define REQUIRE(cond)                                                        \
-    do {                                                                     \
-        if (!(cond)) { std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); return 1; } \
-    } while (0)
-
-static bool dump(std::string const &path, std::vector<double> const &v) {
-    FILE *f = std::fopen(path.c_str(), "wb");
-    if (!f) return false;
-    const int64_t n = (int64_t)v.size();
-    bool ok = std::fwrite(&n, sizeof(n), 1, f) == 1 && std::fwrite(v.data(), sizeof(double), v.size(), f) == v.size();
-    return std::fclose(f) == 0 && ok;
-}
 
 int main(int argc, char **argv) {
     const std::string out = argc > 1 ? argv[1] : ".";
@@ -96,10 +83,7 @@ int main(int argc, char **argv) {
             REQUIRE(std::string(e.what()) == "Continental cell (1,1) has no continental area on 2-minute grid. (1-48, 1-4)");
         }
     } catch (Exception const &e) {
-        if (e.code == IBH_ENODEVICE) {
-            std::printf("no GPU: %s (no CPU fallback)\n", e.what());
-            return 3;
-        }
+        if (no_gpu(e)) return 3;
         std::printf("FAILED: exception %d: %s\n", e.code, e.what());
         return 1;
     }

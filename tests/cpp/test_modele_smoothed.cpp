@@ -8,17 +8,12 @@
 #include <string>
 #include <vector>
 
-#include "../../icebin_amd/host/icebin_hip.hpp"
+#include "host_test.h"
 
 using namespace icebin;
 using icebin::modele::HntrSpec;
 
-#define REQUIRE(cond)                                                        \
-    do {                                                                     \
-        if (!(cond)) { std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); return 1; } \
-    } while (0)
-
-// <int64 n><n values>
+// dump()'s format read back: <int64 n><n values>
 template <class T>
 static std::vector<T> load(std::string const &path) {
     std::vector<T> v;
@@ -31,25 +26,6 @@ static std::vector<T> load(std::string const &path) {
     }
     std::fclose(f);
     return v;
-}
-template <class T>
-static bool dump(std::string const &path, std::vector<T> const &v) {
-    FILE *f = std::fopen(path.c_str(), "wb");
-    if (!f) return false;
-    const int64_t n = (int64_t)v.size();
-    bool ok = std::fwrite(&n, sizeof(n), 1, f) == 1 && std::fwrite(v.data(), sizeof(T), v.size(), f) == v.size();
-    return std::fclose(f) == 0 && ok;
-}
-static bool dump_matrix(std::string const &out, std::string const &name, linear::Weighted const &w) {
-    std::vector<int> r, c;
-    std::vector<double> v;
-    w.M_coo(r, c, v);
-    std::vector<int64_t> d0, d1;
-    for (long x : w.dim_to_sparse(0)) d0.push_back(x);
-    for (long x : w.dim_to_sparse(1)) d1.push_back(x);
-    return dump(out + "/" + name + ".row", r) && dump(out + "/" + name + ".col", c) && dump(out + "/" + name + ".val", v) &&
-           dump(out + "/" + name + ".wM", w.wM()) && dump(out + "/" + name + ".Mw", w.Mw()) && dump(out + "/" + name + ".dim0", d0) &&
-           dump(out + "/" + name + ".dim1", d1);
 }
 
 int main(int argc, char **argv) {
@@ -103,10 +79,7 @@ int main(int argc, char **argv) {
         try { rm->matrix_d("XvE", {{nullptr, &dimE}}, smoothed); REQUIRE(false); } catch (Exception const &e) { REQUIRE(e.code == IBH_ENOTIMPL); }
         REQUIRE(dimE.dense_extent() == nE);
     } catch (Exception const &e) {
-        if (e.code == IBH_ENODEVICE) {
-            std::printf("no GPU: %s (no CPU fallback)\n", e.what());
-            return 3;
-        }
+        if (no_gpu(e)) return 3;
         std::printf("FAILED: exception %d: %s\n", e.code, e.what());
         return 1;
     }

@@ -7,14 +7,9 @@
 #include <limits>
 #include <vector>
 
-#include "../../icebin_amd/host/icebin_hip.hpp"
+#include "host_test.h"
 
 using namespace icebin;
-
-#define REQUIRE(cond)                                                        \
-    do {                                                                     \
-        if (!(cond)) { std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); return 1; } \
-    } while (0)
 
 static bool same_bits(double a, double b) { return std::memcmp(&a, &b, sizeof(double)) == 0; }
 

@@ -11,24 +11,10 @@
 #include <string>
 #include <vector>
 
-#include "../../icebin_amd/host/icebin_hip.hpp"
+#include "host_test.h"
 
 using namespace icebin;
 using icebin::modele::HntrSpec;
-
-#define REQUIRE(cond)                                                        \
-    do {                                                                     \
-        if (!(cond)) { std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); return 1; } \
-    } while (0)
-
-template <class T>
-static bool dump(std::string const &path, std::vector<T> const &v) {
-    FILE *f = std::fopen(path.c_str(), "wb");
-    if (!f) return false;
-    const int64_t n = (int64_t)v.size();
-    bool ok = std::fwrite(&n, sizeof(n), 1, f) == 1 && std::fwrite(v.data(), sizeof(T), v.size(), f) == v.size();
-    return std::fclose(f) == 0 && ok;
-}
 
 static bool dump_vec(std::string const &prefix, VectorMultivec const &v) {
     std::vector<long> ix = v.index();
@@ -187,10 +173,7 @@ int main(int argc, char **argv) {
             }
         }
     } catch (Exception const &e) {
-        if (e.code == IBH_ENODEVICE) {
-            std::printf("no GPU: %s (no CPU fallback)\n", e.what());
-            return 3;
-        }
+        if (no_gpu(e)) return 3;
         std::printf("FAILED: exception %d: %s\n", e.code, e.what());
         return 1;
     }

@@ -1,48 +1,20 @@
 """Compiles the C++ test of etopo1_ice (tests/cpp/test_etopo1_ice.cpp) against libicebin_hip.so (g++, no HIP headers needed),
 runs it, and compares its planes with the Python surface (icebin_amd.etopo1), bitwise."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
-from icebin_amd import _capi
-from icebin_amd.build import build_library
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EXE = os.path.join(ROOT, "tests", "cpp", "test_etopo1_ice")
-
-
-def compile_exe():
-    lib = build_library()
-    src = os.path.join(ROOT, "tests", "cpp", "test_etopo1_ice.cpp")
-    hdrs = [os.path.join(ROOT, "icebin_amd", "host", h) for h in ("icebin_hip.hpp", "ncio.hpp")]
-    libdir = os.path.dirname(lib)
-    if (not os.path.exists(EXE)) or os.path.getmtime(EXE) < max(os.path.getmtime(f) for f in [src, lib] + hdrs):
-        subprocess.check_call(["g++", "-std=c++14", "-O1", "-Wall", "-o", EXE, src, "-L" + libdir, "-licebin_hip",
-                               "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib"])
-    return EXE
-
-
-def read(path, dtype):
-    with open(path, "rb") as f:
-        n = int(np.frombuffer(f.read(8), np.int64)[0])
-        return np.frombuffer(f.read(np.dtype(dtype).itemsize * n), dtype)
+import cpp_programs as cpp
+from cpp_programs import read
 
 
 def test_cpp_etopo1_ice_compiles_and_fails_loudly_without_gpu(tmp_path):
-    exe = compile_exe()
-    if _capi.device_count() > 0:
-        pytest.skip("GPU present: covered by the gpu-marked test")
-    r = subprocess.run([exe, str(tmp_path)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 3, r.stdout + r.stderr
-    assert "no CPU fallback" in r.stdout
+    cpp.fails_loudly_without_gpu("test_etopo1_ice", tmp_path, timeout=300)
 
 
 @pytest.mark.gpu
 def test_cpp_etopo1_ice_on_gpu(tmp_path):
     from icebin_amd import HntrSpec, etopo1
-    r = subprocess.run([compile_exe(), str(tmp_path)], capture_output=True, text=True, timeout=600)
+    r = cpp.run(cpp.exe("test_etopo1_ice", allow_compile=False), tmp_path, timeout=600)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "all checks passed" in r.stdout
     Cg, I, H = HntrSpec(8, 4, 0., 2700.), HntrSpec(32, 16, 0., 675.), HntrSpec(16, 8, 0., 1350.)

@@ -1,30 +1,13 @@
 """Compiles the C++ test of Hntr's matrix forms (tests/cpp/test_hntr_matrix.cpp) against libicebin_hip.so (g++, no HIP headers
 needed), runs it, and compares what its accumulators and matrix_d produced with the Python surface, bitwise."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
-from icebin_amd import _capi
-from icebin_amd.build import build_library
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EXE = os.path.join(ROOT, "tests", "cpp", "test_hntr_matrix")
-
-
-def compile_exe():
-    lib = build_library()
-    src = os.path.join(ROOT, "tests", "cpp", "test_hntr_matrix.cpp")
-    hdrs = [os.path.join(ROOT, "icebin_amd", "host", h) for h in ("icebin_hip.hpp", "ncio.hpp")]
-    libdir = os.path.dirname(lib)
-    if (not os.path.exists(EXE)) or os.path.getmtime(EXE) < max(os.path.getmtime(f) for f in [src, lib] + hdrs):
-        subprocess.check_call(["g++", "-std=c++14", "-O1", "-Wall", "-o", EXE, src, "-L" + libdir, "-licebin_hip",
-                               "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib"])
-    return EXE
+import cpp_programs as cpp
 
 
 def read(path):
+    """the program's own format, three arrays under one count (its four-argument dump)"""
     with open(path, "rb") as f:
         n = int(np.frombuffer(f.read(8), np.int64)[0])
         a = np.frombuffer(f.read(4 * n), np.int32)
@@ -34,18 +17,13 @@ def read(path):
 
 
 def test_cpp_hntr_matrix_compiles_and_fails_loudly_without_gpu(tmp_path):
-    exe = compile_exe()
-    if _capi.device_count() > 0:
-        pytest.skip("GPU present: covered by the gpu-marked test")
-    r = subprocess.run([exe, str(tmp_path)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 3, r.stdout + r.stderr
-    assert "no CPU fallback" in r.stdout
+    cpp.fails_loudly_without_gpu("test_hntr_matrix", tmp_path, timeout=300)
 
 
 @pytest.mark.gpu
 def test_cpp_hntr_matrix_on_gpu(tmp_path):
     from icebin_amd import Hntr, HntrSpec, SparseSet
-    r = subprocess.run([compile_exe(), str(tmp_path)], capture_output=True, text=True, timeout=300)
+    r = cpp.run(cpp.exe("test_hntr_matrix", allow_compile=False), tmp_path, timeout=300)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "all checks passed" in r.stdout
     B, A = HntrSpec(72, 46, 0.5, 240.), HntrSpec(144, 90, 0.25, 120.)

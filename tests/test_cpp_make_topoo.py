@@ -1,39 +1,16 @@
 """Compiles the C++ test of make_topoO (tests/cpp/test_make_topoo.cpp) against libicebin_hip.so (g++, no HIP headers needed),
 runs it, and compares its planes with the Python surface (icebin_amd.topoo), bitwise."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
+import cpp_programs as cpp
 from icebin_amd import _capi
-from icebin_amd.build import build_library
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EXE = os.path.join(ROOT, "tests", "cpp", "test_make_topoo")
-
-
-def compile_exe():
-    lib = build_library()
-    src = os.path.join(ROOT, "tests", "cpp", "test_make_topoo.cpp")
-    hdrs = [os.path.join(ROOT, "icebin_amd", "host", h) for h in ("icebin_hip.hpp", "ncio.hpp")]
-    libdir = os.path.dirname(lib)
-    if (not os.path.exists(EXE)) or os.path.getmtime(EXE) < max(os.path.getmtime(f) for f in [src, lib] + hdrs):
-        subprocess.check_call(["g++", "-std=c++14", "-O1", "-Wall", "-o", EXE, src, "-L" + libdir, "-licebin_hip",
-                               "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib"])
-    return EXE
-
-
-def read(path):
-    with open(path, "rb") as f:
-        n = int(np.frombuffer(f.read(8), np.int64)[0])
-        return np.frombuffer(f.read(8 * n), np.float64)
 
 
 def test_cpp_make_topoo_compiles_and_fails_loudly_without_gpu(tmp_path):
-    """the refusals that need no device run either way; without a GPU the first call that needs one says so"""
-    exe = compile_exe()
-    r = subprocess.run([exe, str(tmp_path)], capture_output=True, text=True, timeout=300)
+    """the refusals that need no device run either way; without a GPU the first call that needs one says so.  (Not
+    cpp.fails_loudly_without_gpu, which skips where there is a device: this one runs there too and must pass.)"""
+    r = cpp.run(cpp.exe("test_make_topoo"), tmp_path, timeout=300)
     if _capi.device_count() > 0:
         assert r.returncode == 0, r.stdout + r.stderr
     else:
@@ -44,7 +21,7 @@ def test_cpp_make_topoo_compiles_and_fails_loudly_without_gpu(tmp_path):
 @pytest.mark.gpu
 def test_cpp_make_topoo_on_gpu(tmp_path):
     from icebin_amd import HntrSpec, topoo
-    r = subprocess.run([compile_exe(), str(tmp_path)], capture_output=True, text=True, timeout=600)
+    r = cpp.run(cpp.exe("test_make_topoo", allow_compile=False), tmp_path, timeout=600)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "all checks passed" in r.stdout
     O, I, S = HntrSpec(12, 12, 0., 900.), HntrSpec(48, 48, 0., 225.), HntrSpec(18, 9, 0., 1200.)
@@ -57,5 +34,5 @@ def test_cpp_make_topoo_on_gpu(tmp_path):
     fl = np.where(k % 4 == 0, 0., (k % 9) / 16.0)
     res = topoo.make_topoO(I, O, fg, zt, zs, fo, S, fl, set_to_land=[(3, 4)], set_to_ocean=[(7, 6)], resets=[(-30., [(5, 5)]), (53., [(6, 7)])])
     for n in topoo.PLANES:
-        assert np.array_equal(read(tmp_path / n).view(np.uint64), getattr(res, n).cpu().numpy().reshape(-1).view(np.uint64)), n
-    assert read(tmp_path / "counts").astype(np.int64).tolist() == list(res.counts.values())
+        assert np.array_equal(cpp.read(tmp_path / n, np.float64).view(np.uint64), getattr(res, n).cpu().numpy().reshape(-1).view(np.uint64)), n
+    assert cpp.read(tmp_path / "counts", np.float64).astype(np.int64).tolist() == list(res.counts.values())

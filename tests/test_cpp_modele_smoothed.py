@@ -3,48 +3,17 @@ RegridParams(true, true, sigma), icebin_amd/host/icebin_hip.hpp) against libiceb
 compares its EvI, IvE and IvA with the ctypes surface, bitwise; the Cython module's to_modele(...).regrid_matrices(..., sigma=)
 .matrix("IvE") gives the same."""
 import os
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
-from icebin_amd import _capi
-from icebin_amd.build import build_library
+import cpp_programs as cpp
+from cpp_programs import ROOT, bits, read, write
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EXE = os.path.join(ROOT, "tests", "cpp", "test_modele_smoothed")
 SIGMA = (60e3, 45e3, 250.)
 O = (144, 90, 0., 120.)
 R = 6371000.
-
-
-def compile_exe():
-    lib = build_library()
-    src = os.path.join(ROOT, "tests", "cpp", "test_modele_smoothed.cpp")
-    hdrs = [os.path.join(ROOT, "icebin_amd", "host", h) for h in ("icebin_hip.hpp", "ncio.hpp")]
-    libdir = os.path.dirname(lib)
-    if (not os.path.exists(EXE)) or os.path.getmtime(EXE) < max(os.path.getmtime(f) for f in [src, lib] + hdrs):
-        subprocess.check_call(["g++", "-std=c++14", "-O1", "-Wall", "-o", EXE, src, "-L" + libdir, "-licebin_hip",
-                               "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib"])
-    return EXE
-
-
-def write(path, a, dtype):
-    a = np.ascontiguousarray(a, dtype).reshape(-1)
-    with open(path, "wb") as f:
-        f.write(np.asarray([a.size], np.int64).tobytes())
-        f.write(a.tobytes())
-
-
-def read(path, dtype):
-    with open(path, "rb") as f:
-        n = int(np.frombuffer(f.read(8), np.int64)[0])
-        return np.frombuffer(f.read(np.dtype(dtype).itemsize * n), dtype)
-
-
-def bits(x):
-    return np.ascontiguousarray(x, np.float64).view(np.uint64)
 
 
 def inputs(indir):
@@ -72,14 +41,9 @@ def inputs(indir):
 
 
 def test_cpp_modele_smoothed_compiles_and_fails_loudly_without_gpu(tmp_path):
-    exe = compile_exe()
-    if _capi.device_count() > 0:
-        pytest.skip("GPU present: covered by the gpu-marked test")
     inputs(tmp_path / "in")
     os.makedirs(tmp_path / "out")
-    r = subprocess.run([exe, str(tmp_path / "in"), str(tmp_path / "out")], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 3, r.stdout + r.stderr
-    assert "no CPU fallback" in r.stdout
+    cpp.fails_loudly_without_gpu("test_modele_smoothed", tmp_path / "in", tmp_path / "out", timeout=300)
 
 
 def same_as_files(w, outdir, name):
@@ -100,7 +64,7 @@ def test_cpp_modele_smoothed_on_gpu(tmp_path):
     from icebin_amd import HntrSpec, SparseSet, from_synthetic
     g, em, fp, fm = inputs(tmp_path / "in")
     os.makedirs(tmp_path / "out")
-    r = subprocess.run([compile_exe(), str(tmp_path / "in"), str(tmp_path / "out")], capture_output=True, text=True, timeout=600)
+    r = cpp.run(cpp.exe("test_modele_smoothed", allow_compile=False), tmp_path / "in", tmp_path / "out", timeout=600)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "all checks passed" in r.stdout
     rm = from_synthetic(g).to_modele((fp, fm), hspecO=HntrSpec(*O), eq_rad=R).regrid_matrices("greenland", em)
