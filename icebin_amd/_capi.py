@@ -387,3 +387,21 @@ def destroy(fn_name, handle):
         getattr(L, fn_name)(handle)
     except Exception:
         pass
+
+
+class Handle:
+    """Owner of one library handle: `_h` is a ctypes.c_void_p (None before the constructor sets it and once destroyed) and
+    `_destroy` names the ibh_*_destroy that frees it.  The handle is destroyed exactly once, by close() or when the object goes."""
+    _h = None
+    _destroy = None
+
+    def close(self):
+        """Destroy the handle now (idempotent; `del` does the same)."""
+        h, self._h = self._h, None
+        destroy(self._destroy, h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:      # interpreter shutdown
+            pass

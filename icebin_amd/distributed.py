@@ -12,8 +12,13 @@ Assembly (config 5: several ice sheets): sheets are independent regridders
 to disjoint rank sets by size; the ranks of one set build the same matrices redundantly (a build is
 1-6 ms, cheaper than broadcasting a 0.5 GB CSR over one xGMI link) and shard the sheet's fields.
 """
+import ctypes as C
+
 import torch
 import torch.distributed as dist
+
+from . import _capi
+from ._arrays import dptr, padded_planes, plane_stride, stream_arg
 
 
 def field_shard(nf_total, world, rank):
@@ -190,8 +195,6 @@ class FieldShardedApply:
         self._cur_h = 0
         if local_apply is None:
             # raw C-ABI calls, arguments prepared once: the per-apply host cost must stay below the ~10 us kernel
-            import ctypes as C
-            from . import _capi
             L = _capi.lib()
             h, check, nrow_, ld_ = weighted._h, _capi.check, nrow, ld
             fc = int(bool(force_conservation))
@@ -222,6 +225,7 @@ class FieldShardedApply:
     def apply(self, x_local, fill=float("nan")):
         """x_local: float64 tensor [nf_local, ncol_d] on the ops' device, row-contiguous.  Returns (group, slot)."""
         assert x_local.shape[0] == self.nl
+        # (not plane_stride: the local_apply the caller may have injected takes the stride as it is, and refuses what it must)
         return self.apply_ptr(x_local if self._is_host() else x_local.data_ptr(), x_local.stride(0) if self.nl > 1 else self.ncol, fill)
 
     def _is_host(self):
@@ -299,11 +303,13 @@ class FieldShardedApply:
 
 
 # ---- the same behind the C-ABI: ibh_comm + ibh_weighted_apply_sharded_device (RCCL called from the library) ----------------
-class Communicator:
+class Communicator(_capi.Handle):
     """ibh_comm: the ranks of a field-sharded regrid, one process per GPU.  `bootstrap` ships rank 0's 128-byte RCCL unique id
     to the other ranks -- by default through torch.distributed.broadcast_object_list on whatever process group is up (any
     backend: it only carries 128 bytes); a C++ host would use its own channel (ModelE: MPI_Bcast).  world == 1 needs nothing.
-    `exchange` (a Python callable, tests only) replaces RCCL by a custom transport (ibh_comm_create_custom)."""
+    `exchange` (a Python callable, tests only) replaces RCCL by a custom transport (ibh_comm_create_custom).  close() synchronises
+    the exchanges and destroys the communicator now (idempotent; `del` does the same)."""
+    _destroy = "ibh_comm_destroy"
 
     def __init__(self, world=1, rank=0, bootstrap=None, exchange=None, rccl=None, gatherv=None, stream=None, planes_padded=False):
         """rccl: None = only when world > 1; True = also at world 1 (a one-rank RCCL communicator: exercises the library's
@@ -313,9 +319,6 @@ class Communicator:
         (ibh_comm_set_stream: the caller's stream outlives the communicator -- what a transport whose allocator keeps
         per-stream state wants); planes_padded: the gap between nrow_d and the row stride of the result arrays is padding
         (ibh_comm_set_option)."""
-        import ctypes as C
-        from . import _capi
-        self._capi, self._C = _capi, C
         L = _capi.lib()
         h = C.c_void_p()
         self._cb = self._cbv = None
@@ -384,24 +387,11 @@ class Communicator:
 
     def set_option(self, key, value):
         """ibh_comm_set_option, e.g. ("planes_padded", 1)"""
-        self._capi.check(self._capi.lib().ibh_comm_set_option(self._h, key.encode(), int(value)))
-
-    def close(self):
-        """Synchronise the exchanges and destroy the communicator now (idempotent; `del` does the same)."""
-        h, self._h = getattr(self, "_h", None), None
-        if h is not None:
-            self._capi.destroy("ibh_comm_destroy", h)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:      # interpreter shutdown
-            pass
+        _capi.check(_capi.lib().ibh_comm_set_option(self._h, key.encode(), int(value)))
 
     def wait(self, stream=None):
         """Make `stream` (a raw stream handle; default torch's current stream) wait for the exchanges enqueued so far."""
-        s = torch.cuda.current_stream().cuda_stream if stream is None else stream
-        self._capi.check(self._capi.lib().ibh_comm_wait(self._h, self._C.c_void_p(s)))
+        _capi.check(_capi.lib().ibh_comm_wait(self._h, stream_arg(None, stream)))
 
 
 def apply_sharded(weighted, comm, x_local, out_all=None, fill=float("nan"), block_fields=0, stream=None, force_conservation=False):
@@ -409,18 +399,14 @@ def apply_sharded(weighted, comm, x_local, out_all=None, fill=float("nan"), bloc
     [world * nvar_local, nrow_d] on every rank (rows padded to 512 bytes when allocated here); complete after comm.wait().
     force_conservation: each rank corrects its own fields of a non-conservative (smoothed) matrix before they travel, as
     Weighted.apply(force_conservation=True)."""
-    import ctypes as C
-    from . import _capi
     assert x_local.is_cuda and x_local.dtype == torch.float64 and x_local.dim() == 2 and x_local.stride(1) == 1
-    nl = x_local.shape[0]
+    nl, lda = x_local.shape[0], plane_stride(x_local, weighted.ncol_d, "x_local")
     if out_all is None:
-        ld = (weighted.nrow_d + 63) // 64 * 64
-        out_all = torch.zeros((comm.world * nl, ld), dtype=torch.float64, device=x_local.device)[:, : weighted.nrow_d]
+        out_all = padded_planes(comm.world * nl, weighted.nrow_d, x_local.device, zero=True)
     assert out_all.shape == (comm.world * nl, weighted.nrow_d) and out_all.stride(1) == 1
-    s = torch.cuda.current_stream(x_local.device).cuda_stream if stream is None else stream
     _capi.check(_capi.lib().ibh_weighted_apply_sharded_conserve_device(
-        weighted._h, comm._h, C.c_void_p(x_local.data_ptr()), nl, max(x_local.stride(0), weighted.ncol_d), C.c_void_p(out_all.data_ptr()),
-        max(out_all.stride(0), weighted.nrow_d), float(fill), int(bool(force_conservation)), int(block_fields), C.c_void_p(s)))
+        weighted._h, comm._h, dptr(x_local), nl, lda, dptr(out_all), plane_stride(out_all, weighted.nrow_d, "out_all"), float(fill),
+        int(bool(force_conservation)), int(block_fields), stream_arg(x_local, stream)))
     return out_all
 
 
@@ -428,20 +414,17 @@ def apply_many_sharded(weighted, comm, xs_local, outs_all, fill=float("nan"), st
     """ibh_weighted_apply_many_sharded_conserve_device: len(xs_local) field batches through ONE SpMM launch and ONE grouped
     exchange; outs_all: list of [world * nvar_local, nrow_d] result arrays (all with the same row stride).  force_conservation:
     as apply_sharded."""
-    import ctypes as C
-    from . import _capi
     nb = len(xs_local)
     assert nb == len(outs_all) and nb >= 1
-    nl, lda = xs_local[0].shape[0], max(xs_local[0].stride(0), weighted.ncol_d)
-    ldb = max(outs_all[0].stride(0), weighted.nrow_d)
+    nl, ncol, nrow = xs_local[0].shape[0], weighted.ncol_d, weighted.nrow_d
+    lda, ldb = plane_stride(xs_local[0], ncol, "x_local"), plane_stride(outs_all[0], nrow, "out_all")
     for x, o in zip(xs_local, outs_all):
-        assert x.is_cuda and x.dtype == torch.float64 and x.shape == (nl, weighted.ncol_d) and max(x.stride(0), weighted.ncol_d) == lda
-        assert o.shape == (comm.world * nl, weighted.nrow_d) and max(o.stride(0), weighted.nrow_d) == ldb and o.stride(1) == 1
+        assert x.is_cuda and x.dtype == torch.float64 and x.shape == (nl, ncol) and plane_stride(x, ncol, "x_local") == lda
+        assert o.shape == (comm.world * nl, nrow) and plane_stride(o, nrow, "out_all") == ldb and o.stride(1) == 1
     xa = (C.c_void_p * nb)(*[x.data_ptr() for x in xs_local])
     oa = (C.c_void_p * nb)(*[o.data_ptr() for o in outs_all])
-    s = torch.cuda.current_stream(xs_local[0].device).cuda_stream if stream is None else stream
     _capi.check(_capi.lib().ibh_weighted_apply_many_sharded_conserve_device(weighted._h, comm._h, nb, xa, nl, lda, oa, ldb, float(fill),
-                                                                            int(bool(force_conservation)), C.c_void_p(s)))
+                                                                            int(bool(force_conservation)), stream_arg(xs_local[0], stream)))
     return outs_all
 
 
@@ -452,9 +435,7 @@ class CabiFieldShardedApply:
     group g+1 (the library orders work by the address ranges in flight).  force_conservation: as apply_sharded."""
 
     def __init__(self, weighted, nf_total, comm, device, steps_per_gather=1, force_conservation=False):
-        import ctypes as C
-        from . import _capi
-        self._C, self._capi, self._L = C, _capi, _capi.lib()
+        self._L = _capi.lib()
         self.w, self.comm, self.G = weighted, comm, int(steps_per_gather)
         self.fc = int(bool(force_conservation))
         assert nf_total % comm.world == 0, "the C-ABI sharded apply takes equal shards"
@@ -466,26 +447,23 @@ class CabiFieldShardedApply:
         comm.set_option("planes_padded", 1)        # (the planes of these arrays are rounded up to 512 bytes: the gap is ours)
         self._i = 0
 
-    def _stream(self):
-        return self._C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
     def apply_many_ptr(self, x_ptrs, ldx, fill=float("nan")):
-        C, m, i = self._C, len(x_ptrs), self._i
+        m, i = len(x_ptrs), self._i
         g, slot = (i // self.G) & 1, i % self.G
         assert 1 <= m <= self.G - slot
         xa = (C.c_void_p * m)(*x_ptrs)
         oa = (C.c_void_p * m)(*[self._out[g][slot + s].data_ptr() for s in range(m)])
-        self._capi.check(self._L.ibh_weighted_apply_many_sharded_conserve_device(self.w._h, self.comm._h, m, xa, self.nl, ldx, oa, self.ld, fill,
-                                                                                 self.fc, self._stream()))
+        _capi.check(self._L.ibh_weighted_apply_many_sharded_conserve_device(self.w._h, self.comm._h, m, xa, self.nl, ldx, oa, self.ld, fill,
+                                                                            self.fc, stream_arg(self._out[g])))
         self._i = i + m
         return g, slot
 
     def apply_ptr(self, x_ptr, ldx, fill=float("nan")):
-        C, i = self._C, self._i
+        i = self._i
         g, slot = (i // self.G) & 1, i % self.G
-        self._capi.check(self._L.ibh_weighted_apply_sharded_conserve_device(self.w._h, self.comm._h, C.c_void_p(x_ptr), self.nl, ldx,
-                                                                            C.c_void_p(self._out[g][slot].data_ptr()), self.ld, fill, self.fc, 0,
-                                                                            self._stream()))
+        _capi.check(self._L.ibh_weighted_apply_sharded_conserve_device(self.w._h, self.comm._h, C.c_void_p(x_ptr), self.nl, ldx,
+                                                                       dptr(self._out[g][slot]), self.ld, fill, self.fc, 0,
+                                                                       stream_arg(self._out[g])))
         self._i = i + 1
         return g, slot
 

@@ -7,6 +7,7 @@ from collections import OrderedDict
 import numpy as np
 
 from . import _capi
+from ._arrays import dptr, is_cuda, named_planes, stream_arg, to_device
 from ._capi import check, lib
 
 MAX_TILE = 8192                 # IBH_ETOPO1_MAX_TILE: fine cells of one coarse cell
@@ -14,55 +15,15 @@ PLANES = ("FOCEAN1m", "FGICE1m", "ZICETOP1m", "ZSOLG1m")
 PLANES_H = ("FOCEANh", "FGICEh", "ZICETOPh", "ZSOLGh")
 
 
-def _einval(msg):
-    return _capi.IcebinHipError(_capi.IBH_EINVAL, msg)
-
-
-def _inputs(hspecI, hspecC, focean, zictop, zsolid, fgiceC):
-    """The four inputs as flat contiguous arrays, all numpy or all torch CUDA tensors: (arrays, on_device).  Needs no device."""
-    named = (("focean", focean, "int16", hspecI.size), ("zictop", zictop, "int16", hspecI.size), ("zsolid", zsolid, "int16", hspecI.size),
-             ("fgiceC", fgiceC, "float64", hspecC.size))
-    dev = [hasattr(p, "is_cuda") and bool(p.is_cuda) for _, p, _, _ in named]
-    if any(dev) != all(dev):
-        raise _einval("focean / zictop / zsolid / fgiceC: some planes are on the host and some on the device (%s)"
-                      % ", ".join("%s: %s" % (n[0], "device" if d else "host") for n, d in zip(named, dev)))
-    out = []
-    for name, p, dtype, size in named:
-        if p is None:
-            raise _einval("%s: null plane" % name)
-        if dev[0]:
-            if str(p.dtype) != "torch." + dtype:
-                raise _einval("%s: dtype %s, the plane is %s" % (name, p.dtype, dtype))
-            p = p.reshape(-1).contiguous()
-            n = p.numel()
-        else:
-            p = np.asarray(p)
-            if p.dtype != np.dtype(dtype):
-                raise _einval("%s: dtype %s, the plane is %s" % (name, p.dtype, dtype))
-            p = np.ascontiguousarray(p.reshape(-1))
-            n = p.size
-        if n != size:
-            raise _einval("%s: the plane holds %d cells, its grid has %d" % (name, n, size))
-        out.append(p)
-    return out, dev[0]
-
-
-class Etopo1Ice:
+class Etopo1Ice(_capi.Handle):
     """What etopo1_ice returns: .FOCEAN1m / .FGICE1m / .ZICETOP1m / .ZSOLG1m, torch.int16 CUDA tensors [jmI, imI], and
     .FOCEANh / .FGICEh / .ZICETOPh / .ZSOLGh, torch.float64 [jmH, imH] (None without hspecH)."""
+    _destroy = "ibh_etopo1_ice_destroy"
 
     def __init__(self, hspecI, hspecC, hspecH, include_greenland):
         self.hspecI, self.hspecC, self.hspecH, self.include_greenland = hspecI, hspecC, hspecH, bool(include_greenland)
-        self._h = None
         for n in PLANES + PLANES_H:
             setattr(self, n, None)
-
-    def __del__(self):
-        try:
-            _capi.destroy("ibh_etopo1_ice_destroy", getattr(self, "_h", None))
-        except Exception:      # interpreter shutdown
-            pass
-        self._h = None
 
     def ice_scan(self, hspecO):
         """global_ec.IceScan(hspecO, hspecI, FGICE1m, ZICETOP1m) on the resident planes (global_ec.cpp:762-816)."""
@@ -73,9 +34,8 @@ class Etopo1Ice:
         """topoo.make_topoO on the resident planes (topo_base.cpp:263-809): no 1' plane leaves the device.  FLAKES: a torch CUDA
         tensor, or a host array (uploaded)."""
         from .topoo import make_topoO
-        if not (hasattr(FLAKES, "is_cuda") and FLAKES.is_cuda):
-            import torch
-            FLAKES = torch.from_numpy(np.ascontiguousarray(FLAKES, np.float64).copy()).to(self.FGICE1m.device)
+        if not is_cuda(FLAKES):
+            FLAKES = to_device(np.ascontiguousarray(FLAKES, np.float64), self.FGICE1m.device)
         return make_topoO(self.hspecI, hspecO, self.FGICE1m, self.ZICETOP1m, self.ZSOLG1m, self.FOCEAN1m, hspecS, FLAKES, set_to_land,
                           set_to_ocean, resets)
 
@@ -112,7 +72,9 @@ def etopo1_ice(hspecI, hspecC, focean, zictop, zsolid, fgiceC, include_greenland
     (FOCEAN: 0 land, 1 ocean, 2 Greenland), fgiceC: float64 [jmC, imC]; all host numpy arrays (uploaded once in their own
     width) or all torch CUDA tensors (read in place, on torch's current stream).  Inputs are never written.  Returns an
     Etopo1Ice; the semantics, line by line, are in include/icebin_hip.h."""
-    planes, on_device = _inputs(hspecI, hspecC, focean, zictop, zsolid, fgiceC)
+    planes, on_device = named_planes((("focean", focean, "int16", hspecI.size), ("zictop", zictop, "int16", hspecI.size),
+                                      ("zsolid", zsolid, "int16", hspecI.size), ("fgiceC", fgiceC, "float64", hspecC.size)),
+                                     "focean / zictop / zsolid / fgiceC: some planes are on the host and some on the device")
     H = hspecH
     h = C.c_void_p()
     check(lib().ibh_etopo1_ice_create(C.byref(h), hspecI.im, hspecI.jm, hspecI.offi, hspecI.dlat, hspecC.im, hspecC.jm,
@@ -121,14 +83,12 @@ def etopo1_ice(hspecI, hspecC, focean, zictop, zsolid, fgiceC, include_greenland
     res._h = h
     import torch
     if not on_device:
-        planes = [torch.from_numpy(p if p.flags.writeable else p.copy()).cuda() for p in planes]     # (torch takes no read-only array)
+        planes = [to_device(p) for p in planes]
     dev = planes[0].device
     out = [torch.empty((hspecI.jm, hspecI.im), dtype=torch.int16, device=dev) for _ in PLANES]
     outh = torch.empty((4, H.size), dtype=torch.float64, device=dev) if H else None
-    s = torch.cuda.current_stream(dev).cuda_stream
-    check(lib().ibh_etopo1_ice_device(h, *[C.c_void_p(p.data_ptr()) for p in planes], int(bool(include_greenland)),
-                                      *[C.c_void_p(o.data_ptr()) for o in out], C.c_void_p(outh.data_ptr()) if H else None,
-                                      H.size if H else 0, C.c_void_p(s)))
+    check(lib().ibh_etopo1_ice_device(h, *[dptr(p) for p in planes], int(bool(include_greenland)), *[dptr(o) for o in out], dptr(outh),
+                                      H.size if H else 0, stream_arg(planes[0])))
     res._keep = planes          # the inputs are read on the stream: they live as long as the result
     for n, o in zip(PLANES, out):
         setattr(res, n, o)

@@ -7,6 +7,7 @@ import math
 import numpy as np
 
 from . import _capi
+from ._arrays import dptr, einval, is_cuda, named_planes, stream_arg
 from ._capi import check, lib, ptr
 from .hntr import Hntr
 from .linear import SparseSet, linear_Weighted
@@ -59,11 +60,10 @@ def native_area(hspec, to_sparse, eq_rad):
 
 def _mask_arg(elevmaskI):
     """(pointer, n, on_device, stream, keep-alive) of a host array or a torch.float64 CUDA tensor."""
-    if hasattr(elevmaskI, "is_cuda") and elevmaskI.is_cuda:
-        import torch
+    if is_cuda(elevmaskI):
         em = elevmaskI.reshape(-1).contiguous()
-        assert em.dtype == torch.float64
-        return em.data_ptr(), em.numel(), 1, torch.cuda.current_stream(em.device).cuda_stream, em
+        assert str(em.dtype) == "torch.float64"
+        return em.data_ptr(), em.numel(), 1, stream_arg(em).value or 0, em
     em = np.ascontiguousarray(np.asarray(elevmaskI, np.float64).reshape(-1))
     return ptr(em).value, len(em), 0, None, em
 
@@ -230,16 +230,12 @@ def write_matrices(gcm, elevmaskI, hspecI2, fname, names=MATRIX_NAMES, correctA=
 CHUNK_SIZE = 12000000           # global_ec.cpp:100
 
 
-def _einval(msg):
-    return _capi.IcebinHipError(_capi.IBH_EINVAL, msg)
-
-
 def chunk_plan(imO, jmO, mult_i, mult_j, counts, chunk_size=CHUNK_SIZE):
     """The chunk walk of global_ec.cpp:863-893 over host counts c[k] = fgiceO[k] != 0 ? nice[k] : 0, k = jO*imO + iO (no GPU
     needed): [((chunkno, jO0, iO0, jO1, iO1), nice), ...].  See IceScan.chunks."""
     c = np.ascontiguousarray(np.asarray(counts).reshape(-1), np.int32)
     if len(c) != int(imO) * int(jmO):
-        raise _einval("counts: %d cells, the ocean grid has %d" % (len(c), int(imO) * int(jmO)))
+        raise einval("counts: %d cells, the ocean grid has %d" % (len(c), int(imO) * int(jmO)))
     n = C.c_int32()
     args = (int(imO), int(jmO), int(mult_i), int(mult_j), ptr(c), int(chunk_size))
     check(lib().ibh_global_ec_chunk_plan_counts(*args, 0, None, None, C.byref(n)))
@@ -248,58 +244,30 @@ def chunk_plan(imO, jmO, mult_i, mult_j, counts, chunk_size=CHUNK_SIZE):
     return [(tuple(int(x) for x in ch[i]), int(nice[i])) for i in range(n.value)]
 
 
-class IceScan:
+class IceScan(_capi.Handle):
     """The global ice of global_ec's main() (global_ec.cpp:752-816) on the device: fgiceI / elevI are the int16 planes
     [jmI, imI] (FGICE1m / ZICETOP1m), host numpy arrays (uploaded once in their own width and kept) or torch.int16 CUDA
     tensors (kept as they are).  hspecI must nest in hspecO.  One pass over both planes gives .nice and .elevI_range;
     .fgiceO is Hntr(17.17, hspecO, hspecI).regrid(1.0, fgiceI).  fgiceO and nice are torch CUDA tensors [jmO, imO]."""
+    _destroy = "ibh_global_ec_scan_destroy"
 
     def __init__(self, hspecO, hspecI, fgiceI, elevI):
         self.hspecO, self.hspecI = hspecO, hspecI
-        self._h = None
-        planes, dev = [], [hasattr(p, "is_cuda") and p.is_cuda for p in (fgiceI, elevI)]
-        if dev[0] != dev[1]:
-            raise _einval("fgiceI / elevI: one plane is on the host and one on the device")
-        for name, p in (("fgiceI", fgiceI), ("elevI", elevI)):
-            if dev[0]:
-                if str(p.dtype) != "torch.int16":
-                    raise _einval("%s: dtype %s, the ice planes are int16" % (name, p.dtype))
-                p = p.reshape(-1).contiguous()
-                n = p.numel()
-            else:
-                p = np.asarray(p)
-                if p.dtype != np.int16:
-                    raise _einval("%s: dtype %s, the ice planes are int16" % (name, p.dtype))
-                p = np.ascontiguousarray(p.reshape(-1))
-                n = p.size
-            if n != hspecI.size:
-                raise _einval("%s: the plane holds %d cells, hspecI has %d" % (name, n, hspecI.size))
-            planes.append(p)
-        stream = None
-        if dev[0]:
-            import torch
-            stream = torch.cuda.current_stream(planes[0].device).cuda_stream
-            pp = [C.c_void_p(p.data_ptr()) for p in planes]
-        else:
-            pp = [ptr(p) for p in planes]
+        planes, dev = named_planes((("fgiceI", fgiceI, "int16", hspecI.size), ("elevI", elevI, "int16", hspecI.size)),
+                                   "fgiceI / elevI: one plane is on the host and one on the device", mix_detail=False,
+                                   dtype_is="the ice planes are %s", cells_of="hspecI has %d", null=None)
+        pp = [dptr(p) if dev else ptr(p) for p in planes]
         h = C.c_void_p()
         from .hntr import I16
         check(lib().ibh_global_ec_scan_create(hspecO.im, hspecO.jm, hspecO.offi, hspecO.dlat, hspecI.im, hspecI.jm, hspecI.offi, hspecI.dlat,
-                                              pp[0], pp[1], hspecI.size, I16, int(dev[0]), C.c_void_p(stream), C.byref(h)))
+                                              pp[0], pp[1], hspecI.size, I16, int(dev), stream_arg(planes[0]) if dev else None, C.byref(h)))
         self._h = h
-        self._planes = planes if dev[0] else None       # device planes are read in place: they live as long as the scan
+        self._planes = planes if dev else None       # device planes are read in place: they live as long as the scan
         self.mult_i, self.mult_j = hspecI.im // hspecO.im, hspecI.jm // hspecO.jm
         r = np.zeros(2, np.int16)
         check(lib().ibh_global_ec_scan_get(h, None, None, ptr(r), None, None))
         self.elevI_range = (int(r[0]), int(r[1]))
         self._fgiceO = self._nice = None
-
-    def __del__(self):
-        try:
-            _capi.destroy("ibh_global_ec_scan_destroy", getattr(self, "_h", None))
-        except Exception:      # interpreter shutdown
-            pass
-        self._h = None
 
     def _copies(self):
         """fgiceO and nice as torch tensors: device-to-device copies of the scan's arrays, made once."""
@@ -308,8 +276,7 @@ class IceScan:
             shape = (self.hspecO.jm, self.hspecO.im)
             f = torch.empty(shape, dtype=torch.float64, device="cuda")
             n = torch.empty(shape, dtype=torch.int32, device="cuda")
-            s = torch.cuda.current_stream(f.device).cuda_stream
-            check(lib().ibh_global_ec_scan_copy_device(self._h, C.c_void_p(f.data_ptr()), C.c_void_p(n.data_ptr()), C.c_void_p(s)))
+            check(lib().ibh_global_ec_scan_copy_device(self._h, dptr(f), dptr(n), stream_arg(f)))
             self._fgiceO, self._nice = f, n
         return self._fgiceO, self._nice
 
@@ -348,13 +315,12 @@ class IceScan:
         if len(chunk) == 2:
             chunk = chunk[0]
         if len(chunk) != 5:
-            raise _einval("chunk: expected (chunkno, jO0, iO0, jO1, iO1)")
+            raise einval("chunk: expected (chunkno, jO0, iO0, jO1, iO1)")
         if out is None:
             out = torch.empty(self.hspecI.size, dtype=torch.float64, device="cuda")
-        if not (hasattr(out, "is_cuda") and out.is_cuda and out.dtype == torch.float64 and out.is_contiguous()):
-            raise _einval("out: the mask is written to a contiguous torch.float64 CUDA tensor of %d cells" % self.hspecI.size)
-        s = torch.cuda.current_stream(out.device).cuda_stream
-        check(lib().ibh_global_ec_chunk_mask(self._h, *[int(x) for x in chunk[1:]], C.c_void_p(out.data_ptr()), out.numel(), C.c_void_p(s)))
+        if not (is_cuda(out) and out.dtype == torch.float64 and out.is_contiguous()):
+            raise einval("out: the mask is written to a contiguous torch.float64 CUDA tensor of %d cells" % self.hspecI.size)
+        check(lib().ibh_global_ec_chunk_mask(self._h, *[int(x) for x in chunk[1:]], dptr(out), out.numel(), stream_arg(out)))
         return out
 
 
@@ -393,7 +359,7 @@ def _combine(mats, scale, host=None):
     """mats: the chunks' matrices in order; host: None (the handles' own sets) or [(dimB, dimA, extB, extA), ...]."""
     n = len(mats)
     if n == 0:
-        raise _einval("chunk_results: combine_chunks needs at least one chunk")
+        raise einval("chunk_results: combine_chunks needs at least one chunk")
     hs = (C.c_void_p * n)(*[m._h.value for m in mats])
     nnz = sum(m.nnz for m in mats)
     iB, iA, val = np.zeros(nnz, np.int64), np.zeros(nnz, np.int64), np.zeros(nnz)
@@ -413,7 +379,7 @@ def _chunk_matrix(result, c, name):
     for vn in (name, name.replace("A", "O")):
         if vn in result:
             return result[vn]
-    raise _einval("name: chunk %d holds no matrix %r (it has %s)" % (c, name, ", ".join(sorted(result))))
+    raise einval("name: chunk %d holds no matrix %r (it has %s)" % (c, name, ", ".join(sorted(result))))
 
 
 def combine_chunks(chunk_results, name, scale=False):
@@ -433,7 +399,7 @@ def combine_chunk_files(ifnames, ofname, names=MATRIX_NAMES, scale=False):
     from . import ncio
     dss = [ncio.Dataset.read(f) for f in ifnames]
     if not dss:
-        raise _einval("ifnames: combine_chunk_files needs at least one chunk file")
+        raise einval("ifnames: combine_chunk_files needs at least one chunk file")
     out, ds, written = {}, ncio.Dataset(), {}
 
     def dim_name(letter, vname, to_sparse):
@@ -449,7 +415,7 @@ def combine_chunk_files(ifnames, ofname, names=MATRIX_NAMES, scale=False):
         mats, host = [], []
         for c, d in enumerate(dss):
             if vname + ".info" not in d.variables:
-                raise _einval("names: chunk file %s holds no matrix %r" % (ifnames[c], name))
+                raise einval("names: chunk file %s holds no matrix %r" % (ifnames[c], name))
             w = linear_Weighted.nc_read(d, vname)
             mats.append(w)
             host.append((w._dims[0], w._dims[1], w._sparse_extents[0], w._sparse_extents[1]))

@@ -159,21 +159,15 @@ def project(sproj, lon, lat):
     return x, y
 
 
-class LonLatCells:
+class LonLatCells(_capi.Handle):
     """The realised cells of a GridSpec_LonLat in HBM (ibh_lonlat_cells): projected polygons, native and projected areas."""
+    _destroy = "ibh_lonlat_cells_destroy"
 
     def __init__(self, handle, spec):
         self._h, self.spec = handle, spec
         nc, nv, nA = C.c_int32(), C.c_int64(), C.c_int64()
         check(lib().ibh_lonlat_cells_size(handle, C.byref(nc), C.byref(nv), C.byref(nA)))
         self.ncell, self.nvert, self.nA = nc.value, nv.value, nA.value
-
-    def __del__(self):
-        try:
-            _capi.destroy("ibh_lonlat_cells_destroy", getattr(self, "_h", None))
-        except Exception:      # interpreter shutdown
-            pass
-        self._h = None
 
     def get(self, lonlat=False):
         """Copy-out: dict(iA, polyptr, vx, vy, native_area, proj_area[, lon, lat])."""

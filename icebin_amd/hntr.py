@@ -8,6 +8,7 @@ import ctypes as C
 import numpy as np
 
 from . import _capi
+from ._arrays import dptr, leading_dim, padded_planes, stream_arg
 from ._capi import check, lib, ptr
 
 # kinds of Hntr matrix (ibh_hntr_matrix_d) and the to-dense transforms of MakeDenseEigenT
@@ -81,9 +82,10 @@ def _kind(kind):
     return int(k)
 
 
-class Hntr:
+class Hntr(_capi.Handle):
     """Hntr(yp17, Bspec, Aspec, DATMIS=0) (hntr.hpp:114, hntr.cpp:63-79): yp17 is ignored, as in the reference.
     Creating one uploads the partition to the current HIP device (IBH_ENODEVICE without one)."""
+    _destroy = "ibh_hntr_destroy"
 
     def __init__(self, yp17, Bgrid, Agrid, DATMIS=0.):
         self.Bgrid, self.Agrid, self.DATMIS = Bgrid, Agrid, float(DATMIS)
@@ -91,13 +93,6 @@ class Hntr:
         check(lib().ibh_hntr_create(C.byref(h), Agrid.im, Agrid.jm, Agrid.offi, Agrid.dlat, Bgrid.im, Bgrid.jm, Bgrid.offi,
                                     Bgrid.dlat, self.DATMIS))
         self._h = h
-
-    def __del__(self):
-        try:
-            _capi.destroy("ibh_hntr_destroy", getattr(self, "_h", None))
-        except Exception:      # interpreter shutdown
-            pass
-        self._h = None
 
     def _planes(self, X, what):
         X = np.asarray(X)
@@ -198,15 +193,13 @@ class Hntr:
             assert W.is_cuda and W.dtype in types and W.dim() == 2 and W.stride(1) == 1 and W.shape[1] == nA
             assert W.shape[0] in (1, nvar)
         if out is None:
-            out = torch.empty((nvar, (nB + 63) // 64 * 64), dtype=torch.float64, device=A.device)[:, :nB]
+            out = padded_planes(nvar, nB, A.device)
         assert out.is_cuda and out.dtype == torch.float64 and out.dim() == 2 and out.shape == (nvar, nB) and out.stride(1) == 1
         wta_ld, lda, ldb = device_strides(nvar, nA, nB, 1 if const else W.shape[0], 0 if const else W.stride(0), A.stride(0),
                                           out.stride(0))
-        s = torch.cuda.current_stream(A.device).cuda_stream if stream is None else stream
-        check(lib().ibh_hntr_regrid_typed_device(self._h, None if const else C.c_void_p(W.data_ptr()), F64 if const else _code(W.dtype),
-                                                 wta_ld, float(WTA) if const else 0., C.c_void_p(A.data_ptr()), _code(A.dtype), nvar,
-                                                 lda, C.c_void_p(out.data_ptr()), ldb, int(bool(mean_polar)), float(wtm), float(wtb),
-                                                 C.c_void_p(s)))
+        check(lib().ibh_hntr_regrid_typed_device(self._h, None if const else dptr(W), F64 if const else _code(W.dtype),
+                                                 wta_ld, float(WTA) if const else 0., dptr(A), _code(A.dtype), nvar,
+                                                 lda, dptr(out), ldb, int(bool(mean_polar)), float(wtm), float(wtb), stream_arg(A, stream)))
         return out
 
     def regrid_shape(self, nvar, WTA_dtype, A_dtype, per_field=False):
@@ -224,15 +217,6 @@ class Hntr:
 def device_strides(nvar, nA, nB, wta_planes, wta_stride, a_stride, out_stride):
     """(wta_ld, lda, ldb) for ibh_hntr_regrid_device from the plane strides of torch tensors.  A single plane's stride is
     never read.  One weight plane, or planes broadcast with stride 0 (`w.expand(nvar, -1)`), is the shared weight
-    (wta_ld = 0).  Otherwise every stride must hold a whole plane: a smaller one (a broadcast A or out, an overlapping
-    as_strided view) would make the kernel read or write past the tensor, so it is refused before anything is launched."""
-    wta_ld = 0 if wta_planes == 1 or wta_stride == 0 else wta_stride
-    lda = nA if nvar == 1 else a_stride
-    ldb = nB if nvar == 1 else out_stride
-    if wta_ld and wta_ld < nA:
-        raise ValueError("WTA planes overlap: stride %d < %d cells" % (wta_ld, nA))
-    if lda < nA:
-        raise ValueError("A planes overlap: stride %d < %d cells" % (lda, nA))
-    if ldb < nB:
-        raise ValueError("out planes overlap: stride %d < %d cells" % (ldb, nB))
-    return wta_ld, lda, ldb
+    (wta_ld = 0).  Otherwise every stride must hold a whole plane (leading_dim: refused before anything is launched)."""
+    wta_ld = 0 if wta_planes == 1 or wta_stride == 0 else leading_dim(wta_planes, wta_stride, nA, "WTA")
+    return wta_ld, leading_dim(nvar, a_stride, nA, "A"), leading_dim(nvar, out_stride, nB, "out")

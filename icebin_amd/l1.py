@@ -8,8 +8,9 @@ from . import _capi
 from ._capi import check, lib, ptr
 
 
-class Mesh:
+class Mesh(_capi.Handle):
     """Vertices vx, vy [nvert] and elements tri [ntri, 3] (vertex ids, counter-clockwise), resident in HBM."""
+    _destroy = "ibh_l1_mesh_destroy"
 
     def __init__(self, vx, vy, tri):
         self.vx, self.vy = np.ascontiguousarray(vx, np.float64), np.ascontiguousarray(vy, np.float64)
@@ -23,28 +24,15 @@ class Mesh:
     nvert = property(lambda self: len(self.vx))
     ntri = property(lambda self: len(self.tri))
 
-    def __del__(self):
-        try:
-            _capi.destroy("ibh_l1_mesh_destroy", getattr(self, "_h", None))
-        except Exception:      # interpreter shutdown
-            pass
-        self._h = None
 
-
-class ExchangeGrid:
+class ExchangeGrid(_capi.Handle):
     """The exchange grid of a mesh in HBM, sorted by (iA, iTri).  indices int32[nX, 2] (iA, iTri), areas f64[nX], and the
     ragged polygons vptr int32[nX+1], qx, qy are copied out on first use."""
+    _destroy = "ibh_l1_exgrid_destroy"
 
     def __init__(self, handle):
         self._h = handle
         self._arrays = None
-
-    def __del__(self):
-        try:
-            _capi.destroy("ibh_l1_exgrid_destroy", getattr(self, "_h", None))
-        except Exception:      # interpreter shutdown
-            pass
-        self._h = None
 
     def _get(self):
         if self._arrays is None:

@@ -5,11 +5,13 @@ import ctypes as C
 import numpy as np
 
 from . import _capi
+from ._arrays import dptr, leading_dim, padded_planes, plane_stride, stream_arg, to_device
 from ._capi import check, lib, ptr
 
 
-class SparseSet:
+class SparseSet(_capi.Handle):
     """spsparse::SparseSet<long,int>: dense ids handed out first-seen (eigen_types.hpp:24)."""
+    _destroy = "ibh_sparse_set_destroy"
 
     def __init__(self, sparse_extent=-1, to_sparse=None, _handle=None):
         h = C.c_void_p()
@@ -28,13 +30,6 @@ class SparseSet:
         h = C.c_void_p()
         check(lib().ibh_sparse_set_create_identity(int(n), C.byref(h)))
         return cls(_handle=h)
-
-    def __del__(self):
-        try:
-            _capi.destroy("ibh_sparse_set_destroy", getattr(self, "_h", None))
-        except Exception:      # interpreter shutdown
-            pass
-        self._h = None
 
     def sparse_extent(self):
         v = C.c_int64()
@@ -74,13 +69,14 @@ class SparseSet:
         check(lib().ibh_sparse_set_add_dense_multivec(self._h, mv._h, C.c_void_p(stream)))
 
 
-class linear_Weighted:
+class linear_Weighted(_capi.Handle):
     """A regrid matrix M plus its two weight vectors, resident in HBM.
 
     Mirrors ibmisc.linear_Weighted (matrix_formats.rst:139-195): apply_M, apply_weight, apply_wM,
     apply_Mw, to_coo, get_weights, shape; plus the C++ members of linear::Weighted_Eigen the IceBin
     callers touch (dims, wM, Mw, conservative, scaled, apply()).
     """
+    _destroy = "ibh_weighted_destroy"
 
     def __init__(self, handle, keep=()):
         self._h = handle
@@ -93,13 +89,6 @@ class linear_Weighted:
         self.conservative, self.scaled = bool(cons.value), bool(sc.value)
         self._dims = [None, None]
         self._sparse_extents = [None, None]
-
-    def __del__(self):
-        try:
-            _capi.destroy("ibh_weighted_destroy", getattr(self, "_h", None))
-        except Exception:      # interpreter shutdown
-            pass
-        self._h = None
 
     # ---- loaders -------------------------------------------------------------------------
     @classmethod
@@ -228,16 +217,10 @@ class linear_Weighted:
         """Same on fields already resident in HBM: dA is a torch.float64 CUDA tensor [nvar, ncol_d]
         (row stride >= ncol_d); only enqueues work on `stream` (default: torch's current stream)."""
         import torch
-        assert dA.is_cuda and dA.dtype == torch.float64 and dA.dim() == 2 and dA.stride(1) == 1
-        assert dA.shape[1] == self.ncol_d
-        nvar = dA.shape[0]
-        if out is None:
-            out = _aligned_planes(torch, nvar, self.nrow_d, dA.device)
-        assert out.is_cuda and out.dtype == torch.float64 and out.shape == (nvar, self.nrow_d) and out.stride(1) == 1
-        s = torch.cuda.current_stream(dA.device).cuda_stream if stream is None else stream
-        check(lib().ibh_weighted_apply_device(self._h, C.c_void_p(dA.data_ptr()), nvar, dA.stride(0) if nvar > 1 else max(dA.stride(0), self.ncol_d),
-                                             C.c_void_p(out.data_ptr()), out.stride(0) if nvar > 1 else max(out.stride(0), self.nrow_d),
-                                             float(fill), int(force_conservation), C.c_void_p(s)))
+        nvar, lda = _fields(torch, (dA,), self.ncol_d)
+        out, ldb = _result(torch, out, nvar, self.nrow_d, dA.device)
+        check(lib().ibh_weighted_apply_device(self._h, dA.data_ptr(), nvar, lda, out.data_ptr(), ldb, float(fill), int(force_conservation),
+                                             stream_arg(dA, stream)))
         return out
 
     def apply_many_device(self, dAs, outs=None, fill=float("nan"), force_conservation=True, stream=None):
@@ -248,21 +231,14 @@ class linear_Weighted:
         nb = len(dAs)
         if nb == 0:
             return []
-        nvar, lda = dAs[0].shape[0], max(dAs[0].stride(0), self.ncol_d)
-        for a in dAs:
-            assert a.is_cuda and a.dtype == torch.float64 and a.dim() == 2 and a.stride(1) == 1
-            assert a.shape == (nvar, self.ncol_d) and max(a.stride(0), self.ncol_d) == lda
+        nvar, lda = _fields(torch, dAs, self.ncol_d)
         if outs is None:
-            outs = [_aligned_planes(torch, nvar, self.nrow_d, dAs[0].device) for _ in range(nb)]
-        ldb = max(outs[0].stride(0), self.nrow_d)
-        for o in outs:
-            assert o.is_cuda and o.dtype == torch.float64 and o.shape == (nvar, self.nrow_d) and o.stride(1) == 1
-            assert max(o.stride(0), self.nrow_d) == ldb
+            outs = [padded_planes(nvar, self.nrow_d, dAs[0].device) for _ in range(nb)]
+        ldb = _fields(torch, outs, self.nrow_d, "out", nvar)[1]
         xp = (C.c_void_p * nb)(*[a.data_ptr() for a in dAs])
         yp = (C.c_void_p * nb)(*[o.data_ptr() for o in outs])
-        s = torch.cuda.current_stream(dAs[0].device).cuda_stream if stream is None else stream
         check(lib().ibh_weighted_apply_many_device(self._h, nb, xp, nvar, lda, yp, ldb, float(fill), int(force_conservation),
-                                                  C.c_void_p(s)))
+                                                  stream_arg(dAs[0], stream)))
         return outs
 
     def row_stats_device(self, dx, want_sum=True, want_min=True, want_max=True, stream=None):
@@ -273,9 +249,7 @@ class linear_Weighted:
         import torch
         assert dx.is_cuda and dx.dtype == torch.float64 and dx.is_contiguous() and dx.numel() == self.ncol_d
         outs = [torch.empty(self.nrow_d, dtype=torch.float64, device=dx.device) if want else None for want in (want_sum, want_min, want_max)]
-        s = torch.cuda.current_stream(dx.device).cuda_stream if stream is None else stream
-        check(lib().ibh_weighted_row_stats_device(self._h, C.c_void_p(dx.data_ptr()), *[C.c_void_p(o.data_ptr()) if o is not None else None
-                                                                                     for o in outs], C.c_void_p(s)))
+        check(lib().ibh_weighted_row_stats_device(self._h, dptr(dx), *[dptr(o) for o in outs], stream_arg(dx, stream)))
         return tuple(outs)
 
     def reserve(self, nvar):
@@ -300,40 +274,24 @@ class linear_Weighted:
         """One launch for both products (ibh_weighted_apply_pair_device); returns (B1, B2).  B1 is bitwise apply_device's
         result, B2 = second.apply_device(B1, force_conservation=False) to 1e-12."""
         import torch
-        assert dA.is_cuda and dA.dtype == torch.float64 and dA.dim() == 2 and dA.stride(1) == 1 and dA.shape[1] == self.ncol_d
-        nvar = dA.shape[0]
-        if out1 is None:
-            out1 = _aligned_planes(torch, nvar, self.nrow_d, dA.device)
-        if out2 is None:
-            out2 = _aligned_planes(torch, nvar, second.nrow_d, dA.device)
-        for o, n in ((out1, self.nrow_d), (out2, second.nrow_d)):
-            assert o.is_cuda and o.dtype == torch.float64 and o.shape == (nvar, n) and o.stride(1) == 1
-        s = torch.cuda.current_stream(dA.device).cuda_stream if stream is None else stream
-        ld = lambda t, n: t.stride(0) if nvar > 1 else max(t.stride(0), n)
-        check(lib().ibh_weighted_apply_pair_device(self._h, second._h, C.c_void_p(dA.data_ptr()), nvar, ld(dA, self.ncol_d),
-                                                  C.c_void_p(out1.data_ptr()), ld(out1, self.nrow_d), C.c_void_p(out2.data_ptr()),
-                                                  ld(out2, second.nrow_d), float(fill), C.c_void_p(s)))
+        nvar, lda = _fields(torch, (dA,), self.ncol_d)
+        out1, ld1 = _result(torch, out1, nvar, self.nrow_d, dA.device)
+        out2, ld2 = _result(torch, out2, nvar, second.nrow_d, dA.device)
+        check(lib().ibh_weighted_apply_pair_device(self._h, second._h, dA.data_ptr(), nvar, lda, out1.data_ptr(), ld1, out2.data_ptr(), ld2, float(fill),
+                                                  stream_arg(dA, stream)))
         return out1, out2
 
     def apply_chain_device(self, second, third, dA, out1=None, out2=None, out3=None, fill=float("nan"), stream=None):
         """B1 = self * A, B2 = second * B1 (the fused pair: pair_prepare(second) first), B3 = third * B2, as two stream-ordered
         launches (ibh_weighted_apply_chain_device); returns (B1, B2, B3), bitwise the pair apply followed by third.apply_device."""
         import torch
-        assert dA.is_cuda and dA.dtype == torch.float64 and dA.dim() == 2 and dA.stride(1) == 1 and dA.shape[1] == self.ncol_d
-        nvar = dA.shape[0]
-        outs = []
-        for o, n in ((out1, self.nrow_d), (out2, second.nrow_d), (out3, third.nrow_d)):
-            if o is None:
-                o = _aligned_planes(torch, nvar, n, dA.device)
-            assert o.is_cuda and o.dtype == torch.float64 and o.shape == (nvar, n) and o.stride(1) == 1
-            outs.append(o)
-        s = torch.cuda.current_stream(dA.device).cuda_stream if stream is None else stream
-        ld = lambda t, n: t.stride(0) if nvar > 1 else max(t.stride(0), n)
-        check(lib().ibh_weighted_apply_chain_device(self._h, second._h, third._h, C.c_void_p(dA.data_ptr()), nvar, ld(dA, self.ncol_d),
-                                                   C.c_void_p(outs[0].data_ptr()), ld(outs[0], self.nrow_d), C.c_void_p(outs[1].data_ptr()),
-                                                   ld(outs[1], second.nrow_d), C.c_void_p(outs[2].data_ptr()), ld(outs[2], third.nrow_d),
-                                                   float(fill), C.c_void_p(s)))
-        return tuple(outs)
+        nvar, lda = _fields(torch, (dA,), self.ncol_d)
+        out1, ld1 = _result(torch, out1, nvar, self.nrow_d, dA.device)
+        out2, ld2 = _result(torch, out2, nvar, second.nrow_d, dA.device)
+        out3, ld3 = _result(torch, out3, nvar, third.nrow_d, dA.device)
+        check(lib().ibh_weighted_apply_chain_device(self._h, second._h, third._h, dA.data_ptr(), nvar, lda, out1.data_ptr(), ld1,
+                                                   out2.data_ptr(), ld2, out3.data_ptr(), ld3, float(fill), stream_arg(dA, stream)))
+        return out1, out2, out3
 
     def apply_transformed_device(self, dV, T, b, out=None, fill=float("nan"), stream=None):
         """The coupler's fused product  M * (V*T + b)  on HBM-resident fields (IceCoupler.cpp:203-252,
@@ -342,21 +300,20 @@ class linear_Weighted:
         import torch
         T = np.ascontiguousarray(T, np.float64)
         b = np.ascontiguousarray(b, np.float64)
-        assert dV.is_cuda and dV.dtype == torch.float64 and dV.dim() == 2 and dV.stride(1) == 1
-        assert dV.shape == (T.shape[0], self.ncol_d) and b.shape == (T.shape[1],)
+        nin, ldv = _fields(torch, (dV,), self.ncol_d, "V")
+        assert nin == T.shape[0] and b.shape == (T.shape[1],)
         nout = T.shape[1]
-        if out is None:
-            out = _aligned_planes(torch, nout, self.nrow_d, dV.device)
-        s = torch.cuda.current_stream(dV.device).cuda_stream if stream is None else stream
+        if out is None:         # (a caller's array is taken as it comes, as ever)
+            out = padded_planes(nout, self.nrow_d, dV.device)
         check(lib().ibh_weighted_apply_transformed_device(
-            self._h, C.c_void_p(dV.data_ptr()), dV.shape[0], max(dV.stride(0), self.ncol_d), ptr(T), ptr(b), nout,
-            C.c_void_p(out.data_ptr()), max(out.stride(0), self.nrow_d), float(fill), C.c_void_p(s)))
+            self._h, dV.data_ptr(), nin, ldv, ptr(T), ptr(b), nout, out.data_ptr(), plane_stride(out, self.nrow_d, "out"), float(fill),
+            stream_arg(dV, stream)))
         return out
 
     def apply_transformed(self, V_b, T, b, fill=np.nan):
         """Host-array form of apply_transformed_device (dense index spaces)."""
         import torch
-        dV = torch.from_numpy(np.ascontiguousarray(np.atleast_2d(V_b), np.float64)).cuda()
+        dV = to_device(np.ascontiguousarray(np.atleast_2d(V_b), np.float64))
         out = self.apply_transformed_device(dV, T, b, fill=fill)
         torch.cuda.synchronize()
         return out.cpu().numpy()
@@ -446,11 +403,27 @@ class linear_Weighted:
         return buf.value.decode()
 
 
-def _aligned_planes(torch, nvar, n, device):
-    """[nvar, n] float64 view whose rows (field planes) start on 512-byte boundaries: whole-line
-    wave stores measure 6.0 instead of 4.0 TB/s on MI355X (shortrow)."""
-    ld = (n + 63) // 64 * 64
-    return torch.empty((nvar, ld), dtype=torch.float64, device=device)[:, :n]
+def _fields(torch, ts, n, what="A", nvar=None):
+    """(nvar, ld) of the field batches ts of a device apply: torch.float64 CUDA tensors [nvar, n] with unit inner stride and one
+    leading dimension (nvar None: that of the first).  The loop is here, not at the caller: one call per apply."""
+    if nvar is None:
+        nvar = ts[0].shape[0]
+    ld = None
+    for t in ts:
+        assert t.is_cuda and t.dtype == torch.float64 and t.shape == (nvar, n) and t.stride(1) == 1
+        if ld is None:
+            s0 = t.stride(0)
+            ld = leading_dim(nvar, s0, n, what)
+        else:
+            assert t.stride(0) == s0 or leading_dim(nvar, t.stride(0), n, what) == ld
+    return nvar, ld
+
+
+def _result(torch, out, nvar, n, device):
+    """(out, ldb) of a device apply's result [nvar, n]: the caller's array, checked as the fields are, or padded planes on `device`."""
+    if out is None:
+        out = padded_planes(nvar, n, device)
+    return out, _fields(torch, (out,), n, "out", nvar)[1]
 
 
 def coo_multiply(M, xx, fill=np.nan, ignore_nan=False):

@@ -6,6 +6,7 @@ import ctypes as C
 import numpy as np
 
 from . import _capi
+from ._arrays import dptr, is_cuda, stream_arg, to_device
 from ._capi import check, lib, ptr
 from .hntr import HntrSpec
 from .linear import SparseSet, linear_Weighted
@@ -27,22 +28,16 @@ def make_hntrA(hspecO):
     return HntrSpec(hspecO.im // 2, hspecO.jm // 2, hspecO.offi * 0.5, hspecO.dlat * 2.)
 
 
-class RegridMatrices_ModelE:
+class RegridMatrices_ModelE(_capi.Handle):
     """The RegridMatrices_Dynamic that GCMRegridder_ModelE::regrid_matrices returns: matrix() / matrix_d() over
     AvI EvI AvX EvX IvA IvE XvA XvE, the aliases EAmvIp AAmvIp IpvEAm IpvAAm and the test matrices AOmvAAm / AAmvAOm."""
+    _destroy = "ibh_modele_matrices_destroy"
 
     def __init__(self, handle, keep, scale, sigma=(0., 0., 0.)):
         self._h = handle
         self._keep = keep
         self._scale = bool(scale)
         self._sigma = tuple(float(s) for s in sigma)
-
-    def __del__(self):
-        try:
-            _capi.destroy("ibh_modele_matrices_destroy", getattr(self, "_h", None))
-        except Exception:      # interpreter shutdown
-            pass
-        self._h = None
 
     def matrix(self, spec_name):
         """Own dims, the scale and the sigma the object was made with (_icebin.pyx:56-75; RegridMatrices_Dynamic.cpp:425-437)."""
@@ -141,14 +136,10 @@ def compute_AAmvEAm(EOpvAOp_result, hspecO, eq_rad, foceanAOp, foceanAOm, scale=
     return linear_Weighted(h, keep=(dims,))
 
 
-def _is_device(x):
-    return hasattr(x, "is_cuda")
-
-
 def _planes(arrays, n, what):
-    """The planes of one call as flat float64 arrays of n cells, all on the host (numpy, used in place when they can be) or
-    all in HBM (torch CUDA tensors, always in place) -> (planes, on_device)."""
-    dev = [_is_device(a) for a in arrays if a is not None]
+    """The planes of one call as flat float64 arrays of n cells, all on the host (numpy or CPU torch, used in place when they
+    can be) or all in HBM (torch CUDA tensors, always in place) -> (planes, on_device)."""
+    dev = [is_cuda(a) for a in arrays if a is not None]
     if any(dev) and not all(dev):
         raise ValueError("%s: host and device planes are mixed" % what)
     on_device = bool(dev) and dev[0]
@@ -157,8 +148,7 @@ def _planes(arrays, n, what):
         if a is None:
             out.append(None)
         elif on_device:
-            import torch
-            if not (a.is_cuda and a.dtype == torch.float64 and a.is_contiguous() and a.numel() == n):
+            if not (str(a.dtype) == "torch.float64" and a.is_contiguous() and a.numel() == n):
                 raise ValueError("%s: a device plane must be a contiguous float64 CUDA tensor of %d cells" % (what, n))
             out.append(a)
         else:
@@ -170,11 +160,11 @@ def _planes(arrays, n, what):
 
 
 def _pointer_list(planes):
-    return (C.c_void_p * len(planes))(*[p.data_ptr() if _is_device(p) else p.ctypes.data for p in planes])
+    return (C.c_void_p * len(planes))(*[p.data_ptr() if is_cuda(p) else p.ctypes.data for p in planes])
 
 
 def _host(a):
-    return a.cpu().numpy() if _is_device(a) else np.asarray(a)
+    return a.cpu().numpy() if is_cuda(a) else np.asarray(a)
 
 
 def land_fraction_errors(bad, focean, flake, fgrnd, fgice, im):
@@ -214,9 +204,8 @@ def merge_topoO_rm(topoo, lands, ices, hspecO, eq_rad=0.):
         planes += [torch.empty(nO, dtype=torch.float64, device=dev) for _ in range(2)]
         mask = torch.empty(nO, dtype=torch.int16, device=dev)
         flags = torch.empty(nO, dtype=torch.int32, device=dev)
-        st = torch.cuda.current_stream(dev).cuda_stream
         check(lib().ibh_modele_merge_topoO_device(hl, len(lands), hi, len(ices), hspecO.im, hspecO.jm, float(eq_rad), _pointer_list(planes),
-                                                 C.c_void_p(mask.data_ptr()), C.c_void_p(flags.data_ptr()), C.byref(nerr), C.c_void_p(st)))
+                                                 dptr(mask), dptr(flags), C.byref(nerr), stream_arg(mask)))
     else:
         planes += [np.empty(nO), np.empty(nO)]
         mask, flags = np.zeros(nO, np.int16), np.zeros(nO, np.uint32)
@@ -256,17 +245,15 @@ def make_topoA(topoo, mergemaskOm, hspecO, hspecA, indexingHCA, hcdefs, underice
     if on_device:
         import torch
         dev = planesO[0].device
-        if not (_is_device(mergemaskOm) and mergemaskOm.dtype == torch.int16 and mergemaskOm.is_contiguous() and mergemaskOm.numel() == nO):
+        if not (is_cuda(mergemaskOm) and mergemaskOm.dtype == torch.int16 and mergemaskOm.is_contiguous() and mergemaskOm.numel() == nO):
             raise ValueError("make_topoA: mergemaskOm must be a contiguous int16 CUDA tensor of %d cells" % nO)
         planesA = [torch.empty(nA, dtype=torch.float64, device=dev) for _ in range(9)]
         maskA = torch.empty(nA, dtype=torch.int16, device=dev)
         fhc, elevE = (torch.empty((nhc + 1) * nA, dtype=torch.float64, device=dev) for _ in range(2))
         underice = torch.empty((nhc + 1) * nA, dtype=torch.int16, device=dev)
         flags = torch.empty(nA, dtype=torch.int32, device=dev)
-        st = torch.cuda.current_stream(dev).cuda_stream
-        check(lib().ibh_modele_make_topoA_device(_pointer_list(planesO), C.c_void_p(mergemaskOm.data_ptr()), *args, _pointer_list(planesA),
-                                                *[C.c_void_p(t.data_ptr()) for t in (maskA, fhc, elevE, underice, flags)], C.byref(nerr),
-                                                C.c_void_p(st)))
+        check(lib().ibh_modele_make_topoA_device(_pointer_list(planesO), dptr(mergemaskOm), *args, _pointer_list(planesA),
+                                                *[dptr(t) for t in (maskA, fhc, elevE, underice, flags)], C.byref(nerr), stream_arg(maskA)))
     else:
         mO = np.ascontiguousarray(mergemaskOm, np.int16).reshape(-1)
         if mO.size != nO:
@@ -342,7 +329,7 @@ class TopoPacker:
         :1216-1228 does: append what else belongs in them first.  -> (gcm_ivalsA, gcm_ivalsE)."""
         from .multivec import VectorMultivec, append_planes_many
         mask = topoa["mergemask"]
-        on_device = _is_device(mask)
+        on_device = is_cuda(mask)
         ncell = mask.numel() if on_device else np.asarray(mask).size
         if not run_ice:
             mask0 = mask
@@ -350,9 +337,8 @@ class TopoPacker:
             mask0 = self.mergemaskA0
             if mask0 is None:
                 raise RuntimeError("TopoPacker.pack: run_ice without a mask of an earlier step (initialise with run_ice=False)")
-            if _is_device(mask0) != on_device:      # the planes moved between the host and the device since the last step
-                import torch
-                mask0 = torch.from_numpy(np.ascontiguousarray(mask0)).to(mask.device) if on_device else mask0.cpu().numpy()
+            if is_cuda(mask0) != on_device:      # the planes moved between the host and the device since the last step
+                mask0 = to_device(np.ascontiguousarray(mask0), mask.device) if on_device else mask0.cpu().numpy()
         source = {"fhc": "fhc", "elevE": "elevE", "underice_d": "underice"}
         outA = VectorMultivec(len(self.varsA)) if outA is None else outA
         outE = VectorMultivec(len(self.varsE)) if outE is None else outE

@@ -8,27 +8,18 @@ import ctypes as C
 import numpy as np
 
 from . import _capi
+from ._arrays import dptr, is_cuda, plane_stride, stream_arg, to_device
 from ._capi import check, lib, ptr
-
-
-def _is_cuda(a):
-    return hasattr(a, "is_cuda") and a.is_cuda
-
-
-def _stream(t):
-    import torch
-    return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
 
 
 def _to_device(a, ndim):
     """(tensor, came from the host): a float64 CUDA tensor with unit inner stride."""
-    import torch
-    if _is_cuda(a):
-        assert a.dtype == torch.float64 and a.dim() == ndim and a.stride(-1) == 1
+    if is_cuda(a):
+        assert str(a.dtype) == "torch.float64" and a.dim() == ndim and a.stride(-1) == 1
         return a, False
     h = np.ascontiguousarray(a, np.float64)
     assert h.ndim == ndim
-    return torch.from_numpy(h).cuda(), True
+    return to_device(h), True
 
 
 def _back(t, host):
@@ -39,8 +30,9 @@ def _back(t, host):
     return t.cpu().numpy()
 
 
-class VectorMultivec:
+class VectorMultivec(_capi.Handle):
     """VectorMultivec(nvar): index int64[n], weights float64[n], vals float64[n, nvar] (multivec.hpp:25-31)."""
+    _destroy = "ibh_multivec_destroy"
 
     def __init__(self, nvar, _handle=None):
         h = C.c_void_p()
@@ -49,13 +41,6 @@ class VectorMultivec:
         else:
             check(lib().ibh_multivec_create(int(nvar), C.byref(h)))
         self._h = h
-
-    def __del__(self):
-        try:
-            _capi.destroy("ibh_multivec_destroy", getattr(self, "_h", None))
-        except Exception:      # interpreter shutdown
-            pass
-        self._h = None
 
     def _size(self):
         n, nvar = C.c_int64(), C.c_int32()
@@ -119,8 +104,8 @@ class VectorMultivec:
         (IceCoupler.cpp:447-458): index = dims[0] to_sparse, weight = wM, values = B[:, row]."""
         dB, _ = _to_device(B, 2)
         assert dB.shape[1] == w.nrow_d
-        check(lib().ibh_multivec_append_weighted_device(self._h, w._h, C.c_void_p(dB.data_ptr()), dB.shape[0],
-                                                       max(dB.stride(0), w.nrow_d), _stream(dB)))
+        check(lib().ibh_multivec_append_weighted_device(self._h, w._h, dptr(dB), dB.shape[0], plane_stride(dB, w.nrow_d, "B"),
+                                                       stream_arg(dB)))
 
     def append(self, other):
         check(lib().ibh_multivec_append(self._h, other._h))
@@ -137,11 +122,10 @@ class VectorMultivec:
     def affine(self, mm, bb):
         """couple()'s unit conversion (modele/GCMCoupler_ModelE.cpp:1216-1228): vals[:, k] = vals[:, k] * mm[k] + bb[k] over every
         entry, one product then one add.  Enqueued on torch's current stream; the grouping of the merge calls stays valid."""
-        import torch
         mm, bb = np.ascontiguousarray(mm, np.float64).reshape(-1), np.ascontiguousarray(bb, np.float64).reshape(-1)
         if len(mm) != self.nvar or len(bb) != self.nvar:
             raise ValueError("affine: %d mm and %d bb for nvar=%d" % (len(mm), len(bb), self.nvar))
-        check(lib().ibh_multivec_affine_device(self._h, ptr(mm), ptr(bb), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        check(lib().ibh_multivec_affine_device(self._h, ptr(mm), ptr(bb), stream_arg()))
 
     def to_dense_scale(self, nE, out=None):
         """1 / (sum of weights per cell) over [0, nE), +inf where no entry falls (multivec.cpp:35-50).  Returns a CUDA tensor
@@ -149,8 +133,8 @@ class VectorMultivec:
         import torch
         if out is None:
             out = torch.empty(int(nE), dtype=torch.float64, device="cuda")
-        assert _is_cuda(out) and out.dtype == torch.float64 and out.shape == (int(nE),) and out.is_contiguous()
-        check(lib().ibh_multivec_to_dense_scale(self._h, int(nE), C.c_void_p(out.data_ptr()), _stream(out)))
+        assert is_cuda(out) and out.dtype == torch.float64 and out.shape == (int(nE),) and out.is_contiguous()
+        check(lib().ibh_multivec_to_dense_scale(self._h, int(nE), dptr(out), stream_arg(out)))
         return out
 
     def to_dense(self, scale, fill):
@@ -159,7 +143,7 @@ class VectorMultivec:
         ds, host = _to_device(scale, 1)
         nE = ds.shape[0]
         out = torch.empty((self.nvar, nE), dtype=torch.float64, device=ds.device)
-        check(lib().ibh_multivec_to_dense(self._h, C.c_void_p(ds.data_ptr()), float(fill), C.c_void_p(out.data_ptr()), nE, nE, _stream(ds)))
+        check(lib().ibh_multivec_to_dense(self._h, dptr(ds), float(fill), dptr(out), nE, nE, stream_arg(ds)))
         return _back(out, host)
 
     def update_dense(self, scale, out):
@@ -169,8 +153,7 @@ class VectorMultivec:
         do, host = _to_device(out, 2)
         nE = ds.shape[0]
         assert do.shape == (self.nvar, nE)
-        check(lib().ibh_multivec_update_dense(self._h, C.c_void_p(ds.data_ptr()), C.c_void_p(do.data_ptr()), max(do.stride(0), nE), nE,
-                                             _stream(do)))
+        check(lib().ibh_multivec_update_dense(self._h, dptr(ds), dptr(do), plane_stride(do, nE, "out"), nE, stream_arg(do)))
         if host:
             out[...] = _back(do, True)
         return out
@@ -182,8 +165,8 @@ class VectorMultivec:
         nd = sparse_set.dense_extent()
         if out is None:
             out = torch.empty((self.nvar, nd), dtype=torch.float64, device="cuda")
-        assert _is_cuda(out) and out.dtype == torch.float64 and out.shape == (self.nvar, nd) and out.stride(1) == 1
-        check(lib().ibh_multivec_densify_device(self._h, sparse_set._h, C.c_void_p(out.data_ptr()), max(out.stride(0), nd), _stream(out)))
+        assert is_cuda(out) and out.dtype == torch.float64 and out.shape == (self.nvar, nd) and out.stride(1) == 1
+        check(lib().ibh_multivec_densify_device(self._h, sparse_set._h, dptr(out), plane_stride(out, nd, "out"), stream_arg(out)))
         return out
 
 
@@ -192,7 +175,7 @@ def append_planes_many(packs, mask, mask0=None):
     is a list of dict(vec, planes, nclass=1, plane_class_stride=None, index_strides=None, types=None) -> the number of kept
     cells.  The masks and every plane are numpy arrays, or all are torch CUDA tensors."""
     arrays = [mask] + ([] if mask0 is None else [mask0]) + [p for k in packs for p in k["planes"]]
-    dev = [_is_cuda(a) for a in arrays]
+    dev = [is_cuda(a) for a in arrays]
     if any(dev) and not all(dev):
         raise ValueError("append_planes: host and device arrays are mixed")
     on_device = dev[0]
@@ -208,7 +191,7 @@ def append_planes_many(packs, mask, mask0=None):
         return np.ascontiguousarray(a, np.int16 if int16_only or a.dtype == np.int16 else np.float64).reshape(-1)
 
     def address(a):
-        return a.data_ptr() if on_device else a.ctypes.data
+        return None if a is None else a.data_ptr() if on_device else a.ctypes.data
 
     def size(a):
         return a.numel() if on_device else a.size
@@ -240,12 +223,11 @@ def append_planes_many(packs, mask, mask0=None):
         s.nvar, s.nclass, s.plane_class_stride = len(planes), nclass, stride
         s.index_stride_cell, s.index_stride_class = int(strides[0]), int(strides[1])
     nkept = C.c_int64()
+    args = (C.cast(structs, C.c_void_p), len(packs), ncell, address(m), address(m0), C.byref(nkept))
     if on_device:
-        check(lib().ibh_multivec_append_planes_many_device(C.cast(structs, C.c_void_p), len(packs), ncell, C.c_void_p(address(m)),
-                                                          None if m0 is None else C.c_void_p(address(m0)), C.byref(nkept), _stream(m)))
+        check(lib().ibh_multivec_append_planes_many_device(*args, stream_arg(m)))
     else:
-        check(lib().ibh_multivec_append_planes_many_host(C.cast(structs, C.c_void_p), len(packs), ncell, C.c_void_p(address(m)),
-                                                        None if m0 is None else C.c_void_p(address(m0)), C.byref(nkept)))
+        check(lib().ibh_multivec_append_planes_many_host(*args))
     return nkept.value
 
 

@@ -5,25 +5,20 @@ import ctypes as C
 import numpy as np
 
 from . import _capi
+from ._arrays import dptr, is_cuda, stream_arg
 from ._capi import check, lib, ptr
 from .linear import SparseSet, linear_Weighted
 
 _INTERP = {"Z_INTERP": 0, "ELEV_CLASS_INTERP": 1}     # IceRegridder.hpp:36-39
 
 
-class RegridMatrices:
+class RegridMatrices(_capi.Handle):
     """cdef class RegridMatrices (_icebin.pyx:50-75) over RegridMatrices_Dynamic."""
+    _destroy = "ibh_regrid_matrices_destroy"
 
     def __init__(self, handle, keep):
         self._h = handle
         self._keep = keep
-
-    def __del__(self):
-        try:
-            _capi.destroy("ibh_regrid_matrices_destroy", getattr(self, "_h", None))
-        except Exception:      # interpreter shutdown
-            pass
-        self._h = None
 
     def matrix(self, spec_name):
         """Compute a regrid matrix: 'EvI', 'AvI', 'IvA', 'IvE', 'EvA', 'AvE' (also 'AvX', 'XvA',
@@ -237,17 +232,15 @@ class GCMRegridder:
         sheet = self._sheets[sheet_name]       # KeyError like ice_regridders().index.at()
         sig = np.asarray(sigma, np.float64)
         h = C.c_void_p()
-        if hasattr(elevmaskI, "is_cuda") and elevmaskI.is_cuda:
+        if is_cuda(elevmaskI):
             # elevation mask already in HBM (torch.float64 CUDA tensor): no trip over PCIe
-            import torch
             em = elevmaskI.reshape(-1).contiguous()
-            assert em.dtype == torch.float64
-            st = torch.cuda.current_stream(em.device).cuda_stream
-            check(lib().ibh_regrid_matrices_create_device(sheet.h, C.c_void_p(em.data_ptr()), em.numel(), int(scale),
-                                                         int(correctA), ptr(sig), C.c_void_p(st), C.byref(h)))
-            return RegridMatrices(h, keep=(self,))
-        em = np.ascontiguousarray(np.asarray(elevmaskI, np.float64).reshape(-1))
-        check(lib().ibh_regrid_matrices_create(sheet.h, ptr(em), len(em), int(scale), int(correctA), ptr(sig), C.byref(h)))
+            assert str(em.dtype) == "torch.float64"
+            check(lib().ibh_regrid_matrices_create_device(sheet.h, dptr(em), em.numel(), int(scale), int(correctA), ptr(sig),
+                                                         stream_arg(em), C.byref(h)))
+        else:
+            em = np.ascontiguousarray(np.asarray(elevmaskI, np.float64).reshape(-1))
+            check(lib().ibh_regrid_matrices_create(sheet.h, ptr(em), len(em), int(scale), int(correctA), ptr(sig), C.byref(h)))
         return RegridMatrices(h, keep=(self,))
 
 

@@ -7,6 +7,7 @@ from collections import OrderedDict
 import numpy as np
 
 from . import _capi
+from ._arrays import dptr, einval, named_planes, stream_arg, to_device
 from ._capi import check, lib
 
 MAX_TILE = 8192                 # IBH_MAKE_TOPOO_MAX_TILE: fine cells of a tile sorted in LDS; larger tiles take the long path
@@ -38,45 +39,11 @@ PLANES = tuple(ATTRS)
 COUNTS = ("FGICE_low", "FGICE_high", "FLAKE_reduced", "FGRND_range", "dZOCEN_nonpositive", "FLAKE_one")
 
 
-def _einval(msg):
-    return _capi.IcebinHipError(_capi.IBH_EINVAL, msg)
-
-
-def _inputs(hspecI, hspecS, FGICE1m, ZICETOP1m, ZSOLG1m, FOCEAN1m, FLAKES):
-    """The five inputs as flat contiguous arrays, all numpy or all torch CUDA tensors: (arrays, on_device).  Needs no device."""
-    named = (("FGICE1m", FGICE1m, "int16", hspecI.size), ("ZICETOP1m", ZICETOP1m, "int16", hspecI.size),
-             ("ZSOLG1m", ZSOLG1m, "int16", hspecI.size), ("FOCEAN1m", FOCEAN1m, "int16", hspecI.size), ("FLAKES", FLAKES, "float64", hspecS.size))
-    for name, p, _, _ in named:
-        if p is None:
-            raise _einval("%s: null plane" % name)
-    dev = [hasattr(p, "is_cuda") and bool(p.is_cuda) for _, p, _, _ in named]
-    if any(dev) != all(dev):
-        raise _einval("FGICE1m / ZICETOP1m / ZSOLG1m / FOCEAN1m / FLAKES: some planes are on the host and some on the device (%s)"
-                      % ", ".join("%s: %s" % (n[0], "device" if d else "host") for n, d in zip(named, dev)))
-    out = []
-    for name, p, dtype, size in named:
-        if dev[0]:
-            if str(p.dtype) != "torch." + dtype:
-                raise _einval("%s: dtype %s, the plane is %s" % (name, p.dtype, dtype))
-            p = p.reshape(-1).contiguous()
-            n = p.numel()
-        else:
-            p = np.asarray(p)
-            if p.dtype != np.dtype(dtype):
-                raise _einval("%s: dtype %s, the plane is %s" % (name, p.dtype, dtype))
-            p = np.ascontiguousarray(p.reshape(-1))
-            n = p.size
-        if n != size:
-            raise _einval("%s: the plane holds %d cells, its grid has %d" % (name, n, size))
-        out.append(p)
-    return out, dev[0]
-
-
 def _ij(cells, what):
     """A list of 1-based (i, j) as int32 [n, 2]."""
     a = np.asarray(list(cells), np.int64).reshape(-1, 2) if len(cells) else np.zeros((0, 2), np.int64)
     if a.size and (np.abs(a) >= 2 ** 31).any():
-        raise _einval("%s: an entry overflows int32" % what)
+        raise einval("%s: an entry overflows int32" % what)
     return np.ascontiguousarray(a, np.int32)
 
 
@@ -91,21 +58,14 @@ def fatal_message(kind, hspecI, hspecO, J, I):
     return "Continental cell (%d,%d) has no continental area on 2-minute grid. (%d-%d, %d-%d)" % (I, J, I11, I1M, J11, J1M)
 
 
-class TopoO:
+class TopoO(_capi.Handle):
     """What make_topoO returns: the 20 planes under the reference's names (PLANES), torch.float64 CUDA tensors [jmO, imO], and
     .counts, the reference's stderr warnings as counts (COUNTS)."""
+    _destroy = "ibh_make_topoo_destroy"
 
     def __init__(self, hspecI, hspecO, hspecS):
         self.hspecI, self.hspecO, self.hspecS = hspecI, hspecO, hspecS
-        self._h = None
         self.counts = None
-
-    def __del__(self):
-        try:
-            _capi.destroy("ibh_make_topoo_destroy", getattr(self, "_h", None))
-        except Exception:      # interpreter shutdown
-            pass
-        self._h = None
 
     def topoo(self):
         """The planes as the dict merge_topoO / make_topoA / update_topo take (they stay in HBM)."""
@@ -137,7 +97,10 @@ def make_topoO(hspecI, hspecO, FGICE1m, ZICETOP1m, ZSOLG1m, FOCEAN1m, hspecS, FL
     their own width) or all torch CUDA tensors (read in place, on torch's current stream); inputs are never written.  Returns a
     TopoO.  Raises ValueError with the reference's message for the first ocean cell without ocean area or continental cell
     without land; the semantics, line by line, are in include/icebin_hip.h."""
-    planes, on_device = _inputs(hspecI, hspecS, FGICE1m, ZICETOP1m, ZSOLG1m, FOCEAN1m, FLAKES)
+    planes, on_device = named_planes(
+        (("FGICE1m", FGICE1m, "int16", hspecI.size), ("ZICETOP1m", ZICETOP1m, "int16", hspecI.size), ("ZSOLG1m", ZSOLG1m, "int16", hspecI.size),
+         ("FOCEAN1m", FOCEAN1m, "int16", hspecI.size), ("FLAKES", FLAKES, "float64", hspecS.size)),
+        "FGICE1m / ZICETOP1m / ZSOLG1m / FOCEAN1m / FLAKES: some planes are on the host and some on the device", null="first")
     land, ocean = _ij(set_to_land, "set_to_land"), _ij(set_to_ocean, "set_to_ocean")
     rij = _ij([ij for _, ijs in resets for ij in ijs], "resets")
     relev = np.ascontiguousarray([float(elev) for elev, ijs in resets for _ in ijs], np.float64)
@@ -149,13 +112,12 @@ def make_topoO(hspecI, hspecO, FGICE1m, ZICETOP1m, ZSOLG1m, FOCEAN1m, hspecS, FL
     res._h = h
     import torch
     if not on_device:
-        planes = [torch.from_numpy(p if p.flags.writeable else p.copy()).cuda() for p in planes]     # (torch takes no read-only array)
-    dev = planes[0].device
-    out = torch.empty((len(PLANES), hspecO.jm, hspecO.im), dtype=torch.float64, device=dev)
-    s = torch.cuda.current_stream(dev).cuda_stream
-    check(lib().ibh_make_topoo_device(h, *[C.c_void_p(p.data_ptr()) for p in planes], C.c_void_p(out.data_ptr()), hspecO.size, C.c_void_p(s)))
+        planes = [to_device(p) for p in planes]
+    out = torch.empty((len(PLANES), hspecO.jm, hspecO.im), dtype=torch.float64, device=planes[0].device)
+    s = stream_arg(out)
+    check(lib().ibh_make_topoo_device(h, *[dptr(p) for p in planes], dptr(out), hspecO.size, s))
     st = np.zeros(10, np.int64)
-    check(lib().ibh_make_topoo_status(h, C.c_void_p(s), _capi.ptr(st)))
+    check(lib().ibh_make_topoo_status(h, s, _capi.ptr(st)))
     res._keep = planes
     first = [(int(st[k]), kind) for k, kind in ((1, "ocean"), (3, "continental")) if st[k] >= 0]
     if first:

@@ -7,7 +7,8 @@ long-double references of tests/apply_sidepath_cases.py (pinned against the CPU 
   C  weight_dot_kernel / weight_dot_final_kernel through apply_weight: 1 .. 256 chunks, the cap, both weight vectors;
   D  the conservation correction: the row side chunked, batches across the 32-batch split, padded planes, the exact variant, a
      conservative matrix, the host entry, a captured apply;
-  E  rowperm_kernel: 8192 rows (built), 8193 and 1 (declined), ties by index.
+  E  rowperm_kernel: 8192 rows (built), 8193 and 1 (declined), ties by index;
+  F  the leading dimension of a field batch: a broadcast batch is refused before any launch, a slice of a wider buffer is taken.
 
 Every gated case prints its largest err / bound (pytest -s); the bounds are derived in apply_sidepath_cases' docstring.  No row or
 element is left out of a comparison: dead rows hold fill exactly, NaN sits exactly where the reference has it."""
@@ -373,3 +374,35 @@ def test_longest_rows_first_is_the_same_apply(nrow):
         assert not np.any(base[q] == CANARY) and not np.any(lpt[q] == CANARY)
         assert asc.same_bits(lpt[q], base[q]), "batch %d: longest rows first changed the result" % q
         report("rowblock %d rows batch %d" % (nrow, q), asc.check_product(m, base[q], Xs[q], FILL, "rowblock %d rows" % nrow))
+
+
+# ---- F: the leading dimension of a field batch ------------------------------------------------------------------------------------
+def test_broadcast_fields_are_refused_and_a_slice_of_a_wider_buffer_is_taken():
+    """Three fields on the 50 km IvA through apply_many_device, apply_transformed_device and apply_sharded (world 1): a broadcast
+    batch (x.expand(3, -1), row stride 0) raises ValueError before anything is launched -- the result array keeps its canaries --, and
+    a [3, n] slice of a [3, n + 5] buffer gives bitwise the result of the contiguous batch."""
+    import torch
+    from icebin_amd import synthetic as syn
+    from icebin_amd.distributed import Communicator, apply_sharded
+    g = syn.make_grids("g50")
+    w = icebin_amd.from_synthetic(g).regrid_matrices("greenland", syn.dome_elevmask(g)).matrix("IvA")
+    n, nrow = w.ncol_d, w.nrow_d
+    x = torch.from_numpy(syn.fields(3, n)).cuda()
+    wide = torch.full((3, n + 5), float("nan"), dtype=torch.float64, device="cuda")
+    wide[:, :n] = x
+    T, b, comm = np.eye(3), np.zeros(3), Communicator()
+    calls = {"apply_many_device": lambda a, out: w.apply_many_device([a], [out], fill=FILL)[0],
+             "apply_transformed_device": lambda a, out: w.apply_transformed_device(a, T, b, out=out, fill=FILL),
+             "apply_sharded": lambda a, out: apply_sharded(w, comm, a, out_all=out, fill=FILL)}
+    for name, call in calls.items():
+        outs = [torch.full((3, nrow), CANARY, dtype=torch.float64, device="cuda") for _ in range(3)]
+        with pytest.raises(ValueError, match="planes overlap: stride 0 < %d cells" % n):
+            call(x[:1].expand(3, -1), outs[0])
+        torch.cuda.synchronize()
+        assert bool((outs[0] == CANARY).all()), name + ": the refused call wrote its result array"
+        assert call(x, outs[1]) is outs[1] and call(wide[:, :n], outs[2]) is outs[2]
+        comm.wait()
+        torch.cuda.synchronize()
+        assert not bool((outs[1] == CANARY).any()), name
+        assert torch.equal(outs[1].view(torch.int64), outs[2].view(torch.int64)), name + ": the slice of a wider buffer differs"
+    comm.close()
