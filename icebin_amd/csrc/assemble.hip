@@ -100,6 +100,7 @@ struct XCell {
     double vE0, vE1;
     double rsE;         // sum(GvEp row x): one entry -> v, two -> fl(v0 + v1)
     bool range_error;
+    bool underflow;     // a weight != 0 and an area != 0 whose product is 0: fewer entries than the class pattern says
 };
 
 __device__ __forceinline__ int dev_lower_bound(const double *__restrict__ xp, int n, double xx) {
@@ -139,6 +140,7 @@ __device__ __forceinline__ XCell make_cell(const RgView &rg, long iA, long iI, d
     c.vE0 = c.vE1 = 0.0;
     c.rsE = 0.0;
     c.range_error = false;
+    c.underflow = false;
     if (WITH_EP && c.unmasked) {
         const double elevation = e < 0.0 ? 0.0 : e;          // std::max(elev, 0.0), :123
         if (rg.interp == 0) {                                // Z_INTERP, :127-145
@@ -152,6 +154,7 @@ __device__ __forceinline__ XCell make_cell(const RgView &rg, long iA, long iI, d
             double v0 = 0.0, v1 = 0.0;
             if (w0 != 0) { v0 = c.a * w0; h0 = v0 != 0; }
             if (w1 != 0) { v1 = c.a * w1; h1 = v1 != 0; }
+            c.underflow = c.a != 0 && ((w0 != 0 && !h0) || (w1 != 0 && !h1));
             const long k0 = c.iA * rg.sA + (long)i0 * rg.sHC, k1 = c.iA * rg.sA + (long)i1 * rg.sHC;
             if (h0) {
                 c.iE0 = k0; c.vE0 = v0; c.nep = 1;

@@ -271,7 +271,7 @@ struct ibh_regrid_matrices {
     int scale = 1, correctA = 0;
     double sigma[3] = {0, 0, 0};
     // one byte per ice cell, a function of its elevation and the regridder's elevation classes alone (ibh::elevmask_classes,
-    // streamasm.inl): 0xFF masked, 0xFE elevation beyond the last class (linterp_1d_b's error), else first class | classes << 6.
+    // streamasm.inl): 0xFF masked, 0xFE elevation beyond the last class (linterp_1d_b's error), 0xFD a class weight below 1e-30, else first class | classes << 6.
     // Made once per elevmask -- at creation for grids the streamed build serves, else by the first build that wants it -- and read by
     // every matrix of this object in place of the 8-byte elevation wherever only the mask or the class pattern matters.
     mutable ibh::DevBuf<uint8_t> em_cls;

@@ -35,7 +35,8 @@
 constexpr int FA_ILMAX = 8;         // exchange cells per ice cell
 constexpr int FA_DUPMAX = 4;        // consecutive cells with the same (iA, iI)
 constexpr int FA_OLDMAX = 512;      // straddling entries of one range ranked in LDS
-enum { FA_ERR_OLDOVER = 1, FA_ERR_MISSING = 2 };
+// (UNDERFLOW: area * class weight underflowed to zero where neither factor is zero -- the static entry counts do not hold)
+enum { FA_ERR_OLDOVER = 1, FA_ERR_MISSING = 2, FA_ERR_UNDERFLOW = 4 };
 
 struct PlanView {
     const int32_t *arng, *aidx, *ilptr, *ilist, *ifirst;
@@ -530,6 +531,9 @@ __global__ __launch_bounds__(T, T == 128 ? 8 : 1) void k_fa_count(RgView rg, Pla
                 }
                 if (WITH_EP && c.range_error) atomicMin(err_x, (uint32_t)x);
                 else {
+                    // the static counts take (classes of the elevation) x (cells with an area): an entry lost to underflow is not
+                    // among them -- general pipeline (a build that counts by visiting has no such assumption)
+                    if (WITH_EP && pl.icnt_pos && c.underflow) atomicOr(flags, (uint32_t)FA_ERR_UNDERFLOW);
                     // EvA / AvE number the A side by "the range has entries": a cell of GvAp without an elevation-class entry
                     // (an area so small that area * weight underflows) would be numbered without one -- general pipeline
                     if (WITH_EP && eva_check && c.inAp && c.nep == 0) atomicOr(flags, (uint32_t)FA_ERR_MISSING);
@@ -1766,7 +1770,10 @@ static bool fast_build_gp(const ibh_regrid_matrices *rm, const MatSpec *sp, cons
             std::memcpy(h, fa_chain_state().h_cnt, sizeof(h));
         } else readback_sync(h, d_cnt, sizeof(h), st);
         if (h[0] != 0xffffffffu) fail_elevation_range(rm, h[0]);
-        if (h[1]) return false;                                 // a limit of the fast path was hit: general pipeline
+        // a limit of the fast path was hit, or area * weight underflowed while the static counts were in use (FA_ERR_UNDERFLOW; an
+        // optimistic build has run its emit kernels by now: the static counts only over-count and the outputs are allocated by upper
+        // bounds, so nothing was written out of place): general pipeline
+        if (h[1]) return false;
         IBH_CHECK(h[4] < (1u << 31) && h[2] < (1u << 31), "matrix too large for int32 indices");
         return true;
     };

@@ -85,10 +85,11 @@ __device__ __forceinline__ unsigned long long sa_wave_or64(unsigned long long v)
 
 // ---- S1: one byte (two) per cell -------------------------------------------------------------------------------------------------
 // The class pattern of an elevation: the classes it lies between and which of the two weights are non-zero
-// (IceRegridder_L0.cpp:127-150).  With no area below 1e-290 in the plan, area * weight != 0 <=> area != 0 and weight != 0.
-struct SaCls { int c0, ncls; bool err; };
+// (IceRegridder_L0.cpp:127-150).  With no area below 1e-290 in the plan and no weight below 1e-30 in the mask (tinyw: the byte
+// 0xFD, and the streamed build hands the matrix on), area * weight != 0 <=> area != 0 and weight != 0: the product is >= 1e-320.
+struct SaCls { int c0, ncls; bool err, tinyw; };
 __device__ __forceinline__ SaCls sa_classes(const RgView &rg, double e) {
-    SaCls k{0, 0, false};
+    SaCls k{0, 0, false, false};
     const double elevation = e < 0.0 ? 0.0 : e;
     if (rg.interp == 0) {
         int i1 = dev_lower_bound(rg.hc, rg.nhc, elevation);
@@ -98,6 +99,7 @@ __device__ __forceinline__ SaCls sa_classes(const RgView &rg, double e) {
         const double ratio = (elevation - rg.hc[i0]) / (rg.hc[i1] - rg.hc[i0]);
         const double w0 = 1.0 - ratio, w1 = ratio;
         const bool h0 = w0 != 0, h1 = w1 != 0;
+        k.tinyw = (h0 && fabs(w0) < 1e-30) || (h1 && fabs(w1) < 1e-30);
         k.ncls = (h0 ? 1 : 0) + (h1 ? 1 : 0);
         k.c0 = h0 ? i0 : i1;
     } else {
@@ -131,7 +133,7 @@ __global__ __launch_bounds__(256) void k_em_classes(RgView rg, long nI, uint8_t 
     else if (rg.nhc < 1) b = 0;
     else {
         const SaCls k = sa_classes(rg, e);
-        b = k.err ? (uint8_t)0xFE : (uint8_t)(k.c0 | (k.ncls << 6));
+        b = k.err ? (uint8_t)0xFE : k.tinyw ? (uint8_t)0xFD : (uint8_t)(k.c0 | (k.ncls << 6));
     }
     out[i] = b;
 }
@@ -183,6 +185,7 @@ __global__ __launch_bounds__(SA_T) void k_sa_flags(RgView rg, PlanView pl, SaBuf
         int n = 0, c0 = 0, ncls_e = 0;
         if (WITH_EP && unm) {
             if (ev[u] == 0xFEu) atomicMin(err_x, (uint32_t)x);
+            else if (ev[u] == 0xFDu) atomicOr(err_x + 1, (uint32_t)FA_ERR_UNDERFLOW);      // (the fallback flags sit behind err_x; no entries here)
             else { ncls_e = (int)(ev[u] >> 6); c0 = (int)(ev[u] & 63u); n = (head && gnz) ? ncls_e : 0; }
         }
         const bool ent = head && unm && (WITH_EP ? n > 0 : gpos);
@@ -474,7 +477,8 @@ __global__ __launch_bounds__(SA_T) void k_sa_emit(RgView rg, PlanView pl, MatSpe
         hintv[u] = -1;
         if (WITH_EP && ent) {
             // the class search was done by k_sa_flags: byte = first class | classes << 6.  Z_INTERP: two classes -> (c0, c0 + 1); one
-            // class -> the elevation sits exactly on class c0, which lower_bound reports as the UPPER index (the lower one only at 0)
+            // class -> the elevation sits exactly on class c0, which lower_bound reports as the UPPER index (the lower one only at 0;
+            // make_cell raises an index of 0 to 1 itself, as linterp_1d_b does: the `c0 == 0` arm below only spells that out)
             const unsigned cb8 = sb.cls[x];
             const int c0 = (int)(cb8 & 63), n = (int)(cb8 >> 6);
             hintv[u] = rg.interp == 0 ? (n == 2 ? c0 + 1 : (c0 == 0 ? 1 : c0)) : c0;
@@ -1500,7 +1504,7 @@ static bool stream_build(const ibh_regrid_matrices *rm, const MatSpec *sp, const
         P0[k + 1] = P0[k] + hk[2]; G0[k + 1] = G0[k] + hk[3]; E0[k + 1] = E0[k] + hk[4]; L0[k + 1] = L0[k] + hk[5];
     }
     if (err_x != 0xffffffffu) fail_elevation_range(rm, err_x);
-    if (fl) return false;                                        // a limit of the fast path was hit (on some rank): general pipeline
+    if (fl) return false;                                        // a limit of the fast path was hit, or the mask holds a weight below 1e-30 (on some rank): general pipeline
     IBH_CHECK(E0[world] < (1u << 31) && P0[world] < (1u << 31), "matrix too large for int32 indices");
     const uint32_t *hme = hh + 8 * rank;
     const uint32_t nnz = (uint32_t)E0[world];

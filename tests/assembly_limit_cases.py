@@ -29,25 +29,25 @@ TINY = 1e-290                          # k_plan_ifirst: a nonzero |area| below t
 
 # name -> (where, what is measured, value inside the limit, value beyond it; "in" / "over": any value on that side)
 THRESHOLDS = {
-    "sorted": ("fastasm.inl:65 k_plan_flags", "adjacent (iA, iI) pairs out of order", 0, 1),
-    "nhc": ("fastasm.inl:169 ensure_plan (the streamed build: asm_plan.h plan_stream)", "elevation classes (nhc <= FA_NC = 64)", 64, 65),
-    "ilmax": ("fastasm.inl:98 k_plan_ifirst", "exchange cells of one ice cell (<= FA_ILMAX = 8)", 8, 9),
-    "dupmax": ("fastasm.inl:81 k_plan_ranges", "longest run of one (iA, iI) pair (<= FA_DUPMAX = 4)", 4, 5),
-    "tiny": ("fastasm.inl:108 k_plan_ifirst", "smallest nonzero |area| (>= 1e-290 keeps the static counts)", TINY, np.nextafter(TINY, 0.0)),
+    "sorted": ("fastasm.inl:66 k_plan_flags", "adjacent (iA, iI) pairs out of order", 0, 1),
+    "nhc": ("fastasm.inl:170 ensure_plan (the streamed build: asm_plan.h plan_stream)", "elevation classes (nhc <= FA_NC = 64)", 64, 65),
+    "ilmax": ("fastasm.inl:99 k_plan_ifirst", "exchange cells of one ice cell (<= FA_ILMAX = 8)", 8, 9),
+    "dupmax": ("fastasm.inl:82 k_plan_ranges", "longest run of one (iA, iI) pair (<= FA_DUPMAX = 4)", 4, 5),
+    "tiny": ("fastasm.inl:109 k_plan_ifirst", "smallest nonzero |area| (>= 1e-290 keeps the static counts)", TINY, np.nextafter(TINY, 0.0)),
     "rel32_ep": ("asm_plan.h stream_rel32", "2 * longest range (elevation-class builds; <= 65535: 16-bit positions)", 65534, 65536),
     "rel32": ("asm_plan.h stream_rel32", "longest range (builds without classes; <= 65535: 16-bit positions)", 65535, 65536),
     "emit_blocks": ("asm_plan.h stream_emit_grid (EMIT_BLOCKS)", "exchange cells of a 32-bit-position grid (<= 8192 workgroups x 1024 cells)", "in", "over"),
-    "oldseg_s": ("streamasm.inl:354 k_sa_ranges / :258 k_sa_rangecounts", "straddlers of one (range, class) segment, small table (<= 128)", 128, 129),
-    "oldseg_l": ("streamasm.inl:354 k_sa_ranges / :258 k_sa_rangecounts", "straddlers of one (range, class) segment, large table (<= 512)", 512, 513),
+    "oldseg_s": ("streamasm.inl:357 k_sa_ranges / :261 k_sa_rangecounts", "straddlers of one (range, class) segment, small table (<= 128)", 128, 129),
+    "oldseg_l": ("streamasm.inl:357 k_sa_ranges / :261 k_sa_rangecounts", "straddlers of one (range, class) segment, large table (<= 512)", 512, 513),
     "default_oldseg": ("asm_plan.h stream_oldseg", "mean range length (<= 2048: the small straddler table)", "in", "over"),
     "default_wpr4": ("asm_plan.h stream_wpr", "mean range length (<= 1024: one wave per range)", "in", "over"),
     "default_wpr16": ("asm_plan.h stream_wpr", "mean range length (<= 4096: four waves per range)", "in", "over"),
     "default_rowsl": ("asm_plan.h stream_rowsl", "ranges (< 16384: no lane-parallel row kernel)", "in", "over"),
-    "fa_oldmax": ("fastasm.inl:644 k_fa_count / :1163 k_fa_range", "straddling entries of one range (<= FA_OLDMAX = 512)", 512, 513),
-    "lcap_s0": ("fastasm.inl:980 k_fa_range<128, 2>", "entries of one range (<= LCAP = 1024: values in LDS)", 1024, 1025),
-    "lcap_s1": ("fastasm.inl:980 k_fa_range<256, 4>", "entries of one range (<= LCAP = 2048)", 2048, 2049),
-    "lcap_s2": ("fastasm.inl:980 k_fa_range<1024, 4>", "entries of one range (<= LCAP = 4096)", 4096, 4097),
-    "lcap_s3": ("fastasm.inl:980 k_fa_range<1024, 1>", "entries of one range (<= LCAP = 4096)", 4096, 4097),
+    "fa_oldmax": ("fastasm.inl:648 k_fa_count / :1167 k_fa_range", "straddling entries of one range (<= FA_OLDMAX = 512)", 512, 513),
+    "lcap_s0": ("fastasm.inl:984 k_fa_range<128, 2>", "entries of one range (<= LCAP = 1024: values in LDS)", 1024, 1025),
+    "lcap_s1": ("fastasm.inl:984 k_fa_range<256, 4>", "entries of one range (<= LCAP = 2048)", 2048, 2049),
+    "lcap_s2": ("fastasm.inl:984 k_fa_range<1024, 4>", "entries of one range (<= LCAP = 4096)", 4096, 4097),
+    "lcap_s3": ("fastasm.inl:984 k_fa_range<1024, 1>", "entries of one range (<= LCAP = 4096)", 4096, 4097),
     "pass_s0": ("asm_plan.h FA_SHAPE_T x FA_SHAPE_CPT, shape 0 (128 x 2)", "range length against one pass of 256 cells", 256, 257),
     "pass_s1": ("asm_plan.h FA_SHAPE_T x FA_SHAPE_CPT, shape 1 (256 x 4)", "range length against one pass of 1024 cells", 1024, 1025),
     "pass_s2": ("asm_plan.h FA_SHAPE_T x FA_SHAPE_CPT, shape 2 (1024 x 4)", "range length against one pass of 4096 cells", 4096, 4097),
@@ -57,6 +57,11 @@ THRESHOLDS = {
     "chained": ("asm_plan.h range_chained", "ranges (x 1 class) of a one-class build (< 2^15: scans chained in k_fa_count)", 32767, 32768),
     "rscan_many": ("asm_plan.h range_scan_form", "ranges of an unchained build (<= 4096: k_fa_rscan in one workgroup)", 4096, 4097),
     "psums": ("asm_plan.h range_sums_form", "ice cells with several exchange cells (<= 2^20: k_fa_psums8)", "in", "over"),
+    # what the entry counts above are made of (a cell between two classes has two entries)
+    "entries_max": ("streamasm.inl k_sa_ranges (rel)", "most entries of one range (<= 65535: they fit 16-bit positions)", 65534, 65536),
+    "rel16_used": ("streamasm.inl k_sa_ranges (rel)", "largest position a range of that many entries must hold in a 16-bit build (<= 32767: bit 15 never set)", "in", 65533),
+    "two_class": ("assemble.hip make_cell (nep == 2)", "share of exchange cells with two entries (0: one class each)", 0.0, "over"),
+    "weight_underflow": ("fastasm.inl:536 k_fa_count / streamasm.inl:102 sa_classes", "cells with area != 0, weight != 0, area * weight == 0 (0: the static counts hold)", 0, 1),
 }
 # the predicate "inside the limit" of each row, on the measured value
 INSIDE = {
@@ -69,6 +74,7 @@ INSIDE = {
     "pass_s0": lambda v: v <= 256, "pass_s1": lambda v: v <= 1024, "pass_s2": lambda v: v <= 4096, "pass_s3": lambda v: v <= 1024,
     "stream_default": lambda v: v < (1 << 20), "optimistic": lambda v: v <= (1 << 20), "chained": lambda v: v < 32768,
     "rscan_many": lambda v: v <= 4096, "psums": lambda v: v <= (1 << 20),
+    "entries_max": lambda v: v <= 65535, "rel16_used": lambda v: v <= 32767, "two_class": lambda v: v == 0, "weight_underflow": lambda v: v == 0,
 }
 # rows whose measured property is the SET of range lengths (a grid can hold both sides at once)
 PER_RANGE = {"lcap_s0", "lcap_s1", "lcap_s2", "lcap_s3", "pass_s0", "pass_s1", "pass_s2", "pass_s3"}
@@ -80,7 +86,12 @@ def build_grid(d):
       straddle   [(r0, r1, n, cls)]: n ice cells first seen in range r0 with one more exchange cell in range r1, in class cls;
       multi      [(r0, k, n)]: n ice cells with one exchange cell in each of ranges r0 .. r0 + k - 1;
       dups       [(r, run, n)]: n ice cells with `run` exchange cells in a row in range r, all the same (iA, iI);
-      nhc        elevation classes (every ice cell sits exactly on one class: one entry per exchange cell in E);
+      nhc        elevation classes (without `elev` every ice cell sits exactly on one class: one entry per exchange cell in E);
+      elev       where ice cells lie against the classes (a group spec is a class c: exactly on it, or (c0, c1, f): at
+                 hcdefs[c0] + f * (hcdefs[c1] - hcdefs[c0]), two entries when 0 < f < 1):
+                 {"plain": (c, f): every plain cell between classes c and c + 1 (c "cycle": ice cell % (nhc - 1)),
+                  "straddle" / "multi" / "dups": one group spec (or None: as without `elev`) per entry of that list,
+                  "cells": {ice cell: elevation}, the key "min_area" naming the ice cell of the area["min"] exchange cell};
       area       {"zero_every": k, "neg_every": k, "min": value}: areas 1e6 * (0.5 .. 1.5), every k-th zero / negative, and
                  one exchange cell (the middle of the last range) with the given smallest |area|;
       inversion  "first" / "last": the first / last two exchange cells swapped (the grid is sorted by (iA, iI) otherwise);
@@ -91,6 +102,7 @@ def build_grid(d):
     nR, nhc = len(lengths), int(d.get("nhc", 4))
     room = lengths.copy()
     iA_parts, iI_parts, cls = [], [], []
+    group = []                             # (list, index in it) of every special ice cell
     nI = 0
 
     def put(r, ice, n=1):
@@ -99,17 +111,17 @@ def build_grid(d):
         iA_parts.append(np.full(n, r, np.int64))
         iI_parts.append(np.full(n, ice, np.int64))
 
-    for r0, r1, n, c in d.get("straddle", ()):
+    for gi, (r0, r1, n, c) in enumerate(d.get("straddle", ())):
         for _ in range(n):
-            put(r0, nI); put(r1, nI); cls.append(c); nI += 1
-    for r0, k, n in d.get("multi", ()):
+            put(r0, nI); put(r1, nI); cls.append(c); group.append(("straddle", gi)); nI += 1
+    for gi, (r0, k, n) in enumerate(d.get("multi", ())):
         for _ in range(n):
             for r in range(r0, r0 + k):
                 put(r, nI)
-            cls.append(nI % nhc); nI += 1
-    for r, run, n in d.get("dups", ()):
+            cls.append(nI % nhc); group.append(("multi", gi)); nI += 1
+    for gi, (r, run, n) in enumerate(d.get("dups", ())):
         for _ in range(n):
-            put(r, nI, run); cls.append(nI % nhc); nI += 1
+            put(r, nI, run); cls.append(nI % nhc); group.append(("dups", gi)); nI += 1
     # every other cell: an ice cell of its own (bulk-generated: the large grids have millions)
     pair = int(d.get("pairs", 0))          # > 0: the plain cells come as duplicate pairs (two cells per ice cell)
     for r in range(nR):
@@ -134,14 +146,31 @@ def build_grid(d):
         area[3::a["zero_every"]] = 0.0
     if a.get("neg_every"):
         area[5::a["neg_every"]] *= -1.0
+    x_min = int(lengths[:-1].sum() + lengths[-1] // 2)
+    ice_min = int(iI[x_min])
     if "min" in a:
-        area[int(lengths[:-1].sum() + lengths[-1] // 2)] = a["min"]
+        area[x_min] = a["min"]
     if d.get("inversion") == "first":
         iA[[0, 1]], iI[[0, 1]] = iA[[1, 0]], iI[[1, 0]]
     elif d.get("inversion") == "last":
         iA[[-2, -1]], iI[[-2, -1]] = iA[[-1, -2]], iI[[-1, -2]]
     hcdefs = 100.0 * np.arange(nhc)
     em = hcdefs[cls].copy()
+    e = d.get("elev")
+    if e:
+        def between(c0, c1, f):
+            return hcdefs[c0] + f * (hcdefs[c1] - hcdefs[c0])
+        if "plain" in e:
+            c, f = e["plain"]
+            ice = np.arange(len(group), nI)
+            c0 = ice % (nhc - 1) if c == "cycle" else np.full(len(ice), c)
+            em[ice] = between(c0, c0 + 1, f)
+        for ice, (kind, gi) in enumerate(group):
+            spec = (e.get(kind) or [None] * (gi + 1))[gi]
+            if spec is not None:
+                em[ice] = between(*spec) if isinstance(spec, tuple) else hcdefs[spec]
+        for ice, v in e.get("cells", {}).items():
+            em[ice_min if ice == "min_area" else ice] = v
     if d.get("masked"):
         em[::d["masked"]] = np.nan
     proj = 1e9 * (1.0 + rng.random(nR))
@@ -266,6 +295,95 @@ CASES = [
     dict(name="emit_blocks_and_psums", grid=dict(ranges=[65536] * 129, nhc=3, pairs=1), knobs=[{}, NOSTREAM],
          builds=[(n, ONE, "own") for n, _, _ in I_BUILDS],
          path=[2, 1], reference="general", covers={"emit_blocks": 129 * 65536, "psums": 129 * 32768, "rel32": 65536}),
+]
+
+# ---- the same limits in ENTRIES: ice cells between two classes have two entries in the E-keyed matrices (make_cell, nep == 2) ------
+TWO = dict(plain=("cycle", 0.25))          # every plain cell a quarter of the way from its class to the next: weights 0.75 / 0.25
+_SHAPES = [dict(NOSTREAM, assemble_range_shape=s) for s in range(4)] + [dict(NOSTREAM, assemble_range_shape=1, assemble_static_count=0)]
+_WPRS = [STREAM, dict(STREAM, assemble_stream_wpr=1), dict(STREAM, assemble_stream_wpr=4)]
+_LONG = [(0, 1, 30, 1), (1, 3, 40, 2), (1, 2, 12, 0)]
+_LONG2 = dict(TWO, straddle=[(1, 2, 0.5), (2, 3, 0.25), (0, 1, 0.75)])
+E_BUILDS = I_BUILDS + [("EvX", ONE, "own"), ("XvE", ONE, "own")]
+EI_BUILDS = [("EvI", ALLB, "own"), ("IvE", ALLB, "own")]
+E_OF_ALL = [b for b in ALL_BUILDS if "E" in b[0]]         # the matrices of ALL_BUILDS with elevation classes
+# SMALL with one exchange cell of area 1e-280 (above the cut: the plan keeps its static counts), its ice cell at `e`.  The oracle's
+# EvI / EvX hold 806 / 823 entries with e = 1e-60 as with e = 0, and 807 / 824 with e = 1e-40.
+_under = lambda e: dict(SMALL, area=dict(min=1e-280), elev=dict(cells={"min_area": e}))
+# SMALL at the ends of the class table: every plain cell between two classes (62 / 63 among them), the groups on 63, on 0, between
+# 62 and 63 and between 0 and 1 -- the class bytes 62 | 2 << 6 and 63 | 1 << 6 next to the sentinels 0xFD .. 0xFF
+_ENDS = dict(plain=("cycle", 0.5), straddle=[(62, 63, 0.5), 63, 0, (0, 1, 0.5)], dups=[(62, 63, 0.25), 0], multi=[63])
+CASES += [
+    # the long range two-class throughout: 65 534 entries in 16-bit positions (the last one 65 533), 65 536 in 32-bit ones
+    dict(name="rel32_ep_in_two", grid=dict(ranges=[300, 32767, 700, 2000], straddle=_LONG, elev=_LONG2), knobs=_WPRS, builds=ALL_BUILDS,
+         path=2, covers={"rel32_ep": 65534, "entries_max": 65534, "rel16_used": 65533, "two_class": 1.0, "weight_underflow": 0}),
+    dict(name="rel32_ep_out_two", grid=dict(ranges=[300, 32768, 700, 2000], straddle=_LONG, elev=_LONG2), knobs=_WPRS, builds=ALL_BUILDS,
+         path=2, covers={"rel32_ep": 65536, "entries_max": 65536, "rel16_used": 0, "emit_blocks": 35768}),
+    # 65 535 cells: the builds without classes keep 16-bit positions, the class builds of the same grid hold 131 070 entries
+    dict(name="rel32_in_two", grid=dict(ranges=[300, 65535, 700, 2000], straddle=_LONG[:2], elev=_LONG2), knobs=[STREAM], builds=ALL_BUILDS,
+         path=2, covers={"rel32": 65535, "rel32_ep": "over", "entries_max": 131070}),
+    # LCAP counts entries, the passes count cells: ranges of 512 / 1024 / 2048 two-class cells sit ON every LCAP, one cell more is
+    # beyond it while a pass of shape 2 (4096 cells) or 3 (1024) still holds the range; 511 two-class + 2 on-class cells make 1024
+    # entries, 512 + 1 make the odd 1025 (the on-class cells: `dups` runs of one cell)
+    dict(name="lcap_entries", grid=dict(ranges=[512, 1024, 2048, 513, 300], nhc=5, dups=[(3, 1, 2)], straddle=[(0, 4, 20, 1), (1, 4, 30, 2)],
+                                        elev=dict(TWO, dups=[2], straddle=[(1, 2, 0.5), (2, 3, 0.5)])),
+         knobs=_SHAPES, builds=ALL_BUILDS, path=1,
+         covers={"lcap_s0": 1024, "lcap_s1": 2048, "lcap_s2": 4096, "lcap_s3": 4096, "pass_s0": 512, "pass_s1": 513, "pass_s2": 2048,
+                 "pass_s3": 513}),
+    dict(name="lcap_entries_over", grid=dict(ranges=[513, 1025, 2049, 514, 300], nhc=5, dups=[(3, 1, 1)], straddle=[(0, 4, 20, 1), (1, 4, 30, 2)],
+                                             elev=dict(TWO, dups=[2], straddle=[(1, 2, 0.5), (2, 3, 0.5)])),
+         knobs=_SHAPES, builds=ALL_BUILDS, path=1,
+         covers={"lcap_s0": 1026, "lcap_s1": 2050, "lcap_s2": 4098, "lcap_s3": 4098, "pass_s0": 513, "pass_s1": 1025, "pass_s2": 2049,
+                 "pass_s3": 1025}),
+    dict(name="lcap_entries_odd", grid=dict(ranges=[513, 300], nhc=5, dups=[(0, 1, 1)], elev=dict(TWO, dups=[2])), knobs=_SHAPES,
+         builds=E_BUILDS, path=1, covers={"lcap_s0": 1025, "pass_s0": 513, "pass_s1": 513}),
+    # 256 two-class straddlers are 512 straddling entries; one on-class straddler more is 513 (EvI and IvE only: AvI and IvA have 257 straddlers
+    # there, and on exchange-cell keys nothing straddles: those stay with the per-range build)
+    dict(name="fa_oldmax_512_two", grid=dict(ranges=[600, 700], straddle=[(0, 1, 256, 1)], elev=dict(straddle=[(1, 2, 0.5)])), knobs=[NOSTREAM],
+         builds=I_BUILDS, path=1, covers={"fa_oldmax": 512}),
+    dict(name="fa_oldmax_513_two", grid=dict(ranges=[600, 700], straddle=[(0, 1, 256, 1), (0, 1, 1, 2)], elev=dict(straddle=[(1, 2, 0.5), None])),
+         knobs=[NOSTREAM], builds=EI_BUILDS, path=0, discard=True, covers={"fa_oldmax": 513}),
+    # n two-class straddlers between classes 1 and 2 fill the segments of both; one on-class straddler of class 2 more and only the
+    # UPPER class's segment is over
+    dict(name="oldseg_s_128_two", grid=dict(ranges=[400, 500, 300], straddle=[(0, 1, 128, 1), (1, 2, 20, 2)], elev=dict(straddle=[(1, 2, 0.5), None])),
+         knobs=[STREAM], builds=I_BUILDS, path=2, covers={"oldseg_s": 128, "default_oldseg": 400, "rel16_used": "in", "entries_max": "in"}),
+    dict(name="oldseg_s_129_two", grid=dict(ranges=[400, 500, 300], straddle=[(0, 1, 128, 1), (1, 2, 20, 2), (0, 1, 1, 2)],
+                                            elev=dict(straddle=[(1, 2, 0.5), None, None])),
+         knobs=[STREAM], builds=I_BUILDS, path=1, discard=True, covers={"oldseg_s": 129}),
+    dict(name="oldseg_l_512_two", grid=dict(ranges=[2600, 2600], straddle=[(0, 1, 512, 1)], elev=dict(straddle=[(1, 2, 0.5)])), knobs=[STREAM],
+         builds=I_BUILDS, path=2, covers={"oldseg_l": 512, "default_oldseg": 2600, "default_wpr4": 2600}),
+    dict(name="oldseg_l_513_two", grid=dict(ranges=[2600, 2600], straddle=[(0, 1, 512, 1), (0, 1, 1, 2)], elev=dict(straddle=[(1, 2, 0.5), None])),
+         knobs=[STREAM], builds=I_BUILDS, path=0, discard=True, covers={"oldseg_l": 513}),
+    dict(name="oldseg_l_forced_512_two", grid=dict(ranges=[600, 700], straddle=[(0, 1, 512, 1)], elev=dict(straddle=[(1, 2, 0.5)])),
+         knobs=[dict(STREAM, assemble_stream_oldseg=512)], builds=I_BUILDS, path=2, covers={"oldseg_l": 512, "default_oldseg": "in"}),
+    dict(name="oldseg_l_forced_513_two", grid=dict(ranges=[600, 700], straddle=[(0, 1, 512, 1), (0, 1, 1, 2)], elev=dict(straddle=[(1, 2, 0.5), None])),
+         knobs=[dict(STREAM, assemble_stream_oldseg=512)], builds=I_BUILDS, path=0, discard=True, covers={"oldseg_l": 513}),
+    # the ice cells in several ranges and the duplicate runs two-class: a merged run sums both entries
+    dict(name="ilmax8_two", grid=dict(ranges=[30] * 10, multi=[(1, 8, 3)], straddle=[(0, 9, 2, 1)], elev=dict(multi=[(1, 2, 0.25)], straddle=[(0, 1, 0.5)])),
+         knobs=[{}, STREAM], builds=E_BUILDS, path=[1, 2], covers={"ilmax": 8, "two_class": "over"}),
+    dict(name="ilmax9_two", grid=dict(ranges=[30] * 10, multi=[(1, 9, 3)], straddle=[(0, 9, 2, 1)], elev=dict(multi=[(1, 2, 0.25)], straddle=[(0, 1, 0.5)])),
+         knobs=[{}, STREAM], builds=E_BUILDS, path=0, covers={"ilmax": 9, "two_class": "over"}),
+    dict(name="dup4_two", grid=dict(ranges=[50, 60, 70], dups=[(1, 4, 3), (2, 2, 4)], straddle=[(0, 2, 5, 2)], elev=dict(dups=[(0, 1, 0.25), (2, 3, 0.5)])),
+         knobs=[{}, STREAM], builds=E_BUILDS, path=[1, 2], covers={"dupmax": 4, "two_class": "over"}),
+    dict(name="dup5_two", grid=dict(ranges=[50, 60, 70], dups=[(1, 5, 1), (2, 2, 4)], straddle=[(0, 2, 5, 2)], elev=dict(dups=[(0, 1, 0.25), (2, 3, 0.5)])),
+         knobs=[{}, STREAM], builds=E_BUILDS, path=0, covers={"dupmax": 5, "two_class": "over"}),
+    dict(name="nhc64_ends", grid=dict(SMALL, nhc=64, elev=_ENDS), knobs=[{}, STREAM], builds=ALL_BUILDS, path=[1, 2],
+         covers={"nhc": 64, "two_class": "over"}),
+    dict(name="nhc65_ends", grid=dict(SMALL, nhc=65, elev=_ENDS), knobs=[{}, STREAM], builds=I_BUILDS, path=0, covers={"nhc": 65}),
+    # area * weight underflows: the oracle drops the entry, the class pattern of the elevation still says two.  The static counts of
+    # both fast builds are (classes of the elevation) x (cells with an area), so neither may build this grid: the streamed build
+    # refuses a mask with a weight below 1e-30 (times the plan's smallest area, 1e-290, that is the smallest product it could
+    # not tell from zero), the per-range build raises a fallback flag where it meets the underflow -- path 0, whatever the knobs.
+    # (The matrices with classes: the others multiply no weights and keep their fast builds.)
+    dict(name="weight_underflow", grid=_under(1e-60), knobs=[{}, STREAM, NOSTREAM], builds=E_OF_ALL, path=0, discard=True,
+         covers={"weight_underflow": 1, "tiny": 1e-280}),
+    dict(name="weight_underflow_plain", grid=_under(1e-60), knobs=[{}, STREAM, NOSTREAM], builds=[b for b in ALL_BUILDS if "E" not in b[0]],
+         path=[1, 2, 1], covers={"weight_underflow": 1}),
+    # ... the product a subnormal (1e-280 * 1e-42): the entry stays.  The streamed build hands the mask on (weight below 1e-30),
+    # the per-range build meets no underflow and builds it.
+    dict(name="weight_subnormal", grid=_under(1e-40), knobs=[{}, STREAM, NOSTREAM], builds=E_OF_ALL, path=1, discard=True,
+         covers={"weight_underflow": 0, "tiny": 1e-280}),
+    dict(name="weight_on_class", grid=_under(0.0), knobs=[{}, STREAM, NOSTREAM], builds=ALL_BUILDS, path=[1, 2, 1],
+         covers={"weight_underflow": 0, "two_class": 0.0, "tiny": 1e-280}),
 ]
 
 # the shared (several-rank) streamed build of a 32-bit-position grid: tests/test_distributed_gloo.py's worker, config "limits:<case>"
